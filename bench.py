@@ -9,8 +9,16 @@ counter blocks (row blocks) or of the palette split's result rows, and the
 acceptance step.  value = W*H*P*steps / max-over-ranks wall time (strong
 scaling: the 4096^2 image is row-block sharded over the N GPUs).
 
-Run: python bench.py [--gpus N] [--steps K] [--warmup W].  N > 1 runs one
-process per GPU: under torch.distributed.run (RANK/LOCAL_RANK/WORLD_SIZE/MASTER_*
+Run: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full].
+A plain run sets up, settles the clocks, warms up, times the K steps and prints
+the line with the headline figure.  --full adds every other measurement, as
+extra keys of the same line: BASELINE config 3's real search (device-resident
+and host-driven), a second pass of the steps under HIP events (kernel_avg_ms,
+roofline), the CPU baseline and the reference's own kernels on this GPU.
+--dump-outputs DIR writes what the search holds after the last timed step (what
+hq_search_best returns, and a fixed sample of the last step's index images) as
+DIR/<name>.npy, the same files for the same arguments.
+N > 1 runs one process per GPU: under torch.distributed.run (RANK/LOCAL_RANK/WORLD_SIZE/MASTER_*
 set; WORLD_SIZE must equal N), or, when WORLD_SIZE is unset, bench.py starts
 the N rank processes itself (launch_ranks: the parent imports neither torch nor
 libhq, so nothing touches the GPU before the ranks exist) and relays rank 0's
@@ -400,6 +408,54 @@ def full_search(lib, _lib, m, K, P, seed, sa_device, restore):
     return {"wall_s": round(wall, 3), "iterations": it.value, "best_error": err.value}, best
 
 
+SETTLE_STEPS = 300          # at C3 (4096^2, P = 4: ~0.2 s); scaled by the pixel-evaluations of a step
+DUMP_SAMPLE = 1 << 20       # pixels of each index image that --dump-outputs keeps
+DUMP_SEED = 20240229        # ... drawn with this seed (the same pixels in every run)
+DUMP_BYTES = 48 << 20       # ... and fewer of them when the palettes' rows together would pass this
+
+
+def settle_clocks(lib, _lib, m, K, P, seed, pixels):
+    """The GPU's clocks take ~0.1 s of sustained load to settle (a timed region of
+    a few steps straight after set-up measured ~7% slow): run a search of its
+    own, a fixed number of iterations for the shape, and drop it.  The timed
+    search is created afterwards and does not depend on it."""
+    import hybridquantization_amd as hq
+
+    n = max(10, min(2000, SETTLE_STEPS * (4096 * 4096 * 4) // max(1, pixels * P)))
+    sw = hq.SWASA(population=P, imax=10 ** 9, seed=seed)
+    params = sw.params()
+    s = C.c_void_p()
+    _lib.check(lib.hq_search_create(m.ctx, C.byref(params), K, sw.seed, C.byref(s)), m.ctx)
+    ran = C.c_int()
+    _lib.check(lib.hq_search_run(s, n, C.byref(ran)), m.ctx)
+    lib.hq_search_destroy(s)
+
+
+def dump_outputs(path, lib, _lib, m, best, berr, it, K, P, n_own, lo, n_pal):
+    """--dump-outputs: what a caller of the timed path receives after its last
+    step.  best_palette [K, 4] f32, best_error [1] f64 and best_iteration [1]
+    f64 are hq_search_best's results; last_indices [n_pal, S] f32 is the colour
+    the last step's assignment chose for a fixed, seeded sample of S pixels
+    under each of the candidate palettes this rank evaluated (hq_get_indices32;
+    the whole image when it has no more than S pixels; rank 0's rows and
+    palettes at N > 1)."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "best_palette.npy"), best.reshape(K, 4).astype(np.float32))
+    np.save(os.path.join(path, "best_error.npy"), np.array([berr], np.float64))
+    np.save(os.path.join(path, "best_iteration.npy"), np.array([it], np.float64))
+    keep = min(DUMP_SAMPLE, DUMP_BYTES // (4 * max(1, n_pal)))
+    if n_own > keep:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n_own, keep, replace=False))
+    else:
+        pick = np.arange(n_own)
+    idx = np.zeros(n_own, np.uint32)
+    rows = np.zeros((n_pal, pick.size), np.float32)
+    for p in range(n_pal):
+        _lib.check(lib.hq_get_indices32(m.ctx, lo + p, idx.ctypes.data_as(C.POINTER(C.c_uint32))), m.ctx)
+        rows[p] = idx[pick]
+    np.save(os.path.join(path, "last_indices.npy"), rows)
+
+
 def main():
     if len(sys.argv) == 3 and sys.argv[1] == "--ref-kernels-child":
         _ref_kernels_child(sys.argv[2])
@@ -429,10 +485,16 @@ def main():
                     help="N > 1: row-block shards + one all-reduce, or each rank the whole image and P/N "
                          "palettes + one all-gather (SURVEY 8e); auto: palettes when P >= 8 N and N "
                          "divides P (C5: 1.23x faster per rank, DESIGN.md 5), else rows")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline figure: BASELINE config 3's "
+                         "imax = 5000 search, the per-kernel pass under HIP events (kernel_avg_ms, "
+                         "roofline), the CPU baseline and the reference's kernels on this GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the search's outputs after the last timed step as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=8.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-full-search", action="store_true",
-                    help="skip the imax = 5000 search of BASELINE config 3 (extra keys)")
+                    help="with --full: skip the imax = 5000 search of BASELINE config 3 (extra keys)")
     ap.add_argument("--dry-run", action="store_true",
                     help="test the rank wiring only: gloo process group, no libhq, no GPU")
     args = ap.parse_args()
@@ -518,8 +580,13 @@ def main():
     # timed region of a few steps straight after set-up measured ~7% slow (20
     # vs 100 steps: 0.72 vs 0.67 ms).  At N > 1 every rank runs it, device-
     # resident with the communicator (the same path as the timed steps).
+    # A plain run settles the clocks with SETTLE_STEPS iterations (~0.2 s at C3)
+    # of a search of its own instead, so that its headline figure is measured
+    # as the one after the full search is.
     search_line = None
-    if not args.no_full_search:
+    if not args.full:
+        settle_clocks(lib, _lib, m, args.K, P, args.seed, W * H)  # (the same count on every rank)
+    elif not args.no_full_search:
         dev, bdev = full_search(lib, _lib, m, args.K, P, args.seed, 1, sa_device)
         where = (f"rows [{r0}, {r1}) of an {args.shard_of}-way split, "
                  f"{'a one-rank communicator' if args.shard_comm else 'no collective'}" if args.shard_of > 0
@@ -551,8 +618,8 @@ def main():
             torch.cuda.synchronize()
             dist.barrier()
 
-    # Timed region: the search loop alone.  Kernel times come from a second pass of
-    # the same number of steps with HIP events on the context stream: an event
+    # Timed region: the search loop alone.  Kernel times come (--full) from a second
+    # pass of the same number of steps with HIP events on the context stream: an event
     # between two kernels leaves the GPU idle ~5-10 us (measured in the rocprofv3
     # timeline), ~4% of a step, so they stay out of the timed region.
     sync_all()
@@ -560,45 +627,37 @@ def main():
     _lib.check(lib.hq_search_run(search, args.steps, C.byref(ran)), m.ctx)
     sync_all()
     elapsed = time.perf_counter() - t0
-    lib.hq_profile_reset(m.ctx)
-    lib.hq_profile_enable(m.ctx, 1)
-    _lib.check(lib.hq_search_run(search, args.steps, C.byref(ran)), m.ctx)
-    lib.hq_profile_enable(m.ctx, 0)
-    if world > 1:
-        elapsed = hqd.max_over_ranks(dist, elapsed)
-
-    prof = {}
-    for k in profiled_stages(world, rccl_ranks > 0):
-        ms = C.c_double()
-        n = C.c_int64()
-        lib.hq_profile_get(m.ctx, k.encode(), C.byref(ms), C.byref(n))
-        prof[k] = (ms.value / max(n.value, 1), n.value)
-    kernel_avg, kernel_max = kernel_profile(prof, world, dist and (lambda v: hqd.max_each_over_ranks(dist, v)))
+    if ran.value != args.steps:
+        raise RuntimeError(f"bench.py: the timed region ran {ran.value} steps, not {args.steps}")
+    n_own = W * (r1 - r0)
     best = np.zeros(4 * args.K, np.float32)
     berr = C.c_double()
     it = C.c_int()
+    if args.dump_outputs and rank == 0:  # the state the timed steps left, before any further pass
+        _lib.check(lib.hq_search_best(search, _lib.fptr(best), C.byref(berr), C.byref(it)), m.ctx)
+        lo, n_pal = hqd.palette_slice(P, world, rank) if psplit else (0, P)
+        dump_outputs(args.dump_outputs, lib, _lib, m, best, berr.value, it.value, args.K, P, n_own, lo, n_pal)
+    if world > 1:
+        elapsed = hqd.max_over_ranks(dist, elapsed)
+
+    if args.full:
+        lib.hq_profile_reset(m.ctx)
+        lib.hq_profile_enable(m.ctx, 1)
+        _lib.check(lib.hq_search_run(search, args.steps, C.byref(ran)), m.ctx)
+        lib.hq_profile_enable(m.ctx, 0)
+        prof = {}
+        for k in profiled_stages(world, rccl_ranks > 0):
+            ms = C.c_double()
+            n = C.c_int64()
+            lib.hq_profile_get(m.ctx, k.encode(), C.byref(ms), C.byref(n))
+            prof[k] = (ms.value / max(n.value, 1), n.value)
+        kernel_avg, kernel_max = kernel_profile(prof, world, dist and (lambda v: hqd.max_each_over_ranks(dist, v)))
     lib.hq_search_best(search, _lib.fptr(best), C.byref(berr), C.byref(it))
     lib.hq_search_destroy(search)
 
-    n_own = W * (r1 - r0)
     value = W * H * P * args.steps / elapsed / 1e6
     if args.shard_of > 0:  # experiment: one rank's rows only (per-rank rate, not a job total)
         value = n_own * P * args.steps / elapsed / 1e6
-    # Dominant kernel: the cost kernel (S-CIELAB stencil + Opp->Lab + dE76).  With P > 1
-    # palettes per launch its HBM bytes (LabRef once + P index images) amortise
-    # and FP32 VALU bounds it; its flops: cost_accounting.
-    half = m.halfSize
-    kernel, hb, chunked, flops_nominal, flops_exec = cost_accounting(half, args.K, args.grid, opts)
-    cost_ms = prof["cost"][0]
-    P_dev = hqd.palette_slice(P, world, rank)[1] if psplit else P  # palettes one device's cost kernel evaluates
-    alg_flops = n_own * P_dev * flops_nominal
-    exec_flops = n_own * P_dev * flops_exec
-    achieved_tf = alg_flops / (cost_ms * 1e-3) / 1e12 if cost_ms > 0 else 0.0
-    exec_tf = exec_flops / (cost_ms * 1e-3) / 1e12 if cost_ms > 0 else 0.0
-    alg_bytes = n_own * (12 + P_dev * (1 if args.K <= 256 else 2 if chunked else 4))
-    hbm_gbs = alg_bytes / (cost_ms * 1e-3) / 1e9 if cost_ms > 0 else 0.0
-    traffic, traffic_src = measured_traffic(W, args.K, P, args.grid, world, kernel.split("+")[0],
-                                            args.dpi, args.distance, with_source=True)
     # whole-evaluation view: the metric's 24 B/px-eval HBM-read roofline
     eval_roof_mpx = HBM_PEAK_GBS * 1e9 / 24.0 / 1e6 * world
     out = {
@@ -625,38 +684,56 @@ def main():
                    **({"shard_of": args.shard_of, "rows": [r0, r1], "shard_comm": bool(args.shard_comm)}
                       if args.shard_of > 0 else {}),
                    **({"options": args.opt} if args.opt else {})},
-        "roofline": {"bound": "valu", "achieved": round(achieved_tf, 2), "peak": FP32_PEAK_TFLOPS,
-                     "unit": "TFLOP/s", "frac": round(achieved_tf / FP32_PEAK_TFLOPS, 4),
-                     "traffic": traffic, "traffic_source": traffic_src and f"profiles/{traffic_src}",
-                     "kernel": kernel, "kernel_avg_ms": round(cost_ms, 4),
-                     "flops_per_px_eval": flops_nominal, "exec_flops_per_px_eval": flops_exec,
-                     "half": half, "tap_bucket": hb or None,
-                     "alg_flops_per_launch": alg_flops, "exec_flops_per_launch": exec_flops,
-                     "frac_executed_taps": round(exec_tf / FP32_PEAK_TFLOPS, 4),
-                     "alg_bytes_per_launch": alg_bytes, "hbm_GBs_alg": round(hbm_gbs, 1),
-                     "hbm_frac": round(hbm_gbs / HBM_PEAK_GBS, 4),
-                     "note": "fp32-accurate stencil: vertical taps on the matrix cores as split-f16 "
-                             "products (hi*hi+hi*lo+lo*hi, fp32 accumulate), horizontal taps, Lab and dE on "
-                             "FP32 VALU.  bound valu: the compute roof is the FP32 vector peak, 157.3 TFLOP/s "
-                             "(the f32 MFMA peak is the same number on gfx950); achieved = the nominal "
-                             "7*2*(2 half+1)*2 + 40 flop/px-eval of the reference's stencil + Lab/dE (628 at "
-                             "half 10) over the kernel time (all P palettes' launches); frac_executed_taps = "
-                             "the flops the kernel executes (bucket taps, trimmed narrow filters); hbm_frac = the kernel's algorithmic bytes (LabRef 12 B + P index bytes "
-                             "per pixel) over its time against 8 TB/s; traffic = HBM bytes/launch from the "
-                             "committed rocprofv3 FETCH_SIZE(x2)+WRITE_SIZE passes when their config matches; "
-                             "kernel_avg_ms: HIP events carried by the launches on the context stream over a "
-                             "second pass of the same steps, right after the timed one (events idle the GPU "
-                             "~5-10 us each, so the timed pass has none)"},
         "split": "palettes" if psplit else "rows" if world > 1 else "none",
         "rccl_ranks": rccl_ranks,
         "metric_hbm_roofline_frac": round(value / eval_roof_mpx, 4),
-        "kernel_avg_ms": kernel_avg,
-        **({"kernel_avg_ms_max_over_ranks": kernel_max} if kernel_max is not None else {}),
         "best_error": berr.value,
     }
+    if args.full:  # per-kernel figures of the second pass and the roofline they give
+        # Dominant kernel: the cost kernel (S-CIELAB stencil + Opp->Lab + dE76).  With P > 1
+        # palettes per launch its HBM bytes (LabRef once + P index images) amortise
+        # and FP32 VALU bounds it; its flops: cost_accounting.
+        half = m.halfSize
+        kernel, hb, chunked, flops_nominal, flops_exec = cost_accounting(half, args.K, args.grid, opts)
+        cost_ms = prof["cost"][0]
+        P_dev = hqd.palette_slice(P, world, rank)[1] if psplit else P  # palettes one device's cost kernel evaluates
+        alg_flops = n_own * P_dev * flops_nominal
+        exec_flops = n_own * P_dev * flops_exec
+        achieved_tf = alg_flops / (cost_ms * 1e-3) / 1e12 if cost_ms > 0 else 0.0
+        exec_tf = exec_flops / (cost_ms * 1e-3) / 1e12 if cost_ms > 0 else 0.0
+        alg_bytes = n_own * (12 + P_dev * (1 if args.K <= 256 else 2 if chunked else 4))
+        hbm_gbs = alg_bytes / (cost_ms * 1e-3) / 1e9 if cost_ms > 0 else 0.0
+        traffic, traffic_src = measured_traffic(W, args.K, P, args.grid, world, kernel.split("+")[0],
+                                                args.dpi, args.distance, with_source=True)
+        out.update({
+            "roofline": {"bound": "valu", "achieved": round(achieved_tf, 2), "peak": FP32_PEAK_TFLOPS,
+                         "unit": "TFLOP/s", "frac": round(achieved_tf / FP32_PEAK_TFLOPS, 4),
+                         "traffic": traffic, "traffic_source": traffic_src and f"profiles/{traffic_src}",
+                         "kernel": kernel, "kernel_avg_ms": round(cost_ms, 4),
+                         "flops_per_px_eval": flops_nominal, "exec_flops_per_px_eval": flops_exec,
+                         "half": half, "tap_bucket": hb or None,
+                         "alg_flops_per_launch": alg_flops, "exec_flops_per_launch": exec_flops,
+                         "frac_executed_taps": round(exec_tf / FP32_PEAK_TFLOPS, 4),
+                         "alg_bytes_per_launch": alg_bytes, "hbm_GBs_alg": round(hbm_gbs, 1),
+                         "hbm_frac": round(hbm_gbs / HBM_PEAK_GBS, 4),
+                         "note": "fp32-accurate stencil: vertical taps on the matrix cores as split-f16 "
+                                 "products (hi*hi+hi*lo+lo*hi, fp32 accumulate), horizontal taps, Lab and dE on "
+                                 "FP32 VALU.  bound valu: the compute roof is the FP32 vector peak, 157.3 TFLOP/s "
+                                 "(the f32 MFMA peak is the same number on gfx950); achieved = the nominal "
+                                 "7*2*(2 half+1)*2 + 40 flop/px-eval of the reference's stencil + Lab/dE (628 at "
+                                 "half 10) over the kernel time (all P palettes' launches); frac_executed_taps = "
+                                 "the flops the kernel executes (bucket taps, trimmed narrow filters); hbm_frac = the kernel's algorithmic bytes (LabRef 12 B + P index bytes "
+                                 "per pixel) over its time against 8 TB/s; traffic = HBM bytes/launch from the "
+                                 "committed rocprofv3 FETCH_SIZE(x2)+WRITE_SIZE passes when their config matches; "
+                                 "kernel_avg_ms: HIP events carried by the launches on the context stream over a "
+                                 "second pass of the same steps, right after the timed one (events idle the GPU "
+                                 "~5-10 us each, so the timed pass has none)"},
+            "kernel_avg_ms": kernel_avg,
+            **({"kernel_avg_ms_max_over_ranks": kernel_max} if kernel_max is not None else {}),
+        })
     if search_line is not None and rank == 0:
         out["full_search_c3"] = search_line
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args)
         ref = out["cpu_baseline"].get("reference_kernels_on_this_gpu") or {}
         if ref.get("value"):  # this line's value over the reference's own kernels on this GPU

@@ -13,9 +13,9 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -v -rA --durations=0 --tim
 rc=$?; echo "pytest rc=$rc"; tail -2 $E/pytest_gpu.log; fatal $rc pytest
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $E/smoke.log 2>&1
 rc=$?; echo "smoke rc=$rc"; tail -2 $E/smoke.log; fatal $rc smoke
-timeout -k 10 600 python bench.py > $E/bench.json 2> $E/bench.err
+timeout -k 10 600 python bench.py --full > $E/bench.json 2> $E/bench.err
 rc=$?; echo "bench rc=$rc"; cut -c1-300 $E/bench.json; fatal $rc bench
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $E/trace -o bench -- python3 bench.py --no-cpu-baseline > $E/bench_under_rocprof.json 2> $E/bench_under_rocprof.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $E/trace -o bench -- python3 bench.py --full --no-cpu-baseline > $E/bench_under_rocprof.json 2> $E/bench_under_rocprof.err
 rc=$?; echo "trace rc=$rc"; fatal $rc trace
 : > $E/configs.jsonl
 # each line starts on settled clocks: the full C3-schedule search of its shape first
@@ -28,12 +28,12 @@ for cfg in "--size 1024 --K 64 --population 1" "--population 1" "" "--size 8192 
            "--size 1024 --K 1024 --steps 50 --warmup 5 --no-full-search" \
            "--size 1024 --K 4096 --steps 20 --warmup 3 --no-full-search" \
            "--size 1024 --K 8192 --steps 10 --warmup 2 --no-full-search"; do
-  timeout -k 10 300 python bench.py --no-cpu-baseline $cfg >> $E/configs.jsonl 2>> $E/configs.err
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline $cfg >> $E/configs.jsonl 2>> $E/configs.err
   rc=$?; echo "config [$cfg] rc=$rc"; fatal $rc "config $cfg"
 done
-timeout -k 10 200 python bench.py --no-cpu-baseline --shard-of 8 --steps 200 > $E/shard8.json 2> $E/shard8.err
+timeout -k 10 200 python bench.py --full --no-cpu-baseline --shard-of 8 --steps 200 > $E/shard8.json 2> $E/shard8.err
 rc=$?; echo "shard8 rc=$rc"; cut -c1-200 $E/shard8.json; fatal $rc shard8
-timeout -k 10 200 python bench.py --no-cpu-baseline --shard-of 8 --shard-comm --steps 200 > $E/shard8_comm.json 2> $E/shard8_comm.err
+timeout -k 10 200 python bench.py --full --no-cpu-baseline --shard-of 8 --shard-comm --steps 200 > $E/shard8_comm.json 2> $E/shard8_comm.err
 rc=$?; echo "shard8 comm rc=$rc"; cut -c1-200 $E/shard8_comm.json; fatal $rc shard8_comm
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -s KILL 120 rocprofv3 --pmc $c --kernel-include-regex "cost|assign|build_grid|sa_step|finalize" -f csv -d $E/traffic_$c -o run -- python3 scripts/profile_eval.py --evals 3 > $E/traffic_$c.log 2>&1

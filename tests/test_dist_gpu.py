@@ -131,7 +131,7 @@ def test_bench_gpus_1_prints_one_line(gpu):
     import json
 
     r = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--size", "256", "--K", "16",
-                "--population", "2", "--no-cpu-baseline", "--no-full-search"])
+                "--population", "2", "--full", "--no-cpu-baseline", "--no-full-search"])
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout  # stdout carries the line and nothing else
@@ -162,10 +162,43 @@ def test_bench_shard_with_comm_keeps_stdout_to_one_line(gpu):
     import json
 
     r = _bench(["--steps", "3", "--warmup", "1", "--size", "512", "--K", "16", "--population", "2",
-                "--shard-of", "2", "--shard-comm", "--no-cpu-baseline", "--no-full-search"])
+                "--shard-of", "2", "--shard-comm", "--full", "--no-cpu-baseline", "--no-full-search"])
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout
     d = json.loads(lines[0])
     assert d["rccl_ranks"] == 1 and d["config"]["shard_comm"] is True
     assert d["kernel_avg_ms"]["comm"] > 0 and d["kernel_avg_ms"]["finalize"] == 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_same_outputs_twice(gpu, tmp_path):
+    """A plain run (no --full) prints the headline line without the keys of the
+    extra measurements, and --dump-outputs writes what the search holds after
+    the last timed step: float arrays, identical from run to run, the best
+    error the line's own.  333 x 333 pixels: more than one cost tile, ragged."""
+    import json
+
+    import numpy as np
+
+    dumps = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        r = _bench(["--gpus", "1", "--steps", "4", "--warmup", "2", "--size", "333", "--K", "16",
+                    "--population", "3", "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout
+        line = json.loads(lines[0])
+        assert line["steps"] == 4 and line["value"] > 0 and line["ms_per_step"] > 0
+        assert line["unit"] == "Mpixel*evals/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+        for key in ("roofline", "kernel_avg_ms", "full_search_c3", "cpu_baseline"):
+            assert key not in line
+        out = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert sorted(out) == ["best_error", "best_iteration", "best_palette", "last_indices"]
+        assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+        assert out["best_palette"].shape == (16, 4) and out["last_indices"].shape == (3, 333 * 333)
+        assert out["best_error"][0] == line["best_error"] and out["best_error"][0] > 0
+        assert 0 <= out["last_indices"].min() and out["last_indices"].max() < 16
+        dumps.append(out)
+    for k in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][k], dumps[1][k])
