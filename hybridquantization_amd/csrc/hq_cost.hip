@@ -96,6 +96,20 @@ __device__ __forceinline__ TileItem tile_item(const CostArgs& a, int w, int P) {
     return t;
 }
 
+// dE2000: a shard's tile rows lie on the full image's tile grid.  The first
+// one starts at fast_grid_row0 <= r0, and the kernels' `if constexpr (DE == 2)`
+// statements mask its rows above r0.  So a pixel sits at the same row of its
+// tile, its taps at the same K slots of the vertical pass, in every sharding:
+// the shards' per-pixel dE are the full image's bit for bit, at the price of
+// up to one extra, partly masked tile row per shard.  dE76 and dE94 keep their
+// tiles from r0, and their kernels the parent's statements token for token
+// (a shared helper that folds to `true` for them still moved their registers).
+template <int DE, int TW, int TH>
+__device__ __forceinline__ void tile_item_to_grid(const CostArgs& a, TileItem& t) {
+    static_assert((TH & (TH - 1)) == 0, "fast_grid_row0 masks with TH - 1");
+    if constexpr (DE == 2) t.y0 -= a.g.r0 & (TH - 1);
+}
+
 // The global loads that fill one item's LDS (index rows of its region, its
 // palette's opponent entry), held in registers between issue and commit.
 // Every load is issued before the first wait: vmcnt retires in order, so a
@@ -394,7 +408,8 @@ __global__ __launch_bounds__(256, 6) void cost_mfma_kernel(CostArgs a, int P_) {
     float* s_v = reinterpret_cast<float*>(s_vq);
     const int tid = threadIdx.x;
     const Geom& g = a.g;
-    const TileItem cur = tile_item<TW, TH>(a, xcd_remap(blockIdx.x, a.ntiles * P_), P_);
+    TileItem cur = tile_item<TW, TH>(a, xcd_remap(blockIdx.x, a.ntiles * P_), P_);
+    tile_item_to_grid<DE, TW, TH>(a, cur);
     const TapsPtr<HALF> taps = (TapsPtr<HALF>)(uintptr_t)a.taps;  // H taps x 2^-30
     const int lane = tid & 63, wv = tid >> 6, lc = lane & 15, lk = lane >> 4;
     const uint4* frag = a.vfrag16 + (TRIM ? 2 * 4 * 2 * 64 : 0) + lane;  // [trim][half 0][stack][hi,lo][lane]
@@ -469,7 +484,8 @@ __global__ __launch_bounds__(256, 6) void cost_mfma_kernel(CostArgs a, int P_) {
     float labv[2][3][HR];
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
-        const bool ok = has_item && gy0 + r < g.r1 && gx0 < g.W;
+        bool ok = has_item && gy0 + r < g.r1 && gx0 < g.W;
+        if constexpr (DE == 2) ok = ok && gy0 + r >= g.r0;
         const uint32_t off = ok ? (uint32_t)((gy0 + r - g.r0) * g.lab_pitch + gx0) : 0u;
         const float* src3[3] = {a.labL, a.labA, a.labB};
 #pragma unroll
@@ -499,7 +515,8 @@ __global__ __launch_bounds__(256, 6) void cost_mfma_kernel(CostArgs a, int P_) {
             for (int xo = 0; xo < HR; ++xo) {
                 const float3 lf = opp2f_fast(acc0[xo][r], acc1[xo][r], acc2[xo][r], a.m_lab);
                 const float e = delta_e_f<DE>(labv[r][0][xo], labv[r][1][xo], labv[r][2][xo], lf);
-                const bool in = gy0 + r < g.r1 && gx0 + xo < g.W;
+                bool in = gy0 + r < g.r1 && gx0 + xo < g.W;
+                if constexpr (DE == 2) in = in && gy0 + r >= g.r0;
                 part += in ? e : 0.f;
                 if (a.pix_err && in)  // test option: the per-pixel dE (CL:201-209's error image)
                     a.pix_err[(int64_t)cur.p * a.pix_pitch + (int64_t)(gy0 + r - g.r0) * g.W + gx0 + xo] = e;
@@ -818,7 +835,8 @@ __global__ __launch_bounds__(64 * NW, (cost16w_waves<HB, NCH>())) void cost16w_k
     float* s_v = reinterpret_cast<float*>(s_vq);
     const int tid = threadIdx.x;
     const Geom& g = a.g;
-    const TileItem cur = tile_item<TW, TH>(a, xcd_remap(blockIdx.x, a.ntiles * P_), P_);
+    TileItem cur = tile_item<TW, TH>(a, xcd_remap(blockIdx.x, a.ntiles * P_), P_);
+    tile_item_to_grid<DE, TW, TH>(a, cur);
     const TapsPtr<HB> taps = (TapsPtr<HB>)(uintptr_t)a.taps;  // H taps x 2^-30
     const int lane = tid & 63, wv = tid >> 6, lc = lane & 15, lk = lane >> 4;
     // pair layout: [trim][step][stack][hi, lo][lane] (build_vpass_f16_pair_fragments);
@@ -1007,7 +1025,8 @@ __global__ __launch_bounds__(64 * NW, (cost16w_waves<HB, NCH>())) void cost16w_k
     float4 lab[2][3];
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
-        const bool ok = gy0 + r < g.r1 && gx0 < g.W;
+        bool ok = gy0 + r < g.r1 && gx0 < g.W;
+        if constexpr (DE == 2) ok = ok && gy0 + r >= g.r0;
         const uint32_t off = ok ? (uint32_t)((gy0 + r - g.r0) * g.lab_pitch + gx0) : 0u;
 #ifdef HQ_ABL_NOLABLD  // timing ablation (wrong results): no LabRef loads
 #pragma unroll
@@ -1081,16 +1100,34 @@ __global__ __launch_bounds__(64 * NW, (cost16w_waves<HB, NCH>())) void cost16w_k
     }
     if (a.pix_err) {  // test option: the per-pixel dE (CL:201-209's error image)
 #pragma unroll
-        for (int r = 0; r < 2; ++r)
+        for (int r = 0; r < 2; ++r) {
+            if constexpr (DE == 2) {
+                if (gy0 + r < g.r0) continue;
+            }
 #pragma unroll
             for (int xo = 0; xo < HR; ++xo)
                 if (gy0 + r < g.r1 && gx0 + xo < g.W)
                     a.pix_err[(int64_t)cur.p * a.pix_pitch + (int64_t)(gy0 + r - g.r0) * g.W + gx0 + xo] =
                         e[r][xo];
+        }
     }
     // tiles inside the image and shard (all but the last tile column and row)
     // sum without per-pixel masks
     float part = 0.f;
+    if constexpr (DE == 2) {  // the same, and a shard's first tile row masks its rows above r0
+        if (cur.x0 + TW <= g.W && cur.y0 + TH <= g.r1 && cur.y0 >= g.r0) {
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+#pragma unroll
+                for (int xo = 0; xo < HR; ++xo) part += e[r][xo];
+        } else {
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+#pragma unroll
+                for (int xo = 0; xo < HR; ++xo)
+                    part += (gy0 + r >= g.r0 && gy0 + r < g.r1 && gx0 + xo < g.W) ? e[r][xo] : 0.f;
+        }
+    } else  // (dE76, dE94: the statement as it was, unindented on purpose)
     if (cur.x0 + TW <= g.W && cur.y0 + TH <= g.r1) {
 #pragma unroll
         for (int r = 0; r < 2; ++r)
@@ -1808,6 +1845,10 @@ template __global__ void gen_vtile2_kernel<0, HQ_VT2_RB>(GenArgs, int);
 template __global__ void gen_vtile2_kernel<1, HQ_VT2_RB>(GenArgs, int);
 template __global__ void gen_vtile_kernel<0>(GenArgs, int);
 template __global__ void gen_vtile_kernel<1>(GenArgs, int);
+template __global__ void gen_vmfma_kernel<2, 1>(GenArgs, int);
+template __global__ void gen_vmfma_kernel<2, 2>(GenArgs, int);
+template __global__ void gen_vtile2_kernel<2, HQ_VT2_RB>(GenArgs, int);
+template __global__ void gen_vtile_kernel<2>(GenArgs, int);
 
 // ----------------------------------------------------------------------------
 // Host side: tap tables, MFMA fragments, launchers
@@ -2023,6 +2064,10 @@ void build_fast_taps(int HB, int H, const float* k1, const float* k2, const floa
 
 // tile_rows: 8 (cost_mfma_kernel, 8 x 108 tiles) or 16 (cost16w_kernel, 16 x
 // tile_w tiles, tile_w = 128 or 256)
+// First row of a shard's tile grid (tile_item): r0, or for dE2000 the image's
+// tile row that holds r0.  own_rows of fast_tile_dims counts from it.
+int fast_grid_row0(int de, int r0, int tile_rows) { return de == 2 ? r0 & ~(tile_rows - 1) : r0; }
+
 void fast_tile_dims(int W, int own_rows, int tile_rows, int tile_w, int* tiles_x, int* ntiles) {
     const int tw = tile_rows == kTH16 ? tile_w : kFastTW;
     *tiles_x = (W + tw - 1) / tw;
@@ -2039,9 +2084,12 @@ static void launch_cost16w(const CostArgs& a0, int P, int de, bool trim, hipStre
     if (de == 0) {
         if (trim) HQ_LAUNCH((cost16w_kernel<HB, 0, true, NW>), grid, block, 0, s, a, P);
         else HQ_LAUNCH((cost16w_kernel<HB, 0, false, NW>), grid, block, 0, s, a, P);
-    } else {
+    } else if (de == 1) {
         if (trim) HQ_LAUNCH((cost16w_kernel<HB, 1, true, NW>), grid, block, 0, s, a, P);
         else HQ_LAUNCH((cost16w_kernel<HB, 1, false, NW>), grid, block, 0, s, a, P);
+    } else {  // 2 (known_de)
+        if (trim) HQ_LAUNCH((cost16w_kernel<HB, 2, true, NW>), grid, block, 0, s, a, P);
+        else HQ_LAUNCH((cost16w_kernel<HB, 2, false, NW>), grid, block, 0, s, a, P);
     }
 }
 
@@ -2061,13 +2109,17 @@ static void launch_cost16w_chunked(const CostArgs& a0, int P, int de, bool trim,
     if (de == 0) {
         if (trim) go(cost16w_kernel<10, 0, true, 4, NCH>);
         else go(cost16w_kernel<10, 0, false, 4, NCH>);
-    } else {
+    } else if (de == 1) {
         if (trim) go(cost16w_kernel<10, 1, true, 4, NCH>);
         else go(cost16w_kernel<10, 1, false, 4, NCH>);
+    } else {  // 2 (known_de)
+        if (trim) go(cost16w_kernel<10, 2, true, 4, NCH>);
+        else go(cost16w_kernel<10, 2, false, 4, NCH>);
     }
 }
 
 hipError_t launch_cost_chunked(const CostArgs& a, int P, int nch, int de, bool trim, hipStream_t s) {
+    if (!known_de(de)) return hipErrorInvalidValue;
     switch (nch) {
     case 2: launch_cost16w_chunked<2>(a, P, de, trim, s); break;
     case 4: launch_cost16w_chunked<4>(a, P, de, trim, s); break;
@@ -2082,6 +2134,7 @@ hipError_t launch_cost_chunked(const CostArgs& a, int P, int nch, int de, bool t
 // 256-column tiles (8 waves, 69 KB of LDS at HB = 10): HB = 10 only.
 hipError_t launch_cost_fast(const CostArgs& a0, int P, int de, bool trim, int tile_rows, int tile_w, int HB,
                             hipStream_t s) {
+    if (!known_de(de)) return hipErrorInvalidValue;
     if (tile_rows == kTH16) {
         if (tile_w == 256) {
             if (HB != 10) return hipErrorInvalidValue;
@@ -2103,7 +2156,8 @@ hipError_t launch_cost_fast(const CostArgs& a0, int P, int de, bool trim, int ti
     const dim3 grid((unsigned)(a.ntiles * P));
 #define HQ_COST(KN, DEV, TR) HQ_LAUNCH((KN<DEV, TR>), grid, dim3(256), 0, s, a, P)
     if (de == 0) { if (trim) HQ_COST(cost_mfma_kernel, 0, true); else HQ_COST(cost_mfma_kernel, 0, false); }
-    else { if (trim) HQ_COST(cost_mfma_kernel, 1, true); else HQ_COST(cost_mfma_kernel, 1, false); }
+    else if (de == 1) { if (trim) HQ_COST(cost_mfma_kernel, 1, true); else HQ_COST(cost_mfma_kernel, 1, false); }
+    else { if (trim) HQ_COST(cost_mfma_kernel, 2, true); else HQ_COST(cost_mfma_kernel, 2, false); }
 #undef HQ_COST
     return hipGetLastError();
 }
@@ -2131,6 +2185,7 @@ static void launch_hrow4(const GenArgs& a, int idx_bytes, hipStream_t s) {
 // The tiled generic pair (gen_hrow + gen_vtile).  idx_bytes: 1, 2 (chunked
 // palettes) or 4 (K > 4096).
 hipError_t launch_cost_tiled_generic(const GenArgs& a, int de, int idx_bytes, hipStream_t s) {
+    if (!known_de(de)) return hipErrorInvalidValue;
     const hipEvent_t ev0 = t_ev_start, ev1 = t_ev_stop;
     t_ev_stop = nullptr;
     const bool vm = a.vmfma && a.vtapd && a.half <= kVt2MaxHalf;  // the matrix-core vertical pass
@@ -2175,10 +2230,12 @@ hipError_t launch_cost_tiled_generic(const GenArgs& a, int de, int idx_bytes, hi
         };
         if (two) {
             if (de == 0) gov(gen_vmfma_kernel<0, 2>);
-            else gov(gen_vmfma_kernel<1, 2>);
+            else if (de == 1) gov(gen_vmfma_kernel<1, 2>);
+            else gov(gen_vmfma_kernel<2, 2>);
         } else {
             if (de == 0) gov(gen_vmfma_kernel<0, 1>);
-            else gov(gen_vmfma_kernel<1, 1>);
+            else if (de == 1) gov(gen_vmfma_kernel<1, 1>);
+            else gov(gen_vmfma_kernel<2, 1>);
         }
         t_ev_start = ev0;
         return hipGetLastError();
@@ -2203,7 +2260,8 @@ hipError_t launch_cost_tiled_generic(const GenArgs& a, int de, int idx_bytes, hi
             HQ_LAUNCH(kern, dim3((unsigned)(tx * ty)), dim3(256), l2, s, a, tx);
         };
         if (de == 0) go2(gen_vtile2_kernel<0, HQ_VT2_RB>);
-        else go2(gen_vtile2_kernel<1, HQ_VT2_RB>);
+        else if (de == 1) go2(gen_vtile2_kernel<1, HQ_VT2_RB>);
+        else go2(gen_vtile2_kernel<2, HQ_VT2_RB>);
         t_ev_start = ev0;
         return hipGetLastError();
     }
@@ -2215,13 +2273,15 @@ hipError_t launch_cost_tiled_generic(const GenArgs& a, int de, int idx_bytes, hi
         HQ_LAUNCH(kern, dim3((unsigned)(tiles_x * tiles_y)), dim3(256), vl, s, a, tiles_x);
     };
     if (de == 0) go(gen_vtile_kernel<0>);
-    else go(gen_vtile_kernel<1>);
+    else if (de == 1) go(gen_vtile_kernel<1>);
+    else go(gen_vtile_kernel<2>);
     t_ev_start = ev0;
     return hipGetLastError();
 }
 
 // idx_bytes: 1, 2 (chunked palettes) or 4 (K > 4096)
 hipError_t launch_cost_generic(const GenArgs& a, int de, int idx_bytes, hipStream_t s) {
+    if (!known_de(de)) return hipErrorInvalidValue;
     // profiling events (when set) bracket both launches: start on the first, stop on the second
     const hipEvent_t ev0 = t_ev_start, ev1 = t_ev_stop;
     t_ev_stop = nullptr;
@@ -2233,8 +2293,10 @@ hipError_t launch_cost_generic(const GenArgs& a, int de, int idx_bytes, hipStrea
     const int64_t n_own = (int64_t)a.g.W * (a.g.r1 - a.g.r0);
     if (de == 0)
         HQ_LAUNCH(gen_vpass_kernel<0>, dim3(blocks_for(n_own)), dim3(256), 0, s, a);
-    else
+    else if (de == 1)
         HQ_LAUNCH(gen_vpass_kernel<1>, dim3(blocks_for(n_own)), dim3(256), 0, s, a);
+    else
+        HQ_LAUNCH(gen_vpass_kernel<2>, dim3(blocks_for(n_own)), dim3(256), 0, s, a);
     t_ev_start = ev0;
     return hipGetLastError();
 }

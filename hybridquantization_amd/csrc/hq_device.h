@@ -99,12 +99,157 @@ __device__ __forceinline__ float3 opp2lab_ref(float o0, float o1, float o2, cons
 // below); the cost is compared at 1e-6 relative.
 __device__ __forceinline__ float hw_sqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
 
+// ----------------------------------------------------------------------------
+// CIEDE2000 (DE = 2): libhq's own addition -- the reference's branch is empty
+// (CL:227-230).  Sharma, Wu & Dalal, "The CIEDE2000 color-difference formula:
+// implementation notes, supplementary test data, and mathematical
+// observations", Color Res. Appl. 30(1), 2005, with kL = kC = kH = 1; sample 1
+// is the original's S-CIELAB, sample 2 the candidate (the value is symmetric).
+//
+// Lowering.  No angle is formed except one small one.  With v_i = (a'_i, b_i),
+// C'_i = |v_i|, p = C'_1 C'_2, dot = v_1 . v_2, cross = v_1 x v_2 and
+// hd = p + |dot| (= 2 p cos^2(dh'/2) for dot >= 0, 2 p sin^2(dh'/2) for dot < 0):
+//   dH' = 2 sqrt(p) sin(dh'/2) = cross sqrt(2 / hd)              (dot >= 0)
+//                              = copysign(sqrt(2 hd), cross)      (dot <  0)
+//     -- the half-angle form: neither p + dot nor p - dot is ever taken where
+//     it cancels.  cross = a'_1 b_2 - b_1 a'_2 with both products rounded: its
+//     error 2^-24 p moves dH' by at most 2^-24 sqrt(2 p), the size of C''s own.
+//   h-bar' is the circular mean of the two hues in each of Sharma's cases (the
+//     +-360 of his table is the wrap), i.e. the direction u = (c, s) of
+//     u_1 + u_2 = (C'_2 v_1 + C'_1 v_2) / p, of length sqrt(2 hd / p) for
+//     dot >= 0; for dot < 0 that sum cancels, and u is u_1 - u_2 = (C'_2 v_1 -
+//     C'_1 v_2) / p (same length formula) turned by +-90 degrees, the sign
+//     that of cross.  The formula is discontinuous at opposite hues (dH'
+//     changes sign, h-bar' jumps by 180 degrees; Sharma's pairs 10 and 14 sit
+//     on it): for cross = 0 exactly the side comes from q itself, which swaps
+//     with the samples as cross does, so the value stays symmetric there too.
+//   T = 1 - .17 cos(h - 30) + .24 cos 2h + .32 cos(3h + 6) - .20 cos(4h - 63)
+//     from (c, s) by the double / triple / quadruple angle products, the phase
+//     shifts folded into seven constants.
+//   d-theta = 30 exp(-((h - 275) / 25)^2): (c', s') = u turned by -275 degrees,
+//     phi = h - 275 = 4 atan(t), t = tan(phi / 4) = s' / (2 ch (1 + ch)), ch =
+//     cos(phi / 2) = sqrt((1 + c') / 2); atan by its series to t^9.  For c' <
+//     -1/2 (|phi| > 120 degrees) the Gaussian is < e^-23 and is set to 0 (c' is
+//     clamped there, so t stays finite); so it is for h in [0, 35) degrees,
+//     which Sharma's h-bar' in [0, 360) puts at h - 275 < -240, not at phi =
+//     h + 85 (his Gaussian is not periodic: e^-11.6 would remain).
+//     R_T = -sin(2 d-theta) R_C with 2 d-theta <= pi / 3 by its series to z^9.
+//   x^7 = (x^2)^3 x, and sqrt(x^7 / (x^7 + 25^7)) = rsq(1 + 25^7 rcp(x^7)):
+//     0 at x = 0 (rcp = inf, rsq(inf) = 0) and 1 when x^7 overflows.
+// C'_1 C'_2 = 0: cross = 0, so dH' = 0; S_H and R_T only ever multiply dH', so
+// h-bar' (Sharma: h'_1 + h'_2) is immaterial and any finite u serves (the
+// clamps below keep rsq finite: 0 * rsq = 0).  Two greys give |dL| / S_L;
+// identical colours give dL = dC' = cross = 0 and sqrt(0) = 0 exactly.
+//
+// Rounding.  v_sqrt / v_rcp / v_rsq / v_exp are within 1 ulp; every quantity
+// above is a sum of a few products of O(1)-conditioned terms, so each of dL /
+// S_L, dC' / S_C, dH' / S_H carries a relative error of a few 2^-24 plus the
+// absolute 2^-24 C' of a' = (1 + G) a and C' = sqrt(.) (6e-6 at C' = 100,
+// divided by S_C >= 5.5 or S_H >= 1.8 there).  u: each component within ~4
+// ulp, as dot >= 0 (dot < 0) keeps |u_1 +- u_2| >= sqrt(2); T then within
+// ~1e-6 and S_H within 0.015 C' 1e-6.  atan's truncation moves d-theta by <
+// 2e-7 degrees (the error t^11 / 11 grows with |phi| while the Gaussian's slope
+// dies: worst at phi = 62 degrees), sin's by 1.05^11 / 11! = 4e-8.  The sum
+// under the final root is >= 0 in exact arithmetic (|R_T| <= sqrt(3) < 2) and
+// is clamped at 0 against rounding.  Measured against a float64 statement:
+// DESIGN.md 9.  Finite for every input below 1e9 in magnitude (C'^2 and the
+// squares of the three terms stay below FLT_MAX); a NaN or inf input gives
+// NaN or inf, which acc_add counts as bad like any other dE's.
+// ----------------------------------------------------------------------------
+__device__ __forceinline__ float hw_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+__device__ __forceinline__ float hw_rsq(float x) { return __builtin_amdgcn_rsqf(x); }
+
+// sqrt(x^7 / (x^7 + 25^7)), x >= 0
+__device__ __forceinline__ float de00_c7(float x) {
+    const float x2 = x * x;
+    return hw_rsq(fmaf(6103515625.0f, hw_rcp((x2 * x2) * (x2 * x)), 1.0f));
+}
+
+__device__ __forceinline__ float ciede2000(float L1, float a1, float b1, float L2, float a2, float b2) {
+    constexpr float kTiny = 0x1p-100f;  // keeps rsq finite at C' = 0; below any C'^2 that matters
+    // a' = (1 + G) a, G = (1 - sqrt(Cbar^7 / (Cbar^7 + 25^7))) / 2
+    const float bb1 = b1 * b1, bb2 = b2 * b2;
+    const float cb = 0.5f * (hw_sqrt(fmaf(a1, a1, bb1)) + hw_sqrt(fmaf(a2, a2, bb2)));
+    const float g1 = fmaf(-0.5f, de00_c7(cb), 1.5f);
+    const float ap1 = g1 * a1, ap2 = g1 * a2;
+    const float c1 = hw_sqrt(fmaf(ap1, ap1, bb1)), c2 = hw_sqrt(fmaf(ap2, ap2, bb2));
+    const float dL = L2 - L1, dC = c2 - c1;
+    const float p = c1 * c2;
+    const float dot = fmaf(ap1, ap2, b1 * b2);
+    // both products rounded (no contraction into an fma, which would leave one
+    // product's rounding error behind): exactly antisymmetric under a swap of the
+    // samples, and exactly 0 for identical colours, a zero chroma, equal or opposite hues
+    float cross;
+    {
+#pragma clang fp contract(off)
+        cross = ap1 * b2 - b1 * ap2;
+    }
+    const bool near = dot >= 0.f;  // hues within 90 degrees: u_1 + u_2; else u_1 - u_2
+    const float hd = p + fabsf(dot);
+    const float rhd = hw_rsq(fmaxf(hd, kTiny));
+    const float c1s = near ? c1 : -c1;
+    const float un = rhd * hw_rsq(fmaxf(p + p, kTiny));
+    const float qx = fmaf(c2, ap1, c1s * ap2) * un, qy = fmaf(c2, b1, c1s * b2) * un;
+    // the side of opposite hues: cross's sign; for cross = 0 exactly, a rule that
+    // swaps with the samples as cross does (q = u_1 - u_2 does), so that the
+    // value stays symmetric on the discontinuity itself
+    const float side = copysignf(1.0f, cross != 0.f ? cross : qx != 0.f ? qx : -qy);
+    const float dH = near ? 1.41421356f * (cross * rhd) : side * (1.41421356f * (hd * rhd));
+    // u = (cc, ss): the mean hue's direction (dot < 0: q turned by +-90 degrees)
+    const float cc = near ? qx : -(side * qy);
+    const float ss = near ? qy : side * qx;
+    const float cx2 = fmaf(cc, cc, -(ss * ss)), sx2 = 2.0f * (cc * ss);
+    const float cx3 = fmaf(cx2, cc, -(sx2 * ss)), sx3 = fmaf(sx2, cc, cx2 * ss);
+    const float cx4 = fmaf(cx2, cx2, -(sx2 * sx2)), sx4 = 2.0f * (sx2 * cx2);
+    float T = fmaf(-0.147224319f, cc, 1.0f);
+    T = fmaf(-0.085f, ss, T);
+    T = fmaf(0.24f, cx2, T);
+    T = fmaf(0.318247007f, cx3, T);
+    T = fmaf(-0.0334491082f, sx3, T);
+    T = fmaf(-0.0907981f, cx4, T);
+    T = fmaf(-0.178201305f, sx4, T);
+    // Gaussian of phi = h - 275 degrees
+    const float cr = fmaf(0.0871557427f, cc, -0.996194698f * ss);
+    const float sr = fmaf(0.0871557427f, ss, 0.996194698f * cc);
+    const float ch = hw_sqrt(fmaf(0.5f, fmaxf(cr, -0.5f), 0.5f));
+    const float t = sr * hw_rcp(fmaf(ch + ch, ch, ch + ch));
+    const float t2 = t * t;
+    float at = fmaf(t2, 1.0f / 9.0f, -1.0f / 7.0f);
+    at = fmaf(at, t2, 1.0f / 5.0f);
+    at = fmaf(at, t2, -1.0f / 3.0f);
+    at = fmaf(at, t2, 1.0f);
+    at *= t;
+    // exp(-(phi / 25 deg)^2), phi = 4 atan t: 2^(-(720 / (25 pi))^2 log2(e) atan^2)
+    const float gs = __builtin_amdgcn_exp2f(-121.243864f * (at * at));
+    // Sharma's h-bar' runs over [0, 360), so h - 275 over [-275, 85): his Gaussian is
+    // not periodic, and hues in [0, 35) degrees (phi in [85, 120)) are on its far side
+    const bool off = cr < -0.5f || (ss >= 0.f && cc > 0.f);
+    const float z = off ? 0.f : 1.04719755f * gs;  // 2 d-theta in radians
+    const float z2 = z * z;
+    float sn = fmaf(z2, 1.0f / 362880.0f, -1.0f / 5040.0f);
+    sn = fmaf(sn, z2, 1.0f / 120.0f);
+    sn = fmaf(sn, z2, -1.0f / 6.0f);
+    sn = fmaf(sn * z2, z, z);
+    const float cbp = 0.5f * (c1 + c2);
+    const float rt = -2.0f * (sn * de00_c7(cbp));
+    const float l50 = fmaf(0.5f, L1 + L2, -50.0f), l2 = l50 * l50;
+    const float sl = fmaf(0.015f * l2, hw_rsq(20.0f + l2), 1.0f);
+    const float sc = fmaf(0.045f, cbp, 1.0f);
+    const float sh = fmaf(0.015f * cbp, T, 1.0f);
+    const float tl = dL * hw_rcp(sl), tc = dC * hw_rcp(sc), th = dH * hw_rcp(sh);
+    const float e2 = fmaf(tl, tl, fmaf(tc, tc, th * fmaf(rt, tc, th)));
+    return hw_sqrt(fmaxf(e2, 0.f));
+}
+
 template <int DE>
 __device__ __forceinline__ float delta_e(float L1, float a1, float b1, float L2, float a2,
                                          float b2) {
+    static_assert(DE >= 0 && DE <= 2, "dE types: 0 CIE76, 1 CIE94, 2 CIEDE2000");
     if constexpr (DE == 0) {
         const float dl = L1 - L2, da = a1 - a2, db = b1 - b2;
         return hw_sqrt((dl * dl + da * da) + db * db);
+    } else if constexpr (DE == 2) {
+        return ciede2000(L1, a1, b1, L2, a2, b2);
     } else {
         const float dL = L1 - L2;
         const float c1 = hw_sqrt(fmaf(a1, a1, b1 * b1));

@@ -11,6 +11,11 @@ namespace hq {
 
 inline unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
 
+// The dE types with kernels (the DE template argument: hq_delta_e's values 0
+// CIE76, 1 CIE94, 2 CIEDE2000).  Every launcher that takes a `de` refuses any
+// other value before its three-way dispatch, so none can fall into a branch.
+inline bool known_de(int de) { return de >= 0 && de <= 2; }
+
 // Profiling: the next launches carry start/stop events in their dispatch packet
 // (hipExtLaunchKernel), so timing a kernel adds no marker packet between kernels
 // (each hipEventRecord between two kernels left the GPU idle ~5 us).  Set by

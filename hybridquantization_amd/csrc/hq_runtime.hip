@@ -37,6 +37,7 @@ int assign_residency(int NG);
 int assign_residency_chunked();
 hipError_t launch_cost_chunked(const CostArgs&, int P, int nch, int de, bool trim, hipStream_t);
 void fast_tile_dims(int W, int own_rows, int tile_rows, int tile_w, int* tiles_x, int* ntiles);
+int fast_grid_row0(int de, int r0, int tile_rows);
 void opp2xyz_over_illum(const float inv_illum[3], float m[9]);
 hipError_t launch_cost_fast(const CostArgs&, int P, int de, bool trim, int tile_rows, int tile_w, int HB,
                             hipStream_t);
@@ -766,7 +767,7 @@ int enqueue_core(hq_ctx* c, int P, int K, const hipEvent_t* ev, bool fold = fals
         ca.acc_p0 = 0;
         ca.g = g;
         ca.K = K;
-        fast_tile_dims(g.W, g.r1 - g.r0, rows, tw, &ca.tiles_x, &ca.ntiles);
+        fast_tile_dims(g.W, g.r1 - fast_grid_row0(c->de_type, g.r0, rows), rows, tw, &ca.tiles_x, &ca.ntiles);
         opp2xyz_over_illum(inv, ca.m_lab);
         ca.pix_err = c->pixel_err ? c->d_pixerr.as<float>() : nullptr;
         ca.pix_pitch = (int64_t)g.W * (g.r1 - g.r0);
@@ -872,8 +873,6 @@ int check_eval_args(hq_ctx* c, const float* palettes, int P, int K) {
     if (!palettes || P < 1 || K < 1) return fail(c, HQ_ERR_ARG, "bad palettes / P=%d / K=%d", P, K);
     if (K > kMaxKWide)
         return fail(c, HQ_ERR_ARG, "K=%d > %d (the plugin's limit, HQ:192)", K, kMaxKWide);
-    if (c->de_type == HQ_DE_CIEDE2000)
-        return fail(c, HQ_ERR_UNSUPPORTED, "CIEDE2000 is unimplemented in the reference (CL:227-230)");
     return HQ_OK;
 }
 
@@ -1075,8 +1074,6 @@ int device_search_run(hq_search* s, int iterations, int* ran) {
     // option such as 'grid' or 'assign_blocks_per_cu', a new image): size its
     // work buffers for the current geometry before enqueueing anything.
     if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
-    if (c->de_type == HQ_DE_CIEDE2000)
-        return fail(c, HQ_ERR_UNSUPPORTED, "CIEDE2000 is unimplemented in the reference (CL:227-230)");
     const NchScope scope(c, s->nch);
     if ((rc = ensure_population(c, s->P, s->K))) return rc;
     if (s->comm != c->comm || s->fold != search_folds(c))
@@ -1537,8 +1534,6 @@ int hq_quantize(hq_ctx* c, const float* rgba4, int64_t n, const float* colors, i
 int hq_compute_error(hq_ctx* c, const float* orig4, const float* quant4, int64_t n,
                      float* err_img4, double* mean) {
     if (!c || !orig4 || !quant4 || n < 1 || !mean) return HQ_ERR_ARG;
-    if (c->de_type == HQ_DE_CIEDE2000)
-        return fail(c, HQ_ERR_UNSUPPORTED, "CIEDE2000 is unimplemented in the reference (CL:227-230)");
     int rc = bind(c);
     if (rc) return rc;
     const int64_t nb = (n + 255) / 256;
@@ -1611,8 +1606,6 @@ int hq_search_create(hq_ctx* c, const hq_swasa_params* params, int K, uint64_t s
     int rc;
     if (device) {
         if (!c->have_image) rc = fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
-        else if (c->de_type == HQ_DE_CIEDE2000)
-            rc = fail(c, HQ_ERR_UNSUPPORTED, "CIEDE2000 is unimplemented in the reference (CL:227-230)");
         else rc = bind(c);
         if (rc) {
             hq_search_destroy(s);

@@ -43,7 +43,15 @@ enum hq_status {
     HQ_ERR_NOMEM = 6
 };
 
-/* IM:20 enum deltaETypes.  CIE76 is what the plugin always uses (HQ:96, HQ:145). */
+/* IM:20 enum deltaETypes.  CIE76 is what the plugin always uses (HQ:96, HQ:145).
+ * CIE94 is the reference's (CL:217-226), its unclamped dH included: NaN on real
+ * images.  CIEDE2000 is libhq's own addition -- the reference's branch is empty
+ * (CL:227-230): the formula of Sharma, Wu & Dalal, "The CIEDE2000
+ * color-difference formula: implementation notes, supplementary test data, and
+ * mathematical observations", Color Res. Appl. 30(1), 2005, kL = kC = kH = 1,
+ * sample 1 the original's S-CIELAB and sample 2 the candidate's; finite (no
+ * NaN of the CIE94 kind) for Lab values below 1e9 in magnitude, on every path a
+ * context of the other types takes. */
 enum hq_delta_e { HQ_DE_CIE76 = 0, HQ_DE_CIE94 = 1, HQ_DE_CIEDE2000 = 2 };
 
 /* SP:19 enum Whitepoint */
@@ -115,7 +123,10 @@ int hq_get_labref(hq_ctx *ctx, float *lab4);
  * outside the fast path's range, option "chunked" 0 or "grid" 0: the exhaustive
  * argmin with 32-bit indices and the generic stencil path.  All give the same
  * indices and used flags (bit-exact) and the same cost (1e-6 relative):
- * costs[p] = mean dE76 + delta * #unused (IM:712, SW:74-82); used[p*K+k] in
+ * costs[p] = mean dE + delta * #unused (IM:712, SW:74-82), dE of the context's
+ * type: dE76, the reference's dE94, or CIEDE2000 (libhq's addition, Sharma, Wu
+ * & Dalal 2005; see hq_delta_e) -- the argmin is nearest in RGB whatever the
+ * type, so indices and used flags do not depend on it; used[p*K+k] in
  * {0,1} (CL:193), may be NULL.  On a sharded context with a communicator the
  * partial sums are all-reduced over RCCL first. */
 int hq_eval_population(hq_ctx *ctx, const float *palettes, int P, int K, float delta,
@@ -144,7 +155,8 @@ int hq_get_pixel_errors(hq_ctx *ctx, int p, float *err);
 int hq_quantize(hq_ctx *ctx, const float *rgba4, int64_t n, const float *colors, int K,
                 float *out4, int32_t *used);
 /* IM:858 computeError(original, quantized, errorImage): mean dE (configured
- * type) and errImg4 = (255-e)^2/255^2 replicated in .xyz (IM:886-893). */
+ * type; HQ_DE_CIEDE2000 is libhq's addition, Sharma, Wu & Dalal 2005: see
+ * hq_delta_e) and errImg4 = (255-e)^2/255^2 replicated in .xyz (IM:886-893). */
 int hq_compute_error(hq_ctx *ctx, const float *orig4, const float *quant4, int64_t n,
                      float *err_img4, double *mean);
 
