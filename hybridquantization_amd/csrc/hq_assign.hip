@@ -664,8 +664,7 @@ void launch_assign_t(const AssignArgs& a0, int P, hipStream_t s) {
         }
         t_ev_start = nullptr;
         t_ev_stop = ev1;
-        const unsigned ub = (unsigned)std::min<int64_t>(512, (a.n_ext + 4095) / 4096);
-        HQ_LAUNCH(used_idx16_kernel, dim3(ub, (unsigned)npal), dim3(256), 0, s, a);
+        launch_used_idx16(a, npal, s);
         t_ev_start = ev0;
         return;
     }
@@ -699,19 +698,18 @@ void launch_used_idx16(const AssignArgs& a, int P, hipStream_t s) {
 }
 
 hipError_t launch_assign(const AssignArgs& a, int P, hipStream_t s) {
-    if (a.rgbx) launch_assign_t<true>(a, P, s);
-    else launch_assign_t<false>(a, P, s);
+    with_bool(a.rgbx, [&](auto U8) { launch_assign_t<U8.value>(a, P, s); });
     return hipGetLastError();
 }
 
 // Resident workgroups per CU of assign_pipe_kernel<NG> (the auto size of one
 // grid-stride round; the packed and planar forms and, for NG = 4, the chunk
 // combining forms take the larger register count); 0 if the query fails.
+static const auto q = [](auto kern) {  // resident workgroups of 256 threads per CU; 0 if the query fails
+    int n = 0;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, 256, 0) == hipSuccess ? n : 0;
+};
 int assign_residency(int NG) {
-    auto q = [](auto kern) {
-        int n = 0;
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, 256, 0) == hipSuccess ? n : 0;
-    };
     switch (NG) {
     case 1: return std::min(q(assign_pipe_kernel<1, false>), q(assign_pipe_kernel<1, true>));
     case 2: return std::min(q(assign_pipe_kernel<2, false>), q(assign_pipe_kernel<2, true>));
@@ -722,10 +720,6 @@ int assign_residency(int NG) {
 
 // The same for the chunk-combining forms (chunked palettes, nch = 2 .. 16).
 int assign_residency_chunked() {
-    auto q = [](auto kern) {
-        int n = 0;
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, 256, 0) == hipSuccess ? n : 0;
-    };
     int r = std::min(q(assign_pipe_kernel<4, false, 2>), q(assign_pipe_kernel<4, true, 2>));
     r = std::min(r, std::min(q(assign_pipe_kernel<4, false, 4>), q(assign_pipe_kernel<4, true, 4>)));
     r = std::min(r, std::min(q(assign_pipe_kernel<4, false, 4, 2>), q(assign_pipe_kernel<4, true, 4, 2>)));

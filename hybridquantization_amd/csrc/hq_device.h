@@ -35,9 +35,7 @@ __constant__ float c_RGB2XYZ[9] = {0.4124564f, 0.3575761f, 0.1804375f, 0.2126729
                                    0.0721750f, 0.0193339f, 0.1191920f, 0.9503041f};
 __constant__ float c_XYZ2Opp[9] = {0.2787336f,  0.7218031f, -0.1065520f, -0.4487736f, 0.2898056f,
                                    -0.0771569f, 0.0859513f, -0.5899859f, 0.5011089f};
-#define HQ_OPP2XYZ {0.624045f, -1.87044f, -0.155304f, 1.36606f, 0.931563f, \
-                   0.433903f, 1.5013f,   1.41761f,  2.53307f}
-__constant__ float c_Opp2XYZ[9] = HQ_OPP2XYZ;
+__constant__ float c_Opp2XYZ[9] = HQ_OPP2XYZ;  // (hq_cost_layout.h: the host's opp2xyz_over_illum reads it too)
 __constant__ float c_RGB2Opp[9] = {0.266413f,  0.603167f, 0.00113333f, -0.124957f, 0.0375879f,
                                    -0.133381f, -0.0803345f, -0.331467f, 0.449132f};
 
@@ -382,6 +380,10 @@ __device__ __forceinline__ float dist2_rank_pk(f32x2 rg, float b, float4 c) {
 }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+// operands and accumulator of v_mfma_f32_16x16x32_f16 (both cost files' vertical passes)
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 template <typename V>
 __device__ __forceinline__ V wave_sum(V v) {

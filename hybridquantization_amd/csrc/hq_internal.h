@@ -1,9 +1,12 @@
-// hq_internal.h -- structs shared by the HIP kernels (hq_kernels.hip) and the
-// host runtime (hq_runtime.hip).  Not part of the public ABI (include/hq.h).
+// hq_internal.h -- structs shared by the HIP kernels (the hq_*.hip translation
+// units) and the host runtime (hq_runtime.hip).  Not part of the public ABI
+// (include/hq.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "hq_cost_layout.h"
 
 namespace hq {
 
@@ -21,7 +24,6 @@ inline int chunk_count(int K) {
     return n;
 }
 constexpr int kMaxTaps = 255;     // generic path limit (2*half+1)
-constexpr int kNumFilt = 7;       // separable filter pairs of the S-CIELAB stencil
 constexpr int kL1Cap = 31;        // level-1 candidate list capacity (32-B entry)
 #ifndef HQ_L2B
 #define HQ_L2B 8  // bytes per level-2 entry: 8 (count + 7 indices) or 16 (count + 15)

@@ -626,14 +626,11 @@ __global__ __launch_bounds__(kN16Threads) void assign16_kernel(AssignArgs a, int
     }
 }
 
-void launch_used_idx16(const AssignArgs& a, int P, hipStream_t s);  // (hq_assign.hip)
-
-// assign16 then the used bits from the final indices; the profiling events
-// bracket both.
+// assign16 then the used bits from the final indices (launch_used_idx16,
+// hq_assign.hip); the profiling events bracket both.
 hipError_t launch_assign16(const AssignArgs& a0, int P, hipStream_t s) {
-    const hipEvent_t ev0 = t_ev_start, ev1 = t_ev_stop;
+    LaunchEventPair ev;
     AssignArgs a = a0;
-    t_ev_stop = nullptr;
     const int npal = a.K <= 4096 ? 2 : 1;  // two 64 KiB tables fit one workgroup up to K = 4096
     const size_t lds = sizeof(float4) * (size_t)a.K * npal;
     const dim3 grid((unsigned)(a.nblocks * ((P + npal - 1) / npal)));
@@ -642,22 +639,12 @@ hipError_t launch_assign16(const AssignArgs& a0, int P, hipStream_t s) {
         ok = allow_dyn_lds(reinterpret_cast<const void*>(kern), lds);
         if (ok) HQ_LAUNCH(kern, grid, dim3(kN16Threads), lds, s, a, P);
     };
-    if (npal == 2) {
-        if (a.rgbx) go(assign16_kernel<true, 2>);
-        else go(assign16_kernel<false, 2>);
-    } else {
-        if (a.rgbx) go(assign16_kernel<true, 1>);
-        else go(assign16_kernel<false, 1>);
-    }
-    if (!ok) {
-        t_ev_start = ev0;
-        t_ev_stop = ev1;
-        return hipErrorInvalidConfiguration;  // the LDS raise was refused: nothing launched
-    }
-    t_ev_start = nullptr;
-    t_ev_stop = ev1;
+    with_bool(a.rgbx, [&](auto RGBX) {
+        with_bool(npal == 2, [&](auto TWO) { go(assign16_kernel<RGBX.value, TWO.value ? 2 : 1>); });
+    });
+    if (!ok) return hipErrorInvalidConfiguration;  // the LDS raise was refused: nothing launched
+    ev.second();
     launch_used_idx16(a, P, s);
-    t_ev_start = ev0;
     return hipGetLastError();
 }
 

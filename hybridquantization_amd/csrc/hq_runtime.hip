@@ -11,10 +11,12 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <mutex>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
-#include "hq_internal.h"
+#include "hq_launch.h"
 #include "hq_swasa.h"
 
 #ifndef HQ_COST_TW
@@ -24,53 +26,24 @@
 #define HQ_SA_GRAPH 0  // (measured slower: C3 0.528 -> 0.540 ms, shard-of-8 0.1035 -> 0.110 ms per step)
 #endif
 
-namespace hq {
-// launchers from hq_kernels.hip
-hipError_t launch_prep_palette(const PaletteArgs&, int P, hipStream_t);
-hipError_t launch_sa_step(const SaArgs&, hipStream_t);
-void set_launch_events(hipEvent_t start, hipEvent_t stop);
-hipError_t launch_build_grid(const GridArgs&, int P, hipStream_t);
-hipError_t launch_assign(const AssignArgs&, int P, hipStream_t);
-hipError_t launch_lists16_grid(const Lists16Args&, int P, hipStream_t);
-hipError_t launch_assign16(const AssignArgs&, int P, hipStream_t);
-int assign_residency(int NG);
-int assign_residency_chunked();
-hipError_t launch_cost_chunked(const CostArgs&, int P, int nch, int de, bool trim, hipStream_t);
-void fast_tile_dims(int W, int own_rows, int tile_rows, int tile_w, int* tiles_x, int* ntiles);
-int fast_grid_row0(int de, int r0, int tile_rows);
-void opp2xyz_over_illum(const float inv_illum[3], float m[9]);
-hipError_t launch_cost_fast(const CostArgs&, int P, int de, bool trim, int tile_rows, int tile_w, int HB,
-                            hipStream_t);
-int fast_bucket(int half);
-size_t vpass_f16_stack_fragment_halves(int HB);
-void build_vpass_f16_pair_fragments(int HB, int H, const float* k1, const float* k2, const float* k3,
-                                    const float* absk3, uint16_t* out);
-size_t vpass_f16_pair_fragment_halves(int HB);
-size_t vtile_dup_tap_words(int H);
-void build_vtile_dup_taps(int H, const float* k1, const float* k2, const float* absk3, uint32_t* out);
-void build_vpass_f16_stack_fragments(int HB, int H, const float* k1, const float* k2, const float* k3,
-                                     const float* absk3, uint16_t* out);
-size_t fast_taps_bytes(int HB);
-void build_fast_taps(int HB, int H, const float* k1, const float* k2, const float* k3, const float* absk3,
-                     void* out);
-bool trim_window_ok(const float* k1, int H, int HB);
+namespace hq {  // launch state shared by every launcher (hq_launch.h)
+thread_local hipEvent_t t_ev_start = nullptr, t_ev_stop = nullptr;
 
-hipError_t launch_cost_generic(const GenArgs&, int de, int idx_bytes, hipStream_t);
-hipError_t launch_cost_tiled_generic(const GenArgs&, int de, int idx_bytes, hipStream_t);
-hipError_t launch_prep_wide(const WideArgs&, int P, hipStream_t);
-hipError_t launch_assign_wide(const WideArgs&, int P, hipStream_t);
-hipError_t launch_finalize(const FinalizeArgs&, int P, hipStream_t);
-hipError_t launch_pack_u8(const float*, const float*, const float*, uint32_t*, int*, int64_t, hipStream_t);
-hipError_t launch_labref_opp(const float*, const float*, const float*, float4*, int64_t, hipStream_t);
-hipError_t launch_xyz_to_opp(const float4*, float4*, int64_t, hipStream_t);
-hipError_t launch_rgb_to_xyz(const float*, const float*, const float*, float4*, int64_t, hipStream_t);
-hipError_t launch_labref_hconv(const float4*, float4*, const float*, int, int, int, int64_t, hipStream_t);
-hipError_t launch_labref_vconv(const float4*, float4*, const float*, int, int, int, const Geom&, hipStream_t);
-hipError_t launch_labref_lab(const float4*, float*, float*, float*, float4*, int, int64_t, int,
-                             const float*, hipStream_t);
-hipError_t launch_lab_to_planar(const float4*, float*, float*, float*, int, int64_t, int, hipStream_t);
-hipError_t launch_quantize(const float4*, const float4*, int, int*, float4*, int64_t, hipStream_t);
-hipError_t launch_error_image(const float4*, const float4*, float4*, double*, int64_t, int, hipStream_t);
+void set_launch_events(hipEvent_t start, hipEvent_t stop) {
+    t_ev_start = start;
+    t_ev_stop = stop;
+}
+
+bool allow_dyn_lds(const void* fn, size_t bytes) {
+    static std::mutex mu;
+    static std::unordered_map<const void*, size_t> granted;
+    const std::lock_guard<std::mutex> lock(mu);
+    size_t& g = granted[fn];
+    if (bytes <= g) return true;
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return false;
+    g = bytes;
+    return true;
+}
 }  // namespace hq
 
 using namespace hq;
@@ -88,6 +61,10 @@ struct DevBuf {
         hipError_t e = hipMalloc(&p, n);
         if (e == hipSuccess) bytes = n;
         return e;
+    }
+    hipError_t upload(const void* src, size_t n) {  // ensure(n), then a blocking copy from the host
+        const hipError_t e = ensure(n);
+        return e != hipSuccess ? e : hipMemcpy(p, src, n, hipMemcpyHostToDevice);
     }
     void release() {
         if (p) (void)hipFree(p);
@@ -1044,10 +1021,8 @@ int device_search_create(hq_ctx* c, const hq_swasa_params* params, int K, uint64
         A[n] = (A[n - 1] * mult) & mask;
         C[n] = (C[n - 1] * mult + 0xBull) & mask;
     }
-    HIP_TRY(c, s->jA.ensure(sizeof(uint64_t) * nj));
-    HIP_TRY(c, s->jC.ensure(sizeof(uint64_t) * nj));
-    HIP_TRY(c, hipMemcpy(s->jA.p, A.data(), sizeof(uint64_t) * nj, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(s->jC.p, C.data(), sizeof(uint64_t) * nj, hipMemcpyHostToDevice));
+    HIP_TRY(c, s->jA.upload(A.data(), sizeof(uint64_t) * nj));
+    HIP_TRY(c, s->jC.upload(C.data(), sizeof(uint64_t) * nj));
     const uint64_t s0 = (seed ^ mult) & mask;  // JavaRandom::set_seed
     HIP_TRY(c, hipMemcpy(s->seed[0].p, &s0, sizeof s0, hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemset(s->err[0].p, 0, sizeof(double) * P));
@@ -1239,14 +1214,10 @@ int hq_set_filters(hq_ctx* c, int taps, const float* k1, const float* k2, const 
     c->k2.assign(k2, k2 + 4 * taps);
     c->k3.assign(k3, k3 + taps);
     c->absk3.assign(absk3, absk3 + taps);
-    HIP_TRY(c, c->d_k1.ensure(sizeof(float) * 4 * taps));
-    HIP_TRY(c, c->d_k2.ensure(sizeof(float) * 4 * taps));
-    HIP_TRY(c, c->d_k3.ensure(sizeof(float) * taps));
-    HIP_TRY(c, c->d_absk3.ensure(sizeof(float) * taps));
-    HIP_TRY(c, hipMemcpy(c->d_k1.p, k1, sizeof(float) * 4 * taps, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->d_k2.p, k2, sizeof(float) * 4 * taps, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->d_k3.p, k3, sizeof(float) * taps, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->d_absk3.p, absk3, sizeof(float) * taps, hipMemcpyHostToDevice));
+    HIP_TRY(c, c->d_k1.upload(k1, sizeof(float) * 4 * taps));
+    HIP_TRY(c, c->d_k2.upload(k2, sizeof(float) * 4 * taps));
+    HIP_TRY(c, c->d_k3.upload(k3, sizeof(float) * taps));
+    HIP_TRY(c, c->d_absk3.upload(absk3, sizeof(float) * taps));
     {  // the tiled generic path's vertical taps per plane (t1.xyz: k1, t2.xyz: k2, t3: |k3|)
         c->vtap_pitch = (taps + 15) / 16 * 16 + 16;
         std::vector<float> vt((size_t)kNumFilt * c->vtap_pitch, 0.f);
@@ -1257,21 +1228,18 @@ int hq_set_filters(hq_ctx* c, int taps, const float* k1, const float* k2, const 
             }
             vt[(size_t)6 * c->vtap_pitch + t] = absk3[t];
         }
-        HIP_TRY(c, c->d_vtaps.ensure(sizeof(float) * vt.size()));
-        HIP_TRY(c, hipMemcpy(c->d_vtaps.p, vt.data(), sizeof(float) * vt.size(), hipMemcpyHostToDevice));
+        HIP_TRY(c, c->d_vtaps.upload(vt.data(), sizeof(float) * vt.size()));
         std::vector<float> ht((size_t)8 * taps);
         for (int t = 0; t < taps; ++t) {
             const float v[8] = {k1[4 * t], k1[4 * t + 1], k1[4 * t + 2], k3[t], k2[4 * t], k2[4 * t + 1], k2[4 * t + 2], 0.f};
             std::copy(v, v + 8, ht.begin() + 8 * t);
         }
-        HIP_TRY(c, c->d_htaps.ensure(sizeof(float) * ht.size()));
-        HIP_TRY(c, hipMemcpy(c->d_htaps.p, ht.data(), sizeof(float) * ht.size(), hipMemcpyHostToDevice));
+        HIP_TRY(c, c->d_htaps.upload(ht.data(), sizeof(float) * ht.size()));
         // gen_vmfma's vertical taps (t3: |k3|), then gen_hmfma's horizontal ones (t3: k3)
         std::vector<uint32_t> fm(2 * vtile_dup_tap_words(c->half));
         build_vtile_dup_taps(c->half, k1, k2, absk3, fm.data());
         build_vtile_dup_taps(c->half, k1, k2, k3, fm.data() + vtile_dup_tap_words(c->half));
-        HIP_TRY(c, c->d_vfragm.ensure(fm.size() * sizeof(uint32_t)));
-        HIP_TRY(c, hipMemcpy(c->d_vfragm.p, fm.data(), fm.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_TRY(c, c->d_vfragm.upload(fm.data(), fm.size() * sizeof(uint32_t)));
     }
     // fast path: the filters centred in the smallest tap bucket that holds them
     // (half-widths up to 24: every dpi / viewing distance of HQ:229-231 up to
@@ -1282,18 +1250,13 @@ int hq_set_filters(hq_ctx* c, int taps, const float* k1, const float* k2, const 
         const int HB = c->fast_hb;
         std::vector<uint16_t> f16s(vpass_f16_stack_fragment_halves(HB));
         build_vpass_f16_stack_fragments(HB, c->half, k1, k2, k3, absk3, f16s.data());
-        HIP_TRY(c, c->d_vfrag16.ensure(f16s.size() * sizeof(uint16_t)));
-        HIP_TRY(c, hipMemcpy(c->d_vfrag16.p, f16s.data(), f16s.size() * sizeof(uint16_t),
-                             hipMemcpyHostToDevice));
+        HIP_TRY(c, c->d_vfrag16.upload(f16s.data(), f16s.size() * sizeof(uint16_t)));
         std::vector<uint16_t> f16p(vpass_f16_pair_fragment_halves(HB));
         build_vpass_f16_pair_fragments(HB, c->half, k1, k2, k3, absk3, f16p.data());
-        HIP_TRY(c, c->d_vfrag16p.ensure(f16p.size() * sizeof(uint16_t)));
-        HIP_TRY(c, hipMemcpy(c->d_vfrag16p.p, f16p.data(), f16p.size() * sizeof(uint16_t),
-                             hipMemcpyHostToDevice));
+        HIP_TRY(c, c->d_vfrag16p.upload(f16p.data(), f16p.size() * sizeof(uint16_t)));
         std::vector<char> tb(fast_taps_bytes(HB));
         build_fast_taps(HB, c->half, k1, k2, k3, absk3, tb.data());
-        HIP_TRY(c, c->d_taps.ensure(tb.size()));
-        HIP_TRY(c, hipMemcpy(c->d_taps.p, tb.data(), tb.size(), hipMemcpyHostToDevice));
+        HIP_TRY(c, c->d_taps.upload(tb.data(), tb.size()));
     }
     c->have_image = false;  // halo depends on the filters
     return HQ_OK;

@@ -6,9 +6,6 @@
 #include "hq_device.h"
 #include "hq_launch.h"
 
-#include <mutex>
-#include <unordered_map>
-
 namespace hq {
 
 // ----------------------------------------------------------------------------
@@ -918,23 +915,6 @@ __global__ __launch_bounds__(1024) void finalize_kernel(FinalizeArgs a) {
 // ----------------------------------------------------------------------------
 // Launchers
 // ----------------------------------------------------------------------------
-thread_local hipEvent_t t_ev_start = nullptr, t_ev_stop = nullptr;
-
-bool allow_dyn_lds(const void* fn, size_t bytes) {
-    static std::mutex mu;
-    static std::unordered_map<const void*, size_t> granted;
-    const std::lock_guard<std::mutex> lock(mu);
-    size_t& g = granted[fn];
-    if (bytes <= g) return true;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return false;
-    g = bytes;
-    return true;
-}
-void set_launch_events(hipEvent_t start, hipEvent_t stop) {
-    t_ev_start = start;
-    t_ev_stop = stop;
-}
-
 hipError_t launch_prep_palette(const PaletteArgs& a, int P, hipStream_t s) {
     HQ_LAUNCH(prep_palette_kernel, dim3(P), dim3(1024), 0, s, a);
     return hipGetLastError();

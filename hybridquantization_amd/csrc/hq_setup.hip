@@ -252,15 +252,10 @@ hipError_t launch_quantize(const float4* in, const float4* colors, int K, int* u
 hipError_t launch_error_image(const float4* orig, const float4* quant, float4* err_img,
                               double* partial, int64_t n, int de, hipStream_t s) {
     if (!known_de(de)) return hipErrorInvalidValue;
-    if (de == 0)
-        hipLaunchKernelGGL(error_image_kernel<0>, dim3(blocks_for(n)), dim3(256), 0, s, orig,
+    with_de(de, [&](auto DE) {
+        hipLaunchKernelGGL(error_image_kernel<DE.value>, dim3(blocks_for(n)), dim3(256), 0, s, orig,
                            quant, err_img, partial, n);
-    else if (de == 1)
-        hipLaunchKernelGGL(error_image_kernel<1>, dim3(blocks_for(n)), dim3(256), 0, s, orig,
-                           quant, err_img, partial, n);
-    else
-        hipLaunchKernelGGL(error_image_kernel<2>, dim3(blocks_for(n)), dim3(256), 0, s, orig,
-                           quant, err_img, partial, n);
+    });
     return hipGetLastError();
 }
 

@@ -3,7 +3,7 @@
 // argmin of CL:179-193 over LDS-staged colour chunks, and used flags as the
 // reference keeps them (int usedColors[K], CL:193).  The stencil cost of these
 // populations runs the generic two-pass path on the 32-bit index image
-// (hq_cost.hip, gen_*_kernel<uint32_t>).
+// (hq_cost_generic.hip, gen_*_kernel<uint32_t>).
 #include "hq_device.h"
 #include "hq_launch.h"
 

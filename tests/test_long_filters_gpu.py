@@ -1,4 +1,4 @@
-"""The long-filter cost path (halfSize > 24: hq_cost.hip's generic pairs) across
+"""The long-filter cost path (halfSize > 24: hq_cost_generic.hip's pairs) across
 half-width boundaries, dE types, index widths, palettes outside the fast
 range, row-block shards shorter than their halo, the search and a filter
 switch on a live context.

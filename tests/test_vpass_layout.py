@@ -1,5 +1,5 @@
 """CPU check of the vertical stencil's (hi, lo) pair layout (hq_cost.hip
-vblock_pair / build_vpass_f16_pair_fragments, cost16w above HB = 10).
+vblock_pair / hq_cost_taps.cpp build_vpass_f16_pair_fragments, cost16w above HB = 10).
 
 For one column and one filter, the kernel computes output rows y = 8 h + o of a
 16-row tile (halves h = 0, 1; o = 0..7) as MFMA K steps u = 0..S-1 over the
