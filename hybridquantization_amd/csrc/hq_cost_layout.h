@@ -31,6 +31,12 @@ struct CostTaps {
 // exactly (a power of two).
 constexpr float kVTapScale = 65536.0f;                      // 2^16
 constexpr float kVOutScale = 1.0f / (16384.0f * 65536.0f);  // 2^-30
+// The largest |tap| whose hi part stays finite: tap x 2^16 <= 65504, f16's
+// largest finite value (0.99951171875; the largest designed tap, the centre of
+// k1.x at 4 dpi / 45 cm, is 0.986).  A caller's filter set with a tap beyond
+// it, or a non-finite one, takes the fp32 forms (taps_fit_split, checked at
+// hq_set_filters), as a palette outside the split range does.
+constexpr float kVTapMax = 65504.0f / kVTapScale;
 
 // Region row of K slot (g = lane >> 4, j) of the vertical pass's B operand.
 // Half 0 (output rows 0-7): rows 4j + g (lane group g holds every 4th row).
@@ -69,6 +75,7 @@ constexpr int vtile_pair_steps(int H) { return (16 + 2 * H + 15) / 16; }
 // ---- the table builders (hq_cost_taps.cpp) ------------------------------------
 int fast_bucket(int half);
 bool trim_window_ok(const float* k1, int H, int HB);
+bool taps_fit_split(const float* k1, const float* k2, const float* k3, const float* absk3, int taps);
 void opp2xyz_over_illum(const float inv_illum[3], float m[9]);
 void build_fast_taps(int HB, int H, const float* k1, const float* k2, const float* k3, const float* absk3,
                      void* out);

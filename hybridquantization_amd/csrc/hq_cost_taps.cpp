@@ -190,6 +190,20 @@ bool trim_window_ok(const float* k1, int H, int HB) {
     return true;
 }
 
+// Every tap of the set is finite and within kVTapMax: the split-f16 tables
+// (split_vtap: the bucket fragments, gen_vmfma's and gen_hmfma's tap rows) hold
+// it.  Else tap x 2^16 rounds to f16's infinity and the matrix-core passes
+// return a non-finite cost: such a set runs on the fp32 forms.
+bool taps_fit_split(const float* k1, const float* k2, const float* k3, const float* absk3, int taps) {
+    const auto fits = [](float w) { return std::fabs(w) <= kVTapMax; };  // (false for NaN)
+    for (int t = 0; t < taps; ++t) {
+        for (int ch = 0; ch < 3; ++ch)
+            if (!fits(k1[4 * t + ch]) || !fits(k2[4 * t + ch])) return false;
+        if (!fits(k3[t]) || !fits(absk3[t])) return false;
+    }
+    return true;
+}
+
 // [0] the bucket's taps as designed, [1] the same with the horizontal taps
 // scaled by 2^-30 (exact) for the matrix-core vertical pass, whose outputs
 // carry 2^30.  Layout: two CostTaps<HB>.

@@ -168,6 +168,8 @@ struct hq_ctx {
     int trim = 1;          // skip taps < 1e-9 of the peak of the narrow k1 filters
     bool trim_ok = false;  // set by hq_set_filters (the bucket's narrow-filter windows hold)
     bool pal_generic = false;  // this population needs the generic cost path (palette_fits_fast)
+    bool taps_generic = false;  // set by hq_set_filters: a tap outside the split-f16 range (taps_fit_split),
+                                // so the cost runs on the fp32 forms whatever cost_variant and gen_vmfma say
 
     // comm
     ncclComm_t comm = nullptr;
@@ -440,7 +442,7 @@ bool use_lists16(const hq_ctx* c) {
 // front: nothing may allocate while a search run is captured into a graph).
 // Chunked palettes: the 16 x 128 tiles at HB = 10 only.
 bool cost_fast(const hq_ctx* c) {
-    return c->cost_variant == 0 && c->fast_hb > 0 && !c->pal_generic &&
+    return c->cost_variant == 0 && c->fast_hb > 0 && !c->pal_generic && !c->taps_generic &&
            (c->nch_cur == 1 || (c->nch_cur <= kMaxNchFast && c->fast_hb == 10 && c->cost_rows == 16 &&
                                 c->cost_tw == 128));
 }
@@ -571,8 +573,9 @@ int enqueue_generic_cost(hq_ctx* c, int P, const void* idx_base, int idx_bytes, 
         gn.hrow4 = c->gen_hrow4;
         gn.hrow_no = c->gen_hrow_no;
         gn.vtile2 = c->gen_vtile2;
-        // split-f16 planes hold |x| < 4 (x 2^14): palettes outside the fast range stay on fp32
-        gn.vmfma = c->gen_vmfma && !c->pal_generic;
+        // split-f16 planes hold |x| < 4 (x 2^14), split taps |w| <= kVTapMax: palettes and
+        // filters outside the fast range stay on fp32 (gen_hmfma runs only with gen_vmfma)
+        gn.vmfma = c->gen_vmfma && !c->pal_generic && !c->taps_generic;
         gn.vtapd = c->d_vfragm.bytes ? c->d_vfragm.as<uint32_t>() : nullptr;
         gn.hmfma = c->gen_hmfma;
         gn.shape = c->gen_shape;
@@ -1246,6 +1249,7 @@ int hq_set_filters(hq_ctx* c, int taps, const float* k1, const float* k2, const 
     // ~200 dpi at 45 cm); longer filters take the generic path
     c->fast_hb = fast_bucket(c->half);
     c->trim_ok = c->fast_hb > 0 && trim_window_ok(k1, c->half, c->fast_hb);
+    c->taps_generic = !taps_fit_split(k1, k2, k3, absk3, taps);
     if (c->fast_hb > 0) {
         const int HB = c->fast_hb;
         std::vector<uint16_t> f16s(vpass_f16_stack_fragment_halves(HB));

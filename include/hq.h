@@ -82,7 +82,11 @@ int hq_design_filters(int dpi, double viewing_distance, int whitepoint, int max_
                       float *illum);
 
 /* IM:800 updateOpenCLFilters(filters, absfilters): uploads the packed taps.
- * halfSize = (4*taps)/8 as IM:408. */
+ * halfSize = (4*taps)/8 as IM:408.  Any taps are accepted.  The matrix-core
+ * cost kernels hold a tap as f16 parts of tap * 2^16, so a set with a tap of
+ * magnitude above 65504 / 65536 (0.99951; every designed tap is below 0.987)
+ * or a non-finite tap is evaluated by the fp32 cost kernels instead: the same
+ * results within fp32 rounding, at the generic path's speed. */
 int hq_set_filters(hq_ctx *ctx, int taps, const float *k1, const float *k2, const float *k3,
                    const float *absk3);
 

@@ -67,19 +67,23 @@ def _partial(m, pals, P, K):
     return out[:, 0].copy(), out[:, 1:].copy()
 
 
-def _ref(dpi, vd, half, w, h, Ks=(64, 256)):
+def _ref(dpi, vd, half, w, h, Ks=(64, 256), f=None, image=None, palette=None):
     """Image, oracle LabRef and, per palette, the oracle's parts and the float64
-    per-pixel dE76: computed once per case, shared and read-only."""
-    key = (dpi, vd, w, h, Ks)
+    per-pixel dE76: computed once per case, shared and read-only.  f: a filter
+    set of the caller's in place of the designed one of (dpi, vd), which then
+    are only its key; image(w, h, seed) -> R, G, B and palette(K, seed) in place
+    of the dark-block image and palettes (test_fast_path_gpu.py)."""
+    key = (dpi, vd, w, h, Ks) + ((image.__name__,) if image else ())
     if key in _REFS:
         return _REFS[key]
-    f = _filters(dpi, vd, half)
-    R, G, B = _dark_case(w, h, seed=w + h)
+    f = _filters(dpi, vd, half) if f is None else f
+    assert f.half == half
+    R, G, B = (image or _dark_case)(w, h, seed=w + h)
     rgba = o.inline_rgba(R, G, B)
     lab = c_oracle.srgb_to_scielab(R, G, B, f, w, nthreads=_threads())
     per = []
     for j, K in enumerate(Ks):
-        pal = _pal_with_dark(K, 900 + j + w)
+        pal = (palette or _pal_with_dark)(K, 900 + j + w)
         cost, parts = c_oracle.eval_palette(rgba, lab, pal, f, w, nthreads=_threads(), return_parts=True)
         ex = exact_pixel_err(parts["idx"], pal, lab, f, w, h)
         for a in (parts["idx"], parts["used"], parts["err"], ex):
@@ -103,23 +107,32 @@ def _ref(dpi, vd, half, w, h, Ks=(64, 256)):
 PIX_MAX, PIX_MEAN = 2.0, 1.5
 
 
-def _pixel_bars(err, ref, label, fails):
+def _pixel_bars(err, ref, label, fails, min_sample=0, yard=None):
     """|gpu - oracle| <= 2e-4 on every pixel; |gpu - float64| within PIX_MAX x the
     oracle's worst pixel and PIX_MEAN x its mean.  Prints the figures, appends
-    what misses to `fails` (asserted by the caller after every form has run)."""
+    what misses to `fails` (asserted by the caller after every form has run).
+    min_sample, yard (test_fast_path_gpu.py, whose images go down to 1 x 1; every
+    image of this module is under the plain bars): below min_sample pixels the
+    mean bar is not applied and the worst pixel is held to PIX_MAX x the larger
+    of the image's own oracle worst pixel and `yard`, the oracle's on a larger
+    image of the same filters."""
     e_gpu, e_orc = np.abs(err - ref["ex"]), np.abs(ref["err"] - ref["ex"])
     worst = float(np.abs(err - ref["err"]).max())
+    small = err.size < min_sample
+    o_max = max(float(e_orc.max()), yard if small and yard is not None else 0.0)
+    o_mean = float(e_orc.mean())
     stats = (f"{label}: |gpu-exact| max {e_gpu.max():.3g} mean {e_gpu.mean():.3g}; |oracle-exact| max "
-             f"{e_orc.max():.3g} mean {e_orc.mean():.3g}; ratios {e_gpu.max() / e_orc.max():.3f} "
-             f"{e_gpu.mean() / e_orc.mean():.3f}; |gpu-oracle| max {worst:.3g}")
+             f"{e_orc.max():.3g} mean {o_mean:.3g}{f' (yard {yard:.3g})' if small and yard is not None else ''}; "
+             f"ratios {e_gpu.max() / o_max if o_max else np.inf:.3f} "
+             f"{e_gpu.mean() / o_mean if o_mean else np.inf:.3f}; |gpu-oracle| max {worst:.3g}")
     print(stats)
     if not np.isfinite(err).all():
         fails.append(f"non-finite pixel: {stats}")
     if not worst <= 2e-4:
         fails.append(f"beyond 2e-4 of the oracle's error image: {stats}")
-    if not e_gpu.max() <= PIX_MAX * e_orc.max():
+    if not e_gpu.max() <= PIX_MAX * o_max:
         fails.append(f"worst pixel: {stats}")
-    if not e_gpu.mean() <= PIX_MEAN * e_orc.mean():
+    if not small and not e_gpu.mean() <= PIX_MEAN * o_mean:
         fails.append(f"mean: {stats}")
 
 
