@@ -28,6 +28,7 @@ HQ_WP_D50, HQ_WP_D65 = 0, 1
 _f = C.POINTER(C.c_float)
 _d = C.POINTER(C.c_double)
 _i32 = C.POINTER(C.c_int32)
+_i64 = C.POINTER(C.c_int64)
 _u8 = C.POINTER(C.c_uint8)
 _ctx = C.c_void_p
 
@@ -64,6 +65,10 @@ SIGNATURES = {
     "hq_get_indices": (C.c_int, [_ctx, C.c_int, _u8]),
     "hq_get_indices32": (C.c_int, [_ctx, C.c_int, C.POINTER(C.c_uint32)]),
     "hq_get_pixel_errors": (C.c_int, [_ctx, C.c_int, _f]),
+    "hq_cluster_sums": (C.c_int, [_ctx, C.c_int, C.c_int, _i64, _i64]),
+    "hq_centroids_from_sums": (C.c_int, [_i64, C.c_int64, C.c_int, C.c_int, _f]),
+    "hq_refine_population": (C.c_int, [_ctx, _f, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _d,
+                                       _i32, _d]),
     "hq_quantize": (C.c_int, [_ctx, _f, C.c_int64, _f, C.c_int, _f, _i32]),
     "hq_compute_error": (C.c_int, [_ctx, _f, _f, C.c_int64, _f, _d]),
     "hq_comm_unique_id": (C.c_int, [C.POINTER(C.c_ubyte)]),
@@ -131,6 +136,10 @@ def dptr(a):
 
 def iptr(a):
     return a.ctypes.data_as(_i32)
+
+
+def i64ptr(a):
+    return a.ctypes.data_as(_i64)
 
 
 def u8ptr(a):

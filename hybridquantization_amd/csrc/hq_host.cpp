@@ -317,3 +317,22 @@ extern "C" int hq_swasa_search_host(const hq_swasa_params* params, int K, uint64
     if (trace) std::copy(tr.begin(), tr.end(), trace);
     return HQ_OK;
 }
+
+// The k-means update (libhq's addition, no reference counterpart): every colour
+// that has pixels becomes their mean, from the exact integer sums of
+// hq_cluster_sums in units of 1/den; a colour without pixels keeps its bits.
+extern "C" int hq_centroids_from_sums(const int64_t* sums, int64_t den, int P, int K, float* palettes) {
+    if (!sums || !palettes || P < 1 || K < 1) return HQ_ERR_ARG;
+    const bool bytes = den == 255;
+    if (!bytes && den != ((int64_t)1 << 32)) return HQ_ERR_ARG;
+    for (size_t i = 0, n = (size_t)P * K; i < n; ++i) {
+        const int64_t* s = sums + 4 * i;
+        if (s[3] <= 0) continue;
+        const double count = (double)s[3];
+        float* c = palettes + 4 * i;
+        for (int ch = 0; ch < 3; ++ch)
+            c[ch] = bytes ? (float)((double)s[ch] / (255.0 * count)) : (float)(std::ldexp((double)s[ch], -32) / count);
+        c[3] = 0.0f;
+    }
+    return HQ_OK;
+}

@@ -252,6 +252,31 @@ struct WideArgs {
     int K;
 };
 
+// Per-colour pixel sums of the last evaluated population (hq_centroid.hip): the
+// k-means half the argmin leaves open.  A workgroup covers at most
+// cent_max_span pixels, which bounds its LDS accumulators (the bound is worked
+// out there).
+constexpr int kCentLdsK = kMaxK;          // K up to here (the u8 index images): accumulators in LDS;
+                                          // above: global atomics straight away
+constexpr int kCentBlocksPerCu = 4;       // workgroups per CU over all palette groups
+// pixels per workgroup, at most: the packed form (32-bit fields of byte sums), the planar form
+// (a 16-bit count above a 48-bit sum of values up to 2^32)
+__host__ __device__ constexpr uint32_t cent_max_span(bool u8) { return u8 ? 1u << 22 : 1u << 15; }
+struct ClusterArgs {
+    const void* idx;        // [P][idx_pitch] index images over the extended rows: u8, u16 or u32
+    const float* R;         // planar, extended rows (padded to a multiple of 4 floats)
+    const float* G;
+    const float* B;
+    const uint32_t* rgbx;   // packed 8-bit R,G,B (AssignArgs::rgbx), else null
+    unsigned long long* sums;  // [P][K][4] sum R, sum G, sum B, count (zeroed before the launch)
+    int* bad;               // planar form: set to 1 by an owned pixel that is not in [0, 1]
+    int64_t idx_pitch;      // elements per palette
+    uint32_t q0, q1;        // the owned rows: positions [q0, q1) of the extended rows
+    int P, K;
+    int nblocks;            // workgroups per group of 4 palettes   } set by the
+    uint32_t qspan;         // quads of 4 pixels per workgroup      } launcher
+};
+
 // Generic two-pass path (any half-width), one palette per launch.
 struct GenArgs {
     const void* idx;         // palette's index image (extended rows): u8, or u32 for K > 256

@@ -82,8 +82,8 @@ struct ProfSlot {
 
 // Profiling events per evaluation / search iteration: start, stop of grid (0,
 // 1), assign (2, 3), cost (4, 5), finalize (6, 7), sa_step (8, 9) and the
-// collective (10, 11).
-constexpr int kProfEvents = 12;
+// collective (10, 11), and of hq_cluster_sums' centroid kernel (12, 13).
+constexpr int kProfEvents = 14;
 
 }  // namespace
 
@@ -132,6 +132,10 @@ struct hq_ctx {
     double* h_out = nullptr;  // pinned [P][1+K]
     size_t h_pal_bytes = 0, h_out_bytes = 0;
     int last_P = 0;
+    // hq_cluster_sums: the index images on the device are those of a population of last_P x
+    // K_cur evaluated by hq_eval_population[_partial] (a search run or a new image unsets it)
+    bool sums_ok = false;
+    DevBuf d_sums;             // [P][K][4] int64 sums, then the planar form's range flag
 
     // options
     int G2 = 32;           // argmin grid resolution (0 = exhaustive)
@@ -177,7 +181,7 @@ struct hq_ctx {
 
     // profiling
     bool prof = false;
-    ProfSlot prof_assign, prof_cost, prof_grid, prof_finalize, prof_sa, prof_comm;
+    ProfSlot prof_assign, prof_cost, prof_grid, prof_finalize, prof_sa, prof_comm, prof_centroid;
     // profiling: start/stop of grid, assign, cost, finalize, [sa_step], the collective
     hipEvent_t ev[kProfEvents] = {};
     int num_cu = 256;
@@ -344,6 +348,7 @@ int set_image_common(hq_ctx* c, const std::vector<float>& R, const std::vector<f
         if (!c->img_u8) c->d_rgbx.release();
     }
     if (illum) std::memcpy(c->illum, illum, sizeof c->illum);
+    c->sums_ok = false;  // (the index images of the last evaluation belong to the old image)
     const int own = g.r1 - g.r0;
     const size_t lplane = sizeof(float) * (size_t)g.lab_pitch * std::max(own, 1);
     HIP_TRY(c, c->d_labL.ensure(lplane));
@@ -904,7 +909,56 @@ int eval_partial_into_hout(hq_ctx* c, const float* palettes, int P, int K) {
     }
     c->pal_generic = false;  // device-resident searches generate clamped palettes
     c->nch_cur = 1;
+    c->sums_ok = rc == HQ_OK;
     return rc;
+}
+
+// hq_cluster_sums into `out` ([P][K][4]); nothing is written unless HQ_OK.
+int cluster_sums(hq_ctx* c, int P, int K, int64_t* out, int64_t* den) {
+    if (!c->have_image || !c->sums_ok)
+        return fail(c, HQ_ERR_STATE, "no population evaluated by hq_eval_population[_partial] on this image "
+                                     "since the last search run");
+    if (P != c->last_P || K != c->K_cur)
+        return fail(c, HQ_ERR_STATE, "P=%d, K=%d: the last evaluation had P=%d, K=%d", P, K, c->last_P, c->K_cur);
+    if (c->slice_n != c->last_P || c->slice_ranks > 1 || (c->psplit && c->comm))
+        return fail(c, HQ_ERR_UNSUPPORTED, "palette slice: this device holds %d of the %d index images",
+                    c->slice_n, c->last_P);
+    int rc = bind(c);
+    if (rc) return rc;
+    const Geom& g = c->g;
+    hipStream_t s = c->stream;
+    const size_t n4 = (size_t)P * K * 4;
+    HIP_TRY(c, c->d_sums.ensure(sizeof(int64_t) * (n4 + 1)));
+    HIP_TRY(c, hipMemsetAsync(c->d_sums.p, 0, sizeof(int64_t) * (n4 + 1), s));
+    // the owned rows of the index images, as hq_get_indices[32] reads them
+    ClusterArgs ca{};
+    const int idx_bytes = c->last_nch > 1 ? 2 : K > kMaxK ? 4 : 1;
+    ca.idx = idx_bytes == 2 ? c->d_idx16.p : idx_bytes == 4 ? c->d_idx32.p : c->d_idx.p;
+    ca.R = c->d_R.as<float>();
+    ca.G = c->d_G.as<float>();
+    ca.B = c->d_B.as<float>();
+    const bool u8 = c->img_u8 && c->img_u8_path;  // (assign's condition)
+    ca.rgbx = u8 ? c->d_rgbx.as<uint32_t>() : nullptr;
+    ca.sums = c->d_sums.as<unsigned long long>();
+    ca.bad = reinterpret_cast<int*>(c->d_sums.as<int64_t>() + n4);
+    ca.idx_pitch = g.idx_pitch;
+    ca.q0 = (uint32_t)((int64_t)(g.r0 - g.e0) * g.W);
+    ca.q1 = ca.q0 + (uint32_t)((int64_t)g.W * (g.r1 - g.r0));
+    ca.P = P;
+    ca.K = K;
+    if (c->prof) set_launch_events(c->ev[12], c->ev[13]);
+    const hipError_t e = launch_cluster_sums(ca, idx_bytes, c->num_cu, s);
+    set_launch_events(nullptr, nullptr);
+    HIP_TRY(c, e);
+    std::vector<int64_t> h(n4 + 1);
+    HIP_TRY(c, hipMemcpyAsync(h.data(), c->d_sums.p, sizeof(int64_t) * (n4 + 1), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (c->prof) prof_add(c, c->prof_centroid, c->ev[12], c->ev[13]);
+    if (h[n4] != 0)
+        return fail(c, HQ_ERR_UNSUPPORTED, "planar image with a pixel outside [0, 1] or not finite: no exact sums");
+    std::memcpy(out, h.data(), sizeof(int64_t) * n4);
+    *den = u8 ? 255 : (int64_t)1 << 32;
+    return HQ_OK;
 }
 
 }  // namespace
@@ -1190,7 +1244,7 @@ void hq_destroy(hq_ctx* c) {
                       &c->d_labL, &c->d_labA, &c->d_labB, &c->d_pal_in, &c->d_pal, &c->d_opp, &c->d_opp16,
                       &c->d_dup, &c->d_pflags, &c->d_lvl1, &c->d_lvl2, &c->d_idx,
                       &c->d_used_mask, &c->d_acc, &c->d_out, &c->d_gen_t, &c->d_taps,
-                      &c->d_vfrag16, &c->d_vfrag16p, &c->d_vfragm, &c->d_htaps, &c->d_idx32, &c->d_used32, &c->d_pixerr, &c->d_idx16, &c->d_dist, &c->d_l1n, &c->d_l2n})
+                      &c->d_vfrag16, &c->d_vfrag16p, &c->d_vfragm, &c->d_htaps, &c->d_idx32, &c->d_used32, &c->d_pixerr, &c->d_idx16, &c->d_dist, &c->d_l1n, &c->d_l2n, &c->d_sums})
         b->release();
     if (c->h_pal) (void)hipHostFree(c->h_pal);
     if (c->h_out) (void)hipHostFree(c->h_out);
@@ -1263,6 +1317,7 @@ int hq_set_filters(hq_ctx* c, int taps, const float* k1, const float* k2, const 
         HIP_TRY(c, c->d_taps.upload(tb.data(), tb.size()));
     }
     c->have_image = false;  // halo depends on the filters
+    c->sums_ok = false;
     return HQ_OK;
 }
 
@@ -1415,6 +1470,58 @@ int hq_get_pixel_errors(hq_ctx* c, int p, float* err) {
     const int64_t n_own = (int64_t)c->g.W * (c->g.r1 - c->g.r0);
     HIP_TRY(c, hipMemcpy(err, c->d_pixerr.as<float>() + (int64_t)p * n_own, sizeof(float) * n_own,
                          hipMemcpyDeviceToHost));
+    return HQ_OK;
+}
+
+int hq_cluster_sums(hq_ctx* c, int P, int K, int64_t* sums, int64_t* den) {
+    if (!c) return HQ_ERR_ARG;
+    if (!sums || !den || P < 1 || K < 1) return fail(c, HQ_ERR_ARG, "bad sums / den / P=%d / K=%d", P, K);
+    return cluster_sums(c, P, K, sums, den);
+}
+
+int hq_refine_population(hq_ctx* c, float* palettes, int P, int K, int steps, float delta, int keep_best,
+                         double* costs, int32_t* used, double* trace) {
+    if (!costs) return fail(c, HQ_ERR_ARG, "null output");
+    int rc = check_eval_args(c, palettes, P, K);
+    if (rc) return rc;
+    if (steps < 0) return fail(c, HQ_ERR_ARG, "steps=%d < 0", steps);
+    if (c->comm && c->nranks > 1)
+        return fail(c, HQ_ERR_UNSUPPORTED, "hq_refine_population with a communicator of %d ranks: add the "
+                                           "shards' hq_cluster_sums yourself", c->nranks);
+    if (c->slice_ranks > 1) return fail(c, HQ_ERR_UNSUPPORTED, "hq_refine_population on a palette slice");
+    if (c->g.r0 != 0 || c->g.r1 != c->g.H)
+        return fail(c, HQ_ERR_STATE, "sharded context: hq_refine_population needs the whole image");
+    const size_t n4 = (size_t)P * K * 4, nu = (size_t)P * K;
+    std::vector<float> cur(palettes, palettes + n4), best_pal;
+    std::vector<double> cst(P), best_cost;
+    std::vector<int32_t> usd(nu), best_used;
+    std::vector<int64_t> sums(n4);
+    if ((rc = hq_eval_population(c, cur.data(), P, K, delta, cst.data(), usd.data()))) return rc;
+    if (trace) std::copy(cst.begin(), cst.end(), trace);
+    if (keep_best) best_pal = cur, best_cost = cst, best_used = usd;
+    for (int s = 1; s <= steps; ++s) {
+        int64_t den = 0;
+        if ((rc = cluster_sums(c, P, K, sums.data(), &den))) return rc;
+        if ((rc = hq_centroids_from_sums(sums.data(), den, P, K, cur.data())))
+            return fail(c, rc, "hq_centroids_from_sums failed");
+        if ((rc = hq_eval_population(c, cur.data(), P, K, delta, cst.data(), usd.data()))) return rc;
+        if (trace) std::copy(cst.begin(), cst.end(), trace + (size_t)s * P);
+        for (int p = 0; keep_best && p < P; ++p) {
+            // strictly lower (the earliest step keeps a tie); a number beats a NaN, never the reverse
+            const double a = cst[p], b = best_cost[p];
+            if (!(a < b || (b != b && a == a))) continue;
+            best_cost[p] = a;
+            std::copy(cur.begin() + (size_t)p * K * 4, cur.begin() + (size_t)(p + 1) * K * 4,
+                      best_pal.begin() + (size_t)p * K * 4);
+            std::copy(usd.begin() + (size_t)p * K, usd.begin() + (size_t)(p + 1) * K, best_used.begin() + (size_t)p * K);
+        }
+    }
+    const std::vector<float>& rp = keep_best ? best_pal : cur;
+    const std::vector<double>& rc_ = keep_best ? best_cost : cst;
+    const std::vector<int32_t>& ru = keep_best ? best_used : usd;
+    std::copy(rp.begin(), rp.end(), palettes);
+    std::copy(rc_.begin(), rc_.end(), costs);
+    if (used) std::copy(ru.begin(), ru.end(), used);
     return HQ_OK;
 }
 
@@ -1593,6 +1700,7 @@ int hq_search_create(hq_ctx* c, const hq_swasa_params* params, int K, uint64_t s
         s->driver = new SearchDriver(*params, K, seed, eval);
         rc = s->driver->start();
     }
+    c->sums_ok = false;  // (the search's own evaluations replace the index images)
     if (rc) {
         hq_search_destroy(s);
         return rc;
@@ -1603,11 +1711,15 @@ int hq_search_create(hq_ctx* c, const hq_swasa_params* params, int K, uint64_t s
 
 int hq_search_run(hq_search* s, int iterations, int* ran) {
     if (!s || iterations < 0) return HQ_ERR_ARG;
+    int rc;
     if (!s->driver) {
-        int rc = bind(s->ctx);
-        return rc ? rc : device_search_run(s, iterations, ran);
+        rc = bind(s->ctx);
+        if (!rc) rc = device_search_run(s, iterations, ran);
+    } else {
+        rc = s->driver->run(iterations, ran, nullptr);
     }
-    return s->driver->run(iterations, ran, nullptr);
+    if (s->ctx) s->ctx->sums_ok = false;  // (hq_cluster_sums: a search run has evaluated since)
+    return rc;
 }
 
 int hq_search_best(const hq_search* s, float* colors, double* best_error, int* iteration) {
@@ -1654,7 +1766,8 @@ int hq_profile_enable(hq_ctx* c, int on) {
 
 int hq_profile_reset(hq_ctx* c) {
     if (!c) return HQ_ERR_ARG;
-    c->prof_assign = c->prof_cost = c->prof_grid = c->prof_finalize = c->prof_sa = c->prof_comm = ProfSlot{};
+    c->prof_assign = c->prof_cost = c->prof_grid = c->prof_finalize = c->prof_sa = c->prof_comm = c->prof_centroid =
+        ProfSlot{};
     return HQ_OK;
 }
 
@@ -1667,6 +1780,7 @@ int hq_profile_get(hq_ctx* c, const char* kernel, double* total_ms, int64_t* lau
     else if (!std::strcmp(kernel, "finalize")) s = &c->prof_finalize;
     else if (!std::strcmp(kernel, "sa_step")) s = &c->prof_sa;
     else if (!std::strcmp(kernel, "comm")) s = &c->prof_comm;
+    else if (!std::strcmp(kernel, "centroid")) s = &c->prof_centroid;
     else return fail(c, HQ_ERR_ARG, "unknown kernel '%s'", kernel);
     if (total_ms) *total_ms = s->ms;
     if (launches) *launches = s->launches;

@@ -166,14 +166,54 @@ class ImageManipulation:
         check(self._lib.hq_get_indices32(ctx, int(p), out.ctypes.data_as(C.POINTER(C.c_uint32))), ctx)
         return out
 
+    # k-means refinement: libhq's additions (hq_cluster_sums & co., no reference counterpart)
+    def clusterSums(self, P: int, K: int):
+        """Per palette and colour of the last evaluated population: the exact sum of the
+        assigned pixels over the owned rows and their count -> (sums int64 (P, K, 4)
+        = (sum R, sum G, sum B, count) in units of 1/den, den = 255 or 2**32)."""
+        ctx = self._require()
+        sums = np.zeros((int(P), int(K), 4), np.int64)
+        den = C.c_int64()
+        check(self._lib.hq_cluster_sums(ctx, int(P), int(K), _lib.i64ptr(sums), C.byref(den)), ctx)
+        return sums, den.value
+
+    @staticmethod
+    def centroidsFromSums(sums, den, palettes):
+        """The k-means update of hq_centroids_from_sums: palettes (P, 4K) float32 with
+        every colour that has pixels replaced by their mean (.w = 0); the others keep
+        their bits.  Returns a new array."""
+        sums = np.ascontiguousarray(sums, dtype=np.int64)
+        P, K = sums.shape[0], sums.shape[1]
+        pal = _f32(palettes).reshape(P, 4 * K).copy()
+        check(load().hq_centroids_from_sums(_lib.i64ptr(sums), int(den), P, K, fptr(pal)))
+        return pal
+
+    def refinePopulation(self, colors, steps, delta: float = 2.0, keep_best=True, return_trace=False):
+        """hq_refine_population: `steps` k-means steps on each palette of colors (P, 4K).
+        Returns (palettes (P, 4K), costs (P,), used (P, K)) [, trace (steps + 1, P)]."""
+        ctx = self._require()
+        pal = _f32(np.stack([np.asarray(c, np.float32).reshape(-1) for c in colors])).copy()
+        P, K = pal.shape[0], pal.shape[1] // 4
+        costs = np.zeros(P, np.float64)
+        used = np.zeros((P, K), np.int32)
+        trace = np.zeros((int(steps) + 1, P), np.float64)
+        check(self._lib.hq_refine_population(ctx, fptr(pal), P, K, int(steps), float(delta),
+                                             int(bool(keep_best)), dptr(costs), iptr(used),
+                                             dptr(trace)), ctx)
+        return (pal, costs, used, trace) if return_trace else (pal, costs, used)
+
     # IM:383
     def findBestQuantization(self, inlinergbOriginal, inlineScielabOriginal, w, nbOfColors,
                              simulatedAnnealing, filters, absfilters, illuminant,
-                             iterations=None, stop=None):
+                             iterations=None, stop=None, lloydSteps=0):
         """Full SWASA search (IM:383-591) on the GPU; returns bestColors float[4K].
 
         ``simulatedAnnealing`` is a :class:`~hybridquantization_amd.swasa.SWASA`;
         ``stop`` is an optional callable polled between chunks (IM:499).
+        ``lloydSteps`` > 0 (libhq's addition, the k-means half of the hybrid method):
+        the best palette is then polished by that many k-means steps, keeping the
+        lowest-cost step (hq_refine_population, keep_best); ``bestError`` and the
+        returned colours are the polished ones, ``bestErrorSA`` the search's own.
         """
         ctx = self._require()
         if not self.openCLFiltersReady:
@@ -207,9 +247,16 @@ class ImageManipulation:
             self.iterations = it.value
             if self.verbose:
                 print("Final error : %.5f" % err.value)  # IM:589
-            return best
         finally:
             self._lib.hq_search_destroy(handle)
+        if int(lloydSteps) > 0:
+            self.bestErrorSA = self.bestError
+            pal, costs, _ = self.refinePopulation(best.reshape(1, -1), int(lloydSteps), sw.delta,
+                                                  keep_best=True)
+            best, self.bestError = pal[0], float(costs[0])
+            if self.verbose:
+                print("Final error after %d k-means steps : %.5f" % (int(lloydSteps), self.bestError))
+        return best
 
     # IM:770
     def quantize(self, inlineImageRGB, colors):

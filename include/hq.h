@@ -154,6 +154,51 @@ int hq_get_indices32(hq_ctx *ctx, int p, uint32_t *idx);
  * otherwise. */
 int hq_get_pixel_errors(hq_ctx *ctx, int p, float *err);
 
+/* ---- k-means palette refinement: libhq's additions, no reference counterpart ----
+ * The plugin implements Schaefer & Nolle's hybrid quantization, of which the
+ * reference holds the simulated-annealing half only.  A k-means step replaces
+ * each palette colour by the mean of the pixels assigned to it; the assignment
+ * is the evaluation's argmin (the index images stay on the device), the three
+ * entry points below add the means.
+ *
+ * hq_cluster_sums: per palette and colour of the population last evaluated by
+ * hq_eval_population or hq_eval_population_partial on this context, the sum of
+ * the assigned pixels and their count over the owned rows (halo rows are not
+ * counted): sums[((p*K)+k)*4 + {0,1,2,3}] = (sum R, sum G, sum B, count), exact
+ * integers in units of 1 / *den.  *den = 255 when the evaluation's argmin read
+ * the packed 8-bit copy of a k/255 image (sums of the bytes), else 2^32: each
+ * channel value v adds llrint(v * 2^32) (round half to even; exact for every
+ * float in [2^-9, 1], the nearest multiple of 2^-32 below).  Option "img_u8" 0
+ * gives 2^32 on every image.  The sums of disjoint shards of one image add up
+ * exactly to the whole image's when their den agree.  Every argmin path and
+ * index width is served (K <= 256, chunked palettes, K > 16384, "grid" 0).
+ * HQ_ERR_STATE: no population evaluated yet, P or K other than that
+ * evaluation's, or a search run has evaluated since.  HQ_ERR_UNSUPPORTED: a
+ * palette slice ("slice_ranks" > 1, "palette_split"), or (den 2^32) a pixel of
+ * the owned rows that is not finite or lies outside [0, 1] -- sums and den are
+ * then left untouched.  With at most 2^30 pixels per shard no sum overflows. */
+int hq_cluster_sums(hq_ctx *ctx, int P, int K, int64_t *sums, int64_t *den);
+/* The k-means update from such sums (of one context, or several shards' added
+ * up).  Host-only, needs no context.  Every colour with count > 0 becomes the
+ * mean of its pixels, channel c = (float)((double)sum_c / (255.0 * (double)count))
+ * for den = 255, (float)(ldexp((double)sum_c, -32) / (double)count) for
+ * den = 2^32, and .w = 0.  A colour with count 0 keeps its bits: a duplicate at
+ * a higher index, a colour no pixel is nearest to, a non-finite colour.  Any
+ * other den: HQ_ERR_ARG. */
+int hq_centroids_from_sums(const int64_t *sums, int64_t den, int P, int K, float *palettes);
+/* Evaluates the P palettes, then `steps` times: hq_cluster_sums, the update
+ * above, an evaluation of the updated palettes.  trace (may be NULL) receives
+ * the costs of step 0 (the input) to step `steps`, trace[s*P + p].  keep_best 0:
+ * palettes, costs and used are those of the last step.  keep_best 1: per
+ * palette those of its lowest-cost step, the earliest on a tie; a NaN cost
+ * never beats a number.  k-means lowers the RGB distortion while the cost is
+ * S-CIELAB dE plus delta per unused colour, so the cost can rise: keep_best 1
+ * refuses that.  steps = 0 is hq_eval_population.  used may be NULL.  Needs
+ * the whole image on this context (HQ_ERR_STATE on a shard) and no
+ * communicator of more than one rank (HQ_ERR_UNSUPPORTED). */
+int hq_refine_population(hq_ctx *ctx, float *palettes, int P, int K, int steps, float delta,
+                         int keep_best, double *costs, int32_t *used, double *trace);
+
 /* IM:770 quantize(inlineImageRGB, colors): chosen colour per pixel (CL:147-170).
  * used (K ints) may be NULL. */
 int hq_quantize(hq_ctx *ctx, const float *rgba4, int64_t n, const float *colors, int K,
@@ -214,7 +259,8 @@ int hq_swasa_search_host(const hq_swasa_params *params, int K, uint64_t seed, in
  * context stream while enabled (bench.py roofline). */
 int hq_profile_enable(hq_ctx *ctx, int on);
 /* names: "assign", "cost", "grid", "finalize", "sa_step" (device-resident search), "comm" (the
- * per-evaluation RCCL all-reduce or all-gather, with a communicator); returns total ms and launch
+ * per-evaluation RCCL all-reduce or all-gather, with a communicator), "centroid"
+ * (hq_cluster_sums' kernel); returns total ms and launch
  * count (HIP events on the context stream). */
 int hq_profile_get(hq_ctx *ctx, const char *kernel, double *total_ms, int64_t *launches);
 int hq_profile_reset(hq_ctx *ctx);
