@@ -41,6 +41,7 @@ class hq_swasa_params(C.Structure):
 
 
 EVAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, _f, C.c_int, C.c_int, _d)
+REFINE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, _f, C.c_int, C.c_int)
 
 # name -> (restype, argtypes); the exported surface of include/hq.h
 SIGNATURES = {
@@ -80,8 +81,11 @@ SIGNATURES = {
     "hq_search_run": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "hq_search_best": (C.c_int, [C.c_void_p, _f, _d, C.POINTER(C.c_int)]),
     "hq_search_destroy": (None, [C.c_void_p]),
+    "hq_search_set_lloyd": (C.c_int, [C.c_void_p, C.c_int]),
     "hq_swasa_search_host": (C.c_int, [C.POINTER(hq_swasa_params), C.c_int, C.c_uint64,
                                        C.c_int, EVAL_FN, C.c_void_p, _f, _d, _d]),
+    "hq_swasa_search_host_lloyd": (C.c_int, [C.POINTER(hq_swasa_params), C.c_int, C.c_uint64,
+                                             C.c_int, EVAL_FN, REFINE_FN, C.c_int, C.c_void_p, _f, _d, _d]),
     "hq_profile_enable": (C.c_int, [_ctx, C.c_int]),
     "hq_profile_get": (C.c_int, [_ctx, C.c_char_p, _d, C.POINTER(C.c_int64)]),
     "hq_profile_reset": (C.c_int, [_ctx]),

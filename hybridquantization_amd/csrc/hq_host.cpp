@@ -12,6 +12,7 @@
 #include <limits>
 #include <vector>
 
+#include "hq_lloyd.h"
 #include "hq_swasa.h"
 
 namespace {
@@ -265,6 +266,10 @@ int SearchDriver::run(int iterations, int* ran, std::vector<double>* trace) {
         sw_.reduce_temperature_if_necessary(ite);                     // IM:507
         for (int j = 0; j < P_; ++j)                                  // IM:508-511
             sw_.generate_neighboring_colors(&colors_[(size_t)j * n], &current_[(size_t)j * n], K_, ite);
+        if (every_ > 0 && refine_ && ite % every_ == 0) {             // hybrid iteration: one k-means move
+            const int rr = refine_(current_.data(), P_, K_);
+            if (rr) { if (ran) *ran = done; return rr; }
+        }
         int rc = eval_(current_.data(), P_, K_, errors_.data());      // IM:515
         if (rc) { if (ran) *ran = done; return rc; }
         double minerror = std::numeric_limits<double>::max();
@@ -297,15 +302,20 @@ int SearchDriver::run(int iterations, int* ran, std::vector<double>* trace) {
 
 }  // namespace hq
 
-extern "C" int hq_swasa_search_host(const hq_swasa_params* params, int K, uint64_t seed,
-                                    int iterations, hq_eval_fn eval, void* user,
-                                    float* best_colors, double* best_error, double* trace) {
+extern "C" int hq_swasa_search_host_lloyd(const hq_swasa_params* params, int K, uint64_t seed,
+                                          int iterations, hq_eval_fn eval, hq_refine_fn refine, int every,
+                                          void* user, float* best_colors, double* best_error,
+                                          double* trace) {
     if (!params || !eval || K < 1 || params->population < 1 || params->imax < 1 ||
-        params->iTc < 1)
+        params->iTc < 1 || every < 0)
         return HQ_ERR_ARG;
     hq::SearchDriver d(*params, K, seed, [&](const float* pal, int P, int KK, double* costs) {
         return eval(user, pal, P, KK, costs) ? HQ_ERR_ARG : HQ_OK;
     });
+    if (refine && every > 0) {
+        d.set_refine([&](float* pal, int P, int KK) { return refine(user, pal, P, KK); });
+        d.set_every(every);
+    }
     int rc = d.start();
     if (rc) return rc;
     std::vector<double> tr;
@@ -318,6 +328,13 @@ extern "C" int hq_swasa_search_host(const hq_swasa_params* params, int K, uint64
     return HQ_OK;
 }
 
+extern "C" int hq_swasa_search_host(const hq_swasa_params* params, int K, uint64_t seed,
+                                    int iterations, hq_eval_fn eval, void* user,
+                                    float* best_colors, double* best_error, double* trace) {
+    return hq_swasa_search_host_lloyd(params, K, seed, iterations, eval, nullptr, 0, user, best_colors,
+                                      best_error, trace);
+}
+
 // The k-means update (libhq's addition, no reference counterpart): every colour
 // that has pixels becomes their mean, from the exact integer sums of
 // hq_cluster_sums in units of 1/den; a colour without pixels keeps its bits.
@@ -328,10 +345,9 @@ extern "C" int hq_centroids_from_sums(const int64_t* sums, int64_t den, int P, i
     for (size_t i = 0, n = (size_t)P * K; i < n; ++i) {
         const int64_t* s = sums + 4 * i;
         if (s[3] <= 0) continue;
-        const double count = (double)s[3];
         float* c = palettes + 4 * i;
         for (int ch = 0; ch < 3; ++ch)
-            c[ch] = bytes ? (float)((double)s[ch] / (255.0 * count)) : (float)(std::ldexp((double)s[ch], -32) / count);
+            c[ch] = hq::lloyd_mean(s[ch], s[3], bytes);
         c[3] = 0.0f;
     }
     return HQ_OK;

@@ -277,6 +277,19 @@ struct ClusterArgs {
     uint32_t qspan;         // quads of 4 pixels per workgroup      } launcher
 };
 
+// lloyd_update_kernel (hq_search.hip): the k-means move of a device-resident
+// hybrid iteration.  Candidate colour k of palette p with count > 0 becomes the
+// mean of its pixels (lloyd_mean, hq_lloyd.h), in place; the palette is
+// prepared again (prep's outputs) and the sums it read are zeroed for the next
+// hybrid iteration.
+struct LloydArgs {
+    unsigned long long* sums;  // [P][K][4] ClusterArgs::sums of the assign-only pass
+    float* cand;               // [P][4K] the search's candidates (the next sa_step's cand_in)
+    PaletteArgs prep;          // outputs of the palette prep of the updated candidates
+    int K;
+    int bytes;                 // sums in units of 1/255 (the packed image), else 2^-32
+};
+
 // Generic two-pass path (any half-width), one palette per launch.
 struct GenArgs {
     const void* idx;         // palette's index image (extended rows): u8, or u32 for K > 256

@@ -92,6 +92,7 @@ bool allow_dyn_lds(const void* fn, size_t bytes);
 // hq_search.hip
 hipError_t launch_prep_palette(const PaletteArgs&, int P, hipStream_t);
 hipError_t launch_sa_step(const SaArgs&, hipStream_t);
+hipError_t launch_lloyd_update(const LloydArgs&, int P, hipStream_t);
 hipError_t launch_build_grid(const GridArgs&, int P, hipStream_t);
 hipError_t launch_finalize(const FinalizeArgs&, int P, hipStream_t);
 // hq_assign.hip

@@ -84,6 +84,11 @@ struct ProfSlot {
 // 1), assign (2, 3), cost (4, 5), finalize (6, 7), sa_step (8, 9) and the
 // collective (10, 11), and of hq_cluster_sums' centroid kernel (12, 13).
 constexpr int kProfEvents = 14;
+// A search iteration has those and, when it is a hybrid iteration, the pairs of
+// its assign-only pass (grid 14, 15; assign 16, 17: enqueue_core's slots 0 .. 3
+// shifted by kProfLloyd), the sums kernel (18, 19) and the update kernel (20, 21).
+constexpr int kProfLloyd = kProfEvents;
+constexpr int kProfSearchEvents = kProfLloyd + 8;
 
 }  // namespace
 
@@ -136,6 +141,9 @@ struct hq_ctx {
     // K_cur evaluated by hq_eval_population[_partial] (a search run or a new image unsets it)
     bool sums_ok = false;
     DevBuf d_sums;             // [P][K][4] int64 sums, then the planar form's range flag
+    // hybrid iterations: every owned pixel of the planar image is finite and in [0, 1], the
+    // condition of the planar form's sums (-1: not established yet for this image)
+    int planar_ok = -1;
 
     // options
     int G2 = 32;           // argmin grid resolution (0 = exhaustive)
@@ -181,7 +189,7 @@ struct hq_ctx {
 
     // profiling
     bool prof = false;
-    ProfSlot prof_assign, prof_cost, prof_grid, prof_finalize, prof_sa, prof_comm, prof_centroid;
+    ProfSlot prof_assign, prof_cost, prof_grid, prof_finalize, prof_sa, prof_comm, prof_centroid, prof_lloyd;
     // profiling: start/stop of grid, assign, cost, finalize, [sa_step], the collective
     hipEvent_t ev[kProfEvents] = {};
     int num_cu = 256;
@@ -199,13 +207,14 @@ struct hq_search {
     Swasa* pol = nullptr;
     hq_swasa_params prm{};
     int P = 0, ite = 0, st = 0, cd = 0;  // state and candidate buffer parities
+    int every = 0;                       // hq_search_set_lloyd: iteration ite % every == 0 is hybrid (0: none)
     int nch = 1;                         // chunked palettes (256 < K <= 16384): chunks per palette
     bool fold = false;                   // accept steps reduce the partials (no finalize launch)
     ncclComm_t comm = nullptr;           // the context's communicator at hq_search_create
     float t_acc = 0.f;                   // temperature / threshold of the iteration
     double keep_acc = 0.0;               // whose population awaits acceptance
     DevBuf colors[2], cand[2], err[2], seed[2], best_err[2], best_colors, jA, jC;
-    std::vector<hipEvent_t> pev;         // profiling: 8 events per iteration of a run
+    std::vector<hipEvent_t> pev;         // profiling: kProfSearchEvents events per iteration of a run
     hipGraphExec_t gexec = nullptr;      // option sa_graph: the last run's iteration chain
     int gexec_iters = 0;                 // (its iteration count: the topology an update must match)
 };
@@ -349,6 +358,7 @@ int set_image_common(hq_ctx* c, const std::vector<float>& R, const std::vector<f
     }
     if (illum) std::memcpy(c->illum, illum, sizeof c->illum);
     c->sums_ok = false;  // (the index images of the last evaluation belong to the old image)
+    c->planar_ok = -1;
     const int own = g.r1 - g.r0;
     const size_t lplane = sizeof(float) * (size_t)g.lab_pitch * std::max(own, 1);
     HIP_TRY(c, c->d_labL.ensure(lplane));
@@ -680,7 +690,13 @@ int palette_slice(hq_ctx* c, int P, int* lo, int* n) {
 
 // Each evaluation takes the other counter set than the last one (build_grid
 // zeroes it), so an accept step can read the last set while the next is filled.
-int enqueue_core(hq_ctx* c, int P, int K, const hipEvent_t* ev, bool fold = false) {
+// assign_only (a hybrid iteration's first pass): the argmin alone -- grid build
+// or zeroing, then assign -- for the index images the sums kernel reads; no
+// cost kernel, no finalize, no collective.  It fills the other set's used bits
+// without making that set the current one: c->acc_par stays the set of the
+// last full pass (what sa_args, the fold and the finalize read), and the full
+// pass that follows takes, and zeroes, the same set again.
+int enqueue_core(hq_ctx* c, int P, int K, const hipEvent_t* ev, bool fold = false, bool assign_only = false) {
     const Geom& g = c->g;
     hipStream_t s = c->stream;
     const int nch = c->nch_cur, Ks = nch > 1 ? kMaxK : K;
@@ -688,9 +704,14 @@ int enqueue_core(hq_ctx* c, int P, int K, const hipEvent_t* ev, bool fold = fals
     int lo = 0, Pl = P;
     if (int rc = palette_slice(c, P, &lo, &Pl)) return rc;
     const int Ps = Pl * nch, so = lo * nch;  // sub-palettes, the first one's index
-    if (Pl < P && !c->comm)  // test-only slice: the other palettes' rows read as zero
+    if (Pl < P && !c->comm && !assign_only)  // test-only slice: the other palettes' rows read as zero
         HIP_TRY(c, hipMemsetAsync(c->d_out.p, 0, sizeof(double) * (size_t)P * (1 + K), s));
     c->acc_par ^= 1;
+    struct ParRestore {  // assign_only: back to the last full pass's set on every way out
+        hq_ctx* c;
+        bool on;
+        ~ParRestore() { if (on) c->acc_par ^= 1; }
+    } restore{c, assign_only};
     const GridArgs ga = grid_args(c, Ps, Ks, so);
     auto timed = [&](int slot) {
         if (ev) set_launch_events(ev[2 * slot], ev[2 * slot + 1]);
@@ -761,6 +782,14 @@ int enqueue_core(hq_ctx* c, int P, int K, const hipEvent_t* ev, bool fold = fals
     hipError_t e = n16 ? launch_assign16(aa, Pl, s) : launch_assign(aa, Ps, s);
     untimed();
     HIP_TRY(c, e);
+    if (assign_only) {
+        c->slice_lo = lo;
+        c->slice_n = Pl;
+        c->last_P = P;
+        c->K_cur = K;
+        c->last_nch = nch;
+        return HQ_OK;
+    }
     if (fast) {
         timed(2);
         e = nch > 1 ? launch_cost_chunked(ca, Pl, nch, c->de_type, c->trim && c->trim_ok, s)
@@ -913,6 +942,32 @@ int eval_partial_into_hout(hq_ctx* c, const float* palettes, int P, int K) {
     return rc;
 }
 
+// The sums form assign's own condition picks: the packed bytes (den 255), else
+// the planar floats (den 2^32).
+bool sums_u8(const hq_ctx* c) { return c->img_u8 && c->img_u8_path; }
+
+// The sums kernel's arguments for the index images of the last evaluation (or
+// assign-only pass) of P palettes of K colours: the owned rows, as
+// hq_get_indices[32] reads them, into d_sums ([P][K][4], then the range flag).
+ClusterArgs cluster_args(hq_ctx* c, int P, int K, int* idx_bytes) {
+    const Geom& g = c->g;
+    ClusterArgs ca{};
+    *idx_bytes = c->last_nch > 1 ? 2 : K > kMaxK ? 4 : 1;
+    ca.idx = *idx_bytes == 2 ? c->d_idx16.p : *idx_bytes == 4 ? c->d_idx32.p : c->d_idx.p;
+    ca.R = c->d_R.as<float>();
+    ca.G = c->d_G.as<float>();
+    ca.B = c->d_B.as<float>();
+    ca.rgbx = sums_u8(c) ? c->d_rgbx.as<uint32_t>() : nullptr;
+    ca.sums = c->d_sums.as<unsigned long long>();
+    ca.bad = reinterpret_cast<int*>(c->d_sums.as<int64_t>() + (size_t)P * K * 4);
+    ca.idx_pitch = g.idx_pitch;
+    ca.q0 = (uint32_t)((int64_t)(g.r0 - g.e0) * g.W);
+    ca.q1 = ca.q0 + (uint32_t)((int64_t)g.W * (g.r1 - g.r0));
+    ca.P = P;
+    ca.K = K;
+    return ca;
+}
+
 // hq_cluster_sums into `out` ([P][K][4]); nothing is written unless HQ_OK.
 int cluster_sums(hq_ctx* c, int P, int K, int64_t* out, int64_t* den) {
     if (!c->have_image || !c->sums_ok)
@@ -925,27 +980,13 @@ int cluster_sums(hq_ctx* c, int P, int K, int64_t* out, int64_t* den) {
                     c->slice_n, c->last_P);
     int rc = bind(c);
     if (rc) return rc;
-    const Geom& g = c->g;
     hipStream_t s = c->stream;
     const size_t n4 = (size_t)P * K * 4;
     HIP_TRY(c, c->d_sums.ensure(sizeof(int64_t) * (n4 + 1)));
     HIP_TRY(c, hipMemsetAsync(c->d_sums.p, 0, sizeof(int64_t) * (n4 + 1), s));
-    // the owned rows of the index images, as hq_get_indices[32] reads them
-    ClusterArgs ca{};
-    const int idx_bytes = c->last_nch > 1 ? 2 : K > kMaxK ? 4 : 1;
-    ca.idx = idx_bytes == 2 ? c->d_idx16.p : idx_bytes == 4 ? c->d_idx32.p : c->d_idx.p;
-    ca.R = c->d_R.as<float>();
-    ca.G = c->d_G.as<float>();
-    ca.B = c->d_B.as<float>();
-    const bool u8 = c->img_u8 && c->img_u8_path;  // (assign's condition)
-    ca.rgbx = u8 ? c->d_rgbx.as<uint32_t>() : nullptr;
-    ca.sums = c->d_sums.as<unsigned long long>();
-    ca.bad = reinterpret_cast<int*>(c->d_sums.as<int64_t>() + n4);
-    ca.idx_pitch = g.idx_pitch;
-    ca.q0 = (uint32_t)((int64_t)(g.r0 - g.e0) * g.W);
-    ca.q1 = ca.q0 + (uint32_t)((int64_t)g.W * (g.r1 - g.r0));
-    ca.P = P;
-    ca.K = K;
+    int idx_bytes = 1;
+    const ClusterArgs ca = cluster_args(c, P, K, &idx_bytes);
+    const bool u8 = sums_u8(c);
     if (c->prof) set_launch_events(c->ev[12], c->ev[13]);
     const hipError_t e = launch_cluster_sums(ca, idx_bytes, c->num_cu, s);
     set_launch_events(nullptr, nullptr);
@@ -1042,6 +1083,82 @@ int ensure_events(hq_search* s, size_t n) {
     return HQ_OK;
 }
 
+// ---- hybrid iterations (hq_search_set_lloyd) -----------------------------------
+// The scope of a k-means move is hq_refine_population's: the whole image on
+// this context, every palette's index image here.
+int lloyd_scope(hq_search* s) {
+    hq_ctx* c = s->ctx;
+    if (c->have_image && (c->g.r0 != 0 || c->g.r1 != c->g.H))
+        return fail(c, HQ_ERR_STATE, "sharded context: a hybrid iteration needs the whole image");
+    if (c->comm && c->nranks > 1)
+        return fail(c, HQ_ERR_UNSUPPORTED, "hybrid iterations with a communicator of %d ranks", c->nranks);
+    if (c->psplit || c->slice_ranks > 1) return fail(c, HQ_ERR_UNSUPPORTED, "hybrid iterations on a palette slice");
+    if (!s->driver && s->nch > 1)
+        return fail(c, HQ_ERR_UNSUPPORTED, "hybrid iterations of a device-resident search need K <= %d (K = %d): "
+                                           "set option sa_device 0 before hq_search_create", kMaxK, s->K);
+    return HQ_OK;
+}
+
+// A run of `iterations` from iteration `ite` (the last one done) holds a hybrid iteration.
+bool lloyd_in_run(const hq_search* s, int ite, int iterations) {
+    if (s->every <= 0) return false;
+    const int last = (int)std::min<int64_t>((int64_t)ite + iterations, s->prm.imax);
+    return last / s->every > ite / s->every;
+}
+
+// The planar form's sums need every owned pixel finite and in [0, 1]: a property
+// of the image, established once per image by one launch of the sums kernel (one
+// palette of one colour over the first index image -- any u8 index addresses the
+// kernel's LDS table) and a read of its flag.
+int lloyd_validate(hq_search* s) {
+    hq_ctx* c = s->ctx;
+    if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
+    if (sums_u8(c)) return HQ_OK;
+    if (c->planar_ok < 0) {
+        int rc = bind(c);
+        if (rc) return rc;
+        hipStream_t st = c->stream;
+        HIP_TRY(c, c->d_idx.ensure((size_t)c->g.idx_pitch + 256));
+        HIP_TRY(c, c->d_sums.ensure(sizeof(int64_t) * (4 + 1)));
+        HIP_TRY(c, hipMemsetAsync(c->d_sums.p, 0, sizeof(int64_t) * (4 + 1), st));
+        int idx_bytes = 1;
+        ClusterArgs ca = cluster_args(c, 1, 1, &idx_bytes);
+        ca.idx = c->d_idx.p;  // (the u8 image, whatever the last evaluation's index width)
+        HIP_TRY(c, launch_cluster_sums(ca, 1, c->num_cu, st));
+        int bad = 1;
+        HIP_TRY(c, hipMemcpyAsync(&bad, ca.bad, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        c->planar_ok = bad == 0;
+    }
+    if (!c->planar_ok)
+        return fail(c, HQ_ERR_UNSUPPORTED, "planar image with a pixel outside [0, 1] or not finite: no exact sums, "
+                                           "no hybrid iteration");
+    return HQ_OK;
+}
+
+// The k-means move of a device-resident hybrid iteration, after the sa_step that
+// generated and prepared the candidates (now cand[cd]): the assign-only pass,
+// the sums kernel into d_sums (zero on entry: the run's memset, then the update
+// kernel's own zeroing) and the update kernel, which prepares the updated
+// candidates for the evaluation that follows.  ev: the iteration's events.
+int enqueue_lloyd(hq_search* s, const hipEvent_t* ev) {
+    hq_ctx* c = s->ctx;
+    int rc = enqueue_core(c, s->P, s->K, ev ? ev + kProfLloyd : nullptr, s->fold, true);
+    if (rc) return rc;
+    int idx_bytes = 1;
+    const ClusterArgs ca = cluster_args(c, s->P, s->K, &idx_bytes);
+    if (ev) set_launch_events(ev[kProfLloyd + 4], ev[kProfLloyd + 5]);
+    hipError_t e = launch_cluster_sums(ca, idx_bytes, c->num_cu, c->stream);
+    set_launch_events(nullptr, nullptr);
+    HIP_TRY(c, e);
+    const LloydArgs la{ca.sums, s->cand[s->cd].as<float>(), prep_args(c, s->K), s->K, sums_u8(c) ? 1 : 0};
+    if (ev) set_launch_events(ev[kProfLloyd + 6], ev[kProfLloyd + 7]);
+    e = launch_lloyd_update(la, s->P, c->stream);
+    set_launch_events(nullptr, nullptr);
+    HIP_TRY(c, e);
+    return HQ_OK;
+}
+
 int device_search_create(hq_ctx* c, const hq_swasa_params* params, int K, uint64_t seed, hq_search* s) {
     const int P = params->population;
     s->prm = *params;
@@ -1112,7 +1229,14 @@ int device_search_run(hq_search* s, int iterations, int* ran) {
         return fail(c, HQ_ERR_STATE, "communicator or palette split changed after hq_search_create: "
                                      "recreate the search");
     const bool prof = c->prof;
-    if (prof && (rc = ensure_events(s, (size_t)kProfEvents * iterations))) return rc;
+    if (prof && (rc = ensure_events(s, (size_t)kProfSearchEvents * iterations))) return rc;
+    // hybrid iterations in this run: the sums buffer before anything is enqueued
+    // (no allocation while a run is captured), zeroed once below -- the update
+    // kernel leaves it zero for the next hybrid iteration
+    const bool lloyd = lloyd_in_run(s, s->ite, iterations);
+    const size_t sums_bytes = sizeof(int64_t) * ((size_t)s->P * s->K * 4 + 1);
+    if (lloyd) HIP_TRY(c, c->d_sums.ensure(sums_bytes));
+    std::vector<char> hybrid;  // per iteration of this run (profiling: whose extra events were recorded)
     // option sa_graph: the run's kernels go into one hipGraph (stream capture),
     // replayed as a whole -- a chain of dependent kernels costs ~2.7 us per
     // kernel from the stream and ~1.8 from a graph (profiles/r04_graph_gap_
@@ -1128,14 +1252,23 @@ int device_search_run(hq_search* s, int iterations, int* ran) {
         }
         return rc0;
     };
+    if (lloyd) {
+        const hipError_t e = hipMemsetAsync(c->d_sums.p, 0, sums_bytes, c->stream);
+        if (e != hipSuccess) {
+            (void)abort_capture(0);
+            HIP_TRY(c, e);
+        }
+    }
     for (; done < iterations && s->ite < s->prm.imax; ++done) {
         const int ite = ++s->ite;
         s->pol->reduce_temperature_if_necessary(ite);                  // IM:507
         const float amax = s->pol->max_step_width(ite) / 256.0f;       // SW:91-101
-        const hipEvent_t* ev = prof ? &s->pev[(size_t)kProfEvents * done] : nullptr;
+        const hipEvent_t* ev = prof ? &s->pev[(size_t)kProfSearchEvents * done] : nullptr;
         // accept the previous iteration's population (none at the first of a run)
         if ((rc = enqueue_sa_step(s, done > 0, false, true, false, amax, ev ? ev + 8 : nullptr)))
             return abort_capture(rc);
+        hybrid.push_back(s->every > 0 && ite % s->every == 0);
+        if (hybrid.back() && (rc = enqueue_lloyd(s, ev))) return abort_capture(rc);
         if ((rc = enqueue_core(c, s->P, s->K, ev, s->fold))) return abort_capture(rc);
         s->t_acc = s->pol->temperature();     // SW:54-57 at this iteration
         s->keep_acc = s->pol->keep_threshold(ite);
@@ -1168,8 +1301,14 @@ int device_search_run(hq_search* s, int iterations, int* ran) {
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (int i = 0; prof && i < done; ++i) {
-        prof_accumulate(c, &s->pev[(size_t)kProfEvents * i], !s->fold);
-        prof_accumulate_sa(c, &s->pev[(size_t)kProfEvents * i]);
+        const hipEvent_t* ev = &s->pev[(size_t)kProfSearchEvents * i];
+        prof_accumulate(c, ev, !s->fold);
+        prof_accumulate_sa(c, ev);
+        if (!hybrid[i]) continue;  // (events of an earlier run's hybrid iteration may sit in these slots)
+        if (c->G2 > 0) prof_add(c, c->prof_grid, ev[kProfLloyd], ev[kProfLloyd + 1]);
+        prof_add(c, c->prof_assign, ev[kProfLloyd + 2], ev[kProfLloyd + 3]);
+        prof_add(c, c->prof_centroid, ev[kProfLloyd + 4], ev[kProfLloyd + 5]);
+        prof_add(c, c->prof_lloyd, ev[kProfLloyd + 6], ev[kProfLloyd + 7]);
     }
     if (ran) *ran = done;
     return HQ_OK;
@@ -1698,6 +1837,20 @@ int hq_search_create(hq_ctx* c, const hq_swasa_params* params, int K, uint64_t s
             return hq_eval_population(c, pal, P, KK, delta, costs, nullptr);
         };
         s->driver = new SearchDriver(*params, K, seed, eval);
+        // the k-means move, host-driven, is the public triple: an evaluation of the
+        // candidates for their argmin (its cost pass is wasted), the sums, the update
+        s->driver->set_refine([c, delta](float* pal, int P, int KK) {
+            std::vector<double> costs(P);
+            std::vector<int64_t> sums((size_t)P * KK * 4);
+            int64_t den = 0;
+            int rr = hq_eval_population(c, pal, P, KK, delta, costs.data(), nullptr);
+            if (!rr) rr = cluster_sums(c, P, KK, sums.data(), &den);
+            if (!rr && (rr = hq_centroids_from_sums(sums.data(), den, P, KK, pal)))
+                return fail(c, rr, "hq_centroids_from_sums failed");
+            return rr;
+        });
+        s->prm = *params;
+        s->P = params->population;
         rc = s->driver->start();
     }
     c->sums_ok = false;  // (the search's own evaluations replace the index images)
@@ -1712,6 +1865,14 @@ int hq_search_create(hq_ctx* c, const hq_swasa_params* params, int K, uint64_t s
 int hq_search_run(hq_search* s, int iterations, int* ran) {
     if (!s || iterations < 0) return HQ_ERR_ARG;
     int rc;
+    // a hybrid iteration in this run: its scope and the image's validity first, so
+    // a refusal leaves the search where it was
+    if (s->ctx && lloyd_in_run(s, s->driver ? s->driver->iteration() : s->ite, iterations)) {
+        if ((rc = lloyd_scope(s)) || (rc = lloyd_validate(s))) {
+            if (ran) *ran = 0;
+            return rc;
+        }
+    }
     if (!s->driver) {
         rc = bind(s->ctx);
         if (!rc) rc = device_search_run(s, iterations, ran);
@@ -1720,6 +1881,16 @@ int hq_search_run(hq_search* s, int iterations, int* ran) {
     }
     if (s->ctx) s->ctx->sums_ok = false;  // (hq_cluster_sums: a search run has evaluated since)
     return rc;
+}
+
+int hq_search_set_lloyd(hq_search* s, int every) {
+    if (!s || !s->ctx) return HQ_ERR_ARG;
+    if (every < 0) return fail(s->ctx, HQ_ERR_ARG, "every=%d < 0", every);
+    if (every > 0)
+        if (int rc = lloyd_scope(s)) return rc;
+    s->every = every;
+    if (s->driver) s->driver->set_every(every);
+    return HQ_OK;
 }
 
 int hq_search_best(const hq_search* s, float* colors, double* best_error, int* iteration) {
@@ -1767,7 +1938,7 @@ int hq_profile_enable(hq_ctx* c, int on) {
 int hq_profile_reset(hq_ctx* c) {
     if (!c) return HQ_ERR_ARG;
     c->prof_assign = c->prof_cost = c->prof_grid = c->prof_finalize = c->prof_sa = c->prof_comm = c->prof_centroid =
-        ProfSlot{};
+        c->prof_lloyd = ProfSlot{};
     return HQ_OK;
 }
 
@@ -1781,6 +1952,7 @@ int hq_profile_get(hq_ctx* c, const char* kernel, double* total_ms, int64_t* lau
     else if (!std::strcmp(kernel, "sa_step")) s = &c->prof_sa;
     else if (!std::strcmp(kernel, "comm")) s = &c->prof_comm;
     else if (!std::strcmp(kernel, "centroid")) s = &c->prof_centroid;
+    else if (!std::strcmp(kernel, "lloyd")) s = &c->prof_lloyd;
     else return fail(c, HQ_ERR_ARG, "unknown kernel '%s'", kernel);
     if (total_ms) *total_ms = s->ms;
     if (launches) *launches = s->launches;

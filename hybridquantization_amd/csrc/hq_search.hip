@@ -1,10 +1,12 @@
 // hq_search.hip -- per-iteration kernels of the SWASA search around the
 // assign and cost kernels: palette prep (opponent table, duplicates, non-finite
-// guard), the device-resident SA step (IM:497-568 with SW:54-101), the exact
+// guard), the device-resident SA step (IM:497-568 with SW:54-101), the k-means
+// update of a hybrid iteration (libhq's addition), the exact
 // two-level candidate grid of the pruned argmin, and the fixed-order fp64
 // finalize (IM:736-768, SW:74-82).
 #include "hq_device.h"
 #include "hq_launch.h"
+#include "hq_lloyd.h"
 
 namespace hq {
 
@@ -494,6 +496,39 @@ __global__ __launch_bounds__(1024) void sa_step_kernel(SaArgs a) {
 }
 
 // ----------------------------------------------------------------------------
+// lloyd_update: grid (P), block 1024.  The k-means move of a hybrid iteration
+// (libhq's addition), between the assign-only pass + the sums kernel and the
+// evaluation.  Thread k < K holds candidate colour k of palette p and its 32 B
+// of sums (two 16-B loads): with a count > 0 the colour becomes the mean of its
+// pixels -- lloyd_mean, the host rule's own arithmetic in fp64, so the bits are
+// hq_centroids_from_sums' -- and goes back into the candidate buffer in place
+// (what the next sa_step reads as cand_in); with count 0 it keeps its bits.
+// The sums are zeroed once read, for the next hybrid iteration, and the palette
+// is prepared again so pal, opp, opp16, dup and pflags are the updated one's.
+// ----------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void lloyd_update_kernel(LloydArgs a) {
+    const int p = blockIdx.x, k = threadIdx.x;
+    __shared__ float4 s[kMaxK];
+    __shared__ PrepLds L;
+    float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (k < a.K) {
+        float4* const cp = reinterpret_cast<float4*>(a.cand) + (int64_t)p * a.K + k;
+        ulonglong2* const sp = reinterpret_cast<ulonglong2*>(a.sums + ((int64_t)p * a.K + k) * 4);
+        const ulonglong2 rg = sp[0], bn = sp[1];
+        c = *cp;
+        if (bn.y > 0ull) {
+            const bool bytes = a.bytes != 0;
+            c = make_float4(lloyd_mean((int64_t)rg.x, (int64_t)bn.y, bytes), lloyd_mean((int64_t)rg.y, (int64_t)bn.y, bytes),
+                            lloyd_mean((int64_t)bn.x, (int64_t)bn.y, bytes), 0.f);
+            *cp = c;
+        }
+        sp[0] = sp[1] = make_ulonglong2(0ull, 0ull);
+    }
+    bool nf;
+    (void)prep_palette_body(a.prep, p, c, s, L, true, nf);
+}
+
+// ----------------------------------------------------------------------------
 // build_grid: grid (G1^3, P), block 256.  One workgroup per level-1 cell; it
 // also writes the 64 level-2 children (G2 = 4*G1).
 //
@@ -922,6 +957,11 @@ hipError_t launch_prep_palette(const PaletteArgs& a, int P, hipStream_t s) {
 
 hipError_t launch_sa_step(const SaArgs& a, hipStream_t s) {
     HQ_LAUNCH(sa_step_kernel, dim3(a.P * a.nch), dim3(1024), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_lloyd_update(const LloydArgs& a, int P, hipStream_t s) {
+    HQ_LAUNCH(lloyd_update_kernel, dim3(P), dim3(1024), 0, s, a);
     return hipGetLastError();
 }
 

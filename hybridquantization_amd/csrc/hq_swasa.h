@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdint>
 #include <functional>
+#include <utility>
 #include <vector>
 
 #include "../../include/hq.h"
@@ -57,6 +58,8 @@ class Swasa {
 };
 
 using PopulationEval = std::function<int(const float* palettes, int P, int K, double* costs)>;
+// The k-means move of a hybrid iteration: updates the candidates in place.
+using PopulationRefine = std::function<int(float* palettes, int P, int K)>;
 
 // IM:383-591 as a resumable state machine.
 class SearchDriver {
@@ -64,6 +67,12 @@ class SearchDriver {
     SearchDriver(const hq_swasa_params& p, int K, uint64_t seed, PopulationEval eval);
     int start();                          // IM:385-493: reset, initial population, argmin
     int run(int iterations, int* ran, std::vector<double>* trace);   // IM:497-568
+    // Hybrid iterations (libhq's addition): with every > 0 and a refine step,
+    // the candidates of iteration ite (1-based, counted across run calls) with
+    // ite % every == 0 go through `refine` between their generation and their
+    // evaluation.  Applies to the iterations that follow.
+    void set_refine(PopulationRefine refine) { refine_ = std::move(refine); }
+    void set_every(int every) { every_ = every; }
     const std::vector<float>& best_colors() const { return best_colors_; }
     double best_error() const { return best_error_; }
     int iteration() const { return ite_; }
@@ -72,6 +81,8 @@ class SearchDriver {
     Swasa sw_;
     int K_, P_;
     PopulationEval eval_;
+    PopulationRefine refine_;
+    int every_ = 0;
     std::vector<float> colors_, current_;   // [P][4K]
     std::vector<double> current_errors_, errors_;
     std::vector<float> best_colors_;

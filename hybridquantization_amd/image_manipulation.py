@@ -205,7 +205,7 @@ class ImageManipulation:
     # IM:383
     def findBestQuantization(self, inlinergbOriginal, inlineScielabOriginal, w, nbOfColors,
                              simulatedAnnealing, filters, absfilters, illuminant,
-                             iterations=None, stop=None, lloydSteps=0):
+                             iterations=None, stop=None, lloydSteps=0, lloydEvery=0):
         """Full SWASA search (IM:383-591) on the GPU; returns bestColors float[4K].
 
         ``simulatedAnnealing`` is a :class:`~hybridquantization_amd.swasa.SWASA`;
@@ -214,6 +214,10 @@ class ImageManipulation:
         the best palette is then polished by that many k-means steps, keeping the
         lowest-cost step (hq_refine_population, keep_best); ``bestError`` and the
         returned colours are the polished ones, ``bestErrorSA`` the search's own.
+        ``lloydEvery`` > 0 (hq_search_set_lloyd): every iteration whose 1-based count
+        is a multiple of it is a hybrid iteration -- each candidate takes one k-means
+        move before it is evaluated, inside the search, on the device when the
+        search is device-resident.  The two compose.
         """
         ctx = self._require()
         if not self.openCLFiltersReady:
@@ -228,6 +232,8 @@ class ImageManipulation:
         check(self._lib.hq_search_create(ctx, C.byref(params), int(nbOfColors), sw.seed,
                                          C.byref(handle)), ctx)
         try:
+            if int(lloydEvery) != 0:
+                check(self._lib.hq_search_set_lloyd(handle, int(lloydEvery)), ctx)
             total = params.imax if iterations is None else min(int(iterations), params.imax)
             done = 0
             while done < total:

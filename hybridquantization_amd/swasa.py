@@ -50,12 +50,18 @@ class SWASA:
     def computePenalty(self, usedColors) -> float:  # SW:74-82
         return float(np.count_nonzero(np.asarray(usedColors) == 0)) * self.delta
 
-    def search_host(self, K: int, eval_population, iterations=None):
+    def search_host(self, K: int, eval_population, iterations=None, refine=None, every=0):
         """Run the native SWASA driver with a Python population evaluator.
 
         eval_population(palettes (P, K, 4) float32) -> costs (P,).  Returns
         (best_colors float[4K], best_error, trace (iterations, 1+P)).  This is
         the hook the CPU tests use to check the policy without a GPU.
+
+        ``refine`` and ``every`` (libhq's addition, hq_swasa_search_host_lloyd): on
+        iteration ite with ite % every == 0 the candidates go through
+        refine(palettes (P, K, 4) float32) before they are evaluated; it updates
+        the array in place or returns the updated palettes.  With ``refine``
+        None and ``every`` 0 this is hq_swasa_search_host.
         """
         lib = load()
         params = self.params()
@@ -77,8 +83,25 @@ class SWASA:
         best = np.zeros(4 * K, np.float32)
         err = C.c_double()
         trace = np.zeros(iters * (1 + self.population), np.float64)
-        rc = lib.hq_swasa_search_host(C.byref(params), int(K), self.seed, iters, cb, None,
-                                      _lib.fptr(best), C.byref(err), _lib.dptr(trace))
+        if refine is None and int(every) == 0:
+            rc = lib.hq_swasa_search_host(C.byref(params), int(K), self.seed, iters, cb, None,
+                                          _lib.fptr(best), C.byref(err), _lib.dptr(trace))
+        else:
+            def _rf(user, pal, P, KK):
+                try:
+                    arr = np.ctypeslib.as_array(pal, shape=(P * KK * 4,)).reshape(P, KK, 4)
+                    res = refine(arr)  # in place, or the updated palettes
+                    if res is not None:
+                        arr[...] = np.asarray(res, np.float32).reshape(P, KK, 4)
+                    return 0
+                except Exception as e:
+                    errbox.append(e)
+                    return 1
+
+            rf = _lib.REFINE_FN(_rf) if refine is not None else _lib.REFINE_FN()
+            rc = lib.hq_swasa_search_host_lloyd(C.byref(params), int(K), self.seed, iters, cb, rf,
+                                                int(every), None, _lib.fptr(best), C.byref(err),
+                                                _lib.dptr(trace))
         if errbox:
             raise errbox[0]
         check(rc)

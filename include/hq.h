@@ -245,6 +245,33 @@ int hq_search_create(hq_ctx *ctx, const hq_swasa_params *params, int K, uint64_t
 int hq_search_run(hq_search *s, int iterations, int *ran);
 int hq_search_best(const hq_search *s, float *colors, double *best_error, int *iteration);
 void hq_search_destroy(hq_search *s);
+/* Hybrid iterations (libhq's addition: Schaefer & Nolle interleave a k-means
+ * step with the annealing moves, the reference holds the annealing half only).
+ * every = 0 (the default) is the plain search, bit for bit.  With every > 0,
+ * iteration ite -- the 1-based count hq_search_best reports, continuing across
+ * hq_search_run calls -- is a hybrid iteration when ite % every == 0; the initial
+ * population is never refined.  In a hybrid iteration the candidates are drawn
+ * as always (SW:91-101, the same random stream, no extra draws); each member's
+ * candidate X is then replaced by one k-means update of X -- the assignment is
+ * the evaluation's argmin of X, the sums are hq_cluster_sums' (the same den),
+ * the update is hq_centroids_from_sums' rule exactly -- and the updated
+ * candidate is what is evaluated, accepted or rejected, copied by the
+ * convergence step and recorded as best (IM:515-545).
+ * Callable any time after hq_search_create, also between runs; it applies to
+ * the iterations that follow.  every < 0: HQ_ERR_ARG.  every > 0 on a row-block
+ * shard (option "shard_solo" included): HQ_ERR_STATE; with a communicator of
+ * more than one rank, "palette_split" or "slice_ranks" > 1: HQ_ERR_UNSUPPORTED;
+ * on a device-resident search of K > 256 (chunked palettes):
+ * HQ_ERR_UNSUPPORTED -- a host-driven search (option "sa_device" 0) takes every
+ * K hq_cluster_sums serves.  The device-resident search (K <= 256) runs a
+ * hybrid iteration without a host round trip: an assign-only pass, the sums
+ * kernel, the update kernel ("lloyd" in hq_profile_get), then the evaluation.
+ * When the sums would be the planar form's (den 2^32) and the image holds a
+ * pixel that is not finite or lies outside [0, 1] -- hq_cluster_sums'
+ * HQ_ERR_UNSUPPORTED -- the hq_search_run call that would run the first hybrid
+ * iteration returns HQ_ERR_UNSUPPORTED with *ran = 0 and the search has not
+ * advanced (checked once per image, before anything is enqueued). */
+int hq_search_set_lloyd(hq_search *s, int every);
 
 /* Host-only SWASA driver with a caller-supplied population evaluator; same
  * policy code as hq_search_*.  Used to test the SA semantics without a GPU.
@@ -254,13 +281,25 @@ typedef int (*hq_eval_fn)(void *user, const float *palettes, int P, int K, doubl
 int hq_swasa_search_host(const hq_swasa_params *params, int K, uint64_t seed, int iterations,
                          hq_eval_fn eval, void *user, float *best_colors, double *best_error,
                          double *trace);
+/* The same with hybrid iterations (hq_search_set_lloyd's semantics, the same
+ * driver code as a host-driven hq_search_*): on iteration ite with
+ * ite % every == 0, refine(user, palettes[P*K*4], P, K) updates the candidates
+ * in place between their generation and their evaluation; it returns 0 on
+ * success, any other value ends the search and is returned as is.  every = 0
+ * or a NULL refine is hq_swasa_search_host bit for bit; every < 0: HQ_ERR_ARG. */
+typedef int (*hq_refine_fn)(void *user, float *palettes, int P, int K);
+int hq_swasa_search_host_lloyd(const hq_swasa_params *params, int K, uint64_t seed, int iterations,
+                               hq_eval_fn eval, hq_refine_fn refine, int every, void *user,
+                               float *best_colors, double *best_error, double *trace);
 
 /* Kernel timing of the dominant kernels, measured with HIP events on the
  * context stream while enabled (bench.py roofline). */
 int hq_profile_enable(hq_ctx *ctx, int on);
 /* names: "assign", "cost", "grid", "finalize", "sa_step" (device-resident search), "comm" (the
  * per-evaluation RCCL all-reduce or all-gather, with a communicator), "centroid"
- * (hq_cluster_sums' kernel); returns total ms and launch
+ * (hq_cluster_sums' kernel), "lloyd" (the update kernel of a device-resident
+ * hybrid iteration, whose assign-only pass and sums kernel count under "grid",
+ * "assign" and "centroid"); returns total ms and launch
  * count (HIP events on the context stream). */
 int hq_profile_get(hq_ctx *ctx, const char *kernel, double *total_ms, int64_t *launches);
 int hq_profile_reset(hq_ctx *ctx);
