@@ -70,6 +70,8 @@ SIGNATURES = {
     "hq_centroids_from_sums": (C.c_int, [_i64, C.c_int64, C.c_int, C.c_int, _f]),
     "hq_refine_population": (C.c_int, [_ctx, _f, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _d,
                                        _i32, _d]),
+    "hq_color_histogram": (C.c_int, [_ctx, C.c_int, _i64, _i64]),
+    "hq_median_cut": (C.c_int, [_i64, C.c_int, C.c_int64, C.c_int, _f, C.POINTER(C.c_int)]),
     "hq_quantize": (C.c_int, [_ctx, _f, C.c_int64, _f, C.c_int, _f, _i32]),
     "hq_compute_error": (C.c_int, [_ctx, _f, _f, C.c_int64, _f, _d]),
     "hq_comm_unique_id": (C.c_int, [C.POINTER(C.c_ubyte)]),
@@ -78,6 +80,8 @@ SIGNATURES = {
     "hq_swasa_default_params": (None, [C.POINTER(hq_swasa_params)]),
     "hq_search_create": (C.c_int, [_ctx, C.POINTER(hq_swasa_params), C.c_int, C.c_uint64,
                                    C.POINTER(C.c_void_p)]),
+    "hq_search_create_from": (C.c_int, [_ctx, C.POINTER(hq_swasa_params), C.c_int, C.c_uint64, _f,
+                                        C.POINTER(C.c_void_p)]),
     "hq_search_run": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "hq_search_best": (C.c_int, [C.c_void_p, _f, _d, C.POINTER(C.c_int)]),
     "hq_search_destroy": (None, [C.c_void_p]),
@@ -86,6 +90,8 @@ SIGNATURES = {
                                        C.c_int, EVAL_FN, C.c_void_p, _f, _d, _d]),
     "hq_swasa_search_host_lloyd": (C.c_int, [C.POINTER(hq_swasa_params), C.c_int, C.c_uint64,
                                              C.c_int, EVAL_FN, REFINE_FN, C.c_int, C.c_void_p, _f, _d, _d]),
+    "hq_swasa_search_host_from": (C.c_int, [C.POINTER(hq_swasa_params), C.c_int, C.c_uint64,
+                                            C.c_int, EVAL_FN, REFINE_FN, C.c_int, _f, C.c_void_p, _f, _d, _d]),
     "hq_profile_enable": (C.c_int, [_ctx, C.c_int]),
     "hq_profile_get": (C.c_int, [_ctx, C.c_char_p, _d, C.POINTER(C.c_int64)]),
     "hq_profile_reset": (C.c_int, [_ctx]),

@@ -238,12 +238,14 @@ static int argmin_first(const std::vector<double>& a) {  // IM:843-856
     return m;
 }
 
-int SearchDriver::start() {
+int SearchDriver::start(const float* population) {
     const int n = 4 * K_;
     sw_.reset();                                                   // IM:385
     colors_.assign((size_t)P_ * n, 0.0f);
     current_.assign((size_t)P_ * n, 0.0f);
     for (int i = 0; i < P_; ++i) sw_.generate_random_colors(K_, &colors_[(size_t)i * n]);  // IM:413-417
+    if (population)  // a given start: the draws above are made all the same
+        for (size_t e = 0; e < colors_.size(); ++e) colors_[e] = e % 4 == 3 ? 0.0f : population[e];
     current_errors_.assign(P_, 0.0);
     errors_.assign(P_, 0.0);
     int rc = eval_(colors_.data(), P_, K_, current_errors_.data());  // IM:490
@@ -302,13 +304,22 @@ int SearchDriver::run(int iterations, int* ran, std::vector<double>* trace) {
 
 }  // namespace hq
 
-extern "C" int hq_swasa_search_host_lloyd(const hq_swasa_params* params, int K, uint64_t seed,
-                                          int iterations, hq_eval_fn eval, hq_refine_fn refine, int every,
-                                          void* user, float* best_colors, double* best_error,
-                                          double* trace) {
+// A given population is one the search could hold: every channel finite and in
+// [0, 1], where SW:96-98 keeps its colours (.w is not read: it is stored as 0).
+bool hq::population_in_range(const float* population, int P, int K) {
+    for (size_t e = 0, n = (size_t)P * 4 * K; e < n; ++e)
+        if (e % 4 != 3 && !(population[e] >= 0.0f && population[e] <= 1.0f)) return false;  // (NaN fails both)
+    return true;
+}
+
+extern "C" int hq_swasa_search_host_from(const hq_swasa_params* params, int K, uint64_t seed,
+                                         int iterations, hq_eval_fn eval, hq_refine_fn refine, int every,
+                                         const float* population, void* user, float* best_colors,
+                                         double* best_error, double* trace) {
     if (!params || !eval || K < 1 || params->population < 1 || params->imax < 1 ||
         params->iTc < 1 || every < 0)
         return HQ_ERR_ARG;
+    if (population && !hq::population_in_range(population, params->population, K)) return HQ_ERR_ARG;
     hq::SearchDriver d(*params, K, seed, [&](const float* pal, int P, int KK, double* costs) {
         return eval(user, pal, P, KK, costs) ? HQ_ERR_ARG : HQ_OK;
     });
@@ -316,7 +327,7 @@ extern "C" int hq_swasa_search_host_lloyd(const hq_swasa_params* params, int K, 
         d.set_refine([&](float* pal, int P, int KK) { return refine(user, pal, P, KK); });
         d.set_every(every);
     }
-    int rc = d.start();
+    int rc = d.start(population);
     if (rc) return rc;
     std::vector<double> tr;
     int ran = 0;
@@ -328,11 +339,19 @@ extern "C" int hq_swasa_search_host_lloyd(const hq_swasa_params* params, int K, 
     return HQ_OK;
 }
 
+extern "C" int hq_swasa_search_host_lloyd(const hq_swasa_params* params, int K, uint64_t seed,
+                                          int iterations, hq_eval_fn eval, hq_refine_fn refine, int every,
+                                          void* user, float* best_colors, double* best_error,
+                                          double* trace) {
+    return hq_swasa_search_host_from(params, K, seed, iterations, eval, refine, every, nullptr, user,
+                                     best_colors, best_error, trace);
+}
+
 extern "C" int hq_swasa_search_host(const hq_swasa_params* params, int K, uint64_t seed,
                                     int iterations, hq_eval_fn eval, void* user,
                                     float* best_colors, double* best_error, double* trace) {
-    return hq_swasa_search_host_lloyd(params, K, seed, iterations, eval, nullptr, 0, user, best_colors,
-                                      best_error, trace);
+    return hq_swasa_search_host_from(params, K, seed, iterations, eval, nullptr, 0, nullptr, user,
+                                     best_colors, best_error, trace);
 }
 
 // The k-means update (libhq's addition, no reference counterpart): every colour

@@ -277,6 +277,23 @@ struct ClusterArgs {
     uint32_t qspan;         // quads of 4 pixels per workgroup      } launcher
 };
 
+// Colour histogram of the owned rows (hq_hist.hip, hq_color_histogram): per cell
+// of a 2^bits grid per channel the sum of its pixels and their count, in the
+// units of ClusterArgs::sums.
+constexpr int kHistBlocksPerCu = 8;       // workgroups per CU: one resident round
+struct HistArgs {
+    const float* R;         // planar, extended rows (padded to a multiple of 4 floats)
+    const float* G;
+    const float* B;
+    const uint32_t* rgbx;   // packed 8-bit R,G,B (AssignArgs::rgbx), else null
+    unsigned long long* cells;  // [2^(3 bits)][4] sum R, sum G, sum B, count (zeroed before the launch)
+    int* bad;               // planar form: set to 1 by an owned pixel that is not in [0, 1]
+    uint32_t q0, q1;        // the owned rows: positions [q0, q1) of the extended rows
+    int bits;               // 2 .. 6
+    int nblocks;            // workgroups                           } set by the
+    uint32_t qspan;         // quads of 4 pixels per workgroup      } launcher
+};
+
 // lloyd_update_kernel (hq_search.hip): the k-means move of a device-resident
 // hybrid iteration.  Candidate colour k of palette p with count > 0 becomes the
 // mean of its pixels (lloyd_mean, hq_lloyd.h), in place; the palette is

@@ -118,6 +118,8 @@ hipError_t launch_cost_generic(const GenArgs&, int de, int idx_bytes, hipStream_
 hipError_t launch_cost_tiled_generic(const GenArgs&, int de, int idx_bytes, hipStream_t);
 // hq_centroid.hip: per-colour pixel sums; idx_bytes 1, 2 or 4, num_cu sizes the grid
 hipError_t launch_cluster_sums(const ClusterArgs&, int idx_bytes, int num_cu, hipStream_t);
+// hq_hist.hip: the colour histogram of the owned rows; num_cu sizes the grid
+hipError_t launch_color_histogram(const HistArgs&, int num_cu, hipStream_t);
 // hq_setup.hip
 hipError_t launch_pack_u8(const float*, const float*, const float*, uint32_t*, int*, int64_t, hipStream_t);
 hipError_t launch_labref_opp(const float*, const float*, const float*, float4*, int64_t, hipStream_t);

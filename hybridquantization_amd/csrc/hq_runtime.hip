@@ -144,6 +144,7 @@ struct hq_ctx {
     // hybrid iterations: every owned pixel of the planar image is finite and in [0, 1], the
     // condition of the planar form's sums (-1: not established yet for this image)
     int planar_ok = -1;
+    DevBuf d_hist;             // hq_color_histogram: [2^(3 bits)][4] int64 cells, then the range flag
 
     // options
     int G2 = 32;           // argmin grid resolution (0 = exhaustive)
@@ -189,9 +190,11 @@ struct hq_ctx {
 
     // profiling
     bool prof = false;
-    ProfSlot prof_assign, prof_cost, prof_grid, prof_finalize, prof_sa, prof_comm, prof_centroid, prof_lloyd;
+    ProfSlot prof_assign, prof_cost, prof_grid, prof_finalize, prof_sa, prof_comm, prof_centroid, prof_lloyd,
+        prof_hist;
     // profiling: start/stop of grid, assign, cost, finalize, [sa_step], the collective
     hipEvent_t ev[kProfEvents] = {};
+    hipEvent_t ev_hist[2] = {};  // ... and of hq_color_histogram's kernel
     int num_cu = 256;
     size_t lds_optin = 160 * 1024;  // per-workgroup LDS a kernel may opt into (hq_create's query)
 };
@@ -1002,6 +1005,43 @@ int cluster_sums(hq_ctx* c, int P, int K, int64_t* out, int64_t* den) {
     return HQ_OK;
 }
 
+// hq_color_histogram into `out` ([2^(3 bits)][4]); nothing is written unless
+// HQ_OK.  The image buffers are read, a table of its own is written: the index
+// images, the counter sets and d_sums stay what they are.
+int color_histogram(hq_ctx* c, int bits, int64_t* out, int64_t* den) {
+    int rc = bind(c);
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    const Geom& g = c->g;
+    const size_t n4 = (size_t)4 << (3 * bits);
+    HIP_TRY(c, c->d_hist.ensure(sizeof(int64_t) * (n4 + 1)));
+    HIP_TRY(c, hipMemsetAsync(c->d_hist.p, 0, sizeof(int64_t) * (n4 + 1), s));
+    const bool u8 = sums_u8(c);
+    HistArgs ha{};
+    ha.R = c->d_R.as<float>();
+    ha.G = c->d_G.as<float>();
+    ha.B = c->d_B.as<float>();
+    ha.rgbx = u8 ? c->d_rgbx.as<uint32_t>() : nullptr;
+    ha.cells = c->d_hist.as<unsigned long long>();
+    ha.bad = reinterpret_cast<int*>(c->d_hist.as<int64_t>() + n4);
+    ha.q0 = (uint32_t)((int64_t)(g.r0 - g.e0) * g.W);
+    ha.q1 = ha.q0 + (uint32_t)((int64_t)g.W * (g.r1 - g.r0));
+    ha.bits = bits;
+    if (c->prof) set_launch_events(c->ev_hist[0], c->ev_hist[1]);
+    const hipError_t e = launch_color_histogram(ha, c->num_cu, s);
+    set_launch_events(nullptr, nullptr);
+    HIP_TRY(c, e);
+    std::vector<int64_t> h(n4 + 1);
+    HIP_TRY(c, hipMemcpyAsync(h.data(), c->d_hist.p, sizeof(int64_t) * (n4 + 1), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (c->prof) prof_add(c, c->prof_hist, c->ev_hist[0], c->ev_hist[1]);
+    if (h[n4] != 0)
+        return fail(c, HQ_ERR_UNSUPPORTED, "planar image with a pixel outside [0, 1] or not finite: no exact sums");
+    std::memcpy(out, h.data(), sizeof(int64_t) * n4);
+    *den = u8 ? 255 : (int64_t)1 << 32;
+    return HQ_OK;
+}
+
 }  // namespace
 
 namespace {
@@ -1159,7 +1199,9 @@ int enqueue_lloyd(hq_search* s, const hipEvent_t* ev) {
     return HQ_OK;
 }
 
-int device_search_create(hq_ctx* c, const hq_swasa_params* params, int K, uint64_t seed, hq_search* s) {
+// population: hq_search_create_from's ([P][4K], checked), or null for the random one.
+int device_search_create(hq_ctx* c, const hq_swasa_params* params, int K, uint64_t seed, const float* population,
+                         hq_search* s) {
     const int P = params->population;
     s->prm = *params;
     s->P = P;
@@ -1208,6 +1250,22 @@ int device_search_create(hq_ctx* c, const hq_swasa_params* params, int K, uint64
     s->st = s->cd = 0;
     // IM:385-493: random population (SW:40-52), its evaluation, argmin
     if ((rc = enqueue_sa_step(s, false, false, true, true, 0.f))) return rc;
+    // A given population takes the random one's place after that step has drawn it (the seed
+    // is past the 3 K P draws as always): into the candidate buffer the accept step reads,
+    // and through the palette prep as an evaluation uploads it (chunked palettes: pack_chunks'
+    // sub-palettes), so the prep's outputs and the duplicate flags are the given colours'.
+    std::vector<float> given;  // (.w = 0; read by the copy below until the synchronise)
+    if (population) {
+        given.assign(population, population + n4);
+        for (size_t e = 3; e < n4; e += 4) given[e] = 0.0f;
+        hipStream_t st = c->stream;
+        HIP_TRY(c, hipMemcpyAsync(s->cand[s->cd].p, given.data(), sizeof(float) * n4, hipMemcpyHostToDevice, st));
+        const size_t n_in = s->nch > 1 ? (size_t)P * s->nch * kMaxK : (size_t)P * K;
+        if (s->nch > 1) pack_chunks(given.data(), P, K, s->nch, c->h_pal);
+        else std::memcpy(c->h_pal, given.data(), sizeof(float) * n4);
+        HIP_TRY(c, hipMemcpyAsync(c->d_pal_in.p, c->h_pal, sizeof(float4) * n_in, hipMemcpyHostToDevice, st));
+        HIP_TRY(c, launch_prep_palette(prep_args(c, s->nch > 1 ? kMaxK : K), P * s->nch, st));
+    }
     if ((rc = enqueue_core(c, P, K, nullptr, s->fold))) return rc;
     if ((rc = enqueue_sa_step(s, true, true, false, false, 0.f))) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1370,6 +1428,7 @@ int hq_create(int device, int delta_e_type, hq_ctx** out) {
     for (int ng = 1; ng <= 4; ++ng) c->assign_res[ng] = assign_residency(ng);
     c->assign_res_chunked = assign_residency_chunked();
     for (auto& e : c->ev) (void)hipEventCreate(&e);
+    for (auto& e : c->ev_hist) (void)hipEventCreate(&e);
     *out = c;
     return HQ_OK;
 }
@@ -1383,11 +1442,14 @@ void hq_destroy(hq_ctx* c) {
                       &c->d_labL, &c->d_labA, &c->d_labB, &c->d_pal_in, &c->d_pal, &c->d_opp, &c->d_opp16,
                       &c->d_dup, &c->d_pflags, &c->d_lvl1, &c->d_lvl2, &c->d_idx,
                       &c->d_used_mask, &c->d_acc, &c->d_out, &c->d_gen_t, &c->d_taps,
-                      &c->d_vfrag16, &c->d_vfrag16p, &c->d_vfragm, &c->d_htaps, &c->d_idx32, &c->d_used32, &c->d_pixerr, &c->d_idx16, &c->d_dist, &c->d_l1n, &c->d_l2n, &c->d_sums})
+                      &c->d_vfrag16, &c->d_vfrag16p, &c->d_vfragm, &c->d_htaps, &c->d_idx32, &c->d_used32, &c->d_pixerr, &c->d_idx16, &c->d_dist, &c->d_l1n, &c->d_l2n, &c->d_sums,
+                      &c->d_hist})
         b->release();
     if (c->h_pal) (void)hipHostFree(c->h_pal);
     if (c->h_out) (void)hipHostFree(c->h_out);
     for (auto& e : c->ev)
+        if (e) (void)hipEventDestroy(e);
+    for (auto& e : c->ev_hist)
         if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -1618,6 +1680,13 @@ int hq_cluster_sums(hq_ctx* c, int P, int K, int64_t* sums, int64_t* den) {
     return cluster_sums(c, P, K, sums, den);
 }
 
+int hq_color_histogram(hq_ctx* c, int bits, int64_t* cells, int64_t* den) {
+    if (!c) return HQ_ERR_ARG;
+    if (!cells || !den || bits < 2 || bits > 6) return fail(c, HQ_ERR_ARG, "bad cells / den / bits=%d (2 .. 6)", bits);
+    if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
+    return color_histogram(c, bits, cells, den);
+}
+
 int hq_refine_population(hq_ctx* c, float* palettes, int P, int K, int steps, float delta, int keep_best,
                          double* costs, int32_t* used, double* trace) {
     if (!costs) return fail(c, HQ_ERR_ARG, "null output");
@@ -1805,10 +1874,17 @@ int hq_comm_info(hq_ctx* c, int* nranks, int* rank) {
 
 int hq_search_create(hq_ctx* c, const hq_swasa_params* params, int K, uint64_t seed,
                      hq_search** out) {
+    return hq_search_create_from(c, params, K, seed, nullptr, out);
+}
+
+int hq_search_create_from(hq_ctx* c, const hq_swasa_params* params, int K, uint64_t seed,
+                          const float* population, hq_search** out) {
     if (!c || !params || !out) return HQ_ERR_ARG;
     *out = nullptr;
     if (params->population < 1 || params->imax < 1 || params->iTc < 1 || K < 1)
         return fail(c, HQ_ERR_ARG, "bad SWASA parameters");
+    if (population && !population_in_range(population, params->population, K))
+        return fail(c, HQ_ERR_ARG, "initial population with a channel that is not finite or outside [0, 1]");
     // device-resident: K <= 256, or chunked palettes (256 < K <= 16384); at most
     // kSaMaxP palettes (sa_step's per-palette tables) and kSaMaxSub sub-palettes
     // (its fold reads 8 used words per sub-palette, at most 4 per thread)
@@ -1830,7 +1906,7 @@ int hq_search_create(hq_ctx* c, const hq_swasa_params* params, int K, uint64_t s
             return fail(c, HQ_ERR_STATE, "sharded context without a communicator");
         }
         s->nch = nch;
-        rc = device_search_create(c, params, K, seed, s);
+        rc = device_search_create(c, params, K, seed, population, s);
     } else {
         const float delta = params->delta;
         auto eval = [c, delta](const float* pal, int P, int KK, double* costs) {
@@ -1851,7 +1927,7 @@ int hq_search_create(hq_ctx* c, const hq_swasa_params* params, int K, uint64_t s
         });
         s->prm = *params;
         s->P = params->population;
-        rc = s->driver->start();
+        rc = s->driver->start(population);
     }
     c->sums_ok = false;  // (the search's own evaluations replace the index images)
     if (rc) {
@@ -1938,7 +2014,7 @@ int hq_profile_enable(hq_ctx* c, int on) {
 int hq_profile_reset(hq_ctx* c) {
     if (!c) return HQ_ERR_ARG;
     c->prof_assign = c->prof_cost = c->prof_grid = c->prof_finalize = c->prof_sa = c->prof_comm = c->prof_centroid =
-        c->prof_lloyd = ProfSlot{};
+        c->prof_lloyd = c->prof_hist = ProfSlot{};
     return HQ_OK;
 }
 
@@ -1953,6 +2029,7 @@ int hq_profile_get(hq_ctx* c, const char* kernel, double* total_ms, int64_t* lau
     else if (!std::strcmp(kernel, "comm")) s = &c->prof_comm;
     else if (!std::strcmp(kernel, "centroid")) s = &c->prof_centroid;
     else if (!std::strcmp(kernel, "lloyd")) s = &c->prof_lloyd;
+    else if (!std::strcmp(kernel, "hist")) s = &c->prof_hist;
     else return fail(c, HQ_ERR_ARG, "unknown kernel '%s'", kernel);
     if (total_ms) *total_ms = s->ms;
     if (launches) *launches = s->launches;

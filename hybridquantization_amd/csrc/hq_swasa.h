@@ -57,6 +57,9 @@ class Swasa {
     float temperature_, step_width_;
 };
 
+// A population a search may start from: every R, G, B finite and in [0, 1].
+bool population_in_range(const float* population, int P, int K);
+
 using PopulationEval = std::function<int(const float* palettes, int P, int K, double* costs)>;
 // The k-means move of a hybrid iteration: updates the candidates in place.
 using PopulationRefine = std::function<int(float* palettes, int P, int K)>;
@@ -65,7 +68,10 @@ using PopulationRefine = std::function<int(float* palettes, int P, int K)>;
 class SearchDriver {
    public:
     SearchDriver(const hq_swasa_params& p, int K, uint64_t seed, PopulationEval eval);
-    int start();                          // IM:385-493: reset, initial population, argmin
+    // IM:385-493: reset, initial population, argmin.  With a population ([P][4K]; libhq's
+    // addition) the random colours are drawn and thrown away and the given ones take their
+    // place, .w = 0: the generator ends where the plain start leaves it.
+    int start(const float* population = nullptr);
     int run(int iterations, int* ran, std::vector<double>* trace);   // IM:497-568
     // Hybrid iterations (libhq's addition): with every > 0 and a refine step,
     // the candidates of iteration ite (1-based, counted across run calls) with

@@ -24,6 +24,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import HQUnavailable, check, dptr, fptr, iptr, load
+from .swasa import initial_population
 
 
 class deltaETypes:  # IM:20
@@ -202,10 +203,35 @@ class ImageManipulation:
                                              dptr(trace)), ctx)
         return (pal, costs, used, trace) if return_trace else (pal, costs, used)
 
+    # seeding the search from the image: libhq's additions (hq_color_histogram, hq_median_cut)
+    def colorHistogram(self, bits: int = 5):
+        """Colour histogram of the owned rows of the image set: (cells int64
+        (2**(3 bits), 4) = (sum R, sum G, sum B, count) per cell (r << 2 bits) | (g << bits) | b
+        in units of 1/den, den = 255 or 2**32 as clusterSums')."""
+        ctx = self._require()
+        cells = np.zeros((1 << (3 * int(bits)) if 2 <= int(bits) <= 6 else 1, 4), np.int64)
+        den = C.c_int64()
+        check(self._lib.hq_color_histogram(ctx, int(bits), _lib.i64ptr(cells), C.byref(den)), ctx)
+        return cells, den.value
+
+    @staticmethod
+    def medianCut(cells, bits, den, K):
+        """hq_median_cut: the deterministic median cut of such a histogram to K colours ->
+        (palette float32[4K], made): colour i < made is the mean of box i's pixels, the
+        colours from made on repeat them (fewer non-empty cells than K)."""
+        cells = np.ascontiguousarray(cells, dtype=np.int64)
+        if not 2 <= int(bits) <= 6 or cells.size != 4 << (3 * int(bits)):
+            raise _lib.HQError(_lib.HQ_ERR_ARG, f"bits={bits} with {cells.size // 4} cells")
+        pal = np.zeros(4 * max(int(K), 1), np.float32)
+        made = C.c_int()
+        check(load().hq_median_cut(_lib.i64ptr(cells), int(bits), int(den), int(K), fptr(pal), C.byref(made)))
+        return pal, made.value
+
     # IM:383
     def findBestQuantization(self, inlinergbOriginal, inlineScielabOriginal, w, nbOfColors,
                              simulatedAnnealing, filters, absfilters, illuminant,
-                             iterations=None, stop=None, lloydSteps=0, lloydEvery=0):
+                             iterations=None, stop=None, lloydSteps=0, lloydEvery=0,
+                             init=None, initBits=5):
         """Full SWASA search (IM:383-591) on the GPU; returns bestColors float[4K].
 
         ``simulatedAnnealing`` is a :class:`~hybridquantization_amd.swasa.SWASA`;
@@ -218,6 +244,13 @@ class ImageManipulation:
         is a multiple of it is a hybrid iteration -- each candidate takes one k-means
         move before it is evaluated, inside the search, on the device when the
         search is device-resident.  The two compose.
+        ``init`` (hq_search_create_from): None is the reference's random start;
+        ``"mediancut"`` starts every member of the population from the median cut of
+        the image's colour histogram at ``initBits`` bits per channel (the members
+        part at iteration 1, each with its own draws); an array of shape (4K,) or
+        (P, 4K) is the start as given.  ``seedColors`` is then the creation's best
+        palette and ``seedError`` its cost, before any iteration.  It composes
+        with ``lloydEvery`` and ``lloydSteps``.
         """
         ctx = self._require()
         if not self.openCLFiltersReady:
@@ -229,9 +262,24 @@ class ImageManipulation:
         sw = simulatedAnnealing
         params = sw.params()
         handle = C.c_void_p()
-        check(self._lib.hq_search_create(ctx, C.byref(params), int(nbOfColors), sw.seed,
-                                         C.byref(handle)), ctx)
+        K = int(nbOfColors)
+        if init is None:
+            check(self._lib.hq_search_create(ctx, C.byref(params), K, sw.seed, C.byref(handle)), ctx)
+        else:
+            if isinstance(init, str):
+                if init != "mediancut":
+                    raise ValueError(f"init={init!r}: None, 'mediancut' or an array")
+                cells, den = self.colorHistogram(int(initBits))
+                init, _ = self.medianCut(cells, int(initBits), den, K)
+            pop = initial_population(init, params.population, K)
+            check(self._lib.hq_search_create_from(ctx, C.byref(params), K, sw.seed, fptr(pop),
+                                                  C.byref(handle)), ctx)
         try:
+            if init is not None:
+                seed = np.zeros(4 * K, np.float32)
+                seed_err = C.c_double()
+                check(self._lib.hq_search_best(handle, fptr(seed), C.byref(seed_err), None), ctx)
+                self.seedColors, self.seedError = seed, seed_err.value
             if int(lloydEvery) != 0:
                 check(self._lib.hq_search_set_lloyd(handle, int(lloydEvery)), ctx)
             total = params.imax if iterations is None else min(int(iterations), params.imax)

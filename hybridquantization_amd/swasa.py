@@ -16,6 +16,17 @@ from . import _lib
 from ._lib import check, load
 
 
+def initial_population(init, P: int, K: int) -> np.ndarray:
+    """A given start as the (P, 4K) float32 array hq_search_create_from and
+    hq_swasa_search_host_from take: (P, 4K) as it is, (4K,) for every member."""
+    pop = np.asarray(init, np.float32)
+    if pop.shape == (4 * K,):
+        pop = np.tile(pop, (P, 1))
+    if pop.shape != (P, 4 * K):
+        raise ValueError(f"initial population of shape {pop.shape}: want ({4 * K},) or ({P}, {4 * K})")
+    return np.ascontiguousarray(pop)
+
+
 class SWASA:
     """SW:14 ``SWASA(population, imax, iTc, delta, convDelay, convSpread, t0, alpha, s0, beta, HQ)``."""
 
@@ -50,7 +61,7 @@ class SWASA:
     def computePenalty(self, usedColors) -> float:  # SW:74-82
         return float(np.count_nonzero(np.asarray(usedColors) == 0)) * self.delta
 
-    def search_host(self, K: int, eval_population, iterations=None, refine=None, every=0):
+    def search_host(self, K: int, eval_population, iterations=None, refine=None, every=0, initial=None):
         """Run the native SWASA driver with a Python population evaluator.
 
         eval_population(palettes (P, K, 4) float32) -> costs (P,).  Returns
@@ -62,6 +73,10 @@ class SWASA:
         refine(palettes (P, K, 4) float32) before they are evaluated; it updates
         the array in place or returns the updated palettes.  With ``refine``
         None and ``every`` 0 this is hq_swasa_search_host.
+
+        ``initial`` (libhq's addition, hq_swasa_search_host_from): the population the
+        search starts from, (P, 4K) or (4K,) for every member, in place of the
+        random one, whose draws are still made.
         """
         lib = load()
         params = self.params()
@@ -83,10 +98,8 @@ class SWASA:
         best = np.zeros(4 * K, np.float32)
         err = C.c_double()
         trace = np.zeros(iters * (1 + self.population), np.float64)
-        if refine is None and int(every) == 0:
-            rc = lib.hq_swasa_search_host(C.byref(params), int(K), self.seed, iters, cb, None,
-                                          _lib.fptr(best), C.byref(err), _lib.dptr(trace))
-        else:
+        rf = _lib.REFINE_FN()
+        if refine is not None:
             def _rf(user, pal, P, KK):
                 try:
                     arr = np.ctypeslib.as_array(pal, shape=(P * KK * 4,)).reshape(P, KK, 4)
@@ -98,7 +111,16 @@ class SWASA:
                     errbox.append(e)
                     return 1
 
-            rf = _lib.REFINE_FN(_rf) if refine is not None else _lib.REFINE_FN()
+            rf = _lib.REFINE_FN(_rf)
+        if initial is not None:
+            pop = initial_population(initial, self.population, int(K))
+            rc = lib.hq_swasa_search_host_from(C.byref(params), int(K), self.seed, iters, cb, rf,
+                                               int(every), _lib.fptr(pop), None, _lib.fptr(best),
+                                               C.byref(err), _lib.dptr(trace))
+        elif refine is None and int(every) == 0:
+            rc = lib.hq_swasa_search_host(C.byref(params), int(K), self.seed, iters, cb, None,
+                                          _lib.fptr(best), C.byref(err), _lib.dptr(trace))
+        else:
             rc = lib.hq_swasa_search_host_lloyd(C.byref(params), int(K), self.seed, iters, cb, rf,
                                                 int(every), None, _lib.fptr(best), C.byref(err),
                                                 _lib.dptr(trace))

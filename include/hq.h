@@ -199,6 +199,47 @@ int hq_centroids_from_sums(const int64_t *sums, int64_t den, int P, int K, float
 int hq_refine_population(hq_ctx *ctx, float *palettes, int P, int K, int steps, float delta,
                          int keep_best, double *costs, int32_t *used, double *trace);
 
+/* ---- seeding the search from the image: libhq's additions, no reference counterpart ----
+ * The reference starts every search from uniform random palettes (SW:40-52).
+ * The three entry points below give a start that knows the image: a colour
+ * histogram on the device, a median cut of it on the host, and (further down)
+ * hq_search_create_from, a search that starts from a given population.
+ *
+ * hq_color_histogram: cells[2^(3 bits)][4] = (sum R, sum G, sum B, count) of the
+ * owned rows of the context's image (halo rows are not counted), exact integers
+ * in hq_cluster_sums' units: *den = 255 and byte sums when the argmin reads the
+ * packed 8-bit copy of a k/255 image (option "img_u8" 1, the default), else
+ * *den = 2^32 and q(v) = RN(v 2^32) per channel value.  The cell of a pixel is
+ * (r << 2 bits) | (g << bits) | b, a channel value v having the coordinate
+ * min(floor(v 2^bits), 2^bits - 1) -- a power-of-two scaling, exact in fp32; on
+ * a k/255 image it equals byte >> (8 - bits), so both forms of one image fill the
+ * same cells.  The histograms of disjoint shards of one image add up exactly to
+ * the whole image's when their den agree.  bits in 2 .. 6, else HQ_ERR_ARG; no
+ * image set: HQ_ERR_STATE; (den 2^32) an owned pixel that is not finite or lies
+ * outside [0, 1]: HQ_ERR_UNSUPPORTED, cells and den untouched.  Needs no
+ * evaluated population and disturbs none: hq_cluster_sums and hq_get_indices
+ * answer after it as before it. */
+int hq_color_histogram(hq_ctx *ctx, int bits, int64_t *cells, int64_t *den);
+/* A palette of K colours from such a histogram (of one context, or several
+ * shards' added up) by median cut.  Host-only, needs no context, deterministic,
+ * integer arithmetic until the final means.
+ *  - A box is an inclusive range of cell coordinates per axis, always shrunk to
+ *    the tight bounds of its non-empty cells.  The first box holds every
+ *    non-empty cell; boxes are split until there are K or every box is one cell.
+ *  - The box to split is the one with the largest count (e_R^2 + e_G^2 + e_B^2),
+ *    e = hi - lo per axis in cells (64-bit integers; 0 exactly for a single
+ *    cell), the lowest box index on a tie; along the axis of the largest e, a
+ *    tie to R, then G, then B.
+ *  - With m[x] the box's counts per coordinate x = lo .. hi of that axis, t is the
+ *    smallest x with 2 sum_{x' <= x} m[x'] >= count, then min(t, hi - 1); the
+ *    part [lo, t] keeps the box's index, [t + 1, hi] is appended as a new box.
+ *  - Colour i < *made (the number of boxes) is the mean of box i's pixels per
+ *    channel by hq_centroids_from_sums' rule, .w = 0; colour i >= *made copies
+ *    colour i mod *made (an image of fewer non-empty cells than K).
+ * HQ_ERR_ARG: K < 1, bits outside 2 .. 6, den other than 255 or 2^32, a negative
+ * count, a total count of 0 or above 2^48 (the priority would leave 64 bits). */
+int hq_median_cut(const int64_t *cells, int bits, int64_t den, int K, float *palette, int *made);
+
 /* IM:770 quantize(inlineImageRGB, colors): chosen colour per pixel (CL:147-170).
  * used (K ints) may be NULL. */
 int hq_quantize(hq_ctx *ctx, const float *rgba4, int64_t n, const float *colors, int K,
@@ -242,6 +283,20 @@ void hq_swasa_default_params(hq_swasa_params *p);
  * stop flag between run() calls (IM:499). */
 int hq_search_create(hq_ctx *ctx, const hq_swasa_params *params, int K, uint64_t seed,
                      hq_search **out);
+/* The same search from a given population (libhq's addition): IM:385-493 with
+ * the colours replaced.  The 3 K P nextFloat draws of the random population are
+ * still made and thrown away, so after creation the generator is where
+ * hq_search_create leaves it; `population` ([P][4K], P = params->population) is
+ * what gets evaluated, ranked (IM:843-856, the first of equal minima), recorded
+ * as best and moved by iteration 1.  Everything after creation is
+ * hq_search_create's search: hq_search_set_lloyd, "sa_device", "sa_graph", the
+ * communicator paths (every rank passes the same population).  A population
+ * equal to the draws is hq_search_create bit for bit; population NULL is
+ * hq_search_create itself.  .w is stored as 0.  HQ_ERR_ARG: a channel that is
+ * not finite or lies outside [0, 1], where the search keeps its colours
+ * (SW:96-98). */
+int hq_search_create_from(hq_ctx *ctx, const hq_swasa_params *params, int K, uint64_t seed,
+                          const float *population, hq_search **out);
 int hq_search_run(hq_search *s, int iterations, int *ran);
 int hq_search_best(const hq_search *s, float *colors, double *best_error, int *iteration);
 void hq_search_destroy(hq_search *s);
@@ -291,6 +346,14 @@ typedef int (*hq_refine_fn)(void *user, float *palettes, int P, int K);
 int hq_swasa_search_host_lloyd(const hq_swasa_params *params, int K, uint64_t seed, int iterations,
                                hq_eval_fn eval, hq_refine_fn refine, int every, void *user,
                                float *best_colors, double *best_error, double *trace);
+/* The same from a given population (hq_search_create_from's semantics, the same
+ * driver code as a host-driven search): population [P][4K] or NULL, which is
+ * hq_swasa_search_host_lloyd.  HQ_ERR_ARG: a channel that is not finite or lies
+ * outside [0, 1], a null eval. */
+int hq_swasa_search_host_from(const hq_swasa_params *params, int K, uint64_t seed, int iterations,
+                              hq_eval_fn eval, hq_refine_fn refine, int every,
+                              const float *population, void *user,
+                              float *best_colors, double *best_error, double *trace);
 
 /* Kernel timing of the dominant kernels, measured with HIP events on the
  * context stream while enabled (bench.py roofline). */
@@ -299,7 +362,7 @@ int hq_profile_enable(hq_ctx *ctx, int on);
  * per-evaluation RCCL all-reduce or all-gather, with a communicator), "centroid"
  * (hq_cluster_sums' kernel), "lloyd" (the update kernel of a device-resident
  * hybrid iteration, whose assign-only pass and sums kernel count under "grid",
- * "assign" and "centroid"); returns total ms and launch
+ * "assign" and "centroid"), "hist" (hq_color_histogram's kernel); returns total ms and launch
  * count (HIP events on the context stream). */
 int hq_profile_get(hq_ctx *ctx, const char *kernel, double *total_ms, int64_t *launches);
 int hq_profile_reset(hq_ctx *ctx);
