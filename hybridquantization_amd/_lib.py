@@ -70,6 +70,10 @@ SIGNATURES = {
     "hq_centroids_from_sums": (C.c_int, [_i64, C.c_int64, C.c_int, C.c_int, _f]),
     "hq_refine_population": (C.c_int, [_ctx, _f, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _d,
                                        _i32, _d]),
+    "hq_cluster_errors": (C.c_int, [_ctx, C.c_int, C.c_int, _i64, _f]),
+    "hq_reseed_unused": (C.c_int, [_i64, _f, C.c_int, C.c_int, C.c_int, _f, C.POINTER(C.c_int)]),
+    "hq_repair_population": (C.c_int, [_ctx, _f, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int,
+                                       _d, _i32, _d]),
     "hq_color_histogram": (C.c_int, [_ctx, C.c_int, _i64, _i64]),
     "hq_median_cut": (C.c_int, [_i64, C.c_int, C.c_int64, C.c_int, _f, C.POINTER(C.c_int)]),
     "hq_quantize": (C.c_int, [_ctx, _f, C.c_int64, _f, C.c_int, _f, _i32]),
@@ -86,6 +90,7 @@ SIGNATURES = {
     "hq_search_best": (C.c_int, [C.c_void_p, _f, _d, C.POINTER(C.c_int)]),
     "hq_search_destroy": (None, [C.c_void_p]),
     "hq_search_set_lloyd": (C.c_int, [C.c_void_p, C.c_int]),
+    "hq_search_set_repair": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "hq_swasa_search_host": (C.c_int, [C.POINTER(hq_swasa_params), C.c_int, C.c_uint64,
                                        C.c_int, EVAL_FN, C.c_void_p, _f, _d, _d]),
     "hq_swasa_search_host_lloyd": (C.c_int, [C.POINTER(hq_swasa_params), C.c_int, C.c_uint64,

@@ -272,6 +272,10 @@ int SearchDriver::run(int iterations, int* ran, std::vector<double>* trace) {
             const int rr = refine_(current_.data(), P_, K_);
             if (rr) { if (ran) *ran = done; return rr; }
         }
+        if (repair_every_ > 0 && repair_ && ite % repair_every_ == 0) {  // repair iteration: unused colours reseeded
+            const int rr = repair_(current_.data(), P_, K_);
+            if (rr) { if (ran) *ran = done; return rr; }
+        }
         int rc = eval_(current_.data(), P_, K_, errors_.data());      // IM:515
         if (rc) { if (ran) *ran = done; return rc; }
         double minerror = std::numeric_limits<double>::max();

@@ -277,6 +277,31 @@ struct ClusterArgs {
     uint32_t qspan;         // quads of 4 pixels per workgroup      } launcher
 };
 
+// Per-colour error statistics of the last evaluated population (hq_errsum.hip,
+// hq_cluster_errors): ClusterArgs' view of the index images and the pixels, plus
+// the error image the cost kernels stored and the prepared palettes.
+struct ClusterErrArgs {
+    const void* idx;        // [P][idx_pitch] index images over the extended rows: u8, u16 or u32
+    const float* R;         // planar, extended rows (padded to a multiple of 4 floats)
+    const float* G;
+    const float* B;
+    const uint32_t* rgbx;   // packed 8-bit R,G,B when the argmin read it, else null
+    const float* pix_err;   // [P][err_pitch] per-pixel dE of the owned rows (CostArgs::pix_err)
+    const float4* pal;      // [P][pal_pitch] the prepared palettes (.w = 0)
+    unsigned long long* stats;  // [P][K][4] sum of RN(e 2^20), count, key of the worst movable pixel
+                                // ((bits of e) << 32 | 2^32 - 1 - position; 0: none), 0 (zeroed before the launch)
+    float4* worst;          // [P][K] (R, G, B, 0) of that pixel, zeros without one
+    int* bad;               // set to 1 by an owned pixel whose dE is not a finite number in [0, 2^20)
+    int64_t idx_pitch;      // elements per palette
+    int64_t err_pitch;
+    int64_t pal_pitch;
+    uint32_t q0, q1;        // the owned rows: positions [q0, q1) of the extended rows
+    uint32_t pos0;          // position y w + x in the full image of extended position 0
+    int P, K;
+    int nblocks;            // workgroups per group of 4 palettes   } set by the
+    uint32_t qspan;         // quads of 4 pixels per workgroup      } launcher
+};
+
 // Colour histogram of the owned rows (hq_hist.hip, hq_color_histogram): per cell
 // of a 2^bits grid per channel the sum of its pixels and their count, in the
 // units of ClusterArgs::sums.
@@ -305,6 +330,20 @@ struct LloydArgs {
     PaletteArgs prep;          // outputs of the palette prep of the updated candidates
     int K;
     int bytes;                 // sums in units of 1/255 (the packed image), else 2^-32
+};
+
+// reseed_kernel (hq_search.hip): the repair move of a device-resident repair
+// iteration, hq_reseed_unused's rule on the device.  Unused candidate colours of
+// palette p become worst pixels of the clusters with the most error, in place;
+// the palette is prepared again (prep's outputs) and the statistics it read are
+// zeroed for the next repair iteration.
+struct ReseedArgs {
+    unsigned long long* stats;  // [P][K][4] ClusterErrArgs::stats of the error pass
+    const float4* worst;       // [P][K] ClusterErrArgs::worst
+    float* cand;               // [P][4K] the search's candidates (the next sa_step's cand_in)
+    PaletteArgs prep;          // outputs of the palette prep of the repaired candidates
+    int K;
+    int max_moves;             // colours moved per palette at most (< 0: no limit)
 };
 
 // Generic two-pass path (any half-width), one palette per launch.

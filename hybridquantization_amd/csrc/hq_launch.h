@@ -93,6 +93,7 @@ bool allow_dyn_lds(const void* fn, size_t bytes);
 hipError_t launch_prep_palette(const PaletteArgs&, int P, hipStream_t);
 hipError_t launch_sa_step(const SaArgs&, hipStream_t);
 hipError_t launch_lloyd_update(const LloydArgs&, int P, hipStream_t);
+hipError_t launch_reseed(const ReseedArgs&, int P, hipStream_t);
 hipError_t launch_build_grid(const GridArgs&, int P, hipStream_t);
 hipError_t launch_finalize(const FinalizeArgs&, int P, hipStream_t);
 // hq_assign.hip
@@ -118,6 +119,8 @@ hipError_t launch_cost_generic(const GenArgs&, int de, int idx_bytes, hipStream_
 hipError_t launch_cost_tiled_generic(const GenArgs&, int de, int idx_bytes, hipStream_t);
 // hq_centroid.hip: per-colour pixel sums; idx_bytes 1, 2 or 4, num_cu sizes the grid
 hipError_t launch_cluster_sums(const ClusterArgs&, int idx_bytes, int num_cu, hipStream_t);
+// hq_errsum.hip: per-colour error sums and worst pixels, then the gather of their colours
+hipError_t launch_cluster_errors(const ClusterErrArgs&, int idx_bytes, int num_cu, hipStream_t);
 // hq_hist.hip: the colour histogram of the owned rows; num_cu sizes the grid
 hipError_t launch_color_histogram(const HistArgs&, int num_cu, hipStream_t);
 // hq_setup.hip

@@ -88,7 +88,11 @@ constexpr int kProfEvents = 14;
 // its assign-only pass (grid 14, 15; assign 16, 17: enqueue_core's slots 0 .. 3
 // shifted by kProfLloyd), the sums kernel (18, 19) and the update kernel (20, 21).
 constexpr int kProfLloyd = kProfEvents;
-constexpr int kProfSearchEvents = kProfLloyd + 8;
+// ... and, when it is a repair iteration, the pairs of its error pass (grid 22, 23; assign 24,
+// 25; cost 26, 27: enqueue_core's slots 0 .. 5 shifted by kProfRepair), the error kernels
+// (28, 29) and the reseed kernel (30, 31).
+constexpr int kProfRepair = kProfLloyd + 8;
+constexpr int kProfSearchEvents = kProfRepair + 10;
 
 }  // namespace
 
@@ -145,6 +149,10 @@ struct hq_ctx {
     // condition of the planar form's sums (-1: not established yet for this image)
     int planar_ok = -1;
     DevBuf d_hist;             // hq_color_histogram: [2^(3 bits)][4] int64 cells, then the range flag
+    // hq_cluster_errors: the error image on the device is that of the last evaluation (option
+    // "pixel_err" was on when hq_eval_population[_partial] enqueued it; read with sums_ok)
+    bool err_ok = false;
+    DevBuf d_errstat, d_worst; // [P][K][4] u64 statistics, then the flag; [P][K] float4 worst pixels
 
     // options
     int G2 = 32;           // argmin grid resolution (0 = exhaustive)
@@ -191,10 +199,11 @@ struct hq_ctx {
     // profiling
     bool prof = false;
     ProfSlot prof_assign, prof_cost, prof_grid, prof_finalize, prof_sa, prof_comm, prof_centroid, prof_lloyd,
-        prof_hist;
+        prof_hist, prof_errsum, prof_reseed;
     // profiling: start/stop of grid, assign, cost, finalize, [sa_step], the collective
     hipEvent_t ev[kProfEvents] = {};
     hipEvent_t ev_hist[2] = {};  // ... and of hq_color_histogram's kernel
+    hipEvent_t ev_err[2] = {};   // ... and of hq_cluster_errors' kernels (made at the first profiled call)
     int num_cu = 256;
     size_t lds_optin = 160 * 1024;  // per-workgroup LDS a kernel may opt into (hq_create's query)
 };
@@ -211,6 +220,8 @@ struct hq_search {
     hq_swasa_params prm{};
     int P = 0, ite = 0, st = 0, cd = 0;  // state and candidate buffer parities
     int every = 0;                       // hq_search_set_lloyd: iteration ite % every == 0 is hybrid (0: none)
+    int repair_every = 0;                // hq_search_set_repair: iteration ite % repair_every == 0 repairs (0: none)
+    int repair_moves = -1;               // ... at most so many colours per palette (< 0: no limit)
     int nch = 1;                         // chunked palettes (256 < K <= 16384): chunks per palette
     bool fold = false;                   // accept steps reduce the partials (no finalize launch)
     ncclComm_t comm = nullptr;           // the context's communicator at hq_search_create
@@ -243,6 +254,16 @@ int fail(hq_ctx* c, int code, const char* fmt, ...) {
             return fail((ctx), _e == hipErrorOutOfMemory ? HQ_ERR_NOMEM : HQ_ERR_DEVICE,        \
                         "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
     } while (0)
+
+// Option "pixel_err" forced on for a call's own evaluations, the caller's value back on every way out.
+struct PixelErrScope {
+    hq_ctx* c;
+    int was;
+    explicit PixelErrScope(hq_ctx* c_) : c(c_), was(c_->pixel_err) { c->pixel_err = 1; }
+    ~PixelErrScope() { c->pixel_err = was; }
+    PixelErrScope(const PixelErrScope&) = delete;
+    PixelErrScope& operator=(const PixelErrScope&) = delete;
+};
 
 #define NCCL_TRY(ctx, expr)                                                                     \
     do {                                                                                        \
@@ -699,7 +720,12 @@ int palette_slice(hq_ctx* c, int P, int* lo, int* n) {
 // without making that set the current one: c->acc_par stays the set of the
 // last full pass (what sa_args, the fold and the finalize read), and the full
 // pass that follows takes, and zeroes, the same set again.
-int enqueue_core(hq_ctx* c, int P, int K, const hipEvent_t* ev, bool fold = false, bool assign_only = false) {
+// err_pass (a repair iteration's first pass): grid, assign and cost -- the index
+// images and, with option "pixel_err" in force, the error image the error kernel
+// reads -- but no finalize and no collective, into the other set like an
+// assign-only pass and for the same reason: nothing reads its sums.
+int enqueue_core(hq_ctx* c, int P, int K, const hipEvent_t* ev, bool fold = false, bool assign_only = false,
+                 bool err_pass = false) {
     const Geom& g = c->g;
     hipStream_t s = c->stream;
     const int nch = c->nch_cur, Ks = nch > 1 ? kMaxK : K;
@@ -714,7 +740,7 @@ int enqueue_core(hq_ctx* c, int P, int K, const hipEvent_t* ev, bool fold = fals
         hq_ctx* c;
         bool on;
         ~ParRestore() { if (on) c->acc_par ^= 1; }
-    } restore{c, assign_only};
+    } restore{c, assign_only || err_pass};
     const GridArgs ga = grid_args(c, Ps, Ks, so);
     auto timed = [&](int slot) {
         if (ev) set_launch_events(ev[2 * slot], ev[2 * slot + 1]);
@@ -803,6 +829,14 @@ int enqueue_core(hq_ctx* c, int P, int K, const hipEvent_t* ev, bool fold = fals
         int rc = nch > 1 ? enqueue_generic_cost(c, Pl, c->d_idx16.p, 2, nch * kMaxK, ev, lo)
                          : enqueue_generic_cost(c, Pl, c->d_idx.p, 1, kMaxK, ev, lo);
         if (rc) return rc;
+    }
+    if (err_pass) {
+        c->slice_lo = lo;
+        c->slice_n = Pl;
+        c->last_P = P;
+        c->K_cur = K;
+        c->last_nch = nch;
+        return HQ_OK;
     }
     if (!fold) {  // (a folding search's accept step reads the sums itself)
         FinalizeArgs fa{ga.acc_zero, ga.used_glob, used_stride(Ps), c->d_out.as<double>() + (int64_t)lo * (1 + K),
@@ -942,6 +976,7 @@ int eval_partial_into_hout(hq_ctx* c, const float* palettes, int P, int K) {
     c->pal_generic = false;  // device-resident searches generate clamped palettes
     c->nch_cur = 1;
     c->sums_ok = rc == HQ_OK;
+    c->err_ok = c->sums_ok && c->pixel_err;
     return rc;
 }
 
@@ -1002,6 +1037,89 @@ int cluster_sums(hq_ctx* c, int P, int K, int64_t* out, int64_t* den) {
         return fail(c, HQ_ERR_UNSUPPORTED, "planar image with a pixel outside [0, 1] or not finite: no exact sums");
     std::memcpy(out, h.data(), sizeof(int64_t) * n4);
     *den = u8 ? 255 : (int64_t)1 << 32;
+    return HQ_OK;
+}
+
+// The error kernel's arguments for the index images, the error image and the
+// prepared palettes of the last evaluation of P palettes of K colours, into
+// d_errstat ([P][K][4], then the flag) and d_worst ([P][K]).
+ClusterErrArgs cluster_err_args(hq_ctx* c, int P, int K, int* idx_bytes) {
+    const Geom& g = c->g;
+    const ClusterArgs ca = cluster_args(c, P, K, idx_bytes);
+    ClusterErrArgs ea{};
+    ea.idx = ca.idx;
+    ea.R = ca.R;
+    ea.G = ca.G;
+    ea.B = ca.B;
+    ea.rgbx = ca.rgbx;
+    ea.pix_err = c->d_pixerr.as<float>();
+    ea.pal = c->d_pal.as<float4>();
+    ea.stats = c->d_errstat.as<unsigned long long>();
+    ea.worst = c->d_worst.as<float4>();
+    ea.bad = reinterpret_cast<int*>(c->d_errstat.as<int64_t>() + (size_t)P * K * 4);
+    ea.idx_pitch = g.idx_pitch;
+    ea.err_pitch = (int64_t)g.W * (g.r1 - g.r0);
+    // chunked palettes: a palette's nch sub-palettes of 256 lie back to back, colour k at k
+    ea.pal_pitch = c->last_nch > 1 ? (int64_t)c->last_nch * kMaxK : std::max(K, kMaxK);
+    ea.q0 = ca.q0;
+    ea.q1 = ca.q1;
+    ea.pos0 = (uint32_t)((int64_t)g.e0 * g.W);
+    ea.P = P;
+    ea.K = K;
+    return ea;
+}
+
+// hq_cluster_errors into err ([P][K][4]) and worst ([P][K][4]); nothing is written
+// unless HQ_OK, or -- ignore_bad, the repair move inside a search -- whatever the
+// flag says (the pixels it stands for are left out either way).  The index
+// images, the error image, the counter sets and d_sums stay what they are.
+int cluster_errors(hq_ctx* c, int P, int K, int64_t* err, float* worst, bool ignore_bad = false) {
+    if (!c->have_image || !c->sums_ok)
+        return fail(c, HQ_ERR_STATE, "no population evaluated by hq_eval_population[_partial] on this image "
+                                     "since the last search run");
+    if (P != c->last_P || K != c->K_cur)
+        return fail(c, HQ_ERR_STATE, "P=%d, K=%d: the last evaluation had P=%d, K=%d", P, K, c->last_P, c->K_cur);
+    const Geom& g = c->g;
+    const int64_t n_own = (int64_t)g.W * (g.r1 - g.r0);
+    if (!c->err_ok || c->d_pixerr.bytes < sizeof(float) * (size_t)P * (size_t)n_own)
+        return fail(c, HQ_ERR_STATE, "option pixel_err was off at the last evaluation: no error image");
+    if (c->slice_n != c->last_P || c->slice_ranks > 1 || (c->psplit && c->comm))
+        return fail(c, HQ_ERR_UNSUPPORTED, "palette slice: this device holds %d of the %d index images",
+                    c->slice_n, c->last_P);
+    if ((int64_t)g.W * g.H >= ((int64_t)1 << 32))
+        return fail(c, HQ_ERR_UNSUPPORTED, "image of 2^32 pixels or more: a position does not fit 32 bits");
+    int rc = bind(c);
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    const size_t n4 = (size_t)P * K * 4;
+    HIP_TRY(c, c->d_errstat.ensure(sizeof(int64_t) * (n4 + 1)));
+    HIP_TRY(c, c->d_worst.ensure(sizeof(float) * n4));
+    HIP_TRY(c, hipMemsetAsync(c->d_errstat.p, 0, sizeof(int64_t) * (n4 + 1), s));
+    int idx_bytes = 1;
+    const ClusterErrArgs ea = cluster_err_args(c, P, K, &idx_bytes);
+    if (c->prof && !c->ev_err[0])
+        for (auto& e : c->ev_err) HIP_TRY(c, hipEventCreate(&e));
+    if (c->prof) set_launch_events(c->ev_err[0], c->ev_err[1]);
+    const hipError_t e = launch_cluster_errors(ea, idx_bytes, c->num_cu, s);
+    set_launch_events(nullptr, nullptr);
+    HIP_TRY(c, e);
+    std::vector<uint64_t> h(n4 + 1);
+    std::vector<float> hw(n4);
+    HIP_TRY(c, hipMemcpyAsync(h.data(), c->d_errstat.p, sizeof(int64_t) * (n4 + 1), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(hw.data(), c->d_worst.p, sizeof(float) * n4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (c->prof) prof_add(c, c->prof_errsum, c->ev_err[0], c->ev_err[1]);
+    if (h[n4] != 0 && !ignore_bad)
+        return fail(c, HQ_ERR_UNSUPPORTED, "a pixel's dE is not a finite number below 2^20 (dE94's NaN, a non-finite "
+                                           "colour or LabRef): no exact error sums");
+    for (size_t i = 0; i < n4; i += 4) {
+        const uint64_t key = h[i + 2];
+        err[i] = (int64_t)h[i];
+        err[i + 1] = (int64_t)h[i + 1];
+        err[i + 2] = (int64_t)(key >> 32);
+        err[i + 3] = key ? (int64_t)(0xffffffffu - (uint32_t)key) : -1;
+    }
+    std::memcpy(worst, hw.data(), sizeof(float) * n4);
     return HQ_OK;
 }
 
@@ -1139,11 +1257,33 @@ int lloyd_scope(hq_search* s) {
     return HQ_OK;
 }
 
-// A run of `iterations` from iteration `ite` (the last one done) holds a hybrid iteration.
-bool lloyd_in_run(const hq_search* s, int ite, int iterations) {
-    if (s->every <= 0) return false;
+// A run of `iterations` from iteration `ite` (the last one done) holds an iteration
+// that is a multiple of `every`.
+bool period_in_run(const hq_search* s, int every, int ite, int iterations) {
+    if (every <= 0) return false;
     const int last = (int)std::min<int64_t>((int64_t)ite + iterations, s->prm.imax);
-    return last / s->every > ite / s->every;
+    return last / every > ite / every;
+}
+// ... a hybrid iteration.
+bool lloyd_in_run(const hq_search* s, int ite, int iterations) { return period_in_run(s, s->every, ite, iterations); }
+
+// ---- repair iterations (hq_search_set_repair) ----------------------------------
+// hq_repair_population's scope, and a dE type whose costs are numbers.
+int repair_scope(hq_search* s) {
+    hq_ctx* c = s->ctx;
+    if (c->de_type == HQ_DE_CIE94)
+        return fail(c, HQ_ERR_UNSUPPORTED, "repair iterations on a dE94 context: its costs are NaN on real images");
+    if (c->have_image && (c->g.r0 != 0 || c->g.r1 != c->g.H))
+        return fail(c, HQ_ERR_STATE, "sharded context: a repair iteration needs the whole image");
+    if (c->comm && c->nranks > 1)
+        return fail(c, HQ_ERR_UNSUPPORTED, "repair iterations with a communicator of %d ranks", c->nranks);
+    if (c->psplit || c->slice_ranks > 1) return fail(c, HQ_ERR_UNSUPPORTED, "repair iterations on a palette slice");
+    if (!s->driver && s->nch > 1)
+        return fail(c, HQ_ERR_UNSUPPORTED, "repair iterations of a device-resident search need K <= %d (K = %d): "
+                                           "set option sa_device 0 before hq_search_create", kMaxK, s->K);
+    if (c->have_image && (int64_t)c->g.W * c->g.H >= ((int64_t)1 << 32))
+        return fail(c, HQ_ERR_UNSUPPORTED, "image of 2^32 pixels or more: a position does not fit 32 bits");
+    return HQ_OK;
 }
 
 // The planar form's sums need every owned pixel finite and in [0, 1]: a property
@@ -1194,6 +1334,36 @@ int enqueue_lloyd(hq_search* s, const hipEvent_t* ev) {
     const LloydArgs la{ca.sums, s->cand[s->cd].as<float>(), prep_args(c, s->K), s->K, sums_u8(c) ? 1 : 0};
     if (ev) set_launch_events(ev[kProfLloyd + 6], ev[kProfLloyd + 7]);
     e = launch_lloyd_update(la, s->P, c->stream);
+    set_launch_events(nullptr, nullptr);
+    HIP_TRY(c, e);
+    return HQ_OK;
+}
+
+// The repair move of a device-resident repair iteration, after the sa_step that
+// generated and prepared the candidates (now cand[cd]) and after the k-means move
+// when the iteration is hybrid too: a full pass that stores the error image
+// (option "pixel_err" forced on for it alone), the error kernels into d_errstat
+// (zero on entry: the run's memset, then the reseed kernel's own zeroing) and
+// d_worst, and the reseed kernel, which prepares the repaired candidates for the
+// evaluation that follows.  The flag of pixels without a usable dE is not read:
+// they are left out, as the host-driven form leaves them out.
+int enqueue_repair(hq_search* s, const hipEvent_t* ev) {
+    hq_ctx* c = s->ctx;
+    int rc;
+    {
+        const PixelErrScope scope(c);
+        rc = enqueue_core(c, s->P, s->K, ev ? ev + kProfRepair : nullptr, s->fold, false, true);
+    }
+    if (rc) return rc;
+    int idx_bytes = 1;
+    const ClusterErrArgs ea = cluster_err_args(c, s->P, s->K, &idx_bytes);
+    if (ev) set_launch_events(ev[kProfRepair + 6], ev[kProfRepair + 7]);
+    hipError_t e = launch_cluster_errors(ea, idx_bytes, c->num_cu, c->stream);
+    set_launch_events(nullptr, nullptr);
+    HIP_TRY(c, e);
+    const ReseedArgs ra{ea.stats, ea.worst, s->cand[s->cd].as<float>(), prep_args(c, s->K), s->K, s->repair_moves};
+    if (ev) set_launch_events(ev[kProfRepair + 8], ev[kProfRepair + 9]);
+    e = launch_reseed(ra, s->P, c->stream);
     set_launch_events(nullptr, nullptr);
     HIP_TRY(c, e);
     return HQ_OK;
@@ -1295,6 +1465,16 @@ int device_search_run(hq_search* s, int iterations, int* ran) {
     const size_t sums_bytes = sizeof(int64_t) * ((size_t)s->P * s->K * 4 + 1);
     if (lloyd) HIP_TRY(c, c->d_sums.ensure(sums_bytes));
     std::vector<char> hybrid;  // per iteration of this run (profiling: whose extra events were recorded)
+    // repair iterations in this run: the same for the error image, the statistics and the
+    // worst pixels -- nothing of it without one
+    const bool repair = period_in_run(s, s->repair_every, s->ite, iterations);
+    const size_t stat_bytes = sizeof(int64_t) * ((size_t)s->P * s->K * 4 + 1);
+    if (repair) {
+        HIP_TRY(c, c->d_pixerr.ensure(sizeof(float) * (size_t)s->P * std::max<int64_t>((int64_t)c->g.W * (c->g.r1 - c->g.r0), 1)));
+        HIP_TRY(c, c->d_errstat.ensure(stat_bytes));
+        HIP_TRY(c, c->d_worst.ensure(sizeof(float) * (size_t)s->P * s->K * 4));
+    }
+    std::vector<char> repairs;
     // option sa_graph: the run's kernels go into one hipGraph (stream capture),
     // replayed as a whole -- a chain of dependent kernels costs ~2.7 us per
     // kernel from the stream and ~1.8 from a graph (profiles/r04_graph_gap_
@@ -1317,6 +1497,13 @@ int device_search_run(hq_search* s, int iterations, int* ran) {
             HIP_TRY(c, e);
         }
     }
+    if (repair) {
+        const hipError_t e = hipMemsetAsync(c->d_errstat.p, 0, stat_bytes, c->stream);
+        if (e != hipSuccess) {
+            (void)abort_capture(0);
+            HIP_TRY(c, e);
+        }
+    }
     for (; done < iterations && s->ite < s->prm.imax; ++done) {
         const int ite = ++s->ite;
         s->pol->reduce_temperature_if_necessary(ite);                  // IM:507
@@ -1327,6 +1514,8 @@ int device_search_run(hq_search* s, int iterations, int* ran) {
             return abort_capture(rc);
         hybrid.push_back(s->every > 0 && ite % s->every == 0);
         if (hybrid.back() && (rc = enqueue_lloyd(s, ev))) return abort_capture(rc);
+        repairs.push_back(s->repair_every > 0 && ite % s->repair_every == 0);
+        if (repairs.back() && (rc = enqueue_repair(s, ev))) return abort_capture(rc);
         if ((rc = enqueue_core(c, s->P, s->K, ev, s->fold))) return abort_capture(rc);
         s->t_acc = s->pol->temperature();     // SW:54-57 at this iteration
         s->keep_acc = s->pol->keep_threshold(ite);
@@ -1362,6 +1551,13 @@ int device_search_run(hq_search* s, int iterations, int* ran) {
         const hipEvent_t* ev = &s->pev[(size_t)kProfSearchEvents * i];
         prof_accumulate(c, ev, !s->fold);
         prof_accumulate_sa(c, ev);
+        if (repairs[i]) {  // (events of an earlier run's repair iteration may sit in these slots)
+            if (c->G2 > 0) prof_add(c, c->prof_grid, ev[kProfRepair], ev[kProfRepair + 1]);
+            prof_add(c, c->prof_assign, ev[kProfRepair + 2], ev[kProfRepair + 3]);
+            prof_add(c, c->prof_cost, ev[kProfRepair + 4], ev[kProfRepair + 5]);
+            prof_add(c, c->prof_errsum, ev[kProfRepair + 6], ev[kProfRepair + 7]);
+            prof_add(c, c->prof_reseed, ev[kProfRepair + 8], ev[kProfRepair + 9]);
+        }
         if (!hybrid[i]) continue;  // (events of an earlier run's hybrid iteration may sit in these slots)
         if (c->G2 > 0) prof_add(c, c->prof_grid, ev[kProfLloyd], ev[kProfLloyd + 1]);
         prof_add(c, c->prof_assign, ev[kProfLloyd + 2], ev[kProfLloyd + 3]);
@@ -1443,13 +1639,15 @@ void hq_destroy(hq_ctx* c) {
                       &c->d_dup, &c->d_pflags, &c->d_lvl1, &c->d_lvl2, &c->d_idx,
                       &c->d_used_mask, &c->d_acc, &c->d_out, &c->d_gen_t, &c->d_taps,
                       &c->d_vfrag16, &c->d_vfrag16p, &c->d_vfragm, &c->d_htaps, &c->d_idx32, &c->d_used32, &c->d_pixerr, &c->d_idx16, &c->d_dist, &c->d_l1n, &c->d_l2n, &c->d_sums,
-                      &c->d_hist})
+                      &c->d_hist, &c->d_errstat, &c->d_worst})
         b->release();
     if (c->h_pal) (void)hipHostFree(c->h_pal);
     if (c->h_out) (void)hipHostFree(c->h_out);
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
     for (auto& e : c->ev_hist)
+        if (e) (void)hipEventDestroy(e);
+    for (auto& e : c->ev_err)
         if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -1733,6 +1931,64 @@ int hq_refine_population(hq_ctx* c, float* palettes, int P, int K, int steps, fl
     return HQ_OK;
 }
 
+int hq_cluster_errors(hq_ctx* c, int P, int K, int64_t* err, float* worst_rgb) {
+    if (!c) return HQ_ERR_ARG;
+    if (!err || !worst_rgb || P < 1 || K < 1) return fail(c, HQ_ERR_ARG, "bad err / worst_rgb / P=%d / K=%d", P, K);
+    return cluster_errors(c, P, K, err, worst_rgb);
+}
+
+int hq_repair_population(hq_ctx* c, float* palettes, int P, int K, int steps, float delta, int max_moves,
+                         int keep_best, double* costs, int32_t* used, double* trace) {
+    if (!costs) return fail(c, HQ_ERR_ARG, "null output");
+    int rc = check_eval_args(c, palettes, P, K);
+    if (rc) return rc;
+    if (steps < 0) return fail(c, HQ_ERR_ARG, "steps=%d < 0", steps);
+    if (c->comm && c->nranks > 1)
+        return fail(c, HQ_ERR_UNSUPPORTED, "hq_repair_population with a communicator of %d ranks: merge the "
+                                           "shards' hq_cluster_errors yourself", c->nranks);
+    if (c->slice_ranks > 1) return fail(c, HQ_ERR_UNSUPPORTED, "hq_repair_population on a palette slice");
+    if (c->g.r0 != 0 || c->g.r1 != c->g.H)
+        return fail(c, HQ_ERR_STATE, "sharded context: hq_repair_population needs the whole image");
+    const PixelErrScope scope(c);  // the evaluations below store their error images
+    const size_t n4 = (size_t)P * K * 4, nu = (size_t)P * K;
+    std::vector<float> cur(palettes, palettes + n4), best_pal, worst(n4);
+    std::vector<double> cst(P), best_cost;
+    std::vector<int32_t> usd(nu), best_used;
+    std::vector<int64_t> err(n4);
+    std::vector<int> moved(P);
+    if ((rc = hq_eval_population(c, cur.data(), P, K, delta, cst.data(), usd.data()))) return rc;
+    if (trace) std::copy(cst.begin(), cst.end(), trace);
+    if (keep_best) best_pal = cur, best_cost = cst, best_used = usd;
+    for (int s = 1; s <= steps; ++s) {
+        if ((rc = cluster_errors(c, P, K, err.data(), worst.data()))) return rc;
+        if ((rc = hq_reseed_unused(err.data(), worst.data(), P, K, max_moves, cur.data(), moved.data())))
+            return fail(c, rc, "hq_reseed_unused failed");
+        if (std::all_of(moved.begin(), moved.end(), [](int m) { return m == 0; })) {
+            // nothing left to repair: the remaining steps repeat this one
+            for (int t = s; trace && t <= steps; ++t) std::copy(cst.begin(), cst.end(), trace + (size_t)t * P);
+            break;
+        }
+        if ((rc = hq_eval_population(c, cur.data(), P, K, delta, cst.data(), usd.data()))) return rc;
+        if (trace) std::copy(cst.begin(), cst.end(), trace + (size_t)s * P);
+        for (int p = 0; keep_best && p < P; ++p) {
+            // strictly lower (the earliest step keeps a tie); a number beats a NaN, never the reverse
+            const double a = cst[p], b = best_cost[p];
+            if (!(a < b || (b != b && a == a))) continue;
+            best_cost[p] = a;
+            std::copy(cur.begin() + (size_t)p * K * 4, cur.begin() + (size_t)(p + 1) * K * 4,
+                      best_pal.begin() + (size_t)p * K * 4);
+            std::copy(usd.begin() + (size_t)p * K, usd.begin() + (size_t)(p + 1) * K, best_used.begin() + (size_t)p * K);
+        }
+    }
+    const std::vector<float>& rp = keep_best ? best_pal : cur;
+    const std::vector<double>& rc_ = keep_best ? best_cost : cst;
+    const std::vector<int32_t>& ru = keep_best ? best_used : usd;
+    std::copy(rp.begin(), rp.end(), palettes);
+    std::copy(rc_.begin(), rc_.end(), costs);
+    if (used) std::copy(ru.begin(), ru.end(), used);
+    return HQ_OK;
+}
+
 int hq_rgb_to_xyz(hq_ctx* c, const float* R, const float* G, const float* B, int64_t n,
                   float* xyz4) {
     if (!c || !R || !G || !B || !xyz4 || n < 1) return HQ_ERR_ARG;
@@ -1925,6 +2181,19 @@ int hq_search_create_from(hq_ctx* c, const hq_swasa_params* params, int K, uint6
                 return fail(c, rr, "hq_centroids_from_sums failed");
             return rr;
         });
+        // the repair move, host-driven: an evaluation of the candidates that stores their
+        // error image, the error statistics (pixels with no usable dE left out) and the rule
+        s->driver->set_repair([c, delta, s](float* pal, int P, int KK) {
+            const PixelErrScope scope(c);
+            std::vector<double> costs(P);
+            std::vector<int64_t> err((size_t)P * KK * 4);
+            std::vector<float> worst((size_t)P * KK * 4);
+            int rr = hq_eval_population(c, pal, P, KK, delta, costs.data(), nullptr);
+            if (!rr) rr = cluster_errors(c, P, KK, err.data(), worst.data(), true);
+            if (!rr && (rr = hq_reseed_unused(err.data(), worst.data(), P, KK, s->repair_moves, pal, nullptr)))
+                return fail(c, rr, "hq_reseed_unused failed");
+            return rr;
+        });
         s->prm = *params;
         s->P = params->population;
         rc = s->driver->start(population);
@@ -1949,6 +2218,12 @@ int hq_search_run(hq_search* s, int iterations, int* ran) {
             return rc;
         }
     }
+    if (s->ctx && period_in_run(s, s->repair_every, s->driver ? s->driver->iteration() : s->ite, iterations)) {
+        if ((rc = repair_scope(s))) {
+            if (ran) *ran = 0;
+            return rc;
+        }
+    }
     if (!s->driver) {
         rc = bind(s->ctx);
         if (!rc) rc = device_search_run(s, iterations, ran);
@@ -1966,6 +2241,17 @@ int hq_search_set_lloyd(hq_search* s, int every) {
         if (int rc = lloyd_scope(s)) return rc;
     s->every = every;
     if (s->driver) s->driver->set_every(every);
+    return HQ_OK;
+}
+
+int hq_search_set_repair(hq_search* s, int every, int max_moves) {
+    if (!s || !s->ctx) return HQ_ERR_ARG;
+    if (every < 0) return fail(s->ctx, HQ_ERR_ARG, "every=%d < 0", every);
+    if (every > 0)
+        if (int rc = repair_scope(s)) return rc;
+    s->repair_every = every;
+    s->repair_moves = max_moves;
+    if (s->driver) s->driver->set_repair_every(every);
     return HQ_OK;
 }
 
@@ -2014,7 +2300,7 @@ int hq_profile_enable(hq_ctx* c, int on) {
 int hq_profile_reset(hq_ctx* c) {
     if (!c) return HQ_ERR_ARG;
     c->prof_assign = c->prof_cost = c->prof_grid = c->prof_finalize = c->prof_sa = c->prof_comm = c->prof_centroid =
-        c->prof_lloyd = c->prof_hist = ProfSlot{};
+        c->prof_lloyd = c->prof_hist = c->prof_errsum = c->prof_reseed = ProfSlot{};
     return HQ_OK;
 }
 
@@ -2030,6 +2316,8 @@ int hq_profile_get(hq_ctx* c, const char* kernel, double* total_ms, int64_t* lau
     else if (!std::strcmp(kernel, "centroid")) s = &c->prof_centroid;
     else if (!std::strcmp(kernel, "lloyd")) s = &c->prof_lloyd;
     else if (!std::strcmp(kernel, "hist")) s = &c->prof_hist;
+    else if (!std::strcmp(kernel, "errsum")) s = &c->prof_errsum;
+    else if (!std::strcmp(kernel, "reseed")) s = &c->prof_reseed;
     else return fail(c, HQ_ERR_ARG, "unknown kernel '%s'", kernel);
     if (total_ms) *total_ms = s->ms;
     if (launches) *launches = s->launches;

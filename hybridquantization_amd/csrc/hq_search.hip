@@ -948,6 +948,64 @@ __global__ __launch_bounds__(1024) void finalize_kernel(FinalizeArgs a) {
 }
 
 // ----------------------------------------------------------------------------
+// reseed: grid (P), block 1024 (after the kernels that were here before it, which so keep
+// their places in the code object).  The repair move of a repair iteration (libhq's
+// addition), between the error pass + the error kernels and the evaluation:
+// hq_reseed_unused's rule, in the same integers, so the bits are the host's.
+// Thread k < K holds candidate colour k of palette p and its 32 B of statistics
+// (sum, count, key of the worst movable pixel, 0).  A colour with count 0 is a
+// receiver, its rank the number of receivers below it; a colour with count > 0
+// and a key is a donor, its rank the number of donors that precede it under (sum
+// descending, index ascending) -- K comparisons per thread out of LDS, a strict
+// order, so the ranks are a permutation.  The receiver of rank r takes the worst
+// pixel's colour of the donor of rank r while donors and max_moves last, and
+// goes back into the candidate buffer in place (what the next sa_step reads as
+// cand_in); every other colour keeps its bits.  The statistics are zeroed once
+// read, for the next repair iteration, and the palette is prepared again.
+// ----------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void reseed_kernel(ReseedArgs a) {
+    const int p = blockIdx.x, k = threadIdx.x;
+    __shared__ float4 s[kMaxK];
+    __shared__ PrepLds L;
+    __shared__ unsigned long long s_sum[kMaxK];
+    __shared__ uint8_t s_role[kMaxK];  // 1 receiver, 2 donor, 0 neither
+    __shared__ int s_donor[kMaxK];     // the donor of rank r
+    float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4* const cp = reinterpret_cast<float4*>(a.cand) + (int64_t)p * a.K + min(k, a.K - 1);
+    int role = 0;
+    unsigned long long sum = 0ull;
+    if (k < a.K) {
+        ulonglong2* const sp = reinterpret_cast<ulonglong2*>(a.stats + ((int64_t)p * a.K + k) * 4);
+        const ulonglong2 sn = sp[0], kz = sp[1];
+        c = *cp;
+        sum = sn.x;
+        role = sn.y == 0ull ? 1 : (kz.x != 0ull ? 2 : 0);
+        s_sum[k] = sum;
+        s_role[k] = (uint8_t)role;
+        sp[0] = sp[1] = make_ulonglong2(0ull, 0ull);
+    }
+    __syncthreads();
+    int rank = 0, nd = 0;
+    if (k < a.K) {
+        for (int j = 0; j < a.K; ++j) {
+            const int rj = s_role[j];
+            nd += rj == 2;
+            if (role == 1) rank += rj == 1 && j < k;
+            else if (role == 2) rank += rj == 2 && (s_sum[j] > sum || (s_sum[j] == sum && j < k));
+        }
+        if (role == 2) s_donor[rank] = k;
+    }
+    __syncthreads();
+    if (role == 1 && rank < nd && (a.max_moves < 0 || rank < a.max_moves)) {
+        const float4 w = a.worst[(int64_t)p * a.K + s_donor[rank]];
+        c = make_float4(w.x, w.y, w.z, 0.f);
+        *cp = c;
+    }
+    bool nf;
+    (void)prep_palette_body(a.prep, p, c, s, L, true, nf);
+}
+
+// ----------------------------------------------------------------------------
 // Launchers
 // ----------------------------------------------------------------------------
 hipError_t launch_prep_palette(const PaletteArgs& a, int P, hipStream_t s) {
@@ -962,6 +1020,11 @@ hipError_t launch_sa_step(const SaArgs& a, hipStream_t s) {
 
 hipError_t launch_lloyd_update(const LloydArgs& a, int P, hipStream_t s) {
     HQ_LAUNCH(lloyd_update_kernel, dim3(P), dim3(1024), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_reseed(const ReseedArgs& a, int P, hipStream_t s) {
+    HQ_LAUNCH(reseed_kernel, dim3(P), dim3(1024), 0, s, a);
     return hipGetLastError();
 }
 

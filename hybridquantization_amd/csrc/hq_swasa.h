@@ -79,6 +79,10 @@ class SearchDriver {
     // evaluation.  Applies to the iterations that follow.
     void set_refine(PopulationRefine refine) { refine_ = std::move(refine); }
     void set_every(int every) { every_ = every; }
+    // Repair iterations (libhq's addition), the same way with a period of their own:
+    // `repair` runs after `refine` when an iteration is both.
+    void set_repair(PopulationRefine repair) { repair_ = std::move(repair); }
+    void set_repair_every(int every) { repair_every_ = every; }
     const std::vector<float>& best_colors() const { return best_colors_; }
     double best_error() const { return best_error_; }
     int iteration() const { return ite_; }
@@ -89,6 +93,8 @@ class SearchDriver {
     PopulationEval eval_;
     PopulationRefine refine_;
     int every_ = 0;
+    PopulationRefine repair_;
+    int repair_every_ = 0;
     std::vector<float> colors_, current_;   // [P][4K]
     std::vector<double> current_errors_, errors_;
     std::vector<float> best_colors_;

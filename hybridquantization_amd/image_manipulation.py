@@ -203,6 +203,47 @@ class ImageManipulation:
                                              dptr(trace)), ctx)
         return (pal, costs, used, trace) if return_trace else (pal, costs, used)
 
+    # repairing unused colours: libhq's additions (hq_cluster_errors & co., no reference counterpart)
+    def clusterErrors(self, P: int, K: int):
+        """Per palette and colour of the last population evaluated with option
+        "pixel_err" 1: (err int64 (P, K, 4) = (sum of llrint(dE 2**20), count, bits of
+        the worst movable pixel's dE, its position y w + x or -1), worst float32
+        (P, K, 4) = that pixel's (R, G, B, 0))."""
+        ctx = self._require()
+        err = np.zeros((int(P), int(K), 4), np.int64)
+        worst = np.zeros((int(P), int(K), 4), np.float32)
+        check(self._lib.hq_cluster_errors(ctx, int(P), int(K), _lib.i64ptr(err), fptr(worst)), ctx)
+        return err, worst
+
+    @staticmethod
+    def reseedUnused(err, worst, palettes, max_moves=-1):
+        """The repair rule of hq_reseed_unused: palettes (P, 4K) float32 with every unused
+        colour moved onto the worst pixel of the clusters with the most error (at most
+        max_moves per palette, < 0: no limit).  Returns (a new array, moved (P,))."""
+        err = np.ascontiguousarray(err, dtype=np.int64)
+        P, K = err.shape[0], err.shape[1]
+        worst = np.ascontiguousarray(worst, dtype=np.float32).reshape(P, K, 4)
+        pal = _f32(palettes).reshape(P, 4 * K).copy()
+        moved = np.zeros(P, np.int32)
+        check(load().hq_reseed_unused(_lib.i64ptr(err), fptr(worst), P, K, int(max_moves), fptr(pal),
+                                      moved.ctypes.data_as(C.POINTER(C.c_int))))
+        return pal, moved
+
+    def repairPopulation(self, colors, steps, delta: float = 2.0, max_moves=-1, keep_best=True,
+                         return_trace=False):
+        """hq_repair_population: `steps` repair steps on each palette of colors (P, 4K).
+        Returns (palettes (P, 4K), costs (P,), used (P, K)) [, trace (steps + 1, P)]."""
+        ctx = self._require()
+        pal = _f32(np.stack([np.asarray(c, np.float32).reshape(-1) for c in colors])).copy()
+        P, K = pal.shape[0], pal.shape[1] // 4
+        costs = np.zeros(P, np.float64)
+        used = np.zeros((P, K), np.int32)
+        trace = np.zeros((int(steps) + 1, P), np.float64)
+        check(self._lib.hq_repair_population(ctx, fptr(pal), P, K, int(steps), float(delta),
+                                             int(max_moves), int(bool(keep_best)), dptr(costs),
+                                             iptr(used), dptr(trace)), ctx)
+        return (pal, costs, used, trace) if return_trace else (pal, costs, used)
+
     # seeding the search from the image: libhq's additions (hq_color_histogram, hq_median_cut)
     def colorHistogram(self, bits: int = 5):
         """Colour histogram of the owned rows of the image set: (cells int64
@@ -231,7 +272,7 @@ class ImageManipulation:
     def findBestQuantization(self, inlinergbOriginal, inlineScielabOriginal, w, nbOfColors,
                              simulatedAnnealing, filters, absfilters, illuminant,
                              iterations=None, stop=None, lloydSteps=0, lloydEvery=0,
-                             init=None, initBits=5):
+                             init=None, initBits=5, repairEvery=0, repairMoves=-1, repairSteps=0):
         """Full SWASA search (IM:383-591) on the GPU; returns bestColors float[4K].
 
         ``simulatedAnnealing`` is a :class:`~hybridquantization_amd.swasa.SWASA`;
@@ -251,6 +292,13 @@ class ImageManipulation:
         (P, 4K) is the start as given.  ``seedColors`` is then the creation's best
         palette and ``seedError`` its cost, before any iteration.  It composes
         with ``lloydEvery`` and ``lloydSteps``.
+        ``repairEvery`` > 0 (hq_search_set_repair): every iteration whose 1-based count
+        is a multiple of it is a repair iteration -- each candidate's unused colours
+        (at most ``repairMoves``, < 0: no limit) move onto the worst pixels of the
+        clusters with the most error before it is evaluated, after the k-means move
+        when the iteration is hybrid too.  ``repairSteps`` > 0: the best palette is
+        polished by that many repair steps (hq_repair_population, keep_best) before
+        the k-means polish; ``bestErrorSA`` is the search's own error.
         """
         ctx = self._require()
         if not self.openCLFiltersReady:
@@ -282,6 +330,8 @@ class ImageManipulation:
                 self.seedColors, self.seedError = seed, seed_err.value
             if int(lloydEvery) != 0:
                 check(self._lib.hq_search_set_lloyd(handle, int(lloydEvery)), ctx)
+            if int(repairEvery) != 0:
+                check(self._lib.hq_search_set_repair(handle, int(repairEvery), int(repairMoves)), ctx)
             total = params.imax if iterations is None else min(int(iterations), params.imax)
             done = 0
             while done < total:
@@ -303,8 +353,15 @@ class ImageManipulation:
                 print("Final error : %.5f" % err.value)  # IM:589
         finally:
             self._lib.hq_search_destroy(handle)
-        if int(lloydSteps) > 0:
+        if int(repairSteps) > 0 or int(lloydSteps) > 0:
             self.bestErrorSA = self.bestError
+        if int(repairSteps) > 0:
+            pal, costs, _ = self.repairPopulation(best.reshape(1, -1), int(repairSteps), sw.delta,
+                                                  int(repairMoves), keep_best=True)
+            best, self.bestError = pal[0], float(costs[0])
+            if self.verbose:
+                print("Final error after %d repair steps : %.5f" % (int(repairSteps), self.bestError))
+        if int(lloydSteps) > 0:
             pal, costs, _ = self.refinePopulation(best.reshape(1, -1), int(lloydSteps), sw.delta,
                                                   keep_best=True)
             best, self.bestError = pal[0], float(costs[0])

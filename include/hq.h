@@ -199,6 +199,76 @@ int hq_centroids_from_sums(const int64_t *sums, int64_t den, int P, int K, float
 int hq_refine_population(hq_ctx *ctx, float *palettes, int P, int K, int steps, float delta,
                          int keep_best, double *costs, int32_t *used, double *trace);
 
+/* ---- repairing unused colours: libhq's additions, no reference counterpart ----
+ * The cost is mean dE + delta per unused colour (IM:712, SW:74-82), and neither
+ * a k-means move (a colour without pixels keeps its bits) nor a median cut of an
+ * image with few colours (the copies past *made) brings an unused colour back.
+ * The entry points below do: the per-colour error of an evaluated population on
+ * the device, a host rule that moves every unused colour onto the worst pixel of
+ * a cluster that carries much error, and a polish call around the two.
+ *
+ * hq_cluster_errors: per palette and colour of the population last evaluated by
+ * hq_eval_population[_partial] on this context with option "pixel_err" 1 in
+ * force, over the owned rows (halo rows are not counted),
+ * err[((p*K)+k)*4 + {0,1,2,3}]:
+ *  [0] the sum over the pixels assigned to k of llrint(e * 2^20), e the pixel's
+ *      fp32 dE as the cost kernel stored it (hq_get_pixel_errors), widened to
+ *      double: the product is exact, the rounding half to even.  Exact integers,
+ *      independent of any order; no overflow while a cluster's dE sum stays
+ *      below 2^43.
+ *  [1] the count of those pixels: hq_cluster_sums' count.
+ *  [2], [3] the cluster's worst movable pixel.  A pixel is movable when its RGB
+ *      as the argmin saw it (the planar floats, or the packed bytes' value
+ *      k/255 rebuilt in fp32) differs from colour k in at least one channel
+ *      under fp32 != -- moving a colour onto a pixel it already equals changes
+ *      nothing.  The worst one has the largest dE, on a tie the lowest position
+ *      y*w + x in the FULL image.  [2] = the bits of that dE as a non-negative
+ *      integer, [3] = the position; no movable pixel: [2] = 0, [3] = -1.
+ * worst_rgb[((p*K)+k)*4 ..] = (R, G, B, 0) of that pixel as the argmin saw it,
+ * zeros without one.
+ * Shards: [0] and [1] of disjoint shards of one image add up exactly to the
+ * whole image's; [2], [3] and worst_rgb merge by the same rule as inside a
+ * shard -- the larger [2] wins, then the lower [3], worst_rgb follows the winner.
+ * (The whole image's: where the shards' stored dE are.  The cost kernels give a
+ * pixel the same dE bits in every sharding for CIEDE2000; for dE76 and dE94
+ * when a row block starts on a multiple of their tile rows, 16 by default.)
+ * Every argmin path and index width is served, as by hq_cluster_sums, and the
+ * evaluated population is not disturbed (hq_cluster_sums, hq_get_indices and
+ * hq_get_pixel_errors answer after it as before it).
+ * HQ_ERR_STATE: no population evaluated yet, P or K other than that
+ * evaluation's, a search run has evaluated since, or "pixel_err" was off at
+ * that evaluation.  HQ_ERR_UNSUPPORTED: a palette slice ("slice_ranks" > 1,
+ * "palette_split"); a full image of 2^32 pixels or more; an owned pixel whose dE
+ * is not a finite number in [0, 2^20) (dE94's NaN, a non-finite palette colour,
+ * a caller's NaN LabRef) -- such a pixel is counted in [1] but left out of [0]
+ * and of the worst pixel, and both outputs are then left untouched. */
+int hq_cluster_errors(hq_ctx *ctx, int P, int K, int64_t *err, float *worst_rgb);
+/* The repair rule from such statistics (of one context, or several shards'
+ * merged as above).  Host-only, needs no context, integer arithmetic,
+ * deterministic.  Per palette: the receivers are the colours with count 0, in
+ * ascending index; the donors are the colours with count > 0 and [3] >= 0,
+ * ordered by [0] descending, the lower index first on a tie.  The i-th
+ * receiver becomes the i-th donor's worst_rgb, .w = 0, until the receivers, the
+ * donors or max_moves (< 0: no limit) run out.  Each donor gives once and keeps
+ * its own colour.  Two donors cannot hand out equal colours (equal RGB has one
+ * argmin, so the two pixels would sit in one cluster), and a reseeded colour
+ * differs from its donor's (the pixel is movable).  moved[p] (moved may be
+ * NULL) = the number of colours replaced.  HQ_ERR_ARG: a negative count or
+ * sum, P < 1, K < 1, a null pointer; the palettes are then left untouched. */
+int hq_reseed_unused(const int64_t *err, const float *worst_rgb, int P, int K, int max_moves,
+                     float *palettes, int *moved);
+/* Evaluates the P palettes with "pixel_err" forced on for the call (the
+ * caller's value is back afterwards), then `steps` times: hq_cluster_errors,
+ * hq_reseed_unused(max_moves), an evaluation of the repaired palettes.  trace,
+ * keep_best, costs and used as in hq_refine_population.  A step that moves no
+ * colour of any palette ends the loop: the remaining trace rows repeat the last
+ * step's costs.  hq_refine_population's scope: the whole image on this context
+ * (HQ_ERR_STATE on a shard), no communicator of more than one rank
+ * (HQ_ERR_UNSUPPORTED); hq_cluster_errors' refusals are passed on. */
+int hq_repair_population(hq_ctx *ctx, float *palettes, int P, int K, int steps, float delta,
+                         int max_moves, int keep_best, double *costs, int32_t *used,
+                         double *trace);
+
 /* ---- seeding the search from the image: libhq's additions, no reference counterpart ----
  * The reference starts every search from uniform random palettes (SW:40-52).
  * The three entry points below give a start that knows the image: a colour
@@ -327,6 +397,25 @@ void hq_search_destroy(hq_search *s);
  * iteration returns HQ_ERR_UNSUPPORTED with *ran = 0 and the search has not
  * advanced (checked once per image, before anything is enqueued). */
 int hq_search_set_lloyd(hq_search *s, int every);
+/* Repair iterations (libhq's addition): hq_search_set_lloyd's iteration rule,
+ * call times, scope and refusals with a period of its own, and in addition
+ * HQ_ERR_UNSUPPORTED on a context of HQ_DE_CIE94 (its costs are NaN on real
+ * images).  every = 0 (the default) is the search without them, bit for bit:
+ * nothing is enqueued, allocated or written for them.  In a repair iteration
+ * the candidates are drawn as always (no extra draws); when the iteration is a
+ * hybrid one too the k-means update runs first; then each candidate is
+ * evaluated with its error image stored, repaired by hq_cluster_errors' and
+ * hq_reseed_unused(max_moves)'s rules, and the repaired candidate is what is
+ * evaluated, accepted or rejected, copied by the convergence step and recorded
+ * as best.  Pixels without a usable dE (hq_cluster_errors' HQ_ERR_UNSUPPORTED)
+ * are simply left out.  Option "pixel_err" stays what the caller set.  The
+ * host-driven search (option "sa_device" 0) takes every K; the device-resident
+ * one (K <= 256) runs a repair iteration without a host round trip, as one
+ * linear chain ("sa_graph" 1 captures it): a full pass that stores the error
+ * image -- into the other counter set, like the hybrid iteration's assign-only
+ * pass -- the error kernels ("errsum" in hq_profile_get), the reseed kernel
+ * ("reseed"), then the evaluation.  Both forms give the same search bit for bit. */
+int hq_search_set_repair(hq_search *s, int every, int max_moves);
 
 /* Host-only SWASA driver with a caller-supplied population evaluator; same
  * policy code as hq_search_*.  Used to test the SA semantics without a GPU.
@@ -362,7 +451,10 @@ int hq_profile_enable(hq_ctx *ctx, int on);
  * per-evaluation RCCL all-reduce or all-gather, with a communicator), "centroid"
  * (hq_cluster_sums' kernel), "lloyd" (the update kernel of a device-resident
  * hybrid iteration, whose assign-only pass and sums kernel count under "grid",
- * "assign" and "centroid"), "hist" (hq_color_histogram's kernel); returns total ms and launch
+ * "assign" and "centroid"), "hist" (hq_color_histogram's kernel), "errsum" (hq_cluster_errors'
+ * kernels: the statistics and the gather of the worst pixels' colours), "reseed" (the reseed
+ * kernel of a device-resident repair iteration, whose error pass counts under "grid", "assign"
+ * and "cost"); returns total ms and launch
  * count (HIP events on the context stream). */
 int hq_profile_get(hq_ctx *ctx, const char *kernel, double *total_ms, int64_t *launches);
 int hq_profile_reset(hq_ctx *ctx);
@@ -407,8 +499,9 @@ int hq_profile_reset(hq_ctx *ctx);
  *                  replayed (0, default: measured slower, 0.540 against 0.528 ms per C3 step)
  *   "shard_solo"   experiment only: let a row-block shard run hq_search_* without a
  *                  communicator (its own partial costs; per-rank timing at N GPUs)
- *   "pixel_err"    test only: 1 = the cost kernels also write the per-pixel dE
- *                  (hq_get_pixel_errors)
+ *   "pixel_err"    1 = the cost kernels also write the per-pixel dE (hq_get_pixel_errors, the
+ *                  test surface; hq_cluster_errors reads it; hq_repair_population and repair
+ *                  iterations set it for their own passes and put the caller's value back)
  *   "palette_split" 1 = with a communicator of N ranks, each holding the whole image
  *                  (hq_set_image): rank r evaluates palettes [r P/N, (r+1) P/N) and one
  *                  all-gather gives every rank all P results (SURVEY 8e's split of large
