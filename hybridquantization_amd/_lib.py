@@ -74,6 +74,7 @@ SIGNATURES = {
     "hq_reseed_unused": (C.c_int, [_i64, _f, C.c_int, C.c_int, C.c_int, _f, C.POINTER(C.c_int)]),
     "hq_repair_population": (C.c_int, [_ctx, _f, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int,
                                        _d, _i32, _d]),
+    "hq_dither_population": (C.c_int, [_ctx, _f, C.c_int, C.c_int, C.c_float, C.c_float, _d, _i32]),
     "hq_color_histogram": (C.c_int, [_ctx, C.c_int, _i64, _i64]),
     "hq_median_cut": (C.c_int, [_i64, C.c_int, C.c_int64, C.c_int, _f, C.POINTER(C.c_int)]),
     "hq_quantize": (C.c_int, [_ctx, _f, C.c_int64, _f, C.c_int, _f, _i32]),

@@ -104,6 +104,8 @@ int assign_residency_chunked();
 // hq_lists16.hip
 hipError_t launch_lists16_grid(const Lists16Args&, int P, hipStream_t);
 hipError_t launch_assign16(const AssignArgs&, int P, hipStream_t);
+// hq_dither.hip: one workgroup per palette
+hipError_t launch_dither(const DitherArgs&, int P, hipStream_t);
 // hq_wide.hip
 hipError_t launch_prep_wide(const WideArgs&, int P, hipStream_t);
 hipError_t launch_assign_wide(const WideArgs&, int P, hipStream_t);

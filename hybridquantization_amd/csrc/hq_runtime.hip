@@ -153,6 +153,7 @@ struct hq_ctx {
     // "pixel_err" was on when hq_eval_population[_partial] enqueued it; read with sums_ok)
     bool err_ok = false;
     DevBuf d_errstat, d_worst; // [P][K][4] u64 statistics, then the flag; [P][K] float4 worst pixels
+    DevBuf d_dcarry;           // hq_dither_population: [P][3][W] errors of a strip's last row
 
     // options
     int G2 = 32;           // argmin grid resolution (0 = exhaustive)
@@ -186,6 +187,7 @@ struct hq_ctx {
     int sa_device = 1;     // hq_search_*: 1 = SWASA iterations resident on the device (no host
                            // round trip per iteration), 0 = host-driven (one eval call each)
     int pixel_err = 0;     // test option: the cost kernels also write the per-pixel dE
+    int dither_rows = 1024;  // hq_dither_population: rows per strip (option "dither_rows")
     int trim = 1;          // skip taps < 1e-9 of the peak of the narrow k1 filters
     bool trim_ok = false;  // set by hq_set_filters (the bucket's narrow-filter windows hold)
     bool pal_generic = false;  // this population needs the generic cost path (palette_fits_fast)
@@ -199,7 +201,7 @@ struct hq_ctx {
     // profiling
     bool prof = false;
     ProfSlot prof_assign, prof_cost, prof_grid, prof_finalize, prof_sa, prof_comm, prof_centroid, prof_lloyd,
-        prof_hist, prof_errsum, prof_reseed;
+        prof_hist, prof_errsum, prof_reseed, prof_dither;
     // profiling: start/stop of grid, assign, cost, finalize, [sa_step], the collective
     hipEvent_t ev[kProfEvents] = {};
     hipEvent_t ev_hist[2] = {};  // ... and of hq_color_histogram's kernel
@@ -724,8 +726,12 @@ int palette_slice(hq_ctx* c, int P, int* lo, int* n) {
 // images and, with option "pixel_err" in force, the error image the error kernel
 // reads -- but no finalize and no collective, into the other set like an
 // assign-only pass and for the same reason: nothing reads its sums.
+// dither (hq_dither_population; null: the plain argmin): the index images are the
+// Floyd-Steinberg rendering at that strength -- the counter set and the used bits
+// zeroed as without a grid, then dither_kernel in the place of grid + assign (its
+// events are the assign pair's), the cost and finalize as ever.
 int enqueue_core(hq_ctx* c, int P, int K, const hipEvent_t* ev, bool fold = false, bool assign_only = false,
-                 bool err_pass = false) {
+                 bool err_pass = false, const float* dither = nullptr) {
     const Geom& g = c->g;
     hipStream_t s = c->stream;
     const int nch = c->nch_cur, Ks = nch > 1 ? kMaxK : K;
@@ -747,7 +753,7 @@ int enqueue_core(hq_ctx* c, int P, int K, const hipEvent_t* ev, bool fold = fals
     };
     auto untimed = [&]() { set_launch_events(nullptr, nullptr); };
     const bool n16 = use_lists16(c);
-    if (c->G2 > 0) {  // (build_grid also zeroes the used bits and the sums)
+    if (c->G2 > 0 && !dither) {  // (build_grid also zeroes the used bits and the sums)
         timed(0);
         const hipError_t e =
             n16 ? launch_lists16_grid(Lists16Args{ga.pal, ga.pflags, c->d_l1n.as<uint16_t>(), c->d_l2n.as<uint16_t>(),
@@ -808,7 +814,12 @@ int enqueue_core(hq_ctx* c, int P, int K, const hipEvent_t* ev, bool fold = fals
         ca.pix_pitch = (int64_t)g.W * (g.r1 - g.r0);
     }
     timed(1);
-    hipError_t e = n16 ? launch_assign16(aa, Pl, s) : launch_assign(aa, Ps, s);
+    hipError_t e = dither ? launch_dither(DitherArgs{aa.R, aa.G, aa.B, ga.pal, aa.idx, ga.used_glob,
+                                                     c->d_dcarry.as<float>(), g.idx_pitch, g.W, g.H, K,
+                                                     c->dither_rows, *dither},
+                                          Pl, s)
+                   : n16  ? launch_assign16(aa, Pl, s)
+                          : launch_assign(aa, Ps, s);
     untimed();
     HIP_TRY(c, e);
     if (assign_only) {
@@ -1290,10 +1301,7 @@ int repair_scope(hq_search* s) {
 // of the image, established once per image by one launch of the sums kernel (one
 // palette of one colour over the first index image -- any u8 index addresses the
 // kernel's LDS table) and a read of its flag.
-int lloyd_validate(hq_search* s) {
-    hq_ctx* c = s->ctx;
-    if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
-    if (sums_u8(c)) return HQ_OK;
+int planar_in_range(hq_ctx* c) {  // -> c->planar_ok
     if (c->planar_ok < 0) {
         int rc = bind(c);
         if (rc) return rc;
@@ -1310,6 +1318,13 @@ int lloyd_validate(hq_search* s) {
         HIP_TRY(c, hipStreamSynchronize(st));
         c->planar_ok = bad == 0;
     }
+    return HQ_OK;
+}
+int lloyd_validate(hq_search* s) {
+    hq_ctx* c = s->ctx;
+    if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
+    if (sums_u8(c)) return HQ_OK;
+    if (int rc = planar_in_range(c)) return rc;
     if (!c->planar_ok)
         return fail(c, HQ_ERR_UNSUPPORTED, "planar image with a pixel outside [0, 1] or not finite: no exact sums, "
                                            "no hybrid iteration");
@@ -1639,7 +1654,7 @@ void hq_destroy(hq_ctx* c) {
                       &c->d_dup, &c->d_pflags, &c->d_lvl1, &c->d_lvl2, &c->d_idx,
                       &c->d_used_mask, &c->d_acc, &c->d_out, &c->d_gen_t, &c->d_taps,
                       &c->d_vfrag16, &c->d_vfrag16p, &c->d_vfragm, &c->d_htaps, &c->d_idx32, &c->d_used32, &c->d_pixerr, &c->d_idx16, &c->d_dist, &c->d_l1n, &c->d_l2n, &c->d_sums,
-                      &c->d_hist, &c->d_errstat, &c->d_worst})
+                      &c->d_hist, &c->d_errstat, &c->d_worst, &c->d_dcarry})
         b->release();
     if (c->h_pal) (void)hipHostFree(c->h_pal);
     if (c->h_out) (void)hipHostFree(c->h_out);
@@ -1782,17 +1797,9 @@ int hq_eval_population_partial(hq_ctx* c, const float* palettes, int P, int K, d
     return HQ_OK;
 }
 
-int hq_eval_population(hq_ctx* c, const float* palettes, int P, int K, float delta,
-                       double* costs, int32_t* used) {
-    if (!costs) return fail(c, HQ_ERR_ARG, "null output");
-    int rc = eval_partial_into_hout(c, palettes, P, K);
-    if (rc) return rc;
-    // IM:712: averageArray(error) + computePenalty(used).  After an all-reduce
-    // the used entries count the ranks using colour k; unused <=> 0.
-    const bool full = c->g.r0 == 0 && c->g.r1 == c->g.H;
-    if ((!full || c->slice_ranks > 1) && !(c->comm && c->nranks > 1))
-        return fail(c, HQ_ERR_STATE, "sharded context or palette slice without a communicator: use "
-                                     "hq_eval_population_partial");
+// IM:712 from the [P][1+K] rows in h_out: averageArray(error) + computePenalty(used).
+// After an all-reduce the used entries count the ranks using colour k; unused <=> 0.
+static void costs_from_hout(const hq_ctx* c, int P, int K, float delta, double* costs, int32_t* used) {
     const double n_total = (double)c->g.W * (double)c->g.H;
     for (int p = 0; p < P; ++p) {
         const double* o = c->h_out + (size_t)p * (1 + K);
@@ -1804,6 +1811,66 @@ int hq_eval_population(hq_ctx* c, const float* palettes, int P, int K, float del
         }
         costs[p] = o[0] / n_total + penalty;
     }
+}
+
+int hq_eval_population(hq_ctx* c, const float* palettes, int P, int K, float delta,
+                       double* costs, int32_t* used) {
+    if (!costs) return fail(c, HQ_ERR_ARG, "null output");
+    int rc = eval_partial_into_hout(c, palettes, P, K);
+    if (rc) return rc;
+    const bool full = c->g.r0 == 0 && c->g.r1 == c->g.H;
+    if ((!full || c->slice_ranks > 1) && !(c->comm && c->nranks > 1))
+        return fail(c, HQ_ERR_STATE, "sharded context or palette slice without a communicator: use "
+                                     "hq_eval_population_partial");
+    costs_from_hout(c, P, K, delta, costs, used);
+    return HQ_OK;
+}
+
+int hq_dither_population(hq_ctx* c, const float* palettes, int P, int K, float strength, float delta,
+                         double* costs, int32_t* used) {
+    if (!c) return HQ_ERR_ARG;
+    if (!palettes || !costs || P < 1 || K < 1) return fail(c, HQ_ERR_ARG, "bad palettes / costs / P=%d / K=%d", P, K);
+    if (!(strength >= 0.0f && strength <= 1.0f)) return fail(c, HQ_ERR_ARG, "strength %g not in [0, 1]", strength);
+    if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
+    if (c->g.r0 != 0 || c->g.r1 != c->g.H)
+        return fail(c, HQ_ERR_STATE, "sharded context: error diffusion needs the whole image");
+    if (c->comm && c->nranks > 1)
+        return fail(c, HQ_ERR_UNSUPPORTED, "hq_dither_population with a communicator of %d ranks", c->nranks);
+    if (c->psplit || c->slice_ranks > 1) return fail(c, HQ_ERR_UNSUPPORTED, "hq_dither_population on a palette slice");
+    if (K > kMaxK)
+        return fail(c, HQ_ERR_UNSUPPORTED, "K=%d > %d: the dither kernel keeps the palette in LDS and writes "
+                                           "8-bit indices", K, kMaxK);
+    if (!population_in_range(palettes, P, K))
+        return fail(c, HQ_ERR_ARG, "palette with a channel that is not finite or outside [0, 1]");
+    int rc = bind(c);
+    if (rc) return rc;
+    // the errors stay bounded (|e| <= 1) for pixels in [0, 1]: a property of the image, established
+    // once per image as the hybrid search's is (the packed 8-bit copy exists only for k/255 images)
+    if (!c->img_u8) {
+        if ((rc = planar_in_range(c))) return rc;
+        if (!c->planar_ok)
+            return fail(c, HQ_ERR_UNSUPPORTED, "image with a pixel outside [0, 1] or not finite: no error diffusion");
+    }
+    c->nch_cur = 1;
+    c->pal_generic = false;
+    if ((rc = ensure_population(c, P, K))) return rc;
+    HIP_TRY(c, c->d_dcarry.ensure(sizeof(float) * (size_t)P * 3 * c->g.W));
+    std::memcpy(c->h_pal, palettes, sizeof(float) * 4 * (size_t)P * K);
+    hipStream_t s = c->stream;
+    c->sums_ok = c->err_ok = false;  // (a k-means or repair move from a dithered assignment is neither)
+    HIP_TRY(c, hipMemcpyAsync(c->d_pal_in.p, c->h_pal, sizeof(float4) * (size_t)P * K, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, launch_prep_palette(prep_args(c, K), P, s));
+    const hipEvent_t* ev = c->prof ? c->ev : nullptr;
+    if ((rc = enqueue_core(c, P, K, ev, false, false, false, &strength))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->h_out, c->d_out.p, sizeof(double) * (size_t)P * (1 + K), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (ev) {
+        prof_add(c, c->prof_dither, ev[2], ev[3]);
+        prof_add(c, c->prof_cost, ev[4], ev[5]);
+        prof_add(c, c->prof_finalize, ev[6], ev[7]);
+        if (c->comm) prof_add(c, c->prof_comm, ev[10], ev[11]);
+    }
+    costs_from_hout(c, P, K, delta, costs, used);
     return HQ_OK;
 }
 
@@ -2300,7 +2367,7 @@ int hq_profile_enable(hq_ctx* c, int on) {
 int hq_profile_reset(hq_ctx* c) {
     if (!c) return HQ_ERR_ARG;
     c->prof_assign = c->prof_cost = c->prof_grid = c->prof_finalize = c->prof_sa = c->prof_comm = c->prof_centroid =
-        c->prof_lloyd = c->prof_hist = c->prof_errsum = c->prof_reseed = ProfSlot{};
+        c->prof_lloyd = c->prof_hist = c->prof_errsum = c->prof_reseed = c->prof_dither = ProfSlot{};
     return HQ_OK;
 }
 
@@ -2318,6 +2385,7 @@ int hq_profile_get(hq_ctx* c, const char* kernel, double* total_ms, int64_t* lau
     else if (!std::strcmp(kernel, "hist")) s = &c->prof_hist;
     else if (!std::strcmp(kernel, "errsum")) s = &c->prof_errsum;
     else if (!std::strcmp(kernel, "reseed")) s = &c->prof_reseed;
+    else if (!std::strcmp(kernel, "dither")) s = &c->prof_dither;
     else return fail(c, HQ_ERR_ARG, "unknown kernel '%s'", kernel);
     if (total_ms) *total_ms = s->ms;
     if (launches) *launches = s->launches;
@@ -2389,6 +2457,10 @@ int hq_set_option(hq_ctx* c, const char* name, int value) {
         c->chunked = value != 0;
     } else if (!std::strcmp(name, "pixel_err")) {
         c->pixel_err = value != 0;
+    } else if (!std::strcmp(name, "dither_rows")) {
+        if (value < 64 || value > 1024 || value % 64)
+            return fail(c, HQ_ERR_ARG, "dither_rows must be a multiple of 64 in 64 .. 1024");
+        c->dither_rows = value;
     } else if (!std::strcmp(name, "img_u8")) {
         c->img_u8_path = value != 0;
     } else if (!std::strcmp(name, "assign_blocks_per_cu")) {

@@ -244,6 +244,34 @@ class ImageManipulation:
                                              iptr(used), dptr(trace)), ctx)
         return (pal, costs, used, trace) if return_trace else (pal, costs, used)
 
+    # dithered rendering: libhq's addition (hq_dither_population, no reference counterpart)
+    def ditherPopulation(self, colors, strength: float = 1.0, delta: float = 2.0, return_used=False):
+        """computeQuantizationErrorPopulation of the Floyd-Steinberg rendering at ``strength``
+        in [0, 1] (0: the plain evaluation, bit for bit): colors (P, 4K), K <= 256 ->
+        costs (P,) [, used (P, K)].  getIndices and getPixelErrors then answer for the
+        dithered rendering; clusterSums and clusterErrors need a plain evaluation again."""
+        ctx = self._require()
+        pal = _f32(np.stack([np.asarray(c, np.float32).reshape(-1) for c in colors]))
+        P, K = pal.shape[0], pal.shape[1] // 4
+        costs = np.zeros(P, np.float64)
+        used = np.zeros((P, K), np.int32)
+        check(self._lib.hq_dither_population(ctx, fptr(pal), P, K, float(strength), float(delta),
+                                             dptr(costs), iptr(used)), ctx)
+        return (costs, used) if return_used else costs
+
+    def quantizeDithered(self, colors, strength: float = 1.0):
+        """The dithered rendering of the context's image (setImage, findBestQuantization)
+        with the palette colors float[4K]: ``quantize``'s output format, an inline float4
+        image palette[idx] with .w = 0, the indices read back from the device and gathered
+        on the host.  Sets ``lastUsedColors`` and ``ditherError``, the rendering's mean dE."""
+        pal = _f32(colors).reshape(1, -1)
+        costs, used = self.ditherPopulation(pal, strength, 0.0, return_used=True)
+        table = pal.reshape(-1, 4).copy()
+        table[:, 3] = 0.0
+        self.lastUsedColors = used[0]
+        self.ditherError = float(costs[0])
+        return table[self.getIndices(0)].reshape(-1)
+
     # seeding the search from the image: libhq's additions (hq_color_histogram, hq_median_cut)
     def colorHistogram(self, bits: int = 5):
         """Colour histogram of the owned rows of the image set: (cells int64
@@ -272,7 +300,8 @@ class ImageManipulation:
     def findBestQuantization(self, inlinergbOriginal, inlineScielabOriginal, w, nbOfColors,
                              simulatedAnnealing, filters, absfilters, illuminant,
                              iterations=None, stop=None, lloydSteps=0, lloydEvery=0,
-                             init=None, initBits=5, repairEvery=0, repairMoves=-1, repairSteps=0):
+                             init=None, initBits=5, repairEvery=0, repairMoves=-1, repairSteps=0,
+                             dither=0.0, ditherSearch=False):
         """Full SWASA search (IM:383-591) on the GPU; returns bestColors float[4K].
 
         ``simulatedAnnealing`` is a :class:`~hybridquantization_amd.swasa.SWASA`;
@@ -299,8 +328,25 @@ class ImageManipulation:
         when the iteration is hybrid too.  ``repairSteps`` > 0: the best palette is
         polished by that many repair steps (hq_repair_population, keep_best) before
         the k-means polish; ``bestErrorSA`` is the search's own error.
+        ``dither`` > 0 (hq_dither_population, a strength up to 1): once the search and its
+        polishes are done, the best palette is also evaluated in its Floyd-Steinberg
+        rendering; ``bestErrorDithered`` is that cost, ``bestError`` stays the plain one.
+        ``ditherSearch`` (needs ``dither`` > 0): the search optimises the dithered cost
+        instead, host-driven (SWASA.search_host with ditherPopulation as its evaluator;
+        ``stop`` is not polled); ``init`` composes with it, the k-means and repair moves
+        do not (ValueError: both start from a nearest-colour assignment).  ``bestError``
+        and ``bestErrorDithered`` are then both the dithered cost.
         """
         ctx = self._require()
+        dither = float(dither)
+        if not 0.0 <= dither <= 1.0:
+            raise ValueError(f"dither={dither!r}: a strength in [0, 1]")
+        if ditherSearch:
+            if not dither > 0.0:
+                raise ValueError("ditherSearch needs dither > 0")
+            moves = dict(lloydEvery=lloydEvery, repairEvery=repairEvery, lloydSteps=lloydSteps, repairSteps=repairSteps)
+            if any(int(v) != 0 for v in moves.values()):
+                raise ValueError("ditherSearch with " + ", ".join(k for k, v in moves.items() if int(v) != 0))
         if not self.openCLFiltersReady:
             self.updateOpenCLFilters(filters, absfilters)
         # Always upload (IM:450-478 does too): an identity cache keyed on id() can
@@ -311,14 +357,25 @@ class ImageManipulation:
         params = sw.params()
         handle = C.c_void_p()
         K = int(nbOfColors)
+        if isinstance(init, str):
+            if init != "mediancut":
+                raise ValueError(f"init={init!r}: None, 'mediancut' or an array")
+            cells, den = self.colorHistogram(int(initBits))
+            init, _ = self.medianCut(cells, int(initBits), den, K)
+        if ditherSearch:
+            P = params.population
+            total = params.imax if iterations is None else min(int(iterations), params.imax)
+            best, err, _ = sw.search_host(
+                K, lambda ps: self.ditherPopulation(ps.reshape(P, -1), dither, sw.delta), iterations=total,
+                initial=None if init is None else initial_population(init, P, K))
+            self.bestError = self.bestErrorDithered = err
+            self.iterations = total
+            if self.verbose:
+                print("Final error : %.5f" % err)
+            return best
         if init is None:
             check(self._lib.hq_search_create(ctx, C.byref(params), K, sw.seed, C.byref(handle)), ctx)
         else:
-            if isinstance(init, str):
-                if init != "mediancut":
-                    raise ValueError(f"init={init!r}: None, 'mediancut' or an array")
-                cells, den = self.colorHistogram(int(initBits))
-                init, _ = self.medianCut(cells, int(initBits), den, K)
             pop = initial_population(init, params.population, K)
             check(self._lib.hq_search_create_from(ctx, C.byref(params), K, sw.seed, fptr(pop),
                                                   C.byref(handle)), ctx)
@@ -367,6 +424,10 @@ class ImageManipulation:
             best, self.bestError = pal[0], float(costs[0])
             if self.verbose:
                 print("Final error after %d k-means steps : %.5f" % (int(lloydSteps), self.bestError))
+        if dither > 0.0:
+            self.bestErrorDithered = float(self.ditherPopulation(best.reshape(1, -1), dither, sw.delta)[0])
+            if self.verbose:
+                print("Final error, dithered at strength %g : %.5f" % (dither, self.bestErrorDithered))
         return best
 
     # IM:770

@@ -269,6 +269,39 @@ int hq_repair_population(hq_ctx *ctx, float *palettes, int P, int K, int steps, 
                          int max_moves, int keep_best, double *costs, int32_t *used,
                          double *trace);
 
+/* ---- dithered rendering: libhq's addition, no reference counterpart ----
+ * S-CIELAB blurs the opponent channels as the eye does before it takes dE; the
+ * nearest-colour rendering's error is low-frequency and survives that blur, an
+ * error-diffused rendering's does not.  hq_dither_population evaluates the P
+ * palettes (K <= 256) on the context's image as hq_eval_population does, with
+ * the index images chosen by raster Floyd-Steinberg error diffusion instead of
+ * the argmin alone.  In the argmin's space (the sRGB-coded planar floats), per
+ * channel, every operation one fp32 operation rounded to nearest and none
+ * contracted into an fma, e = 0 outside the image, s = strength:
+ *     a = 7 e(x-1, y)   b = 3 e(x+1, y-1)   c = 5 e(x, y-1)   d = e(x-1, y-1)
+ *     t = ((a + b) + (c + d)) * 0.0625
+ *     v = min(max(pix + s * t, 0), 1)
+ *     idx(x, y) = the first minimum over k of the argmin's distance(v, pal[k])
+ *     e(x, y) = v - pal[idx]          (pal[k].w taken as 0)
+ * At strength 0 the indices, used flags and costs are hq_eval_population's, bit
+ * for bit.  costs[p] = mean dE + delta * #unused of the dithered rendering: the
+ * context's dE type and whichever cost path its filters and options select; a
+ * colour is used when it appears in the dithered index image.  used may be NULL.
+ * Afterwards hq_get_indices, hq_get_indices32 and hq_get_pixel_errors answer for
+ * the dithered rendering, and hq_cluster_sums and hq_cluster_errors return
+ * HQ_ERR_STATE until the next hq_eval_population[_partial] (a k-means or repair
+ * move from a dithered assignment is neither).  Toward a live hq_search the
+ * call behaves as hq_eval_population does.
+ * HQ_ERR_ARG: P < 1, K < 1, a null palettes or costs, a strength outside
+ * [0, 1] (NaN included), a palette channel that is not finite or outside [0, 1]
+ * (hq_search_create_from's rule).  HQ_ERR_STATE: no image set, a row-block
+ * shard.  HQ_ERR_UNSUPPORTED: a communicator of more than one rank, option
+ * "palette_split" or "slice_ranks" > 1, K > 256, an image pixel that is not
+ * finite or outside [0, 1] (found on the device once per image).  On any refusal
+ * the outputs and the evaluated state are untouched. */
+int hq_dither_population(hq_ctx *ctx, const float *palettes, int P, int K, float strength,
+                         float delta, double *costs, int32_t *used);
+
 /* ---- seeding the search from the image: libhq's additions, no reference counterpart ----
  * The reference starts every search from uniform random palettes (SW:40-52).
  * The three entry points below give a start that knows the image: a colour
@@ -454,7 +487,8 @@ int hq_profile_enable(hq_ctx *ctx, int on);
  * "assign" and "centroid"), "hist" (hq_color_histogram's kernel), "errsum" (hq_cluster_errors'
  * kernels: the statistics and the gather of the worst pixels' colours), "reseed" (the reseed
  * kernel of a device-resident repair iteration, whose error pass counts under "grid", "assign"
- * and "cost"); returns total ms and launch
+ * and "cost"), "dither" (hq_dither_population's kernel, which stands in the place of "grid"
+ * and "assign": a dithered evaluation counts nothing under those); returns total ms and launch
  * count (HIP events on the context stream). */
 int hq_profile_get(hq_ctx *ctx, const char *kernel, double *total_ms, int64_t *launches);
 int hq_profile_reset(hq_ctx *ctx);
@@ -502,6 +536,9 @@ int hq_profile_reset(hq_ctx *ctx);
  *   "pixel_err"    1 = the cost kernels also write the per-pixel dE (hq_get_pixel_errors, the
  *                  test surface; hq_cluster_errors reads it; hq_repair_population and repair
  *                  iterations set it for their own passes and put the caller's value back)
+ *   "dither_rows"  hq_dither_population: rows per strip of the dither kernel, a multiple of 64
+ *                  in 64 .. 1024 (default 1024; anything else is HQ_ERR_ARG).  The results do
+ *                  not depend on it, bit for bit: it lets small test images cross strips
  *   "palette_split" 1 = with a communicator of N ranks, each holding the whole image
  *                  (hq_set_image): rank r evaluates palettes [r P/N, (r+1) P/N) and one
  *                  all-gather gives every rank all P results (SURVEY 8e's split of large
