@@ -1,0 +1,969 @@
+// hq_eval.hip -- libhq host runtime, evaluation: the population buffers, the pass
+// over a prepared population (enqueue_core, enqueue_wide, the generic cost), the
+// evaluation, dither, index, sums, error and histogram entry points, and the two
+// improvement loops built on them (refine, repair).  Shared declarations:
+// hq_runtime.h.
+#include <cmath>
+
+#include "hq_runtime.h"
+
+using namespace hq;
+
+namespace {
+
+// Assign workgroups per palette group: assign_blocks_per_cu per CU, but no more
+// than pixel chunks (256 pixels, one per thread): idle workgroups still fill LDS,
+// and after the XCD relabelling they would all sit on the last XCDs (a 512-row
+// shard ran assign on half the chip: 0.071 vs 0.053 ms).  (Evening out the
+// chunks per workgroup instead -- 1064 workgroups of 2 for 2128 chunks -- was
+// slower than 2048 with 80 of them taking a second chunk.)
+// assign: one pixel per thread per 256-thread chunk, with one resident round
+// of workgroups, makes each thread's pixel sequence a grid stride: every thread
+// gets the same number of pixels +-1 (512-row shard 0.1306 -> 0.1261 ms per
+// step vs 4 pixels per chunk at 16 workgroups per CU; 4096^2 unchanged).
+#ifndef HQ_ASSIGN_MINPX
+#define HQ_ASSIGN_MINPX 6
+#endif
+int assign_blocks(const hq_ctx* c, int P) {
+    // at least HQ_ASSIGN_MINPX pixels per thread: a launch's fixed part (table
+    // fill, pipeline start, the used-bit flush) is paid per workgroup (C2,
+    // 1024^2 P = 1: 2048 workgroups of 2 pixels per thread took 14 us, 1045 of 4
+    // took 12.3, 523 of 8 took 8.5; the 512-row shard, 5.5 per thread at 1536
+    // workgroups, slowed from 43 to 46 us at 8)
+    const int64_t chunk = 256 * HQ_ASSIGN_MINPX;
+    const int ng = std::min(P, 4);
+    const int res = c->nch_cur > 1 ? c->assign_res_chunked : c->assign_res[ng];
+    const int per_cu = c->assign_blocks_per_cu > 0 ? c->assign_blocks_per_cu : res > 0 ? res : 4;
+    const int64_t nblocks = (int64_t)c->num_cu * per_cu;
+    return (int)std::max<int64_t>(1, std::min<int64_t>(nblocks, (c->g.n_ext + chunk - 1) / chunk));
+}
+
+// Chunked palettes of 4 to 32 chunks take the native 16-bit lists (option lists16).
+// Their kernels take up to 144 KiB (lists16_kernel at K = 8192) and 128 KiB
+// (assign16_kernel) of dynamic LDS: a device that cannot grant that (less than
+// gfx950's 160 KiB per workgroup) keeps the per-chunk grids.
+bool use_lists16(const hq_ctx* c) {
+    const int min_nch = c->lists16 >= 2 ? 2 : kN16MinNch;  // (2: also 2 and 4 chunks)
+    if (!(c->lists16 > 0 && c->G2 > 0 && c->nch_cur >= min_nch && c->nch_cur <= kN16MaxNch)) return false;
+    const size_t K = (size_t)kMaxK * c->nch_cur;
+    const size_t grid_lds = ((K > 4096 ? 3 : 4) * sizeof(float) + sizeof(uint16_t)) * K +
+                            sizeof(uint16_t) * 64 * n16_l1_words((int)K);
+    const size_t assign_lds = sizeof(float4) * K * (K <= 4096 ? 2 : 1);
+    return std::max(grid_lds, assign_lds) <= c->lds_optin;
+}
+
+// The population being enqueued takes the fast tiled cost kernels (else the
+// generic pair, whose [7][n_ext] scratch ensure_population then allocates up
+// front: nothing may allocate while a search run is captured into a graph).
+// Chunked palettes: the 16 x 128 tiles at HB = 10 only.
+bool cost_fast(const hq_ctx* c) {
+    return c->cost_variant == 0 && c->fast_hb > 0 && !c->pal_generic && !c->taps_generic &&
+           (c->nch_cur == 1 || (c->nch_cur <= kMaxNchFast && c->fast_hb == 10 && c->cost_rows == 16 &&
+                                c->cost_tw == 128));
+}
+
+}  // namespace
+
+namespace hq {
+
+// Ensure population buffers for P palettes of K colours.
+int ensure_population(hq_ctx* c, int P, int K) {
+    const Geom& g = c->g;
+    if (c->nch_cur > 1) {  // chunked palettes: 16-bit indices, then P nch sub-palettes of 256
+        HIP_TRY(c, c->d_idx16.ensure(sizeof(uint16_t) * (size_t)P * g.idx_pitch + 256));
+        if (c->nch_cur > 4) HIP_TRY(c, c->d_dist.ensure(sizeof(float) * (size_t)P * g.idx_pitch));
+        if (use_lists16(c)) {
+            HIP_TRY(c, c->d_l1n.ensure(sizeof(uint16_t) * n16_l1_words(K) * (size_t)P * kN16G1 * kN16G1 * kN16G1));
+            // (palette pairs interleaved: an odd population's last pair half empty)
+            HIP_TRY(c, c->d_l2n.ensure(sizeof(uint16_t) * kN16L2Words * (size_t)(P + 1) / 2 * 2 * kN16G2 * kN16G2 * kN16G2));
+        }
+        P *= c->nch_cur;  // (d_out, h_out: P nch (1 + 256) >= P (1 + K) doubles)
+        K = kMaxK;
+    }
+    const int G2 = c->G2 > 0 ? c->G2 : 4;
+    const int G1 = G2 / 4;
+    const int64_t l1p = round_up((int64_t)G1 * G1 * G1 * 32, 256);
+    const int64_t l2g = round_up((int64_t)G2 * G2 * G2 * kL2Line, 256);  // per group of 4 palettes
+    const int64_t n_own = (int64_t)g.W * (g.r1 - g.r0);
+    HIP_TRY(c, c->d_pal_in.ensure(sizeof(float4) * (size_t)P * K));
+    HIP_TRY(c, c->d_pal.ensure(sizeof(float4) * (size_t)P * std::max(K, kMaxK)));
+    HIP_TRY(c, c->d_opp.ensure(sizeof(float4) * (size_t)P * std::max(K, kMaxK)));
+    if (K > kMaxK) {
+        HIP_TRY(c, c->d_idx32.ensure(sizeof(uint32_t) * (size_t)P * g.idx_pitch));
+        HIP_TRY(c, c->d_used32.ensure(sizeof(uint32_t) * (size_t)P * K));
+    }
+    HIP_TRY(c, c->d_opp16.ensure(sizeof(uint4) * (size_t)P * kMaxK));
+    HIP_TRY(c, c->d_dup.ensure((size_t)P * kMaxK));
+    HIP_TRY(c, c->d_pflags.ensure(sizeof(int) * (size_t)P));
+    HIP_TRY(c, c->d_lvl1.ensure((size_t)P * l1p));
+    HIP_TRY(c, c->d_lvl2.ensure((size_t)((P + 3) / 4) * l2g));
+    // + 256: the cost kernels' interior fills read whole dword pairs, up to 7
+    // bytes past a region's last column (past the buffer on the last palette's
+    // last row when idx_pitch has no padding)
+    HIP_TRY(c, c->d_idx.ensure((size_t)P * g.idx_pitch + 256));
+    const size_t rb = (size_t)rank_blocks(c);  // counter / used-bit blocks per set
+    HIP_TRY(c, c->d_used_mask.ensure(2 * rb * sizeof(uint32_t) * kUsedSlots * (size_t)used_stride(P)));
+    HIP_TRY(c, c->d_acc.ensure(2 * rb * sizeof(uint64_t) * acc_words(P)));
+    HIP_TRY(c, c->d_out.ensure(sizeof(double) * (size_t)P * (1 + K)));
+    if (c->pixel_err) HIP_TRY(c, c->d_pixerr.ensure(sizeof(float) * (size_t)P * std::max<int64_t>(n_own, 1)));
+    // the generic path's [7][n_ext] scratch, here rather than at its first launch: an
+    // allocation cannot happen while a search run is being captured into a graph
+    if (!cost_fast(c) || K > kMaxK) HIP_TRY(c, c->d_gen_t.ensure(sizeof(float) * 7 * (size_t)g.n_ext + 256));
+    HIP_TRY(c, c->h_pal.ensure(sizeof(float) * 4 * (size_t)P * K));
+    HIP_TRY(c, c->h_out.ensure(sizeof(double) * (size_t)P * (1 + K)));
+    return HQ_OK;
+}
+
+PaletteArgs prep_args(hq_ctx* c, int K) {
+    return PaletteArgs{c->d_pal_in.as<float4>(), c->d_pal.as<float4>(), c->d_opp.as<float4>(),
+                       c->d_opp16.as<uint4>(), c->d_dup.as<uint8_t>(), c->d_pflags.as<int>(), K};
+}
+
+// Counter set `par` of an evaluation of P palettes (P nch sub-palettes Ps).
+uint64_t* acc_base(hq_ctx* c, int par, int P) {
+    return c->d_acc.as<uint64_t>() + (size_t)par * rank_blocks(c) * acc_words(P);
+}
+uint32_t* used_base(hq_ctx* c, int par, int Ps) {
+    return c->d_used_mask.as<uint32_t>() + (size_t)par * rank_blocks(c) * kUsedSlots * used_stride(Ps);
+}
+
+}  // namespace hq
+
+namespace {
+
+uint64_t* acc_set(hq_ctx* c, int par, int P) { return acc_base(c, par, P) + (size_t)own_block(c) * acc_words(P); }
+uint32_t* used_set(hq_ctx* c, int par, int Ps) {
+    return used_base(c, par, Ps) + (size_t)own_block(c) * kUsedSlots * used_stride(Ps);
+}
+
+GridArgs grid_args(hq_ctx* c, int P, int K, int so = 0) {
+    const int G2 = c->G2 > 0 ? c->G2 : 4;
+    const int G1 = G2 / 4;
+    // (P = sub-palettes; the counters of set c->acc_par)
+    const int nch = c->nch_cur;
+    // (so: the first of the P sub-palettes in the prepared tables, a palette split's slice)
+    return GridArgs{c->d_pal.as<float4>() + (int64_t)so * kMaxK, c->d_dup.as<uint8_t>() + (int64_t)so * kMaxK,
+                    c->d_pflags.as<int>() + so, c->d_lvl1.as<uint8_t>(), c->d_lvl2.as<uint8_t>(),
+                    used_set(c, c->acc_par, P),
+                    used_stride(P), K, G1,
+                    round_up((int64_t)G1 * G1 * G1 * 32, 256), round_up((int64_t)G2 * G2 * G2 * kL2Line, 256),
+                    acc_set(c, c->acc_par, P / nch), P / nch, nch};
+}
+
+// The generic two-pass cost (CL:234-306 per pixel, any half-width) of P
+// palettes, one launch pair each: index images at idx_base (u8, u16 (chunked
+// palettes) or u32: idx_bytes) with c->g.idx_pitch elements per palette, opponent
+// tables of opp_stride entries per palette in d_opp.  Pair `cost` times all P pairs.
+int enqueue_generic_cost(hq_ctx* c, int P, const void* idx_base, int idx_bytes, int opp_stride, ProfRec& pr,
+                         Pair cost, int p_off = 0) {
+    const Geom& g = c->g;
+    hipStream_t s = c->stream;
+    HIP_TRY(c, c->d_gen_t.ensure(sizeof(float) * 7 * (size_t)g.n_ext + 256));
+    const int64_t n_own = (int64_t)g.W * (g.r1 - g.r0);
+    const float inv[3] = {1.0f / c->illum[0], 1.0f / c->illum[1], 1.0f / c->illum[2]};
+    for (int p = 0; p < P; ++p) {
+        GenArgs gn{};
+        gn.idx = static_cast<const char*>(idx_base) + (int64_t)p * g.idx_pitch * idx_bytes;
+        gn.opp = c->d_opp.as<float4>() + (int64_t)(p_off + p) * opp_stride;
+        gn.k1 = c->d_k1.as<float>();
+        gn.k2 = c->d_k2.as<float>();
+        gn.k3 = c->d_k3.as<float>();
+        gn.absk3 = c->d_absk3.as<float>();
+        gn.t = c->d_gen_t.as<float>();
+        gn.labL = c->d_labL.as<float>();
+        gn.labA = c->d_labA.as<float>();
+        gn.labB = c->d_labB.as<float>();
+        gn.acc = acc_set(c, c->acc_par, P);
+        gn.p = p;
+        gn.P = P;
+        gn.g = g;
+        gn.half = c->half;
+        gn.pix_err = c->pixel_err ? c->d_pixerr.as<float>() + (int64_t)p * n_own : nullptr;
+        gn.vtaps = c->d_vtaps.as<float>();
+        gn.vtap_pitch = c->vtap_pitch;
+        gn.hrow4 = c->gen_hrow4;
+        gn.hrow_no = c->gen_hrow_no;
+        gn.vtile2 = c->gen_vtile2;
+        // split-f16 planes hold |x| < 4 (x 2^14), split taps |w| <= kVTapMax: palettes and
+        // filters outside the fast range stay on fp32 (gen_hmfma runs only with gen_vmfma)
+        gn.vmfma = c->gen_vmfma && !c->pal_generic && !c->taps_generic;
+        gn.vtapd = c->d_vfragm.bytes ? c->d_vfragm.as<uint32_t>() : nullptr;
+        gn.hmfma = c->gen_hmfma;
+        gn.shape = c->gen_shape;
+        gn.htapd = gn.vtapd ? gn.vtapd + vtile_dup_tap_words(c->half) : nullptr;
+        gn.htaps = c->d_htaps.as<float4>();
+        opp2xyz_over_illum(inv, gn.m_lab);
+        // the events span every palette's launch pair: start on the first, stop on the last;
+        // cost_variant 2: the per-pixel pair in the reference's summation order
+        HIP_TRY(c, timed_launch(pr, cost, [&] {
+            return c->cost_variant == 2 ? launch_cost_generic(gn, c->de_type, idx_bytes, s)
+                                        : launch_cost_tiled_generic(gn, c->de_type, idx_bytes, s);
+        }, p == 0, p == P - 1));
+    }
+    return HQ_OK;
+}
+
+// The palettes of a P-palette population this device evaluates: a palette
+// split (psplit with a communicator of N ranks, or the test-only slice options)
+// takes [r P/N, (r+1) P/N) on the whole image; anything else all P.
+int palette_slice(hq_ctx* c, int P, int* lo, int* n) {
+    int R = 1, r = 0;
+    if (c->psplit && c->comm) R = c->nranks, r = c->rank;
+    else if (c->slice_ranks > 1) R = c->slice_ranks, r = c->slice_rank;
+    *lo = 0;
+    *n = P;
+    if (R == 1) return HQ_OK;
+    if (r < 0 || r >= R) return fail(c, HQ_ERR_ARG, "palette split: rank %d outside [0, %d)", r, R);
+    if (P % R) return fail(c, HQ_ERR_ARG, "palette split: population %d not divisible by %d ranks", P, R);
+    if (!whole_image(c))
+        return fail(c, HQ_ERR_STATE, "palette split: every rank needs the whole image (hq_set_image)");
+    *n = P / R;
+    *lo = r * *n;
+    return HQ_OK;
+}
+
+// The collective that ends a pass of P palettes (this device's: [lo, lo + Pl), Ps
+// sub-palettes) on a context with a communicator, under the comm pair (profiling
+// only: an event record between launches idles the GPU a few us, so the timed pass
+// of bench.py records none).
+int enqueue_collective(hq_ctx* c, bool fold, int P, int K, int lo, int Pl, int Ps, ProfRec& pr) {
+    hipStream_t s = c->stream;
+    if (pr.ev) {
+        HIP_TRY(c, hipEventRecord(pr.ev[2 * kPComm], s));
+        pr.recorded |= 1u << kPComm;
+    }
+    if (fold) {
+        // row blocks under a folding search: every rank's counter block and
+        // used-bit block to every rank (in place), one group of two
+        // all-gathers; the accept step sums the integer counters and ORs the
+        // bits of all the blocks itself
+        const size_t na = acc_words(Pl), nu = (size_t)kUsedSlots * used_stride(Ps);
+        NCCL_TRY(c, ncclGroupStart());
+        NCCL_TRY(c, ncclAllGather(acc_set(c, c->acc_par, Pl), acc_base(c, c->acc_par, Pl), na, ncclUint64,
+                                  c->comm, s));
+        NCCL_TRY(c, ncclAllGather(used_set(c, c->acc_par, Ps), used_base(c, c->acc_par, Ps), nu, ncclUint32,
+                                  c->comm, s));
+        NCCL_TRY(c, ncclGroupEnd());
+    } else if (c->psplit) {  // every rank's slice of d_out to every rank (in place; one rank: a no-op)
+        NCCL_TRY(c, ncclAllGather(c->d_out.as<double>() + (int64_t)lo * (1 + K), c->d_out.p,
+                                  (size_t)Pl * (1 + K), ncclFloat64, c->comm, s));
+    } else {  // also with one rank (a no-op copy), so that path is exercised on one GPU
+        NCCL_TRY(c, ncclAllReduce(c->d_out.p, c->d_out.p, (size_t)P * (1 + K), ncclFloat64, ncclSum,
+                                  c->comm, s));
+    }
+    if (pr.ev) HIP_TRY(c, hipEventRecord(pr.ev[2 * kPComm + 1], s));
+    return HQ_OK;
+}
+
+// The index images, [and error image, counters, d_out rows] on the device are now
+// those of P palettes of K colours in nch chunks, of which [lo, lo + Pl) are here.
+void note_evaluated(hq_ctx* c, int P, int K, int nch, int lo, int Pl) {
+    c->slice_lo = lo;
+    c->slice_n = Pl;
+    c->last_P = P;
+    c->K_cur = K;
+    c->last_nch = nch;
+}
+
+// K > 256 (hq_wide.hip): prep, exhaustive argmin into 32-bit indices and
+// per-colour used flags, the generic cost, finalize, [all-reduce or, under a
+// palette split, all-gather].  A palette split takes the same slice
+// [lo, lo + Pl) as enqueue_core: the other ranks' palettes are prepped here
+// too (cheap) but neither assigned nor costed, so no rank counts them.
+int enqueue_wide(hq_ctx* c, int P, int K, ProfRec& pr) {
+    const Geom& g = c->g;
+    hipStream_t s = c->stream;
+    int lo = 0, Pl = P;
+    if (int rc = palette_slice(c, P, &lo, &Pl)) return rc;
+    WideArgs wa{c->d_pal_in.as<float4>(), c->d_pal.as<float4>(), c->d_opp.as<float4>(), c->d_pflags.as<int>(),
+                c->d_R.as<float>(), c->d_G.as<float>(), c->d_B.as<float>(), c->d_idx32.as<uint32_t>(),
+                c->d_used32.as<uint32_t>(), g.n_ext, g.idx_pitch, K};
+    c->acc_par ^= 1;
+    if (Pl < P && !c->comm)  // test-only slice: the other palettes' rows read as zero
+        HIP_TRY(c, hipMemsetAsync(c->d_out.p, 0, sizeof(double) * (size_t)P * (1 + K), s));
+    HIP_TRY(c, hipMemsetAsync(acc_set(c, c->acc_par, Pl), 0, sizeof(uint64_t) * acc_words(Pl), s));
+    HIP_TRY(c, hipMemsetAsync(c->d_pflags.p, 0, sizeof(int) * (size_t)P, s));
+    HIP_TRY(c, launch_prep_wide(wa, P, s));
+    HIP_TRY(c, hipMemsetAsync(c->d_used32.p, 0, sizeof(uint32_t) * (size_t)Pl * K, s));
+    // the slice's palettes: indices and used flags in rows 0 .. Pl - 1
+    WideArgs ws = wa;
+    ws.pal += (int64_t)lo * K;
+    ws.opp += (int64_t)lo * K;
+    ws.pflags += lo;
+    HIP_TRY(c, timed_launch(pr, kPAssign, [&] { return launch_assign_wide(ws, Pl, s); }));
+    if (int rc = enqueue_generic_cost(c, Pl, c->d_idx32.p, 4, K, pr, kPCost, lo)) return rc;
+    FinalizeArgs fa{acc_set(c, c->acc_par, Pl), nullptr, 0, c->d_out.as<double>() + (int64_t)lo * (1 + K), Pl, K,
+                    c->d_used32.as<uint32_t>(), 8};
+    HIP_TRY(c, timed_launch(pr, kPFinalize, [&] { return launch_finalize(fa, Pl, s); }));
+    if (c->comm)
+        if (int rc = enqueue_collective(c, false, P, K, lo, Pl, Pl, pr)) return rc;
+    note_evaluated(c, P, K, 1, lo, Pl);
+    return HQ_OK;
+}
+
+}  // namespace
+
+// Enqueue pass `pass` (hq_runtime.h: how far it goes, its index images, its
+// counter set) over the P prepared palettes of K colours (d_pal, d_opp, d_dup,
+// d_pflags).  pr: the launches carry their pairs' events themselves
+// (timed_launch), four pairs from pass.pairs().
+// Chunked palettes (c->nch_cur = nch > 1, 256 < K <= 256 nch): the grid and
+// assign run on P nch sub-palettes of 256 colours (d_pal etc. hold them,
+// prep_palette made them), assign combines them into 16-bit indices, the cost
+// kernel reads those with a 256 nch-entry table.
+int hq::enqueue_core(hq_ctx* c, int P, int K, ProfRec& pr, Pass pass) {
+    const Geom& g = c->g;
+    hipStream_t s = c->stream;
+    const int nch = c->nch_cur, Ks = nch > 1 ? kMaxK : K;
+    const bool dither = pass.kind == Pass::Dither;
+    const int p0 = pass.pairs();
+    const Pair pgrid = Pair(p0), passign = dither ? kPDither : Pair(p0 + 1), pcost = Pair(p0 + 2),
+               pfinalize = Pair(p0 + 3);
+    // the palettes this device evaluates: all, or a palette split's slice [lo, lo + Pl)
+    int lo = 0, Pl = P;
+    if (int rc = palette_slice(c, P, &lo, &Pl)) return rc;
+    const int Ps = Pl * nch, so = lo * nch;  // sub-palettes, the first one's index
+    if (Pl < P && !c->comm && pass.kind != Pass::AssignOnly)  // test-only slice: the other palettes' rows read as zero
+        HIP_TRY(c, hipMemsetAsync(c->d_out.p, 0, sizeof(double) * (size_t)P * (1 + K), s));
+    c->acc_par ^= 1;
+    struct ParRestore {  // a side pass: back to the last full pass's set on every way out
+        hq_ctx* c;
+        bool on;
+        ~ParRestore() { if (on) c->acc_par ^= 1; }
+    } restore{c, pass.side()};
+    const GridArgs ga = grid_args(c, Ps, Ks, so);
+    const bool n16 = use_lists16(c);
+    if (c->G2 > 0 && !dither) {  // (build_grid also zeroes the used bits and the sums)
+        HIP_TRY(c, timed_launch(pr, pgrid, [&] {
+            return n16 ? launch_lists16_grid(Lists16Args{ga.pal, ga.pflags, c->d_l1n.as<uint16_t>(),
+                                                         c->d_l2n.as<uint16_t>(), ga.used_glob, used_stride(Ps),
+                                                         ga.acc_zero, Pl, K, nch * kMaxK, nch},
+                                             Pl, s)
+                       : launch_build_grid(ga, Ps, s);
+        }));
+    } else {
+        HIP_TRY(c, hipMemsetAsync(ga.used_glob, 0, sizeof(uint32_t) * kUsedSlots * (size_t)used_stride(Ps), s));
+        HIP_TRY(c, hipMemsetAsync(ga.acc_zero, 0, sizeof(uint64_t) * acc_words(Pl), s));
+    }
+    const int nblocks = assign_blocks(c, Ps);
+    AssignArgs aa{c->d_R.as<float>(), c->d_G.as<float>(), c->d_B.as<float>(),
+                  c->img_u8 && c->img_u8_path ? c->d_rgbx.as<uint32_t>() : nullptr, ga.pal, ga.pflags,
+                  c->d_lvl1.as<uint8_t>(), c->d_lvl2.as<uint8_t>(),
+                  c->d_idx.as<uint8_t>(), ga.used_glob, used_stride(Ps), g.n_ext, g.idx_pitch,
+                  ga.lvl1_pitch, ga.lvl2_gstride, Ks, c->G2, nblocks};
+    if (nch > 1) {
+        aa.idx16 = c->d_idx16.as<uint16_t>();
+        aa.dist = nch > 4 ? c->d_dist.as<float>() : nullptr;
+        aa.nch = nch;
+        while ((1 << aa.lg_nch) < nch) ++aa.lg_nch;
+    }
+    if (n16) {  // one palette of K colours per workgroup (its table in LDS)
+        aa.l1n = c->d_l1n.as<uint16_t>();
+        aa.l2n = c->d_l2n.as<uint16_t>();
+        aa.kpal = nch * kMaxK;
+        aa.K = K;
+        // one resident round of 1024-thread workgroups over the P palettes, >= 4 pixels per thread
+        const int ngr = K <= 4096 ? (Pl + 1) / 2 : Pl;  // workgroup groups: palette pairs up to K = 4096
+        aa.nblocks = (int)std::max<int64_t>(
+            1, std::min<int64_t>(std::max(1, c->num_cu / ngr), (g.n_ext + 4095) / 4096));
+    }
+    const float inv[3] = {1.0f / c->illum[0], 1.0f / c->illum[1], 1.0f / c->illum[2]};
+    const bool fast = cost_fast(c);
+    // 8-row tiles (cost_mfma_kernel) exist for the 21-tap bucket only
+    const int rows = c->fast_hb == 10 ? c->cost_rows : 16;
+    const int tw = c->fast_hb == 10 ? c->cost_tw : 128;  // 256-column tiles: HB = 10 only
+    CostArgs ca{};
+    if (fast) {
+        ca.idx = nch > 1 ? c->d_idx16.as<uint8_t>() : c->d_idx.as<uint8_t>();
+        ca.opp16 = c->d_opp16.as<uint4>() + (int64_t)so * kMaxK;
+        ca.taps = c->d_taps.p;
+        ca.vfrag16 = c->d_vfrag16.as<uint4>();
+        ca.vfrag16p = c->d_vfrag16p.as<uint4>();
+        ca.labL = c->d_labL.as<float>();
+        ca.labA = c->d_labA.as<float>();
+        ca.labB = c->d_labB.as<float>();
+        ca.acc = ga.acc_zero;
+        ca.acc_P = Pl;
+        ca.acc_p0 = 0;
+        ca.g = g;
+        ca.K = K;
+        fast_tile_dims(g.W, g.r1 - fast_grid_row0(c->de_type, g.r0, rows), rows, tw, &ca.tiles_x, &ca.ntiles);
+        opp2xyz_over_illum(inv, ca.m_lab);
+        ca.pix_err = c->pixel_err ? c->d_pixerr.as<float>() : nullptr;
+        ca.pix_pitch = (int64_t)g.W * (g.r1 - g.r0);
+    }
+    HIP_TRY(c, timed_launch(pr, passign, [&] {
+        return dither ? launch_dither(DitherArgs{aa.R, aa.G, aa.B, ga.pal, aa.idx, ga.used_glob,
+                                                 c->d_dcarry.as<float>(), g.idx_pitch, g.W, g.H, K,
+                                                 c->dither_rows, pass.strength},
+                                      Pl, s)
+               : n16  ? launch_assign16(aa, Pl, s)
+                      : launch_assign(aa, Ps, s);
+    }));
+    if (pass.kind != Pass::AssignOnly) {
+        if (fast) {
+            HIP_TRY(c, timed_launch(pr, pcost, [&] {
+                return nch > 1 ? launch_cost_chunked(ca, Pl, nch, c->de_type, c->trim && c->trim_ok, s)
+                               : launch_cost_fast(ca, Pl, c->de_type, c->trim && c->trim_ok, rows, tw, c->fast_hb,
+                                                  s);
+            }));
+        } else {
+            int rc = nch > 1 ? enqueue_generic_cost(c, Pl, c->d_idx16.p, 2, nch * kMaxK, pr, pcost, lo)
+                             : enqueue_generic_cost(c, Pl, c->d_idx.p, 1, kMaxK, pr, pcost, lo);
+            if (rc) return rc;
+        }
+    }
+    if (!pass.side()) {
+        if (pass.kind != Pass::Fold) {  // (a folding search's accept step reads the sums itself)
+            FinalizeArgs fa{ga.acc_zero, ga.used_glob, used_stride(Ps),
+                            c->d_out.as<double>() + (int64_t)lo * (1 + K), Pl, K, nullptr, 8 * nch};
+            HIP_TRY(c, timed_launch(pr, pfinalize, [&] { return launch_finalize(fa, Pl, s); }));
+        }
+        if (c->comm)
+            if (int rc = enqueue_collective(c, pass.kind == Pass::Fold, P, K, lo, Pl, Ps, pr)) return rc;
+    }
+    note_evaluated(c, P, K, nch, lo, Pl);
+    return HQ_OK;
+}
+
+namespace {
+
+// Host-driven evaluation of the P palettes in h_pal: upload, prep, enqueue_core,
+// read back d_out into h_out.
+int enqueue_eval(hq_ctx* c, int P, int K) {
+    hipStream_t s = c->stream;
+    const size_t n_in = c->nch_cur > 1 ? (size_t)P * c->nch_cur * kMaxK : (size_t)P * K;
+    HIP_TRY(c, hipMemcpyAsync(c->d_pal_in.p, c->h_pal.p, sizeof(float4) * n_in, hipMemcpyHostToDevice, s));
+    ProfRec pr = prof_begin(c);
+    int rc;
+    if (c->nch_cur > 1) {  // h_pal holds P nch sub-palettes of 256 (pack_chunks)
+        HIP_TRY(c, launch_prep_palette(prep_args(c, kMaxK), P * c->nch_cur, s));
+        rc = enqueue_core(c, P, K, pr);
+    } else if (K > kMaxK) {
+        rc = enqueue_wide(c, P, K, pr);  // (builds no grid)
+    } else {
+        HIP_TRY(c, launch_prep_palette(prep_args(c, K), P, s));
+        rc = enqueue_core(c, P, K, pr);
+    }
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->h_out.p, c->d_out.p, sizeof(double) * (size_t)P * (1 + K),
+                              hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    prof_accumulate(c, pr);
+    return HQ_OK;
+}
+
+int check_eval_args(hq_ctx* c, const float* palettes, int P, int K) {
+    if (!c) return HQ_ERR_ARG;
+    if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
+    if (!palettes || P < 1 || K < 1) return fail(c, HQ_ERR_ARG, "bad palettes / P=%d / K=%d", P, K);
+    if (K > kMaxKWide)
+        return fail(c, HQ_ERR_ARG, "K=%d > %d (the plugin's limit, HQ:192)", K, kMaxKWide);
+    return HQ_OK;
+}
+
+// The fast cost kernels take the opponent colours as split f16 of x * 2^14
+// (split_f16): |opp| must stay below 65504 / 2^14 ~ 4.  RGB2Opp's largest
+// absolute row sum is 0.871, so a palette channel x in [-59, 1.93] keeps
+// |opp| < 4 (lin(x) = x / 12.92 below 0.04045, ((x + 0.055) / 1.055)^2.4
+// above).  Colours outside [-32, 1.9] -- never produced by the SA, which
+// clamps to [0, 1] (SW:103-106), but accepted by hq_eval_population -- and
+// non-finite colours send the population to the generic fp32 path.
+bool palette_fits_fast(const float* pal, int P, int K) {
+    for (size_t i = 0, n = (size_t)P * K; i < n; ++i)
+        for (int ch = 0; ch < 3; ++ch) {
+            const float x = pal[4 * i + ch];
+            if (!(x >= -32.0f && x <= 1.9f)) return false;
+        }
+    return true;
+}
+
+int eval_partial_into_hout(hq_ctx* c, const float* palettes, int P, int K) {
+    int rc = check_eval_args(c, palettes, P, K);
+    if (rc) return rc;
+    if ((rc = bind(c))) return rc;
+    const bool fits = palette_fits_fast(palettes, P, K);
+    // 256 < K <= 16384: chunks of 256 colours through the grid and assign, and the
+    // tiled cost kernel up to 32 chunks (the generic pair above).  Palettes outside
+    // the fast range (non-finite colours among
+    // them) take the exhaustive K > 256 path instead, which keeps the
+    // reference's NaN semantics across all K colours.
+    c->nch_cur = c->chunked && fits && c->G2 > 0 && K > kMaxK && K <= kMaxKChunked ? chunk_count(K) : 1;
+    c->pal_generic = !fits;  // (before ensure_population: it sizes the generic path's scratch)
+    if (!(rc = ensure_population(c, P, K))) {
+        if (c->nch_cur > 1) pack_chunks(palettes, P, K, c->nch_cur, c->h_pal.as<float>());
+        else std::memcpy(c->h_pal.p, palettes, sizeof(float) * 4 * (size_t)P * K);
+        rc = enqueue_eval(c, P, K);
+    }
+    c->pal_generic = false;  // device-resident searches generate clamped palettes
+    c->nch_cur = 1;
+    c->sums_ok = rc == HQ_OK;
+    c->err_ok = c->sums_ok && c->pixel_err;
+    return rc;
+}
+
+// The index images of the last evaluation (K colours): their base and element width.
+const void* index_images(const hq_ctx* c, int K, int* idx_bytes) {
+    *idx_bytes = c->last_nch > 1 ? 2 : K > kMaxK ? 4 : 1;
+    return *idx_bytes == 2 ? c->d_idx16.p : *idx_bytes == 4 ? c->d_idx32.p : c->d_idx.p;
+}
+
+// P, K are the last evaluation's (by hq_eval_population[_partial], on this image,
+// no search run since) and every palette's index image is on this device.
+int check_last_population(hq_ctx* c, int P, int K) {
+    if (!c->have_image || !c->sums_ok)
+        return fail(c, HQ_ERR_STATE, "no population evaluated by hq_eval_population[_partial] on this image "
+                                     "since the last search run");
+    if (P != c->last_P || K != c->K_cur)
+        return fail(c, HQ_ERR_STATE, "P=%d, K=%d: the last evaluation had P=%d, K=%d", P, K, c->last_P, c->K_cur);
+    if (c->slice_n != c->last_P || c->slice_ranks > 1 || (c->psplit && c->comm))
+        return fail(c, HQ_ERR_UNSUPPORTED, "palette slice: this device holds %d of the %d index images",
+                    c->slice_n, c->last_P);
+    return HQ_OK;
+}
+
+// Palette p of the last population is on this device: *local, its place among them.
+int check_local_palette(hq_ctx* c, int p, int* local) {
+    if (p < 0 || p >= c->last_P) return fail(c, HQ_ERR_ARG, "palette %d not in last population", p);
+    if (p < c->slice_lo || p >= c->slice_lo + c->slice_n)
+        return fail(c, HQ_ERR_ARG, "palette %d was evaluated on another rank (palette split)", p);
+    *local = p - c->slice_lo;
+    return HQ_OK;
+}
+
+// hq_color_histogram into `out` ([2^(3 bits)][4]); nothing is written unless
+// HQ_OK.  The image buffers are read, a table of its own is written: the index
+// images, the counter sets and d_sums stay what they are.
+int color_histogram(hq_ctx* c, int bits, int64_t* out, int64_t* den) {
+    int rc = bind(c);
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    const Geom& g = c->g;
+    const size_t n4 = (size_t)4 << (3 * bits);
+    HIP_TRY(c, c->d_hist.ensure(sizeof(int64_t) * (n4 + 1)));
+    HIP_TRY(c, hipMemsetAsync(c->d_hist.p, 0, sizeof(int64_t) * (n4 + 1), s));
+    const bool u8 = sums_u8(c);
+    HistArgs ha{};
+    ha.R = c->d_R.as<float>();
+    ha.G = c->d_G.as<float>();
+    ha.B = c->d_B.as<float>();
+    ha.rgbx = u8 ? c->d_rgbx.as<uint32_t>() : nullptr;
+    ha.cells = c->d_hist.as<unsigned long long>();
+    ha.bad = reinterpret_cast<int*>(c->d_hist.as<int64_t>() + n4);
+    ha.q0 = (uint32_t)((int64_t)(g.r0 - g.e0) * g.W);
+    ha.q1 = ha.q0 + (uint32_t)((int64_t)g.W * (g.r1 - g.r0));
+    ha.bits = bits;
+    ProfRec pr = prof_begin(c);
+    HIP_TRY(c, timed_launch(pr, kPHist, [&] { return launch_color_histogram(ha, c->num_cu, s); }));
+    std::vector<int64_t> h(n4 + 1);
+    HIP_TRY(c, hipMemcpyAsync(h.data(), c->d_hist.p, sizeof(int64_t) * (n4 + 1), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    prof_accumulate(c, pr);
+    if (h[n4] != 0)
+        return fail(c, HQ_ERR_UNSUPPORTED, "planar image with a pixel outside [0, 1] or not finite: no exact sums");
+    std::memcpy(out, h.data(), sizeof(int64_t) * n4);
+    *den = u8 ? 255 : (int64_t)1 << 32;
+    return HQ_OK;
+}
+
+// IM:712 from the [P][1+K] rows in h_out: averageArray(error) + computePenalty(used).
+// After an all-reduce the used entries count the ranks using colour k; unused <=> 0.
+void costs_from_hout(const hq_ctx* c, int P, int K, float delta, double* costs, int32_t* used) {
+    const double n_total = (double)c->g.W * (double)c->g.H;
+    for (int p = 0; p < P; ++p) {
+        const double* o = c->h_out.as<double>() + (size_t)p * (1 + K);
+        double penalty = 0.0;
+        for (int k = 0; k < K; ++k) {
+            const bool u = o[1 + k] != 0.0;
+            if (!u) penalty += delta;
+            if (used) used[(size_t)p * K + k] = u ? 1 : 0;
+        }
+        costs[p] = o[0] / n_total + penalty;
+    }
+}
+
+// The improvement loop of hq_refine_population and hq_repair_population: evaluate,
+// then `steps` times move(cur, &changed) -> status on the palettes in place and
+// evaluate again, tracing every evaluation's costs and returning the last
+// population or, keep_best, each palette's best.  A move that changed nothing
+// ends the loop: the remaining steps would repeat this one, and the trace says so.
+template <typename Move>
+int improve_population(hq_ctx* c, float* palettes, int P, int K, int steps, float delta, int keep_best,
+                       double* costs, int32_t* used, double* trace, Move&& move) {
+    const size_t n4 = (size_t)P * K * 4, nu = (size_t)P * K;
+    std::vector<float> cur(palettes, palettes + n4), best_pal;
+    std::vector<double> cst(P), best_cost;
+    std::vector<int32_t> usd(nu), best_used;
+    int rc;
+    if ((rc = hq_eval_population(c, cur.data(), P, K, delta, cst.data(), usd.data()))) return rc;
+    if (trace) std::copy(cst.begin(), cst.end(), trace);
+    if (keep_best) best_pal = cur, best_cost = cst, best_used = usd;
+    for (int s = 1; s <= steps; ++s) {
+        bool changed = true;
+        if ((rc = move(cur.data(), &changed))) return rc;
+        if (!changed) {
+            for (int t = s; trace && t <= steps; ++t) std::copy(cst.begin(), cst.end(), trace + (size_t)t * P);
+            break;
+        }
+        if ((rc = hq_eval_population(c, cur.data(), P, K, delta, cst.data(), usd.data()))) return rc;
+        if (trace) std::copy(cst.begin(), cst.end(), trace + (size_t)s * P);
+        for (int p = 0; keep_best && p < P; ++p) {
+            // strictly lower (the earliest step keeps a tie); a number beats a NaN, never the reverse
+            const double a = cst[p], b = best_cost[p];
+            if (!(a < b || (b != b && a == a))) continue;
+            best_cost[p] = a;
+            std::copy(cur.begin() + (size_t)p * K * 4, cur.begin() + (size_t)(p + 1) * K * 4,
+                      best_pal.begin() + (size_t)p * K * 4);
+            std::copy(usd.begin() + (size_t)p * K, usd.begin() + (size_t)(p + 1) * K, best_used.begin() + (size_t)p * K);
+        }
+    }
+    const std::vector<float>& rp = keep_best ? best_pal : cur;
+    const std::vector<double>& rc_ = keep_best ? best_cost : cst;
+    const std::vector<int32_t>& ru = keep_best ? best_used : usd;
+    std::copy(rp.begin(), rp.end(), palettes);
+    std::copy(rc_.begin(), rc_.end(), costs);
+    if (used) std::copy(ru.begin(), ru.end(), used);
+    return HQ_OK;
+}
+
+// The argument checks hq_refine_population and hq_repair_population share (`what`: the call's
+// name, hint: what a multi-rank caller does instead).
+int check_improve_args(hq_ctx* c, const float* palettes, int P, int K, int steps, const double* costs,
+                       const char* what, const char* hint) {
+    if (!costs) return fail(c, HQ_ERR_ARG, "null output");
+    if (int rc = check_eval_args(c, palettes, P, K)) return rc;
+    if (steps < 0) return fail(c, HQ_ERR_ARG, "steps=%d < 0", steps);
+    // (option "palette_split" without a communicator slices nothing: these two go on)
+    return whole_image_only(c, what, hint, false);
+}
+
+}  // namespace
+
+namespace hq {
+
+// [P][K] palettes -> P nch sub-palettes of 256 colours: sub-palette p nch + c
+// holds colours 256 c .. 256 c + 255 of palette p, and copies of colour 0 past
+// K (a copy of colour 0 ties it and never wins the chunk combine, which keeps
+// the first chunk at equal distance; hq_assign.hip).
+void pack_chunks(const float* pal, int P, int K, int nch, float* out) {
+    for (int p = 0; p < P; ++p)
+        for (int k = 0; k < nch * kMaxK; ++k) {
+            const float* src = pal + 4 * ((size_t)p * K + (k < K ? k : 0));
+            float* dst = out + 4 * ((size_t)p * nch * kMaxK + k);
+            dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2]; dst[3] = src[3];
+        }
+}
+
+// The sums kernel's arguments for the index images of the last evaluation (or
+// assign-only pass) of P palettes of K colours: the owned rows, as
+// hq_get_indices[32] reads them, into d_sums ([P][K][4], then the range flag).
+ClusterArgs cluster_args(hq_ctx* c, int P, int K, int* idx_bytes) {
+    const Geom& g = c->g;
+    ClusterArgs ca{};
+    ca.idx = index_images(c, K, idx_bytes);
+    ca.R = c->d_R.as<float>();
+    ca.G = c->d_G.as<float>();
+    ca.B = c->d_B.as<float>();
+    ca.rgbx = sums_u8(c) ? c->d_rgbx.as<uint32_t>() : nullptr;
+    ca.sums = c->d_sums.as<unsigned long long>();
+    ca.bad = reinterpret_cast<int*>(c->d_sums.as<int64_t>() + (size_t)P * K * 4);
+    ca.idx_pitch = g.idx_pitch;
+    ca.q0 = (uint32_t)((int64_t)(g.r0 - g.e0) * g.W);
+    ca.q1 = ca.q0 + (uint32_t)((int64_t)g.W * (g.r1 - g.r0));
+    ca.P = P;
+    ca.K = K;
+    return ca;
+}
+
+// hq_cluster_sums into `out` ([P][K][4]); nothing is written unless HQ_OK.
+int cluster_sums(hq_ctx* c, int P, int K, int64_t* out, int64_t* den) {
+    int rc = check_last_population(c, P, K);
+    if (rc) return rc;
+    if ((rc = bind(c))) return rc;
+    hipStream_t s = c->stream;
+    const size_t n4 = (size_t)P * K * 4;
+    HIP_TRY(c, c->d_sums.ensure(sizeof(int64_t) * (n4 + 1)));
+    HIP_TRY(c, hipMemsetAsync(c->d_sums.p, 0, sizeof(int64_t) * (n4 + 1), s));
+    int idx_bytes = 1;
+    const ClusterArgs ca = cluster_args(c, P, K, &idx_bytes);
+    const bool u8 = sums_u8(c);
+    ProfRec pr = prof_begin(c);
+    HIP_TRY(c, timed_launch(pr, kPSums, [&] { return launch_cluster_sums(ca, idx_bytes, c->num_cu, s); }));
+    std::vector<int64_t> h(n4 + 1);
+    HIP_TRY(c, hipMemcpyAsync(h.data(), c->d_sums.p, sizeof(int64_t) * (n4 + 1), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    prof_accumulate(c, pr);
+    if (h[n4] != 0)
+        return fail(c, HQ_ERR_UNSUPPORTED, "planar image with a pixel outside [0, 1] or not finite: no exact sums");
+    std::memcpy(out, h.data(), sizeof(int64_t) * n4);
+    *den = u8 ? 255 : (int64_t)1 << 32;
+    return HQ_OK;
+}
+
+// The error kernel's arguments for the index images, the error image and the
+// prepared palettes of the last evaluation of P palettes of K colours, into
+// d_errstat ([P][K][4], then the flag) and d_worst ([P][K]).
+ClusterErrArgs cluster_err_args(hq_ctx* c, int P, int K, int* idx_bytes) {
+    const Geom& g = c->g;
+    const ClusterArgs ca = cluster_args(c, P, K, idx_bytes);
+    ClusterErrArgs ea{};
+    ea.idx = ca.idx;
+    ea.R = ca.R;
+    ea.G = ca.G;
+    ea.B = ca.B;
+    ea.rgbx = ca.rgbx;
+    ea.pix_err = c->d_pixerr.as<float>();
+    ea.pal = c->d_pal.as<float4>();
+    ea.stats = c->d_errstat.as<unsigned long long>();
+    ea.worst = c->d_worst.as<float4>();
+    ea.bad = reinterpret_cast<int*>(c->d_errstat.as<int64_t>() + (size_t)P * K * 4);
+    ea.idx_pitch = g.idx_pitch;
+    ea.err_pitch = (int64_t)g.W * (g.r1 - g.r0);
+    // chunked palettes: a palette's nch sub-palettes of 256 lie back to back, colour k at k
+    ea.pal_pitch = c->last_nch > 1 ? (int64_t)c->last_nch * kMaxK : std::max(K, kMaxK);
+    ea.q0 = ca.q0;
+    ea.q1 = ca.q1;
+    ea.pos0 = (uint32_t)((int64_t)g.e0 * g.W);
+    ea.P = P;
+    ea.K = K;
+    return ea;
+}
+
+// hq_cluster_errors into err ([P][K][4]) and worst ([P][K][4]); nothing is written
+// unless HQ_OK, or -- ignore_bad, the repair move inside a search -- whatever the
+// flag says (the pixels it stands for are left out either way).  The index
+// images, the error image, the counter sets and d_sums stay what they are.
+int cluster_errors(hq_ctx* c, int P, int K, int64_t* err, float* worst, bool ignore_bad) {
+    int rc = check_last_population(c, P, K);
+    if (rc) return rc;
+    const Geom& g = c->g;
+    const int64_t n_own = (int64_t)g.W * (g.r1 - g.r0);
+    if (!c->err_ok || c->d_pixerr.bytes < sizeof(float) * (size_t)P * (size_t)n_own)
+        return fail(c, HQ_ERR_STATE, "option pixel_err was off at the last evaluation: no error image");
+    if ((int64_t)g.W * g.H >= ((int64_t)1 << 32))
+        return fail(c, HQ_ERR_UNSUPPORTED, "image of 2^32 pixels or more: a position does not fit 32 bits");
+    if ((rc = bind(c))) return rc;
+    hipStream_t s = c->stream;
+    const size_t n4 = (size_t)P * K * 4;
+    HIP_TRY(c, c->d_errstat.ensure(sizeof(int64_t) * (n4 + 1)));
+    HIP_TRY(c, c->d_worst.ensure(sizeof(float) * n4));
+    HIP_TRY(c, hipMemsetAsync(c->d_errstat.p, 0, sizeof(int64_t) * (n4 + 1), s));
+    int idx_bytes = 1;
+    const ClusterErrArgs ea = cluster_err_args(c, P, K, &idx_bytes);
+    ProfRec pr = prof_begin(c);
+    HIP_TRY(c, timed_launch(pr, kPErrsum, [&] { return launch_cluster_errors(ea, idx_bytes, c->num_cu, s); }));
+    std::vector<uint64_t> h(n4 + 1);
+    std::vector<float> hw(n4);
+    HIP_TRY(c, hipMemcpyAsync(h.data(), c->d_errstat.p, sizeof(int64_t) * (n4 + 1), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(hw.data(), c->d_worst.p, sizeof(float) * n4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    prof_accumulate(c, pr);
+    if (h[n4] != 0 && !ignore_bad)
+        return fail(c, HQ_ERR_UNSUPPORTED, "a pixel's dE is not a finite number below 2^20 (dE94's NaN, a non-finite "
+                                           "colour or LabRef): no exact error sums");
+    for (size_t i = 0; i < n4; i += 4) {
+        const uint64_t key = h[i + 2];
+        err[i] = (int64_t)h[i];
+        err[i + 1] = (int64_t)h[i + 1];
+        err[i + 2] = (int64_t)(key >> 32);
+        err[i + 3] = key ? (int64_t)(0xffffffffu - (uint32_t)key) : -1;
+    }
+    std::memcpy(worst, hw.data(), sizeof(float) * n4);
+    return HQ_OK;
+}
+
+// The planar form's sums need every owned pixel finite and in [0, 1]: a property
+// of the image, established once per image by one launch of the sums kernel (one
+// palette of one colour over the first index image -- any u8 index addresses the
+// kernel's LDS table) and a read of its flag.
+int planar_in_range(hq_ctx* c) {
+    if (c->planar_ok < 0) {
+        int rc = bind(c);
+        if (rc) return rc;
+        hipStream_t st = c->stream;
+        HIP_TRY(c, c->d_idx.ensure((size_t)c->g.idx_pitch + 256));
+        HIP_TRY(c, c->d_sums.ensure(sizeof(int64_t) * (4 + 1)));
+        HIP_TRY(c, hipMemsetAsync(c->d_sums.p, 0, sizeof(int64_t) * (4 + 1), st));
+        int idx_bytes = 1;
+        ClusterArgs ca = cluster_args(c, 1, 1, &idx_bytes);
+        ca.idx = c->d_idx.p;  // (the u8 image, whatever the last evaluation's index width)
+        HIP_TRY(c, launch_cluster_sums(ca, 1, c->num_cu, st));
+        int bad = 1;
+        HIP_TRY(c, hipMemcpyAsync(&bad, ca.bad, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        c->planar_ok = bad == 0;
+    }
+    return HQ_OK;
+}
+
+}  // namespace hq
+
+extern "C" {
+
+int hq_eval_population_partial(hq_ctx* c, const float* palettes, int P, int K, double* partial) {
+    if (!partial) return fail(c, HQ_ERR_ARG, "null output");
+    int rc = eval_partial_into_hout(c, palettes, P, K);
+    if (rc) return rc;
+    std::memcpy(partial, c->h_out.p, sizeof(double) * (size_t)P * (1 + K));
+    return HQ_OK;
+}
+
+int hq_eval_population(hq_ctx* c, const float* palettes, int P, int K, float delta,
+                       double* costs, int32_t* used) {
+    if (!costs) return fail(c, HQ_ERR_ARG, "null output");
+    int rc = eval_partial_into_hout(c, palettes, P, K);
+    if (rc) return rc;
+    if ((!whole_image(c) || c->slice_ranks > 1) && !(c->comm && c->nranks > 1))
+        return fail(c, HQ_ERR_STATE, "sharded context or palette slice without a communicator: use "
+                                     "hq_eval_population_partial");
+    costs_from_hout(c, P, K, delta, costs, used);
+    return HQ_OK;
+}
+
+int hq_dither_population(hq_ctx* c, const float* palettes, int P, int K, float strength, float delta,
+                         double* costs, int32_t* used) {
+    if (!c) return HQ_ERR_ARG;
+    if (!palettes || !costs || P < 1 || K < 1) return fail(c, HQ_ERR_ARG, "bad palettes / costs / P=%d / K=%d", P, K);
+    if (!(strength >= 0.0f && strength <= 1.0f)) return fail(c, HQ_ERR_ARG, "strength %g not in [0, 1]", strength);
+    if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
+    int rc = whole_image_only(c, "hq_dither_population (error diffusion)");
+    if (rc) return rc;
+    if (K > kMaxK)
+        return fail(c, HQ_ERR_UNSUPPORTED, "K=%d > %d: the dither kernel keeps the palette in LDS and writes "
+                                           "8-bit indices", K, kMaxK);
+    if (!population_in_range(palettes, P, K))
+        return fail(c, HQ_ERR_ARG, "palette with a channel that is not finite or outside [0, 1]");
+    if ((rc = bind(c))) return rc;
+    // the errors stay bounded (|e| <= 1) for pixels in [0, 1]: a property of the image, established
+    // once per image as the hybrid search's is (the packed 8-bit copy exists only for k/255 images)
+    if (!c->img_u8) {
+        if ((rc = planar_in_range(c))) return rc;
+        if (!c->planar_ok)
+            return fail(c, HQ_ERR_UNSUPPORTED, "image with a pixel outside [0, 1] or not finite: no error diffusion");
+    }
+    c->nch_cur = 1;
+    c->pal_generic = false;
+    if ((rc = ensure_population(c, P, K))) return rc;
+    HIP_TRY(c, c->d_dcarry.ensure(sizeof(float) * (size_t)P * 3 * c->g.W));
+    std::memcpy(c->h_pal.p, palettes, sizeof(float) * 4 * (size_t)P * K);
+    hipStream_t s = c->stream;
+    c->sums_ok = c->err_ok = false;  // (a k-means or repair move from a dithered assignment is neither)
+    HIP_TRY(c, hipMemcpyAsync(c->d_pal_in.p, c->h_pal.p, sizeof(float4) * (size_t)P * K, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, launch_prep_palette(prep_args(c, K), P, s));
+    ProfRec pr = prof_begin(c);
+    if ((rc = enqueue_core(c, P, K, pr, Pass{Pass::Dither, strength}))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->h_out.p, c->d_out.p, sizeof(double) * (size_t)P * (1 + K), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    prof_accumulate(c, pr);
+    costs_from_hout(c, P, K, delta, costs, used);
+    return HQ_OK;
+}
+
+int hq_get_indices(hq_ctx* c, int p, uint8_t* idx) {
+    if (!c || !idx) return HQ_ERR_ARG;
+    int rc = check_local_palette(c, p, &p);
+    if (rc) return rc;
+    if (c->K_cur > kMaxK)
+        return fail(c, HQ_ERR_STATE, "K=%d > 256: indices are 32-bit (hq_get_indices32)", c->K_cur);
+    if ((rc = bind(c))) return rc;
+    const Geom& g = c->g;
+    const int64_t off = (int64_t)(g.r0 - g.e0) * g.W;
+    const int64_t n_own = (int64_t)g.W * (g.r1 - g.r0);
+    HIP_TRY(c, hipMemcpy(idx, c->d_idx.as<uint8_t>() + (int64_t)p * g.idx_pitch + off, n_own,
+                         hipMemcpyDeviceToHost));
+    return HQ_OK;
+}
+
+int hq_get_indices32(hq_ctx* c, int p, uint32_t* idx) {
+    if (!c || !idx) return HQ_ERR_ARG;
+    int rc = check_local_palette(c, p, &p);
+    if (rc) return rc;
+    if ((rc = bind(c))) return rc;
+    const Geom& g = c->g;
+    const int64_t off = (int64_t)(g.r0 - g.e0) * g.W;
+    const int64_t n_own = (int64_t)g.W * (g.r1 - g.r0);
+    // the image at its own width (u16: chunked palettes; u32: K > 16384), widened here
+    int idx_bytes = 1;
+    const char* base = static_cast<const char*>(index_images(c, c->K_cur, &idx_bytes));
+    std::vector<unsigned char> raw((size_t)n_own * idx_bytes);
+    HIP_TRY(c, hipMemcpy(raw.data(), base + ((int64_t)p * g.idx_pitch + off) * idx_bytes, raw.size(),
+                         hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n_own; ++i) {
+        uint32_t v = 0;
+        std::memcpy(&v, raw.data() + i * idx_bytes, idx_bytes);  // (little-endian host)
+        idx[i] = v;
+    }
+    return HQ_OK;
+}
+
+int hq_get_pixel_errors(hq_ctx* c, int p, float* err) {
+    if (!c || !err) return HQ_ERR_ARG;
+    if (!c->pixel_err) return fail(c, HQ_ERR_STATE, "option pixel_err is off");
+    int rc = check_local_palette(c, p, &p);
+    if (rc) return rc;
+    if (c->d_pixerr.bytes < sizeof(float) * (size_t)c->last_P * (size_t)c->g.W * (c->g.r1 - c->g.r0))
+        return fail(c, HQ_ERR_STATE, "pixel_err was set after the last evaluation");
+    if ((rc = bind(c))) return rc;
+    const int64_t n_own = (int64_t)c->g.W * (c->g.r1 - c->g.r0);
+    HIP_TRY(c, hipMemcpy(err, c->d_pixerr.as<float>() + (int64_t)p * n_own, sizeof(float) * n_own,
+                         hipMemcpyDeviceToHost));
+    return HQ_OK;
+}
+
+int hq_cluster_sums(hq_ctx* c, int P, int K, int64_t* sums, int64_t* den) {
+    if (!c) return HQ_ERR_ARG;
+    if (!sums || !den || P < 1 || K < 1) return fail(c, HQ_ERR_ARG, "bad sums / den / P=%d / K=%d", P, K);
+    return cluster_sums(c, P, K, sums, den);
+}
+
+int hq_color_histogram(hq_ctx* c, int bits, int64_t* cells, int64_t* den) {
+    if (!c) return HQ_ERR_ARG;
+    if (!cells || !den || bits < 2 || bits > 6) return fail(c, HQ_ERR_ARG, "bad cells / den / bits=%d (2 .. 6)", bits);
+    if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
+    return color_histogram(c, bits, cells, den);
+}
+
+int hq_cluster_errors(hq_ctx* c, int P, int K, int64_t* err, float* worst_rgb) {
+    if (!c) return HQ_ERR_ARG;
+    if (!err || !worst_rgb || P < 1 || K < 1) return fail(c, HQ_ERR_ARG, "bad err / worst_rgb / P=%d / K=%d", P, K);
+    return cluster_errors(c, P, K, err, worst_rgb);
+}
+
+int hq_refine_population(hq_ctx* c, float* palettes, int P, int K, int steps, float delta, int keep_best,
+                         double* costs, int32_t* used, double* trace) {
+    int rc = check_improve_args(c, palettes, P, K, steps, costs, "hq_refine_population",
+                                ": add the shards' hq_cluster_sums yourself");
+    if (rc) return rc;
+    std::vector<int64_t> sums((size_t)P * K * 4);
+    return improve_population(c, palettes, P, K, steps, delta, keep_best, costs, used, trace,
+                              [&](float* cur, bool*) {
+        int64_t den = 0;
+        int r = cluster_sums(c, P, K, sums.data(), &den);
+        if (!r && (r = hq_centroids_from_sums(sums.data(), den, P, K, cur)))
+            return fail(c, r, "hq_centroids_from_sums failed");
+        return r;
+    });
+}
+
+int hq_repair_population(hq_ctx* c, float* palettes, int P, int K, int steps, float delta, int max_moves,
+                         int keep_best, double* costs, int32_t* used, double* trace) {
+    int rc = check_improve_args(c, palettes, P, K, steps, costs, "hq_repair_population",
+                                ": merge the shards' hq_cluster_errors yourself");
+    if (rc) return rc;
+    const PixelErrScope scope(c);  // the evaluations below store their error images
+    const size_t n4 = (size_t)P * K * 4;
+    std::vector<float> worst(n4);
+    std::vector<int64_t> err(n4);
+    std::vector<int> moved(P);
+    return improve_population(c, palettes, P, K, steps, delta, keep_best, costs, used, trace,
+                              [&](float* cur, bool* changed) {
+        int r = cluster_errors(c, P, K, err.data(), worst.data());
+        if (!r && (r = hq_reseed_unused(err.data(), worst.data(), P, K, max_moves, cur, moved.data())))
+            return fail(c, r, "hq_reseed_unused failed");
+        // nothing left to repair: the remaining steps repeat this one
+        *changed = !std::all_of(moved.begin(), moved.end(), [](int m) { return m == 0; });
+        return r;
+    });
+}
+
+}  // extern "C"

@@ -1,0 +1,403 @@
+// hq_runtime.h -- what the host runtime's translation units share: the context and
+// the search (the opaque types of include/hq.h), the owners of their device memory,
+// pinned memory and events, the pass value, the profiling tables and the checks
+// written once.  hq_runtime.hip: context, filters, image, options, profiling and
+// the stand-alone utilities; hq_eval.hip: population buffers and evaluation;
+// hq_search_run.hip: the device-resident search and hq_search_*.  Not part of the
+// public ABI.
+//
+// Ownership: a DevBuf, PinBuf or EventSet frees what it holds when it goes out of
+// scope or its owner is deleted; nothing in the runtime frees one by hand except
+// to give memory back early (option lists16 = 0).
+#pragma once
+
+#include <rccl/rccl.h>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "hq_launch.h"
+#include "hq_swasa.h"
+
+#ifndef HQ_COST_TW
+#define HQ_COST_TW 128
+#endif
+#ifndef HQ_SA_GRAPH
+#define HQ_SA_GRAPH 0  // (measured slower: C3 0.528 -> 0.540 ms, shard-of-8 0.1035 -> 0.110 ms per step)
+#endif
+
+namespace hq {
+
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    hipError_t ensure(size_t n) {
+        if (n <= bytes) return hipSuccess;
+        release();
+        hipError_t e = hipMalloc(&p, n);
+        if (e == hipSuccess) bytes = n;
+        return e;
+    }
+    hipError_t upload(const void* src, size_t n) {  // ensure(n), then a blocking copy from the host
+        const hipError_t e = ensure(n);
+        return e != hipSuccess ? e : hipMemcpy(p, src, n, hipMemcpyHostToDevice);
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+    template <typename T>
+    T* as() const { return static_cast<T*>(p); }
+};
+
+// Pinned host memory, grown like a DevBuf.
+struct PinBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    PinBuf() = default;
+    PinBuf(const PinBuf&) = delete;
+    PinBuf& operator=(const PinBuf&) = delete;
+    ~PinBuf() { if (p) (void)hipHostFree(p); }
+    hipError_t ensure(size_t n) {
+        if (n <= bytes) return hipSuccess;
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        bytes = 0;
+        hipError_t e = hipHostMalloc(&p, n, hipHostMallocDefault);
+        if (e == hipSuccess) bytes = n;
+        return e;
+    }
+    template <typename T>
+    T* as() const { return static_cast<T*>(p); }
+};
+
+// Profiling events.  A slot whose event could not be created stays null: a launch
+// under a null event is an untimed launch.
+struct EventSet {
+    std::vector<hipEvent_t> ev;
+    EventSet() = default;
+    EventSet(const EventSet&) = delete;
+    EventSet& operator=(const EventSet&) = delete;
+    ~EventSet() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    hipError_t ensure(size_t n) {
+        if (n > ev.size()) ev.resize(n, nullptr);
+        for (hipEvent_t& e : ev)
+            if (!e) {
+                const hipError_t r = hipEventCreate(&e);
+                if (r != hipSuccess) {
+                    e = nullptr;
+                    return r;
+                }
+            }
+        return hipSuccess;
+    }
+};
+
+// ---- profiling: stages (hq_profile_get's names) and event pairs ----------------
+struct ProfSlot {
+    double ms = 0.0;
+    int64_t launches = 0;
+};
+
+enum Stage {
+    kStGrid, kStAssign, kStCost, kStFinalize, kStSaStep, kStComm, kStCentroid, kStLloyd, kStHist, kStErrsum,
+    kStReseed, kStDither, kStages
+};
+inline constexpr const char* kStageNames[kStages] = {"grid", "assign", "cost", "finalize", "sa_step", "comm",
+                                                     "centroid", "lloyd", "hist", "errsum", "reseed", "dither"};
+
+// The start/stop event pairs of one evaluation (the context's EventSet) or of one
+// search iteration (kPairs pairs per iteration of a run in hq_search::pev).  A pass
+// takes four consecutive pairs -- grid, assign, cost, finalize -- from its first
+// (pass_pairs): the main evaluation's, a hybrid iteration's assign-only pass's or
+// a repair iteration's cost pass's.
+enum Pair {
+    kPGrid, kPAssign, kPCost, kPFinalize,  // the evaluation
+    kPSaStep,                              // the SA step that generated its population
+    kPComm,                                // its collective
+    kPDither,                              // dither_kernel in the place of grid + assign
+    kPLloydGrid, kPLloydAssign,            // hybrid iteration: the assign-only pass,
+    kPSums, kPLloydUpdate,                 // the sums kernel (also hq_cluster_sums'), the update kernel
+    kPRepGrid, kPRepAssign, kPRepCost,     // repair iteration: the cost pass,
+    kPErrsum, kPReseed,                    // the error kernels (also hq_cluster_errors'), the reseed kernel
+    kPHist,                                // hq_color_histogram's kernel
+    kPairs
+};
+// The stage each pair's time and launch count go to.
+inline constexpr Stage kPairStage[kPairs] = {kStGrid, kStAssign, kStCost, kStFinalize, kStSaStep, kStComm,
+                                             kStDither, kStGrid, kStAssign, kStCentroid, kStLloyd, kStGrid,
+                                             kStAssign, kStCost, kStErrsum, kStReseed, kStHist};
+
+// One evaluation's or iteration's events and which pairs it recorded (events of an
+// earlier call may sit in the other slots, so only recorded pairs are accumulated).
+struct ProfRec {
+    const hipEvent_t* ev = nullptr;  // 2 kPairs events; null: not profiling
+    uint32_t recorded = 0;           // bit p: pair p
+};
+
+// `launch()` with pair p's events riding on it (start / stop: which of the two; a
+// launch loop times its first and last).  The pending events are cleared on every
+// way out, so the caller may return on the error at once.
+template <typename F>
+inline hipError_t timed_launch(ProfRec& pr, Pair p, F&& launch, bool start = true, bool stop = true) {
+    if (pr.ev) {
+        set_launch_events(start ? pr.ev[2 * p] : nullptr, stop ? pr.ev[2 * p + 1] : nullptr);
+        pr.recorded |= 1u << p;
+    }
+    const hipError_t e = launch();
+    set_launch_events(nullptr, nullptr);
+    return e;
+}
+
+// ---- a pass: how far an evaluation goes and how its index images are made -------
+// Full: grid, assign, cost, finalize into d_out, the collective on d_out.
+// Fold: a folding search's evaluation -- no finalize (the accept step reads the
+//   fixed-point sums itself); the collective gathers the ranks' counter blocks.
+// AssignOnly (a hybrid iteration's first pass): the argmin alone -- grid build or
+//   zeroing, then assign -- for the index images the sums kernel reads.
+// CostOnly (a repair iteration's first pass): grid, assign and cost -- the index
+//   images and, with option "pixel_err" in force, the error image the error kernel
+//   reads.
+// Dither (hq_dither_population): a full pass whose index images are the
+//   Floyd-Steinberg rendering at `strength` -- the counter set and the used bits
+//   zeroed as without a grid, then dither_kernel in the place of grid + assign.
+// Counter-set parity: each pass takes the other counter set than the last one
+// (build_grid zeroes it), so an accept step can read the last set while the next
+// is filled.  A side pass (AssignOnly, CostOnly: nothing reads its sums, so no
+// finalize and no collective) fills the other set without making it the current
+// one: c->acc_par stays the set of the last full pass (what sa_args, the fold and
+// the finalize read), and the full pass that follows takes, and zeroes, the same
+// set again.
+struct Pass {
+    enum Kind { Full, Fold, AssignOnly, CostOnly, Dither } kind = Full;
+    float strength = 0.f;  // Dither
+    bool side() const { return kind == AssignOnly || kind == CostOnly; }
+    Pair pairs() const { return kind == AssignOnly ? kPLloydGrid : kind == CostOnly ? kPRepGrid : kPGrid; }
+};
+
+}  // namespace hq
+
+struct hq_ctx {
+    int device = 0;
+    int de_type = HQ_DE_CIE76;
+    hipStream_t stream = nullptr;
+    std::string err;
+
+    // filters (IM:800-841)
+    int taps = 0, half = 0;
+    std::vector<float> k1, k2, k3, absk3;
+    hq::DevBuf d_k1, d_k2, d_k3, d_absk3;
+    hq::DevBuf d_vtaps;    // tiled generic path: [7][vtap_pitch] vertical taps per plane, zero-padded
+    int vtap_pitch = 0;
+    int fast_hb = 0;   // fast path tap bucket (fast_bucket(half)); 0 = generic path only
+    hq::DevBuf d_taps;     // fast path taps, build_fast_taps (the filters centred in the bucket)
+    hq::DevBuf d_vfrag16;  // split-f16 MFMA A fragments of the stacked vertical taps
+    hq::DevBuf d_vfrag16p; // the same in cost16w's (hi, lo) pair layout
+    hq::DevBuf d_vfragm;   // the tiled generic path's matrix-core vertical taps (build_vtile_dup_taps)
+    hq::DevBuf d_htaps;    // gen_hrow4's packed horizontal taps [T][2] float4
+
+    // image
+    bool have_image = false;
+    hq::Geom g{};
+    float illum[3] = {0.95047f, 1.0f, 1.0883f};
+    hq::DevBuf d_R, d_G, d_B;          // planar, extended rows (n_ext, padded to 4)
+    hq::DevBuf d_rgbx;                 // packed 8-bit copy of R,G,B when every channel is k/255
+    bool img_u8 = false;
+    hq::DevBuf d_labL, d_labA, d_labB;  // planar LabRef, owned rows, lab_pitch
+
+    // population work buffers
+    int P_cap = 0, K_cur = 0;
+    hq::DevBuf d_pal_in, d_pal, d_opp, d_opp16, d_dup, d_pflags, d_lvl1, d_lvl2, d_idx, d_used_mask,
+        d_acc, d_out, d_gen_t;
+    // d_acc: two sets of fixed-point dE sums [kAccSlots][P][4] u64 (acc_add), d_used_mask two
+    // sets of used bits [kUsedSlots][used_stride]; evaluation n fills set acc_par = n & 1
+    int acc_par = 0;
+    hq::DevBuf d_pixerr;           // option "pixel_err": [P][n_own] per-pixel dE of the last evaluation
+    hq::DevBuf d_idx32, d_used32;  // K > 16384 (hq_wide.hip): 32-bit index images, per-colour used flags
+    hq::DevBuf d_idx16, d_dist;    // 256 < K <= 16384 (chunked): 16-bit index images, pass distances
+    hq::DevBuf d_l1n, d_l2n;       // the native 16-bit candidate lists (hq_lists16.hip)
+    int nch_cur = 1;           // chunks per palette of the population being enqueued (1: K <= 256)
+    int last_nch = 1;          // ... of the last evaluation (its index image: u16 when > 1)
+    hq::PinBuf h_pal;          // pinned [P][K][4] float
+    hq::PinBuf h_out;          // pinned [P][1+K] double
+    int last_P = 0;
+    // hq_cluster_sums: the index images on the device are those of a population of last_P x
+    // K_cur evaluated by hq_eval_population[_partial] (a search run or a new image unsets it)
+    bool sums_ok = false;
+    hq::DevBuf d_sums;             // [P][K][4] int64 sums, then the planar form's range flag
+    // hybrid iterations: every owned pixel of the planar image is finite and in [0, 1], the
+    // condition of the planar form's sums (-1: not established yet for this image)
+    int planar_ok = -1;
+    hq::DevBuf d_hist;             // hq_color_histogram: [2^(3 bits)][4] int64 cells, then the range flag
+    // hq_cluster_errors: the error image on the device is that of the last evaluation (option
+    // "pixel_err" was on when hq_eval_population[_partial] enqueued it; read with sums_ok)
+    bool err_ok = false;
+    hq::DevBuf d_errstat, d_worst; // [P][K][4] u64 statistics, then the flag; [P][K] float4 worst pixels
+    hq::DevBuf d_dcarry;           // hq_dither_population: [P][3][W] errors of a strip's last row
+
+    // options
+    int G2 = 32;           // argmin grid resolution (0 = exhaustive)
+    int cost_variant = 0;  // 0 fast tiled (default), 1 generic two-pass (LDS-tiled), 2 the generic
+                           // pair per pixel in the reference's summation order
+    int cost_rows = 16;    // fast path tiles: 16 x 128 (cost16w_kernel) or 8 x 108 (cost_mfma_kernel)
+    int cost_tw = HQ_COST_TW;  // 16-row tiles at HB = 10: 128 (4 waves) or 256 columns (8 waves; slower)
+    int gen_hrow4 = 1;     // tiled generic path: 4 outputs per thread in the horizontal pass
+    int gen_vtile2 = 1;    // tiled generic path: double-buffered LDS-DMA vertical pass (half <= 64)
+    int gen_vmfma = 1;     // tiled generic path: the vertical pass on the matrix cores (half <= 64)
+    int gen_hmfma = 1;     // ... and the horizontal pass (gen_hmfma) with it
+    int gen_shape = 0;     // their tile shapes: 0 by grid size, 1 short, 2 tall (option gen_tile_shape)
+    int gen_hrow_no = 4;   // tiled generic path: horizontal outputs per thread (4 or 8)
+    int sa_graph = HQ_SA_GRAPH;  // device-resident search: each run's kernels as one hipGraph
+    int assign_blocks_per_cu = 0;  // 0 = auto: assign_pipe_kernel<NG>'s residency (the occupancy
+                                   // query, assign_res[NG]), one round of workgroups, each
+                                   // thread a grid-stride pixel sequence
+    int assign_res[5] = {};   // [NG]
+    int assign_res_chunked = 0;  // the chunk-combining forms (NG = 4)
+    int psplit = 0;        // with a communicator of N ranks and the whole image on every rank: rank r
+                           // evaluates palettes [r P/N, (r+1) P/N), then one all-gather (option
+                           // "palette_split"; SURVEY 8e's split of large populations)
+    int slice_ranks = 1, slice_rank = 0;  // test only: the same slice without a communicator
+    int slice_lo = 0, slice_n = 0;        // the last evaluation's palettes held on this device
+    int fold_blocks = 1, fold_block = 0;  // test only: rank blocks of the counters without a communicator
+    int lists16 = 1;       // native 16-bit candidate lists: 1 = chunked palettes of 4 to 32 chunks, 2 = 2 .. 32
+    int chunked = 1;       // 256 < K <= 16384: palettes as 256-colour chunks through the grid and
+                           // tiled kernels (option "chunked"; 0 = the exhaustive K > 256 path)
+    int img_u8_path = 1;   // assign reads the packed 8-bit image when there is one (option 'img_u8')
+    int shard_solo = 0;    // experiment: a sharded search without a communicator (per-rank timing)
+    int sa_device = 1;     // hq_search_*: 1 = SWASA iterations resident on the device (no host
+                           // round trip per iteration), 0 = host-driven (one eval call each)
+    int pixel_err = 0;     // test option: the cost kernels also write the per-pixel dE
+    int dither_rows = 1024;  // hq_dither_population: rows per strip (option "dither_rows")
+    int trim = 1;          // skip taps < 1e-9 of the peak of the narrow k1 filters
+    bool trim_ok = false;  // set by hq_set_filters (the bucket's narrow-filter windows hold)
+    bool pal_generic = false;  // this population needs the generic cost path (palette_fits_fast)
+    bool taps_generic = false;  // set by hq_set_filters: a tap outside the split-f16 range (taps_fit_split),
+                                // so the cost runs on the fp32 forms whatever cost_variant and gen_vmfma say
+
+    // comm
+    ncclComm_t comm = nullptr;
+    int nranks = 1, rank = 0;
+
+    // profiling
+    bool prof = false;
+    hq::ProfSlot prof_stage[hq::kStages];
+    hq::EventSet ev;  // 2 kPairs events, made by hq_create
+    int num_cu = 256;
+    size_t lds_optin = 160 * 1024;  // per-workgroup LDS a kernel may opt into (hq_create's query)
+};
+
+struct hq_search {
+    hq_ctx* ctx;
+    hq::SearchDriver* driver;  // host-driven search (sa_device = 0), else null
+    int K;
+    // device-resident search: the SWASA state lives on the device, ping-ponged
+    // between [0] and [1] by sa_step_kernel; the host keeps the iteration-only
+    // quantities (temperature, step width, convergence threshold) in `pol`,
+    // whose RNG is unused.
+    hq::Swasa* pol = nullptr;
+    hq_swasa_params prm{};
+    int P = 0, ite = 0, st = 0, cd = 0;  // state and candidate buffer parities
+    int every = 0;                       // hq_search_set_lloyd: iteration ite % every == 0 is hybrid (0: none)
+    int repair_every = 0;                // hq_search_set_repair: iteration ite % repair_every == 0 repairs (0: none)
+    int repair_moves = -1;               // ... at most so many colours per palette (< 0: no limit)
+    int nch = 1;                         // chunked palettes (256 < K <= 16384): chunks per palette
+    bool fold = false;                   // accept steps reduce the partials (no finalize launch)
+    ncclComm_t comm = nullptr;           // the context's communicator at hq_search_create
+    float t_acc = 0.f;                   // temperature / threshold of the iteration
+    double keep_acc = 0.0;               // whose population awaits acceptance
+    hq::DevBuf colors[2], cand[2], err[2], seed[2], best_err[2], best_colors, jA, jC;
+    hq::EventSet pev;                    // profiling: 2 kPairs events per iteration of a run
+    hipGraphExec_t gexec = nullptr;      // option sa_graph: the last run's iteration chain
+    int gexec_iters = 0;                 // (its iteration count: the topology an update must match)
+};
+
+namespace hq {
+
+int fail(hq_ctx* c, int code, const char* fmt, ...);
+
+#define HIP_TRY(ctx, expr)                                                                      \
+    do {                                                                                        \
+        hipError_t _e = (expr);                                                                 \
+        if (_e != hipSuccess)                                                                   \
+            return fail((ctx), _e == hipErrorOutOfMemory ? HQ_ERR_NOMEM : HQ_ERR_DEVICE,        \
+                        "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+    } while (0)
+
+#define NCCL_TRY(ctx, expr)                                                                     \
+    do {                                                                                        \
+        ncclResult_t _r = (expr);                                                               \
+        if (_r != ncclSuccess)                                                                  \
+            return fail((ctx), HQ_ERR_COMM, "%s failed: %s", #expr, ncclGetErrorString(_r));    \
+    } while (0)
+
+// Option "pixel_err" forced on for a call's own evaluations, the caller's value back on every way out.
+struct PixelErrScope {
+    hq_ctx* c;
+    int was;
+    explicit PixelErrScope(hq_ctx* c_) : c(c_), was(c_->pixel_err) { c->pixel_err = 1; }
+    ~PixelErrScope() { c->pixel_err = was; }
+    PixelErrScope(const PixelErrScope&) = delete;
+    PixelErrScope& operator=(const PixelErrScope&) = delete;
+};
+
+// The chunk count of the population being enqueued, for one search call.
+struct NchScope {
+    hq_ctx* c;
+    NchScope(hq_ctx* cc, int nch) : c(cc) { c->nch_cur = nch; }
+    ~NchScope() { c->nch_cur = 1; }
+};
+
+inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
+inline bool whole_image(const hq_ctx* c) { return c->g.r0 == 0 && c->g.r1 == c->g.H; }
+
+// A row-block split (a communicator, no palette split) keeps one block of
+// counters and used bits per rank in each set, [ranks][...]: every rank fills
+// its own block, and a device-resident search's one all-gather per iteration
+// hands every rank all the blocks, which its accept step folds (no finalize).
+// (test options fold_blocks / fold_block: the same layout without a communicator,
+// this context filling block fold_block and the others staying zero)
+inline int rank_blocks(const hq_ctx* c) { return c->comm ? (c->psplit ? 1 : c->nranks) : c->fold_blocks; }
+inline int own_block(const hq_ctx* c) { return c->comm ? (rank_blocks(c) > 1 ? c->rank : 0) : c->fold_block; }
+// A device-resident search folds the partials in its accept step unless the
+// palette split all-gathers finalized rows.
+inline bool search_folds(const hq_ctx* c) { return !(c->comm && c->psplit); }
+// The sums form assign's own condition picks: the packed bytes (den 255), else
+// the planar floats (den 2^32).
+inline bool sums_u8(const hq_ctx* c) { return c->img_u8 && c->img_u8_path; }
+
+// hq_runtime.hip
+int bind(hq_ctx* c);
+// `what` (a call's or a move's name) works on the whole image, with every palette's index image on
+// this context: refused on a row-block shard (HQ_ERR_STATE), with a communicator of more than one
+// rank (HQ_ERR_UNSUPPORTED; comm_hint: what to do instead) and on a palette slice
+// (HQ_ERR_UNSUPPORTED; psplit_alone: also under option "palette_split" without a communicator,
+// where it slices nothing).
+int whole_image_only(hq_ctx* c, const char* what, const char* comm_hint = "", bool psplit_alone = true);
+ProfRec prof_begin(hq_ctx* c);  // the context's events (profiling on) or none
+// Add the recorded pairs' kernel times to their stages (the events have completed).
+void prof_accumulate(hq_ctx* c, const ProfRec& pr);
+
+// hq_eval.hip
+int ensure_population(hq_ctx* c, int P, int K);
+PaletteArgs prep_args(hq_ctx* c, int K);
+uint64_t* acc_base(hq_ctx* c, int par, int P);
+uint32_t* used_base(hq_ctx* c, int par, int Ps);
+int enqueue_core(hq_ctx* c, int P, int K, ProfRec& pr, Pass pass = {});
+void pack_chunks(const float* pal, int P, int K, int nch, float* out);
+ClusterArgs cluster_args(hq_ctx* c, int P, int K, int* idx_bytes);
+ClusterErrArgs cluster_err_args(hq_ctx* c, int P, int K, int* idx_bytes);
+int cluster_sums(hq_ctx* c, int P, int K, int64_t* out, int64_t* den);
+int cluster_errors(hq_ctx* c, int P, int K, int64_t* err, float* worst, bool ignore_bad = false);
+int planar_in_range(hq_ctx* c);  // -> c->planar_ok
+
+}  // namespace hq

@@ -1,0 +1,499 @@
+// hq_search_run.hip -- libhq host runtime, the search: the device-resident SWASA
+// run (its SA steps, hybrid and repair iterations, the optional graph capture) and
+// the hq_search_* entry points, host-driven searches among them.  The kernels:
+// hq_search.hip; shared declarations: hq_runtime.h.
+#include "hq_runtime.h"
+
+using namespace hq;
+
+namespace {
+
+// The arguments of an SA step: accept the population in cand[cd] (if `accept`,
+// its counters in set c->acc_par), then generate the next candidates into
+// cand[1 - cd] (if `generate`).
+SaArgs sa_args(hq_search* s, bool accept, bool init, bool generate, bool random, float amax) {
+    hq_ctx* c = s->ctx;
+    SaArgs a{};
+    a.out = c->d_out.as<double>();
+    a.colors_in = s->colors[s->st].as<float>();
+    a.colors_out = s->colors[1 - s->st].as<float>();
+    a.cand_in = s->cand[s->cd].as<float>();
+    a.cand_out = s->cand[1 - s->cd].as<float>();
+    a.err_in = s->err[s->st].as<double>();
+    a.err_out = s->err[1 - s->st].as<double>();
+    a.seed_in = s->seed[s->st].as<uint64_t>();
+    a.seed_out = s->seed[1 - s->st].as<uint64_t>();
+    a.best_err_in = s->best_err[s->st].as<double>();
+    a.best_err_out = s->best_err[1 - s->st].as<double>();
+    a.best_colors = s->best_colors.as<float>();
+    a.jump_A = s->jA.as<uint64_t>();
+    a.jump_C = s->jC.as<uint64_t>();
+    a.prep = prep_args(c, s->nch > 1 ? kMaxK : s->K);
+    a.nch = s->nch;
+    a.n_total = (double)c->g.W * (double)c->g.H;
+    a.keep_threshold = s->keep_acc;
+    a.temperature = s->t_acc;
+    a.amax = amax;
+    a.delta = s->prm.delta;
+    a.P = s->P;
+    a.K = s->K;
+    a.accept = accept;
+    a.init = init;
+    a.generate = generate;
+    a.random = random;
+    a.convergence = s->prm.convergence;
+    a.acc = acc_base(c, c->acc_par, a.P);
+    a.used_glob = used_base(c, c->acc_par, a.P * s->nch);
+    a.used_stride = used_stride(a.P * s->nch);
+    a.fold = s->fold;
+    a.nranks = rank_blocks(c);
+    a.acc_rank_words = (int64_t)acc_words(a.P);
+    return a;
+}
+
+// One sa_step launch (sa_args).
+int enqueue_sa_step(hq_search* s, bool accept, bool init, bool generate, bool random, float amax, ProfRec& pr) {
+    hq_ctx* c = s->ctx;
+    const SaArgs a = sa_args(s, accept, init, generate, random, amax);
+    HIP_TRY(c, timed_launch(pr, kPSaStep, [&] { return launch_sa_step(a, c->stream); }));
+    s->st = 1 - s->st;
+    if (generate) s->cd = 1 - s->cd;
+    return HQ_OK;
+}
+
+// What a hybrid or a repair iteration of a device-resident search needs beyond the whole image.
+int device_move_scope(hq_search* s, const char* what) {
+    if (!s->driver && s->nch > 1)
+        return fail(s->ctx, HQ_ERR_UNSUPPORTED, "%s of a device-resident search need K <= %d (K = %d): "
+                                                "set option sa_device 0 before hq_search_create", what, kMaxK, s->K);
+    return HQ_OK;
+}
+
+// ---- hybrid iterations (hq_search_set_lloyd) -----------------------------------
+// The scope of a k-means move is hq_refine_population's: the whole image on
+// this context, every palette's index image here.
+int lloyd_scope(hq_search* s) {
+    if (int rc = whole_image_only(s->ctx, "hybrid iterations")) return rc;
+    return device_move_scope(s, "hybrid iterations");
+}
+
+// A run of `iterations` from iteration `ite` (the last one done) holds an iteration
+// that is a multiple of `every`.
+bool period_in_run(const hq_search* s, int every, int ite, int iterations) {
+    if (every <= 0) return false;
+    const int last = (int)std::min<int64_t>((int64_t)ite + iterations, s->prm.imax);
+    return last / every > ite / every;
+}
+
+// ---- repair iterations (hq_search_set_repair) ----------------------------------
+// hq_repair_population's scope, and a dE type whose costs are numbers.
+int repair_scope(hq_search* s) {
+    hq_ctx* c = s->ctx;
+    if (c->de_type == HQ_DE_CIE94)
+        return fail(c, HQ_ERR_UNSUPPORTED, "repair iterations on a dE94 context: its costs are NaN on real images");
+    if (int rc = whole_image_only(c, "repair iterations")) return rc;
+    if (int rc = device_move_scope(s, "repair iterations")) return rc;
+    if (c->have_image && (int64_t)c->g.W * c->g.H >= ((int64_t)1 << 32))
+        return fail(c, HQ_ERR_UNSUPPORTED, "image of 2^32 pixels or more: a position does not fit 32 bits");
+    return HQ_OK;
+}
+
+int lloyd_validate(hq_search* s) {
+    hq_ctx* c = s->ctx;
+    if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
+    if (sums_u8(c)) return HQ_OK;
+    if (int rc = planar_in_range(c)) return rc;
+    if (!c->planar_ok)
+        return fail(c, HQ_ERR_UNSUPPORTED, "planar image with a pixel outside [0, 1] or not finite: no exact sums, "
+                                           "no hybrid iteration");
+    return HQ_OK;
+}
+
+// The k-means move of a device-resident hybrid iteration, after the sa_step that
+// generated and prepared the candidates (now cand[cd]): the assign-only pass,
+// the sums kernel into d_sums (zero on entry: the run's memset, then the update
+// kernel's own zeroing) and the update kernel, which prepares the updated
+// candidates for the evaluation that follows.  pr: the iteration's events.
+int enqueue_lloyd(hq_search* s, ProfRec& pr) {
+    hq_ctx* c = s->ctx;
+    int rc = enqueue_core(c, s->P, s->K, pr, Pass{Pass::AssignOnly});
+    if (rc) return rc;
+    int idx_bytes = 1;
+    const ClusterArgs ca = cluster_args(c, s->P, s->K, &idx_bytes);
+    HIP_TRY(c, timed_launch(pr, kPSums, [&] { return launch_cluster_sums(ca, idx_bytes, c->num_cu, c->stream); }));
+    const LloydArgs la{ca.sums, s->cand[s->cd].as<float>(), prep_args(c, s->K), s->K, sums_u8(c) ? 1 : 0};
+    HIP_TRY(c, timed_launch(pr, kPLloydUpdate, [&] { return launch_lloyd_update(la, s->P, c->stream); }));
+    return HQ_OK;
+}
+
+// The repair move of a device-resident repair iteration, after the sa_step that
+// generated and prepared the candidates (now cand[cd]) and after the k-means move
+// when the iteration is hybrid too: a cost pass that stores the error image
+// (option "pixel_err" forced on for it alone), the error kernels into d_errstat
+// (zero on entry: the run's memset, then the reseed kernel's own zeroing) and
+// d_worst, and the reseed kernel, which prepares the repaired candidates for the
+// evaluation that follows.  The flag of pixels without a usable dE is not read:
+// they are left out, as the host-driven form leaves them out.
+int enqueue_repair(hq_search* s, ProfRec& pr) {
+    hq_ctx* c = s->ctx;
+    int rc;
+    {
+        const PixelErrScope scope(c);
+        rc = enqueue_core(c, s->P, s->K, pr, Pass{Pass::CostOnly});
+    }
+    if (rc) return rc;
+    int idx_bytes = 1;
+    const ClusterErrArgs ea = cluster_err_args(c, s->P, s->K, &idx_bytes);
+    HIP_TRY(c, timed_launch(pr, kPErrsum, [&] { return launch_cluster_errors(ea, idx_bytes, c->num_cu, c->stream); }));
+    const ReseedArgs ra{ea.stats, ea.worst, s->cand[s->cd].as<float>(), prep_args(c, s->K), s->K, s->repair_moves};
+    HIP_TRY(c, timed_launch(pr, kPReseed, [&] { return launch_reseed(ra, s->P, c->stream); }));
+    return HQ_OK;
+}
+
+// A search's evaluation pass: folding (search_folds) or full.
+Pass search_pass(const hq_search* s) { return Pass{s->fold ? Pass::Fold : Pass::Full}; }
+
+// population: hq_search_create_from's ([P][4K], checked), or null for the random one.
+int device_search_create(hq_ctx* c, const hq_swasa_params* params, int K, uint64_t seed, const float* population,
+                         hq_search* s) {
+    const int P = params->population;
+    s->prm = *params;
+    s->P = P;
+    // no communicator, or row blocks: nothing has to see the finalized sums, so
+    // the accept step reads the fixed-point sums itself (one launch less per
+    // iteration; row blocks: one all-gather of every rank's counter blocks in
+    // place of finalize + the all-reduce of P (1 + K) doubles).  The palette
+    // split all-gathers finalized rows.
+    s->fold = search_folds(c);
+    s->comm = c->comm;
+    if (c->slice_ranks > 1 && !c->comm)
+        return fail(c, HQ_ERR_STATE, "palette slice without a communicator (test option): no search");
+    s->pol = new Swasa(*params, seed);
+    const NchScope scope(c, s->nch);
+    int rc = ensure_population(c, P, K);
+    if (rc) return rc;
+    const size_t n4 = (size_t)P * 4 * K;
+    for (int i = 0; i < 2; ++i) {
+        HIP_TRY(c, s->colors[i].ensure(sizeof(float) * n4));
+        HIP_TRY(c, s->cand[i].ensure(sizeof(float) * n4));
+        HIP_TRY(c, s->err[i].ensure(sizeof(double) * P));
+        HIP_TRY(c, s->seed[i].ensure(sizeof(uint64_t)));
+    }
+    for (int i = 0; i < 2; ++i) HIP_TRY(c, s->best_err[i].ensure(sizeof(double)));
+    HIP_TRY(c, s->best_colors.ensure(sizeof(float) * 4 * K));
+    // java.util.Random jumps: n steps = A_n s + C_n (mod 2^48), n = 0 .. 3KP
+    const size_t nj = (size_t)3 * K * P + 1;
+    std::vector<uint64_t> A(nj), C(nj);
+    const uint64_t mask = (1ull << 48) - 1, mult = 0x5DEECE66Dull;
+    A[0] = 1;
+    C[0] = 0;
+    for (size_t n = 1; n < nj; ++n) {
+        A[n] = (A[n - 1] * mult) & mask;
+        C[n] = (C[n - 1] * mult + 0xBull) & mask;
+    }
+    HIP_TRY(c, s->jA.upload(A.data(), sizeof(uint64_t) * nj));
+    HIP_TRY(c, s->jC.upload(C.data(), sizeof(uint64_t) * nj));
+    const uint64_t s0 = (seed ^ mult) & mask;  // JavaRandom::set_seed
+    HIP_TRY(c, hipMemcpy(s->seed[0].p, &s0, sizeof s0, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemset(s->err[0].p, 0, sizeof(double) * P));
+    if (rank_blocks(c) > 1 && !c->comm) {  // test layout: the blocks no rank fills read zero
+        HIP_TRY(c, hipMemsetAsync(c->d_acc.p, 0, c->d_acc.bytes, c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->d_used_mask.p, 0, c->d_used_mask.bytes, c->stream));
+    }
+    for (int i = 0; i < 2; ++i) HIP_TRY(c, hipMemset(s->best_err[i].p, 0, sizeof(double)));
+    s->st = s->cd = 0;
+    ProfRec untimed;
+    // IM:385-493: random population (SW:40-52), its evaluation, argmin
+    if ((rc = enqueue_sa_step(s, false, false, true, true, 0.f, untimed))) return rc;
+    // A given population takes the random one's place after that step has drawn it (the seed
+    // is past the 3 K P draws as always): into the candidate buffer the accept step reads,
+    // and through the palette prep as an evaluation uploads it (chunked palettes: pack_chunks'
+    // sub-palettes), so the prep's outputs and the duplicate flags are the given colours'.
+    std::vector<float> given;  // (.w = 0; read by the copy below until the synchronise)
+    if (population) {
+        given.assign(population, population + n4);
+        for (size_t e = 3; e < n4; e += 4) given[e] = 0.0f;
+        hipStream_t st = c->stream;
+        HIP_TRY(c, hipMemcpyAsync(s->cand[s->cd].p, given.data(), sizeof(float) * n4, hipMemcpyHostToDevice, st));
+        const size_t n_in = s->nch > 1 ? (size_t)P * s->nch * kMaxK : (size_t)P * K;
+        if (s->nch > 1) pack_chunks(given.data(), P, K, s->nch, c->h_pal.as<float>());
+        else std::memcpy(c->h_pal.p, given.data(), sizeof(float) * n4);
+        HIP_TRY(c, hipMemcpyAsync(c->d_pal_in.p, c->h_pal.p, sizeof(float4) * n_in, hipMemcpyHostToDevice, st));
+        HIP_TRY(c, launch_prep_palette(prep_args(c, s->nch > 1 ? kMaxK : K), P * s->nch, st));
+    }
+    if ((rc = enqueue_core(c, P, K, untimed, search_pass(s)))) return rc;
+    if ((rc = enqueue_sa_step(s, true, true, false, false, 0.f, untimed))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    s->ite = 0;
+    return HQ_OK;
+}
+
+// IM:497-568 for up to `iterations` iterations, all enqueued before one sync.
+int device_search_run(hq_search* s, int iterations, int* ran) {
+    hq_ctx* c = s->ctx;
+    int done = 0, rc;
+    // The context may have changed since hq_search_create or the last run (an
+    // option such as 'grid' or 'assign_blocks_per_cu', a new image): size its
+    // work buffers for the current geometry before enqueueing anything.
+    if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
+    const NchScope scope(c, s->nch);
+    if ((rc = ensure_population(c, s->P, s->K))) return rc;
+    if (s->comm != c->comm || s->fold != search_folds(c))
+        return fail(c, HQ_ERR_STATE, "communicator or palette split changed after hq_search_create: "
+                                     "recreate the search");
+    // profiling: each iteration's events and the pairs it records (events of an earlier run's
+    // hybrid or repair iteration may sit in the slots this run does not use)
+    const bool prof = c->prof;
+    if (prof) HIP_TRY(c, s->pev.ensure((size_t)2 * kPairs * iterations));
+    std::vector<ProfRec> recs(prof ? iterations : 0);
+    ProfRec untimed;
+    // hybrid iterations in this run: the sums buffer before anything is enqueued
+    // (no allocation while a run is captured), zeroed once below -- the update
+    // kernel leaves it zero for the next hybrid iteration
+    const bool lloyd = period_in_run(s, s->every, s->ite, iterations);
+    const size_t sums_bytes = sizeof(int64_t) * ((size_t)s->P * s->K * 4 + 1);
+    if (lloyd) HIP_TRY(c, c->d_sums.ensure(sums_bytes));
+    // repair iterations in this run: the same for the error image, the statistics and the
+    // worst pixels -- nothing of it without one
+    const bool repair = period_in_run(s, s->repair_every, s->ite, iterations);
+    const size_t stat_bytes = sizeof(int64_t) * ((size_t)s->P * s->K * 4 + 1);
+    if (repair) {
+        HIP_TRY(c, c->d_pixerr.ensure(sizeof(float) * (size_t)s->P * std::max<int64_t>((int64_t)c->g.W * (c->g.r1 - c->g.r0), 1)));
+        HIP_TRY(c, c->d_errstat.ensure(stat_bytes));
+        HIP_TRY(c, c->d_worst.ensure(sizeof(float) * (size_t)s->P * s->K * 4));
+    }
+    // option sa_graph: the run's kernels go into one hipGraph (stream capture),
+    // replayed as a whole -- a chain of dependent kernels costs ~2.7 us per
+    // kernel from the stream and ~1.8 from a graph (profiles/r04_graph_gap_
+    // microbench.txt).  The previous run's executable graph is updated in place
+    // when the iteration count (the topology) is the same, else instantiated
+    // anew.  Not with profiling events (they ride on the launches).
+    const bool graph = c->sa_graph && !prof;
+    if (graph) HIP_TRY(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+    auto abort_capture = [&](int rc0) {
+        if (graph) {
+            hipGraph_t gr = nullptr;
+            if (hipStreamEndCapture(c->stream, &gr) == hipSuccess && gr) (void)hipGraphDestroy(gr);
+        }
+        return rc0;
+    };
+    auto zero_table = [&](const DevBuf& b, size_t bytes) {  // (a failure ends the capture)
+        const hipError_t e = hipMemsetAsync(b.p, 0, bytes, c->stream);
+        if (e != hipSuccess) (void)abort_capture(0);
+        return e;
+    };
+    if (lloyd) HIP_TRY(c, zero_table(c->d_sums, sums_bytes));
+    if (repair) HIP_TRY(c, zero_table(c->d_errstat, stat_bytes));
+    for (; done < iterations && s->ite < s->prm.imax; ++done) {
+        const int ite = ++s->ite;
+        s->pol->reduce_temperature_if_necessary(ite);                  // IM:507
+        const float amax = s->pol->max_step_width(ite) / 256.0f;       // SW:91-101
+        ProfRec& pr = prof ? recs[done] : untimed;
+        if (prof) pr.ev = &s->pev.ev[(size_t)2 * kPairs * done];
+        // accept the previous iteration's population (none at the first of a run)
+        if ((rc = enqueue_sa_step(s, done > 0, false, true, false, amax, pr))) return abort_capture(rc);
+        if (s->every > 0 && ite % s->every == 0 && (rc = enqueue_lloyd(s, pr))) return abort_capture(rc);
+        if (s->repair_every > 0 && ite % s->repair_every == 0 && (rc = enqueue_repair(s, pr)))
+            return abort_capture(rc);
+        if ((rc = enqueue_core(c, s->P, s->K, pr, search_pass(s)))) return abort_capture(rc);
+        s->t_acc = s->pol->temperature();     // SW:54-57 at this iteration
+        s->keep_acc = s->pol->keep_threshold(ite);
+    }
+    if (done > 0 && (rc = enqueue_sa_step(s, true, false, false, false, 0.f, untimed))) return abort_capture(rc);
+    if (graph) {
+        hipGraph_t gr = nullptr;
+        HIP_TRY(c, hipStreamEndCapture(c->stream, &gr));
+        bool updated = false;
+        if (s->gexec && s->gexec_iters == done) {
+            hipGraphNode_t err_node = nullptr;
+            hipGraphExecUpdateResult res = hipGraphExecUpdateError;
+            updated = hipGraphExecUpdate(s->gexec, gr, &err_node, &res) == hipSuccess &&
+                      res == hipGraphExecUpdateSuccess;
+            if (!updated) (void)hipGetLastError();
+        }
+        if (!updated) {
+            if (s->gexec) (void)hipGraphExecDestroy(s->gexec);
+            s->gexec = nullptr;
+            const hipError_t e = hipGraphInstantiate(&s->gexec, gr, nullptr, nullptr, 0);
+            if (e != hipSuccess) {
+                (void)hipGraphDestroy(gr);
+                s->gexec = nullptr;
+                HIP_TRY(c, e);
+            }
+            s->gexec_iters = done;
+        }
+        (void)hipGraphDestroy(gr);
+        HIP_TRY(c, hipGraphLaunch(s->gexec, c->stream));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; prof && i < done; ++i) prof_accumulate(c, recs[i]);
+    if (ran) *ran = done;
+    return HQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hq_search_create(hq_ctx* c, const hq_swasa_params* params, int K, uint64_t seed,
+                     hq_search** out) {
+    return hq_search_create_from(c, params, K, seed, nullptr, out);
+}
+
+int hq_search_create_from(hq_ctx* c, const hq_swasa_params* params, int K, uint64_t seed,
+                          const float* population, hq_search** out) {
+    if (!c || !params || !out) return HQ_ERR_ARG;
+    *out = nullptr;
+    if (params->population < 1 || params->imax < 1 || params->iTc < 1 || K < 1)
+        return fail(c, HQ_ERR_ARG, "bad SWASA parameters");
+    if (population && !population_in_range(population, params->population, K))
+        return fail(c, HQ_ERR_ARG, "initial population with a channel that is not finite or outside [0, 1]");
+    // device-resident: K <= 256, or chunked palettes (256 < K <= 16384); at most
+    // kSaMaxP palettes (sa_step's per-palette tables) and kSaMaxSub sub-palettes
+    // (its fold reads 8 used words per sub-palette, at most 4 per thread)
+    const int nch = K > kMaxK && K <= kMaxKChunked && c->chunked && c->G2 > 0 ? chunk_count(K) : 1;
+    const bool device = c->sa_device && params->population <= kSaMaxP && params->population * nch <= kSaMaxSub &&
+                        (K <= kMaxK || nch > 1);
+    hq_search* s = new hq_search{c, nullptr, K};
+    int rc;
+    if (device) {
+        if (!c->have_image) rc = fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
+        else rc = bind(c);
+        if (rc) {
+            hq_search_destroy(s);
+            return rc;
+        }
+        if (!whole_image(c) && !(c->comm && c->nranks > 1) && !c->shard_solo) {
+            hq_search_destroy(s);
+            return fail(c, HQ_ERR_STATE, "sharded context without a communicator");
+        }
+        s->nch = nch;
+        rc = device_search_create(c, params, K, seed, population, s);
+    } else {
+        const float delta = params->delta;
+        auto eval = [c, delta](const float* pal, int P, int KK, double* costs) {
+            return hq_eval_population(c, pal, P, KK, delta, costs, nullptr);
+        };
+        s->driver = new SearchDriver(*params, K, seed, eval);
+        // the k-means move, host-driven, is the public triple: an evaluation of the
+        // candidates for their argmin (its cost pass is wasted), the sums, the update
+        s->driver->set_refine([c, delta](float* pal, int P, int KK) {
+            std::vector<double> costs(P);
+            std::vector<int64_t> sums((size_t)P * KK * 4);
+            int64_t den = 0;
+            int rr = hq_eval_population(c, pal, P, KK, delta, costs.data(), nullptr);
+            if (!rr) rr = cluster_sums(c, P, KK, sums.data(), &den);
+            if (!rr && (rr = hq_centroids_from_sums(sums.data(), den, P, KK, pal)))
+                return fail(c, rr, "hq_centroids_from_sums failed");
+            return rr;
+        });
+        // the repair move, host-driven: an evaluation of the candidates that stores their
+        // error image, the error statistics (pixels with no usable dE left out) and the rule
+        s->driver->set_repair([c, delta, s](float* pal, int P, int KK) {
+            const PixelErrScope scope(c);
+            std::vector<double> costs(P);
+            std::vector<int64_t> err((size_t)P * KK * 4);
+            std::vector<float> worst((size_t)P * KK * 4);
+            int rr = hq_eval_population(c, pal, P, KK, delta, costs.data(), nullptr);
+            if (!rr) rr = cluster_errors(c, P, KK, err.data(), worst.data(), true);
+            if (!rr && (rr = hq_reseed_unused(err.data(), worst.data(), P, KK, s->repair_moves, pal, nullptr)))
+                return fail(c, rr, "hq_reseed_unused failed");
+            return rr;
+        });
+        s->prm = *params;
+        s->P = params->population;
+        rc = s->driver->start(population);
+    }
+    c->sums_ok = false;  // (the search's own evaluations replace the index images)
+    if (rc) {
+        hq_search_destroy(s);
+        return rc;
+    }
+    *out = s;
+    return HQ_OK;
+}
+
+int hq_search_run(hq_search* s, int iterations, int* ran) {
+    if (!s || iterations < 0) return HQ_ERR_ARG;
+    int rc;
+    // a hybrid iteration in this run: its scope and the image's validity first, so
+    // a refusal leaves the search where it was
+    const int ite = s->driver ? s->driver->iteration() : s->ite;
+    if (s->ctx && period_in_run(s, s->every, ite, iterations)) {
+        if ((rc = lloyd_scope(s)) || (rc = lloyd_validate(s))) {
+            if (ran) *ran = 0;
+            return rc;
+        }
+    }
+    if (s->ctx && period_in_run(s, s->repair_every, ite, iterations)) {
+        if ((rc = repair_scope(s))) {
+            if (ran) *ran = 0;
+            return rc;
+        }
+    }
+    if (!s->driver) {
+        rc = bind(s->ctx);
+        if (!rc) rc = device_search_run(s, iterations, ran);
+    } else {
+        rc = s->driver->run(iterations, ran, nullptr);
+    }
+    if (s->ctx) s->ctx->sums_ok = false;  // (hq_cluster_sums: a search run has evaluated since)
+    return rc;
+}
+
+int hq_search_set_lloyd(hq_search* s, int every) {
+    if (!s || !s->ctx) return HQ_ERR_ARG;
+    if (every < 0) return fail(s->ctx, HQ_ERR_ARG, "every=%d < 0", every);
+    if (every > 0)
+        if (int rc = lloyd_scope(s)) return rc;
+    s->every = every;
+    if (s->driver) s->driver->set_every(every);
+    return HQ_OK;
+}
+
+int hq_search_set_repair(hq_search* s, int every, int max_moves) {
+    if (!s || !s->ctx) return HQ_ERR_ARG;
+    if (every < 0) return fail(s->ctx, HQ_ERR_ARG, "every=%d < 0", every);
+    if (every > 0)
+        if (int rc = repair_scope(s)) return rc;
+    s->repair_every = every;
+    s->repair_moves = max_moves;
+    if (s->driver) s->driver->set_repair_every(every);
+    return HQ_OK;
+}
+
+int hq_search_best(const hq_search* s, float* colors, double* best_error, int* iteration) {
+    if (!s) return HQ_ERR_ARG;
+    if (!s->driver) {
+        hq_ctx* c = s->ctx;
+        int rc = bind(c);
+        if (rc) return rc;
+        if (colors)
+            HIP_TRY(c, hipMemcpy(colors, s->best_colors.p, sizeof(float) * 4 * s->K, hipMemcpyDeviceToHost));
+        if (best_error)
+            HIP_TRY(c, hipMemcpy(best_error, s->best_err[s->st].p, sizeof(double), hipMemcpyDeviceToHost));
+        if (iteration) *iteration = s->ite;
+        return HQ_OK;
+    }
+    if (colors) std::copy(s->driver->best_colors().begin(), s->driver->best_colors().end(), colors);
+    if (best_error) *best_error = s->driver->best_error();
+    if (iteration) *iteration = s->driver->iteration();
+    return HQ_OK;
+}
+
+// As hq_destroy: the context's device current and its stream drained (a run's
+// kernels read the state buffers and record the events) before the members let go
+// of their memory and events (delete s).
+void hq_search_destroy(hq_search* s) {
+    if (!s) return;
+    if (!s->driver && s->ctx) {
+        (void)hipSetDevice(s->ctx->device);
+        (void)hipStreamSynchronize(s->ctx->stream);
+    }
+    if (s->gexec) (void)hipGraphExecDestroy(s->gexec);
+    delete s->pol;
+    delete s->driver;
+    delete s;
+}
+
+}  // extern "C"

@@ -1011,6 +1011,16 @@ def test_device_search_with_single_rank_comm(gpu, filt, split):
         hq._lib.check(lib.hq_search_run(handle, 30, C.byref(ran)), m.ctx)
         assert ran.value == 30
         lib.hq_profile_reset(m.ctx)
+        # the stage table: exactly these twelve names, every one at zero after a reset
+        for stage in ("grid", "assign", "cost", "finalize", "sa_step", "comm", "centroid", "lloyd", "hist",
+                      "errsum", "reseed", "dither"):
+            ms, n = C.c_double(-1.0), C.c_int64(-1)
+            assert lib.hq_profile_get(m.ctx, stage.encode(), C.byref(ms), C.byref(n)) == hq._lib.HQ_OK, stage
+            assert ms.value == 0.0 and n.value == 0, (stage, ms.value, n.value)
+        for stage in ("", "Assign", "sa", "sa_step ", "prof_assign", "kernel", "events"):
+            ms, n = C.c_double(-1.0), C.c_int64(-1)
+            assert lib.hq_profile_get(m.ctx, stage.encode(), C.byref(ms), C.byref(n)) == hq._lib.HQ_ERR_ARG, stage
+            assert ms.value == -1.0 and n.value == -1
         lib.hq_profile_enable(m.ctx, 1)
         hq._lib.check(lib.hq_search_run(handle, 10, C.byref(ran)), m.ctx)
         lib.hq_profile_enable(m.ctx, 0)
