@@ -497,8 +497,8 @@ int eval_partial_into_hout(hq_ctx* c, const float* palettes, int P, int K) {
     }
     c->pal_generic = false;  // device-resident searches generate clamped palettes
     c->nch_cur = 1;
-    c->sums_ok = rc == HQ_OK;
-    c->err_ok = c->sums_ok && c->pixel_err;
+    c->sums_ok = c->idx_ok = rc == HQ_OK;
+    c->err_ok = c->pixerr_ok = c->sums_ok && c->pixel_err;
     return rc;
 }
 
@@ -522,8 +522,13 @@ int check_last_population(hq_ctx* c, int P, int K) {
     return HQ_OK;
 }
 
-// Palette p of the last population is on this device: *local, its place among them.
+// hq_get_indices[32], hq_get_pixel_errors: the index images on the device are those of an
+// evaluation on the image and filters in force (idx_ok: hq_runtime.h), and palette p of
+// that population is on this device: *local, its place among them.
 int check_local_palette(hq_ctx* c, int p, int* local) {
+    if (!c->have_image || !c->idx_ok)
+        return fail(c, HQ_ERR_STATE, "no population evaluated on the current image and filters (the image or the "
+                                     "filters were set, or an evaluation failed, since the last one)");
     if (p < 0 || p >= c->last_P) return fail(c, HQ_ERR_ARG, "palette %d not in last population", p);
     if (p < c->slice_lo || p >= c->slice_lo + c->slice_n)
         return fail(c, HQ_ERR_ARG, "palette %d was evaluated on another rank (palette split)", p);
@@ -848,6 +853,7 @@ int hq_dither_population(hq_ctx* c, const float* palettes, int P, int K, float s
     std::memcpy(c->h_pal.p, palettes, sizeof(float) * 4 * (size_t)P * K);
     hipStream_t s = c->stream;
     c->sums_ok = c->err_ok = false;  // (a k-means or repair move from a dithered assignment is neither)
+    c->idx_ok = c->pixerr_ok = false;  // (until the dithered pass below has come back)
     HIP_TRY(c, hipMemcpyAsync(c->d_pal_in.p, c->h_pal.p, sizeof(float4) * (size_t)P * K, hipMemcpyHostToDevice, s));
     HIP_TRY(c, launch_prep_palette(prep_args(c, K), P, s));
     ProfRec pr = prof_begin(c);
@@ -855,6 +861,8 @@ int hq_dither_population(hq_ctx* c, const float* palettes, int P, int K, float s
     HIP_TRY(c, hipMemcpyAsync(c->h_out.p, c->d_out.p, sizeof(double) * (size_t)P * (1 + K), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     prof_accumulate(c, pr);
+    c->idx_ok = true;  // the getters answer for the dithered rendering
+    c->pixerr_ok = c->pixel_err != 0;
     costs_from_hout(c, P, K, delta, costs, used);
     return HQ_OK;
 }
@@ -901,8 +909,9 @@ int hq_get_pixel_errors(hq_ctx* c, int p, float* err) {
     if (!c->pixel_err) return fail(c, HQ_ERR_STATE, "option pixel_err is off");
     int rc = check_local_palette(c, p, &p);
     if (rc) return rc;
-    if (c->d_pixerr.bytes < sizeof(float) * (size_t)c->last_P * (size_t)c->g.W * (c->g.r1 - c->g.r0))
-        return fail(c, HQ_ERR_STATE, "pixel_err was set after the last evaluation");
+    if (!c->pixerr_ok)
+        return fail(c, HQ_ERR_STATE, "no error image of the last evaluation: pixel_err was set after it, or a search "
+                                     "has run since");
     if ((rc = bind(c))) return rc;
     const int64_t n_own = (int64_t)c->g.W * (c->g.r1 - c->g.r0);
     HIP_TRY(c, hipMemcpy(err, c->d_pixerr.as<float>() + (int64_t)p * n_own, sizeof(float) * n_own,

@@ -242,6 +242,12 @@ struct hq_ctx {
     // hq_cluster_errors: the error image on the device is that of the last evaluation (option
     // "pixel_err" was on when hq_eval_population[_partial] enqueued it; read with sums_ok)
     bool err_ok = false;
+    // hq_get_indices[32], hq_get_pixel_errors: the index images (idx_ok) and the error image
+    // (pixerr_ok: "pixel_err" was on when it was enqueued) on the device are those of the last
+    // evaluation -- plain, partial, dithered or a search's -- of last_P x K_cur on the current
+    // image and filters.  hq_set_image*, hq_set_filters and a failed evaluation unset both; a
+    // search unsets pixerr_ok (its side passes store error images of candidates it then moves).
+    bool idx_ok = false, pixerr_ok = false;
     hq::DevBuf d_errstat, d_worst; // [P][K][4] u64 statistics, then the flag; [P][K] float4 worst pixels
     hq::DevBuf d_dcarry;           // hq_dither_population: [P][3][W] errors of a strip's last row
 

@@ -163,6 +163,9 @@ int compute_labref_device(hq_ctx* c) {
 int set_image_common(hq_ctx* c, const std::vector<float>& R, const std::vector<float>& G,
                      const std::vector<float>& B, const float* lab4_full, const float* illum) {
     const Geom& g = c->g;
+    // c->g is the new image's already: nothing evaluated on the old one may be read at it
+    c->have_image = false;  // (until every plane below is in place)
+    c->sums_ok = c->err_ok = c->idx_ok = c->pixerr_ok = false;
     const size_t plane = sizeof(float) * (size_t)round_up(g.n_ext, 4);
     HIP_TRY(c, c->d_R.ensure(plane));
     HIP_TRY(c, c->d_G.ensure(plane));
@@ -188,7 +191,6 @@ int set_image_common(hq_ctx* c, const std::vector<float>& R, const std::vector<f
         if (!c->img_u8) c->d_rgbx.release();  // (no packed copy: its memory back now)
     }
     if (illum) std::memcpy(c->illum, illum, sizeof c->illum);
-    c->sums_ok = false;  // (the index images of the last evaluation belong to the old image)
     c->planar_ok = -1;
     const int own = g.r1 - g.r0;
     const size_t lplane = sizeof(float) * (size_t)g.lab_pitch * std::max(own, 1);
@@ -312,6 +314,10 @@ int hq_set_filters(hq_ctx* c, int taps, const float* k1, const float* k2, const 
         return fail(c, HQ_ERR_ARG, "bad filters (taps=%d)", taps);
     int rc = bind(c);
     if (rc) return rc;
+    // the halo depends on the filters: the image, and what was evaluated on it, go with them
+    // (before the first early return below, which leaves the new half-width behind)
+    c->have_image = false;
+    c->sums_ok = c->err_ok = c->idx_ok = c->pixerr_ok = false;
     c->taps = taps;
     c->half = (taps * 4) / 8;  // IM:408 filters4[0].length/8
     if (2 * c->half + 1 != taps)
@@ -365,8 +371,6 @@ int hq_set_filters(hq_ctx* c, int taps, const float* k1, const float* k2, const 
         build_fast_taps(HB, c->half, k1, k2, k3, absk3, tb.data());
         HIP_TRY(c, c->d_taps.upload(tb.data(), tb.size()));
     }
-    c->have_image = false;  // halo depends on the filters
-    c->sums_ok = false;
     return HQ_OK;
 }
 

@@ -150,6 +150,17 @@ int enqueue_repair(hq_search* s, ProfRec& pr) {
     return HQ_OK;
 }
 
+// What hq_get_indices[32] and hq_get_pixel_errors may read after hq_search_create* or
+// hq_search_run (hq.h): the index images of the last candidates evaluated -- a
+// device-resident search enqueues its passes itself, a host-driven one goes through
+// hq_eval_population, which keeps the flag -- and no error image: a repair iteration's
+// side pass stores that of candidates it then moves.
+void search_evaluated(hq_ctx* c, bool device, int rc, int evaluations) {
+    if (rc) c->idx_ok = false;
+    else if (device && evaluations > 0) c->idx_ok = true;
+    c->pixerr_ok = false;
+}
+
 // A search's evaluation pass: folding (search_folds) or full.
 Pass search_pass(const hq_search* s) { return Pass{s->fold ? Pass::Fold : Pass::Full}; }
 
@@ -405,6 +416,7 @@ int hq_search_create_from(hq_ctx* c, const hq_swasa_params* params, int K, uint6
         rc = s->driver->start(population);
     }
     c->sums_ok = false;  // (the search's own evaluations replace the index images)
+    search_evaluated(c, !s->driver, rc, 1);
     if (rc) {
         hq_search_destroy(s);
         return rc;
@@ -431,13 +443,18 @@ int hq_search_run(hq_search* s, int iterations, int* ran) {
             return rc;
         }
     }
+    int done = 0;  // (the caller's `ran` is written as before; without one, a count of our own)
+    int* const count = ran ? ran : &done;
     if (!s->driver) {
         rc = bind(s->ctx);
-        if (!rc) rc = device_search_run(s, iterations, ran);
+        if (!rc) rc = device_search_run(s, iterations, count);
     } else {
-        rc = s->driver->run(iterations, ran, nullptr);
+        rc = s->driver->run(iterations, count, nullptr);
     }
-    if (s->ctx) s->ctx->sums_ok = false;  // (hq_cluster_sums: a search run has evaluated since)
+    if (s->ctx) {
+        s->ctx->sums_ok = false;  // (hq_cluster_sums: a search run has evaluated since)
+        search_evaluated(s->ctx, !s->driver, rc, rc ? 0 : *count);
+    }
     return rc;
 }
 

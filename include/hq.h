@@ -140,18 +140,35 @@ int hq_eval_population(hq_ctx *ctx, const float *palettes, int P, int K, float d
  * by an owned-or-halo pixel else 0.0. */
 int hq_eval_population_partial(hq_ctx *ctx, const float *palettes, int P, int K,
                                double *partial);
-/* Per-pixel palette indices (u8, K <= 256) of the last evaluated population's
+/* The read-back rule of hq_get_indices, hq_get_indices32 and hq_get_pixel_errors:
+ * they answer for the last evaluation on the image and filters in force -- the
+ * last successful hq_eval_population[_partial], hq_dither_population (the
+ * dithered rendering), or evaluation inside hq_refine_population,
+ * hq_repair_population, hq_search_create[_from] and hq_search_run (the last
+ * candidates the search evaluated; a run of 0 iterations changes nothing).
+ * hq_set_image*, hq_set_filters and an evaluation that fails after it has
+ * passed its argument checks end that: until the next successful evaluation the
+ * three return HQ_ERR_STATE with a message and write nothing.
+ * hq_get_pixel_errors needs in addition that the evaluation stored its error
+ * image (option "pixel_err" 1 when it was enqueued) and that the option is
+ * still 1; after hq_search_create[_from] or hq_search_run it is HQ_ERR_STATE
+ * until the next evaluation call (a repair iteration's side pass stores the
+ * error image of candidates that the search then moves).
+ *
+ * Per-pixel palette indices (u8, K <= 256) of the last evaluated population's
  * palette p over the owned rows (w*(row_end-row_begin) bytes).  HQ_ERR_STATE
- * when that population had K > 256 colours. */
+ * when that population had K > 256 colours, and by the rule above. */
 int hq_get_indices(hq_ctx *ctx, int p, uint8_t *idx);
 /* The same for any K (1 .. 2^24, HQ:192): 32-bit indices, w*(row_end-row_begin)
- * of them -- the reference's int index of CL:172-193. */
+ * of them -- the reference's int index of CL:172-193.  HQ_ERR_STATE by the
+ * rule above. */
 int hq_get_indices32(hq_ctx *ctx, int p, uint32_t *idx);
 /* Test surface: the per-pixel dE of palette p of the last evaluation over the
  * owned rows (w*(row_end-row_begin) floats) -- the error image the reference
  * reads back per member (IM:663-667, CL:201-209).  Needs option "pixel_err" = 1
  * before that evaluation (the cost kernels then also store it); HQ_ERR_STATE
- * otherwise. */
+ * otherwise, and by the read-back rule above: an error image that an earlier
+ * evaluation stored is never returned for a later one that stored none. */
 int hq_get_pixel_errors(hq_ctx *ctx, int p, float *err);
 
 /* ---- k-means palette refinement: libhq's additions, no reference counterpart ----

@@ -1,0 +1,80 @@
+"""The walk and the class table of tests/reuse_walk.py, on the CPU: the walk uses every
+ordered pair of classes once, and each class meets the precondition of the path it is
+named after, from the table and the oracle alone."""
+
+import numpy as np
+import pytest
+
+import reuse_walk as rw
+from test_fast_path import bucket
+
+ASSIGN_CHUNK = 256 * 6  # hq_eval.hip, assign_blocks: pixels per assign workgroup (HQ_ASSIGN_MINPX 6)
+
+
+def chunk_count(K):  # hq_internal.h
+    n = 1
+    while 256 * n < K:
+        n <<= 1
+    return n
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 5, 12, 13])
+def test_walk_uses_every_ordered_pair_once(n):
+    walk = rw.euler_walk(n)
+    assert len(walk) == n * (n - 1) + 1
+    assert walk[0] == walk[-1] == 0
+    pairs = list(zip(walk[:-1], walk[1:]))
+    assert all(i != j for i, j in pairs)
+    assert sorted(pairs) == [(i, j) for i in range(n) for j in range(n) if i != j]
+    assert walk == rw.euler_walk(n)  # deterministic
+
+
+def test_twelve_classes_make_133_steps():
+    assert len(rw.CLASSES) == 12 and len(set(rw.NAMES)) == 12
+    assert len(rw.euler_walk(len(rw.CLASSES))) == 133
+
+
+@pytest.mark.parametrize("name", rw.NAMES)
+def test_class_meets_its_path(name):
+    c = rw.by_name(name)
+    f, (kind, w, h, _, _), (r0, r1) = rw.filters(c), c["image"], rw.rows(c)
+    half, P, K, opts = f.half, c["P"], c["K"], c["opts"]
+    assert set(opts) == set(rw.OPTION_DEFAULTS)  # every option has an explicit value
+    assert half == c["filters"][2] and w >= half and h >= half
+    rgb = rw.image(c)[:, :3]
+    k = np.rint(rgb.astype(np.float64) * 255).astype(np.float32)
+    on_lattice = bool(np.all(k / np.float32(255) == rgb))  # fp32 k/255, as the device packs it
+    assert on_lattice == (kind == "lattice")
+    assert rgb.min() >= 0.0 and rgb.max() <= 1.0
+    pals = rw.palettes(c).reshape(P, K, 4)
+    fits = bool(np.all((pals[..., :3] >= rw.FAST_RANGE[0]) & (pals[..., :3] <= rw.FAST_RANGE[1])))
+    assert fits == (not c["out_of_range"]) and np.all(pals[..., 3] == 0)
+    # several assign workgroups, more than one cost tile (16 x 128), a halo where there is a shard
+    e0, e1 = max(0, r0 - half), min(h, r1 + half)
+    assert w * (e1 - e0) > ASSIGN_CHUNK and (r1 - r0 > 16 or w > 128)
+    nch = chunk_count(K) if 256 < K <= 16384 and opts["chunked"] and opts["grid"] > 0 and fits else 1
+    want = {
+        "u8-fast": bucket(half) == 10 and nch == 1 and opts["cost_variant"] == 0 and opts["pixel_err"] == 1,
+        "planar-generic": opts["cost_variant"] == 1 and K <= 256,
+        "bucket-19": bucket(half) == 19 and half == 19 and K < 8,
+        "long-filter": bucket(half) == 0 and 24 < half <= 64,
+        "chunk-grids": nch == 2 and opts["lists16"] == 0,
+        "lists16": 4 <= nch <= 32 and opts["lists16"] == 1 and opts["grid"] > 0,
+        "wide-u32": K > 16384 and nch == 1,
+        "grid-0": opts["grid"] == 0 and K <= 256,
+        "shard": c["op"] == "partial" and r0 - half > 0 and r1 + half < h and r0 % 16 != 0,
+        "dither": c["op"] == "dither" and K <= 256 and opts["dither_rows"] == 64 and c["strength"] == 1.0,
+        "out-of-range": not fits and K <= 256,
+        "slice": c["op"] == "partial" and opts["slice_ranks"] == 2 and P % 2 == 0 and opts["slice_rank"] == 1,
+    }[name]
+    assert want, name
+    if name != "slice":
+        assert opts["slice_ranks"] == 1 and list(rw.local_palettes(c)) == list(range(P))
+    else:
+        assert list(rw.local_palettes(c)) == [2, 3]
+    ref = rw.oracle_outputs(c)
+    for p in rw.local_palettes(c):
+        assert np.isfinite(ref["sum"][p]) and ref["sum"][p] > 0
+        assert ref["idx"][p].shape == (w * (r1 - r0),) and ref["idx"][p].max() < K
+        if c["op"] != "partial":
+            assert np.isfinite(ref["cost"][p])
