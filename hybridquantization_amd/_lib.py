@@ -75,6 +75,10 @@ SIGNATURES = {
     "hq_repair_population": (C.c_int, [_ctx, _f, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int,
                                        _d, _i32, _d]),
     "hq_dither_population": (C.c_int, [_ctx, _f, C.c_int, C.c_int, C.c_float, C.c_float, _d, _i32]),
+    "hq_bayer_map": (C.c_int, [C.c_int, _f]),
+    "hq_set_dither_map": (C.c_int, [_ctx, _f, C.c_int, C.c_int]),
+    "hq_ordered_population": (C.c_int, [_ctx, _f, C.c_int, C.c_int, _f, C.c_float, _d, _i32]),
+    "hq_ordered_population_partial": (C.c_int, [_ctx, _f, C.c_int, C.c_int, _f, _d]),
     "hq_color_histogram": (C.c_int, [_ctx, C.c_int, _i64, _i64]),
     "hq_median_cut": (C.c_int, [_i64, C.c_int, C.c_int64, C.c_int, _f, C.POINTER(C.c_int)]),
     "hq_quantize": (C.c_int, [_ctx, _f, C.c_int64, _f, C.c_int, _f, _i32]),
@@ -92,6 +96,7 @@ SIGNATURES = {
     "hq_search_destroy": (None, [C.c_void_p]),
     "hq_search_set_lloyd": (C.c_int, [C.c_void_p, C.c_int]),
     "hq_search_set_repair": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "hq_search_set_ordered": (C.c_int, [C.c_void_p, _f]),
     "hq_swasa_search_host": (C.c_int, [C.POINTER(hq_swasa_params), C.c_int, C.c_uint64,
                                        C.c_int, EVAL_FN, C.c_void_p, _f, _d, _d]),
     "hq_swasa_search_host_lloyd": (C.c_int, [C.POINTER(hq_swasa_params), C.c_int, C.c_uint64,

@@ -269,6 +269,14 @@ __device__ __forceinline__ int64_t quad_cell(float r, float g, float b, int G2) 
            min((int)(b * (float)G2), G2 - 1);
 }
 
+// Ordered dithering, one channel: the value the argmin reads (hq.h), three fp32
+// operations rounded to nearest, none contracted.
+__device__ __forceinline__ float ordered_value(float pix, float amp, float m) {
+#pragma clang fp contract(off)
+    const float t = amp * m;
+    return fminf(fmaxf(pix + t, 0.0f), 1.0f);
+}
+
 // NG: the palettes of the group a pixel pass serves (4, or P mod 4 for the
 // last group, launched on its own): every palette slot is live, so the
 // resolve step has no data-dependent exits.  A group below 4 loads only its NG
@@ -309,12 +317,29 @@ __device__ __forceinline__ uint32_t cell_u8(uint32_t v, int lg) {
 // 3 last), each comparing its group's winner with the best so far in the
 // distance scratch; PASS 0 is a single pass (nch <= 4) and the only one that
 // records used bits (nch > 4: used_idx16_kernel from the final indices).
-template <int NG, bool U8, int CMB = 1, int PASS = 0>
+//
+// ORD (ordered dithering, hq.h: hq_ordered_population; CMB 1, PASS 0): the argmin
+// sees the pixel plus amp[c] times the threshold map's value at the pixel's
+// position in the full image, clamped to [0, 1] (ordered_value).
+//  - The map value comes through L1/L2 as one more unconditional load issued
+//    with the pixel's RGB: its address depends on the position alone, so it adds
+//    no dependent round trip, a wave's 64 consecutive x read one or two lines of
+//    a map row, and a 64 x 64 map (16 KiB) fits L1 beside nothing else that is
+//    reused.  In LDS it would double the workgroup's 17 KiB (NG = 4) and every
+//    workgroup would fill 16 KiB for the ~1,500 pixels it resolves.
+//  - (x, y) of the grid-stride position are kept incrementally: the loads go out
+//    in ascending pixel order, each advancing (x, y) by the stride's (dx, dy) with
+//    one carry (x < W, dx < W: x + dx < 2^31).  Integer adds only, exact for
+//    every position; the one division per thread is that of its first position.
+//  - The cell comes from quad_cell on the perturbed floats (cell_u8 holds for
+//    the unperturbed bytes only), and the value is inside the cube by the clamp.
+template <int NG, bool U8, int CMB = 1, int PASS = 0, bool ORD = false>
 #ifndef HQ_ASSIGN_WAVES
 #define HQ_ASSIGN_WAVES 1
 #endif
 __global__ __launch_bounds__(256, HQ_ASSIGN_WAVES) void assign_pipe_kernel(AssignArgs a, int grp0, int ngroups) {
     static_assert(NG % CMB == 0 && (CMB == 4 || PASS == 0), "combine sets inside the group; passes: 4 chunks");
+    static_assert(!ORD || (CMB == 1 && PASS == 0), "ordered dithering: plain 8-bit index images");
     // [NG][kMaxK]: a fixed palette stride, so each palette's base folds into the
     // ds_read_b128 offset field and a candidate's address is its byte << 4
     __shared__ __attribute__((aligned(16))) float4 s_pal[NG * kMaxK];
@@ -359,9 +384,27 @@ __global__ __launch_bounds__(256, HQ_ASSIGN_WAVES) void assign_pipe_kernel(Assig
     // the group's palette (loaded with the pixel's RGB)
     const float* dist_in = PASS >= 2 ? a.dist + (int64_t)((4 * grp) >> a.lg_nch) * a.idx_pitch : nullptr;
     float pdl[3], pdv[3];  // [NB]: loads in flight, values of pixels being resolved
-    auto load_rgb = [&](uint32_t q, RawPx<U8>& x, float& pd) {
+    // ORD: the map value of each pixel in flight, loaded with its RGB, and the
+    // full-image position (ox, oy) of the next pixel to load (ascending order)
+    float mpl[3];
+    uint32_t ox = 0, oy = 0;
+    if constexpr (ORD) {
+        oy = qbase / a.W;
+        ox = qbase - oy * a.W;
+        oy += a.y0;
+    }
+    auto load_rgb = [&](uint32_t q, RawPx<U8>& x, float& pd, float& mp) {
         const uint32_t qc = min(q, qlast);
         if constexpr (PASS >= 2) pd = at(dist_in, qc);
+        if constexpr (ORD) {
+            // (unconditional, in bounds by the masks whatever q: past the image too)
+            mp = at(a.map, ((oy & a.mh_mask) << a.lg_mw) | (ox & a.mw_mask));
+            ox += a.dx;
+            oy += a.dy;
+            const bool carry = ox >= a.W;
+            ox -= carry ? a.W : 0u;
+            oy += carry ? 1u : 0u;
+        }
         if constexpr (U8) {
             x.v = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(a.rgbx) + (qc << 2));
         } else {
@@ -370,7 +413,7 @@ __global__ __launch_bounds__(256, HQ_ASSIGN_WAVES) void assign_pipe_kernel(Assig
             x.b = at(a.B, qc);
         }
     };
-    auto unpack = [&](const RawPx<U8>& x, float& r, float& g, float& b) {
+    auto unpack = [&](const RawPx<U8>& x, float mp, float& r, float& g, float& b) {
         if constexpr (U8) {
             r = u8_unit(x.v, 0);
             g = u8_unit(x.v, 1);
@@ -380,17 +423,23 @@ __global__ __launch_bounds__(256, HQ_ASSIGN_WAVES) void assign_pipe_kernel(Assig
             g = x.g;
             b = x.b;
         }
+        if constexpr (ORD) {
+            r = ordered_value(r, a.amp[0], mp);
+            g = ordered_value(g, a.amp[1], mp);
+            b = ordered_value(b, a.amp[2], mp);
+        }
     };
     auto lookup = [&](uint32_t q, float r, float g, float b, bool& inside, L2E (&e)[NG], uint32_t raw) {
         // (q past the image: the clamped last pixel, resolved but not stored)
-        inside = U8 ? true : r >= 0.f && r <= 1.f && g >= 0.f && g <= 1.f && b >= 0.f && b <= 1.f;
+        // (ORD: clamped into the cube)
+        inside = U8 || ORD ? true : r >= 0.f && r <= 1.f && g >= 0.f && g <= 1.f && b >= 0.f && b <= 1.f;
 #ifdef HQ_ABL_HASHLOOKUP  // timing ablation (wrong results): a random line, independent of the RGB
         const uint8_t* lb = lines + ((q * 2654435761u) >> 17) * (uint32_t)kL2Line;
 #elif defined(HQ_ABL_COHERENT)  // timing ablation (wrong results): runs of 256 consecutive pixels share a cell
         const uint8_t* lb = lines + (((q >> 8) * 40503u) & (uint32_t)(G2 * G2 * G2 - 1)) * (uint32_t)kL2Line;
 #else
         // (packed pixels: the cell straight from the bytes, cell_u8)
-        const uint8_t* lb = lines + (U8 ? cell_u8(raw, lg_g2) : inside ? (uint32_t)quad_cell(r, g, b, G2) : 0u) *
+        const uint8_t* lb = lines + (U8 && !ORD ? cell_u8(raw, lg_g2) : inside ? (uint32_t)quad_cell(r, g, b, G2) : 0u) *
                                         (uint32_t)kL2Line;
 #endif
         // selected by the `listed` flag at use.  8-B entries: two palettes per
@@ -442,17 +491,18 @@ __global__ __launch_bounds__(256, HQ_ASSIGN_WAVES) void assign_pipe_kernel(Assig
 #pragma unroll
     for (int j = 0; j < NB - 1; ++j) {
         RawPx<U8> x0;
-        load_rgb(qpos(j), x0, pdv[j]);
-        unpack(x0, xr[j], xg[j], xb[j]);
+        float m0 = 0.f;
+        load_rgb(qpos(j), x0, pdv[j], m0);
+        unpack(x0, m0, xr[j], xg[j], xb[j]);
         qq[j] = qpos(j);
         lookup(qq[j], xr[j], xg[j], xb[j], in_[j], E[j], raw_of(x0));
     }
 #if HQ_ASSIGN_DEPTH == 2
-    load_rgb(qpos(2), rb[2], pdl[2]);
-    load_rgb(qpos(3), rb[0], pdl[0]);
+    load_rgb(qpos(2), rb[2], pdl[2], mpl[2]);
+    load_rgb(qpos(3), rb[0], pdl[0], mpl[0]);
 #else
-    load_rgb(qpos(1), rb[1], pdl[1]);
-    load_rgb(qpos(2), rb[0], pdl[0]);
+    load_rgb(qpos(1), rb[1], pdl[1], mpl[1]);
+    load_rgb(qpos(2), rb[0], pdl[0], mpl[0]);
 #endif
     // The palette table is filled while the first pixels' loads are in flight
     // (the fill used to come first: one more memory round trip per workgroup).
@@ -540,10 +590,10 @@ __global__ __launch_bounds__(256, HQ_ASSIGN_WAVES) void assign_pipe_kernel(Assig
     auto step = [&](int i, int h) {  // h == i % 3, a compile-time constant at each call
         const int ia = (h + 2) % 3, fi = (h + 1) % 3;  // (not `a`: the kernel's AssignArgs)
         qq[ia] = qpos(i + 2);
-        unpack(rb[ia], xr[ia], xg[ia], xb[ia]);  // RGB(i+2): landed
+        unpack(rb[ia], mpl[ia], xr[ia], xg[ia], xb[ia]);  // RGB(i+2): landed
         pdv[ia] = pdl[ia];
         lookup(qq[ia], xr[ia], xg[ia], xb[ia], in_[ia], E[ia], raw_of(rb[ia]));
-        load_rgb(qpos(i + 4), rb[fi], pdl[fi]);  // rb[fi] held RGB(i+1), unpacked a step ago
+        load_rgb(qpos(i + 4), rb[fi], pdl[fi], mpl[fi]);  // rb[fi] held RGB(i+1), unpacked a step ago
         resolve(h);
     };
     int i = 0;
@@ -558,10 +608,10 @@ __global__ __launch_bounds__(256, HQ_ASSIGN_WAVES) void assign_pipe_kernel(Assig
     auto step = [&](int i, int h) {  // h == i & 1, a compile-time constant at each call
         const int n = h ^ 1;
         qq[n] = qpos(i + 1);
-        unpack(rb[n], xr[n], xg[n], xb[n]);  // RGB(i+1): landed, needed now anyway
+        unpack(rb[n], mpl[n], xr[n], xg[n], xb[n]);  // RGB(i+1): landed, needed now anyway
         pdv[n] = pdl[n];
         lookup(qq[n], xr[n], xg[n], xb[n], in_[n], E[n], raw_of(rb[n]));
-        load_rgb(qpos(i + 3), rb[n], pdl[n]);
+        load_rgb(qpos(i + 3), rb[n], pdl[n], mpl[n]);
         resolve(h);
     };
     int i = 0;
@@ -702,6 +752,43 @@ hipError_t launch_assign(const AssignArgs& a, int P, hipStream_t s) {
     return hipGetLastError();
 }
 
+// Ordered dithering (a.map set; K <= 256, so no chunks): the ORD instances, the
+// full groups in one launch and the rest group in a second as above.
+template <bool U8>
+void launch_assign_ordered_t(const AssignArgs& a, int P, hipStream_t s) {
+    const hipEvent_t ev0 = t_ev_start, ev1 = t_ev_stop;
+    const int full = P / 4, rest = P % 4;
+#define HQ_ASG(NG, NB, G0, NGR) \
+    HQ_LAUNCH((assign_pipe_kernel<NG, U8, 1, 0, true>), dim3((unsigned)(NB)), dim3(256), 0, s, a, G0, NGR)
+    if (full > 0) {
+        if (rest) t_ev_stop = nullptr;
+        HQ_ASG(4, a.nblocks * full, 0, full);
+        t_ev_stop = ev1;
+        if (rest) t_ev_start = nullptr;
+    }
+    switch (rest) {
+    case 1: HQ_ASG(1, a.nblocks, full, 1); break;
+    case 2: HQ_ASG(2, a.nblocks, full, 1); break;
+    case 3: HQ_ASG(3, a.nblocks, full, 1); break;
+    default: break;
+    }
+#undef HQ_ASG
+    t_ev_start = ev0;
+}
+
+hipError_t launch_assign_ordered(const AssignArgs& a0, int P, hipStream_t s) {
+    if (!a0.map || a0.nch != 1 || a0.W < 1 || a0.nblocks < 1 || a0.mw_mask >= (uint32_t)kMaxMapSide ||
+        a0.mh_mask >= (uint32_t)kMaxMapSide || (a0.mw_mask + 1u) != (1u << a0.lg_mw))
+        return hipErrorInvalidValue;
+    AssignArgs a = a0;
+    a.gstep = 1;
+    const uint32_t cstride = (uint32_t)a.nblocks * 256u;  // the grid stride in pixels
+    a.dy = cstride / a.W;
+    a.dx = cstride - a.dy * a.W;
+    with_bool(a.rgbx, [&](auto U8) { launch_assign_ordered_t<U8.value>(a, P, s); });
+    return hipGetLastError();
+}
+
 // Resident workgroups per CU of assign_pipe_kernel<NG> (the auto size of one
 // grid-stride round; the packed and planar forms and, for NG = 4, the chunk
 // combining forms take the larger register count); 0 if the query fails.
@@ -715,6 +802,16 @@ int assign_residency(int NG) {
     case 2: return std::min(q(assign_pipe_kernel<2, false>), q(assign_pipe_kernel<2, true>));
     case 3: return std::min(q(assign_pipe_kernel<3, false>), q(assign_pipe_kernel<3, true>));
     default: return std::min(q(assign_pipe_kernel<4, false>), q(assign_pipe_kernel<4, true>));
+    }
+}
+
+// The same for the ordered-dithering forms: their own occupancy sizes their launch.
+int assign_residency_ordered(int NG) {
+    switch (NG) {
+    case 1: return std::min(q(assign_pipe_kernel<1, false, 1, 0, true>), q(assign_pipe_kernel<1, true, 1, 0, true>));
+    case 2: return std::min(q(assign_pipe_kernel<2, false, 1, 0, true>), q(assign_pipe_kernel<2, true, 1, 0, true>));
+    case 3: return std::min(q(assign_pipe_kernel<3, false, 1, 0, true>), q(assign_pipe_kernel<3, true, 1, 0, true>));
+    default: return std::min(q(assign_pipe_kernel<4, false, 1, 0, true>), q(assign_pipe_kernel<4, true, 1, 0, true>));
     }
 }
 

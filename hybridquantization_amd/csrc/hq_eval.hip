@@ -1,6 +1,6 @@
 // hq_eval.hip -- libhq host runtime, evaluation: the population buffers, the pass
 // over a prepared population (enqueue_core, enqueue_wide, the generic cost), the
-// evaluation, dither, index, sums, error and histogram entry points, and the two
+// evaluation, dither, ordered-dither, index, sums, error and histogram entry points, and the two
 // improvement loops built on them (refine, repair).  Shared declarations:
 // hq_runtime.h.
 #include <cmath>
@@ -24,7 +24,7 @@ namespace {
 #ifndef HQ_ASSIGN_MINPX
 #define HQ_ASSIGN_MINPX 6
 #endif
-int assign_blocks(const hq_ctx* c, int P) {
+int assign_blocks(const hq_ctx* c, int P, bool ordered = false) {
     // at least HQ_ASSIGN_MINPX pixels per thread: a launch's fixed part (table
     // fill, pipeline start, the used-bit flush) is paid per workgroup (C2,
     // 1024^2 P = 1: 2048 workgroups of 2 pixels per thread took 14 us, 1045 of 4
@@ -32,7 +32,7 @@ int assign_blocks(const hq_ctx* c, int P) {
     // workgroups, slowed from 43 to 46 us at 8)
     const int64_t chunk = 256 * HQ_ASSIGN_MINPX;
     const int ng = std::min(P, 4);
-    const int res = c->nch_cur > 1 ? c->assign_res_chunked : c->assign_res[ng];
+    const int res = ordered ? c->assign_res_ord[ng] : c->nch_cur > 1 ? c->assign_res_chunked : c->assign_res[ng];
     const int per_cu = c->assign_blocks_per_cu > 0 ? c->assign_blocks_per_cu : res > 0 ? res : 4;
     const int64_t nblocks = (int64_t)c->num_cu * per_cu;
     return (int)std::max<int64_t>(1, std::min<int64_t>(nblocks, (c->g.n_ext + chunk - 1) / chunk));
@@ -345,7 +345,7 @@ int hq::enqueue_core(hq_ctx* c, int P, int K, ProfRec& pr, Pass pass) {
         HIP_TRY(c, hipMemsetAsync(ga.used_glob, 0, sizeof(uint32_t) * kUsedSlots * (size_t)used_stride(Ps), s));
         HIP_TRY(c, hipMemsetAsync(ga.acc_zero, 0, sizeof(uint64_t) * acc_words(Pl), s));
     }
-    const int nblocks = assign_blocks(c, Ps);
+    const int nblocks = assign_blocks(c, Ps, pass.ordered);
     AssignArgs aa{c->d_R.as<float>(), c->d_G.as<float>(), c->d_B.as<float>(),
                   c->img_u8 && c->img_u8_path ? c->d_rgbx.as<uint32_t>() : nullptr, ga.pal, ga.pflags,
                   c->d_lvl1.as<uint8_t>(), c->d_lvl2.as<uint8_t>(),
@@ -356,6 +356,17 @@ int hq::enqueue_core(hq_ctx* c, int P, int K, ProfRec& pr, Pass pass) {
         aa.dist = nch > 4 ? c->d_dist.as<float>() : nullptr;
         aa.nch = nch;
         while ((1 << aa.lg_nch) < nch) ++aa.lg_nch;
+    }
+    if (pass.ordered) {  // (K <= 256: no chunks, no 16-bit lists; the map is on the device: ensure_dither_map)
+        if (nch > 1 || dither || !c->d_dmap.p) return fail(c, HQ_ERR_STATE, "ordered pass: K > 256 or no map");
+        const int mw = c->dmap.empty() ? 16 : c->dmap_w, mh = c->dmap.empty() ? 16 : c->dmap_h;
+        aa.map = c->d_dmap.as<float>();
+        aa.mw_mask = (uint32_t)mw - 1u;
+        aa.mh_mask = (uint32_t)mh - 1u;
+        while ((1u << aa.lg_mw) < (uint32_t)mw) ++aa.lg_mw;
+        for (int ch = 0; ch < 3; ++ch) aa.amp[ch] = pass.amp[ch];
+        aa.W = (uint32_t)g.W;
+        aa.y0 = (uint32_t)g.e0;
     }
     if (n16) {  // one palette of K colours per workgroup (its table in LDS)
         aa.l1n = c->d_l1n.as<uint16_t>();
@@ -398,6 +409,7 @@ int hq::enqueue_core(hq_ctx* c, int P, int K, ProfRec& pr, Pass pass) {
                                                  c->dither_rows, pass.strength},
                                       Pl, s)
                : n16  ? launch_assign16(aa, Pl, s)
+               : pass.ordered ? launch_assign_ordered(aa, Ps, s)
                       : launch_assign(aa, Ps, s);
     }));
     if (pass.kind != Pass::AssignOnly) {
@@ -801,9 +813,127 @@ int planar_in_range(hq_ctx* c) {
     return HQ_OK;
 }
 
+int check_ordered_amp(hq_ctx* c, const float* amp) {
+    if (!amp) return fail(c, HQ_ERR_ARG, "null amp");
+    for (int ch = 0; ch < 3; ++ch)
+        if (!(amp[ch] >= 0.0f && amp[ch] <= 1.0f))
+            return fail(c, HQ_ERR_ARG, "amp[%d] = %g not in [0, 1]", ch, amp[ch]);
+    return HQ_OK;
+}
+
+// Ordered dithering lives in assign's 8-bit instances, every palette's index image on this
+// device, and its clamp stands for `inside` only when the pixels themselves are in [0, 1]
+// (the range flag, established once per image; the packed copy exists only for k/255 images).
+int ordered_scope(hq_ctx* c, int K) {
+    if (K > kMaxK)
+        return fail(c, HQ_ERR_UNSUPPORTED, "K=%d > %d: ordered dithering is built into the 8-bit argmin only", K, kMaxK);
+    if (c->psplit || c->slice_ranks > 1) return fail(c, HQ_ERR_UNSUPPORTED, "ordered dithering on a palette slice");
+    if (c->have_image && !c->img_u8) {
+        if (int rc = planar_in_range(c)) return rc;
+        if (!c->planar_ok)
+            return fail(c, HQ_ERR_UNSUPPORTED, "image with a pixel outside [0, 1] or not finite: no ordered dithering");
+    }
+    return HQ_OK;
+}
+
+// The context's map on the device: the buffer once, its contents when the host map changed.
+// (Nothing of this context is in flight: every entry point synchronises its stream.)
+int ensure_dither_map(hq_ctx* c) {
+    if (int rc = bind(c)) return rc;
+    HIP_TRY(c, c->d_dmap.ensure(sizeof(float) * kMaxMapSide * kMaxMapSide));
+    if (!c->dmap_dirty) return HQ_OK;
+    std::vector<float> def;
+    if (c->dmap.empty()) {
+        def.resize(16 * 16);
+        hq_bayer_map(4, def.data());
+    }
+    const std::vector<float>& m = c->dmap.empty() ? def : c->dmap;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(c->d_dmap.p, m.data(), sizeof(float) * m.size(), hipMemcpyHostToDevice));
+    c->dmap_dirty = false;
+    return HQ_OK;
+}
+
 }  // namespace hq
 
+namespace {
+
+// hq_ordered_population[_partial]: every check, then the evaluation into h_out.  On a refusal
+// nothing has been touched.
+int ordered_into_hout(hq_ctx* c, const float* palettes, int P, int K, const float* amp, const void* out,
+                      bool partial) {
+    if (!c) return HQ_ERR_ARG;
+    if (!palettes || !out || P < 1 || K < 1) return fail(c, HQ_ERR_ARG, "bad palettes / output / P=%d / K=%d", P, K);
+    int rc = check_ordered_amp(c, amp);
+    if (rc) return rc;
+    if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
+    if (K <= kMaxK && !population_in_range(palettes, P, K))
+        return fail(c, HQ_ERR_ARG, "palette with a channel that is not finite or outside [0, 1]");
+    if (!partial && !whole_image(c) && !(c->comm && c->nranks > 1))
+        return fail(c, HQ_ERR_STATE, "sharded context without a communicator: use hq_ordered_population_partial");
+    if ((rc = ordered_scope(c, K))) return rc;
+    if ((rc = ensure_dither_map(c))) return rc;
+    c->nch_cur = 1;
+    c->pal_generic = false;
+    if ((rc = ensure_population(c, P, K))) return rc;
+    std::memcpy(c->h_pal.p, palettes, sizeof(float) * 4 * (size_t)P * K);
+    hipStream_t s = c->stream;
+    c->sums_ok = c->err_ok = false;  // (a k-means or repair move from a dithered assignment is neither)
+    c->idx_ok = c->pixerr_ok = false;  // (until the pass below has come back)
+    HIP_TRY(c, hipMemcpyAsync(c->d_pal_in.p, c->h_pal.p, sizeof(float4) * (size_t)P * K, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, launch_prep_palette(prep_args(c, K), P, s));
+    ProfRec pr = prof_begin(c);
+    Pass pass{};
+    pass.ordered = true;
+    for (int ch = 0; ch < 3; ++ch) pass.amp[ch] = amp[ch];
+    if ((rc = enqueue_core(c, P, K, pr, pass))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->h_out.p, c->d_out.p, sizeof(double) * (size_t)P * (1 + K), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    prof_accumulate(c, pr);
+    c->idx_ok = true;  // the getters answer for the ordered rendering
+    c->pixerr_ok = c->pixel_err != 0;
+    return HQ_OK;
+}
+
+}  // namespace
+
 extern "C" {
+
+int hq_set_dither_map(hq_ctx* c, const float* map, int mw, int mh) {
+    if (!c) return HQ_ERR_ARG;
+    if (map) {
+        auto side = [](int v) { return v >= 1 && v <= kMaxMapSide && (v & (v - 1)) == 0; };
+        if (!side(mw) || !side(mh))
+            return fail(c, HQ_ERR_ARG, "map of %d x %d: each side a power of two in 1 .. %d", mw, mh, kMaxMapSide);
+        for (int i = 0; i < mw * mh; ++i)
+            if (!(map[i] >= -0.5f && map[i] <= 0.5f))
+                return fail(c, HQ_ERR_ARG, "map[%d] = %g not in [-0.5, 0.5]", i, map[i]);
+        c->dmap.assign(map, map + (size_t)mw * mh);
+        c->dmap_w = mw;
+        c->dmap_h = mh;
+    } else {
+        c->dmap.clear();
+        c->dmap_w = c->dmap_h = 0;
+    }
+    c->dmap_dirty = true;  // (uploaded by the next ordered evaluation or search run: ensure_dither_map)
+    return HQ_OK;
+}
+
+int hq_ordered_population(hq_ctx* c, const float* palettes, int P, int K, const float amp[3], float delta,
+                          double* costs, int32_t* used) {
+    int rc = ordered_into_hout(c, palettes, P, K, amp, costs, false);
+    if (rc) return rc;
+    costs_from_hout(c, P, K, delta, costs, used);
+    return HQ_OK;
+}
+
+int hq_ordered_population_partial(hq_ctx* c, const float* palettes, int P, int K, const float amp[3],
+                                  double* partial) {
+    int rc = ordered_into_hout(c, palettes, P, K, amp, partial, true);
+    if (rc) return rc;
+    std::memcpy(partial, c->h_out.p, sizeof(double) * (size_t)P * (1 + K));
+    return HQ_OK;
+}
 
 int hq_eval_population_partial(hq_ctx* c, const float* palettes, int P, int K, double* partial) {
     if (!partial) return fail(c, HQ_ERR_ARG, "null output");

@@ -258,6 +258,17 @@ int SearchDriver::start(const float* population) {
     return HQ_OK;
 }
 
+int SearchDriver::rerank() {
+    if (!started_ || ite_ != 0) return HQ_ERR_STATE;
+    const int n = 4 * K_;
+    int rc = eval_(colors_.data(), P_, K_, current_errors_.data());
+    if (rc) return rc;
+    const int m = argmin_first(current_errors_);
+    best_error_ = current_errors_[m];
+    best_colors_.assign(colors_.begin() + (size_t)m * n, colors_.begin() + (size_t)(m + 1) * n);
+    return HQ_OK;
+}
+
 int SearchDriver::run(int iterations, int* ran, std::vector<double>* trace) {
     if (!started_) return HQ_ERR_STATE;
     const int n = 4 * K_;
@@ -373,5 +384,25 @@ extern "C" int hq_centroids_from_sums(const int64_t* sums, int64_t den, int P, i
             c[ch] = hq::lloyd_mean(s[ch], s[3], bytes);
         c[3] = 0.0f;
     }
+    return HQ_OK;
+}
+
+// The Bayer threshold map of side n = 2^log2n (libhq's addition: ordered dithering,
+// hq.h).  Bit i of x ^ y and of y go to bits 2 (L-1-i) + 1 and 2 (L-1-i) of the rank B,
+// a permutation of 0 .. n^2 - 1; map = (B + 0.5) / n^2 - 0.5, exact in fp32 (B + 0.5 has
+// at most 13 significant bits, n^2 is a power of two).
+extern "C" int hq_bayer_map(int log2n, float* map) {
+    if (log2n < 0 || log2n > 6 || !map) return HQ_ERR_ARG;
+    const int L = log2n, n = 1 << L;
+    const float inv = 1.0f / (float)(n * n);
+    for (int y = 0; y < n; ++y)
+        for (int x = 0; x < n; ++x) {
+            unsigned B = 0;
+            for (int i = 0; i < L; ++i) {
+                B |= (unsigned)(((x ^ y) >> i) & 1) << (2 * (L - 1 - i) + 1);
+                B |= (unsigned)((y >> i) & 1) << (2 * (L - 1 - i));
+            }
+            map[y * n + x] = ((float)B + 0.5f) * inv - 0.5f;
+        }
     return HQ_OK;
 }

@@ -201,7 +201,17 @@ struct AssignArgs {
     const uint16_t* l1n = nullptr;
     const uint16_t* l2n = nullptr;
     int kpal = 0;
+    // ordered dithering (hq_ordered_population; launch_assign_ordered): the argmin sees
+    // min(max(pix_c + amp[c] * map[(y & mh_mask) << lg_mw | (x & mw_mask)], 0), 1), (x, y) the
+    // pixel's position in the FULL image.  nch = 1 only.
+    const float* map = nullptr;  // [mh][mw], mw and mh powers of two up to kMaxMapSide
+    uint32_t mw_mask = 0, mh_mask = 0, lg_mw = 0;
+    float amp[3] = {0.f, 0.f, 0.f};
+    uint32_t W = 1;         // the image's width
+    uint32_t y0 = 0;        // the full-image row of extended row 0 (Geom::e0)
+    uint32_t dx = 0, dy = 0;  // nblocks * 256 = dy W + dx, dx < W (set by the launcher)
 };
+constexpr int kMaxMapSide = 64;  // threshold maps: up to 64 x 64 (hq_set_dither_map)
 
 // dither_kernel (hq_dither.hip): the Floyd-Steinberg index images of P palettes
 // of K <= 256 colours over the whole image, in the place of grid + assign.

@@ -101,6 +101,9 @@ hipError_t launch_assign(const AssignArgs&, int P, hipStream_t);
 void launch_used_idx16(const AssignArgs&, int P, hipStream_t);
 int assign_residency(int NG);
 int assign_residency_chunked();
+// ... with ordered dithering (AssignArgs::map and what goes with it; K <= 256)
+hipError_t launch_assign_ordered(const AssignArgs&, int P, hipStream_t);
+int assign_residency_ordered(int NG);
 // hq_lists16.hip
 hipError_t launch_lists16_grid(const Lists16Args&, int P, hipStream_t);
 hipError_t launch_assign16(const AssignArgs&, int P, hipStream_t);

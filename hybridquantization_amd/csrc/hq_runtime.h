@@ -178,9 +178,15 @@ inline hipError_t timed_launch(ProfRec& pr, Pair p, F&& launch, bool start = tru
 // one: c->acc_par stays the set of the last full pass (what sa_args, the fold and
 // the finalize read), and the full pass that follows takes, and zeroes, the same
 // set again.
+// Ordered (hq_ordered_population, hq_search_set_ordered): any of the argmin kinds
+//   above with `ordered` set -- the same grid, then assign's ordered-dithering
+//   instances with the context's threshold map and `amp` (launch_assign_ordered);
+//   everything after the index images is the kind's own.  K <= 256.
 struct Pass {
     enum Kind { Full, Fold, AssignOnly, CostOnly, Dither } kind = Full;
     float strength = 0.f;  // Dither
+    bool ordered = false;
+    float amp[3] = {0.f, 0.f, 0.f};  // ordered: the amplitude per channel
     bool side() const { return kind == AssignOnly || kind == CostOnly; }
     Pair pairs() const { return kind == AssignOnly ? kPLloydGrid : kind == CostOnly ? kPRepGrid : kPGrid; }
 };
@@ -250,6 +256,13 @@ struct hq_ctx {
     bool idx_ok = false, pixerr_ok = false;
     hq::DevBuf d_errstat, d_worst; // [P][K][4] u64 statistics, then the flag; [P][K] float4 worst pixels
     hq::DevBuf d_dcarry;           // hq_dither_population: [P][3][W] errors of a strip's last row
+    // ordered dithering: the threshold map (hq_set_dither_map; empty: the default, Bayer 16 x 16)
+    // and its device copy, kMaxMapSide^2 floats made once by ensure_dither_map (its address is
+    // in captured launches) and written by it whenever the host map has changed
+    std::vector<float> dmap;
+    int dmap_w = 0, dmap_h = 0;
+    hq::DevBuf d_dmap;
+    bool dmap_dirty = true;
 
     // options
     int G2 = 32;           // argmin grid resolution (0 = exhaustive)
@@ -269,6 +282,7 @@ struct hq_ctx {
                                    // thread a grid-stride pixel sequence
     int assign_res[5] = {};   // [NG]
     int assign_res_chunked = 0;  // the chunk-combining forms (NG = 4)
+    int assign_res_ord[5] = {};  // [NG]: the ordered-dithering forms
     int psplit = 0;        // with a communicator of N ranks and the whole image on every rank: rank r
                            // evaluates palettes [r P/N, (r+1) P/N), then one all-gather (option
                            // "palette_split"; SURVEY 8e's split of large populations)
@@ -317,6 +331,8 @@ struct hq_search {
     int repair_every = 0;                // hq_search_set_repair: iteration ite % repair_every == 0 repairs (0: none)
     int repair_moves = -1;               // ... at most so many colours per palette (< 0: no limit)
     int nch = 1;                         // chunked palettes (256 < K <= 16384): chunks per palette
+    bool ordered = false;                // hq_search_set_ordered: every evaluation is the ordered one
+    float amp[3] = {0.f, 0.f, 0.f};      // ... at this amplitude per channel
     bool fold = false;                   // accept steps reduce the partials (no finalize launch)
     ncclComm_t comm = nullptr;           // the context's communicator at hq_search_create
     float t_acc = 0.f;                   // temperature / threshold of the iteration
@@ -405,5 +421,10 @@ ClusterErrArgs cluster_err_args(hq_ctx* c, int P, int K, int* idx_bytes);
 int cluster_sums(hq_ctx* c, int P, int K, int64_t* out, int64_t* den);
 int cluster_errors(hq_ctx* c, int P, int K, int64_t* err, float* worst, bool ignore_bad = false);
 int planar_in_range(hq_ctx* c);  // -> c->planar_ok
+// ordered dithering: amp (may be null: HQ_ERR_ARG) finite and in [0, 1]; what a context must be
+// for it (K <= 256, no palette slice, the image in [0, 1]); the map on the device
+int check_ordered_amp(hq_ctx* c, const float* amp);
+int ordered_scope(hq_ctx* c, int K);
+int ensure_dither_map(hq_ctx* c);
 
 }  // namespace hq

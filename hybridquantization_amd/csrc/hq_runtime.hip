@@ -286,6 +286,7 @@ int hq_create(int device, int delta_e_type, hq_ctx** out) {
     }
     for (int ng = 1; ng <= 4; ++ng) c->assign_res[ng] = assign_residency(ng);
     c->assign_res_chunked = assign_residency_chunked();
+    for (int ng = 1; ng <= 4; ++ng) c->assign_res_ord[ng] = assign_residency_ordered(ng);
     (void)c->ev.ensure(2 * kPairs);
     *out = c;
     return HQ_OK;

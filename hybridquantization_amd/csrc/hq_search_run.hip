@@ -162,7 +162,45 @@ void search_evaluated(hq_ctx* c, bool device, int rc, int evaluations) {
 }
 
 // A search's evaluation pass: folding (search_folds) or full.
-Pass search_pass(const hq_search* s) { return Pass{s->fold ? Pass::Fold : Pass::Full}; }
+// (hq_search_set_ordered: the ordered one at the search's amplitude)
+Pass search_pass(const hq_search* s) {
+    Pass p{s->fold ? Pass::Fold : Pass::Full};
+    p.ordered = s->ordered;
+    for (int ch = 0; ch < 3; ++ch) p.amp[ch] = s->amp[ch];
+    return p;
+}
+
+// A search under the ordered cost moves by annealing alone: a k-means or repair move from a
+// dithered assignment is neither (hq_ordered_population's rule for hq_cluster_sums).
+int ordered_excludes(hq_search* s, const char* what) {
+    if (s->ordered)
+        return fail(s->ctx, HQ_ERR_UNSUPPORTED, "%s in a search under the ordered cost (hq_search_set_ordered)", what);
+    return HQ_OK;
+}
+
+// hq_search_set_ordered before the first iteration: the initial population (still in
+// cand[cd], the buffer create's accept step read) through the palette prep, the search's
+// pass and the initial accept step again -- IM:490-493 under the evaluation now in force.
+// The accept step draws nothing, so the generator stays where create left it.
+int device_search_rerank(hq_search* s) {
+    hq_ctx* c = s->ctx;
+    int rc = bind(c);
+    if (rc) return rc;
+    if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
+    const NchScope scope(c, s->nch);
+    if ((rc = ensure_population(c, s->P, s->K))) return rc;
+    if (s->ordered && (rc = ensure_dither_map(c))) return rc;
+    hipStream_t st = c->stream;
+    if (s->nch > 1) return fail(c, HQ_ERR_UNSUPPORTED, "K=%d > %d", s->K, kMaxK);
+    HIP_TRY(c, hipMemcpyAsync(c->d_pal_in.p, s->cand[s->cd].p, sizeof(float4) * (size_t)s->P * s->K,
+                              hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, launch_prep_palette(prep_args(c, s->K), s->P, st));
+    ProfRec untimed;
+    if ((rc = enqueue_core(c, s->P, s->K, untimed, search_pass(s)))) return rc;
+    if ((rc = enqueue_sa_step(s, true, true, false, false, 0.f, untimed))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(st));
+    return HQ_OK;
+}
 
 // population: hq_search_create_from's ([P][4K], checked), or null for the random one.
 int device_search_create(hq_ctx* c, const hq_swasa_params* params, int K, uint64_t seed, const float* population,
@@ -249,6 +287,7 @@ int device_search_run(hq_search* s, int iterations, int* ran) {
     if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
     const NchScope scope(c, s->nch);
     if ((rc = ensure_population(c, s->P, s->K))) return rc;
+    if (s->ordered && (rc = ensure_dither_map(c))) return rc;  // (before a capture begins)
     if (s->comm != c->comm || s->fold != search_folds(c))
         return fail(c, HQ_ERR_STATE, "communicator or palette split changed after hq_search_create: "
                                      "recreate the search");
@@ -382,8 +421,9 @@ int hq_search_create_from(hq_ctx* c, const hq_swasa_params* params, int K, uint6
         rc = device_search_create(c, params, K, seed, population, s);
     } else {
         const float delta = params->delta;
-        auto eval = [c, delta](const float* pal, int P, int KK, double* costs) {
-            return hq_eval_population(c, pal, P, KK, delta, costs, nullptr);
+        auto eval = [c, delta, s](const float* pal, int P, int KK, double* costs) {
+            return s->ordered ? hq_ordered_population(c, pal, P, KK, s->amp, delta, costs, nullptr)
+                              : hq_eval_population(c, pal, P, KK, delta, costs, nullptr);
         };
         s->driver = new SearchDriver(*params, K, seed, eval);
         // the k-means move, host-driven, is the public triple: an evaluation of the
@@ -443,6 +483,10 @@ int hq_search_run(hq_search* s, int iterations, int* ran) {
             return rc;
         }
     }
+    if (s->ctx && s->ordered && (rc = ordered_scope(s->ctx, s->K))) {  // (the image or an option may have changed)
+        if (ran) *ran = 0;
+        return rc;
+    }
     int done = 0;  // (the caller's `ran` is written as before; without one, a count of our own)
     int* const count = ran ? ran : &done;
     if (!s->driver) {
@@ -461,8 +505,10 @@ int hq_search_run(hq_search* s, int iterations, int* ran) {
 int hq_search_set_lloyd(hq_search* s, int every) {
     if (!s || !s->ctx) return HQ_ERR_ARG;
     if (every < 0) return fail(s->ctx, HQ_ERR_ARG, "every=%d < 0", every);
-    if (every > 0)
+    if (every > 0) {
+        if (int rc = ordered_excludes(s, "hybrid iterations")) return rc;
         if (int rc = lloyd_scope(s)) return rc;
+    }
     s->every = every;
     if (s->driver) s->driver->set_every(every);
     return HQ_OK;
@@ -471,12 +517,45 @@ int hq_search_set_lloyd(hq_search* s, int every) {
 int hq_search_set_repair(hq_search* s, int every, int max_moves) {
     if (!s || !s->ctx) return HQ_ERR_ARG;
     if (every < 0) return fail(s->ctx, HQ_ERR_ARG, "every=%d < 0", every);
-    if (every > 0)
+    if (every > 0) {
+        if (int rc = ordered_excludes(s, "repair iterations")) return rc;
         if (int rc = repair_scope(s)) return rc;
+    }
     s->repair_every = every;
     s->repair_moves = max_moves;
     if (s->driver) s->driver->set_repair_every(every);
     return HQ_OK;
+}
+
+int hq_search_set_ordered(hq_search* s, const float amp[3]) {
+    if (!s || !s->ctx) return HQ_ERR_ARG;
+    hq_ctx* c = s->ctx;
+    const float zeros[3] = {0.f, 0.f, 0.f};
+    if (!amp) amp = zeros;
+    if (int rc = check_ordered_amp(c, amp)) return rc;
+    const bool on = amp[0] != 0.f || amp[1] != 0.f || amp[2] != 0.f;
+    if (on) {
+        if (s->every > 0 || s->repair_every > 0)
+            return fail(c, HQ_ERR_UNSUPPORTED, "a search with hybrid or repair iterations: no ordered cost");
+        if (int rc = ordered_scope(c, s->K)) return rc;
+    }
+    if (on == s->ordered && (!on || (amp[0] == s->amp[0] && amp[1] == s->amp[1] && amp[2] == s->amp[2])))
+        return HQ_OK;  // (nothing changes: nothing is enqueued)
+    const bool was = s->ordered;
+    const float old[3] = {s->amp[0], s->amp[1], s->amp[2]};
+    s->ordered = on;
+    for (int ch = 0; ch < 3; ++ch) s->amp[ch] = on ? amp[ch] : 0.f;  // (zeros: the plain pass itself)
+    const int ite = s->driver ? s->driver->iteration() : s->ite;
+    if (ite != 0) return HQ_OK;
+    // before the first iteration: the initial population's errors and its best are the new evaluation's
+    const int rc = s->driver ? s->driver->rerank() : device_search_rerank(s);
+    c->sums_ok = false;
+    search_evaluated(c, !s->driver, rc, 1);
+    if (rc) {
+        s->ordered = was;
+        for (int ch = 0; ch < 3; ++ch) s->amp[ch] = old[ch];
+    }
+    return rc;
 }
 
 int hq_search_best(const hq_search* s, float* colors, double* best_error, int* iteration) {

@@ -73,6 +73,10 @@ class SearchDriver {
     // place, .w = 0: the generator ends where the plain start leaves it.
     int start(const float* population = nullptr);
     int run(int iterations, int* ran, std::vector<double>* trace);   // IM:497-568
+    // The evaluator has changed before the first iteration (hq_search_set_ordered): the
+    // initial population evaluated and ranked again (IM:490-493); no draws.  HQ_ERR_STATE
+    // once an iteration has run.
+    int rerank();
     // Hybrid iterations (libhq's addition): with every > 0 and a refine step,
     // the candidates of iteration ite (1-based, counted across run calls) with
     // ite % every == 0 go through `refine` between their generation and their

@@ -272,6 +272,84 @@ class ImageManipulation:
         self.ditherError = float(costs[0])
         return table[self.getIndices(0)].reshape(-1)
 
+    # ordered dithering: libhq's addition (hq_ordered_population, no reference counterpart)
+    @staticmethod
+    def bayerMap(log2n: int):
+        """hq_bayer_map: the Bayer threshold map of side 2**log2n (0 .. 6), float32 (n, n),
+        values (B + 0.5) / n**2 - 0.5 for the ranks B = 0 .. n**2 - 1."""
+        n = 1 << int(log2n) if 0 <= int(log2n) <= 6 else 1
+        m = np.zeros((n, n), np.float32)
+        check(load().hq_bayer_map(int(log2n), fptr(m)))
+        return m
+
+    @staticmethod
+    def orderedAmplitude(K: int) -> float:
+        """A starting amplitude for K colours: min(1, 1 / (K**(1/3) - 1)), the spacing of a
+        uniform K-colour lattice in the unit cube.  A heuristic, not a tuned value: real
+        palettes are not lattices, and on noisy images the best amplitude is lower."""
+        side = float(K) ** (1.0 / 3.0) - 1.0
+        return 1.0 if side <= 1.0 else 1.0 / side
+
+    def setDitherMap(self, map=None):
+        """hq_set_dither_map: the context's threshold map, a 2-D array (mh, mw) with each
+        side a power of two up to 64 and values in [-0.5, 0.5]; None restores the default,
+        Bayer 16 x 16."""
+        ctx = self._require()
+        if map is None:
+            check(self._lib.hq_set_dither_map(ctx, None, 0, 0), ctx)
+            return
+        m = np.ascontiguousarray(map, dtype=np.float32)
+        if m.ndim != 2:
+            raise ValueError(f"map of shape {m.shape}: a 2-D array (rows, columns)")
+        check(self._lib.hq_set_dither_map(ctx, fptr(m), m.shape[1], m.shape[0]), ctx)
+
+    @staticmethod
+    def _amp3(amp):
+        a = np.asarray(amp, np.float32).reshape(-1)
+        if a.size == 1:
+            a = np.repeat(a, 3)
+        if a.size != 3:
+            raise ValueError(f"amp={amp!r}: a float or three floats")
+        return np.ascontiguousarray(a)
+
+    def orderedPopulation(self, colors, amp, delta: float = 2.0, return_used=False):
+        """computeQuantizationErrorPopulation of the ordered-dither rendering: the argmin sees
+        each pixel plus ``amp`` (a float, or one per channel, in [0, 1]) times the threshold
+        map at its position.  colors (P, 4K), K <= 256 -> costs (P,) [, used (P, K)]; amp 0 is
+        the plain evaluation, bit for bit.  getIndices and getPixelErrors then answer for this
+        rendering; clusterSums and clusterErrors need a plain evaluation again."""
+        ctx = self._require()
+        pal = _f32(np.stack([np.asarray(c, np.float32).reshape(-1) for c in colors]))
+        P, K = pal.shape[0], pal.shape[1] // 4
+        a = self._amp3(amp)
+        costs = np.zeros(P, np.float64)
+        used = np.zeros((P, K), np.int32)
+        check(self._lib.hq_ordered_population(ctx, fptr(pal), P, K, fptr(a), float(delta),
+                                              dptr(costs), iptr(used)), ctx)
+        return (costs, used) if return_used else costs
+
+    def orderedPopulationPartial(self, colors, amp):
+        """hq_ordered_population_partial: the shard-local (P, 1 + K) partial rows."""
+        ctx = self._require()
+        pal = _f32(np.stack([np.asarray(c, np.float32).reshape(-1) for c in colors]))
+        P, K = pal.shape[0], pal.shape[1] // 4
+        a = self._amp3(amp)
+        part = np.zeros((P, 1 + K), np.float64)
+        check(self._lib.hq_ordered_population_partial(ctx, fptr(pal), P, K, fptr(a), dptr(part)), ctx)
+        return part
+
+    def quantizeOrdered(self, colors, amp):
+        """The ordered-dither rendering of the context's image with the palette colors
+        float[4K], in ``quantize``'s output format (quantizeDithered's way).  Sets
+        ``lastUsedColors`` and ``orderedError``, the rendering's mean dE."""
+        pal = _f32(colors).reshape(1, -1)
+        costs, used = self.orderedPopulation(pal, amp, 0.0, return_used=True)
+        table = pal.reshape(-1, 4).copy()
+        table[:, 3] = 0.0
+        self.lastUsedColors = used[0]
+        self.orderedError = float(costs[0])
+        return table[self.getIndices(0)].reshape(-1)
+
     # seeding the search from the image: libhq's additions (hq_color_histogram, hq_median_cut)
     def colorHistogram(self, bits: int = 5):
         """Colour histogram of the owned rows of the image set: (cells int64
@@ -301,7 +379,7 @@ class ImageManipulation:
                              simulatedAnnealing, filters, absfilters, illuminant,
                              iterations=None, stop=None, lloydSteps=0, lloydEvery=0,
                              init=None, initBits=5, repairEvery=0, repairMoves=-1, repairSteps=0,
-                             dither=0.0, ditherSearch=False):
+                             dither=0.0, ditherSearch=False, ordered=None, orderedSearch=False):
         """Full SWASA search (IM:383-591) on the GPU; returns bestColors float[4K].
 
         ``simulatedAnnealing`` is a :class:`~hybridquantization_amd.swasa.SWASA`;
@@ -336,8 +414,21 @@ class ImageManipulation:
         ``stop`` is not polled); ``init`` composes with it, the k-means and repair moves
         do not (ValueError: both start from a nearest-colour assignment).  ``bestError``
         and ``bestErrorDithered`` are then both the dithered cost.
+        ``ordered`` (hq_ordered_population: an amplitude, a float or three, in [0, 1];
+        ``orderedAmplitude(K)`` is a starting point): once the search and its polishes are
+        done the best palette is also evaluated in its ordered-dither rendering,
+        ``bestErrorOrdered``; ``bestError`` stays the plain one.  ``orderedSearch`` (needs
+        ``ordered``): the search itself runs under the ordered cost (hq_search_set_ordered,
+        device-resident or host-driven as the options say); ``bestError`` and
+        ``bestErrorOrdered`` are then both that cost.  The k-means and repair moves do not
+        compose with it (the library refuses them).
         """
         ctx = self._require()
+        amp = None if ordered is None else self._amp3(ordered)
+        if orderedSearch and (amp is None or not np.any(amp != 0)):
+            raise ValueError("orderedSearch needs a non-zero ordered amplitude")
+        if orderedSearch and (int(lloydSteps) != 0 or int(repairSteps) != 0):
+            raise ValueError("orderedSearch with a k-means or repair polish")
         dither = float(dither)
         if not 0.0 <= dither <= 1.0:
             raise ValueError(f"dither={dither!r}: a strength in [0, 1]")
@@ -385,6 +476,8 @@ class ImageManipulation:
                 seed_err = C.c_double()
                 check(self._lib.hq_search_best(handle, fptr(seed), C.byref(seed_err), None), ctx)
                 self.seedColors, self.seedError = seed, seed_err.value
+            if orderedSearch:
+                check(self._lib.hq_search_set_ordered(handle, fptr(amp)), ctx)
             if int(lloydEvery) != 0:
                 check(self._lib.hq_search_set_lloyd(handle, int(lloydEvery)), ctx)
             if int(repairEvery) != 0:
@@ -428,6 +521,11 @@ class ImageManipulation:
             self.bestErrorDithered = float(self.ditherPopulation(best.reshape(1, -1), dither, sw.delta)[0])
             if self.verbose:
                 print("Final error, dithered at strength %g : %.5f" % (dither, self.bestErrorDithered))
+        if amp is not None:
+            self.bestErrorOrdered = (self.bestError if orderedSearch else
+                                     float(self.orderedPopulation(best.reshape(1, -1), amp, sw.delta)[0]))
+            if self.verbose:
+                print("Final error, ordered dither at amplitude %s : %.5f" % (amp.tolist(), self.bestErrorOrdered))
         return best
 
     # IM:770

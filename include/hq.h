@@ -143,7 +143,8 @@ int hq_eval_population_partial(hq_ctx *ctx, const float *palettes, int P, int K,
 /* The read-back rule of hq_get_indices, hq_get_indices32 and hq_get_pixel_errors:
  * they answer for the last evaluation on the image and filters in force -- the
  * last successful hq_eval_population[_partial], hq_dither_population (the
- * dithered rendering), or evaluation inside hq_refine_population,
+ * dithered rendering), hq_ordered_population[_partial] (the ordered rendering), or
+ * evaluation inside hq_refine_population,
  * hq_repair_population, hq_search_create[_from] and hq_search_run (the last
  * candidates the search evaluated; a run of 0 iterations changes nothing).
  * hq_set_image*, hq_set_filters and an evaluation that fails after it has
@@ -319,6 +320,60 @@ int hq_repair_population(hq_ctx *ctx, float *palettes, int P, int K, int steps, 
 int hq_dither_population(hq_ctx *ctx, const float *palettes, int P, int K, float strength,
                          float delta, double *costs, int32_t *used);
 
+/* ---- ordered dithering: libhq's addition, no reference counterpart ----
+ * Error diffusion is a serial recurrence (one workgroup per palette); a threshold
+ * map gives most of its S-CIELAB gain with every pixel independent, so it lives
+ * inside the pruned-grid argmin, runs on row-block shards and can be the objective
+ * of a device-resident search.  In the argmin's space, per channel c, every
+ * operation one fp32 operation rounded to nearest and none contracted into an fma:
+ *     m   = map[(y mod mh) * mw + (x mod mw)]     x, y: the position in the FULL image
+ *     t_c = amp[c] * m
+ *     v_c = min(max(pix_c + t_c, 0), 1)
+ *     idx(x, y) = the first minimum over k of the argmin's distance(v, pal[k])
+ * pix is the planar float, or k/255 rebuilt in fp32 from the packed 8-bit copy's
+ * byte k -- the two are equal, so both image forms (option "img_u8" 0 / 1) give the
+ * same indices.  At amp = (0, 0, 0) the indices, used flags and costs are
+ * hq_eval_population's, bit for bit.
+ *
+ * hq_bayer_map: the Bayer map of side n = 2^log2n, log2n in 0 .. 6 (else HQ_ERR_ARG),
+ * host-only.  With L = log2n,
+ *     B(x, y) = OR over i < L of (((x ^ y) >> i) & 1) << (2 (L-1-i) + 1)
+ *                              | ((y >> i) & 1)       << (2 (L-1-i))
+ * a permutation of 0 .. n^2 - 1, and map[y n + x] = (B + 0.5) / n^2 - 0.5, exact in
+ * fp32 (n = 2: rows [-0.375, 0.125], [0.375, -0.125]). */
+int hq_bayer_map(int log2n, float *map);
+/* The context's threshold map, mh rows of mw values: mw and mh each a power of two
+ * in 1 .. 64, every value finite and in [-0.5, 0.5], else HQ_ERR_ARG and the map in
+ * force stays.  map NULL (mw, mh ignored) restores the default a fresh context has,
+ * Bayer 16 x 16.  The map is a property of the context like an option: it does not
+ * end the read-back getters' answers, and a search under the ordered cost uses the
+ * map in force when an iteration is enqueued. */
+int hq_set_dither_map(hq_ctx *ctx, const float *map, int mw, int mh);
+/* hq_eval_population with the index images chosen as above: costs[p] = mean dE +
+ * delta * #unused of the ordered rendering, from the unchanged cost path (every dE
+ * type, filter half-width and cost option); a colour is used when it appears in
+ * that index image.  used may be NULL.  K <= 256; option "grid" 0, 16, 32 and 64 all
+ * give the same indices.  Row-block shards are served: y is the full-image row, so
+ * a shard's indices are the whole image's rows, and with a communicator the call
+ * behaves as hq_eval_population does (the collective is the same; more than one
+ * rank has not been run).  Afterwards hq_get_indices[32] and hq_get_pixel_errors
+ * answer for this rendering, and hq_cluster_sums and hq_cluster_errors return
+ * HQ_ERR_STATE until the next hq_eval_population[_partial] (hq_dither_population's
+ * rule).
+ * HQ_ERR_ARG: P < 1, K < 1, a null palettes, costs or amp, an amp[c] that is not
+ * finite or outside [0, 1], a palette channel that is not finite or outside [0, 1].
+ * HQ_ERR_STATE: no image set; a row-block shard without a communicator (use the
+ * partial form).  HQ_ERR_UNSUPPORTED: K > 256, option "palette_split" or
+ * "slice_ranks" > 1, an image pixel that is not finite or outside [0, 1] (the range
+ * flag, found on the device once per image).  On any refusal the outputs and the
+ * evaluated state are untouched. */
+int hq_ordered_population(hq_ctx *ctx, const float *palettes, int P, int K, const float amp[3],
+                          float delta, double *costs, int32_t *used);
+/* The same without the final division and penalty, in hq_eval_population_partial's
+ * layout: the partials of disjoint shards of one image add up to the whole image's. */
+int hq_ordered_population_partial(hq_ctx *ctx, const float *palettes, int P, int K,
+                                  const float amp[3], double *partial);
+
 /* ---- seeding the search from the image: libhq's additions, no reference counterpart ----
  * The reference starts every search from uniform random palettes (SW:40-52).
  * The three entry points below give a start that knows the image: a colour
@@ -466,6 +521,20 @@ int hq_search_set_lloyd(hq_search *s, int every);
  * pass -- the error kernels ("errsum" in hq_profile_get), the reseed kernel
  * ("reseed"), then the evaluation.  Both forms give the same search bit for bit. */
 int hq_search_set_repair(hq_search *s, int every, int max_moves);
+/* A search whose objective is the ordered rendering (libhq's addition): from this
+ * call on every evaluation of the search is hq_ordered_population's at `amp` -- the
+ * candidates of the runs that follow and, when no iteration has run yet, the
+ * initial population too, which is evaluated and ranked again (IM:490-493; no
+ * draws).  amp NULL or zeros is the plain search, bit for bit: nothing extra is
+ * enqueued.  Serves the device-resident search ("sa_graph" 1 included: the pass is
+ * the plain one with assign's ordered instances) and the host-driven one
+ * ("sa_device" 0); the two give the same search bit for bit.  The map in force when
+ * an iteration is enqueued is the one used.  HQ_ERR_ARG: an amp[c] that is not
+ * finite or outside [0, 1].  HQ_ERR_UNSUPPORTED (non-zero amp): K > 256; a k-means
+ * or repair period set -- and hq_search_set_lloyd and hq_search_set_repair refuse a
+ * period likewise while it is on; "palette_split" or "slice_ranks" > 1; an image
+ * pixel outside [0, 1] (also checked by each hq_search_run, *ran = 0). */
+int hq_search_set_ordered(hq_search *s, const float amp[3]);
 
 /* Host-only SWASA driver with a caller-supplied population evaluator; same
  * policy code as hq_search_*.  Used to test the SA semantics without a GPU.
@@ -505,7 +574,8 @@ int hq_profile_enable(hq_ctx *ctx, int on);
  * kernels: the statistics and the gather of the worst pixels' colours), "reseed" (the reseed
  * kernel of a device-resident repair iteration, whose error pass counts under "grid", "assign"
  * and "cost"), "dither" (hq_dither_population's kernel, which stands in the place of "grid"
- * and "assign": a dithered evaluation counts nothing under those); returns total ms and launch
+ * and "assign": a dithered evaluation counts nothing under those; an ordered evaluation's grid
+ * and argmin count under "grid" and "assign" like the plain one's); returns total ms and launch
  * count (HIP events on the context stream). */
 int hq_profile_get(hq_ctx *ctx, const char *kernel, double *total_ms, int64_t *launches);
 int hq_profile_reset(hq_ctx *ctx);
