@@ -67,7 +67,11 @@ __device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
 // A wave whose 256 pixels all have one colour in a palette (flat regions; a
 // single-colour image is the worst case of same-address atomics, 64 lanes on
 // one LDS word) sums them across its lanes first and adds once.
-template <typename IDX_T, bool U8>
+// MSK (a pixel mask, ClusterArgs::mask): a masked-out pixel of a quad is loaded
+// and not added, like the pixels outside [q0, q1) -- so a wave with one is not
+// `full` and takes no shortcut; the planar form's range flag still looks at
+// every owned pixel.
+template <typename IDX_T, bool U8, bool MSK = false>
 __global__ __launch_bounds__(256) void centroid_kernel(ClusterArgs a, int ngroups) {
     constexpr bool LDS = sizeof(IDX_T) == 1;
     constexpr int F = U8 ? 2 : 3;  // 64-bit words per colour
@@ -120,12 +124,15 @@ __global__ __launch_bounds__(256) void centroid_kernel(ClusterArgs a, int ngroup
         for (int pp = 0; pp < 4; ++pp) kq[pp] = load_idx4(idx + (int64_t)(p0 + min(pp, ng - 1)) * a.idx_pitch + q);
         uint64_t r[4], g[4], b[4];
         bool ok[4];
+        uint32_t mq = ~0u;  // MSK: the quad's mask bytes
+        if constexpr (MSK) mq = *reinterpret_cast<const uint32_t*>(a.mask + q);
         if constexpr (U8) {
             const uint4 px = *reinterpret_cast<const uint4*>(a.rgbx + q);
             const uint32_t v[4] = {px.x, px.y, px.z, px.w};
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 ok[i] = in && q + i >= a.q0 && q + i < a.q1;
+                if constexpr (MSK) ok[i] = ok[i] && ((mq >> (8 * i)) & 0xffu) != 0u;
                 r[i] = v[i] & 0xffu;
                 g[i] = (v[i] >> 8) & 0xffu;
                 b[i] = (v[i] >> 16) & 0xffu;
@@ -145,6 +152,7 @@ __global__ __launch_bounds__(256) void centroid_kernel(ClusterArgs a, int ngroup
                                   vb[i] <= 1.f;
                 bad |= own && !fits;
                 ok[i] = own && fits;
+                if constexpr (MSK) ok[i] = ok[i] && ((mq >> (8 * i)) & 0xffu) != 0u;
                 r[i] = unit_q32(fits ? vr[i] : 0.f);
                 g[i] = unit_q32(fits ? vg[i] : 0.f);
                 b[i] = unit_q32(fits ? vb[i] : 0.f);
@@ -202,8 +210,10 @@ hipError_t launch_cluster_sums(const ClusterArgs& a0, int idx_bytes, int num_cu,
     with_idx(idx_bytes, [&](auto it) {
         using T = typename decltype(it)::type;
         with_bool(a.rgbx != nullptr, [&](auto U8) {
-            HQ_LAUNCH((centroid_kernel<T, U8.value>), dim3((unsigned)(a.nblocks * ngroups)), dim3(256), 0, s, a,
-                      ngroups);
+            with_bool(a.mask != nullptr, [&](auto MSK) {
+                HQ_LAUNCH((centroid_kernel<T, U8.value, MSK.value>), dim3((unsigned)(a.nblocks * ngroups)), dim3(256),
+                          0, s, a, ngroups);
+            });
         });
     });
     return hipGetLastError();

@@ -61,11 +61,14 @@ struct TileItem {
     int p, tile, x0, y0;
 };
 
-template <int TW, int TH>
+// MSK (the masked instances, hq_cost_masked.hip): the tile through the live-tile
+// list of the launch (CostArgs::live), which covers nlive P items.
+template <int TW, int TH, bool MSK = false>
 __device__ __forceinline__ TileItem tile_item(const CostArgs& a, int w, int P) {
     TileItem t;
     t.p = w % P;
-    t.tile = w / P;
+    if constexpr (MSK) t.tile = a.live[w / P];
+    else t.tile = w / P;
     t.x0 = (t.tile % a.tiles_x) * TW;
     t.y0 = a.g.r0 + (t.tile / a.tiles_x) * TH;
     return t;
@@ -365,7 +368,7 @@ __device__ __forceinline__ f32x4v mfma3(const f16x8& ah, const f16x8& al, const 
     return d;
 }
 
-template <int DE, bool TRIM>
+template <int DE, bool TRIM, bool MSK = false>
 __global__ __launch_bounds__(256, 6) void cost_mfma_kernel(CostArgs a, int P_) {
     constexpr int HALF = 10, RW = 128, TH = 8, HR = 2, T2 = 2 * HALF;
     constexpr int TW = RW - 2 * HALF, RH = TH + 2 * HALF;
@@ -381,7 +384,9 @@ __global__ __launch_bounds__(256, 6) void cost_mfma_kernel(CostArgs a, int P_) {
     float* s_v = reinterpret_cast<float*>(s_vq);
     const int tid = threadIdx.x;
     const Geom& g = a.g;
-    TileItem cur = tile_item<TW, TH>(a, xcd_remap(blockIdx.x, a.ntiles * P_), P_);
+    TileItem cur;
+    if constexpr (MSK) cur = tile_item<TW, TH, true>(a, xcd_remap(blockIdx.x, a.nlive * P_), P_);
+    else cur = tile_item<TW, TH>(a, xcd_remap(blockIdx.x, a.ntiles * P_), P_);
     tile_item_to_grid<DE, TW, TH>(a, cur);
     const TapsPtr<HALF> taps = (TapsPtr<HALF>)(uintptr_t)a.taps;  // H taps x 2^-30
     const int lane = tid & 63, wv = tid >> 6, lc = lane & 15, lk = lane >> 4;
@@ -455,11 +460,13 @@ __global__ __launch_bounds__(256, 6) void cost_mfma_kernel(CostArgs a, int P_) {
         }
     }
     float labv[2][3][HR];
+    uint32_t mk[2];  // MSK: the mask bytes of each row's 2 pixels, one load at the LabRef offset
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
         bool ok = has_item && gy0 + r < g.r1 && gx0 < g.W;
         if constexpr (DE == 2) ok = ok && gy0 + r >= g.r0;
         const uint32_t off = ok ? (uint32_t)((gy0 + r - g.r0) * g.lab_pitch + gx0) : 0u;
+        if constexpr (MSK) mk[r] = *reinterpret_cast<const uint16_t*>(a.mask + off);
         const float* src3[3] = {a.labL, a.labA, a.labB};
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
@@ -490,6 +497,9 @@ __global__ __launch_bounds__(256, 6) void cost_mfma_kernel(CostArgs a, int P_) {
                 const float e = delta_e_f<DE>(labv[r][0][xo], labv[r][1][xo], labv[r][2][xo], lf);
                 bool in = gy0 + r < g.r1 && gx0 + xo < g.W;
                 if constexpr (DE == 2) in = in && gy0 + r >= g.r0;
+                if constexpr (MSK) {  // a select: a masked-out NaN stays out of the sum
+                    part += in && ((mk[r] >> (8 * xo)) & 0xffu) != 0u ? e : 0.f;
+                } else
                 part += in ? e : 0.f;
                 if (a.pix_err && in)  // test option: the per-pixel dE (CL:201-209's error image)
                     a.pix_err[(int64_t)cur.p * a.pix_pitch + (int64_t)(gy0 + r - g.r0) * g.W + gx0 + xo] = e;
@@ -768,7 +778,7 @@ constexpr int cost16w_waves() {
 // (8 KT bytes): channel 0's x words first, then -- loaded from global memory
 // during channel 0's horizontal pass, once its gathers are done -- the (y, z)
 // pairs in the same bytes.
-template <int HB, int DE, bool TRIM, int NW, int NCH = 1>
+template <int HB, int DE, bool TRIM, int NW, int NCH = 1, bool MSK = false>
 __global__ __launch_bounds__(64 * NW, (cost16w_waves<HB, NCH>())) void cost16w_kernel(CostArgs a, int P_) {
     using Gm = Tile16<HB, NW>;
     constexpr int NTH = 64 * NW, IPR = 8 * NW;  // threads; horizontal items per row pair
@@ -792,7 +802,9 @@ __global__ __launch_bounds__(64 * NW, (cost16w_waves<HB, NCH>())) void cost16w_k
     float* s_v = reinterpret_cast<float*>(s_vq);
     const int tid = threadIdx.x;
     const Geom& g = a.g;
-    TileItem cur = tile_item<TW, TH>(a, xcd_remap(blockIdx.x, a.ntiles * P_), P_);
+    TileItem cur;
+    if constexpr (MSK) cur = tile_item<TW, TH, true>(a, xcd_remap(blockIdx.x, a.nlive * P_), P_);
+    else cur = tile_item<TW, TH>(a, xcd_remap(blockIdx.x, a.ntiles * P_), P_);
     tile_item_to_grid<DE, TW, TH>(a, cur);
     const TapsPtr<HB> taps = (TapsPtr<HB>)(uintptr_t)a.taps;  // H taps x 2^-30
     const int lane = tid & 63, wv = tid >> 6, lc = lane & 15, lk = lane >> 4;
@@ -980,11 +992,13 @@ __global__ __launch_bounds__(64 * NW, (cost16w_waves<HB, NCH>())) void cost16w_k
     }
     // LabRef of the item's 2 x 4 pixels, in flight across the barrier
     float4 lab[2][3];
+    uint32_t mk[2];  // MSK: the mask bytes of each row's 4 pixels, one dword at the LabRef offset
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
         bool ok = gy0 + r < g.r1 && gx0 < g.W;
         if constexpr (DE == 2) ok = ok && gy0 + r >= g.r0;
         const uint32_t off = ok ? (uint32_t)((gy0 + r - g.r0) * g.lab_pitch + gx0) : 0u;
+        if constexpr (MSK) mk[r] = *reinterpret_cast<const uint32_t*>(a.mask + off);
 #ifdef HQ_ABL_NOLABLD  // timing ablation (wrong results): no LabRef loads
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) lab[r][ch] = make_float4(off, off + 1, off + ch, r);
@@ -1071,6 +1085,17 @@ __global__ __launch_bounds__(64 * NW, (cost16w_waves<HB, NCH>())) void cost16w_k
     // tiles inside the image and shard (all but the last tile column and row)
     // sum without per-pixel masks
     float part = 0.f;
+    if constexpr (MSK) {  // every tile with per-pixel selects, in the plain forms' order of additions: an
+                          // all-ones mask gives their bits, a masked-out NaN stays out of the sum
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int xo = 0; xo < HR; ++xo) {
+                bool in = gy0 + r < g.r1 && gx0 + xo < g.W && ((mk[r] >> (8 * xo)) & 0xffu) != 0u;
+                if constexpr (DE == 2) in = in && gy0 + r >= g.r0;
+                part += in ? e[r][xo] : 0.f;
+            }
+    } else
     if constexpr (DE == 2) {  // the same, and a shard's first tile row masks its rows above r0
         if (cur.x0 + TW <= g.W && cur.y0 + TH <= g.r1 && cur.y0 >= g.r0) {
 #pragma unroll
@@ -1107,6 +1132,16 @@ __global__ __launch_bounds__(64 * NW, (cost16w_waves<HB, NCH>())) void cost16w_k
 }
 
 // ---- host side: the fast path's launchers (its tables: hq_cost_taps.cpp) ----
+// This file is compiled twice: as it is (the plain instances and launchers) and
+// through hq_cost_masked.hip with HQ_COST_MASKED defined (the MSK instances and
+// launch_cost_fast_masked / launch_cost_chunked_masked), so the two sets build
+// side by side and the plain set's source is what it was.
+#ifdef HQ_COST_MASKED
+constexpr bool kMasked = true;
+#define HQ_COST_LAUNCHER(name) name##_masked
+#else
+constexpr bool kMasked = false;
+#define HQ_COST_LAUNCHER(name) name
 // The two CostTaps<HB> of build_fast_taps.
 size_t fast_taps_bytes(int HB) { return 2 * 2 * sizeof(float) * kNumFilt * (2 * HB + 1); }
 static_assert(2 * sizeof(CostTaps<24>) == 2 * 2 * sizeof(float) * kNumFilt * 49, "CostTaps: two float [7][2 HB + 1]");
@@ -1117,11 +1152,14 @@ static_assert(2 * sizeof(CostTaps<24>) == 2 * 2 * sizeof(float) * kNumFilt * 49,
 // tile row that holds r0.  own_rows of fast_tile_dims counts from it.
 int fast_grid_row0(int de, int r0, int tile_rows) { return de == 2 ? r0 & ~(tile_rows - 1) : r0; }
 
+int fast_tile_width(int tile_rows, int tile_w) { return tile_rows == kTH16 ? tile_w : kFastTW; }
+
 void fast_tile_dims(int W, int own_rows, int tile_rows, int tile_w, int* tiles_x, int* ntiles) {
-    const int tw = tile_rows == kTH16 ? tile_w : kFastTW;
+    const int tw = fast_tile_width(tile_rows, tile_w);
     *tiles_x = (W + tw - 1) / tw;
     *ntiles = *tiles_x * ((own_rows + tile_rows - 1) / tile_rows);
 }
+#endif
 
 // a.taps = the two CostTaps<HB> of build_fast_taps; [1], which the kernels
 // here read, carries the vertical pass's 2^30 scale in its horizontal taps.
@@ -1131,18 +1169,18 @@ template <int HB, int NW, int NCH = 1>
 static void launch_cost16w(const CostArgs& a0, int P, int de, bool trim, hipStream_t s) {
     CostArgs a = a0;
     a.taps = static_cast<const char*>(a0.taps) + sizeof(CostTaps<HB>);
-    const dim3 grid((unsigned)(a.ntiles * P)), block(64 * NW);
+    const dim3 grid((unsigned)((kMasked ? a.nlive : a.ntiles) * P)), block(64 * NW);
     with_de(de, [&](auto DE) {
         with_bool(trim, [&](auto TRIM) {
-            constexpr auto kern = cost16w_kernel<HB, DE.value, TRIM.value, NW, NCH>;
+            constexpr auto kern = cost16w_kernel<HB, DE.value, TRIM.value, NW, NCH, kMasked>;
             if constexpr (NCH > 1) HQ_LAUNCH_DYN_LDS(kern, grid, block, 8 * (size_t)kMaxK * NCH, s, a, P);
             else HQ_LAUNCH(kern, grid, block, 0, s, a, P);
         });
     });
 }
 
-hipError_t launch_cost_chunked(const CostArgs& a, int P, int nch, int de, bool trim, hipStream_t s) {
-    if (!known_de(de)) return hipErrorInvalidValue;
+hipError_t HQ_COST_LAUNCHER(launch_cost_chunked)(const CostArgs& a, int P, int nch, int de, bool trim, hipStream_t s) {
+    if (!known_de(de) || (kMasked && (!a.mask || !a.live || a.nlive < 1))) return hipErrorInvalidValue;
     switch (nch) {
     case 2: launch_cost16w<10, 4, 2>(a, P, de, trim, s); break;
     case 4: launch_cost16w<10, 4, 4>(a, P, de, trim, s); break;
@@ -1155,9 +1193,10 @@ hipError_t launch_cost_chunked(const CostArgs& a, int P, int nch, int de, bool t
 }
 
 // 256-column tiles (8 waves, 69 KB of LDS at HB = 10) and 8-row tiles: HB = 10 only.
-hipError_t launch_cost_fast(const CostArgs& a0, int P, int de, bool trim, int tile_rows, int tile_w, int HB,
-                            hipStream_t s) {
+hipError_t HQ_COST_LAUNCHER(launch_cost_fast)(const CostArgs& a0, int P, int de, bool trim, int tile_rows, int tile_w,
+                                              int HB, hipStream_t s) {
     if (!known_de(de) || (HB != 10 && (tile_rows != kTH16 || tile_w == 256))) return hipErrorInvalidValue;
+    if (kMasked && (!a0.mask || !a0.live || a0.nlive < 1)) return hipErrorInvalidValue;
     if (tile_rows == kTH16 && tile_w == 256) {
         launch_cost16w<10, 8>(a0, P, de, trim, s);
     } else if (tile_rows == kTH16) {
@@ -1171,10 +1210,10 @@ hipError_t launch_cost_fast(const CostArgs& a0, int P, int de, bool trim, int ti
     } else {
         CostArgs a = a0;
         a.taps = static_cast<const char*>(a0.taps) + sizeof(CostTaps<10>);
-        const dim3 grid((unsigned)(a.ntiles * P));
+        const dim3 grid((unsigned)((kMasked ? a.nlive : a.ntiles) * P));
         with_de(de, [&](auto DE) {
             with_bool(trim, [&](auto TRIM) {
-                HQ_LAUNCH((cost_mfma_kernel<DE.value, TRIM.value>), grid, dim3(256), 0, s, a, P);
+                HQ_LAUNCH((cost_mfma_kernel<DE.value, TRIM.value, kMasked>), grid, dim3(256), 0, s, a, P);
             });
         });
     }

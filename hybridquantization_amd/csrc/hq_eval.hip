@@ -62,9 +62,47 @@ bool cost_fast(const hq_ctx* c) {
                                 c->cost_tw == 128));
 }
 
+// The fast launch's tiles under the options in force: 8-row tiles (cost_mfma_kernel) and
+// 256-column tiles exist for the 21-tap bucket only.
+void fast_tile_shape(const hq_ctx* c, int* rows, int* tw) {
+    *rows = c->fast_hb == 10 ? c->cost_rows : 16;
+    *tw = c->fast_hb == 10 ? c->cost_tw : 128;
+}
+
 }  // namespace
 
 namespace hq {
+
+// The live-tile list of the fast cost launch that the population being enqueued will take
+// (hq_mask.cpp), on the device.  Its inputs are the mask's owned rows, the launch's tile grid
+// (the tile shape, dE2000's shard grid) and whether the launch skips (option "mask_skip", and
+// nothing with "pixel_err": every tile then stores its pixels' dE); rebuilt when one of them has
+// changed.  The buffer's address sits in captured launches and its contents are read by them, so
+// it is written here only -- ensure_population calls this before anything is enqueued or a
+// capture begins -- with nothing of the context in flight (every entry point synchronises).
+int ensure_live_tiles(hq_ctx* c) {
+    if (!c->mask_on || !cost_fast(c)) return HQ_OK;
+    int rows, tw;
+    fast_tile_shape(c, &rows, &tw);
+    const int skip = c->mask_skip && !c->pixel_err;
+    if (!c->live_dirty && rows == c->live_rows && tw == c->live_tw && skip == c->live_skip) return HQ_OK;
+    const Geom& g = c->g;
+    TileGrid tg{};
+    tg.W = g.W, tg.r0 = g.r0, tg.r1 = g.r1;
+    tg.grid_row0 = fast_grid_row0(c->de_type, g.r0, rows);
+    tg.tile_w = fast_tile_width(rows, tw), tg.tile_h = rows;
+    fast_tile_dims(g.W, g.r1 - tg.grid_row0, rows, tw, &tg.tiles_x, &tg.ntiles);
+    std::vector<int32_t> live((size_t)std::max(tg.ntiles, 1));
+    const int n = mask_live_tiles(c->mask_own.data(), tg, skip != 0, live.data());
+    if (int rc = bind(c)) return rc;
+    HIP_TRY(c, c->d_live.ensure(sizeof(int32_t) * live.size()));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(c->d_live.p, live.data(), sizeof(int32_t) * live.size(), hipMemcpyHostToDevice));
+    c->n_live = n;
+    c->live_rows = rows, c->live_tw = tw, c->live_skip = skip;
+    c->live_dirty = false;
+    return HQ_OK;
+}
 
 // Ensure population buffers for P palettes of K colours.
 int ensure_population(hq_ctx* c, int P, int K) {
@@ -111,7 +149,7 @@ int ensure_population(hq_ctx* c, int P, int K) {
     if (!cost_fast(c) || K > kMaxK) HIP_TRY(c, c->d_gen_t.ensure(sizeof(float) * 7 * (size_t)g.n_ext + 256));
     HIP_TRY(c, c->h_pal.ensure(sizeof(float) * 4 * (size_t)P * K));
     HIP_TRY(c, c->h_out.ensure(sizeof(double) * (size_t)P * (1 + K)));
-    return HQ_OK;
+    return ensure_live_tiles(c);  // (a pixel mask on the fast path: the list its launch reads)
 }
 
 PaletteArgs prep_args(hq_ctx* c, int K) {
@@ -179,6 +217,7 @@ int enqueue_generic_cost(hq_ctx* c, int P, const void* idx_base, int idx_bytes, 
         gn.g = g;
         gn.half = c->half;
         gn.pix_err = c->pixel_err ? c->d_pixerr.as<float>() + (int64_t)p * n_own : nullptr;
+        gn.mask = c->mask_on ? c->d_mask.as<uint8_t>() : nullptr;
         gn.vtaps = c->d_vtaps.as<float>();
         gn.vtap_pitch = c->vtap_pitch;
         gn.hrow4 = c->gen_hrow4;
@@ -284,6 +323,7 @@ int enqueue_wide(hq_ctx* c, int P, int K, ProfRec& pr) {
     HIP_TRY(c, hipMemsetAsync(acc_set(c, c->acc_par, Pl), 0, sizeof(uint64_t) * acc_words(Pl), s));
     HIP_TRY(c, hipMemsetAsync(c->d_pflags.p, 0, sizeof(int) * (size_t)P, s));
     HIP_TRY(c, launch_prep_wide(wa, P, s));
+    c->tiles_run = c->tiles_all = 0;  // (hq_mask_info: the generic cost)
     HIP_TRY(c, hipMemsetAsync(c->d_used32.p, 0, sizeof(uint32_t) * (size_t)Pl * K, s));
     // the slice's palettes: indices and used flags in rows 0 .. Pl - 1
     WideArgs ws = wa;
@@ -380,9 +420,9 @@ int hq::enqueue_core(hq_ctx* c, int P, int K, ProfRec& pr, Pass pass) {
     }
     const float inv[3] = {1.0f / c->illum[0], 1.0f / c->illum[1], 1.0f / c->illum[2]};
     const bool fast = cost_fast(c);
-    // 8-row tiles (cost_mfma_kernel) exist for the 21-tap bucket only
-    const int rows = c->fast_hb == 10 ? c->cost_rows : 16;
-    const int tw = c->fast_hb == 10 ? c->cost_tw : 128;  // 256-column tiles: HB = 10 only
+    int rows, tw;
+    fast_tile_shape(c, &rows, &tw);
+    const bool masked = fast && c->mask_on;  // the masked instances over the live-tile list
     CostArgs ca{};
     if (fast) {
         ca.idx = nch > 1 ? c->d_idx16.as<uint8_t>() : c->d_idx.as<uint8_t>();
@@ -402,6 +442,18 @@ int hq::enqueue_core(hq_ctx* c, int P, int K, ProfRec& pr, Pass pass) {
         opp2xyz_over_illum(inv, ca.m_lab);
         ca.pix_err = c->pixel_err ? c->d_pixerr.as<float>() : nullptr;
         ca.pix_pitch = (int64_t)g.W * (g.r1 - g.r0);
+        if (masked) {
+            if (c->live_dirty || rows != c->live_rows || tw != c->live_tw ||
+                c->live_skip != (c->mask_skip && !c->pixel_err))
+                return fail(c, HQ_ERR_STATE, "pixel mask: the live-tile list is not that of this launch");
+            ca.mask = c->d_mask.as<uint8_t>();
+            ca.live = c->d_live.as<int32_t>();
+            ca.nlive = c->n_live;
+        }
+    }
+    if (pass.kind != Pass::AssignOnly) {  // hq_mask_info: what the fast cost pass launches
+        c->tiles_all = fast ? ca.ntiles : 0;
+        c->tiles_run = masked ? ca.nlive : c->tiles_all;
     }
     HIP_TRY(c, timed_launch(pr, passign, [&] {
         return dither ? launch_dither(DitherArgs{aa.R, aa.G, aa.B, ga.pal, aa.idx, ga.used_glob,
@@ -413,7 +465,15 @@ int hq::enqueue_core(hq_ctx* c, int P, int K, ProfRec& pr, Pass pass) {
                       : launch_assign(aa, Ps, s);
     }));
     if (pass.kind != Pass::AssignOnly) {
-        if (fast) {
+        if (masked) {
+            // no owned in-mask pixel: nothing to launch, the zeroed counters are the partial
+            if (ca.nlive > 0)
+                HIP_TRY(c, timed_launch(pr, pcost, [&] {
+                    return nch > 1 ? launch_cost_chunked_masked(ca, Pl, nch, c->de_type, c->trim && c->trim_ok, s)
+                                   : launch_cost_fast_masked(ca, Pl, c->de_type, c->trim && c->trim_ok, rows, tw,
+                                                             c->fast_hb, s);
+                }));
+        } else if (fast) {
             HIP_TRY(c, timed_launch(pr, pcost, [&] {
                 return nch > 1 ? launch_cost_chunked(ca, Pl, nch, c->de_type, c->trim && c->trim_ok, s)
                                : launch_cost_fast(ca, Pl, c->de_type, c->trim && c->trim_ok, rows, tw, c->fast_hb,
@@ -493,6 +553,7 @@ bool palette_fits_fast(const float* pal, int P, int K) {
 int eval_partial_into_hout(hq_ctx* c, const float* palettes, int P, int K) {
     int rc = check_eval_args(c, palettes, P, K);
     if (rc) return rc;
+    if ((rc = mask_scope(c))) return rc;
     if ((rc = bind(c))) return rc;
     const bool fits = palette_fits_fast(palettes, P, K);
     // 256 < K <= 16384: chunks of 256 colours through the grid and assign, and the
@@ -570,6 +631,7 @@ int color_histogram(hq_ctx* c, int bits, int64_t* out, int64_t* den) {
     ha.q0 = (uint32_t)((int64_t)(g.r0 - g.e0) * g.W);
     ha.q1 = ha.q0 + (uint32_t)((int64_t)g.W * (g.r1 - g.r0));
     ha.bits = bits;
+    ha.mask = c->mask_on ? c->d_maskq.as<uint8_t>() : nullptr;
     ProfRec pr = prof_begin(c);
     HIP_TRY(c, timed_launch(pr, kPHist, [&] { return launch_color_histogram(ha, c->num_cu, s); }));
     std::vector<int64_t> h(n4 + 1);
@@ -586,7 +648,7 @@ int color_histogram(hq_ctx* c, int bits, int64_t* out, int64_t* den) {
 // IM:712 from the [P][1+K] rows in h_out: averageArray(error) + computePenalty(used).
 // After an all-reduce the used entries count the ranks using colour k; unused <=> 0.
 void costs_from_hout(const hq_ctx* c, int P, int K, float delta, double* costs, int32_t* used) {
-    const double n_total = (double)c->g.W * (double)c->g.H;
+    const double n_total = cost_divisor(c);  // (a pixel mask: its pixels in the full image)
     for (int p = 0; p < P; ++p) {
         const double* o = c->h_out.as<double>() + (size_t)p * (1 + K);
         double penalty = 0.0;
@@ -689,6 +751,7 @@ ClusterArgs cluster_args(hq_ctx* c, int P, int K, int* idx_bytes) {
     ca.q1 = ca.q0 + (uint32_t)((int64_t)g.W * (g.r1 - g.r0));
     ca.P = P;
     ca.K = K;
+    ca.mask = c->mask_on ? c->d_maskq.as<uint8_t>() : nullptr;
     return ca;
 }
 
@@ -804,6 +867,7 @@ int planar_in_range(hq_ctx* c) {
         int idx_bytes = 1;
         ClusterArgs ca = cluster_args(c, 1, 1, &idx_bytes);
         ca.idx = c->d_idx.p;  // (the u8 image, whatever the last evaluation's index width)
+        ca.mask = nullptr;    // (the flag looks at every owned pixel with or without a mask)
         HIP_TRY(c, launch_cluster_sums(ca, 1, c->num_cu, st));
         int bad = 1;
         HIP_TRY(c, hipMemcpyAsync(&bad, ca.bad, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -867,6 +931,7 @@ int ordered_into_hout(hq_ctx* c, const float* palettes, int P, int K, const floa
     int rc = check_ordered_amp(c, amp);
     if (rc) return rc;
     if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
+    if ((rc = mask_scope(c))) return rc;
     if (K <= kMaxK && !population_in_range(palettes, P, K))
         return fail(c, HQ_ERR_ARG, "palette with a channel that is not finite or outside [0, 1]");
     if (!partial && !whole_image(c) && !(c->comm && c->nranks > 1))
@@ -963,6 +1028,7 @@ int hq_dither_population(hq_ctx* c, const float* palettes, int P, int K, float s
     if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
     int rc = whole_image_only(c, "hq_dither_population (error diffusion)");
     if (rc) return rc;
+    if ((rc = mask_scope(c))) return rc;
     if (K > kMaxK)
         return fail(c, HQ_ERR_UNSUPPORTED, "K=%d > %d: the dither kernel keeps the palette in LDS and writes "
                                            "8-bit indices", K, kMaxK);
@@ -1065,6 +1131,7 @@ int hq_color_histogram(hq_ctx* c, int bits, int64_t* cells, int64_t* den) {
 int hq_cluster_errors(hq_ctx* c, int P, int K, int64_t* err, float* worst_rgb) {
     if (!c) return HQ_ERR_ARG;
     if (!err || !worst_rgb || P < 1 || K < 1) return fail(c, HQ_ERR_ARG, "bad err / worst_rgb / P=%d / K=%d", P, K);
+    if (c->mask_on) return fail(c, HQ_ERR_UNSUPPORTED, "hq_cluster_errors under a pixel mask (hq_set_mask)");
     return cluster_errors(c, P, K, err, worst_rgb);
 }
 
@@ -1089,6 +1156,7 @@ int hq_repair_population(hq_ctx* c, float* palettes, int P, int K, int steps, fl
     int rc = check_improve_args(c, palettes, P, K, steps, costs, "hq_repair_population",
                                 ": merge the shards' hq_cluster_errors yourself");
     if (rc) return rc;
+    if (c->mask_on) return fail(c, HQ_ERR_UNSUPPORTED, "hq_repair_population under a pixel mask (hq_set_mask)");
     const PixelErrScope scope(c);  // the evaluations below store their error images
     const size_t n4 = (size_t)P * K * 4;
     std::vector<float> worst(n4);

@@ -48,7 +48,9 @@ __device__ __forceinline__ uint32_t hist_coord(float v, int bits) {
 //    of its span stay in that cell: one add per run, not per step;
 //  - a sum of 0 (a black channel) is not sent.
 // No LDS, no scratch: every array below is indexed by unrolled constants.
-template <bool U8>
+// MSK (a pixel mask, HistArgs::mask): a masked-out pixel is loaded and not added,
+// like the pixels outside [q0, q1); the range flag still looks at every owned pixel.
+template <bool U8, bool MSK = false>
 __global__ __launch_bounds__(256) void hist_kernel(HistArgs a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int bits = a.bits;
@@ -82,6 +84,8 @@ __global__ __launch_bounds__(256) void hist_kernel(HistArgs a) {
         uint64_t r[4], g[4], b[4];
         uint32_t cell[4];
         bool ok[4];
+        uint32_t mq = ~0u;  // MSK: the quad's mask bytes
+        if constexpr (MSK) mq = *reinterpret_cast<const uint32_t*>(a.mask + q);
         if constexpr (U8) {
             const uint4 px = *reinterpret_cast<const uint4*>(a.rgbx + q);
             const uint32_t v[4] = {px.x, px.y, px.z, px.w};
@@ -89,6 +93,7 @@ __global__ __launch_bounds__(256) void hist_kernel(HistArgs a) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 ok[i] = in && q + i >= a.q0 && q + i < a.q1;
+                if constexpr (MSK) ok[i] = ok[i] && ((mq >> (8 * i)) & 0xffu) != 0u;
                 const uint32_t rb = v[i] & 0xffu, gb = (v[i] >> 8) & 0xffu, bb = (v[i] >> 16) & 0xffu;
                 r[i] = rb, g[i] = gb, b[i] = bb;
                 cell[i] = ((rb >> sh) << (2 * bits)) | ((gb >> sh) << bits) | (bb >> sh);
@@ -108,6 +113,7 @@ __global__ __launch_bounds__(256) void hist_kernel(HistArgs a) {
                                   vb[i] <= 1.f;
                 bad |= own && !fits;
                 ok[i] = own && fits;
+                if constexpr (MSK) ok[i] = ok[i] && ((mq >> (8 * i)) & 0xffu) != 0u;
                 const float cr = fits ? vr[i] : 0.f, cg = fits ? vg[i] : 0.f, cb = fits ? vb[i] : 0.f;
                 r[i] = hist_q32(cr), g[i] = hist_q32(cg), b[i] = hist_q32(cb);
                 cell[i] = (hist_coord(cr, bits) << (2 * bits)) | (hist_coord(cg, bits) << bits) | hist_coord(cb, bits);
@@ -153,7 +159,9 @@ hipError_t launch_color_histogram(const HistArgs& a0, int num_cu, hipStream_t s)
     a.qspan = ((nq + want - 1) / want + 255u) / 256u * 256u;
     a.nblocks = (int)((nq + a.qspan - 1) / a.qspan);
     with_bool(a.rgbx != nullptr, [&](auto U8) {
-        HQ_LAUNCH((hist_kernel<U8.value>), dim3((unsigned)a.nblocks), dim3(256), 0, s, a);
+        with_bool(a.mask != nullptr, [&](auto MSK) {
+            HQ_LAUNCH((hist_kernel<U8.value, MSK.value>), dim3((unsigned)a.nblocks), dim3(256), 0, s, a);
+        });
     });
     return hipGetLastError();
 }

@@ -249,6 +249,11 @@ struct CostArgs {
     float m_lab[9];  // Opp->XYZ rows / illuminant (CL:124-131), opp2xyz_over_illum()
     float* pix_err;  // test option "pixel_err": [P][pix_pitch] per-pixel dE of the owned rows
     int64_t pix_pitch;  // (null: not written)
+    // pixel mask (hq_set_mask; read by the masked instances only, hq_cost_masked.hip): a byte per
+    // owned pixel at the LabRef planes' pitch, (y - r0) lab_pitch + x, non-zero = the pixel counts
+    const uint8_t* mask;
+    const int32_t* live;    // their work items' tiles: item w is palette w % P over tile live[w / P]
+    int nlive;              // entries of live (the launch covers nlive P items)
 };
 
 struct FinalizeArgs {
@@ -301,6 +306,10 @@ struct ClusterArgs {
     int P, K;
     int nblocks;            // workgroups per group of 4 palettes   } set by the
     uint32_t qspan;         // quads of 4 pixels per workgroup      } launcher
+    // pixel mask (hq_set_mask): a byte per position of the extended rows (padded to whole quads),
+    // non-zero = the pixel is added; null: every owned pixel.  The range flag looks at every owned
+    // pixel either way.
+    const uint8_t* mask = nullptr;
 };
 
 // Per-colour error statistics of the last evaluated population (hq_errsum.hip,
@@ -343,6 +352,7 @@ struct HistArgs {
     int bits;               // 2 .. 6
     int nblocks;            // workgroups                           } set by the
     uint32_t qspan;         // quads of 4 pixels per workgroup      } launcher
+    const uint8_t* mask = nullptr;  // pixel mask (ClusterArgs::mask), or null
 };
 
 // lloyd_update_kernel (hq_search.hip): the k-means move of a device-resident
@@ -401,6 +411,7 @@ struct GenArgs {
     int shape = 0;       // matrix-core pair's tile shapes: 0 by grid size, 1 the short forms, 2 the tall ones
     const uint32_t* htapd = nullptr;  // its taps, the same layout (k3 signed: the horizontal t3 taps)
     const float4* htaps = nullptr;  // gen_hrow4: [T][2] (k1.xyz, k3), (k2.xyz, 0) horizontal taps
+    const uint8_t* mask = nullptr;  // pixel mask (CostArgs::mask's layout), or null: every owned pixel counts
 };
 
 }  // namespace hq

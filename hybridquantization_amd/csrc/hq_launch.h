@@ -116,9 +116,14 @@ hipError_t launch_assign_wide(const WideArgs&, int P, hipStream_t);
 size_t fast_taps_bytes(int HB);
 int fast_grid_row0(int de, int r0, int tile_rows);
 void fast_tile_dims(int W, int own_rows, int tile_rows, int tile_w, int* tiles_x, int* ntiles);
+int fast_tile_width(int tile_rows, int tile_w);  // columns of a tile of fast_tile_dims' grid
 hipError_t launch_cost_fast(const CostArgs&, int P, int de, bool trim, int tile_rows, int tile_w, int HB,
                             hipStream_t);
 hipError_t launch_cost_chunked(const CostArgs&, int P, int nch, int de, bool trim, hipStream_t);
+// hq_cost_masked.hip: the same under a pixel mask (CostArgs::mask, live, nlive: nlive >= 1 tiles)
+hipError_t launch_cost_fast_masked(const CostArgs&, int P, int de, bool trim, int tile_rows, int tile_w, int HB,
+                                   hipStream_t);
+hipError_t launch_cost_chunked_masked(const CostArgs&, int P, int nch, int de, bool trim, hipStream_t);
 // hq_cost_generic.hip: any half-width, one palette per launch pair
 hipError_t launch_cost_generic(const GenArgs&, int de, int idx_bytes, hipStream_t);
 hipError_t launch_cost_tiled_generic(const GenArgs&, int de, int idx_bytes, hipStream_t);

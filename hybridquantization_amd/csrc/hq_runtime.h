@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "hq_launch.h"
+#include "hq_mask.h"
 #include "hq_swasa.h"
 
 #ifndef HQ_COST_TW
@@ -263,6 +264,22 @@ struct hq_ctx {
     int dmap_w = 0, dmap_h = 0;
     hq::DevBuf d_dmap;
     bool dmap_dirty = true;
+    // pixel mask (hq_set_mask; a property of the context like the map, dropped by hq_set_image*):
+    // the owned rows on the host (0 / 1, W bytes per row: what the live-tile list is built from),
+    // on the device at the LabRef planes' pitch (the cost kernels) and over the extended rows'
+    // positions (the sums and histogram kernels), and the counts hq_mask_info reports
+    bool mask_on = false;
+    std::vector<uint8_t> mask_own;
+    hq::DevBuf d_mask, d_maskq;
+    int64_t mask_n_full = 0, mask_n_own = 0;
+    // the live-tile list of the fast cost launch (ensure_live_tiles): rebuilt when the mask or
+    // the launch's tile grid or whether it skips has changed, never inside a capture
+    hq::DevBuf d_live;
+    int n_live = 0;
+    bool live_dirty = true;
+    int live_rows = 0, live_tw = 0, live_skip = -1;
+    int mask_skip = 1;     // option "mask_skip": the fast cost pass launches live tiles only
+    int64_t tiles_run = 0, tiles_all = 0;  // hq_mask_info: the last evaluation's fast cost launch
 
     // options
     int G2 = 32;           // argmin grid resolution (0 = exhaustive)
@@ -426,5 +443,14 @@ int planar_in_range(hq_ctx* c);  // -> c->planar_ok
 int check_ordered_amp(hq_ctx* c, const float* amp);
 int ordered_scope(hq_ctx* c, int K);
 int ensure_dither_map(hq_ctx* c);
+// pixel mask: the divisor that finishes a cost (the in-mask pixels of the full image; without a
+// mask W H, the expression it always was); the refusal of a palette slice under a mask; the
+// live-tile list on the device for the launch the options in force select (ensure_population
+// calls it: before anything is enqueued or captured)
+inline double cost_divisor(const hq_ctx* c) {
+    return c->mask_on ? (double)c->mask_n_full : (double)c->g.W * (double)c->g.H;
+}
+int mask_scope(hq_ctx* c);
+int ensure_live_tiles(hq_ctx* c);
 
 }  // namespace hq

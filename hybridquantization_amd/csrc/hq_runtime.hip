@@ -62,6 +62,14 @@ int whole_image_only(hq_ctx* c, const char* what, const char* comm_hint, bool ps
     return HQ_OK;
 }
 
+// A pixel mask measures the whole population on every device that holds pixels: a palette
+// slice (its rows of d_out, its counters) under one is left out.
+int mask_scope(hq_ctx* c) {
+    if (c->mask_on && (c->psplit || c->slice_ranks > 1))
+        return fail(c, HQ_ERR_UNSUPPORTED, "a palette slice (option palette_split or slice_ranks) under a pixel mask");
+    return HQ_OK;
+}
+
 ProfRec prof_begin(hq_ctx* c) { return ProfRec{c->prof ? c->ev.ev.data() : nullptr, 0}; }
 
 void prof_accumulate(hq_ctx* c, const ProfRec& pr) {
@@ -166,6 +174,9 @@ int set_image_common(hq_ctx* c, const std::vector<float>& R, const std::vector<f
     // c->g is the new image's already: nothing evaluated on the old one may be read at it
     c->have_image = false;  // (until every plane below is in place)
     c->sums_ok = c->err_ok = c->idx_ok = c->pixerr_ok = false;
+    c->mask_on = false;  // a mask belongs to an image
+    c->live_dirty = true;
+    c->tiles_run = c->tiles_all = 0;
     const size_t plane = sizeof(float) * (size_t)round_up(g.n_ext, 4);
     HIP_TRY(c, c->d_R.ensure(plane));
     HIP_TRY(c, c->d_G.ensure(plane));
@@ -410,6 +421,58 @@ int hq_set_image_planar_shard(hq_ctx* c, const float* R, const float* G, const f
     return set_image_common(c, r, g, b, nullptr, illum);
 }
 
+int hq_set_mask(hq_ctx* c, const uint8_t* mask, int w, int h) {
+    if (!c) return HQ_ERR_ARG;
+    if (!mask) {  // no mask: the state of a fresh context
+        c->mask_on = false;
+        c->live_dirty = true;
+        return HQ_OK;
+    }
+    if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
+    const Geom& g = c->g;
+    if (w != g.W || h != g.H) return fail(c, HQ_ERR_ARG, "mask of %d x %d on an image of %d x %d", w, h, g.W, g.H);
+    const int64_t n_full = mask_count(mask, (int64_t)g.W * g.H);
+    if (n_full == 0) return fail(c, HQ_ERR_ARG, "mask without a non-zero byte: no pixel would count");
+    int rc = bind(c);
+    if (rc) return rc;
+    // the three copies, built aside so that a failure leaves the mask in force as it was: the
+    // owned rows as 0 / 1; at the LabRef planes' pitch (the cost kernels read a dword of 4 pixels
+    // next to their LabRef float4s); over the extended rows' positions (the quads of the sums
+    // and histogram kernels), zero outside the owned rows and in the padding
+    const int own = g.r1 - g.r0;
+    std::vector<uint8_t> rows((size_t)g.W * own), lab((size_t)g.lab_pitch * std::max(own, 1) + 16, 0),
+        ext((size_t)round_up(g.n_ext, 4) + 16, 0);
+    for (int y = 0; y < own; ++y)
+        for (int x = 0; x < g.W; ++x) {
+            const uint8_t v = mask[(size_t)(g.r0 + y) * g.W + x] != 0;
+            rows[(size_t)y * g.W + x] = v;
+            lab[(size_t)y * g.lab_pitch + x] = v;
+            ext[(size_t)(g.r0 - g.e0 + y) * g.W + x] = v;
+        }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (nothing of this context is in flight)
+    DevBuf d_lab, d_ext;
+    HIP_TRY(c, d_lab.upload(lab.data(), lab.size()));
+    HIP_TRY(c, d_ext.upload(ext.data(), ext.size()));
+    std::swap(c->d_mask.p, d_lab.p), std::swap(c->d_mask.bytes, d_lab.bytes);
+    std::swap(c->d_maskq.p, d_ext.p), std::swap(c->d_maskq.bytes, d_ext.bytes);
+    c->mask_own.swap(rows);
+    c->mask_n_full = n_full;
+    c->mask_n_own = mask_count(c->mask_own.data(), (int64_t)c->mask_own.size());
+    c->mask_on = true;
+    c->live_dirty = true;  // (the list: built by the next evaluation, ensure_live_tiles)
+    return HQ_OK;
+}
+
+int hq_mask_info(hq_ctx* c, int64_t* n_full, int64_t* n_owned, int64_t* tiles_run, int64_t* tiles_all) {
+    if (!c) return HQ_ERR_ARG;
+    const Geom& g = c->g;
+    if (n_full) *n_full = c->mask_on ? c->mask_n_full : c->have_image ? (int64_t)g.W * g.H : 0;
+    if (n_owned) *n_owned = c->mask_on ? c->mask_n_own : c->have_image ? (int64_t)g.W * (g.r1 - g.r0) : 0;
+    if (tiles_run) *tiles_run = c->tiles_run;
+    if (tiles_all) *tiles_all = c->tiles_all;
+    return HQ_OK;
+}
+
 int hq_get_labref(hq_ctx* c, float* lab4) {
     if (!c || !lab4) return HQ_ERR_ARG;
     if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set");
@@ -641,6 +704,8 @@ int hq_set_option(hq_ctx* c, const char* name, int value) {
         }
     } else if (!std::strcmp(name, "chunked")) {
         c->chunked = value != 0;
+    } else if (!std::strcmp(name, "mask_skip")) {
+        c->mask_skip = value != 0;
     } else if (!std::strcmp(name, "pixel_err")) {
         c->pixel_err = value != 0;
     } else if (!std::strcmp(name, "dither_rows")) {

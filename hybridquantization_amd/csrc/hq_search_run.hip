@@ -30,7 +30,7 @@ SaArgs sa_args(hq_search* s, bool accept, bool init, bool generate, bool random,
     a.jump_C = s->jC.as<uint64_t>();
     a.prep = prep_args(c, s->nch > 1 ? kMaxK : s->K);
     a.nch = s->nch;
-    a.n_total = (double)c->g.W * (double)c->g.H;
+    a.n_total = cost_divisor(c);  // (a pixel mask: its pixels in the full image)
     a.keep_threshold = s->keep_acc;
     a.temperature = s->t_acc;
     a.amax = amax;
@@ -89,6 +89,8 @@ bool period_in_run(const hq_search* s, int every, int ite, int iterations) {
 // hq_repair_population's scope, and a dE type whose costs are numbers.
 int repair_scope(hq_search* s) {
     hq_ctx* c = s->ctx;
+    if (c->mask_on)  // (a masked error statistic does not exist: hq_cluster_errors' refusal)
+        return fail(c, HQ_ERR_UNSUPPORTED, "repair iterations under a pixel mask (hq_set_mask)");
     if (c->de_type == HQ_DE_CIE94)
         return fail(c, HQ_ERR_UNSUPPORTED, "repair iterations on a dE94 context: its costs are NaN on real images");
     if (int rc = whole_image_only(c, "repair iterations")) return rc;
@@ -398,6 +400,7 @@ int hq_search_create_from(hq_ctx* c, const hq_swasa_params* params, int K, uint6
         return fail(c, HQ_ERR_ARG, "bad SWASA parameters");
     if (population && !population_in_range(population, params->population, K))
         return fail(c, HQ_ERR_ARG, "initial population with a channel that is not finite or outside [0, 1]");
+    if (int rc = mask_scope(c)) return rc;
     // device-resident: K <= 256, or chunked palettes (256 < K <= 16384); at most
     // kSaMaxP palettes (sa_step's per-palette tables) and kSaMaxSub sub-palettes
     // (its fold reads 8 used words per sub-palette, at most 4 per thread)
@@ -482,6 +485,10 @@ int hq_search_run(hq_search* s, int iterations, int* ran) {
             if (ran) *ran = 0;
             return rc;
         }
+    }
+    if (s->ctx && (rc = mask_scope(s->ctx))) {  // (a palette slice under a pixel mask)
+        if (ran) *ran = 0;
+        return rc;
     }
     if (s->ctx && s->ordered && (rc = ordered_scope(s->ctx, s->K))) {  // (the image or an option may have changed)
         if (ran) *ran = 0;

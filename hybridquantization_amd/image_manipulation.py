@@ -350,6 +350,37 @@ class ImageManipulation:
         self.orderedError = float(costs[0])
         return table[self.getIndices(0)].reshape(-1)
 
+    # a pixel mask on the cost: libhq's addition (hq_set_mask, no reference counterpart)
+    def setMask(self, mask=None):
+        """hq_set_mask: restrict what every cost, clusterSums and colorHistogram measure to
+        the pixels where ``mask`` is non-zero -- an (h, w) or flat array of the FULL image, any
+        integer or bool dtype.  None clears it.  The image must be set first (setImage drops
+        the mask); indices, used flags and stored per-pixel errors do not depend on it."""
+        ctx = self._require()
+        if mask is None:
+            check(self._lib.hq_set_mask(ctx, None, 0, 0), ctx)
+            return
+        m = np.asarray(mask)
+        if m.dtype != np.bool_ and not np.issubdtype(m.dtype, np.integer):
+            raise ValueError(f"mask of dtype {m.dtype}: an integer or bool array")
+        if m.ndim not in (1, 2):
+            raise ValueError(f"mask of shape {m.shape}: (h, w) or flat")
+        w, h = getattr(self, "w", 0), getattr(self, "h", 0)
+        if (m.ndim == 2 and m.shape != (h, w)) or m.size != w * h:
+            raise ValueError(f"mask of shape {m.shape} on an image of {h} x {w}")
+        m = np.ascontiguousarray((m != 0).reshape(-1), dtype=np.uint8)
+        check(self._lib.hq_set_mask(ctx, _lib.u8ptr(m), w, h), ctx)
+
+    def maskInfo(self):
+        """hq_mask_info -> (n_full, n_owned, tiles_run, tiles_all): the in-mask pixels of the
+        full image (w h without a mask) and of the owned rows, and the output tiles per palette
+        the last evaluation's fast cost pass launched / would launch without a mask (0, 0 when
+        it took the generic path)."""
+        ctx = self._require()
+        v = [C.c_int64() for _ in range(4)]
+        check(self._lib.hq_mask_info(ctx, *[C.byref(x) for x in v]), ctx)
+        return tuple(x.value for x in v)
+
     # seeding the search from the image: libhq's additions (hq_color_histogram, hq_median_cut)
     def colorHistogram(self, bits: int = 5):
         """Colour histogram of the owned rows of the image set: (cells int64
@@ -379,7 +410,7 @@ class ImageManipulation:
                              simulatedAnnealing, filters, absfilters, illuminant,
                              iterations=None, stop=None, lloydSteps=0, lloydEvery=0,
                              init=None, initBits=5, repairEvery=0, repairMoves=-1, repairSteps=0,
-                             dither=0.0, ditherSearch=False, ordered=None, orderedSearch=False):
+                             dither=0.0, ditherSearch=False, ordered=None, orderedSearch=False, mask=None):
         """Full SWASA search (IM:383-591) on the GPU; returns bestColors float[4K].
 
         ``simulatedAnnealing`` is a :class:`~hybridquantization_amd.swasa.SWASA`;
@@ -422,8 +453,15 @@ class ImageManipulation:
         device-resident or host-driven as the options say); ``bestError`` and
         ``bestErrorOrdered`` are then both that cost.  The k-means and repair moves do not
         compose with it (the library refuses them).
+        ``mask`` (hq_set_mask; setMask's argument): only the pixels where it is non-zero are
+        measured.  It is set after the image and applies to the search, the polishes,
+        ``init="mediancut"`` (the histogram of the region) and every reported error.  The
+        repair moves have no masked form: ``repairEvery`` / ``repairSteps`` with a mask raise
+        ValueError before anything runs.
         """
         ctx = self._require()
+        if mask is not None and (int(repairEvery) != 0 or int(repairSteps) != 0):
+            raise ValueError("mask with repairEvery or repairSteps: no masked error statistic")
         amp = None if ordered is None else self._amp3(ordered)
         if orderedSearch and (amp is None or not np.any(amp != 0)):
             raise ValueError("orderedSearch needs a non-zero ordered amplitude")
@@ -444,6 +482,8 @@ class ImageManipulation:
         # match a new array that reuses a freed one's id, or miss an in-place edit,
         # and the upload is small next to a 5000-iteration search.
         self.setImage(inlinergbOriginal, inlineScielabOriginal, w, illuminant)
+        if mask is not None:
+            self.setMask(mask)
         sw = simulatedAnnealing
         params = sw.params()
         handle = C.c_void_p()

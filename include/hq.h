@@ -374,6 +374,66 @@ int hq_ordered_population(hq_ctx *ctx, const float *palettes, int P, int K, cons
 int hq_ordered_population_partial(hq_ctx *ctx, const float *palettes, int P, int K,
                                   const float amp[3], double *partial);
 
+/* ---- a pixel mask on the cost: libhq's addition, no reference counterpart ----
+ * Every cost above is a mean over all w * h pixels.  A mask restricts what is
+ * measured to a region: one byte per pixel of the FULL image, mask[y*w + x],
+ * non-zero = the pixel counts (1, 7 and 255 mean the same); N = the number of
+ * in-mask pixels of the full image.  With a mask in force:
+ *  - the argmin and the stencil are what they are without one.  Index images, the
+ *    used flags (a colour is used when it appears in the index image, so the
+ *    penalty term is unchanged) and, with option "pixel_err" 1, the stored dE of
+ *    every owned pixel, masked-out ones included, keep their bits: a masked-out
+ *    pixel's colour is still displayed, and still feeds its neighbours' blur.
+ *  - costs[p] = (sum over the in-mask pixels of dE) / N + delta * #unused.  A
+ *    masked-out pixel is left out by a select, so its dE may be NaN (dE94's, for
+ *    example) without reaching the sum.  hq_eval_population_partial's
+ *    partial[p*(1+K)] is the masked sum over the owned rows.  This holds for every
+ *    evaluation: plain, partial, dithered, ordered, a search's (host-driven and
+ *    device-resident agree bit for bit, as without a mask), hq_refine_population's.
+ *  - hq_cluster_sums (and so hq_refine_population's and a hybrid iteration's
+ *    k-means move): sums and count over the in-mask owned pixels; a colour without
+ *    one has count 0 and keeps its bits; den is unchanged.  The planar form's
+ *    range check (HQ_ERR_UNSUPPORTED for a pixel outside [0, 1]) keeps looking at
+ *    every owned pixel, masked-out ones included.
+ *  - hq_color_histogram: cells over the in-mask owned pixels, so hq_median_cut of
+ *    it seeds from the region.
+ *  Both use the mask in force when they are called.
+ * An all-ones mask gives the unmasked library's outputs bit for bit; no mask set
+ * is the unmasked code path itself.  Weights other than 0 / 1 do not exist: the
+ * exact integer sums above are sized for counts of 1.
+ *
+ * hq_set_mask: `mask` points at the full image's mask, as hq_set_image_shard's
+ * pointers do; a shard keeps its owned rows, every rank passes the same mask, and
+ * N is counted here from the full mask.  mask NULL (w, h ignored): no mask, the
+ * state of a fresh context.  HQ_ERR_STATE: no image set.  HQ_ERR_ARG: w, h other
+ * than the image's, or a mask without a non-zero byte; the mask in force stays.
+ * hq_set_image* drops the mask (it belongs to an image); hq_set_filters keeps it.
+ * The mask is a property of the context like the dither map: setting it does not
+ * end the read-back getters' answers (indices and stored dE do not depend on it).
+ * A search uses the mask in force when an iteration is enqueued, so it may change
+ * between hq_search_run calls; the errors of the members accepted before are
+ * then stale, exactly as after an option change -- nothing is re-evaluated.
+ * While a mask is set, HQ_ERR_UNSUPPORTED with outputs and evaluated state
+ * untouched: any evaluation or search call under option "palette_split" or
+ * "slice_ranks" > 1; hq_cluster_errors and hq_repair_population (a masked error
+ * statistic does not exist); hq_search_set_repair(every > 0), and an
+ * hq_search_run that would run a repair iteration (*ran = 0, the search not
+ * advanced).
+ * Option "mask_skip" (default 1): the fast cost kernels launch one workgroup per
+ * output tile and palette; with 1 only the tiles that hold an in-mask owned pixel
+ * are launched (a list built on the host when the mask, the tile shape or this
+ * option has changed), unless "pixel_err" is 1, when every tile stores its
+ * pixels' dE.  0: every tile.  The results are the same bit for bit.  The generic
+ * cost kernels never skip. */
+int hq_set_mask(hq_ctx *ctx, const uint8_t *mask, int w, int h);
+/* *n_full = in-mask pixels of the full image (w * h without a mask), *n_owned = of
+ * the owned rows, *tiles_run / *tiles_all = output tiles per palette the last
+ * evaluation's fast cost pass launched / would launch without a mask (both 0
+ * when that evaluation took the generic path or none ran on this image).  Any
+ * pointer may be NULL. */
+int hq_mask_info(hq_ctx *ctx, int64_t *n_full, int64_t *n_owned, int64_t *tiles_run,
+                 int64_t *tiles_all);
+
 /* ---- seeding the search from the image: libhq's additions, no reference counterpart ----
  * The reference starts every search from uniform random palettes (SW:40-52).
  * The three entry points below give a start that knows the image: a colour
@@ -626,6 +686,9 @@ int hq_profile_reset(hq_ctx *ctx);
  *   "dither_rows"  hq_dither_population: rows per strip of the dither kernel, a multiple of 64
  *                  in 64 .. 1024 (default 1024; anything else is HQ_ERR_ARG).  The results do
  *                  not depend on it, bit for bit: it lets small test images cross strips
+ *   "mask_skip"    under a pixel mask (hq_set_mask): 1 (default) = the fast cost kernels launch
+ *                  only the tiles that hold an in-mask owned pixel (every tile with "pixel_err"
+ *                  1); 0 = every tile.  The results do not depend on it, bit for bit
  *   "palette_split" 1 = with a communicator of N ranks, each holding the whole image
  *                  (hq_set_image): rank r evaluates palettes [r P/N, (r+1) P/N) and one
  *                  all-gather gives every rank all P results (SURVEY 8e's split of large
