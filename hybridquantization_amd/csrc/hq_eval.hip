@@ -62,16 +62,70 @@ bool cost_fast(const hq_ctx* c) {
                                 c->cost_tw == 128));
 }
 
-// The fast launch's tiles under the options in force: 8-row tiles (cost_mfma_kernel) and
-// 256-column tiles exist for the 21-tap bucket only.
-void fast_tile_shape(const hq_ctx* c, int* rows, int* tw) {
-    *rows = c->fast_hb == 10 ? c->cost_rows : 16;
-    *tw = c->fast_hb == 10 ? c->cost_tw : 128;
+// The palettes of a P-palette population this device evaluates: a palette
+// split (psplit with a communicator of N ranks, or the test-only slice options)
+// takes [r P/N, (r+1) P/N) on the whole image; anything else all P.
+int palette_slice(hq_ctx* c, int P, int* lo, int* n) {
+    int R = 1, r = 0;
+    if (c->psplit && c->comm) R = c->nranks, r = c->rank;
+    else if (c->slice_ranks > 1) R = c->slice_ranks, r = c->slice_rank;
+    *lo = 0;
+    *n = P;
+    if (R == 1) return HQ_OK;
+    if (r < 0 || r >= R) return fail(c, HQ_ERR_ARG, "palette split: rank %d outside [0, %d)", r, R);
+    if (P % R) return fail(c, HQ_ERR_ARG, "palette split: population %d not divisible by %d ranks", P, R);
+    if (!whole_image(c))
+        return fail(c, HQ_ERR_STATE, "palette split: every rank needs the whole image (hq_set_image)");
+    *n = P / R;
+    *lo = r * *n;
+    return HQ_OK;
+}
+
+// The fast launch's tile grid under the options in force: 8-row tiles (cost_mfma_kernel) and
+// 256-column tiles exist for the 21-tap bucket only; dE2000's grid starts at a tile row.
+struct FastGrid { int rows, tw, row0, tiles_x, ntiles; };
+FastGrid fast_grid(const hq_ctx* c) {
+    FastGrid f{};
+    f.rows = c->fast_hb == 10 ? c->cost_rows : 16;
+    f.tw = c->fast_hb == 10 ? c->cost_tw : 128;
+    f.row0 = fast_grid_row0(c->de_type, c->g.r0, f.rows);
+    fast_tile_dims(c->g.W, c->g.r1 - f.row0, f.rows, f.tw, &f.tiles_x, &f.ntiles);
+    return f;
+}
+// (the live-tile list on the device is that launch's)
+bool live_tiles_current(const hq_ctx* c, const FastGrid& f) {
+    return !c->live_dirty && f.rows == c->live_rows && f.tw == c->live_tw &&
+           c->live_skip == (c->mask_skip && !c->pixel_err);
+}
+
+// The argmin grid's levels: resolutions, bytes per palette (level 1) and per 4 palettes (level 2).
+struct GridLayout { int G1, G2; int64_t l1p, l2g; };
+GridLayout grid_layout(const hq_ctx* c) {
+    const int G2 = c->G2 > 0 ? c->G2 : 4, G1 = G2 / 4;
+    return GridLayout{G1, G2, round_up((int64_t)G1 * G1 * G1 * 32, 256),
+                      round_up((int64_t)G2 * G2 * G2 * kL2Line, 256)};
+}
+
+void lab_matrix(const hq_ctx* c, float m[9]) {
+    const float inv[3] = {1.0f / c->illum[0], 1.0f / c->illum[1], 1.0f / c->illum[2]};
+    opp2xyz_over_illum(inv, m);  // (the cost kernels' m_lab)
 }
 
 }  // namespace
 
 namespace hq {
+
+void drop(hq_ctx* c) { c->res = Resident{}; }
+void commit(hq_ctx* c, const Resident& r) { c->res = r; }
+
+Resident resident_of(hq_ctx* c, Resident::Owner owner, int P, int K) {
+    int lo = 0, n = P;
+    (void)palette_slice(c, P, &lo, &n);  // (the pass has taken this slice: it cannot fail here)
+    const bool fast = cost_fast(c) && !(K > kMaxK && c->nch_cur == 1);  // (enqueue_wide: the generic cost)
+    const int64_t all = fast ? fast_grid(c).ntiles : 0;
+    return Resident{owner, P, K, c->nch_cur, lo, n, owner != Resident::Search && c->pixel_err,
+                    fast && c->mask_on ? c->n_live : all, all};
+}
 
 // The live-tile list of the fast cost launch that the population being enqueued will take
 // (hq_mask.cpp), on the device.  Its inputs are the mask's owned rows, the launch's tile grid
@@ -82,16 +136,10 @@ namespace hq {
 // capture begins -- with nothing of the context in flight (every entry point synchronises).
 int ensure_live_tiles(hq_ctx* c) {
     if (!c->mask_on || !cost_fast(c)) return HQ_OK;
-    int rows, tw;
-    fast_tile_shape(c, &rows, &tw);
+    const FastGrid f = fast_grid(c);
+    if (live_tiles_current(c, f)) return HQ_OK;
     const int skip = c->mask_skip && !c->pixel_err;
-    if (!c->live_dirty && rows == c->live_rows && tw == c->live_tw && skip == c->live_skip) return HQ_OK;
-    const Geom& g = c->g;
-    TileGrid tg{};
-    tg.W = g.W, tg.r0 = g.r0, tg.r1 = g.r1;
-    tg.grid_row0 = fast_grid_row0(c->de_type, g.r0, rows);
-    tg.tile_w = fast_tile_width(rows, tw), tg.tile_h = rows;
-    fast_tile_dims(g.W, g.r1 - tg.grid_row0, rows, tw, &tg.tiles_x, &tg.ntiles);
+    const TileGrid tg{c->g.W, c->g.r0, c->g.r1, f.row0, fast_tile_width(f.rows, f.tw), f.rows, f.tiles_x, f.ntiles};
     std::vector<int32_t> live((size_t)std::max(tg.ntiles, 1));
     const int n = mask_live_tiles(c->mask_own.data(), tg, skip != 0, live.data());
     if (int rc = bind(c)) return rc;
@@ -99,7 +147,7 @@ int ensure_live_tiles(hq_ctx* c) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipMemcpy(c->d_live.p, live.data(), sizeof(int32_t) * live.size(), hipMemcpyHostToDevice));
     c->n_live = n;
-    c->live_rows = rows, c->live_tw = tw, c->live_skip = skip;
+    c->live_rows = f.rows, c->live_tw = f.tw, c->live_skip = skip;
     c->live_dirty = false;
     return HQ_OK;
 }
@@ -107,8 +155,13 @@ int ensure_live_tiles(hq_ctx* c) {
 // Ensure population buffers for P palettes of K colours.
 int ensure_population(hq_ctx* c, int P, int K) {
     const Geom& g = c->g;
+    // a buffer the record vouches for: ensure frees what it grows, so the record goes first
+    auto vouched = [c](DevBuf& b, size_t n) {
+        if (n > b.bytes) drop(c);
+        return b.ensure(n);
+    };
     if (c->nch_cur > 1) {  // chunked palettes: 16-bit indices, then P nch sub-palettes of 256
-        HIP_TRY(c, c->d_idx16.ensure(sizeof(uint16_t) * (size_t)P * g.idx_pitch + 256));
+        HIP_TRY(c, vouched(c->d_idx16, sizeof(uint16_t) * (size_t)P * g.idx_pitch + 256));
         if (c->nch_cur > 4) HIP_TRY(c, c->d_dist.ensure(sizeof(float) * (size_t)P * g.idx_pitch));
         if (use_lists16(c)) {
             HIP_TRY(c, c->d_l1n.ensure(sizeof(uint16_t) * n16_l1_words(K) * (size_t)P * kN16G1 * kN16G1 * kN16G1));
@@ -118,32 +171,28 @@ int ensure_population(hq_ctx* c, int P, int K) {
         P *= c->nch_cur;  // (d_out, h_out: P nch (1 + 256) >= P (1 + K) doubles)
         K = kMaxK;
     }
-    const int G2 = c->G2 > 0 ? c->G2 : 4;
-    const int G1 = G2 / 4;
-    const int64_t l1p = round_up((int64_t)G1 * G1 * G1 * 32, 256);
-    const int64_t l2g = round_up((int64_t)G2 * G2 * G2 * kL2Line, 256);  // per group of 4 palettes
-    const int64_t n_own = (int64_t)g.W * (g.r1 - g.r0);
+    const GridLayout gl = grid_layout(c);
     HIP_TRY(c, c->d_pal_in.ensure(sizeof(float4) * (size_t)P * K));
-    HIP_TRY(c, c->d_pal.ensure(sizeof(float4) * (size_t)P * std::max(K, kMaxK)));
+    HIP_TRY(c, vouched(c->d_pal, sizeof(float4) * (size_t)P * std::max(K, kMaxK)));
     HIP_TRY(c, c->d_opp.ensure(sizeof(float4) * (size_t)P * std::max(K, kMaxK)));
     if (K > kMaxK) {
-        HIP_TRY(c, c->d_idx32.ensure(sizeof(uint32_t) * (size_t)P * g.idx_pitch));
-        HIP_TRY(c, c->d_used32.ensure(sizeof(uint32_t) * (size_t)P * K));
+        HIP_TRY(c, vouched(c->d_idx32, sizeof(uint32_t) * (size_t)P * g.idx_pitch));
+        HIP_TRY(c, vouched(c->d_used32, sizeof(uint32_t) * (size_t)P * K));
     }
     HIP_TRY(c, c->d_opp16.ensure(sizeof(uint4) * (size_t)P * kMaxK));
     HIP_TRY(c, c->d_dup.ensure((size_t)P * kMaxK));
     HIP_TRY(c, c->d_pflags.ensure(sizeof(int) * (size_t)P));
-    HIP_TRY(c, c->d_lvl1.ensure((size_t)P * l1p));
-    HIP_TRY(c, c->d_lvl2.ensure((size_t)((P + 3) / 4) * l2g));
+    HIP_TRY(c, c->d_lvl1.ensure((size_t)P * gl.l1p));
+    HIP_TRY(c, c->d_lvl2.ensure((size_t)((P + 3) / 4) * gl.l2g));
     // + 256: the cost kernels' interior fills read whole dword pairs, up to 7
     // bytes past a region's last column (past the buffer on the last palette's
     // last row when idx_pitch has no padding)
-    HIP_TRY(c, c->d_idx.ensure((size_t)P * g.idx_pitch + 256));
+    HIP_TRY(c, vouched(c->d_idx, (size_t)P * g.idx_pitch + 256));
     const size_t rb = (size_t)rank_blocks(c);  // counter / used-bit blocks per set
-    HIP_TRY(c, c->d_used_mask.ensure(2 * rb * sizeof(uint32_t) * kUsedSlots * (size_t)used_stride(P)));
-    HIP_TRY(c, c->d_acc.ensure(2 * rb * sizeof(uint64_t) * acc_words(P)));
+    HIP_TRY(c, vouched(c->d_used_mask, 2 * rb * sizeof(uint32_t) * kUsedSlots * (size_t)used_stride(P)));
+    HIP_TRY(c, vouched(c->d_acc, 2 * rb * sizeof(uint64_t) * acc_words(P)));
     HIP_TRY(c, c->d_out.ensure(sizeof(double) * (size_t)P * (1 + K)));
-    if (c->pixel_err) HIP_TRY(c, c->d_pixerr.ensure(sizeof(float) * (size_t)P * std::max<int64_t>(n_own, 1)));
+    if (c->pixel_err) HIP_TRY(c, vouched(c->d_pixerr, sizeof(float) * (size_t)P * std::max<int64_t>(n_own(g), 1)));
     // the generic path's [7][n_ext] scratch, here rather than at its first launch: an
     // allocation cannot happen while a search run is being captured into a graph
     if (!cost_fast(c) || K > kMaxK) HIP_TRY(c, c->d_gen_t.ensure(sizeof(float) * 7 * (size_t)g.n_ext + 256));
@@ -175,16 +224,14 @@ uint32_t* used_set(hq_ctx* c, int par, int Ps) {
 }
 
 GridArgs grid_args(hq_ctx* c, int P, int K, int so = 0) {
-    const int G2 = c->G2 > 0 ? c->G2 : 4;
-    const int G1 = G2 / 4;
+    const GridLayout gl = grid_layout(c);
     // (P = sub-palettes; the counters of set c->acc_par)
     const int nch = c->nch_cur;
     // (so: the first of the P sub-palettes in the prepared tables, a palette split's slice)
     return GridArgs{c->d_pal.as<float4>() + (int64_t)so * kMaxK, c->d_dup.as<uint8_t>() + (int64_t)so * kMaxK,
                     c->d_pflags.as<int>() + so, c->d_lvl1.as<uint8_t>(), c->d_lvl2.as<uint8_t>(),
                     used_set(c, c->acc_par, P),
-                    used_stride(P), K, G1,
-                    round_up((int64_t)G1 * G1 * G1 * 32, 256), round_up((int64_t)G2 * G2 * G2 * kL2Line, 256),
+                    used_stride(P), K, gl.G1, gl.l1p, gl.l2g,
                     acc_set(c, c->acc_par, P / nch), P / nch, nch};
 }
 
@@ -197,8 +244,6 @@ int enqueue_generic_cost(hq_ctx* c, int P, const void* idx_base, int idx_bytes, 
     const Geom& g = c->g;
     hipStream_t s = c->stream;
     HIP_TRY(c, c->d_gen_t.ensure(sizeof(float) * 7 * (size_t)g.n_ext + 256));
-    const int64_t n_own = (int64_t)g.W * (g.r1 - g.r0);
-    const float inv[3] = {1.0f / c->illum[0], 1.0f / c->illum[1], 1.0f / c->illum[2]};
     for (int p = 0; p < P; ++p) {
         GenArgs gn{};
         gn.idx = static_cast<const char*>(idx_base) + (int64_t)p * g.idx_pitch * idx_bytes;
@@ -216,7 +261,7 @@ int enqueue_generic_cost(hq_ctx* c, int P, const void* idx_base, int idx_bytes, 
         gn.P = P;
         gn.g = g;
         gn.half = c->half;
-        gn.pix_err = c->pixel_err ? c->d_pixerr.as<float>() + (int64_t)p * n_own : nullptr;
+        gn.pix_err = c->pixel_err ? c->d_pixerr.as<float>() + (int64_t)p * n_own(g) : nullptr;
         gn.mask = c->mask_on ? c->d_mask.as<uint8_t>() : nullptr;
         gn.vtaps = c->d_vtaps.as<float>();
         gn.vtap_pitch = c->vtap_pitch;
@@ -231,7 +276,7 @@ int enqueue_generic_cost(hq_ctx* c, int P, const void* idx_base, int idx_bytes, 
         gn.shape = c->gen_shape;
         gn.htapd = gn.vtapd ? gn.vtapd + vtile_dup_tap_words(c->half) : nullptr;
         gn.htaps = c->d_htaps.as<float4>();
-        opp2xyz_over_illum(inv, gn.m_lab);
+        lab_matrix(c, gn.m_lab);
         // the events span every palette's launch pair: start on the first, stop on the last;
         // cost_variant 2: the per-pixel pair in the reference's summation order
         HIP_TRY(c, timed_launch(pr, cost, [&] {
@@ -239,25 +284,6 @@ int enqueue_generic_cost(hq_ctx* c, int P, const void* idx_base, int idx_bytes, 
                                         : launch_cost_tiled_generic(gn, c->de_type, idx_bytes, s);
         }, p == 0, p == P - 1));
     }
-    return HQ_OK;
-}
-
-// The palettes of a P-palette population this device evaluates: a palette
-// split (psplit with a communicator of N ranks, or the test-only slice options)
-// takes [r P/N, (r+1) P/N) on the whole image; anything else all P.
-int palette_slice(hq_ctx* c, int P, int* lo, int* n) {
-    int R = 1, r = 0;
-    if (c->psplit && c->comm) R = c->nranks, r = c->rank;
-    else if (c->slice_ranks > 1) R = c->slice_ranks, r = c->slice_rank;
-    *lo = 0;
-    *n = P;
-    if (R == 1) return HQ_OK;
-    if (r < 0 || r >= R) return fail(c, HQ_ERR_ARG, "palette split: rank %d outside [0, %d)", r, R);
-    if (P % R) return fail(c, HQ_ERR_ARG, "palette split: population %d not divisible by %d ranks", P, R);
-    if (!whole_image(c))
-        return fail(c, HQ_ERR_STATE, "palette split: every rank needs the whole image (hq_set_image)");
-    *n = P / R;
-    *lo = r * *n;
     return HQ_OK;
 }
 
@@ -294,14 +320,25 @@ int enqueue_collective(hq_ctx* c, bool fold, int P, int K, int lo, int Pl, int P
     return HQ_OK;
 }
 
-// The index images, [and error image, counters, d_out rows] on the device are now
-// those of P palettes of K colours in nch chunks, of which [lo, lo + Pl) are here.
-void note_evaluated(hq_ctx* c, int P, int K, int nch, int lo, int Pl) {
-    c->slice_lo = lo;
-    c->slice_n = Pl;
-    c->last_P = P;
-    c->K_cur = K;
-    c->last_nch = nch;
+// A pass over P palettes begins: the slice [lo, lo + Pl) this device takes; on a test-only
+// slice the other palettes' rows of d_out zeroed (writes_out: the pass ends in d_out); the
+// other counter set taken.  A side pass hands the set back on every way out (ParRestore).
+int begin_pass(hq_ctx* c, int P, int K, bool writes_out, int* lo, int* Pl) {
+    if (int rc = palette_slice(c, P, lo, Pl)) return rc;
+    if (*Pl < P && !c->comm && writes_out)  // test-only slice: the other palettes' rows read as zero
+        HIP_TRY(c, hipMemsetAsync(c->d_out.p, 0, sizeof(double) * (size_t)P * (1 + K), c->stream));
+    c->acc_par ^= 1;
+    return HQ_OK;
+}
+struct ParRestore { hq_ctx* c; bool on; ~ParRestore() { if (on) c->acc_par ^= 1; } };
+// ... and ends: finalize into this device's rows of d_out (not a folding search's, whose accept
+// step reads the sums itself), then the collective.  A side pass has neither.
+int end_pass(hq_ctx* c, const Pass& pass, const FinalizeArgs& fa, int P, int K, int lo, int Pl, int Ps,
+             ProfRec& pr) {
+    if (pass.side()) return HQ_OK;
+    if (pass.kind != Pass::Fold)
+        HIP_TRY(c, timed_launch(pr, Pair(pass.pairs() + 3), [&] { return launch_finalize(fa, Pl, c->stream); }));
+    return c->comm ? enqueue_collective(c, pass.kind == Pass::Fold, P, K, lo, Pl, Ps, pr) : HQ_OK;
 }
 
 // K > 256 (hq_wide.hip): prep, exhaustive argmin into 32-bit indices and
@@ -313,17 +350,13 @@ int enqueue_wide(hq_ctx* c, int P, int K, ProfRec& pr) {
     const Geom& g = c->g;
     hipStream_t s = c->stream;
     int lo = 0, Pl = P;
-    if (int rc = palette_slice(c, P, &lo, &Pl)) return rc;
+    if (int rc = begin_pass(c, P, K, true, &lo, &Pl)) return rc;
     WideArgs wa{c->d_pal_in.as<float4>(), c->d_pal.as<float4>(), c->d_opp.as<float4>(), c->d_pflags.as<int>(),
                 c->d_R.as<float>(), c->d_G.as<float>(), c->d_B.as<float>(), c->d_idx32.as<uint32_t>(),
                 c->d_used32.as<uint32_t>(), g.n_ext, g.idx_pitch, K};
-    c->acc_par ^= 1;
-    if (Pl < P && !c->comm)  // test-only slice: the other palettes' rows read as zero
-        HIP_TRY(c, hipMemsetAsync(c->d_out.p, 0, sizeof(double) * (size_t)P * (1 + K), s));
     HIP_TRY(c, hipMemsetAsync(acc_set(c, c->acc_par, Pl), 0, sizeof(uint64_t) * acc_words(Pl), s));
     HIP_TRY(c, hipMemsetAsync(c->d_pflags.p, 0, sizeof(int) * (size_t)P, s));
     HIP_TRY(c, launch_prep_wide(wa, P, s));
-    c->tiles_run = c->tiles_all = 0;  // (hq_mask_info: the generic cost)
     HIP_TRY(c, hipMemsetAsync(c->d_used32.p, 0, sizeof(uint32_t) * (size_t)Pl * K, s));
     // the slice's palettes: indices and used flags in rows 0 .. Pl - 1
     WideArgs ws = wa;
@@ -332,12 +365,128 @@ int enqueue_wide(hq_ctx* c, int P, int K, ProfRec& pr) {
     ws.pflags += lo;
     HIP_TRY(c, timed_launch(pr, kPAssign, [&] { return launch_assign_wide(ws, Pl, s); }));
     if (int rc = enqueue_generic_cost(c, Pl, c->d_idx32.p, 4, K, pr, kPCost, lo)) return rc;
-    FinalizeArgs fa{acc_set(c, c->acc_par, Pl), nullptr, 0, c->d_out.as<double>() + (int64_t)lo * (1 + K), Pl, K,
-                    c->d_used32.as<uint32_t>(), 8};
-    HIP_TRY(c, timed_launch(pr, kPFinalize, [&] { return launch_finalize(fa, Pl, s); }));
-    if (c->comm)
-        if (int rc = enqueue_collective(c, false, P, K, lo, Pl, Pl, pr)) return rc;
-    note_evaluated(c, P, K, 1, lo, Pl);
+    const FinalizeArgs fa{acc_set(c, c->acc_par, Pl), nullptr, 0, c->d_out.as<double>() + (int64_t)lo * (1 + K), Pl,
+                          K, c->d_used32.as<uint32_t>(), 8};
+    return end_pass(c, Pass{}, fa, P, K, lo, Pl, Pl, pr);
+}
+
+// ---- the stages of enqueue_core ---------------------------------------------------
+// The grid (build_grid or the native 16-bit lists; both also zero the used bits and the sums),
+// or without one -- G2 = 0, a dithered pass -- the zeroing.
+int enqueue_grid(hq_ctx* c, const GridArgs& ga, bool build, bool n16, int K, int Pl, int Ps, Pair pgrid,
+                 ProfRec& pr) {
+    hipStream_t s = c->stream;
+    if (!build) {
+        HIP_TRY(c, hipMemsetAsync(ga.used_glob, 0, sizeof(uint32_t) * kUsedSlots * (size_t)used_stride(Ps), s));
+        HIP_TRY(c, hipMemsetAsync(ga.acc_zero, 0, sizeof(uint64_t) * acc_words(Pl), s));
+        return HQ_OK;
+    }
+    const int nch = c->nch_cur;
+    HIP_TRY(c, timed_launch(pr, pgrid, [&] {
+        return n16 ? launch_lists16_grid(Lists16Args{ga.pal, ga.pflags, c->d_l1n.as<uint16_t>(),
+                                                     c->d_l2n.as<uint16_t>(), ga.used_glob, used_stride(Ps),
+                                                     ga.acc_zero, Pl, K, nch * kMaxK, nch},
+                                         Pl, s)
+                   : launch_build_grid(ga, Ps, s);
+    }));
+    return HQ_OK;
+}
+
+// assign over Ps sub-palettes of Ks colours (chunked palettes: into the 16-bit images) ...
+AssignArgs assign_args(hq_ctx* c, const GridArgs& ga, int Ps, int Ks, bool ordered) {
+    const Geom& g = c->g;
+    const int nch = c->nch_cur;
+    AssignArgs aa{c->d_R.as<float>(), c->d_G.as<float>(), c->d_B.as<float>(),
+                  sums_u8(c) ? c->d_rgbx.as<uint32_t>() : nullptr, ga.pal, ga.pflags,
+                  c->d_lvl1.as<uint8_t>(), c->d_lvl2.as<uint8_t>(),
+                  c->d_idx.as<uint8_t>(), ga.used_glob, used_stride(Ps), g.n_ext, g.idx_pitch,
+                  ga.lvl1_pitch, ga.lvl2_gstride, Ks, c->G2, assign_blocks(c, Ps, ordered)};
+    if (nch > 1) {
+        aa.idx16 = c->d_idx16.as<uint16_t>();
+        aa.dist = nch > 4 ? c->d_dist.as<float>() : nullptr;
+        aa.nch = nch;
+        while ((1 << aa.lg_nch) < nch) ++aa.lg_nch;
+    }
+    return aa;
+}
+
+// ... an ordered pass: the map (on the device: ensure_dither_map) and the amplitudes; K <= 256
+int add_ordered(hq_ctx* c, const Pass& pass, AssignArgs& aa) {
+    if (c->nch_cur > 1 || pass.kind == Pass::Dither || !c->d_dmap.p)
+        return fail(c, HQ_ERR_STATE, "ordered pass: K > 256 or no map");
+    const int mw = c->dmap.empty() ? 16 : c->dmap_w, mh = c->dmap.empty() ? 16 : c->dmap_h;
+    aa.map = c->d_dmap.as<float>();
+    aa.mw_mask = (uint32_t)mw - 1u;
+    aa.mh_mask = (uint32_t)mh - 1u;
+    while ((1u << aa.lg_mw) < (uint32_t)mw) ++aa.lg_mw;
+    for (int ch = 0; ch < 3; ++ch) aa.amp[ch] = pass.amp[ch];
+    aa.W = (uint32_t)c->g.W;
+    aa.y0 = (uint32_t)c->g.e0;
+    return HQ_OK;
+}
+
+// ... the native 16-bit lists: one palette of K colours per workgroup (its table in LDS).
+void add_lists16(const hq_ctx* c, int K, int Pl, AssignArgs& aa) {
+    aa.l1n = c->d_l1n.as<uint16_t>();
+    aa.l2n = c->d_l2n.as<uint16_t>();
+    aa.kpal = c->nch_cur * kMaxK;
+    aa.K = K;
+    // one resident round of 1024-thread workgroups over the P palettes, >= 4 pixels per thread
+    const int ngr = K <= 4096 ? (Pl + 1) / 2 : Pl;  // workgroup groups: palette pairs up to K = 4096
+    aa.nblocks = (int)std::max<int64_t>(
+        1, std::min<int64_t>(std::max(1, c->num_cu / ngr), (c->g.n_ext + 4095) / 4096));
+}
+
+// The fast cost launch; under a mask its live-tile list, which has to be this launch's.
+int cost_args(hq_ctx* c, const GridArgs& ga, const FastGrid& f, int K, int so, int Pl, CostArgs* out) {
+    CostArgs ca{};
+    ca.idx = c->nch_cur > 1 ? c->d_idx16.as<uint8_t>() : c->d_idx.as<uint8_t>();
+    ca.opp16 = c->d_opp16.as<uint4>() + (int64_t)so * kMaxK;
+    ca.taps = c->d_taps.p;
+    ca.vfrag16 = c->d_vfrag16.as<uint4>();
+    ca.vfrag16p = c->d_vfrag16p.as<uint4>();
+    ca.labL = c->d_labL.as<float>();
+    ca.labA = c->d_labA.as<float>();
+    ca.labB = c->d_labB.as<float>();
+    ca.acc = ga.acc_zero;
+    ca.acc_P = Pl;
+    ca.acc_p0 = 0;
+    ca.g = c->g;
+    ca.K = K;
+    ca.tiles_x = f.tiles_x;
+    ca.ntiles = f.ntiles;
+    lab_matrix(c, ca.m_lab);
+    ca.pix_err = c->pixel_err ? c->d_pixerr.as<float>() : nullptr;
+    ca.pix_pitch = n_own(c->g);
+    if (c->mask_on) {
+        if (!live_tiles_current(c, f))
+            return fail(c, HQ_ERR_STATE, "pixel mask: the live-tile list is not that of this launch");
+        ca.mask = c->d_mask.as<uint8_t>();
+        ca.live = c->d_live.as<int32_t>();
+        ca.nlive = c->n_live;
+    }
+    *out = ca;
+    return HQ_OK;
+}
+
+// The cost: the fast launch (under a mask over its live tiles, and none without one: the
+// zeroed counters are the partial), else the generic pair.
+int enqueue_cost(hq_ctx* c, const CostArgs& ca, bool fast, const FastGrid& f, int lo, int Pl, Pair pcost,
+                 ProfRec& pr) {
+    hipStream_t s = c->stream;
+    const int nch = c->nch_cur, de = c->de_type;
+    const bool trim = c->trim && c->trim_ok;
+    if (!fast)
+        return nch > 1 ? enqueue_generic_cost(c, Pl, c->d_idx16.p, 2, nch * kMaxK, pr, pcost, lo)
+                       : enqueue_generic_cost(c, Pl, c->d_idx.p, 1, kMaxK, pr, pcost, lo);
+    if (c->mask_on && ca.nlive == 0) return HQ_OK;
+    HIP_TRY(c, timed_launch(pr, pcost, [&] {
+        if (c->mask_on)
+            return nch > 1 ? launch_cost_chunked_masked(ca, Pl, nch, de, trim, s)
+                           : launch_cost_fast_masked(ca, Pl, de, trim, f.rows, f.tw, c->fast_hb, s);
+        return nch > 1 ? launch_cost_chunked(ca, Pl, nch, de, trim, s)
+                       : launch_cost_fast(ca, Pl, de, trim, f.rows, f.tw, c->fast_hb, s);
+    }));
     return HQ_OK;
 }
 
@@ -351,111 +500,31 @@ int enqueue_wide(hq_ctx* c, int P, int K, ProfRec& pr) {
 // assign run on P nch sub-palettes of 256 colours (d_pal etc. hold them,
 // prep_palette made them), assign combines them into 16-bit indices, the cost
 // kernel reads those with a 256 nch-entry table.
+// What it leaves on the device is the caller's to commit (resident_of).
 int hq::enqueue_core(hq_ctx* c, int P, int K, ProfRec& pr, Pass pass) {
     const Geom& g = c->g;
     hipStream_t s = c->stream;
     const int nch = c->nch_cur, Ks = nch > 1 ? kMaxK : K;
-    const bool dither = pass.kind == Pass::Dither;
+    const bool dither = pass.kind == Pass::Dither, costed = pass.kind != Pass::AssignOnly;
     const int p0 = pass.pairs();
-    const Pair pgrid = Pair(p0), passign = dither ? kPDither : Pair(p0 + 1), pcost = Pair(p0 + 2),
-               pfinalize = Pair(p0 + 3);
     // the palettes this device evaluates: all, or a palette split's slice [lo, lo + Pl)
     int lo = 0, Pl = P;
-    if (int rc = palette_slice(c, P, &lo, &Pl)) return rc;
+    if (int rc = begin_pass(c, P, K, costed, &lo, &Pl)) return rc;
+    const ParRestore restore{c, pass.side()};
     const int Ps = Pl * nch, so = lo * nch;  // sub-palettes, the first one's index
-    if (Pl < P && !c->comm && pass.kind != Pass::AssignOnly)  // test-only slice: the other palettes' rows read as zero
-        HIP_TRY(c, hipMemsetAsync(c->d_out.p, 0, sizeof(double) * (size_t)P * (1 + K), s));
-    c->acc_par ^= 1;
-    struct ParRestore {  // a side pass: back to the last full pass's set on every way out
-        hq_ctx* c;
-        bool on;
-        ~ParRestore() { if (on) c->acc_par ^= 1; }
-    } restore{c, pass.side()};
     const GridArgs ga = grid_args(c, Ps, Ks, so);
     const bool n16 = use_lists16(c);
-    if (c->G2 > 0 && !dither) {  // (build_grid also zeroes the used bits and the sums)
-        HIP_TRY(c, timed_launch(pr, pgrid, [&] {
-            return n16 ? launch_lists16_grid(Lists16Args{ga.pal, ga.pflags, c->d_l1n.as<uint16_t>(),
-                                                         c->d_l2n.as<uint16_t>(), ga.used_glob, used_stride(Ps),
-                                                         ga.acc_zero, Pl, K, nch * kMaxK, nch},
-                                             Pl, s)
-                       : launch_build_grid(ga, Ps, s);
-        }));
-    } else {
-        HIP_TRY(c, hipMemsetAsync(ga.used_glob, 0, sizeof(uint32_t) * kUsedSlots * (size_t)used_stride(Ps), s));
-        HIP_TRY(c, hipMemsetAsync(ga.acc_zero, 0, sizeof(uint64_t) * acc_words(Pl), s));
-    }
-    const int nblocks = assign_blocks(c, Ps, pass.ordered);
-    AssignArgs aa{c->d_R.as<float>(), c->d_G.as<float>(), c->d_B.as<float>(),
-                  c->img_u8 && c->img_u8_path ? c->d_rgbx.as<uint32_t>() : nullptr, ga.pal, ga.pflags,
-                  c->d_lvl1.as<uint8_t>(), c->d_lvl2.as<uint8_t>(),
-                  c->d_idx.as<uint8_t>(), ga.used_glob, used_stride(Ps), g.n_ext, g.idx_pitch,
-                  ga.lvl1_pitch, ga.lvl2_gstride, Ks, c->G2, nblocks};
-    if (nch > 1) {
-        aa.idx16 = c->d_idx16.as<uint16_t>();
-        aa.dist = nch > 4 ? c->d_dist.as<float>() : nullptr;
-        aa.nch = nch;
-        while ((1 << aa.lg_nch) < nch) ++aa.lg_nch;
-    }
-    if (pass.ordered) {  // (K <= 256: no chunks, no 16-bit lists; the map is on the device: ensure_dither_map)
-        if (nch > 1 || dither || !c->d_dmap.p) return fail(c, HQ_ERR_STATE, "ordered pass: K > 256 or no map");
-        const int mw = c->dmap.empty() ? 16 : c->dmap_w, mh = c->dmap.empty() ? 16 : c->dmap_h;
-        aa.map = c->d_dmap.as<float>();
-        aa.mw_mask = (uint32_t)mw - 1u;
-        aa.mh_mask = (uint32_t)mh - 1u;
-        while ((1u << aa.lg_mw) < (uint32_t)mw) ++aa.lg_mw;
-        for (int ch = 0; ch < 3; ++ch) aa.amp[ch] = pass.amp[ch];
-        aa.W = (uint32_t)g.W;
-        aa.y0 = (uint32_t)g.e0;
-    }
-    if (n16) {  // one palette of K colours per workgroup (its table in LDS)
-        aa.l1n = c->d_l1n.as<uint16_t>();
-        aa.l2n = c->d_l2n.as<uint16_t>();
-        aa.kpal = nch * kMaxK;
-        aa.K = K;
-        // one resident round of 1024-thread workgroups over the P palettes, >= 4 pixels per thread
-        const int ngr = K <= 4096 ? (Pl + 1) / 2 : Pl;  // workgroup groups: palette pairs up to K = 4096
-        aa.nblocks = (int)std::max<int64_t>(
-            1, std::min<int64_t>(std::max(1, c->num_cu / ngr), (g.n_ext + 4095) / 4096));
-    }
-    const float inv[3] = {1.0f / c->illum[0], 1.0f / c->illum[1], 1.0f / c->illum[2]};
+    if (int rc = enqueue_grid(c, ga, c->G2 > 0 && !dither, n16, K, Pl, Ps, Pair(p0), pr)) return rc;
+    AssignArgs aa = assign_args(c, ga, Ps, Ks, pass.ordered);
+    if (pass.ordered)
+        if (int rc = add_ordered(c, pass, aa)) return rc;
+    if (n16) add_lists16(c, K, Pl, aa);
     const bool fast = cost_fast(c);
-    int rows, tw;
-    fast_tile_shape(c, &rows, &tw);
-    const bool masked = fast && c->mask_on;  // the masked instances over the live-tile list
+    const FastGrid f = fast_grid(c);
     CostArgs ca{};
-    if (fast) {
-        ca.idx = nch > 1 ? c->d_idx16.as<uint8_t>() : c->d_idx.as<uint8_t>();
-        ca.opp16 = c->d_opp16.as<uint4>() + (int64_t)so * kMaxK;
-        ca.taps = c->d_taps.p;
-        ca.vfrag16 = c->d_vfrag16.as<uint4>();
-        ca.vfrag16p = c->d_vfrag16p.as<uint4>();
-        ca.labL = c->d_labL.as<float>();
-        ca.labA = c->d_labA.as<float>();
-        ca.labB = c->d_labB.as<float>();
-        ca.acc = ga.acc_zero;
-        ca.acc_P = Pl;
-        ca.acc_p0 = 0;
-        ca.g = g;
-        ca.K = K;
-        fast_tile_dims(g.W, g.r1 - fast_grid_row0(c->de_type, g.r0, rows), rows, tw, &ca.tiles_x, &ca.ntiles);
-        opp2xyz_over_illum(inv, ca.m_lab);
-        ca.pix_err = c->pixel_err ? c->d_pixerr.as<float>() : nullptr;
-        ca.pix_pitch = (int64_t)g.W * (g.r1 - g.r0);
-        if (masked) {
-            if (c->live_dirty || rows != c->live_rows || tw != c->live_tw ||
-                c->live_skip != (c->mask_skip && !c->pixel_err))
-                return fail(c, HQ_ERR_STATE, "pixel mask: the live-tile list is not that of this launch");
-            ca.mask = c->d_mask.as<uint8_t>();
-            ca.live = c->d_live.as<int32_t>();
-            ca.nlive = c->n_live;
-        }
-    }
-    if (pass.kind != Pass::AssignOnly) {  // hq_mask_info: what the fast cost pass launches
-        c->tiles_all = fast ? ca.ntiles : 0;
-        c->tiles_run = masked ? ca.nlive : c->tiles_all;
-    }
-    HIP_TRY(c, timed_launch(pr, passign, [&] {
+    if (fast)
+        if (int rc = cost_args(c, ga, f, K, so, Pl, &ca)) return rc;
+    HIP_TRY(c, timed_launch(pr, dither ? kPDither : Pair(p0 + 1), [&] {
         return dither ? launch_dither(DitherArgs{aa.R, aa.G, aa.B, ga.pal, aa.idx, ga.used_glob,
                                                  c->d_dcarry.as<float>(), g.idx_pitch, g.W, g.H, K,
                                                  c->dither_rows, pass.strength},
@@ -464,66 +533,34 @@ int hq::enqueue_core(hq_ctx* c, int P, int K, ProfRec& pr, Pass pass) {
                : pass.ordered ? launch_assign_ordered(aa, Ps, s)
                       : launch_assign(aa, Ps, s);
     }));
-    if (pass.kind != Pass::AssignOnly) {
-        if (masked) {
-            // no owned in-mask pixel: nothing to launch, the zeroed counters are the partial
-            if (ca.nlive > 0)
-                HIP_TRY(c, timed_launch(pr, pcost, [&] {
-                    return nch > 1 ? launch_cost_chunked_masked(ca, Pl, nch, c->de_type, c->trim && c->trim_ok, s)
-                                   : launch_cost_fast_masked(ca, Pl, c->de_type, c->trim && c->trim_ok, rows, tw,
-                                                             c->fast_hb, s);
-                }));
-        } else if (fast) {
-            HIP_TRY(c, timed_launch(pr, pcost, [&] {
-                return nch > 1 ? launch_cost_chunked(ca, Pl, nch, c->de_type, c->trim && c->trim_ok, s)
-                               : launch_cost_fast(ca, Pl, c->de_type, c->trim && c->trim_ok, rows, tw, c->fast_hb,
-                                                  s);
-            }));
-        } else {
-            int rc = nch > 1 ? enqueue_generic_cost(c, Pl, c->d_idx16.p, 2, nch * kMaxK, pr, pcost, lo)
-                             : enqueue_generic_cost(c, Pl, c->d_idx.p, 1, kMaxK, pr, pcost, lo);
-            if (rc) return rc;
-        }
+    if (costed)
+        if (int rc = enqueue_cost(c, ca, fast, f, lo, Pl, Pair(p0 + 2), pr)) return rc;
+    const FinalizeArgs fa{ga.acc_zero, ga.used_glob, used_stride(Ps), c->d_out.as<double>() + (int64_t)lo * (1 + K),
+                          Pl, K, nullptr, 8 * nch};
+    return end_pass(c, pass, fa, P, K, lo, Pl, Ps, pr);
+}
+
+namespace hq {
+
+int upload_and_prep(hq_ctx* c, const float* host, const void* dev, int P, int K) {
+    hipStream_t s = c->stream;
+    const int nch = c->nch_cur;
+    const size_t n_in = (size_t)P * (nch > 1 ? nch * kMaxK : K);
+    if (host) {
+        if (nch > 1) pack_chunks(host, P, K, nch, c->h_pal.as<float>());
+        else std::memcpy(c->h_pal.p, host, sizeof(float) * 4 * n_in);
+        HIP_TRY(c, hipMemcpyAsync(c->d_pal_in.p, c->h_pal.p, sizeof(float4) * n_in, hipMemcpyHostToDevice, s));
+    } else {
+        HIP_TRY(c, hipMemcpyAsync(c->d_pal_in.p, dev, sizeof(float4) * n_in, hipMemcpyDeviceToDevice, s));
     }
-    if (!pass.side()) {
-        if (pass.kind != Pass::Fold) {  // (a folding search's accept step reads the sums itself)
-            FinalizeArgs fa{ga.acc_zero, ga.used_glob, used_stride(Ps),
-                            c->d_out.as<double>() + (int64_t)lo * (1 + K), Pl, K, nullptr, 8 * nch};
-            HIP_TRY(c, timed_launch(pr, pfinalize, [&] { return launch_finalize(fa, Pl, s); }));
-        }
-        if (c->comm)
-            if (int rc = enqueue_collective(c, pass.kind == Pass::Fold, P, K, lo, Pl, Ps, pr)) return rc;
-    }
-    note_evaluated(c, P, K, nch, lo, Pl);
+    if (nch == 1 && K > kMaxK) return HQ_OK;
+    HIP_TRY(c, launch_prep_palette(prep_args(c, nch > 1 ? kMaxK : K), P * nch, s));
     return HQ_OK;
 }
+
+}  // namespace hq
 
 namespace {
-
-// Host-driven evaluation of the P palettes in h_pal: upload, prep, enqueue_core,
-// read back d_out into h_out.
-int enqueue_eval(hq_ctx* c, int P, int K) {
-    hipStream_t s = c->stream;
-    const size_t n_in = c->nch_cur > 1 ? (size_t)P * c->nch_cur * kMaxK : (size_t)P * K;
-    HIP_TRY(c, hipMemcpyAsync(c->d_pal_in.p, c->h_pal.p, sizeof(float4) * n_in, hipMemcpyHostToDevice, s));
-    ProfRec pr = prof_begin(c);
-    int rc;
-    if (c->nch_cur > 1) {  // h_pal holds P nch sub-palettes of 256 (pack_chunks)
-        HIP_TRY(c, launch_prep_palette(prep_args(c, kMaxK), P * c->nch_cur, s));
-        rc = enqueue_core(c, P, K, pr);
-    } else if (K > kMaxK) {
-        rc = enqueue_wide(c, P, K, pr);  // (builds no grid)
-    } else {
-        HIP_TRY(c, launch_prep_palette(prep_args(c, K), P, s));
-        rc = enqueue_core(c, P, K, pr);
-    }
-    if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->h_out.p, c->d_out.p, sizeof(double) * (size_t)P * (1 + K),
-                              hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    prof_accumulate(c, pr);
-    return HQ_OK;
-}
 
 int check_eval_args(hq_ctx* c, const float* palettes, int P, int K) {
     if (!c) return HQ_ERR_ARG;
@@ -550,62 +587,101 @@ bool palette_fits_fast(const float* pal, int P, int K) {
     return true;
 }
 
-int eval_partial_into_hout(hq_ctx* c, const float* palettes, int P, int K) {
-    int rc = check_eval_args(c, palettes, P, K);
-    if (rc) return rc;
-    if ((rc = mask_scope(c))) return rc;
-    if ((rc = bind(c))) return rc;
+// One host-driven pass, after the caller's last refusal: upload, prep, `pass` (K > 256
+// unchunked: enqueue_wide), d_out back into h_out ([P][1 + K]).  The record is dropped before
+// the first buffer is grown or written and committed when the pass has come back.
+// 256 < K <= 16384: chunks of 256 colours through the grid and assign, and the tiled cost
+// kernel up to 32 chunks.  Palettes outside the fast range (never a rendering's) take the
+// exhaustive K > 256 path instead, which keeps the reference's NaN semantics.
+int run_pass(hq_ctx* c, const float* palettes, int P, int K, const Pass& pass) {
+    if (int rc = bind(c)) return rc;
+    drop(c);
     const bool fits = palette_fits_fast(palettes, P, K);
-    // 256 < K <= 16384: chunks of 256 colours through the grid and assign, and the
-    // tiled cost kernel up to 32 chunks (the generic pair above).  Palettes outside
-    // the fast range (non-finite colours among
-    // them) take the exhaustive K > 256 path instead, which keeps the
-    // reference's NaN semantics across all K colours.
+    struct Reset {  // device-resident searches generate clamped palettes of their own chunk count
+        hq_ctx* c;
+        ~Reset() { c->pal_generic = false, c->nch_cur = 1; }
+    } reset{c};
     c->nch_cur = c->chunked && fits && c->G2 > 0 && K > kMaxK && K <= kMaxKChunked ? chunk_count(K) : 1;
     c->pal_generic = !fits;  // (before ensure_population: it sizes the generic path's scratch)
-    if (!(rc = ensure_population(c, P, K))) {
-        if (c->nch_cur > 1) pack_chunks(palettes, P, K, c->nch_cur, c->h_pal.as<float>());
-        else std::memcpy(c->h_pal.p, palettes, sizeof(float) * 4 * (size_t)P * K);
-        rc = enqueue_eval(c, P, K);
-    }
-    c->pal_generic = false;  // device-resident searches generate clamped palettes
-    c->nch_cur = 1;
-    c->sums_ok = c->idx_ok = rc == HQ_OK;
-    c->err_ok = c->pixerr_ok = c->sums_ok && c->pixel_err;
-    return rc;
+    if (int rc = ensure_population(c, P, K)) return rc;
+    if (pass.kind == Pass::Dither) HIP_TRY(c, c->d_dcarry.ensure(sizeof(float) * (size_t)P * 3 * c->g.W));
+    hipStream_t s = c->stream;
+    ProfRec pr = prof_begin(c);
+    int rc = upload_and_prep(c, palettes, nullptr, P, K);
+    if (!rc) rc = K > kMaxK && c->nch_cur == 1 ? enqueue_wide(c, P, K, pr) : enqueue_core(c, P, K, pr, pass);
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->h_out.p, c->d_out.p, sizeof(double) * (size_t)P * (1 + K), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    prof_accumulate(c, pr);
+    const bool render = pass.kind == Pass::Dither || pass.ordered;
+    commit(c, resident_of(c, render ? Resident::Render : Resident::Eval, P, K));
+    return HQ_OK;
 }
 
-// The index images of the last evaluation (K colours): their base and element width.
-const void* index_images(const hq_ctx* c, int K, int* idx_bytes) {
-    *idx_bytes = c->last_nch > 1 ? 2 : K > kMaxK ? 4 : 1;
+int eval_partial_into_hout(hq_ctx* c, const float* palettes, int P, int K) {
+    if (int rc = check_eval_args(c, palettes, P, K)) return rc;
+    if (int rc = mask_scope(c)) return rc;
+    return run_pass(c, palettes, P, K, Pass{});
+}
+
+// The index images of a pass over K colours in nch chunks: their base and element width.
+const void* index_images(const hq_ctx* c, int K, int nch, int* idx_bytes) {
+    *idx_bytes = nch > 1 ? 2 : K > kMaxK ? 4 : 1;
     return *idx_bytes == 2 ? c->d_idx16.p : *idx_bytes == 4 ? c->d_idx32.p : c->d_idx.p;
 }
 
 // P, K are the last evaluation's (by hq_eval_population[_partial], on this image,
 // no search run since) and every palette's index image is on this device.
 int check_last_population(hq_ctx* c, int P, int K) {
-    if (!c->have_image || !c->sums_ok)
+    const Resident& r = c->res;
+    if (!c->have_image || !r.sums_ok())
         return fail(c, HQ_ERR_STATE, "no population evaluated by hq_eval_population[_partial] on this image "
                                      "since the last search run");
-    if (P != c->last_P || K != c->K_cur)
-        return fail(c, HQ_ERR_STATE, "P=%d, K=%d: the last evaluation had P=%d, K=%d", P, K, c->last_P, c->K_cur);
-    if (c->slice_n != c->last_P || c->slice_ranks > 1 || (c->psplit && c->comm))
-        return fail(c, HQ_ERR_UNSUPPORTED, "palette slice: this device holds %d of the %d index images",
-                    c->slice_n, c->last_P);
+    if (P != r.P || K != r.K)
+        return fail(c, HQ_ERR_STATE, "P=%d, K=%d: the last evaluation had P=%d, K=%d", P, K, r.P, r.K);
+    if (r.n != r.P || c->slice_ranks > 1 || (c->psplit && c->comm))
+        return fail(c, HQ_ERR_UNSUPPORTED, "palette slice: this device holds %d of the %d index images", r.n, r.P);
     return HQ_OK;
 }
 
 // hq_get_indices[32], hq_get_pixel_errors: the index images on the device are those of an
-// evaluation on the image and filters in force (idx_ok: hq_runtime.h), and palette p of
+// evaluation on the image and filters in force (Resident::idx_ok), and palette p of
 // that population is on this device: *local, its place among them.
 int check_local_palette(hq_ctx* c, int p, int* local) {
-    if (!c->have_image || !c->idx_ok)
+    const Resident& r = c->res;
+    if (!c->have_image || !r.idx_ok())
         return fail(c, HQ_ERR_STATE, "no population evaluated on the current image and filters (the image or the "
                                      "filters were set, or an evaluation failed, since the last one)");
-    if (p < 0 || p >= c->last_P) return fail(c, HQ_ERR_ARG, "palette %d not in last population", p);
-    if (p < c->slice_lo || p >= c->slice_lo + c->slice_n)
+    if (p < 0 || p >= r.P) return fail(c, HQ_ERR_ARG, "palette %d not in last population", p);
+    if (p < r.lo || p >= r.lo + r.n)
         return fail(c, HQ_ERR_ARG, "palette %d was evaluated on another rank (palette split)", p);
-    *local = p - c->slice_lo;
+    *local = p - r.lo;
+    return HQ_OK;
+}
+
+const char* const kNoExactSums = "planar image with a pixel outside [0, 1] or not finite: no exact sums";
+int64_t sums_den(const hq_ctx* c) { return sums_u8(c) ? 255 : (int64_t)1 << 32; }
+
+// One call of a table kernel: `table` (n 64-bit words, then the kernel's flag) zeroed; launch(),
+// which builds its arguments now that the table is in place; table and flag back into h [and
+// extra_src into extra_dst] after one synchronise.  A set flag refuses with `bad` (null: never).
+template <typename Launch>
+int run_table_kernel(hq_ctx* c, DevBuf& table, size_t n, Pair pair, const char* bad, std::vector<int64_t>& h,
+                     Launch&& launch, void* extra_dst = nullptr, const DevBuf* extra_src = nullptr,
+                     size_t extra_bytes = 0) {
+    if (int rc = bind(c)) return rc;
+    hipStream_t s = c->stream;
+    const size_t bytes = sizeof(int64_t) * (n + 1);
+    HIP_TRY(c, table.ensure(bytes));
+    HIP_TRY(c, hipMemsetAsync(table.p, 0, bytes, s));
+    ProfRec pr = prof_begin(c);
+    HIP_TRY(c, timed_launch(pr, pair, launch));
+    h.resize(n + 1);
+    HIP_TRY(c, hipMemcpyAsync(h.data(), table.p, bytes, hipMemcpyDeviceToHost, s));
+    if (extra_dst) HIP_TRY(c, hipMemcpyAsync(extra_dst, extra_src->p, extra_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    prof_accumulate(c, pr);
+    if (bad && h[n] != 0) return fail(c, HQ_ERR_UNSUPPORTED, "%s", bad);
     return HQ_OK;
 }
 
@@ -613,35 +689,24 @@ int check_local_palette(hq_ctx* c, int p, int* local) {
 // HQ_OK.  The image buffers are read, a table of its own is written: the index
 // images, the counter sets and d_sums stay what they are.
 int color_histogram(hq_ctx* c, int bits, int64_t* out, int64_t* den) {
-    int rc = bind(c);
-    if (rc) return rc;
-    hipStream_t s = c->stream;
-    const Geom& g = c->g;
     const size_t n4 = (size_t)4 << (3 * bits);
-    HIP_TRY(c, c->d_hist.ensure(sizeof(int64_t) * (n4 + 1)));
-    HIP_TRY(c, hipMemsetAsync(c->d_hist.p, 0, sizeof(int64_t) * (n4 + 1), s));
-    const bool u8 = sums_u8(c);
-    HistArgs ha{};
-    ha.R = c->d_R.as<float>();
-    ha.G = c->d_G.as<float>();
-    ha.B = c->d_B.as<float>();
-    ha.rgbx = u8 ? c->d_rgbx.as<uint32_t>() : nullptr;
-    ha.cells = c->d_hist.as<unsigned long long>();
-    ha.bad = reinterpret_cast<int*>(c->d_hist.as<int64_t>() + n4);
-    ha.q0 = (uint32_t)((int64_t)(g.r0 - g.e0) * g.W);
-    ha.q1 = ha.q0 + (uint32_t)((int64_t)g.W * (g.r1 - g.r0));
-    ha.bits = bits;
-    ha.mask = c->mask_on ? c->d_maskq.as<uint8_t>() : nullptr;
-    ProfRec pr = prof_begin(c);
-    HIP_TRY(c, timed_launch(pr, kPHist, [&] { return launch_color_histogram(ha, c->num_cu, s); }));
-    std::vector<int64_t> h(n4 + 1);
-    HIP_TRY(c, hipMemcpyAsync(h.data(), c->d_hist.p, sizeof(int64_t) * (n4 + 1), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    prof_accumulate(c, pr);
-    if (h[n4] != 0)
-        return fail(c, HQ_ERR_UNSUPPORTED, "planar image with a pixel outside [0, 1] or not finite: no exact sums");
+    std::vector<int64_t> h;
+    int rc = run_table_kernel(c, c->d_hist, n4, kPHist, kNoExactSums, h, [&] {
+        HistArgs ha{};
+        ha.R = c->d_R.as<float>();
+        ha.G = c->d_G.as<float>();
+        ha.B = c->d_B.as<float>();
+        ha.rgbx = sums_u8(c) ? c->d_rgbx.as<uint32_t>() : nullptr;
+        ha.cells = c->d_hist.as<unsigned long long>();
+        ha.bad = reinterpret_cast<int*>(c->d_hist.as<int64_t>() + n4);
+        owned_range(c->g, &ha.q0, &ha.q1);
+        ha.bits = bits;
+        ha.mask = c->mask_on ? c->d_maskq.as<uint8_t>() : nullptr;
+        return launch_color_histogram(ha, c->num_cu, c->stream);
+    });
+    if (rc) return rc;
     std::memcpy(out, h.data(), sizeof(int64_t) * n4);
-    *den = u8 ? 255 : (int64_t)1 << 32;
+    *den = sums_den(c);
     return HQ_OK;
 }
 
@@ -733,22 +798,20 @@ void pack_chunks(const float* pal, int P, int K, int nch, float* out) {
         }
 }
 
-// The sums kernel's arguments for the index images of the last evaluation (or
-// assign-only pass) of P palettes of K colours: the owned rows, as
-// hq_get_indices[32] reads them, into d_sums ([P][K][4], then the range flag).
-ClusterArgs cluster_args(hq_ctx* c, int P, int K, int* idx_bytes) {
-    const Geom& g = c->g;
+// The sums kernel's arguments for the index images of a pass over P palettes of K
+// colours in nch chunks (the last evaluation's, or an assign-only pass's): the owned
+// rows, as hq_get_indices[32] reads them, into d_sums ([P][K][4], then the range flag).
+ClusterArgs cluster_args(hq_ctx* c, int P, int K, int nch, int* idx_bytes) {
     ClusterArgs ca{};
-    ca.idx = index_images(c, K, idx_bytes);
+    ca.idx = index_images(c, K, nch, idx_bytes);
     ca.R = c->d_R.as<float>();
     ca.G = c->d_G.as<float>();
     ca.B = c->d_B.as<float>();
     ca.rgbx = sums_u8(c) ? c->d_rgbx.as<uint32_t>() : nullptr;
     ca.sums = c->d_sums.as<unsigned long long>();
     ca.bad = reinterpret_cast<int*>(c->d_sums.as<int64_t>() + (size_t)P * K * 4);
-    ca.idx_pitch = g.idx_pitch;
-    ca.q0 = (uint32_t)((int64_t)(g.r0 - g.e0) * g.W);
-    ca.q1 = ca.q0 + (uint32_t)((int64_t)g.W * (g.r1 - g.r0));
+    ca.idx_pitch = c->g.idx_pitch;
+    owned_range(c->g, &ca.q0, &ca.q1);
     ca.P = P;
     ca.K = K;
     ca.mask = c->mask_on ? c->d_maskq.as<uint8_t>() : nullptr;
@@ -757,35 +820,26 @@ ClusterArgs cluster_args(hq_ctx* c, int P, int K, int* idx_bytes) {
 
 // hq_cluster_sums into `out` ([P][K][4]); nothing is written unless HQ_OK.
 int cluster_sums(hq_ctx* c, int P, int K, int64_t* out, int64_t* den) {
-    int rc = check_last_population(c, P, K);
-    if (rc) return rc;
-    if ((rc = bind(c))) return rc;
-    hipStream_t s = c->stream;
+    if (int rc = check_last_population(c, P, K)) return rc;
     const size_t n4 = (size_t)P * K * 4;
-    HIP_TRY(c, c->d_sums.ensure(sizeof(int64_t) * (n4 + 1)));
-    HIP_TRY(c, hipMemsetAsync(c->d_sums.p, 0, sizeof(int64_t) * (n4 + 1), s));
-    int idx_bytes = 1;
-    const ClusterArgs ca = cluster_args(c, P, K, &idx_bytes);
-    const bool u8 = sums_u8(c);
-    ProfRec pr = prof_begin(c);
-    HIP_TRY(c, timed_launch(pr, kPSums, [&] { return launch_cluster_sums(ca, idx_bytes, c->num_cu, s); }));
-    std::vector<int64_t> h(n4 + 1);
-    HIP_TRY(c, hipMemcpyAsync(h.data(), c->d_sums.p, sizeof(int64_t) * (n4 + 1), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    prof_accumulate(c, pr);
-    if (h[n4] != 0)
-        return fail(c, HQ_ERR_UNSUPPORTED, "planar image with a pixel outside [0, 1] or not finite: no exact sums");
+    std::vector<int64_t> h;
+    int rc = run_table_kernel(c, c->d_sums, n4, kPSums, kNoExactSums, h, [&] {
+        int idx_bytes = 1;
+        const ClusterArgs ca = cluster_args(c, P, K, c->res.nch, &idx_bytes);
+        return launch_cluster_sums(ca, idx_bytes, c->num_cu, c->stream);
+    });
+    if (rc) return rc;
     std::memcpy(out, h.data(), sizeof(int64_t) * n4);
-    *den = u8 ? 255 : (int64_t)1 << 32;
+    *den = sums_den(c);
     return HQ_OK;
 }
 
 // The error kernel's arguments for the index images, the error image and the
-// prepared palettes of the last evaluation of P palettes of K colours, into
+// prepared palettes of a pass over P palettes of K colours in nch chunks, into
 // d_errstat ([P][K][4], then the flag) and d_worst ([P][K]).
-ClusterErrArgs cluster_err_args(hq_ctx* c, int P, int K, int* idx_bytes) {
+ClusterErrArgs cluster_err_args(hq_ctx* c, int P, int K, int nch, int* idx_bytes) {
     const Geom& g = c->g;
-    const ClusterArgs ca = cluster_args(c, P, K, idx_bytes);
+    const ClusterArgs ca = cluster_args(c, P, K, nch, idx_bytes);
     ClusterErrArgs ea{};
     ea.idx = ca.idx;
     ea.R = ca.R;
@@ -798,9 +852,9 @@ ClusterErrArgs cluster_err_args(hq_ctx* c, int P, int K, int* idx_bytes) {
     ea.worst = c->d_worst.as<float4>();
     ea.bad = reinterpret_cast<int*>(c->d_errstat.as<int64_t>() + (size_t)P * K * 4);
     ea.idx_pitch = g.idx_pitch;
-    ea.err_pitch = (int64_t)g.W * (g.r1 - g.r0);
+    ea.err_pitch = n_own(g);
     // chunked palettes: a palette's nch sub-palettes of 256 lie back to back, colour k at k
-    ea.pal_pitch = c->last_nch > 1 ? (int64_t)c->last_nch * kMaxK : std::max(K, kMaxK);
+    ea.pal_pitch = nch > 1 ? (int64_t)nch * kMaxK : std::max(K, kMaxK);
     ea.q0 = ca.q0;
     ea.q1 = ca.q1;
     ea.pos0 = (uint32_t)((int64_t)g.e0 * g.W);
@@ -814,42 +868,55 @@ ClusterErrArgs cluster_err_args(hq_ctx* c, int P, int K, int* idx_bytes) {
 // flag says (the pixels it stands for are left out either way).  The index
 // images, the error image, the counter sets and d_sums stay what they are.
 int cluster_errors(hq_ctx* c, int P, int K, int64_t* err, float* worst, bool ignore_bad) {
-    int rc = check_last_population(c, P, K);
-    if (rc) return rc;
+    if (int rc = check_last_population(c, P, K)) return rc;
     const Geom& g = c->g;
-    const int64_t n_own = (int64_t)g.W * (g.r1 - g.r0);
-    if (!c->err_ok || c->d_pixerr.bytes < sizeof(float) * (size_t)P * (size_t)n_own)
+    if (!c->res.err_ok() || c->d_pixerr.bytes < sizeof(float) * (size_t)P * (size_t)n_own(g))
         return fail(c, HQ_ERR_STATE, "option pixel_err was off at the last evaluation: no error image");
     if ((int64_t)g.W * g.H >= ((int64_t)1 << 32))
         return fail(c, HQ_ERR_UNSUPPORTED, "image of 2^32 pixels or more: a position does not fit 32 bits");
-    if ((rc = bind(c))) return rc;
-    hipStream_t s = c->stream;
+    if (int rc = bind(c)) return rc;
     const size_t n4 = (size_t)P * K * 4;
-    HIP_TRY(c, c->d_errstat.ensure(sizeof(int64_t) * (n4 + 1)));
     HIP_TRY(c, c->d_worst.ensure(sizeof(float) * n4));
-    HIP_TRY(c, hipMemsetAsync(c->d_errstat.p, 0, sizeof(int64_t) * (n4 + 1), s));
-    int idx_bytes = 1;
-    const ClusterErrArgs ea = cluster_err_args(c, P, K, &idx_bytes);
-    ProfRec pr = prof_begin(c);
-    HIP_TRY(c, timed_launch(pr, kPErrsum, [&] { return launch_cluster_errors(ea, idx_bytes, c->num_cu, s); }));
-    std::vector<uint64_t> h(n4 + 1);
+    std::vector<int64_t> h;
     std::vector<float> hw(n4);
-    HIP_TRY(c, hipMemcpyAsync(h.data(), c->d_errstat.p, sizeof(int64_t) * (n4 + 1), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(hw.data(), c->d_worst.p, sizeof(float) * n4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    prof_accumulate(c, pr);
-    if (h[n4] != 0 && !ignore_bad)
-        return fail(c, HQ_ERR_UNSUPPORTED, "a pixel's dE is not a finite number below 2^20 (dE94's NaN, a non-finite "
-                                           "colour or LabRef): no exact error sums");
+    const char* bad = ignore_bad ? nullptr
+                                 : "a pixel's dE is not a finite number below 2^20 (dE94's NaN, a non-finite "
+                                   "colour or LabRef): no exact error sums";
+    int rc = run_table_kernel(c, c->d_errstat, n4, kPErrsum, bad, h, [&] {
+        int idx_bytes = 1;
+        const ClusterErrArgs ea = cluster_err_args(c, P, K, c->res.nch, &idx_bytes);
+        return launch_cluster_errors(ea, idx_bytes, c->num_cu, c->stream);
+    }, hw.data(), &c->d_worst, sizeof(float) * n4);
+    if (rc) return rc;
     for (size_t i = 0; i < n4; i += 4) {
-        const uint64_t key = h[i + 2];
-        err[i] = (int64_t)h[i];
-        err[i + 1] = (int64_t)h[i + 1];
+        const uint64_t key = (uint64_t)h[i + 2];
+        err[i] = h[i];
+        err[i + 1] = h[i + 1];
         err[i + 2] = (int64_t)(key >> 32);
         err[i + 3] = key ? (int64_t)(0xffffffffu - (uint32_t)key) : -1;
     }
     std::memcpy(worst, hw.data(), sizeof(float) * n4);
     return HQ_OK;
+}
+
+// The k-means move on the last evaluation's index images: its exact sums, then the centroids
+// into the palettes in place.  The repair move: its error statistics (ignore_bad: pixels
+// with no usable dE left out), then the rule; moved (may be null): colours moved per palette.
+int kmeans_move(hq_ctx* c, int P, int K, float* pal) {
+    std::vector<int64_t> sums((size_t)P * K * 4);
+    int64_t den = 0;
+    int r = cluster_sums(c, P, K, sums.data(), &den);
+    if (!r && (r = hq_centroids_from_sums(sums.data(), den, P, K, pal)))
+        return fail(c, r, "hq_centroids_from_sums failed");
+    return r;
+}
+int repair_move(hq_ctx* c, int P, int K, int max_moves, bool ignore_bad, float* pal, int* moved) {
+    std::vector<int64_t> err((size_t)P * K * 4);
+    std::vector<float> worst(err.size());
+    int r = cluster_errors(c, P, K, err.data(), worst.data(), ignore_bad);
+    if (!r && (r = hq_reseed_unused(err.data(), worst.data(), P, K, max_moves, pal, moved)))
+        return fail(c, r, "hq_reseed_unused failed");
+    return r;
 }
 
 // The planar form's sums need every owned pixel finite and in [0, 1]: a property
@@ -865,8 +932,7 @@ int planar_in_range(hq_ctx* c) {
         HIP_TRY(c, c->d_sums.ensure(sizeof(int64_t) * (4 + 1)));
         HIP_TRY(c, hipMemsetAsync(c->d_sums.p, 0, sizeof(int64_t) * (4 + 1), st));
         int idx_bytes = 1;
-        ClusterArgs ca = cluster_args(c, 1, 1, &idx_bytes);
-        ca.idx = c->d_idx.p;  // (the u8 image, whatever the last evaluation's index width)
+        ClusterArgs ca = cluster_args(c, 1, 1, 1, &idx_bytes);  // (the u8 image, d_idx)
         ca.mask = nullptr;    // (the flag looks at every owned pixel with or without a mask)
         HIP_TRY(c, launch_cluster_sums(ca, 1, c->num_cu, st));
         int bad = 1;
@@ -874,6 +940,13 @@ int planar_in_range(hq_ctx* c) {
         HIP_TRY(c, hipStreamSynchronize(st));
         c->planar_ok = bad == 0;
     }
+    return HQ_OK;
+}
+
+int require_unit_range_image(hq_ctx* c, const char* subject, const char* what) {
+    if (int rc = planar_in_range(c)) return rc;
+    if (!c->planar_ok)
+        return fail(c, HQ_ERR_UNSUPPORTED, "%s with a pixel outside [0, 1] or not finite: %s", subject, what);
     return HQ_OK;
 }
 
@@ -892,12 +965,7 @@ int ordered_scope(hq_ctx* c, int K) {
     if (K > kMaxK)
         return fail(c, HQ_ERR_UNSUPPORTED, "K=%d > %d: ordered dithering is built into the 8-bit argmin only", K, kMaxK);
     if (c->psplit || c->slice_ranks > 1) return fail(c, HQ_ERR_UNSUPPORTED, "ordered dithering on a palette slice");
-    if (c->have_image && !c->img_u8) {
-        if (int rc = planar_in_range(c)) return rc;
-        if (!c->planar_ok)
-            return fail(c, HQ_ERR_UNSUPPORTED, "image with a pixel outside [0, 1] or not finite: no ordered dithering");
-    }
-    return HQ_OK;
+    return c->have_image && !c->img_u8 ? require_unit_range_image(c, "image", "no ordered dithering") : HQ_OK;
 }
 
 // The context's map on the device: the buffer once, its contents when the host map changed.
@@ -938,26 +1006,10 @@ int ordered_into_hout(hq_ctx* c, const float* palettes, int P, int K, const floa
         return fail(c, HQ_ERR_STATE, "sharded context without a communicator: use hq_ordered_population_partial");
     if ((rc = ordered_scope(c, K))) return rc;
     if ((rc = ensure_dither_map(c))) return rc;
-    c->nch_cur = 1;
-    c->pal_generic = false;
-    if ((rc = ensure_population(c, P, K))) return rc;
-    std::memcpy(c->h_pal.p, palettes, sizeof(float) * 4 * (size_t)P * K);
-    hipStream_t s = c->stream;
-    c->sums_ok = c->err_ok = false;  // (a k-means or repair move from a dithered assignment is neither)
-    c->idx_ok = c->pixerr_ok = false;  // (until the pass below has come back)
-    HIP_TRY(c, hipMemcpyAsync(c->d_pal_in.p, c->h_pal.p, sizeof(float4) * (size_t)P * K, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, launch_prep_palette(prep_args(c, K), P, s));
-    ProfRec pr = prof_begin(c);
     Pass pass{};
     pass.ordered = true;
     for (int ch = 0; ch < 3; ++ch) pass.amp[ch] = amp[ch];
-    if ((rc = enqueue_core(c, P, K, pr, pass))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->h_out.p, c->d_out.p, sizeof(double) * (size_t)P * (1 + K), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    prof_accumulate(c, pr);
-    c->idx_ok = true;  // the getters answer for the ordered rendering
-    c->pixerr_ok = c->pixel_err != 0;
-    return HQ_OK;
+    return run_pass(c, palettes, P, K, pass);  // (the getters then answer for the ordered rendering)
 }
 
 }  // namespace
@@ -1034,31 +1086,11 @@ int hq_dither_population(hq_ctx* c, const float* palettes, int P, int K, float s
                                            "8-bit indices", K, kMaxK);
     if (!population_in_range(palettes, P, K))
         return fail(c, HQ_ERR_ARG, "palette with a channel that is not finite or outside [0, 1]");
-    if ((rc = bind(c))) return rc;
     // the errors stay bounded (|e| <= 1) for pixels in [0, 1]: a property of the image, established
     // once per image as the hybrid search's is (the packed 8-bit copy exists only for k/255 images)
-    if (!c->img_u8) {
-        if ((rc = planar_in_range(c))) return rc;
-        if (!c->planar_ok)
-            return fail(c, HQ_ERR_UNSUPPORTED, "image with a pixel outside [0, 1] or not finite: no error diffusion");
-    }
-    c->nch_cur = 1;
-    c->pal_generic = false;
-    if ((rc = ensure_population(c, P, K))) return rc;
-    HIP_TRY(c, c->d_dcarry.ensure(sizeof(float) * (size_t)P * 3 * c->g.W));
-    std::memcpy(c->h_pal.p, palettes, sizeof(float) * 4 * (size_t)P * K);
-    hipStream_t s = c->stream;
-    c->sums_ok = c->err_ok = false;  // (a k-means or repair move from a dithered assignment is neither)
-    c->idx_ok = c->pixerr_ok = false;  // (until the dithered pass below has come back)
-    HIP_TRY(c, hipMemcpyAsync(c->d_pal_in.p, c->h_pal.p, sizeof(float4) * (size_t)P * K, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, launch_prep_palette(prep_args(c, K), P, s));
-    ProfRec pr = prof_begin(c);
-    if ((rc = enqueue_core(c, P, K, pr, Pass{Pass::Dither, strength}))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->h_out.p, c->d_out.p, sizeof(double) * (size_t)P * (1 + K), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    prof_accumulate(c, pr);
-    c->idx_ok = true;  // the getters answer for the dithered rendering
-    c->pixerr_ok = c->pixel_err != 0;
+    if (!c->img_u8 && (rc = require_unit_range_image(c, "image", "no error diffusion"))) return rc;
+    // (the getters then answer for the dithered rendering)
+    if ((rc = run_pass(c, palettes, P, K, Pass{Pass::Dither, strength}))) return rc;
     costs_from_hout(c, P, K, delta, costs, used);
     return HQ_OK;
 }
@@ -1067,13 +1099,11 @@ int hq_get_indices(hq_ctx* c, int p, uint8_t* idx) {
     if (!c || !idx) return HQ_ERR_ARG;
     int rc = check_local_palette(c, p, &p);
     if (rc) return rc;
-    if (c->K_cur > kMaxK)
-        return fail(c, HQ_ERR_STATE, "K=%d > 256: indices are 32-bit (hq_get_indices32)", c->K_cur);
+    if (c->res.K > kMaxK)
+        return fail(c, HQ_ERR_STATE, "K=%d > 256: indices are 32-bit (hq_get_indices32)", c->res.K);
     if ((rc = bind(c))) return rc;
     const Geom& g = c->g;
-    const int64_t off = (int64_t)(g.r0 - g.e0) * g.W;
-    const int64_t n_own = (int64_t)g.W * (g.r1 - g.r0);
-    HIP_TRY(c, hipMemcpy(idx, c->d_idx.as<uint8_t>() + (int64_t)p * g.idx_pitch + off, n_own,
+    HIP_TRY(c, hipMemcpy(idx, c->d_idx.as<uint8_t>() + (int64_t)p * g.idx_pitch + own_first(g), n_own(g),
                          hipMemcpyDeviceToHost));
     return HQ_OK;
 }
@@ -1084,15 +1114,14 @@ int hq_get_indices32(hq_ctx* c, int p, uint32_t* idx) {
     if (rc) return rc;
     if ((rc = bind(c))) return rc;
     const Geom& g = c->g;
-    const int64_t off = (int64_t)(g.r0 - g.e0) * g.W;
-    const int64_t n_own = (int64_t)g.W * (g.r1 - g.r0);
+    const int64_t n = n_own(g);
     // the image at its own width (u16: chunked palettes; u32: K > 16384), widened here
     int idx_bytes = 1;
-    const char* base = static_cast<const char*>(index_images(c, c->K_cur, &idx_bytes));
-    std::vector<unsigned char> raw((size_t)n_own * idx_bytes);
-    HIP_TRY(c, hipMemcpy(raw.data(), base + ((int64_t)p * g.idx_pitch + off) * idx_bytes, raw.size(),
+    const char* base = static_cast<const char*>(index_images(c, c->res.K, c->res.nch, &idx_bytes));
+    std::vector<unsigned char> raw((size_t)n * idx_bytes);
+    HIP_TRY(c, hipMemcpy(raw.data(), base + ((int64_t)p * g.idx_pitch + own_first(g)) * idx_bytes, raw.size(),
                          hipMemcpyDeviceToHost));
-    for (int64_t i = 0; i < n_own; ++i) {
+    for (int64_t i = 0; i < n; ++i) {
         uint32_t v = 0;
         std::memcpy(&v, raw.data() + i * idx_bytes, idx_bytes);  // (little-endian host)
         idx[i] = v;
@@ -1105,13 +1134,12 @@ int hq_get_pixel_errors(hq_ctx* c, int p, float* err) {
     if (!c->pixel_err) return fail(c, HQ_ERR_STATE, "option pixel_err is off");
     int rc = check_local_palette(c, p, &p);
     if (rc) return rc;
-    if (!c->pixerr_ok)
+    if (!c->res.pixerr_ok())
         return fail(c, HQ_ERR_STATE, "no error image of the last evaluation: pixel_err was set after it, or a search "
                                      "has run since");
     if ((rc = bind(c))) return rc;
-    const int64_t n_own = (int64_t)c->g.W * (c->g.r1 - c->g.r0);
-    HIP_TRY(c, hipMemcpy(err, c->d_pixerr.as<float>() + (int64_t)p * n_own, sizeof(float) * n_own,
-                         hipMemcpyDeviceToHost));
+    const int64_t n = n_own(c->g);
+    HIP_TRY(c, hipMemcpy(err, c->d_pixerr.as<float>() + (int64_t)p * n, sizeof(float) * n, hipMemcpyDeviceToHost));
     return HQ_OK;
 }
 
@@ -1132,7 +1160,7 @@ int hq_cluster_errors(hq_ctx* c, int P, int K, int64_t* err, float* worst_rgb) {
     if (!c) return HQ_ERR_ARG;
     if (!err || !worst_rgb || P < 1 || K < 1) return fail(c, HQ_ERR_ARG, "bad err / worst_rgb / P=%d / K=%d", P, K);
     if (c->mask_on) return fail(c, HQ_ERR_UNSUPPORTED, "hq_cluster_errors under a pixel mask (hq_set_mask)");
-    return cluster_errors(c, P, K, err, worst_rgb);
+    return cluster_errors(c, P, K, err, worst_rgb, false);
 }
 
 int hq_refine_population(hq_ctx* c, float* palettes, int P, int K, int steps, float delta, int keep_best,
@@ -1140,15 +1168,8 @@ int hq_refine_population(hq_ctx* c, float* palettes, int P, int K, int steps, fl
     int rc = check_improve_args(c, palettes, P, K, steps, costs, "hq_refine_population",
                                 ": add the shards' hq_cluster_sums yourself");
     if (rc) return rc;
-    std::vector<int64_t> sums((size_t)P * K * 4);
     return improve_population(c, palettes, P, K, steps, delta, keep_best, costs, used, trace,
-                              [&](float* cur, bool*) {
-        int64_t den = 0;
-        int r = cluster_sums(c, P, K, sums.data(), &den);
-        if (!r && (r = hq_centroids_from_sums(sums.data(), den, P, K, cur)))
-            return fail(c, r, "hq_centroids_from_sums failed");
-        return r;
-    });
+                              [&](float* cur, bool*) { return kmeans_move(c, P, K, cur); });
 }
 
 int hq_repair_population(hq_ctx* c, float* palettes, int P, int K, int steps, float delta, int max_moves,
@@ -1158,15 +1179,10 @@ int hq_repair_population(hq_ctx* c, float* palettes, int P, int K, int steps, fl
     if (rc) return rc;
     if (c->mask_on) return fail(c, HQ_ERR_UNSUPPORTED, "hq_repair_population under a pixel mask (hq_set_mask)");
     const PixelErrScope scope(c);  // the evaluations below store their error images
-    const size_t n4 = (size_t)P * K * 4;
-    std::vector<float> worst(n4);
-    std::vector<int64_t> err(n4);
     std::vector<int> moved(P);
     return improve_population(c, palettes, P, K, steps, delta, keep_best, costs, used, trace,
                               [&](float* cur, bool* changed) {
-        int r = cluster_errors(c, P, K, err.data(), worst.data());
-        if (!r && (r = hq_reseed_unused(err.data(), worst.data(), P, K, max_moves, cur, moved.data())))
-            return fail(c, r, "hq_reseed_unused failed");
+        const int r = repair_move(c, P, K, max_moves, false, cur, moved.data());
         // nothing left to repair: the remaining steps repeat this one
         *changed = !std::all_of(moved.begin(), moved.end(), [](int m) { return m == 0; });
         return r;

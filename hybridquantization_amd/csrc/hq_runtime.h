@@ -192,6 +192,29 @@ struct Pass {
     Pair pairs() const { return kind == AssignOnly ? kPLloydGrid : kind == CostOnly ? kPRepGrid : kPGrid; }
 };
 
+// ---- what the last pass left on the device ---------------------------------------
+// Whose index images the device holds -- an evaluation's (hq_eval_population[_partial]), a
+// rendering's (dithered or ordered) or a search's last candidates' -- of P palettes of K colours
+// in nch chunks, [lo, lo + n) of them here; whether that pass stored its error image ("pixel_err");
+// the tiles per palette its fast cost launch ran and has in all (hq_mask_info; 0: the generic cost).
+// It vouches for the index images, d_pixerr, the prepared palettes and the counter and used-bit
+// sets, and changes in drop() and commit() alone.
+struct Resident {
+    enum Owner { None, Eval, Render, Search } owner = None;
+    int P = 0, K = 0, nch = 1, lo = 0, n = 0;
+    bool err_image = false;  // (never a search's: its side passes store candidates' it then moves)
+    int64_t tiles_run = 0, tiles_all = 0;
+    // What may be read; by construction err_ok => sums_ok => idx_ok and pixerr_ok => idx_ok.
+    bool idx_ok() const { return owner != None; }              // hq_get_indices[32]
+    bool sums_ok() const { return owner == Eval; }             // hq_cluster_sums: no rendering's, no search's
+    bool err_ok() const { return sums_ok() && err_image; }     // hq_cluster_errors
+    bool pixerr_ok() const { return idx_ok() && err_image; }   // hq_get_pixel_errors
+    // The same images once a search has evaluated through hq_*_population: the indices alone.
+    Resident of_search() const {
+        return Resident{owner == None ? None : Search, P, K, nch, lo, n, false, tiles_run, tiles_all};
+    }
+};
+
 }  // namespace hq
 
 struct hq_ctx {
@@ -223,7 +246,7 @@ struct hq_ctx {
     hq::DevBuf d_labL, d_labA, d_labB;  // planar LabRef, owned rows, lab_pitch
 
     // population work buffers
-    int P_cap = 0, K_cur = 0;
+    hq::Resident res;  // what the last pass left in them (drop, commit)
     hq::DevBuf d_pal_in, d_pal, d_opp, d_opp16, d_dup, d_pflags, d_lvl1, d_lvl2, d_idx, d_used_mask,
         d_acc, d_out, d_gen_t;
     // d_acc: two sets of fixed-point dE sums [kAccSlots][P][4] u64 (acc_add), d_used_mask two
@@ -234,27 +257,13 @@ struct hq_ctx {
     hq::DevBuf d_idx16, d_dist;    // 256 < K <= 16384 (chunked): 16-bit index images, pass distances
     hq::DevBuf d_l1n, d_l2n;       // the native 16-bit candidate lists (hq_lists16.hip)
     int nch_cur = 1;           // chunks per palette of the population being enqueued (1: K <= 256)
-    int last_nch = 1;          // ... of the last evaluation (its index image: u16 when > 1)
     hq::PinBuf h_pal;          // pinned [P][K][4] float
     hq::PinBuf h_out;          // pinned [P][1+K] double
-    int last_P = 0;
-    // hq_cluster_sums: the index images on the device are those of a population of last_P x
-    // K_cur evaluated by hq_eval_population[_partial] (a search run or a new image unsets it)
-    bool sums_ok = false;
     hq::DevBuf d_sums;             // [P][K][4] int64 sums, then the planar form's range flag
     // hybrid iterations: every owned pixel of the planar image is finite and in [0, 1], the
     // condition of the planar form's sums (-1: not established yet for this image)
     int planar_ok = -1;
     hq::DevBuf d_hist;             // hq_color_histogram: [2^(3 bits)][4] int64 cells, then the range flag
-    // hq_cluster_errors: the error image on the device is that of the last evaluation (option
-    // "pixel_err" was on when hq_eval_population[_partial] enqueued it; read with sums_ok)
-    bool err_ok = false;
-    // hq_get_indices[32], hq_get_pixel_errors: the index images (idx_ok) and the error image
-    // (pixerr_ok: "pixel_err" was on when it was enqueued) on the device are those of the last
-    // evaluation -- plain, partial, dithered or a search's -- of last_P x K_cur on the current
-    // image and filters.  hq_set_image*, hq_set_filters and a failed evaluation unset both; a
-    // search unsets pixerr_ok (its side passes store error images of candidates it then moves).
-    bool idx_ok = false, pixerr_ok = false;
     hq::DevBuf d_errstat, d_worst; // [P][K][4] u64 statistics, then the flag; [P][K] float4 worst pixels
     hq::DevBuf d_dcarry;           // hq_dither_population: [P][3][W] errors of a strip's last row
     // ordered dithering: the threshold map (hq_set_dither_map; empty: the default, Bayer 16 x 16)
@@ -279,7 +288,6 @@ struct hq_ctx {
     bool live_dirty = true;
     int live_rows = 0, live_tw = 0, live_skip = -1;
     int mask_skip = 1;     // option "mask_skip": the fast cost pass launches live tiles only
-    int64_t tiles_run = 0, tiles_all = 0;  // hq_mask_info: the last evaluation's fast cost launch
 
     // options
     int G2 = 32;           // argmin grid resolution (0 = exhaustive)
@@ -304,7 +312,6 @@ struct hq_ctx {
                            // evaluates palettes [r P/N, (r+1) P/N), then one all-gather (option
                            // "palette_split"; SURVEY 8e's split of large populations)
     int slice_ranks = 1, slice_rank = 0;  // test only: the same slice without a communicator
-    int slice_lo = 0, slice_n = 0;        // the last evaluation's palettes held on this device
     int fold_blocks = 1, fold_block = 0;  // test only: rank blocks of the counters without a communicator
     int lists16 = 1;       // native 16-bit candidate lists: 1 = chunked palettes of 4 to 32 chunks, 2 = 2 .. 32
     int chunked = 1;       // 256 < K <= 16384: palettes as 256-colour chunks through the grid and
@@ -413,6 +420,14 @@ inline bool search_folds(const hq_ctx* c) { return !(c->comm && c->psplit); }
 // The sums form assign's own condition picks: the packed bytes (den 255), else
 // the planar floats (den 2^32).
 inline bool sums_u8(const hq_ctx* c) { return c->img_u8 && c->img_u8_path; }
+// The owned rows: their pixels, the first one's position among the extended rows' (the index
+// images' and planes' origin), and both ends as the 32-bit positions the table kernels take.
+inline int64_t n_own(const Geom& g) { return (int64_t)g.W * (g.r1 - g.r0); }
+inline int64_t own_first(const Geom& g) { return (int64_t)(g.r0 - g.e0) * g.W; }
+inline void owned_range(const Geom& g, uint32_t* q0, uint32_t* q1) {
+    *q0 = (uint32_t)own_first(g);
+    *q1 = *q0 + (uint32_t)n_own(g);
+}
 
 // hq_runtime.hip
 int bind(hq_ctx* c);
@@ -427,17 +442,30 @@ ProfRec prof_begin(hq_ctx* c);  // the context's events (profiling on) or none
 void prof_accumulate(hq_ctx* c, const ProfRec& pr);
 
 // hq_eval.hip
+// The record's two transitions: nothing is vouched for; the pass that has come back left `r`.
+// resident_of: what a pass of P x K leaves, from the state it was enqueued in (nch_cur,
+// pal_generic, options, mask): called before that state is reset.
+void drop(hq_ctx* c);
+void commit(hq_ctx* c, const Resident& r);
+Resident resident_of(hq_ctx* c, Resident::Owner owner, int P, int K);
+// (drops the record when, and only when, it reallocates a buffer the record vouches for)
 int ensure_population(hq_ctx* c, int P, int K);
+// P palettes of K colours ([P][4K]) into d_pal_in -- from the host (through h_pal; chunked:
+// pack_chunks' sub-palettes) or, host null, from the device -- and the palette prep (K > 256
+// unchunked: the upload alone, enqueue_wide preps).
+int upload_and_prep(hq_ctx* c, const float* host, const void* dev, int P, int K);
 PaletteArgs prep_args(hq_ctx* c, int K);
 uint64_t* acc_base(hq_ctx* c, int par, int P);
 uint32_t* used_base(hq_ctx* c, int par, int Ps);
 int enqueue_core(hq_ctx* c, int P, int K, ProfRec& pr, Pass pass = {});
 void pack_chunks(const float* pal, int P, int K, int nch, float* out);
-ClusterArgs cluster_args(hq_ctx* c, int P, int K, int* idx_bytes);
-ClusterErrArgs cluster_err_args(hq_ctx* c, int P, int K, int* idx_bytes);
-int cluster_sums(hq_ctx* c, int P, int K, int64_t* out, int64_t* den);
-int cluster_errors(hq_ctx* c, int P, int K, int64_t* err, float* worst, bool ignore_bad = false);
-int planar_in_range(hq_ctx* c);  // -> c->planar_ok
+ClusterArgs cluster_args(hq_ctx* c, int P, int K, int nch, int* idx_bytes);
+ClusterErrArgs cluster_err_args(hq_ctx* c, int P, int K, int nch, int* idx_bytes);
+int kmeans_move(hq_ctx* c, int P, int K, float* pal);  // the last evaluation's sums -> centroids, in place
+int repair_move(hq_ctx* c, int P, int K, int max_moves, bool ignore_bad, float* pal, int* moved);
+// planar_ok established (once per image), else HQ_ERR_UNSUPPORTED "<subject> with a pixel outside
+// [0, 1] or not finite: <what>"
+int require_unit_range_image(hq_ctx* c, const char* subject, const char* what);
 // ordered dithering: amp (may be null: HQ_ERR_ARG) finite and in [0, 1]; what a context must be
 // for it (K <= 256, no palette slice, the image in [0, 1]); the map on the device
 int check_ordered_amp(hq_ctx* c, const float* amp);

@@ -125,10 +125,9 @@ struct ScielabTmp {
 };
 template <typename MakeOpp>
 int scielab_filter(hq_ctx* c, const Geom& g, ScielabTmp& t, MakeOpp&& make_opp) {
-    const int64_t n_own = (int64_t)g.W * (g.r1 - g.r0);
     HIP_TRY(c, t.opp.ensure(sizeof(float4) * g.n_ext));
     HIP_TRY(c, t.tmp.ensure(sizeof(float4) * g.n_ext));
-    HIP_TRY(c, t.conv.ensure(sizeof(float4) * std::max<int64_t>(n_own, 1)));
+    HIP_TRY(c, t.conv.ensure(sizeof(float4) * std::max<int64_t>(n_own(g), 1)));
     t.k3h.assign(4 * c->taps, 0.f);
     t.ak3h.assign(4 * c->taps, 0.f);
     for (int i = 0; i < c->taps; ++i) { t.k3h[4 * i] = c->k3[i]; t.ak3h[4 * i] = c->absk3[i]; }
@@ -153,7 +152,6 @@ int scielab_filter(hq_ctx* c, const Geom& g, ScielabTmp& t, MakeOpp&& make_opp) 
 int compute_labref_device(hq_ctx* c) {
     // IM:100 RGBtoXYZ + IM:285-370 XYZtoScielab on the extended rows.
     const Geom& g = c->g;
-    const int64_t n_own = (int64_t)g.W * (g.r1 - g.r0);
     ScielabTmp t;
     int rc = scielab_filter(c, g, t, [&](float4* opp) {
         HIP_TRY(c, launch_labref_opp(c->d_R.as<float>(), c->d_G.as<float>(), c->d_B.as<float>(), opp, g.n_ext,
@@ -162,7 +160,7 @@ int compute_labref_device(hq_ctx* c) {
     });
     if (rc) return rc;
     HIP_TRY(c, launch_labref_lab(t.conv.as<float4>(), c->d_labL.as<float>(), c->d_labA.as<float>(),
-                                 c->d_labB.as<float>(), nullptr, g.W, n_own, g.lab_pitch, c->illum,
+                                 c->d_labB.as<float>(), nullptr, g.W, n_own(g), g.lab_pitch, c->illum,
                                  c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return HQ_OK;
@@ -173,10 +171,9 @@ int set_image_common(hq_ctx* c, const std::vector<float>& R, const std::vector<f
     const Geom& g = c->g;
     // c->g is the new image's already: nothing evaluated on the old one may be read at it
     c->have_image = false;  // (until every plane below is in place)
-    c->sums_ok = c->err_ok = c->idx_ok = c->pixerr_ok = false;
+    drop(c);
     c->mask_on = false;  // a mask belongs to an image
     c->live_dirty = true;
-    c->tiles_run = c->tiles_all = 0;
     const size_t plane = sizeof(float) * (size_t)round_up(g.n_ext, 4);
     HIP_TRY(c, c->d_R.ensure(plane));
     HIP_TRY(c, c->d_G.ensure(plane));
@@ -212,13 +209,13 @@ int set_image_common(hq_ctx* c, const std::vector<float>& R, const std::vector<f
     HIP_TRY(c, hipMemsetAsync(c->d_labA.p, 0, lplane, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->d_labB.p, 0, lplane, c->stream));
     if (lab4_full) {
-        const int64_t n_own = (int64_t)g.W * own;
+        const int64_t n = n_own(g);
         DevBuf tmp;
-        HIP_TRY(c, tmp.ensure(sizeof(float4) * n_own));
-        HIP_TRY(c, hipMemcpyAsync(tmp.p, lab4_full + (int64_t)g.r0 * g.W * 4, sizeof(float4) * n_own,
+        HIP_TRY(c, tmp.ensure(sizeof(float4) * n));
+        HIP_TRY(c, hipMemcpyAsync(tmp.p, lab4_full + (int64_t)g.r0 * g.W * 4, sizeof(float4) * n,
                                   hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, launch_lab_to_planar(tmp.as<float4>(), c->d_labL.as<float>(), c->d_labA.as<float>(),
-                                        c->d_labB.as<float>(), g.W, n_own, g.lab_pitch, c->stream));
+                                        c->d_labB.as<float>(), g.W, n, g.lab_pitch, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     } else {
         int rc = compute_labref_device(c);
@@ -329,7 +326,7 @@ int hq_set_filters(hq_ctx* c, int taps, const float* k1, const float* k2, const 
     // the halo depends on the filters: the image, and what was evaluated on it, go with them
     // (before the first early return below, which leaves the new half-width behind)
     c->have_image = false;
-    c->sums_ok = c->err_ok = c->idx_ok = c->pixerr_ok = false;
+    drop(c);
     c->taps = taps;
     c->half = (taps * 4) / 8;  // IM:408 filters4[0].length/8
     if (2 * c->half + 1 != taps)
@@ -467,9 +464,9 @@ int hq_mask_info(hq_ctx* c, int64_t* n_full, int64_t* n_owned, int64_t* tiles_ru
     if (!c) return HQ_ERR_ARG;
     const Geom& g = c->g;
     if (n_full) *n_full = c->mask_on ? c->mask_n_full : c->have_image ? (int64_t)g.W * g.H : 0;
-    if (n_owned) *n_owned = c->mask_on ? c->mask_n_own : c->have_image ? (int64_t)g.W * (g.r1 - g.r0) : 0;
-    if (tiles_run) *tiles_run = c->tiles_run;
-    if (tiles_all) *tiles_all = c->tiles_all;
+    if (n_owned) *n_owned = c->mask_on ? c->mask_n_own : c->have_image ? n_own(g) : 0;
+    if (tiles_run) *tiles_run = c->res.tiles_run;
+    if (tiles_all) *tiles_all = c->res.tiles_all;
     return HQ_OK;
 }
 
@@ -643,6 +640,17 @@ int hq_profile_get(hq_ctx* c, const char* kernel, double* total_ms, int64_t* lau
 
 int hq_set_option(hq_ctx* c, const char* name, int value) {
     if (!c || !name) return HQ_ERR_ARG;
+    static const struct { const char* name; int hq_ctx::*flag; } kOnOff[] = {
+        {"trim", &hq_ctx::trim}, {"sa_graph", &hq_ctx::sa_graph}, {"gen_vmfma", &hq_ctx::gen_vmfma},
+        {"gen_hmfma", &hq_ctx::gen_hmfma}, {"gen_vtile2", &hq_ctx::gen_vtile2}, {"gen_hrow4", &hq_ctx::gen_hrow4},
+        {"sa_device", &hq_ctx::sa_device}, {"shard_solo", &hq_ctx::shard_solo}, {"palette_split", &hq_ctx::psplit},
+        {"chunked", &hq_ctx::chunked}, {"mask_skip", &hq_ctx::mask_skip}, {"pixel_err", &hq_ctx::pixel_err},
+        {"img_u8", &hq_ctx::img_u8_path}};
+    for (const auto& o : kOnOff)
+        if (!std::strcmp(name, o.name)) {
+            c->*o.flag = value != 0;
+            return HQ_OK;
+        }
     if (!std::strcmp(name, "grid")) {
         if (value != 0 && value != 16 && value != 32 && value != 64)
             return fail(c, HQ_ERR_ARG, "grid must be 0, 16, 32 or 64");
@@ -650,37 +658,18 @@ int hq_set_option(hq_ctx* c, const char* name, int value) {
     } else if (!std::strcmp(name, "cost_variant")) {
         if (value < 0 || value > 2) return fail(c, HQ_ERR_ARG, "cost_variant must be 0, 1 or 2");
         c->cost_variant = value;
-    } else if (!std::strcmp(name, "trim")) {
-        c->trim = value != 0;
     } else if (!std::strcmp(name, "cost_rows")) {
         if (value != 8 && value != 16) return fail(c, HQ_ERR_ARG, "cost_rows must be 8 or 16");
         c->cost_rows = value;
-    } else if (!std::strcmp(name, "sa_graph")) {
-        c->sa_graph = value != 0;
     } else if (!std::strcmp(name, "gen_hrow_outputs")) {
         if (value != 4 && value != 8) return fail(c, HQ_ERR_ARG, "gen_hrow_outputs must be 4 or 8");
         c->gen_hrow_no = value;
-    } else if (!std::strcmp(name, "gen_vmfma")) {
-        c->gen_vmfma = value != 0;
-    } else if (!std::strcmp(name, "gen_hmfma")) {
-        c->gen_hmfma = value != 0;
     } else if (!std::strcmp(name, "gen_tile_shape")) {
         if (value < 0 || value > 2) return fail(c, HQ_ERR_ARG, "gen_tile_shape: 0, 1 or 2");
         c->gen_shape = (int)value;
-    } else if (!std::strcmp(name, "gen_vtile2")) {
-        c->gen_vtile2 = value != 0;
-    } else if (!std::strcmp(name, "gen_hrow4")) {
-        c->gen_hrow4 = value != 0;
     } else if (!std::strcmp(name, "cost_tw")) {
         if (value != 128 && value != 256) return fail(c, HQ_ERR_ARG, "cost_tw must be 128 or 256");
         c->cost_tw = value;
-
-    } else if (!std::strcmp(name, "sa_device")) {
-        c->sa_device = value != 0;
-    } else if (!std::strcmp(name, "shard_solo")) {
-        c->shard_solo = value != 0;
-    } else if (!std::strcmp(name, "palette_split")) {
-        c->psplit = value != 0;
     } else if (!std::strcmp(name, "slice_ranks")) {
         if (value < 1) return fail(c, HQ_ERR_ARG, "slice_ranks must be >= 1");
         c->slice_ranks = value;
@@ -702,18 +691,10 @@ int hq_set_option(hq_ctx* c, const char* name, int value) {
             c->d_l1n.release();
             c->d_l2n.release();
         }
-    } else if (!std::strcmp(name, "chunked")) {
-        c->chunked = value != 0;
-    } else if (!std::strcmp(name, "mask_skip")) {
-        c->mask_skip = value != 0;
-    } else if (!std::strcmp(name, "pixel_err")) {
-        c->pixel_err = value != 0;
     } else if (!std::strcmp(name, "dither_rows")) {
         if (value < 64 || value > 1024 || value % 64)
             return fail(c, HQ_ERR_ARG, "dither_rows must be a multiple of 64 in 64 .. 1024");
         c->dither_rows = value;
-    } else if (!std::strcmp(name, "img_u8")) {
-        c->img_u8_path = value != 0;
     } else if (!std::strcmp(name, "assign_blocks_per_cu")) {
         if (value < 0 || value > 64) return fail(c, HQ_ERR_ARG, "assign_blocks_per_cu in [0,64] (0 = auto)");
         c->assign_blocks_per_cu = value;

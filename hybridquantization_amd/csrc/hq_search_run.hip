@@ -103,12 +103,7 @@ int repair_scope(hq_search* s) {
 int lloyd_validate(hq_search* s) {
     hq_ctx* c = s->ctx;
     if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
-    if (sums_u8(c)) return HQ_OK;
-    if (int rc = planar_in_range(c)) return rc;
-    if (!c->planar_ok)
-        return fail(c, HQ_ERR_UNSUPPORTED, "planar image with a pixel outside [0, 1] or not finite: no exact sums, "
-                                           "no hybrid iteration");
-    return HQ_OK;
+    return sums_u8(c) ? HQ_OK : require_unit_range_image(c, "planar image", "no exact sums, no hybrid iteration");
 }
 
 // The k-means move of a device-resident hybrid iteration, after the sa_step that
@@ -121,7 +116,7 @@ int enqueue_lloyd(hq_search* s, ProfRec& pr) {
     int rc = enqueue_core(c, s->P, s->K, pr, Pass{Pass::AssignOnly});
     if (rc) return rc;
     int idx_bytes = 1;
-    const ClusterArgs ca = cluster_args(c, s->P, s->K, &idx_bytes);
+    const ClusterArgs ca = cluster_args(c, s->P, s->K, s->nch, &idx_bytes);
     HIP_TRY(c, timed_launch(pr, kPSums, [&] { return launch_cluster_sums(ca, idx_bytes, c->num_cu, c->stream); }));
     const LloydArgs la{ca.sums, s->cand[s->cd].as<float>(), prep_args(c, s->K), s->K, sums_u8(c) ? 1 : 0};
     HIP_TRY(c, timed_launch(pr, kPLloydUpdate, [&] { return launch_lloyd_update(la, s->P, c->stream); }));
@@ -145,22 +140,25 @@ int enqueue_repair(hq_search* s, ProfRec& pr) {
     }
     if (rc) return rc;
     int idx_bytes = 1;
-    const ClusterErrArgs ea = cluster_err_args(c, s->P, s->K, &idx_bytes);
+    const ClusterErrArgs ea = cluster_err_args(c, s->P, s->K, s->nch, &idx_bytes);
     HIP_TRY(c, timed_launch(pr, kPErrsum, [&] { return launch_cluster_errors(ea, idx_bytes, c->num_cu, c->stream); }));
     const ReseedArgs ra{ea.stats, ea.worst, s->cand[s->cd].as<float>(), prep_args(c, s->K), s->K, s->repair_moves};
     HIP_TRY(c, timed_launch(pr, kPReseed, [&] { return launch_reseed(ra, s->P, c->stream); }));
     return HQ_OK;
 }
 
-// What hq_get_indices[32] and hq_get_pixel_errors may read after hq_search_create* or
-// hq_search_run (hq.h): the index images of the last candidates evaluated -- a
-// device-resident search enqueues its passes itself, a host-driven one goes through
-// hq_eval_population, which keeps the flag -- and no error image: a repair iteration's
-// side pass stores that of candidates it then moves.
-void search_evaluated(hq_ctx* c, bool device, int rc, int evaluations) {
-    if (rc) c->idx_ok = false;
-    else if (device && evaluations > 0) c->idx_ok = true;
-    c->pixerr_ok = false;
+// The end of hq_search_create*, hq_search_run and hq_search_set_ordered (status rc, so many
+// evaluations enqueued).  What the getters may read then (hq.h) is the index images of the
+// last candidates evaluated and nothing else: a device-resident search enqueued its passes
+// itself (resident_of, under its chunk count), a host-driven one went through
+// hq_*_population, whose record becomes a search's.  A failure drops the record; a call that
+// evaluated nothing leaves it alone.
+void search_commit(hq_search* s, int rc, int evaluations) {
+    hq_ctx* c = s->ctx;
+    const NchScope scope(c, s->nch);
+    if (rc) drop(c);
+    else if (evaluations > 0)
+        commit(c, s->driver ? c->res.of_search() : resident_of(c, Resident::Search, s->P, s->K));
 }
 
 // A search's evaluation pass: folding (search_folds) or full.
@@ -192,15 +190,12 @@ int device_search_rerank(hq_search* s) {
     const NchScope scope(c, s->nch);
     if ((rc = ensure_population(c, s->P, s->K))) return rc;
     if (s->ordered && (rc = ensure_dither_map(c))) return rc;
-    hipStream_t st = c->stream;
     if (s->nch > 1) return fail(c, HQ_ERR_UNSUPPORTED, "K=%d > %d", s->K, kMaxK);
-    HIP_TRY(c, hipMemcpyAsync(c->d_pal_in.p, s->cand[s->cd].p, sizeof(float4) * (size_t)s->P * s->K,
-                              hipMemcpyDeviceToDevice, st));
-    HIP_TRY(c, launch_prep_palette(prep_args(c, s->K), s->P, st));
+    if ((rc = upload_and_prep(c, nullptr, s->cand[s->cd].p, s->P, s->K))) return rc;
     ProfRec untimed;
     if ((rc = enqueue_core(c, s->P, s->K, untimed, search_pass(s)))) return rc;
     if ((rc = enqueue_sa_step(s, true, true, false, false, 0.f, untimed))) return rc;
-    HIP_TRY(c, hipStreamSynchronize(st));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return HQ_OK;
 }
 
@@ -221,6 +216,7 @@ int device_search_create(hq_ctx* c, const hq_swasa_params* params, int K, uint64
         return fail(c, HQ_ERR_STATE, "palette slice without a communicator (test option): no search");
     s->pol = new Swasa(*params, seed);
     const NchScope scope(c, s->nch);
+    drop(c);  // (the search's own evaluation replaces the index images)
     int rc = ensure_population(c, P, K);
     if (rc) return rc;
     const size_t n4 = (size_t)P * 4 * K;
@@ -229,8 +225,8 @@ int device_search_create(hq_ctx* c, const hq_swasa_params* params, int K, uint64
         HIP_TRY(c, s->cand[i].ensure(sizeof(float) * n4));
         HIP_TRY(c, s->err[i].ensure(sizeof(double) * P));
         HIP_TRY(c, s->seed[i].ensure(sizeof(uint64_t)));
+        HIP_TRY(c, s->best_err[i].ensure(sizeof(double)));
     }
-    for (int i = 0; i < 2; ++i) HIP_TRY(c, s->best_err[i].ensure(sizeof(double)));
     HIP_TRY(c, s->best_colors.ensure(sizeof(float) * 4 * K));
     // java.util.Random jumps: n steps = A_n s + C_n (mod 2^48), n = 0 .. 3KP
     const size_t nj = (size_t)3 * K * P + 1;
@@ -258,19 +254,15 @@ int device_search_create(hq_ctx* c, const hq_swasa_params* params, int K, uint64
     if ((rc = enqueue_sa_step(s, false, false, true, true, 0.f, untimed))) return rc;
     // A given population takes the random one's place after that step has drawn it (the seed
     // is past the 3 K P draws as always): into the candidate buffer the accept step reads,
-    // and through the palette prep as an evaluation uploads it (chunked palettes: pack_chunks'
-    // sub-palettes), so the prep's outputs and the duplicate flags are the given colours'.
+    // and through the palette prep as an evaluation uploads it (upload_and_prep), so the prep's
+    // outputs and the duplicate flags are the given colours'.
     std::vector<float> given;  // (.w = 0; read by the copy below until the synchronise)
     if (population) {
         given.assign(population, population + n4);
         for (size_t e = 3; e < n4; e += 4) given[e] = 0.0f;
-        hipStream_t st = c->stream;
-        HIP_TRY(c, hipMemcpyAsync(s->cand[s->cd].p, given.data(), sizeof(float) * n4, hipMemcpyHostToDevice, st));
-        const size_t n_in = s->nch > 1 ? (size_t)P * s->nch * kMaxK : (size_t)P * K;
-        if (s->nch > 1) pack_chunks(given.data(), P, K, s->nch, c->h_pal.as<float>());
-        else std::memcpy(c->h_pal.p, given.data(), sizeof(float) * n4);
-        HIP_TRY(c, hipMemcpyAsync(c->d_pal_in.p, c->h_pal.p, sizeof(float4) * n_in, hipMemcpyHostToDevice, st));
-        HIP_TRY(c, launch_prep_palette(prep_args(c, s->nch > 1 ? kMaxK : K), P * s->nch, st));
+        HIP_TRY(c, hipMemcpyAsync(s->cand[s->cd].p, given.data(), sizeof(float) * n4, hipMemcpyHostToDevice,
+                                  c->stream));
+        if ((rc = upload_and_prep(c, given.data(), nullptr, P, K))) return rc;
     }
     if ((rc = enqueue_core(c, P, K, untimed, search_pass(s)))) return rc;
     if ((rc = enqueue_sa_step(s, true, true, false, false, 0.f, untimed))) return rc;
@@ -303,15 +295,14 @@ int device_search_run(hq_search* s, int iterations, int* ran) {
     // (no allocation while a run is captured), zeroed once below -- the update
     // kernel leaves it zero for the next hybrid iteration
     const bool lloyd = period_in_run(s, s->every, s->ite, iterations);
-    const size_t sums_bytes = sizeof(int64_t) * ((size_t)s->P * s->K * 4 + 1);
+    const size_t sums_bytes = sizeof(int64_t) * ((size_t)s->P * s->K * 4 + 1);  // (d_sums' and d_errstat's)
     if (lloyd) HIP_TRY(c, c->d_sums.ensure(sums_bytes));
     // repair iterations in this run: the same for the error image, the statistics and the
     // worst pixels -- nothing of it without one
     const bool repair = period_in_run(s, s->repair_every, s->ite, iterations);
-    const size_t stat_bytes = sizeof(int64_t) * ((size_t)s->P * s->K * 4 + 1);
     if (repair) {
-        HIP_TRY(c, c->d_pixerr.ensure(sizeof(float) * (size_t)s->P * std::max<int64_t>((int64_t)c->g.W * (c->g.r1 - c->g.r0), 1)));
-        HIP_TRY(c, c->d_errstat.ensure(stat_bytes));
+        HIP_TRY(c, c->d_pixerr.ensure(sizeof(float) * (size_t)s->P * std::max<int64_t>(n_own(c->g), 1)));
+        HIP_TRY(c, c->d_errstat.ensure(sums_bytes));
         HIP_TRY(c, c->d_worst.ensure(sizeof(float) * (size_t)s->P * s->K * 4));
     }
     // option sa_graph: the run's kernels go into one hipGraph (stream capture),
@@ -335,7 +326,7 @@ int device_search_run(hq_search* s, int iterations, int* ran) {
         return e;
     };
     if (lloyd) HIP_TRY(c, zero_table(c->d_sums, sums_bytes));
-    if (repair) HIP_TRY(c, zero_table(c->d_errstat, stat_bytes));
+    if (repair) HIP_TRY(c, zero_table(c->d_errstat, sums_bytes));
     for (; done < iterations && s->ite < s->prm.imax; ++done) {
         const int ite = ++s->ite;
         s->pol->reduce_temperature_if_necessary(ite);                  // IM:507
@@ -383,6 +374,18 @@ int device_search_run(hq_search* s, int iterations, int* ran) {
     return HQ_OK;
 }
 
+// What a run of `iterations` needs of the context as it is now (the image or an option may
+// have changed): a hybrid iteration in it, its scope and the image's validity; a repair
+// iteration, its scope; no palette slice under a pixel mask; the ordered cost's scope.
+int run_scope(hq_search* s, int iterations) {
+    const int ite = s->driver ? s->driver->iteration() : s->ite;
+    int rc;
+    if (period_in_run(s, s->every, ite, iterations) && ((rc = lloyd_scope(s)) || (rc = lloyd_validate(s)))) return rc;
+    if (period_in_run(s, s->repair_every, ite, iterations) && (rc = repair_scope(s))) return rc;
+    if ((rc = mask_scope(s->ctx))) return rc;
+    return s->ordered ? ordered_scope(s->ctx, s->K) : HQ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -411,14 +414,11 @@ int hq_search_create_from(hq_ctx* c, const hq_swasa_params* params, int K, uint6
     int rc;
     if (device) {
         if (!c->have_image) rc = fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
-        else rc = bind(c);
-        if (rc) {
+        else if (!(rc = bind(c)) && !whole_image(c) && !(c->comm && c->nranks > 1) && !c->shard_solo)
+            rc = fail(c, HQ_ERR_STATE, "sharded context without a communicator");
+        if (rc) {  // (a refusal: nothing of the context has been touched)
             hq_search_destroy(s);
             return rc;
-        }
-        if (!whole_image(c) && !(c->comm && c->nranks > 1) && !c->shard_solo) {
-            hq_search_destroy(s);
-            return fail(c, HQ_ERR_STATE, "sharded context without a communicator");
         }
         s->nch = nch;
         rc = device_search_create(c, params, K, seed, population, s);
@@ -433,33 +433,22 @@ int hq_search_create_from(hq_ctx* c, const hq_swasa_params* params, int K, uint6
         // candidates for their argmin (its cost pass is wasted), the sums, the update
         s->driver->set_refine([c, delta](float* pal, int P, int KK) {
             std::vector<double> costs(P);
-            std::vector<int64_t> sums((size_t)P * KK * 4);
-            int64_t den = 0;
-            int rr = hq_eval_population(c, pal, P, KK, delta, costs.data(), nullptr);
-            if (!rr) rr = cluster_sums(c, P, KK, sums.data(), &den);
-            if (!rr && (rr = hq_centroids_from_sums(sums.data(), den, P, KK, pal)))
-                return fail(c, rr, "hq_centroids_from_sums failed");
-            return rr;
+            const int rr = hq_eval_population(c, pal, P, KK, delta, costs.data(), nullptr);
+            return rr ? rr : kmeans_move(c, P, KK, pal);
         });
         // the repair move, host-driven: an evaluation of the candidates that stores their
         // error image, the error statistics (pixels with no usable dE left out) and the rule
         s->driver->set_repair([c, delta, s](float* pal, int P, int KK) {
             const PixelErrScope scope(c);
             std::vector<double> costs(P);
-            std::vector<int64_t> err((size_t)P * KK * 4);
-            std::vector<float> worst((size_t)P * KK * 4);
-            int rr = hq_eval_population(c, pal, P, KK, delta, costs.data(), nullptr);
-            if (!rr) rr = cluster_errors(c, P, KK, err.data(), worst.data(), true);
-            if (!rr && (rr = hq_reseed_unused(err.data(), worst.data(), P, KK, s->repair_moves, pal, nullptr)))
-                return fail(c, rr, "hq_reseed_unused failed");
-            return rr;
+            const int rr = hq_eval_population(c, pal, P, KK, delta, costs.data(), nullptr);
+            return rr ? rr : repair_move(c, P, KK, s->repair_moves, true, pal, nullptr);
         });
         s->prm = *params;
         s->P = params->population;
         rc = s->driver->start(population);
     }
-    c->sums_ok = false;  // (the search's own evaluations replace the index images)
-    search_evaluated(c, !s->driver, rc, 1);
+    search_commit(s, rc, 1);
     if (rc) {
         hq_search_destroy(s);
         return rc;
@@ -471,26 +460,7 @@ int hq_search_create_from(hq_ctx* c, const hq_swasa_params* params, int K, uint6
 int hq_search_run(hq_search* s, int iterations, int* ran) {
     if (!s || iterations < 0) return HQ_ERR_ARG;
     int rc;
-    // a hybrid iteration in this run: its scope and the image's validity first, so
-    // a refusal leaves the search where it was
-    const int ite = s->driver ? s->driver->iteration() : s->ite;
-    if (s->ctx && period_in_run(s, s->every, ite, iterations)) {
-        if ((rc = lloyd_scope(s)) || (rc = lloyd_validate(s))) {
-            if (ran) *ran = 0;
-            return rc;
-        }
-    }
-    if (s->ctx && period_in_run(s, s->repair_every, ite, iterations)) {
-        if ((rc = repair_scope(s))) {
-            if (ran) *ran = 0;
-            return rc;
-        }
-    }
-    if (s->ctx && (rc = mask_scope(s->ctx))) {  // (a palette slice under a pixel mask)
-        if (ran) *ran = 0;
-        return rc;
-    }
-    if (s->ctx && s->ordered && (rc = ordered_scope(s->ctx, s->K))) {  // (the image or an option may have changed)
+    if (s->ctx && (rc = run_scope(s, iterations))) {  // (first, so a refusal leaves the search where it was)
         if (ran) *ran = 0;
         return rc;
     }
@@ -502,10 +472,7 @@ int hq_search_run(hq_search* s, int iterations, int* ran) {
     } else {
         rc = s->driver->run(iterations, count, nullptr);
     }
-    if (s->ctx) {
-        s->ctx->sums_ok = false;  // (hq_cluster_sums: a search run has evaluated since)
-        search_evaluated(s->ctx, !s->driver, rc, rc ? 0 : *count);
-    }
+    if (s->ctx) search_commit(s, rc, rc ? 0 : *count);
     return rc;
 }
 
@@ -556,8 +523,7 @@ int hq_search_set_ordered(hq_search* s, const float amp[3]) {
     if (ite != 0) return HQ_OK;
     // before the first iteration: the initial population's errors and its best are the new evaluation's
     const int rc = s->driver ? s->driver->rerank() : device_search_rerank(s);
-    c->sums_ok = false;
-    search_evaluated(c, !s->driver, rc, 1);
+    search_commit(s, rc, 1);
     if (rc) {
         s->ordered = was;
         for (int ch = 0; ch < 3; ++ch) s->amp[ch] = old[ch];

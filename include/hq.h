@@ -146,7 +146,9 @@ int hq_eval_population_partial(hq_ctx *ctx, const float *palettes, int P, int K,
  * dithered rendering), hq_ordered_population[_partial] (the ordered rendering), or
  * evaluation inside hq_refine_population,
  * hq_repair_population, hq_search_create[_from] and hq_search_run (the last
- * candidates the search evaluated; a run of 0 iterations changes nothing).
+ * candidates the search evaluated; a run that evaluates nothing changes nothing,
+ * unless it had to reallocate the buffers read here -- a larger image set since
+ * hq_search_create -- which ends it like a failed evaluation).
  * hq_set_image*, hq_set_filters and an evaluation that fails after it has
  * passed its argument checks end that: until the next successful evaluation the
  * three return HQ_ERR_STATE with a message and write nothing.

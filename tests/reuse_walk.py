@@ -13,6 +13,8 @@ import numpy as np
 import c_oracle
 import oracle as o
 from dither_ref import dither
+from mask_ref import masked_cost, rectangle
+from ordered_ref import ordered
 
 # Every option of hq_set_option that an evaluation reads, with its default.  The first two
 # lines are test_long_filters_gpu.GEN_DEFAULTS and what test_fast_path_gpu.DEFAULTS adds
@@ -21,7 +23,7 @@ OPTION_DEFAULTS = dict(
     cost_variant=0, gen_hmfma=1, gen_vmfma=1, gen_vtile2=1, gen_hrow4=1, gen_tile_shape=0, gen_hrow_outputs=4,
     cost_rows=16, cost_tw=128, trim=1, chunked=1, lists16=1,
     grid=32, img_u8=1, pixel_err=0, assign_blocks_per_cu=0, dither_rows=1024, palette_split=0,
-    slice_ranks=1, slice_rank=0)
+    slice_ranks=1, slice_rank=0, mask_skip=1)
 
 # (dpi, viewing distance in cm, half-width)
 HALF10, HALF19, HALF51 = (72, 45.0, 10), (96, 60.0, 19), (300, 50.0, 51)
@@ -29,13 +31,32 @@ HALF10, HALF19, HALF51 = (72, 45.0, 10), (96, 60.0, 19), (300, 50.0, 51)
 # image: (kind, w, h, seed, rows); rows None = the whole image, else the owned rows [r0, r1)
 IMG_U8FAST = ("lattice", 97, 53, 3, None)
 IMG_64 = ("lattice", 64, 48, 7, None)
+# mask: (x0, x1, y0, y1), the rectangle of columns [x0, x1) and rows [y0, y1) that counts.  On
+# IMG_U8FAST's 53 rows (four 16-row tiles, seven 8-row tiles, one tile column either way) rows
+# [5, 20) leave whole tiles dead and, with columns [10, 60), every live tile partly live.
+RECT = (10, 60, 5, 20)
+ORDERED_AMP = (0.06, 0.03, 0.0)
 
 
-def _cls(name, filters, image, P, K, op="eval", lab="oracle", out_of_range=False, **opts):
+def custom_map():
+    """An 8 x 4 threshold map (4 rows of 8) that is not a Bayer map: the 32 ranks shuffled,
+    (rank + 0.5) / 32 - 0.5, so every value lies inside [-0.5, 0.5]."""
+    def make():
+        ranks = np.random.default_rng(58).permutation(32).astype(np.float32).reshape(4, 8)
+        m = (ranks + np.float32(0.5)) / np.float32(32) - np.float32(0.5)
+        m.setflags(write=False)
+        return m
+    return _once(("map",), make)
+
+
+def _cls(name, filters, image, P, K, op="eval", lab="oracle", out_of_range=False, mask=None, map=None, **opts):
+    """mask: None or a rectangle (RECT's form); map: None for the default Bayer map, or "custom"
+    (custom_map).  enter() sets or clears both at every step."""
     unknown = set(opts) - set(OPTION_DEFAULTS)
     assert not unknown, unknown
     return dict(name=name, filters=filters, image=image, P=P, K=K, op=op, lab=lab, out_of_range=out_of_range,
-                opts={**OPTION_DEFAULTS, **opts}, strength=1.0 if op == "dither" else None)
+                opts={**OPTION_DEFAULTS, **opts}, strength=1.0 if op == "dither" else None, mask=mask, map=map,
+                amp=ORDERED_AMP if op == "ordered" else None)
 
 
 # lab: "device" = hq_set_image with lab4 NULL (the S-CIELAB of the image computed on the
@@ -54,6 +75,11 @@ CLASSES = [
     _cls("dither", HALF10, IMG_U8FAST, 2, 16, op="dither", lab="device", dither_rows=64),
     _cls("out-of-range", HALF10, IMG_U8FAST, 2, 16, lab="device", out_of_range=True),
     _cls("slice", HALF10, IMG_64, 4, 64, op="partial", slice_ranks=2, slice_rank=1),
+    # the three below share u8-fast's image, filters and LabRef: a step between them and u8-fast,
+    # grid-0 or dither changes the mask and the map only
+    _cls("ordered", HALF10, IMG_U8FAST, 3, 16, op="ordered", lab="device", map="custom"),
+    _cls("masked", HALF10, IMG_U8FAST, 4, 16, lab="device", mask=RECT, pixel_err=0),
+    _cls("masked-8row", HALF10, IMG_U8FAST, 4, 16, lab="device", mask=RECT, cost_rows=8),
 ]
 NAMES = [c["name"] for c in CLASSES]
 FAST_RANGE = (-32.0, 1.9)  # hq_eval.hip, palette_fits_fast
@@ -139,6 +165,18 @@ def palettes(cls):
     return _once(("pal", cls["name"]), make)
 
 
+def mask_of(cls):
+    """The class's mask as uint8 (h, w), or None."""
+    if cls["mask"] is None:
+        return None
+    _, w, h, _, _ = cls["image"]
+    return rectangle(w, h, *cls["mask"])
+
+
+def map_of(cls):
+    return custom_map() if cls["map"] == "custom" else None
+
+
 def oracle_lab(cls):
     """The oracle's S-CIELAB of the full image, (n, 4)."""
     kind, w, h, seed, _ = cls["image"]
@@ -164,7 +202,8 @@ def oracle_outputs(cls, lab=None):
     idx[p] (int32, the owned rows), used[p] (K flags: the owned and halo rows' for a shard),
     sum[p] (fp64 sum of the fp32 dE over the owned rows) and cost[p] = mean dE + 2 per
     unused colour for a whole image.  A palette outside the slice: None, zeros, 0.
-    The dither class: dither_ref's indices, the oracle's dE of that rendering."""
+    The dither class: dither_ref's indices, the oracle's dE of that rendering; the ordered
+    class: ordered_ref's indices, the same way.  A masked class: mask_ref's masked mean."""
     _, w, h, _, _ = cls["image"]
     f, rgba, pals, K = filters(cls), image(cls), palettes(cls), cls["K"]
     lab = oracle_lab(cls) if lab is None else np.ascontiguousarray(lab, np.float32).reshape(-1, 4)
@@ -180,8 +219,11 @@ def oracle_outputs(cls, lab=None):
             out["sum"].append(0.0)
             out["cost"].append(None)
             continue
-        if cls["op"] == "dither":
-            idx, used = dither(rgba, pal, w, h, cls["strength"])
+        if cls["op"] in ("dither", "ordered"):
+            if cls["op"] == "dither":
+                idx, used = dither(rgba, pal, w, h, cls["strength"])
+            else:
+                idx, used = ordered(rgba[:, :3], pal, w, h, cls["amp"], map_of(cls))
             err = o.ciede76(lab, o.candidate_scielab(idx, pal, f, w, h))
             cost = o.average_array(err) + o.compute_penalty(used, 2.0)
         else:
@@ -190,6 +232,9 @@ def oracle_outputs(cls, lab=None):
             if (r0, r1) != (0, h):  # a colour is used when an owned or halo pixel takes it
                 _, used = c_oracle.assign(rgba[e0 * w:e1 * w], pal, nthreads=_threads())
                 cost = None
+            if cls["mask"] is not None:
+                mask = mask_of(cls)
+                cost = masked_cost(err, mask, int(np.count_nonzero(mask)), np.count_nonzero(np.asarray(used) == 0), 2.0)
         out["idx"].append(np.asarray(idx, np.int32)[own])
         out["used"].append((np.asarray(used) > 0).astype(np.int32))
         out["sum"].append(float(np.sum(np.asarray(err, np.float32)[own].astype(np.float64))))

@@ -4,7 +4,8 @@
     right against the oracle, dither_ref, lloyd_ref, reseed_ref and seed_ref;
 2b  one context through the walk over every ordered pair of classes, bit for bit the
     fresh outputs at every step;
-2c  the read-back getters after "pixel_err" was off, after hq_set_image and hq_set_filters;
+2c  the read-back getters after "pixel_err" was off, after hq_set_image and hq_set_filters,
+    and after a search run of no iterations;
 2d  a search interrupted by other calls on its context against one that is not;
 2e  a context handed from thread to thread, and four contexts side by side.
 
@@ -24,6 +25,7 @@ import oracle as o
 import reuse_walk as rw
 from hybridquantization_amd import _lib
 from lloyd_ref import cluster_sums_ref, q32
+from mask_ref import inside, masked_cluster_sums, masked_histogram
 from reseed_ref import cluster_errors_ref
 from seed_ref import coord_byte, coord_float, histogram_ref
 from test_fast_path_gpu import DEFAULTS as FAST_DEFAULTS
@@ -59,7 +61,9 @@ def new_ctx(gpu, de=DE["de76"]):
 
 def enter(m, cls):
     """Brings the context to the class's state with the fewest calls: every option,
-    hq_set_filters when the filters differ, hq_set_image when the filters or the image do."""
+    hq_set_filters when the filters differ, hq_set_image when the filters or the image do,
+    and -- at every step, since classes that share an image set none between them -- the
+    class's mask and threshold map, or none."""
     for name, v in cls["opts"].items():
         m.setOption(name, v)
     if m.cur_filters != cls["filters"]:
@@ -72,6 +76,8 @@ def enter(m, cls):
         r0, r1 = rw.rows(cls)
         m.setImage(rw.image(cls).reshape(-1), lab, cls["image"][1], m.illum, r0, r1)
         m.cur_image = (cls["image"], cls["lab"])
+    m.setMask(rw.mask_of(cls))
+    m.setDitherMap(rw.map_of(cls))
 
 
 def raw_sums(m, P, K):
@@ -96,6 +102,8 @@ def operate(m, cls):
         out["partial"] = part
     elif cls["op"] == "dither":
         out["costs"], out["used"] = m.ditherPopulation(pals, cls["strength"], 2.0, return_used=True)
+    elif cls["op"] == "ordered":
+        out["costs"], out["used"] = m.orderedPopulation(pals, cls["amp"], 2.0, return_used=True)
     else:
         out["costs"], out["used"] = m.computeQuantizationErrorPopulation(pals, 2.0, return_used=True)
     for p in rw.local_palettes(cls):
@@ -103,6 +111,7 @@ def operate(m, cls):
     if cls["opts"]["pixel_err"]:
         for p in rw.local_palettes(cls):
             out[f"pixel_errors[{p}]"] = m.getPixelErrors(p)
+    out["mask_info"] = np.array(m.maskInfo(), np.int64)  # (n_full, n_owned, tiles_run, tiles_all)
     out["labref"] = m.getLabRef()
     cells, den = m.colorHistogram(3)
     out["histogram"], out["histogram_den"] = cells, np.int64(den)
@@ -150,8 +159,9 @@ def test_option_table_covers_the_path_tests_defaults():
 # 2a. Fresh against fresh, and against the oracle
 # ---------------------------------------------------------------------------
 def sums_allowed(cls):
-    """hq_cluster_sums serves the class: the whole image, not dithered, not sliced."""
-    return cls["op"] != "dither" and cls["opts"]["slice_ranks"] == 1
+    """hq_cluster_sums serves the class: the whole image, not dithered (by diffusion or by a
+    threshold map), not sliced."""
+    return cls["op"] not in ("dither", "ordered") and cls["opts"]["slice_ranks"] == 1
 
 
 @pytest.mark.parametrize("name", rw.NAMES)
@@ -199,13 +209,20 @@ def test_fresh_contexts_agree_and_are_right(gpu, de, name):
     assert den == (255 if cls["image"][0] == "lattice" else 1 << 32)
     px = by if den == 255 else q32(rgb)
     coords = coord_byte(by, 3) if den == 255 else coord_float(rgb, 3)
-    np.testing.assert_array_equal(a["histogram"], histogram_ref(coords, px, 3), err_msg=name)
+    mask = rw.mask_of(cls)  # (the masked classes hold the whole image)
+    np.testing.assert_array_equal(a["histogram"], histogram_ref(coords, px, 3) if mask is None
+                                  else masked_histogram(coords, px, 3, mask), err_msg=name)
     whole = (r0, r1) == (0, h)
+    n_in = w * h if mask is None else int(inside(mask).sum())
+    assert tuple(a["mask_info"][:2]) == (n_in, n_own if mask is None else n_in)
+    if mask is not None:  # the rectangle leaves whole tiles dead: the fast cost launch skips them
+        assert 0 < a["mask_info"][2] < a["mask_info"][3], a["mask_info"]
     if sums_allowed(cls):
         assert a["cluster_sums_status"] == OK and a["cluster_sums_den"] == den
         for p in range(P):
-            np.testing.assert_array_equal(a["cluster_sums"][p], cluster_sums_ref(a[f"indices32[{p}]"][:n_own], px, K),
-                                          err_msg=f"{name} p={p}")
+            idx = a[f"indices32[{p}]"][:n_own]
+            np.testing.assert_array_equal(a["cluster_sums"][p], cluster_sums_ref(idx, px, K) if mask is None
+                                          else masked_cluster_sums(idx, px, K, mask), err_msg=f"{name} p={p}")
     else:
         assert a["cluster_sums_status"] in (ERR_STATE, ERR_UNSUPPORTED) and np.all(a["cluster_sums"] == -7)
     if sums_allowed(cls) and cls["opts"]["pixel_err"]:
@@ -217,6 +234,9 @@ def test_fresh_contexts_agree_and_are_right(gpu, de, name):
             np.testing.assert_array_equal(bits(a["cluster_errors_worst"][p]), bits(want_rgb), err_msg=f"{name} p={p}")
     else:
         assert a["cluster_errors_status"] in (ERR_STATE, ERR_UNSUPPORTED) and np.all(a["cluster_errors"] == -7)
+        assert np.all(a["cluster_errors_worst"] == -7)
+    if mask is not None:  # (no masked error statistic exists, whatever "pixel_err" says)
+        assert a["cluster_errors_status"] == ERR_UNSUPPORTED
     assert whole or name == "shard"
 
 
@@ -228,9 +248,9 @@ WALK = rw.euler_walk(len(rw.CLASSES))
 
 @pytest.mark.parametrize("de", list(DE))
 def test_walk_over_every_transition(gpu, de):
-    """One context through all 133 steps (132 transitions: every ordered pair of the twelve
+    """One context through all 211 steps (210 transitions: every ordered pair of the fifteen
     classes once); at every step every output is the fresh context's, bit for bit."""
-    assert len(WALK) == 133
+    assert len(WALK) == 211
     m = new_ctx(gpu, DE[de])
     try:
         prev = None
@@ -388,6 +408,42 @@ def test_getters_after_a_failed_evaluation_and_after_a_search(gpu):
             np.testing.assert_array_equal(got["hq_get_indices"][1], got["hq_get_indices32"][1])
             assert got["hq_get_indices"][1].max() < K
             assert_refused({"hq_get_pixel_errors": got["hq_get_pixel_errors"]}, "after hq_search_run")
+        finally:
+            s.close()
+    finally:
+        m.close()
+
+
+@pytest.mark.parametrize("grows", [True, False], ids=["larger_image", "same_image"])
+def test_index_getter_after_a_search_run_of_no_iterations(gpu, grows):
+    """A device-resident search (P = 2, K = 16) created on 64 x 48; [the image replaced by
+    193 x 131;] an evaluation of P = 1 and its indices read; hq_search_run(s, 0).  The run
+    enqueues nothing, so nothing it does may make hq_get_indices answer from memory nobody
+    wrote: where it had to grow the index buffer for its own two palettes (the larger image)
+    the getter either refuses with the buffer untouched or returns the bytes read before;
+    where nothing grows it answers HQ_OK with those bytes."""
+    K = 16
+    (w1, h1, s1), (w2, h2, s2) = (64, 48, 7), (193, 131, 9)
+    m = plain_ctx(gpu, sa_device=1)
+    try:
+        m.setImage(lattice(w1, h1, s1), None, w1, m.illum)
+        s = Search(m, K, hq.SWASA(population=2, imax=20, seed=4, t0=0.05), None)
+        try:
+            w, h = (w2, h2) if grows else (w1, h1)
+            if grows:
+                m.setImage(lattice(w2, h2, s2), None, w2, m.illum)
+            m.computeQuantizationErrorPopulation(pals_of(1, K, 11), 2.0)
+            before = m.getIndices(0).copy()
+            assert before.shape == (w * h,) and before.max() < K
+            assert s.run(0) == 0
+            buf = np.full(w * h, 249, np.uint8)
+            rc = hq.load().hq_get_indices(m.ctx, 0, _lib.u8ptr(buf))
+            print(f"grows={grows}: hq_get_indices after hq_search_run(s, 0) returned {rc}, "
+                  f"{'the bytes read before' if np.array_equal(buf, before) else 'untouched' if np.all(buf == 249) else 'other bytes'}")
+            if grows:
+                assert (rc == ERR_STATE and np.all(buf == 249)) or (rc == OK and np.array_equal(buf, before)), rc
+            else:
+                assert rc == OK and np.array_equal(buf, before), rc
         finally:
             s.close()
     finally:

@@ -6,9 +6,12 @@ import numpy as np
 import pytest
 
 import reuse_walk as rw
+from mask_ref import live_tiles_brute
+from ordered_ref import bayer
 from test_fast_path import bucket
 
 ASSIGN_CHUNK = 256 * 6  # hq_eval.hip, assign_blocks: pixels per assign workgroup (HQ_ASSIGN_MINPX 6)
+FAST_TILE = {16: (128, 16), 8: (108, 8)}  # option cost_rows -> the fast cost launch's tile (columns, rows)
 
 
 def chunk_count(K):  # hq_internal.h
@@ -18,7 +21,7 @@ def chunk_count(K):  # hq_internal.h
     return n
 
 
-@pytest.mark.parametrize("n", [1, 2, 3, 5, 12, 13])
+@pytest.mark.parametrize("n", [1, 2, 3, 5, 12, 13, 15])
 def test_walk_uses_every_ordered_pair_once(n):
     walk = rw.euler_walk(n)
     assert len(walk) == n * (n - 1) + 1
@@ -29,9 +32,21 @@ def test_walk_uses_every_ordered_pair_once(n):
     assert walk == rw.euler_walk(n)  # deterministic
 
 
-def test_twelve_classes_make_133_steps():
-    assert len(rw.CLASSES) == 12 and len(set(rw.NAMES)) == 12
-    assert len(rw.euler_walk(len(rw.CLASSES))) == 133
+def test_fifteen_classes_make_211_steps():
+    assert len(rw.CLASSES) == 15 and len(set(rw.NAMES)) == 15
+    assert len(rw.euler_walk(len(rw.CLASSES))) == 15 * 14 + 1 == 211
+
+
+def tile_states(c):
+    """(dead, partly live) tile counts of the class's fast cost launch under its mask, pixel by
+    pixel (mask_ref's brute force)."""
+    _, w, h, _, _ = c["image"]
+    tw, th = FAST_TILE[c["opts"]["cost_rows"]]
+    mask = rw.mask_of(c)
+    live = live_tiles_brute(mask, w, h, tw, th)
+    tx, ty = -(-w // tw), -(-h // th)
+    partly = [t for t in live if not mask[t // tx * th:(t // tx + 1) * th, t % tx * tw:(t % tx + 1) * tw].all()]
+    return tx * ty - len(live), len(partly)
 
 
 @pytest.mark.parametrize("name", rw.NAMES)
@@ -66,8 +81,26 @@ def test_class_meets_its_path(name):
         "dither": c["op"] == "dither" and K <= 256 and opts["dither_rows"] == 64 and c["strength"] == 1.0,
         "out-of-range": not fits and K <= 256,
         "slice": c["op"] == "partial" and opts["slice_ranks"] == 2 and P % 2 == 0 and opts["slice_rank"] == 1,
+        "ordered": c["op"] == "ordered" and K <= 256 and c["map"] == "custom" and c["amp"] == (0.06, 0.03, 0.0),
+        "masked": c["mask"] == (10, 60, 5, 20) and opts["cost_rows"] == 16 and opts["pixel_err"] == 0,
+        "masked-8row": c["mask"] == (10, 60, 5, 20) and opts["cost_rows"] == 8,
     }[name]
     assert want, name
+    assert (c["map"] is not None) == (name == "ordered") and (c["mask"] is not None) == name.startswith("masked")
+    if name == "ordered":
+        tmap = rw.map_of(c)
+        assert tmap.shape == (4, 8) and tmap.dtype == np.float32 and np.all((tmap >= -0.5) & (tmap <= 0.5))
+        assert sorted(np.unique(tmap)) == sorted(tmap.reshape(-1)) and not np.array_equal(tmap, bayer(4)[:4, :8])
+    if c["mask"] is not None:
+        # the fast path of the 21-tap bucket, where both tile shapes exist; in either shape a tile
+        # that is skipped and one that runs with pixels outside the mask
+        assert bucket(half) == 10 and nch == 1 and opts["cost_variant"] == 0 and opts["mask_skip"] == 1
+        dead, partly = tile_states(c)
+        assert dead >= 1 and partly >= 1, (name, dead, partly)
+        other = rw.by_name("masked-8row" if name == "masked" else "masked")
+        # the step between the two masked classes changes the tile shape and nothing else
+        assert {k for k in opts if opts[k] != other["opts"][k]} == {"cost_rows"}
+        assert (c["image"], c["filters"], c["lab"], c["mask"]) == tuple(other[k] for k in ("image", "filters", "lab", "mask"))
     if name != "slice":
         assert opts["slice_ranks"] == 1 and list(rw.local_palettes(c)) == list(range(P))
     else:
