@@ -81,6 +81,8 @@ SIGNATURES = {
     "hq_ordered_population_partial": (C.c_int, [_ctx, _f, C.c_int, C.c_int, _f, _d]),
     "hq_set_mask": (C.c_int, [_ctx, _u8, C.c_int, C.c_int]),
     "hq_mask_info": (C.c_int, [_ctx, _i64, _i64, _i64, _i64]),
+    "hq_set_weights": (C.c_int, [_ctx, _u8, C.c_int, C.c_int]),
+    "hq_weights_info": (C.c_int, [_ctx, _i64, _i64]),
     "hq_color_histogram": (C.c_int, [_ctx, C.c_int, _i64, _i64]),
     "hq_median_cut": (C.c_int, [_i64, C.c_int, C.c_int64, C.c_int, _f, C.POINTER(C.c_int)]),
     "hq_quantize": (C.c_int, [_ctx, _f, C.c_int64, _f, C.c_int, _f, _i32]),

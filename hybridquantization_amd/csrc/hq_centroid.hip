@@ -71,14 +71,30 @@ __device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
 // and not added, like the pixels outside [q0, q1) -- so a wave with one is not
 // `full` and takes no shortcut; the planar form's range flag still looks at
 // every owned pixel.
-template <typename IDX_T, bool U8, bool MSK = false>
+// MSK = 2 (pixel weights, hq_set_weights: the mask bytes are the weights): a pixel of weight w > 0
+// adds w times its channels and w to the count, one multiply per channel ahead of the same adds;
+// weight 0 is the masked-out pixel.  A pixel then adds up to 255 times as much, so the fields are
+// others:
+//  - packed, 2^16 pixels: the same 2 words of 2 fields of 32 bits.  A sum of w byte stays at or
+//    below 255 255 2^16 < 2^32, the count at or below 255 2^16.
+//  - planar, 2^22 pixels: 4 whole words, R, G, B and the count.  A sum of w q(v) stays at or below
+//    255 2^32 2^22 < 2^62.  (hq_cluster_sums refuses an image whose owned weights sum to 2^31 or
+//    more, so that the totals stay below 2^63: hq.h.)  The 32 KiB of LDS hold 5 workgroups per
+//    CU where the 3-word form's 24 KiB hold 6.
+//  The uniform-wave shortcut adds the wave's weight sum for its count.
+template <typename IDX_T, bool U8, int MSK = 0>
 __global__ __launch_bounds__(256) void centroid_kernel(ClusterArgs a, int ngroups) {
     constexpr bool LDS = sizeof(IDX_T) == 1;
-    constexpr int F = U8 ? 2 : 3;  // 64-bit words per colour
+    constexpr bool WGT = MSK == 2;
+    constexpr int F = U8 ? 2 : WGT ? 4 : 3;  // 64-bit words per colour
     static_assert(kCentLdsK == kMaxK && kMaxK == 256, "a u8 index addresses the whole LDS table");
     static_assert(255ull * cent_max_span(true) < (1ull << 32), "packed fields: no carry into the neighbour");
     static_assert(((uint64_t)cent_max_span(false) << 32) < (1ull << 48) && cent_max_span(false) < (1u << 16),
                   "planar B and count: no carry, the count in 16 bits");
+    static_assert(255ull * 255ull * cent_max_span(true, true) < (1ull << 32),
+                  "weighted packed fields: no carry into the neighbour");
+    static_assert(((255ull * cent_max_span(false, true)) << 32) < (1ull << 63),
+                  "weighted planar words: a workgroup's sum of w q(v) below 2^63");
     __shared__ unsigned long long s_acc[LDS ? 4 * kMaxK * F : 1];
     const int w = xcd_remap(blockIdx.x, a.nblocks * ngroups);
     const int blk = w / ngroups, grp = w % ngroups, tid = threadIdx.x;
@@ -93,6 +109,11 @@ __global__ __launch_bounds__(256) void centroid_kernel(ClusterArgs a, int ngroup
             if constexpr (U8) {
                 atomicAdd(e, r | (g << 32));
                 atomicAdd(e + 1, b | (n << 32));
+            } else if constexpr (WGT) {
+                atomicAdd(e, r);
+                atomicAdd(e + 1, g);
+                atomicAdd(e + 2, b);
+                atomicAdd(e + 3, n);
             } else {
                 atomicAdd(e, r);
                 atomicAdd(e + 1, g);
@@ -124,18 +145,21 @@ __global__ __launch_bounds__(256) void centroid_kernel(ClusterArgs a, int ngroup
         for (int pp = 0; pp < 4; ++pp) kq[pp] = load_idx4(idx + (int64_t)(p0 + min(pp, ng - 1)) * a.idx_pitch + q);
         uint64_t r[4], g[4], b[4];
         bool ok[4];
-        uint32_t mq = ~0u;  // MSK: the quad's mask bytes
-        if constexpr (MSK) mq = *reinterpret_cast<const uint32_t*>(a.mask + q);
+        uint32_t mq = ~0u;  // MSK: the quad's mask bytes (MSK = 2: its weights)
+        if constexpr (MSK != 0) mq = *reinterpret_cast<const uint32_t*>(a.mask + q);
+        // what pixel i of the quad adds to its colour's count: 1, or its weight (byte i of mq)
+        auto wt = [&](int i) -> uint32_t { return WGT ? (mq >> (8 * i)) & 0xffu : 1u; };
         if constexpr (U8) {
             const uint4 px = *reinterpret_cast<const uint4*>(a.rgbx + q);
             const uint32_t v[4] = {px.x, px.y, px.z, px.w};
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 ok[i] = in && q + i >= a.q0 && q + i < a.q1;
-                if constexpr (MSK) ok[i] = ok[i] && ((mq >> (8 * i)) & 0xffu) != 0u;
+                if constexpr (MSK != 0) ok[i] = ok[i] && ((mq >> (8 * i)) & 0xffu) != 0u;
                 r[i] = v[i] & 0xffu;
                 g[i] = (v[i] >> 8) & 0xffu;
                 b[i] = (v[i] >> 16) & 0xffu;
+                if constexpr (WGT) r[i] *= wt(i), g[i] *= wt(i), b[i] *= wt(i);
             }
         } else {
             const float4 fr = *reinterpret_cast<const float4*>(a.R + q);
@@ -152,16 +176,17 @@ __global__ __launch_bounds__(256) void centroid_kernel(ClusterArgs a, int ngroup
                                   vb[i] <= 1.f;
                 bad |= own && !fits;
                 ok[i] = own && fits;
-                if constexpr (MSK) ok[i] = ok[i] && ((mq >> (8 * i)) & 0xffu) != 0u;
+                if constexpr (MSK != 0) ok[i] = ok[i] && ((mq >> (8 * i)) & 0xffu) != 0u;
                 r[i] = unit_q32(fits ? vr[i] : 0.f);
                 g[i] = unit_q32(fits ? vg[i] : 0.f);
                 b[i] = unit_q32(fits ? vb[i] : 0.f);
+                if constexpr (WGT) r[i] *= wt(i), g[i] *= wt(i), b[i] *= wt(i);  // (at most 255 2^32: exact)
             }
             if (bad) *a.bad = 1;
         }
         const bool full = __builtin_amdgcn_ballot_w64(!(ok[0] && ok[1] && ok[2] && ok[3])) == 0;
         bool have = false;  // (wave-uniform) the wave's pixel sums, made once for all the palettes
-        uint64_t wr = 0, wg = 0, wb = 0;
+        uint64_t wr = 0, wg = 0, wb = 0, wn = 256ull;
 #pragma unroll
         for (int pp = 0; pp < 4; ++pp) {
             if (pp >= ng) break;
@@ -173,13 +198,14 @@ __global__ __launch_bounds__(256) void centroid_kernel(ClusterArgs a, int ngroup
                     wr = wave_sum(r[0] + r[1] + r[2] + r[3]);
                     wg = wave_sum(g[0] + g[1] + g[2] + g[3]);
                     wb = wave_sum(b[0] + b[1] + b[2] + b[3]);
+                    if constexpr (WGT) wn = wave_sum((uint64_t)(wt(0) + wt(1) + wt(2) + wt(3)));  // the wave's weight sum
                     have = true;
                 }
-                if (lane == 0) add(pp, k0, wr, wg, wb, 256ull);
+                if (lane == 0) add(pp, k0, wr, wg, wb, wn);
             } else {
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
-                    if (ok[i]) add(pp, k[i], r[i], g[i], b[i], 1ull);
+                    if (ok[i]) add(pp, k[i], r[i], g[i], b[i], (uint64_t)wt(i));
             }
         }
     }
@@ -190,6 +216,7 @@ __global__ __launch_bounds__(256) void centroid_kernel(ClusterArgs a, int ngroup
             const int f = e & 3, pp = e >> 10, k = (e >> 2) & (kMaxK - 1);
             unsigned long long v;
             if constexpr (U8) v = (s_acc[(e >> 2) * 2 + (f >> 1)] >> (32 * (f & 1))) & 0xffffffffull;
+            else if constexpr (WGT) v = s_acc[e];
             else if (f < 2) v = s_acc[(e >> 2) * 3 + f];
             else v = f == 2 ? s_acc[(e >> 2) * 3 + 2] & 0xffffffffffffull : s_acc[(e >> 2) * 3 + 2] >> 48;
             if (k < a.K && v) atomicAdd(a.sums + ((int64_t)(p0 + pp) * a.K + k) * 4 + f, v);
@@ -205,12 +232,16 @@ hipError_t launch_cluster_sums(const ClusterArgs& a0, int idx_bytes, int num_cu,
     const int ngroups = (a.P + 3) / 4;
     const uint32_t nq = (((a.q1 + 3u) & ~3u) - (a.q0 & ~3u)) >> 2;
     const uint32_t want = (uint32_t)std::max(1, num_cu * kCentBlocksPerCu / ngroups);
-    a.qspan = std::min(((nq + want - 1) / want + 255u) / 256u * 256u, cent_max_span(a.rgbx != nullptr) / 4u);
+    const bool wgt = a.mask && a.weighted;
+    const uint32_t cap = cent_max_span(a.rgbx != nullptr, wgt) / 4u;
+    const uint32_t by_grid = ((nq + want - 1) / want + 255u) / 256u * 256u;
+    const uint32_t asked = (a.span / 4u + 255u) / 256u * 256u;  // test option "cent_span", in whole 256-quad steps
+    a.qspan = std::min(a.span ? asked : by_grid, cap);
     a.nblocks = (int)((nq + a.qspan - 1) / a.qspan);
     with_idx(idx_bytes, [&](auto it) {
         using T = typename decltype(it)::type;
         with_bool(a.rgbx != nullptr, [&](auto U8) {
-            with_bool(a.mask != nullptr, [&](auto MSK) {
+            with_mask(a.mask != nullptr, wgt, [&](auto MSK) {
                 HQ_LAUNCH((centroid_kernel<T, U8.value, MSK.value>), dim3((unsigned)(a.nblocks * ngroups)), dim3(256),
                           0, s, a, ngroups);
             });

@@ -62,12 +62,14 @@ struct TileItem {
 };
 
 // MSK (the masked instances, hq_cost_masked.hip): the tile through the live-tile
-// list of the launch (CostArgs::live), which covers nlive P items.
-template <int TW, int TH, bool MSK = false>
+// list of the launch (CostArgs::live), which covers nlive P items.  MSK is 0 (the plain
+// instances), 1 (a pixel mask) or 2 (pixel weights, hq_cost_weighted.hip: the mask bytes are the
+// pixels' weights, the live tiles those with a non-zero one).
+template <int TW, int TH, int MSK = 0>
 __device__ __forceinline__ TileItem tile_item(const CostArgs& a, int w, int P) {
     TileItem t;
     t.p = w % P;
-    if constexpr (MSK) t.tile = a.live[w / P];
+    if constexpr (MSK != 0) t.tile = a.live[w / P];
     else t.tile = w / P;
     t.x0 = (t.tile % a.tiles_x) * TW;
     t.y0 = a.g.r0 + (t.tile / a.tiles_x) * TH;
@@ -368,7 +370,7 @@ __device__ __forceinline__ f32x4v mfma3(const f16x8& ah, const f16x8& al, const 
     return d;
 }
 
-template <int DE, bool TRIM, bool MSK = false>
+template <int DE, bool TRIM, int MSK = 0>
 __global__ __launch_bounds__(256, 6) void cost_mfma_kernel(CostArgs a, int P_) {
     constexpr int HALF = 10, RW = 128, TH = 8, HR = 2, T2 = 2 * HALF;
     constexpr int TW = RW - 2 * HALF, RH = TH + 2 * HALF;
@@ -385,7 +387,7 @@ __global__ __launch_bounds__(256, 6) void cost_mfma_kernel(CostArgs a, int P_) {
     const int tid = threadIdx.x;
     const Geom& g = a.g;
     TileItem cur;
-    if constexpr (MSK) cur = tile_item<TW, TH, true>(a, xcd_remap(blockIdx.x, a.nlive * P_), P_);
+    if constexpr (MSK != 0) cur = tile_item<TW, TH, MSK>(a, xcd_remap(blockIdx.x, a.nlive * P_), P_);
     else cur = tile_item<TW, TH>(a, xcd_remap(blockIdx.x, a.ntiles * P_), P_);
     tile_item_to_grid<DE, TW, TH>(a, cur);
     const TapsPtr<HALF> taps = (TapsPtr<HALF>)(uintptr_t)a.taps;  // H taps x 2^-30
@@ -466,7 +468,7 @@ __global__ __launch_bounds__(256, 6) void cost_mfma_kernel(CostArgs a, int P_) {
         bool ok = has_item && gy0 + r < g.r1 && gx0 < g.W;
         if constexpr (DE == 2) ok = ok && gy0 + r >= g.r0;
         const uint32_t off = ok ? (uint32_t)((gy0 + r - g.r0) * g.lab_pitch + gx0) : 0u;
-        if constexpr (MSK) mk[r] = *reinterpret_cast<const uint16_t*>(a.mask + off);
+        if constexpr (MSK != 0) mk[r] = *reinterpret_cast<const uint16_t*>(a.mask + off);
         const float* src3[3] = {a.labL, a.labA, a.labB};
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
@@ -497,7 +499,11 @@ __global__ __launch_bounds__(256, 6) void cost_mfma_kernel(CostArgs a, int P_) {
                 const float e = delta_e_f<DE>(labv[r][0][xo], labv[r][1][xo], labv[r][2][xo], lf);
                 bool in = gy0 + r < g.r1 && gx0 + xo < g.W;
                 if constexpr (DE == 2) in = in && gy0 + r >= g.r0;
-                if constexpr (MSK) {  // a select: a masked-out NaN stays out of the sum
+                if constexpr (MSK == 2) {  // one fma with the weight; weight 0 is the select
+                    const uint32_t wb = (mk[r] >> (8 * xo)) & 0xffu;
+                    part = in && wb != 0u ? fmaf(e, (float)wb, part) : part;
+                } else
+                if constexpr (MSK == 1) {  // a select: a masked-out NaN stays out of the sum
                     part += in && ((mk[r] >> (8 * xo)) & 0xffu) != 0u ? e : 0.f;
                 } else
                 part += in ? e : 0.f;
@@ -778,7 +784,7 @@ constexpr int cost16w_waves() {
 // (8 KT bytes): channel 0's x words first, then -- loaded from global memory
 // during channel 0's horizontal pass, once its gathers are done -- the (y, z)
 // pairs in the same bytes.
-template <int HB, int DE, bool TRIM, int NW, int NCH = 1, bool MSK = false>
+template <int HB, int DE, bool TRIM, int NW, int NCH = 1, int MSK = 0>
 __global__ __launch_bounds__(64 * NW, (cost16w_waves<HB, NCH>())) void cost16w_kernel(CostArgs a, int P_) {
     using Gm = Tile16<HB, NW>;
     constexpr int NTH = 64 * NW, IPR = 8 * NW;  // threads; horizontal items per row pair
@@ -803,7 +809,7 @@ __global__ __launch_bounds__(64 * NW, (cost16w_waves<HB, NCH>())) void cost16w_k
     const int tid = threadIdx.x;
     const Geom& g = a.g;
     TileItem cur;
-    if constexpr (MSK) cur = tile_item<TW, TH, true>(a, xcd_remap(blockIdx.x, a.nlive * P_), P_);
+    if constexpr (MSK != 0) cur = tile_item<TW, TH, MSK>(a, xcd_remap(blockIdx.x, a.nlive * P_), P_);
     else cur = tile_item<TW, TH>(a, xcd_remap(blockIdx.x, a.ntiles * P_), P_);
     tile_item_to_grid<DE, TW, TH>(a, cur);
     const TapsPtr<HB> taps = (TapsPtr<HB>)(uintptr_t)a.taps;  // H taps x 2^-30
@@ -998,7 +1004,7 @@ __global__ __launch_bounds__(64 * NW, (cost16w_waves<HB, NCH>())) void cost16w_k
         bool ok = gy0 + r < g.r1 && gx0 < g.W;
         if constexpr (DE == 2) ok = ok && gy0 + r >= g.r0;
         const uint32_t off = ok ? (uint32_t)((gy0 + r - g.r0) * g.lab_pitch + gx0) : 0u;
-        if constexpr (MSK) mk[r] = *reinterpret_cast<const uint32_t*>(a.mask + off);
+        if constexpr (MSK != 0) mk[r] = *reinterpret_cast<const uint32_t*>(a.mask + off);
 #ifdef HQ_ABL_NOLABLD  // timing ablation (wrong results): no LabRef loads
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) lab[r][ch] = make_float4(off, off + 1, off + ch, r);
@@ -1085,7 +1091,20 @@ __global__ __launch_bounds__(64 * NW, (cost16w_waves<HB, NCH>())) void cost16w_k
     // tiles inside the image and shard (all but the last tile column and row)
     // sum without per-pixel masks
     float part = 0.f;
-    if constexpr (MSK) {  // every tile with per-pixel selects, in the plain forms' order of additions: an
+    if constexpr (MSK == 2) {  // pixel weights: the masked form's pixels in its order, each by one fma with its
+                               // weight (w = 1: fma(e, 1, part) = part + e, the masked bits); weight 0 is the
+                               // select, so a NaN of such a pixel stays out of the sum
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int xo = 0; xo < HR; ++xo) {
+                const uint32_t wb = (mk[r] >> (8 * xo)) & 0xffu;
+                bool in = gy0 + r < g.r1 && gx0 + xo < g.W && wb != 0u;
+                if constexpr (DE == 2) in = in && gy0 + r >= g.r0;
+                part = in ? fmaf(e[r][xo], (float)wb, part) : part;
+            }
+    } else
+    if constexpr (MSK == 1) {  // every tile with per-pixel selects, in the plain forms' order of additions: an
                           // all-ones mask gives their bits, a masked-out NaN stays out of the sum
 #pragma unroll
         for (int r = 0; r < 2; ++r)
@@ -1132,15 +1151,23 @@ __global__ __launch_bounds__(64 * NW, (cost16w_waves<HB, NCH>())) void cost16w_k
 }
 
 // ---- host side: the fast path's launchers (its tables: hq_cost_taps.cpp) ----
-// This file is compiled twice: as it is (the plain instances and launchers) and
-// through hq_cost_masked.hip with HQ_COST_MASKED defined (the MSK instances and
-// launch_cost_fast_masked / launch_cost_chunked_masked), so the two sets build
+// This file is compiled three times: as it is (the plain instances and launchers),
+// through hq_cost_masked.hip with HQ_COST_MASKED defined (the MSK = 1 instances and
+// launch_cost_fast_masked / launch_cost_chunked_masked) and through
+// hq_cost_weighted.hip with HQ_COST_WEIGHTED defined (MSK = 2,
+// launch_cost_fast_weighted / launch_cost_chunked_weighted), so the sets build
 // side by side and the plain set's source is what it was.
-#ifdef HQ_COST_MASKED
+#if defined(HQ_COST_WEIGHTED)
+constexpr bool kMasked = true;  // (the launch covers the live tiles)
+constexpr int kMsk = 2;
+#define HQ_COST_LAUNCHER(name) name##_weighted
+#elif defined(HQ_COST_MASKED)
 constexpr bool kMasked = true;
+constexpr int kMsk = 1;
 #define HQ_COST_LAUNCHER(name) name##_masked
 #else
 constexpr bool kMasked = false;
+constexpr int kMsk = 0;
 #define HQ_COST_LAUNCHER(name) name
 // The two CostTaps<HB> of build_fast_taps.
 size_t fast_taps_bytes(int HB) { return 2 * 2 * sizeof(float) * kNumFilt * (2 * HB + 1); }
@@ -1172,7 +1199,7 @@ static void launch_cost16w(const CostArgs& a0, int P, int de, bool trim, hipStre
     const dim3 grid((unsigned)((kMasked ? a.nlive : a.ntiles) * P)), block(64 * NW);
     with_de(de, [&](auto DE) {
         with_bool(trim, [&](auto TRIM) {
-            constexpr auto kern = cost16w_kernel<HB, DE.value, TRIM.value, NW, NCH, kMasked>;
+            constexpr auto kern = cost16w_kernel<HB, DE.value, TRIM.value, NW, NCH, kMsk>;
             if constexpr (NCH > 1) HQ_LAUNCH_DYN_LDS(kern, grid, block, 8 * (size_t)kMaxK * NCH, s, a, P);
             else HQ_LAUNCH(kern, grid, block, 0, s, a, P);
         });
@@ -1213,7 +1240,7 @@ hipError_t HQ_COST_LAUNCHER(launch_cost_fast)(const CostArgs& a0, int P, int de,
         const dim3 grid((unsigned)((kMasked ? a.nlive : a.ntiles) * P));
         with_de(de, [&](auto DE) {
             with_bool(trim, [&](auto TRIM) {
-                HQ_LAUNCH((cost_mfma_kernel<DE.value, TRIM.value, kMasked>), grid, dim3(256), 0, s, a, P);
+                HQ_LAUNCH((cost_mfma_kernel<DE.value, TRIM.value, kMsk>), grid, dim3(256), 0, s, a, P);
             });
         });
     }

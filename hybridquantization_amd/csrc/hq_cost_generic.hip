@@ -54,7 +54,10 @@ __global__ __launch_bounds__(256) void gen_vpass_kernel(GenArgs a) {
         const int64_t off = (int64_t)(y - a.g.r0) * a.g.lab_pitch + x;
         const float ef = delta_e_f<DE>(a.labL[off], a.labA[off], a.labB[off], lf);
         if (a.pix_err) a.pix_err[q] = ef;  // test option: the per-pixel dE
-        e = a.mask && !a.mask[off] ? 0.0 : (double)ef;  // pixel mask: a select, a masked-out NaN stays out
+        // pixel mask or weights: dE times the byte (a mask's: 0 / 1), an exact double product; a
+        // zero byte is a select, so a masked-out NaN stays out
+        const double wgt = a.mask ? (double)a.mask[off] : 1.0;
+        e = wgt != 0.0 ? (double)ef * wgt : 0.0;
     }
     e = wave_sum(e);
     if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = e;
@@ -303,7 +306,8 @@ __global__ __launch_bounds__(256) void gen_vtile_kernel(GenArgs a, int tiles_x) 
             const int64_t off = (int64_t)(y - g.r0) * g.lab_pitch + gx;
             const float ef = delta_e_f<DE>(a.labL[off], a.labA[off], a.labB[off], lf);
             if (a.pix_err) a.pix_err[(int64_t)(y - g.r0) * g.W + gx] = ef;  // test option: the per-pixel dE
-            part += a.mask && !a.mask[off] ? 0.0 : (double)ef;  // pixel mask: a select, not a product
+            const double wgt = a.mask ? (double)a.mask[off] : 1.0;  // pixel mask or weights (gen_vpass)
+            part += wgt != 0.0 ? (double)ef * wgt : 0.0;
         }
     }
     part = wave_sum_to_lane63(part);
@@ -428,7 +432,8 @@ __global__ __launch_bounds__(256) void gen_vtile2_kernel(GenArgs a, int tiles_x)
             const int64_t off = (int64_t)(y - g.r0) * g.lab_pitch + gx;
             const float ef = delta_e_f<DE>(a.labL[off], a.labA[off], a.labB[off], lf);
             if (a.pix_err) a.pix_err[(int64_t)(y - g.r0) * g.W + gx] = ef;  // test option: the per-pixel dE
-            part += a.mask && !a.mask[off] ? 0.0 : (double)ef;  // pixel mask: a select, not a product
+            const double wgt = a.mask ? (double)a.mask[off] : 1.0;  // pixel mask or weights (gen_vpass)
+            part += wgt != 0.0 ? (double)ef * wgt : 0.0;
         }
     }
     part = wave_sum_to_lane63(part);
@@ -553,7 +558,8 @@ __global__ __launch_bounds__(256) void gen_vmfma_kernel(GenArgs a, int tiles_x) 
                     const int64_t off = (int64_t)(y - gm.r0) * gm.lab_pitch + gx;
                     const float ef = delta_e_f<DE>(a.labL[off], a.labA[off], a.labB[off], lf);
                     if (a.pix_err) a.pix_err[(int64_t)(y - gm.r0) * gm.W + gx] = ef;  // test option: the per-pixel dE
-                    part += a.mask && !a.mask[off] ? 0.0 : (double)ef;  // pixel mask: a select, not a product
+                    const double wgt = a.mask ? (double)a.mask[off] : 1.0;  // pixel mask or weights (gen_vpass)
+                    part += wgt != 0.0 ? (double)ef * wgt : 0.0;
                 }
             }
     part = wave_sum_to_lane63(part);

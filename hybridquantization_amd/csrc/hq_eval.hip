@@ -460,7 +460,7 @@ int cost_args(hq_ctx* c, const GridArgs& ga, const FastGrid& f, int K, int so, i
     ca.pix_pitch = n_own(c->g);
     if (c->mask_on) {
         if (!live_tiles_current(c, f))
-            return fail(c, HQ_ERR_STATE, "pixel mask: the live-tile list is not that of this launch");
+            return fail(c, HQ_ERR_STATE, "%s: the live-tile list is not that of this launch", mask_noun(c));
         ca.mask = c->d_mask.as<uint8_t>();
         ca.live = c->d_live.as<int32_t>();
         ca.nlive = c->n_live;
@@ -481,6 +481,9 @@ int enqueue_cost(hq_ctx* c, const CostArgs& ca, bool fast, const FastGrid& f, in
                        : enqueue_generic_cost(c, Pl, c->d_idx.p, 1, kMaxK, pr, pcost, lo);
     if (c->mask_on && ca.nlive == 0) return HQ_OK;
     HIP_TRY(c, timed_launch(pr, pcost, [&] {
+        if (c->mask_on && c->weights_on)
+            return nch > 1 ? launch_cost_chunked_weighted(ca, Pl, nch, de, trim, s)
+                           : launch_cost_fast_weighted(ca, Pl, de, trim, f.rows, f.tw, c->fast_hb, s);
         if (c->mask_on)
             return nch > 1 ? launch_cost_chunked_masked(ca, Pl, nch, de, trim, s)
                            : launch_cost_fast_masked(ca, Pl, de, trim, f.rows, f.tw, c->fast_hb, s);
@@ -689,6 +692,7 @@ int run_table_kernel(hq_ctx* c, DevBuf& table, size_t n, Pair pair, const char* 
 // HQ_OK.  The image buffers are read, a table of its own is written: the index
 // images, the counter sets and d_sums stay what they are.
 int color_histogram(hq_ctx* c, int bits, int64_t* out, int64_t* den) {
+    if (int rc = weighted_sums_scope(c, "hq_color_histogram")) return rc;
     const size_t n4 = (size_t)4 << (3 * bits);
     std::vector<int64_t> h;
     int rc = run_table_kernel(c, c->d_hist, n4, kPHist, kNoExactSums, h, [&] {
@@ -702,6 +706,7 @@ int color_histogram(hq_ctx* c, int bits, int64_t* out, int64_t* den) {
         owned_range(c->g, &ha.q0, &ha.q1);
         ha.bits = bits;
         ha.mask = c->mask_on ? c->d_maskq.as<uint8_t>() : nullptr;
+        ha.weighted = c->mask_on && c->weights_on;
         return launch_color_histogram(ha, c->num_cu, c->stream);
     });
     if (rc) return rc;
@@ -815,12 +820,15 @@ ClusterArgs cluster_args(hq_ctx* c, int P, int K, int nch, int* idx_bytes) {
     ca.P = P;
     ca.K = K;
     ca.mask = c->mask_on ? c->d_maskq.as<uint8_t>() : nullptr;
+    ca.weighted = c->mask_on && c->weights_on;
+    ca.span = (uint32_t)c->cent_span;
     return ca;
 }
 
 // hq_cluster_sums into `out` ([P][K][4]); nothing is written unless HQ_OK.
 int cluster_sums(hq_ctx* c, int P, int K, int64_t* out, int64_t* den) {
     if (int rc = check_last_population(c, P, K)) return rc;
+    if (int rc = weighted_sums_scope(c, "hq_cluster_sums")) return rc;
     const size_t n4 = (size_t)P * K * 4;
     std::vector<int64_t> h;
     int rc = run_table_kernel(c, c->d_sums, n4, kPSums, kNoExactSums, h, [&] {
@@ -934,6 +942,7 @@ int planar_in_range(hq_ctx* c) {
         int idx_bytes = 1;
         ClusterArgs ca = cluster_args(c, 1, 1, 1, &idx_bytes);  // (the u8 image, d_idx)
         ca.mask = nullptr;    // (the flag looks at every owned pixel with or without a mask)
+        ca.weighted = 0;
         HIP_TRY(c, launch_cluster_sums(ca, 1, c->num_cu, st));
         int bad = 1;
         HIP_TRY(c, hipMemcpyAsync(&bad, ca.bad, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -1159,7 +1168,7 @@ int hq_color_histogram(hq_ctx* c, int bits, int64_t* cells, int64_t* den) {
 int hq_cluster_errors(hq_ctx* c, int P, int K, int64_t* err, float* worst_rgb) {
     if (!c) return HQ_ERR_ARG;
     if (!err || !worst_rgb || P < 1 || K < 1) return fail(c, HQ_ERR_ARG, "bad err / worst_rgb / P=%d / K=%d", P, K);
-    if (c->mask_on) return fail(c, HQ_ERR_UNSUPPORTED, "hq_cluster_errors under a pixel mask (hq_set_mask)");
+    if (c->mask_on) return fail(c, HQ_ERR_UNSUPPORTED, "hq_cluster_errors under %s (%s)", mask_noun(c), mask_call(c));
     return cluster_errors(c, P, K, err, worst_rgb, false);
 }
 
@@ -1168,6 +1177,7 @@ int hq_refine_population(hq_ctx* c, float* palettes, int P, int K, int steps, fl
     int rc = check_improve_args(c, palettes, P, K, steps, costs, "hq_refine_population",
                                 ": add the shards' hq_cluster_sums yourself");
     if (rc) return rc;
+    if (steps > 0 && (rc = weighted_sums_scope(c, "hq_refine_population"))) return rc;
     return improve_population(c, palettes, P, K, steps, delta, keep_best, costs, used, trace,
                               [&](float* cur, bool*) { return kmeans_move(c, P, K, cur); });
 }
@@ -1177,7 +1187,8 @@ int hq_repair_population(hq_ctx* c, float* palettes, int P, int K, int steps, fl
     int rc = check_improve_args(c, palettes, P, K, steps, costs, "hq_repair_population",
                                 ": merge the shards' hq_cluster_errors yourself");
     if (rc) return rc;
-    if (c->mask_on) return fail(c, HQ_ERR_UNSUPPORTED, "hq_repair_population under a pixel mask (hq_set_mask)");
+    if (c->mask_on)
+        return fail(c, HQ_ERR_UNSUPPORTED, "hq_repair_population under %s (%s)", mask_noun(c), mask_call(c));
     const PixelErrScope scope(c);  // the evaluations below store their error images
     std::vector<int> moved(P);
     return improve_population(c, palettes, P, K, steps, delta, keep_best, costs, used, trace,

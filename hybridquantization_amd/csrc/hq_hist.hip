@@ -50,7 +50,12 @@ __device__ __forceinline__ uint32_t hist_coord(float v, int bits) {
 // No LDS, no scratch: every array below is indexed by unrolled constants.
 // MSK (a pixel mask, HistArgs::mask): a masked-out pixel is loaded and not added,
 // like the pixels outside [q0, q1); the range flag still looks at every owned pixel.
-template <bool U8, bool MSK = false>
+// MSK = 2 (pixel weights, hq_set_weights: the mask bytes are the weights): a pixel of weight w > 0
+// adds w times its channels and w to its cell's count -- in the quad merge and in the uniform
+// wave's run too, whose count grows by the wave's weight sum; weight 0 is the masked-out pixel.
+// The words are whole 64-bit sums: w q(v) <= 255 2^32 per pixel, and hq_color_histogram refuses
+// owned weights that sum to 2^31 or more (hq.h), so a total stays below 2^63.
+template <bool U8, int MSK = 0>
 __global__ __launch_bounds__(256) void hist_kernel(HistArgs a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int bits = a.bits;
@@ -83,9 +88,10 @@ __global__ __launch_bounds__(256) void hist_kernel(HistArgs a) {
         const uint32_t q = qa + 4u * min(j, nq - 1u);
         uint64_t r[4], g[4], b[4];
         uint32_t cell[4];
+        uint64_t wt[4] = {1ull, 1ull, 1ull, 1ull};  // what a pixel adds to its cell's count
         bool ok[4];
-        uint32_t mq = ~0u;  // MSK: the quad's mask bytes
-        if constexpr (MSK) mq = *reinterpret_cast<const uint32_t*>(a.mask + q);
+        uint32_t mq = ~0u;  // MSK: the quad's mask bytes (MSK = 2: its weights)
+        if constexpr (MSK != 0) mq = *reinterpret_cast<const uint32_t*>(a.mask + q);
         if constexpr (U8) {
             const uint4 px = *reinterpret_cast<const uint4*>(a.rgbx + q);
             const uint32_t v[4] = {px.x, px.y, px.z, px.w};
@@ -93,9 +99,13 @@ __global__ __launch_bounds__(256) void hist_kernel(HistArgs a) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 ok[i] = in && q + i >= a.q0 && q + i < a.q1;
-                if constexpr (MSK) ok[i] = ok[i] && ((mq >> (8 * i)) & 0xffu) != 0u;
+                if constexpr (MSK != 0) ok[i] = ok[i] && ((mq >> (8 * i)) & 0xffu) != 0u;
                 const uint32_t rb = v[i] & 0xffu, gb = (v[i] >> 8) & 0xffu, bb = (v[i] >> 16) & 0xffu;
                 r[i] = rb, g[i] = gb, b[i] = bb;
+                if constexpr (MSK == 2) {
+                    wt[i] = (mq >> (8 * i)) & 0xffu;
+                    r[i] *= wt[i], g[i] *= wt[i], b[i] *= wt[i];
+                }
                 cell[i] = ((rb >> sh) << (2 * bits)) | ((gb >> sh) << bits) | (bb >> sh);
             }
         } else {
@@ -113,9 +123,13 @@ __global__ __launch_bounds__(256) void hist_kernel(HistArgs a) {
                                   vb[i] <= 1.f;
                 bad |= own && !fits;
                 ok[i] = own && fits;
-                if constexpr (MSK) ok[i] = ok[i] && ((mq >> (8 * i)) & 0xffu) != 0u;
+                if constexpr (MSK != 0) ok[i] = ok[i] && ((mq >> (8 * i)) & 0xffu) != 0u;
                 const float cr = fits ? vr[i] : 0.f, cg = fits ? vg[i] : 0.f, cb = fits ? vb[i] : 0.f;
                 r[i] = hist_q32(cr), g[i] = hist_q32(cg), b[i] = hist_q32(cb);
+                if constexpr (MSK == 2) {  // (at most 255 2^32: exact)
+                    wt[i] = (mq >> (8 * i)) & 0xffu;
+                    r[i] *= wt[i], g[i] *= wt[i], b[i] *= wt[i];
+                }
                 cell[i] = (hist_coord(cr, bits) << (2 * bits)) | (hist_coord(cg, bits) << bits) | hist_coord(cb, bits);
             }
             if (bad) *a.bad = 1;
@@ -129,18 +143,20 @@ __global__ __launch_bounds__(256) void hist_kernel(HistArgs a) {
             const uint64_t wb = hist_wave_sum(b[0] + b[1] + b[2] + b[3]);
             if (run_n && run_cell != c0) flush();
             run_cell = c0;
-            run_r += wr, run_g += wg, run_b += wb, run_n += 256ull;
+            if constexpr (MSK == 2) run_n += hist_wave_sum(wt[0] + wt[1] + wt[2] + wt[3]);  // the wave's weight sum
+            else run_n += 256ull;
+            run_r += wr, run_g += wg, run_b += wb;
         } else {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 bool lead = ok[i];  // the first owned pixel of its cell in the quad adds for the later ones
 #pragma unroll
                 for (int k = 0; k < i; ++k) lead = lead && !(ok[k] && cell[k] == cell[i]);
-                uint64_t sr = r[i], sg = g[i], sb = b[i], sn = 1ull;
+                uint64_t sr = r[i], sg = g[i], sb = b[i], sn = wt[i];
 #pragma unroll
                 for (int k = i + 1; k < 4; ++k) {
                     const bool m = ok[k] && cell[k] == cell[i];
-                    sr += m ? r[k] : 0ull, sg += m ? g[k] : 0ull, sb += m ? b[k] : 0ull, sn += m ? 1ull : 0ull;
+                    sr += m ? r[k] : 0ull, sg += m ? g[k] : 0ull, sb += m ? b[k] : 0ull, sn += m ? wt[k] : 0ull;
                 }
                 if (lead) add(cell[i], sr, sg, sb, sn);
             }
@@ -159,7 +175,7 @@ hipError_t launch_color_histogram(const HistArgs& a0, int num_cu, hipStream_t s)
     a.qspan = ((nq + want - 1) / want + 255u) / 256u * 256u;
     a.nblocks = (int)((nq + a.qspan - 1) / a.qspan);
     with_bool(a.rgbx != nullptr, [&](auto U8) {
-        with_bool(a.mask != nullptr, [&](auto MSK) {
+        with_mask(a.mask != nullptr, a.weighted != 0, [&](auto MSK) {
             HQ_LAUNCH((hist_kernel<U8.value, MSK.value>), dim3((unsigned)a.nblocks), dim3(256), 0, s, a);
         });
     });

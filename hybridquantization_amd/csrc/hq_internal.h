@@ -250,7 +250,9 @@ struct CostArgs {
     float* pix_err;  // test option "pixel_err": [P][pix_pitch] per-pixel dE of the owned rows
     int64_t pix_pitch;  // (null: not written)
     // pixel mask (hq_set_mask; read by the masked instances only, hq_cost_masked.hip): a byte per
-    // owned pixel at the LabRef planes' pitch, (y - r0) lab_pitch + x, non-zero = the pixel counts
+    // owned pixel at the LabRef planes' pitch, (y - r0) lab_pitch + x, non-zero = the pixel counts.
+    // Pixel weights (hq_set_weights; the weighted instances, hq_cost_weighted.hip) use the same
+    // three fields: the byte is the pixel's weight, 0 = the pixel is left out
     const uint8_t* mask;
     const int32_t* live;    // their work items' tiles: item w is palette w % P over tile live[w / P]
     int nlive;              // entries of live (the launch covers nlive P items)
@@ -291,8 +293,12 @@ constexpr int kCentLdsK = kMaxK;          // K up to here (the u8 index images):
                                           // above: global atomics straight away
 constexpr int kCentBlocksPerCu = 4;       // workgroups per CU over all palette groups
 // pixels per workgroup, at most: the packed form (32-bit fields of byte sums), the planar form
-// (a 16-bit count above a 48-bit sum of values up to 2^32)
-__host__ __device__ constexpr uint32_t cent_max_span(bool u8) { return u8 ? 1u << 22 : 1u << 15; }
+// (a 16-bit count above a 48-bit sum of values up to 2^32).  Under pixel weights (a pixel adds
+// up to 255 times as much): the packed form's 32-bit fields hold 2^16 pixels of 255 255; the
+// planar form has four whole 64-bit words per colour, 2^22 pixels of 255 2^32 < 2^40 each.
+__host__ __device__ constexpr uint32_t cent_max_span(bool u8, bool weighted = false) {
+    return weighted ? (u8 ? 1u << 16 : 1u << 22) : (u8 ? 1u << 22 : 1u << 15);
+}
 struct ClusterArgs {
     const void* idx;        // [P][idx_pitch] index images over the extended rows: u8, u16 or u32
     const float* R;         // planar, extended rows (padded to a multiple of 4 floats)
@@ -310,6 +316,11 @@ struct ClusterArgs {
     // non-zero = the pixel is added; null: every owned pixel.  The range flag looks at every owned
     // pixel either way.
     const uint8_t* mask = nullptr;
+    // pixel weights (hq_set_weights): mask holds the weights, and a pixel adds weight times its
+    // channels and its weight to the count
+    int weighted = 0;
+    // test option "cent_span": pixels per workgroup (0: by the grid), clamped to cent_max_span
+    uint32_t span = 0;
 };
 
 // Per-colour error statistics of the last evaluated population (hq_errsum.hip,
@@ -353,6 +364,7 @@ struct HistArgs {
     int nblocks;            // workgroups                           } set by the
     uint32_t qspan;         // quads of 4 pixels per workgroup      } launcher
     const uint8_t* mask = nullptr;  // pixel mask (ClusterArgs::mask), or null
+    int weighted = 0;               // pixel weights (ClusterArgs::weighted)
 };
 
 // lloyd_update_kernel (hq_search.hip): the k-means move of a device-resident
@@ -411,7 +423,9 @@ struct GenArgs {
     int shape = 0;       // matrix-core pair's tile shapes: 0 by grid size, 1 the short forms, 2 the tall ones
     const uint32_t* htapd = nullptr;  // its taps, the same layout (k3 signed: the horizontal t3 taps)
     const float4* htaps = nullptr;  // gen_hrow4: [T][2] (k1.xyz, k3), (k2.xyz, 0) horizontal taps
-    const uint8_t* mask = nullptr;  // pixel mask (CostArgs::mask's layout), or null: every owned pixel counts
+    // pixel mask or pixel weights (CostArgs::mask's layout): a pixel's dE times its byte, as
+    // doubles (a mask's bytes are 0 / 1), a zero byte a select; null: every owned pixel counts
+    const uint8_t* mask = nullptr;
 };
 
 }  // namespace hq

@@ -35,6 +35,13 @@ inline void with_bool(bool b, F&& f) {
     if (b) f(std::true_type{});
     else f(std::false_type{});
 }
+// No mask (0), a pixel mask (1) or pixel weights (2): the MSK template argument.
+template <typename F>
+inline void with_mask(bool mask, bool weighted, F&& f) {
+    if (!mask) f(std::integral_constant<int, 0>{});
+    else if (!weighted) f(std::integral_constant<int, 1>{});
+    else f(std::integral_constant<int, 2>{});
+}
 // Palette index width: 1 byte, 2 (chunked palettes) or 4 (K > 4096).
 template <typename T>
 struct type_tag { using type = T; };
@@ -124,6 +131,10 @@ hipError_t launch_cost_chunked(const CostArgs&, int P, int nch, int de, bool tri
 hipError_t launch_cost_fast_masked(const CostArgs&, int P, int de, bool trim, int tile_rows, int tile_w, int HB,
                                    hipStream_t);
 hipError_t launch_cost_chunked_masked(const CostArgs&, int P, int nch, int de, bool trim, hipStream_t);
+// hq_cost_weighted.hip: the same under pixel weights (CostArgs::mask holds the weights)
+hipError_t launch_cost_fast_weighted(const CostArgs&, int P, int de, bool trim, int tile_rows, int tile_w, int HB,
+                                     hipStream_t);
+hipError_t launch_cost_chunked_weighted(const CostArgs&, int P, int nch, int de, bool trim, hipStream_t);
 // hq_cost_generic.hip: any half-width, one palette per launch pair
 hipError_t launch_cost_generic(const GenArgs&, int de, int idx_bytes, hipStream_t);
 hipError_t launch_cost_tiled_generic(const GenArgs&, int de, int idx_bytes, hipStream_t);

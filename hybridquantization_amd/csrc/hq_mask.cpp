@@ -1,5 +1,5 @@
-// hq_mask.cpp -- the pixel mask's host code: the count of in-mask pixels and the
-// live-tile list of the fast cost kernels (hq_mask.h).  No GPU code: `make
+// hq_mask.cpp -- the pixel mask's and the pixel weights' host code: the count of in-mask
+// pixels, the sum of weights and the live-tile list of the fast cost kernels (hq_mask.h).  No GPU code: `make
 // mask_check` builds this file alone under the sanitizers.
 #include "hq_mask.h"
 
@@ -11,6 +11,12 @@ int64_t mask_count(const uint8_t* mask, int64_t n) {
     int64_t c = 0;
     for (int64_t i = 0; i < n; ++i) c += mask[i] != 0;
     return c;
+}
+
+int64_t weight_sum(const uint8_t* weights, int64_t n) {
+    int64_t s = 0;
+    for (int64_t i = 0; i < n; ++i) s += weights[i];
+    return s;
 }
 
 int mask_live_tiles(const uint8_t* own, const TileGrid& g, bool skip, int32_t* out) {

@@ -281,6 +281,11 @@ struct hq_ctx {
     std::vector<uint8_t> mask_own;
     hq::DevBuf d_mask, d_maskq;
     int64_t mask_n_full = 0, mask_n_own = 0;
+    // pixel weights (hq_set_weights) are the same piece of state: mask_on and weights_on, the
+    // three copies hold the raw bytes (non-zero = the pixel counts, by its byte), mask_n_* count
+    // the non-zero ones and mask_w_* are the weight sums (of a mask: mask_n_*)
+    bool weights_on = false;
+    int64_t mask_w_full = 0, mask_w_own = 0;
     // the live-tile list of the fast cost launch (ensure_live_tiles): rebuilt when the mask or
     // the launch's tile grid or whether it skips has changed, never inside a capture
     hq::DevBuf d_live;
@@ -322,6 +327,7 @@ struct hq_ctx {
                            // round trip per iteration), 0 = host-driven (one eval call each)
     int pixel_err = 0;     // test option: the cost kernels also write the per-pixel dE
     int dither_rows = 1024;  // hq_dither_population: rows per strip (option "dither_rows")
+    int cent_span = 0;       // test option "cent_span": the sums kernel's pixels per workgroup (0: by the grid)
     int trim = 1;          // skip taps < 1e-9 of the peak of the narrow k1 filters
     bool trim_ok = false;  // set by hq_set_filters (the bucket's narrow-filter windows hold)
     bool pal_generic = false;  // this population needs the generic cost path (palette_fits_fast)
@@ -475,10 +481,18 @@ int ensure_dither_map(hq_ctx* c);
 // mask W H, the expression it always was); the refusal of a palette slice under a mask; the
 // live-tile list on the device for the launch the options in force select (ensure_population
 // calls it: before anything is enqueued or captured)
+// (pixel weights: their sum over the full image, below 2^53 and so exact)
 inline double cost_divisor(const hq_ctx* c) {
-    return c->mask_on ? (double)c->mask_n_full : (double)c->g.W * (double)c->g.H;
+    return c->mask_on ? (double)c->mask_w_full : (double)c->g.W * (double)c->g.H;
 }
 int mask_scope(hq_ctx* c);
+// "a pixel mask" / "(hq_set_mask)" or "pixel weights" / "(hq_set_weights)": the refusals' wording
+inline const char* mask_noun(const hq_ctx* c) { return c->weights_on ? "pixel weights" : "a pixel mask"; }
+inline const char* mask_call(const hq_ctx* c) { return c->weights_on ? "hq_set_weights" : "hq_set_mask"; }
+// pixel weights on the planar form (sums in units of 2^-32): HQ_ERR_UNSUPPORTED when the owned
+// rows' weights sum to 2^31 or more (a total could pass 2^63); made on the host, before `what`
+// enqueues anything
+int weighted_sums_scope(hq_ctx* c, const char* what);
 int ensure_live_tiles(hq_ctx* c);
 
 }  // namespace hq

@@ -66,7 +66,14 @@ int whole_image_only(hq_ctx* c, const char* what, const char* comm_hint, bool ps
 // slice (its rows of d_out, its counters) under one is left out.
 int mask_scope(hq_ctx* c) {
     if (c->mask_on && (c->psplit || c->slice_ranks > 1))
-        return fail(c, HQ_ERR_UNSUPPORTED, "a palette slice (option palette_split or slice_ranks) under a pixel mask");
+        return fail(c, HQ_ERR_UNSUPPORTED, "a palette slice (option palette_split or slice_ranks) under %s", mask_noun(c));
+    return HQ_OK;
+}
+
+int weighted_sums_scope(hq_ctx* c, const char* what) {
+    if (c->mask_on && c->weights_on && !sums_u8(c) && c->mask_w_own >= kWeightSumLimit)
+        return fail(c, HQ_ERR_UNSUPPORTED, "%s: the owned rows' weights sum to %lld >= 2^31, and the planar form's "
+                                           "sums (units of 2^-32) could pass 2^63", what, (long long)c->mask_w_own);
     return HQ_OK;
 }
 
@@ -172,7 +179,7 @@ int set_image_common(hq_ctx* c, const std::vector<float>& R, const std::vector<f
     // c->g is the new image's already: nothing evaluated on the old one may be read at it
     c->have_image = false;  // (until every plane below is in place)
     drop(c);
-    c->mask_on = false;  // a mask belongs to an image
+    c->mask_on = c->weights_on = false;  // a mask, or a weight map, belongs to an image
     c->live_dirty = true;
     const size_t plane = sizeof(float) * (size_t)round_up(g.n_ext, 4);
     HIP_TRY(c, c->d_R.ensure(plane));
@@ -418,30 +425,35 @@ int hq_set_image_planar_shard(hq_ctx* c, const float* R, const float* G, const f
     return set_image_common(c, r, g, b, nullptr, illum);
 }
 
-int hq_set_mask(hq_ctx* c, const uint8_t* mask, int w, int h) {
+namespace {
+
+// hq_set_mask (weights false: the copies hold 0 / 1) and hq_set_weights (the raw bytes)
+int set_mask_or_weights(hq_ctx* c, const uint8_t* mask, int w, int h, bool weights) {
     if (!c) return HQ_ERR_ARG;
+    const char* const what = weights ? "weight map" : "mask";
     if (!mask) {  // no mask: the state of a fresh context
-        c->mask_on = false;
+        c->mask_on = c->weights_on = false;
         c->live_dirty = true;
         return HQ_OK;
     }
     if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
     const Geom& g = c->g;
-    if (w != g.W || h != g.H) return fail(c, HQ_ERR_ARG, "mask of %d x %d on an image of %d x %d", w, h, g.W, g.H);
+    if (w != g.W || h != g.H) return fail(c, HQ_ERR_ARG, "%s of %d x %d on an image of %d x %d", what, w, h, g.W, g.H);
     const int64_t n_full = mask_count(mask, (int64_t)g.W * g.H);
-    if (n_full == 0) return fail(c, HQ_ERR_ARG, "mask without a non-zero byte: no pixel would count");
+    if (n_full == 0) return fail(c, HQ_ERR_ARG, "%s without a non-zero byte: no pixel would count", what);
     int rc = bind(c);
     if (rc) return rc;
     // the three copies, built aside so that a failure leaves the mask in force as it was: the
-    // owned rows as 0 / 1; at the LabRef planes' pitch (the cost kernels read a dword of 4 pixels
-    // next to their LabRef float4s); over the extended rows' positions (the quads of the sums
-    // and histogram kernels), zero outside the owned rows and in the padding
+    // owned rows as 0 / 1 (weights: the bytes as they are); at the LabRef planes' pitch (the cost
+    // kernels read a dword of 4 pixels next to their LabRef float4s); over the extended rows'
+    // positions (the quads of the sums and histogram kernels), zero outside the owned rows and in
+    // the padding
     const int own = g.r1 - g.r0;
     std::vector<uint8_t> rows((size_t)g.W * own), lab((size_t)g.lab_pitch * std::max(own, 1) + 16, 0),
         ext((size_t)round_up(g.n_ext, 4) + 16, 0);
     for (int y = 0; y < own; ++y)
         for (int x = 0; x < g.W; ++x) {
-            const uint8_t v = mask[(size_t)(g.r0 + y) * g.W + x] != 0;
+            const uint8_t b = mask[(size_t)(g.r0 + y) * g.W + x], v = weights ? b : (uint8_t)(b != 0);
             rows[(size_t)y * g.W + x] = v;
             lab[(size_t)y * g.lab_pitch + x] = v;
             ext[(size_t)(g.r0 - g.e0 + y) * g.W + x] = v;
@@ -455,8 +467,27 @@ int hq_set_mask(hq_ctx* c, const uint8_t* mask, int w, int h) {
     c->mask_own.swap(rows);
     c->mask_n_full = n_full;
     c->mask_n_own = mask_count(c->mask_own.data(), (int64_t)c->mask_own.size());
+    c->mask_w_full = weights ? weight_sum(mask, (int64_t)g.W * g.H) : n_full;
+    c->mask_w_own = weight_sum(c->mask_own.data(), (int64_t)c->mask_own.size());
     c->mask_on = true;
+    c->weights_on = weights;
     c->live_dirty = true;  // (the list: built by the next evaluation, ensure_live_tiles)
+    return HQ_OK;
+}
+
+}  // namespace
+
+int hq_set_mask(hq_ctx* c, const uint8_t* mask, int w, int h) { return set_mask_or_weights(c, mask, w, h, false); }
+
+int hq_set_weights(hq_ctx* c, const uint8_t* weights, int w, int h) {
+    return set_mask_or_weights(c, weights, w, h, true);
+}
+
+int hq_weights_info(hq_ctx* c, int64_t* w_full, int64_t* w_owned) {
+    if (!c) return HQ_ERR_ARG;
+    const Geom& g = c->g;
+    if (w_full) *w_full = c->mask_on ? c->mask_w_full : c->have_image ? (int64_t)g.W * g.H : 0;
+    if (w_owned) *w_owned = c->mask_on ? c->mask_w_own : c->have_image ? n_own(g) : 0;
     return HQ_OK;
 }
 
@@ -695,6 +726,9 @@ int hq_set_option(hq_ctx* c, const char* name, int value) {
         if (value < 64 || value > 1024 || value % 64)
             return fail(c, HQ_ERR_ARG, "dither_rows must be a multiple of 64 in 64 .. 1024");
         c->dither_rows = value;
+    } else if (!std::strcmp(name, "cent_span")) {
+        if (value < 0) return fail(c, HQ_ERR_ARG, "cent_span must be >= 0 (0 = auto)");
+        c->cent_span = value;
     } else if (!std::strcmp(name, "assign_blocks_per_cu")) {
         if (value < 0 || value > 64) return fail(c, HQ_ERR_ARG, "assign_blocks_per_cu in [0,64] (0 = auto)");
         c->assign_blocks_per_cu = value;

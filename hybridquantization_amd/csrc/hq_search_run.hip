@@ -90,7 +90,7 @@ bool period_in_run(const hq_search* s, int every, int ite, int iterations) {
 int repair_scope(hq_search* s) {
     hq_ctx* c = s->ctx;
     if (c->mask_on)  // (a masked error statistic does not exist: hq_cluster_errors' refusal)
-        return fail(c, HQ_ERR_UNSUPPORTED, "repair iterations under a pixel mask (hq_set_mask)");
+        return fail(c, HQ_ERR_UNSUPPORTED, "repair iterations under %s (%s)", mask_noun(c), mask_call(c));
     if (c->de_type == HQ_DE_CIE94)
         return fail(c, HQ_ERR_UNSUPPORTED, "repair iterations on a dE94 context: its costs are NaN on real images");
     if (int rc = whole_image_only(c, "repair iterations")) return rc;
@@ -103,6 +103,7 @@ int repair_scope(hq_search* s) {
 int lloyd_validate(hq_search* s) {
     hq_ctx* c = s->ctx;
     if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
+    if (int rc = weighted_sums_scope(c, "hybrid iterations")) return rc;
     return sums_u8(c) ? HQ_OK : require_unit_range_image(c, "planar image", "no exact sums, no hybrid iteration");
 }
 

@@ -381,6 +381,42 @@ class ImageManipulation:
         check(self._lib.hq_mask_info(ctx, *[C.byref(x) for x in v]), ctx)
         return tuple(x.value for x in v)
 
+    # pixel weights on the cost: libhq's addition (hq_set_weights, no reference counterpart)
+    def setWeights(self, weights=None):
+        """hq_set_weights: weigh every pixel's error by ``weights`` -- an (h, w) or flat array of
+        the FULL image, any integer or bool dtype, values 0 .. 255 (0: the pixel is left out).
+        Every cost becomes sum(w dE) / sum(w); clusterSums and colorHistogram weigh their sums
+        and counts the same way, so k-means moves and the median-cut seed follow the map.  None
+        clears it.  Mask and weights are one piece of state: the last of setMask / setWeights
+        wins, and setImage drops it.  A float dtype, a value outside 0 .. 255 or a wrong shape is
+        a ValueError.  Refused under weights as under a mask: palette slices, clusterErrors and
+        the repair moves; on a planar (non-8-bit) image clusterSums, colorHistogram and hybrid
+        iterations also need the owned rows' weights to sum to less than 2**31."""
+        ctx = self._require()
+        if weights is None:
+            check(self._lib.hq_set_weights(ctx, None, 0, 0), ctx)
+            return
+        m = np.asarray(weights)
+        if m.dtype != np.bool_ and not np.issubdtype(m.dtype, np.integer):
+            raise ValueError(f"weights of dtype {m.dtype}: an integer or bool array")
+        if m.ndim not in (1, 2):
+            raise ValueError(f"weights of shape {m.shape}: (h, w) or flat")
+        w, h = getattr(self, "w", 0), getattr(self, "h", 0)
+        if (m.ndim == 2 and m.shape != (h, w)) or m.size != w * h:
+            raise ValueError(f"weights of shape {m.shape} on an image of {h} x {w}")
+        if m.size and (int(m.min()) < 0 or int(m.max()) > 255):
+            raise ValueError(f"weights in {int(m.min())} .. {int(m.max())}: bytes, 0 .. 255")
+        m = np.ascontiguousarray(m.reshape(-1), dtype=np.uint8)
+        check(self._lib.hq_set_weights(ctx, _lib.u8ptr(m), w, h), ctx)
+
+    def weightsInfo(self):
+        """hq_weights_info -> (w_full, w_owned): the sum of the weights over the full image and
+        over the owned rows (under a mask or with nothing set: maskInfo's n_full, n_owned)."""
+        ctx = self._require()
+        v = [C.c_int64() for _ in range(2)]
+        check(self._lib.hq_weights_info(ctx, *[C.byref(x) for x in v]), ctx)
+        return tuple(x.value for x in v)
+
     # seeding the search from the image: libhq's additions (hq_color_histogram, hq_median_cut)
     def colorHistogram(self, bits: int = 5):
         """Colour histogram of the owned rows of the image set: (cells int64
@@ -410,7 +446,8 @@ class ImageManipulation:
                              simulatedAnnealing, filters, absfilters, illuminant,
                              iterations=None, stop=None, lloydSteps=0, lloydEvery=0,
                              init=None, initBits=5, repairEvery=0, repairMoves=-1, repairSteps=0,
-                             dither=0.0, ditherSearch=False, ordered=None, orderedSearch=False, mask=None):
+                             dither=0.0, ditherSearch=False, ordered=None, orderedSearch=False, mask=None,
+                             weights=None):
         """Full SWASA search (IM:383-591) on the GPU; returns bestColors float[4K].
 
         ``simulatedAnnealing`` is a :class:`~hybridquantization_amd.swasa.SWASA`;
@@ -458,10 +495,19 @@ class ImageManipulation:
         ``init="mediancut"`` (the histogram of the region) and every reported error.  The
         repair moves have no masked form: ``repairEvery`` / ``repairSteps`` with a mask raise
         ValueError before anything runs.
+        ``weights`` (hq_set_weights; setWeights' argument, bytes 0 .. 255): every pixel's error
+        counts by its weight, in the search, the polishes, ``init="mediancut"`` and every
+        reported error, exactly where a mask would apply.  ``mask`` and ``weights`` together,
+        or ``weights`` with ``repairEvery`` / ``repairSteps`` (no weighted error statistic),
+        raise ValueError before anything runs.
         """
         ctx = self._require()
+        if mask is not None and weights is not None:
+            raise ValueError("mask and weights: one piece of state, give one of them")
         if mask is not None and (int(repairEvery) != 0 or int(repairSteps) != 0):
             raise ValueError("mask with repairEvery or repairSteps: no masked error statistic")
+        if weights is not None and (int(repairEvery) != 0 or int(repairSteps) != 0):
+            raise ValueError("weights with repairEvery or repairSteps: no weighted error statistic")
         amp = None if ordered is None else self._amp3(ordered)
         if orderedSearch and (amp is None or not np.any(amp != 0)):
             raise ValueError("orderedSearch needs a non-zero ordered amplitude")
@@ -484,6 +530,8 @@ class ImageManipulation:
         self.setImage(inlinergbOriginal, inlineScielabOriginal, w, illuminant)
         if mask is not None:
             self.setMask(mask)
+        if weights is not None:
+            self.setWeights(weights)
         sw = simulatedAnnealing
         params = sw.params()
         handle = C.c_void_p()

@@ -88,7 +88,7 @@ def makeChannels(inline):
 
 def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
                  whitepoint=Whitepoint.D65, verbose=False, device=0, iterations=None, dither=0.0,
-                 ordered=None, mask=None):
+                 ordered=None, mask=None, weights=None):
     """HQ:93-137 without the GUI: planar float image (3, N) in [0,1] ->
     (quantized planar image (3, N), bestColors float[4K], best error).  ``dither`` > 0
     (libhq's addition): the returned image is the best palette's Floyd-Steinberg rendering
@@ -96,7 +96,9 @@ def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
     ``ordered`` (an amplitude, a float or three; not together with ``dither``): the returned
     image is the best palette's ordered-dither rendering (ImageManipulation.quantizeOrdered).
     ``mask`` (ImageManipulation.setMask's argument): the search and the returned error measure
-    the pixels where it is non-zero only; the whole image is rendered."""
+    the pixels where it is non-zero only; the whole image is rendered.  ``weights``
+    (ImageManipulation.setWeights' argument, bytes 0 .. 255; not together with ``mask``): the
+    search and the returned error weigh every pixel's error by it."""
     if ordered is not None and float(dither) > 0.0:
         raise ValueError("dither and ordered: one rendering")
     ip = ImageManipulation(deltaETypes.CIE76, verbose, swasa.convergence, device=device)
@@ -105,7 +107,7 @@ def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
         sp = ScielabProcessor(dpi, viewingDistance, whitepoint, None, ip)
         sc_img = sp.sRGBToScielab(image, w)
         best = sp.bestColors(inline_rgb, sc_img, w, nbOfColors, swasa, iterations=iterations, dither=dither,
-                             ordered=ordered, mask=mask)
+                             ordered=ordered, mask=mask, weights=weights)
         q = (ip.quantizeOrdered(best, ordered) if ordered is not None else
              ip.quantizeDithered(best, dither) if float(dither) > 0.0 else ip.quantize(inline_rgb, best))
         return np.stack(makeChannels(q)), best, ip.bestError

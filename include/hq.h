@@ -401,8 +401,8 @@ int hq_ordered_population_partial(hq_ctx *ctx, const float *palettes, int P, int
  *    it seeds from the region.
  *  Both use the mask in force when they are called.
  * An all-ones mask gives the unmasked library's outputs bit for bit; no mask set
- * is the unmasked code path itself.  Weights other than 0 / 1 do not exist: the
- * exact integer sums above are sized for counts of 1.
+ * is the unmasked code path itself.  Weights other than 0 / 1: hq_set_weights,
+ * below.
  *
  * hq_set_mask: `mask` points at the full image's mask, as hq_set_image_shard's
  * pointers do; a shard keeps its owned rows, every rank passes the same mask, and
@@ -435,6 +435,70 @@ int hq_set_mask(hq_ctx *ctx, const uint8_t *mask, int w, int h);
  * pointer may be NULL. */
 int hq_mask_info(hq_ctx *ctx, int64_t *n_full, int64_t *n_owned, int64_t *tiles_run,
                  int64_t *tiles_all);
+
+/* ---- pixel weights on the cost: libhq's addition, no reference counterpart ----
+ * An importance map: one byte per pixel of the FULL image, weights[y*w + x]; the
+ * pixel's weight w is the byte's integer value, 0 .. 255, and says how much the
+ * pixel's dE matters.  W = the sum of the weights over the full image.  Mask and
+ * weights are ONE piece of state: the last of hq_set_mask / hq_set_weights wins,
+ * NULL to either clears it, hq_set_image* drops it, hq_set_filters keeps it.  With
+ * weights in force everything the mask's block says holds, with these changes:
+ *  - the argmin, the stencil, index images, used flags and the stored per-pixel dE
+ *    keep their bits, as under a mask.
+ *  - costs[p] = (sum over the owned pixels with w > 0 of w * dE) / W + delta *
+ *    #unused; hq_eval_population_partial's partial[p*(1+K)] is the weighted sum over
+ *    the owned rows.  A pixel of weight 0 is left out by a select, so its NaN stays
+ *    out.  The arithmetic, operation by operation: the fast cost kernels add a
+ *    pixel to its thread's fp32 partial by one fused multiply-add, part = fma(dE,
+ *    (float)w, part), over the pixels in the masked kernels' order; the partials
+ *    then go the masked kernels' way (to double, wave sum, fixed point).  The
+ *    generic kernels add the exact double product (double)dE * (double)w to their
+ *    double partial.  The finished sum is divided by (double)W, exact below 2^53.
+ *    Consequences: a weight map of zeros and ones is hq_set_mask of the same map
+ *    BIT FOR BIT in every output (fma(e, 1, part) = part + e), and so all ones is
+ *    the unmasked library.  A uniform map of value c > 1 is the unweighted cost
+ *    within 1e-6 relative, NOT bit for bit: each fma rounds c * dE + part once,
+ *    where the unweighted kernel rounds dE + part.
+ *    This holds for every evaluation the mask serves: plain, partial, dithered,
+ *    ordered, hq_refine_population's, host-driven and device-resident searches
+ *    (bit for bit the same search, option "sa_graph" 0 and 1), hybrid iterations,
+ *    hq_search_create_from.
+ *  - hq_cluster_sums (and hq_refine_population's, a hybrid iteration's and the
+ *    device-resident search's k-means move): sums = (sum w*qR, sum w*qG, sum w*qB,
+ *    sum w) over the owned pixels of non-zero weight, den and units unchanged, so
+ *    hq_centroids_from_sums' sum / (den * count) is the weighted mean.  The planar
+ *    form's range check keeps looking at every owned pixel.
+ *    den = 255: nothing can overflow (a pixel adds at most 255 * 255; 2^30 pixels
+ *    stay below 2^46).  den = 2^32: a pixel adds up to 255 * 2^32, so the sums are
+ *    safe exactly while the owned rows' weights sum to LESS THAN 2^31; at or above
+ *    that hq_cluster_sums, hq_color_histogram, hq_refine_population (steps > 0) and
+ *    the hq_search_run that would run a hybrid iteration return
+ *    HQ_ERR_UNSUPPORTED, outputs and state untouched, *ran = 0; the check is made on
+ *    the host before anything is enqueued.  This admits a planar 4096 x 4096 image
+ *    only up to a mean weight just under 128 (2^31 / 2^24); the packed 8-bit form
+ *    has no such limit.
+ *  - hq_color_histogram: cells weighted the same way, count = sum w; hq_median_cut
+ *    takes such cells unchanged, so the seed follows the weights.
+ *  - hq_mask_info's n_full / n_owned count the pixels of non-zero weight;
+ *    tiles_run / tiles_all keep their meaning (a tile is live when it holds an
+ *    owned pixel of non-zero weight; option "mask_skip" as under a mask).
+ * Refused while weights are set, exactly as under a mask (HQ_ERR_UNSUPPORTED,
+ * outputs and evaluated state untouched): palette slices ("palette_split",
+ * "slice_ranks" > 1); hq_cluster_errors, hq_repair_population,
+ * hq_search_set_repair(every > 0) and a run with a repair iteration.  Left out: a
+ * weighted error statistic and repair; weights other than bytes; a weight-aware
+ * used[]; the JNI / Java binding.
+ *
+ * hq_set_weights: pointer, shard, argument and error rules are hq_set_mask's
+ * (HQ_ERR_STATE without an image; HQ_ERR_ARG for w, h other than the image's or an
+ * all-zero map, the state in force kept; NULL clears).  Like the mask it does not
+ * end the read-back getters' answers, and a search uses what is in force when an
+ * iteration is enqueued. */
+int hq_set_weights(hq_ctx *ctx, const uint8_t *weights, int w, int h);
+/* *w_full = the sum of the weights over the full image, *w_owned = over the owned
+ * rows.  Under a mask or with nothing set every counted pixel weighs 1: these are
+ * then hq_mask_info's n_full and n_owned.  Either pointer may be NULL. */
+int hq_weights_info(hq_ctx *ctx, int64_t *w_full, int64_t *w_owned);
 
 /* ---- seeding the search from the image: libhq's additions, no reference counterpart ----
  * The reference starts every search from uniform random palettes (SW:40-52).
@@ -688,7 +752,11 @@ int hq_profile_reset(hq_ctx *ctx);
  *   "dither_rows"  hq_dither_population: rows per strip of the dither kernel, a multiple of 64
  *                  in 64 .. 1024 (default 1024; anything else is HQ_ERR_ARG).  The results do
  *                  not depend on it, bit for bit: it lets small test images cross strips
- *   "mask_skip"    under a pixel mask (hq_set_mask): 1 (default) = the fast cost kernels launch
+ *   "cent_span"    test only: pixels per workgroup of the k-means sums kernel (0, default: by
+ *                  the grid), rounded up to whole steps of 1024 and clamped to the bound of the
+ *                  kernel's accumulator fields.  The results do not depend on it, bit for bit:
+ *                  it lets small test images reach that bound
+ *   "mask_skip"    under a pixel mask (hq_set_mask) or weights: 1 (default) = the fast cost kernels launch
  *                  only the tiles that hold an in-mask owned pixel (every tile with "pixel_err"
  *                  1); 0 = every tile.  The results do not depend on it, bit for bit
  *   "palette_split" 1 = with a communicator of N ranks, each holding the whole image
