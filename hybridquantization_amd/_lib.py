@@ -40,6 +40,32 @@ class hq_swasa_params(C.Structure):
                 ("convergence", C.c_int)]
 
 
+class hq_path_info(C.Structure):
+    """include/hq.h's record of the last pass (hq_last_path); ``size`` is set by the caller."""
+    _fields_ = [("size", C.c_int32), ("pass_", C.c_int32), ("sequence", C.c_int64)] + \
+        [(n, C.c_int32) for n in ("ordered", "P", "K", "nch", "idx_bytes", "pixels", "grid", "argmin",
+                                  "argmin_cmb", "argmin_passes", "cost", "cost_hb", "cost_de", "cost_trim",
+                                  "cost_waves", "cost_nch", "cost_instance", "gen_h", "gen_h_outputs",
+                                  "gen_h_split", "gen_h_rpt", "gen_v", "gen_v_rows")] + \
+        [("why_not_fast", C.c_uint32), ("previous_pass", C.c_int32), ("previous_cost", C.c_int32),
+         ("tiles_run", C.c_int64), ("tiles_all", C.c_int64)]
+
+
+# the names of hq_path_info's kinds (hq.h's enums, in their order) and of hq_path_why's bits
+PATH_NAMES = {
+    "pass_": ("none", "full", "assign_only", "dither"),
+    "previous_pass": ("none", "full", "assign_only", "dither"),
+    "previous_cost": ("none", "cost16w", "cost_mfma", "tiled_generic", "pixel_generic"),
+    "pixels": ("none", "u8", "planar"),
+    "grid": ("none", "build_grid", "lists16"),
+    "argmin": ("none", "assign_pipe", "assign_pipe_ordered", "assign16", "assign_wide", "dither"),
+    "cost": ("none", "cost16w", "cost_mfma", "tiled_generic", "pixel_generic"),
+    "cost_instance": ("plain", "masked", "weighted"),
+    "gen_h": ("none", "gen_hpass", "gen_hrow", "gen_hrow4", "gen_hmfma"),
+    "gen_v": ("none", "gen_vpass", "gen_vtile", "gen_vtile2", "gen_vmfma"),
+}
+PATH_WHY = ("half", "cost_variant", "palette", "taps", "chunk_form", "nch", "wide")
+
 EVAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, _f, C.c_int, C.c_int, _d)
 REFINE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, _f, C.c_int, C.c_int)
 
@@ -110,6 +136,8 @@ SIGNATURES = {
     "hq_profile_enable": (C.c_int, [_ctx, C.c_int]),
     "hq_profile_get": (C.c_int, [_ctx, C.c_char_p, _d, C.POINTER(C.c_int64)]),
     "hq_profile_reset": (C.c_int, [_ctx]),
+    "hq_last_path": (C.c_int, [_ctx, C.POINTER(hq_path_info)]),
+    "hq_search_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "hq_set_option": (C.c_int, [_ctx, C.c_char_p, C.c_int]),
 }
 

@@ -697,13 +697,14 @@ __global__ __launch_bounds__(256) void used_idx16_kernel(AssignArgs a) {
 // then used_idx16.
 // ----------------------------------------------------------------------------
 template <bool U8>
-void launch_assign_t(const AssignArgs& a0, int P, hipStream_t s) {
+void launch_assign_t(const AssignArgs& a0, int P, hipStream_t s, AssignTag* tag) {
     const hipEvent_t ev0 = t_ev_start, ev1 = t_ev_stop;
     AssignArgs a = a0;
     a.gstep = 1;
     if (a.nch > 4) {
         const int npass = a.nch / 4, npal = P / a.nch;
         a.gstep = npass;
+        if (tag) *tag = AssignTag{1, U8, 4, npass};
         for (int j = 0; j < npass; ++j) {
             t_ev_start = j == 0 ? ev0 : nullptr;
             t_ev_stop = nullptr;
@@ -721,6 +722,7 @@ void launch_assign_t(const AssignArgs& a0, int P, hipStream_t s) {
     const int full = P / 4, rest = P % 4;
 #define HQ_ASG(NG, CMB, NB, G0, NGR) \
     HQ_LAUNCH((assign_pipe_kernel<NG, U8, CMB>), dim3((unsigned)(NB)), dim3(256), 0, s, a, G0, NGR)
+    if (tag) *tag = AssignTag{1, U8, a.nch == 4 ? 4 : a.nch == 2 ? 2 : 1, 1};  // (CMB of the launches below)
     if (full > 0) {
         if (rest) t_ev_stop = nullptr;
         if (a.nch == 4) HQ_ASG(4, 4, a.nblocks * full, 0, full);
@@ -747,16 +749,17 @@ void launch_used_idx16(const AssignArgs& a, int P, hipStream_t s) {
     HQ_LAUNCH(used_idx16_kernel, dim3(ub, (unsigned)P), dim3(256), 0, s, a);
 }
 
-hipError_t launch_assign(const AssignArgs& a, int P, hipStream_t s) {
-    with_bool(a.rgbx, [&](auto U8) { launch_assign_t<U8.value>(a, P, s); });
+hipError_t launch_assign(const AssignArgs& a, int P, hipStream_t s, AssignTag* tag) {
+    with_bool(a.rgbx, [&](auto U8) { launch_assign_t<U8.value>(a, P, s, tag); });
     return hipGetLastError();
 }
 
 // Ordered dithering (a.map set; K <= 256, so no chunks): the ORD instances, the
 // full groups in one launch and the rest group in a second as above.
 template <bool U8>
-void launch_assign_ordered_t(const AssignArgs& a, int P, hipStream_t s) {
+void launch_assign_ordered_t(const AssignArgs& a, int P, hipStream_t s, AssignTag* tag) {
     const hipEvent_t ev0 = t_ev_start, ev1 = t_ev_stop;
+    if (tag) *tag = AssignTag{2, U8, 1, 1};
     const int full = P / 4, rest = P % 4;
 #define HQ_ASG(NG, NB, G0, NGR) \
     HQ_LAUNCH((assign_pipe_kernel<NG, U8, 1, 0, true>), dim3((unsigned)(NB)), dim3(256), 0, s, a, G0, NGR)
@@ -776,7 +779,7 @@ void launch_assign_ordered_t(const AssignArgs& a, int P, hipStream_t s) {
     t_ev_start = ev0;
 }
 
-hipError_t launch_assign_ordered(const AssignArgs& a0, int P, hipStream_t s) {
+hipError_t launch_assign_ordered(const AssignArgs& a0, int P, hipStream_t s, AssignTag* tag) {
     if (!a0.map || a0.nch != 1 || a0.W < 1 || a0.nblocks < 1 || a0.mw_mask >= (uint32_t)kMaxMapSide ||
         a0.mh_mask >= (uint32_t)kMaxMapSide || (a0.mw_mask + 1u) != (1u << a0.lg_mw))
         return hipErrorInvalidValue;
@@ -785,7 +788,7 @@ hipError_t launch_assign_ordered(const AssignArgs& a0, int P, hipStream_t s) {
     const uint32_t cstride = (uint32_t)a.nblocks * 256u;  // the grid stride in pixels
     a.dy = cstride / a.W;
     a.dx = cstride - a.dy * a.W;
-    with_bool(a.rgbx, [&](auto U8) { launch_assign_ordered_t<U8.value>(a, P, s); });
+    with_bool(a.rgbx, [&](auto U8) { launch_assign_ordered_t<U8.value>(a, P, s, tag); });
     return hipGetLastError();
 }
 

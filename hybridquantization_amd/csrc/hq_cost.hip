@@ -1193,7 +1193,7 @@ void fast_tile_dims(int W, int own_rows, int tile_rows, int tile_w, int* tiles_x
 // NCH > 1: chunked palettes (NCH chunks of 256 colours, 16-bit indices); the
 // table takes 8 * 256 NCH bytes of dynamic LDS, above 64 KB in all at NCH 16.
 template <int HB, int NW, int NCH = 1>
-static void launch_cost16w(const CostArgs& a0, int P, int de, bool trim, hipStream_t s) {
+static void launch_cost16w(const CostArgs& a0, int P, int de, bool trim, hipStream_t s, CostTag* tag) {
     CostArgs a = a0;
     a.taps = static_cast<const char*>(a0.taps) + sizeof(CostTaps<HB>);
     const dim3 grid((unsigned)((kMasked ? a.nlive : a.ntiles) * P)), block(64 * NW);
@@ -1202,18 +1202,20 @@ static void launch_cost16w(const CostArgs& a0, int P, int de, bool trim, hipStre
             constexpr auto kern = cost16w_kernel<HB, DE.value, TRIM.value, NW, NCH, kMsk>;
             if constexpr (NCH > 1) HQ_LAUNCH_DYN_LDS(kern, grid, block, 8 * (size_t)kMaxK * NCH, s, a, P);
             else HQ_LAUNCH(kern, grid, block, 0, s, a, P);
+            if (tag) *tag = CostTag{1, HB, DE.value, TRIM.value, NW, NCH, kMsk};
         });
     });
 }
 
-hipError_t HQ_COST_LAUNCHER(launch_cost_chunked)(const CostArgs& a, int P, int nch, int de, bool trim, hipStream_t s) {
+hipError_t HQ_COST_LAUNCHER(launch_cost_chunked)(const CostArgs& a, int P, int nch, int de, bool trim, hipStream_t s,
+                                                 CostTag* tag) {
     if (!known_de(de) || (kMasked && (!a.mask || !a.live || a.nlive < 1))) return hipErrorInvalidValue;
     switch (nch) {
-    case 2: launch_cost16w<10, 4, 2>(a, P, de, trim, s); break;
-    case 4: launch_cost16w<10, 4, 4>(a, P, de, trim, s); break;
-    case 8: launch_cost16w<10, 4, 8>(a, P, de, trim, s); break;
-    case 16: launch_cost16w<10, 4, 16>(a, P, de, trim, s); break;
-    case 32: launch_cost16w<10, 4, 32>(a, P, de, trim, s); break;
+    case 2: launch_cost16w<10, 4, 2>(a, P, de, trim, s, tag); break;
+    case 4: launch_cost16w<10, 4, 4>(a, P, de, trim, s, tag); break;
+    case 8: launch_cost16w<10, 4, 8>(a, P, de, trim, s, tag); break;
+    case 16: launch_cost16w<10, 4, 16>(a, P, de, trim, s, tag); break;
+    case 32: launch_cost16w<10, 4, 32>(a, P, de, trim, s, tag); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -1221,17 +1223,17 @@ hipError_t HQ_COST_LAUNCHER(launch_cost_chunked)(const CostArgs& a, int P, int n
 
 // 256-column tiles (8 waves, 69 KB of LDS at HB = 10) and 8-row tiles: HB = 10 only.
 hipError_t HQ_COST_LAUNCHER(launch_cost_fast)(const CostArgs& a0, int P, int de, bool trim, int tile_rows, int tile_w,
-                                              int HB, hipStream_t s) {
+                                              int HB, hipStream_t s, CostTag* tag) {
     if (!known_de(de) || (HB != 10 && (tile_rows != kTH16 || tile_w == 256))) return hipErrorInvalidValue;
     if (kMasked && (!a0.mask || !a0.live || a0.nlive < 1)) return hipErrorInvalidValue;
     if (tile_rows == kTH16 && tile_w == 256) {
-        launch_cost16w<10, 8>(a0, P, de, trim, s);
+        launch_cost16w<10, 8>(a0, P, de, trim, s, tag);
     } else if (tile_rows == kTH16) {
         switch (HB) {
-        case kFastBuckets[0]: launch_cost16w<kFastBuckets[0], 4>(a0, P, de, trim, s); break;
-        case kFastBuckets[1]: launch_cost16w<kFastBuckets[1], 4>(a0, P, de, trim, s); break;
-        case kFastBuckets[2]: launch_cost16w<kFastBuckets[2], 4>(a0, P, de, trim, s); break;
-        case kFastBuckets[3]: launch_cost16w<kFastBuckets[3], 4>(a0, P, de, trim, s); break;
+        case kFastBuckets[0]: launch_cost16w<kFastBuckets[0], 4>(a0, P, de, trim, s, tag); break;
+        case kFastBuckets[1]: launch_cost16w<kFastBuckets[1], 4>(a0, P, de, trim, s, tag); break;
+        case kFastBuckets[2]: launch_cost16w<kFastBuckets[2], 4>(a0, P, de, trim, s, tag); break;
+        case kFastBuckets[3]: launch_cost16w<kFastBuckets[3], 4>(a0, P, de, trim, s, tag); break;
         default: return hipErrorInvalidValue;
         }
     } else {
@@ -1241,6 +1243,7 @@ hipError_t HQ_COST_LAUNCHER(launch_cost_fast)(const CostArgs& a0, int P, int de,
         with_de(de, [&](auto DE) {
             with_bool(trim, [&](auto TRIM) {
                 HQ_LAUNCH((cost_mfma_kernel<DE.value, TRIM.value, kMsk>), grid, dim3(256), 0, s, a, P);
+                if (tag) *tag = CostTag{2, 10, DE.value, TRIM.value, 4, 1, kMsk};
             });
         });
     }

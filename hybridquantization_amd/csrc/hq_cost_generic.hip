@@ -695,17 +695,18 @@ __global__ __launch_bounds__(256, 2) void gen_hmfma_kernel(GenArgs a, int pitch,
 // ---- host side: the launchers; profiling events bracket both launches of a pair ----
 // gen_hrow4 with NO outputs per thread
 template <bool SPLIT, int NO>
-static void launch_hrow4_no(const GenArgs& a, int idx_bytes, hipStream_t s) {
+static void launch_hrow4_no(const GenArgs& a, int idx_bytes, hipStream_t s, GenTag* tag) {
     constexpr int SEG = 256 * NO;
     const dim3 hg((unsigned)((a.g.W + SEG - 1) / SEG), (unsigned)(a.g.e1 - a.g.e0));
     const size_t hl = sizeof(float4) * NO * (size_t)((SEG + 2 * a.half + 3 + NO - 1) / NO);
     with_idx(idx_bytes, [&](auto IT) {
         HQ_LAUNCH_DYN_LDS((gen_hrow4_kernel<typename decltype(IT)::type, SPLIT, NO>), hg, dim3(256), hl, s, a);
+        if (tag) tag->h = 3, tag->h_outputs = NO, tag->h_split = SPLIT;
     });
 }
 template <bool SPLIT>
-static void launch_hrow4(const GenArgs& a, int idx_bytes, hipStream_t s) {  // a.hrow_no: 4 or 8
-    with_bool(a.hrow_no == 8, [&](auto EIGHT) { launch_hrow4_no<SPLIT, EIGHT.value ? 8 : 4>(a, idx_bytes, s); });
+static void launch_hrow4(const GenArgs& a, int idx_bytes, hipStream_t s, GenTag* tag) {  // a.hrow_no: 4 or 8
+    with_bool(a.hrow_no == 8, [&](auto EIGHT) { launch_hrow4_no<SPLIT, EIGHT.value ? 8 : 4>(a, idx_bytes, s, tag); });
 }
 
 // Explicit instantiations of the two kernels that issue dma_window from a
@@ -725,7 +726,7 @@ template __global__ void gen_vtile2_kernel<2, HQ_VT2_RB>(GenArgs, int);
 
 // Both passes on the matrix cores where the options and the half-width allow
 // (gen_hmfma or gen_hrow4's split form, then gen_vmfma).
-static void launch_cost_vmfma(const GenArgs& a, int de, int idx_bytes, hipStream_t s) {
+static void launch_cost_vmfma(const GenArgs& a, int de, int idx_bytes, hipStream_t s, GenTag* tag) {
     // workgroup shapes by grid size: the taller forms only when they still
     // give every CU two rounds of work (1024^2: 128-row tiles left 256
     // workgroups, one per CU)
@@ -748,9 +749,10 @@ static void launch_cost_vmfma(const GenArgs& a, int de, int idx_bytes, hipStream
         const dim3 hg((unsigned)hx, (unsigned)((rows + 16 * rpt - 1) / (16 * rpt)));
         with_idx(idx_bytes, [&](auto IT) {
             HQ_LAUNCH_DYN_LDS((gen_hmfma_kernel<typename decltype(IT)::type>), hg, dim3(256), hl, s, a, pitch, rpt);
+            if (tag) tag->h = 4, tag->h_rpt = rpt;
         });
     } else {
-        launch_hrow4<true>(a, idx_bytes, s);
+        launch_hrow4<true>(a, idx_bytes, s, tag);
     }
     ev.second();
     const int tx = (a.g.W + kVt2W - 1) / kVt2W;
@@ -761,25 +763,28 @@ static void launch_cost_vmfma(const GenArgs& a, int de, int idx_bytes, hipStream
     with_de(de, [&](auto DE) {
         with_bool(two, [&](auto TWO) {
             HQ_LAUNCH_DYN_LDS((gen_vmfma_kernel<DE.value, TWO.value ? 2 : 1>), vg, dim3(256), l2, s, a, tx);
+            if (tag) tag->v = 4, tag->v_rows = TWO.value ? 128 : 64;
         });
     });
 }
 
 // The tiled generic pair (gen_hrow + gen_vtile and their faster forms).
-hipError_t launch_cost_tiled_generic(const GenArgs& a, int de, int idx_bytes, hipStream_t s) {
+hipError_t launch_cost_tiled_generic(const GenArgs& a, int de, int idx_bytes, hipStream_t s, GenTag* tag) {
     if (!known_de(de)) return hipErrorInvalidValue;
+    if (tag) *tag = GenTag{}, tag->cost = 3;
     if (a.vmfma && a.vtapd && a.half <= kVt2MaxHalf) {  // the matrix-core vertical pass
-        launch_cost_vmfma(a, de, idx_bytes, s);
+        launch_cost_vmfma(a, de, idx_bytes, s, tag);
         return hipGetLastError();
     }
     LaunchEventPair ev;
     if (a.hrow4) {  // (option gen_hrow4, default on; gen_hrow stays as its bitwise cross-check)
-        launch_hrow4<false>(a, idx_bytes, s);
+        launch_hrow4<false>(a, idx_bytes, s, tag);
     } else {
         const dim3 hg((unsigned)((a.g.W + 255) / 256), (unsigned)(a.g.e1 - a.g.e0));
         const size_t hl = sizeof(float4) * (256 + 2 * (size_t)a.half);
         with_idx(idx_bytes, [&](auto IT) {
             HQ_LAUNCH(gen_hrow_kernel<typename decltype(IT)::type>, hg, dim3(256), hl, s, a);
+            if (tag) tag->h = 2;
         });
     }
     ev.second();
@@ -790,6 +795,7 @@ hipError_t launch_cost_tiled_generic(const GenArgs& a, int de, int idx_bytes, hi
         const dim3 vg((unsigned)(tx * ty));
         with_de(de, [&](auto DE) {
             HQ_LAUNCH_DYN_LDS((gen_vtile2_kernel<DE.value, HQ_VT2_RB>), vg, dim3(256), l2, s, a, tx);
+            if (tag) tag->v = 3;
         });
         return hipGetLastError();
     }
@@ -798,20 +804,24 @@ hipError_t launch_cost_tiled_generic(const GenArgs& a, int de, int idx_bytes, hi
     const dim3 vg((unsigned)(tiles_x * tiles_y));
     with_de(de, [&](auto DE) {  // window rows above 64 KB (half > 95): the grant raises the limit
         HQ_LAUNCH_DYN_LDS((gen_vtile_kernel<DE.value>), vg, dim3(256), vl, s, a, tiles_x);
+        if (tag) tag->v = 2;
     });
     return hipGetLastError();
 }
 
 // The plain per-pixel pair (gen_hpass + gen_vpass; option cost_variant 1).
-hipError_t launch_cost_generic(const GenArgs& a, int de, int idx_bytes, hipStream_t s) {
+hipError_t launch_cost_generic(const GenArgs& a, int de, int idx_bytes, hipStream_t s, GenTag* tag) {
     if (!known_de(de)) return hipErrorInvalidValue;
+    if (tag) *tag = GenTag{}, tag->cost = 4;
     LaunchEventPair ev;
     with_idx(idx_bytes, [&](auto IT) {
         HQ_LAUNCH(gen_hpass_kernel<typename decltype(IT)::type>, dim3(blocks_for(a.g.n_ext)), dim3(256), 0, s, a);
+        if (tag) tag->h = 1;
     });
     ev.second();
     const int64_t n_own = (int64_t)a.g.W * (a.g.r1 - a.g.r0);
     with_de(de, [&](auto DE) { HQ_LAUNCH(gen_vpass_kernel<DE.value>, dim3(blocks_for(n_own)), dim3(256), 0, s, a); });
+    if (tag) tag->v = 1;
     return hipGetLastError();
 }
 

@@ -194,11 +194,12 @@ __global__ __launch_bounds__(kDitherMaxRows) void dither_kernel(DitherArgs a) {
     if (r < 8) a.used_glob[p * 8 + r] = s_used[r];
 }
 
-hipError_t launch_dither(const DitherArgs& a, int P, hipStream_t s) {
+hipError_t launch_dither(const DitherArgs& a, int P, hipStream_t s, AssignTag* tag) {
     if (a.rows < 64 || a.rows > kDitherMaxRows || a.rows % 64 || a.K < 1 || a.K > kMaxK || a.W < 1 || a.H < 1)
         return hipErrorInvalidValue;
     const int block = min(a.rows, (a.H + 63) / 64 * 64);
     HQ_LAUNCH(dither_kernel, dim3(P), dim3(block), 0, s, a);
+    if (tag) *tag = AssignTag{5, 0, 0, 0};  // (the planar floats, always)
     return hipGetLastError();
 }
 

@@ -56,10 +56,31 @@ bool use_lists16(const hq_ctx* c) {
 // generic pair, whose [7][n_ext] scratch ensure_population then allocates up
 // front: nothing may allocate while a search run is captured into a graph).
 // Chunked palettes: the 16 x 128 tiles at HB = 10 only.
-bool cost_fast(const hq_ctx* c) {
-    return c->cost_variant == 0 && c->fast_hb > 0 && !c->pal_generic && !c->taps_generic &&
-           (c->nch_cur == 1 || (c->nch_cur <= kMaxNchFast && c->fast_hb == 10 && c->cost_rows == 16 &&
-                                c->cost_tw == 128));
+// (as the reasons why not, hq_path_why's bits: enqueue_core records the value it dispatches on)
+uint32_t cost_slow_why(const hq_ctx* c) {
+    uint32_t why = 0;
+    if (c->fast_hb <= 0) why |= HQ_WHY_HALF;
+    if (c->cost_variant != 0) why |= HQ_WHY_VARIANT;
+    if (c->pal_generic) why |= HQ_WHY_PALETTE;
+    if (c->taps_generic) why |= HQ_WHY_TAPS;
+    if (c->nch_cur > kMaxNchFast) why |= HQ_WHY_NCH;
+    else if (c->nch_cur > 1 && c->fast_hb > 0 && !(c->fast_hb == 10 && c->cost_rows == 16 && c->cost_tw == 128))
+        why |= HQ_WHY_CHUNK_FORM;
+    return why;
+}
+bool cost_fast(const hq_ctx* c) { return cost_slow_why(c) == 0; }
+
+// hq_last_path: the pass that has been enqueued becomes the context's record.
+void record_path(hq_ctx* c, hq_path_info pi) {
+    pi.sequence = c->path.sequence + 1;
+    pi.previous_pass = c->path.pass, pi.previous_cost = c->path.cost;
+    c->path = pi;
+}
+void record_argmin(hq_path_info& pi, const AssignTag& at) {
+    pi.argmin = at.kernel;
+    pi.argmin_cmb = at.cmb;
+    pi.argmin_passes = at.passes;
+    pi.pixels = at.kernel == HQ_ARGMIN_NONE ? HQ_PIXELS_NONE : at.u8 ? HQ_PIXELS_U8 : HQ_PIXELS_PLANAR;
 }
 
 // The palettes of a P-palette population this device evaluates: a palette
@@ -240,9 +261,10 @@ GridArgs grid_args(hq_ctx* c, int P, int K, int so = 0) {
 // palettes) or u32: idx_bytes) with c->g.idx_pitch elements per palette, opponent
 // tables of opp_stride entries per palette in d_opp.  Pair `cost` times all P pairs.
 int enqueue_generic_cost(hq_ctx* c, int P, const void* idx_base, int idx_bytes, int opp_stride, ProfRec& pr,
-                         Pair cost, int p_off = 0) {
+                         Pair cost, hq_path_info& pi, int p_off = 0) {
     const Geom& g = c->g;
     hipStream_t s = c->stream;
+    GenTag gt;
     HIP_TRY(c, c->d_gen_t.ensure(sizeof(float) * 7 * (size_t)g.n_ext + 256));
     for (int p = 0; p < P; ++p) {
         GenArgs gn{};
@@ -263,6 +285,7 @@ int enqueue_generic_cost(hq_ctx* c, int P, const void* idx_base, int idx_bytes, 
         gn.half = c->half;
         gn.pix_err = c->pixel_err ? c->d_pixerr.as<float>() + (int64_t)p * n_own(g) : nullptr;
         gn.mask = c->mask_on ? c->d_mask.as<uint8_t>() : nullptr;
+        pi.cost_instance = !c->mask_on ? HQ_INSTANCE_PLAIN : c->weights_on ? HQ_INSTANCE_WEIGHTED : HQ_INSTANCE_MASKED;
         gn.vtaps = c->d_vtaps.as<float>();
         gn.vtap_pitch = c->vtap_pitch;
         gn.hrow4 = c->gen_hrow4;
@@ -280,10 +303,14 @@ int enqueue_generic_cost(hq_ctx* c, int P, const void* idx_base, int idx_bytes, 
         // the events span every palette's launch pair: start on the first, stop on the last;
         // cost_variant 2: the per-pixel pair in the reference's summation order
         HIP_TRY(c, timed_launch(pr, cost, [&] {
-            return c->cost_variant == 2 ? launch_cost_generic(gn, c->de_type, idx_bytes, s)
-                                        : launch_cost_tiled_generic(gn, c->de_type, idx_bytes, s);
+            return c->cost_variant == 2 ? launch_cost_generic(gn, c->de_type, idx_bytes, s, &gt)
+                                        : launch_cost_tiled_generic(gn, c->de_type, idx_bytes, s, &gt);
         }, p == 0, p == P - 1));
     }
+    pi.cost = gt.cost, pi.cost_de = c->de_type;
+    pi.gen_h = gt.h, pi.gen_h_outputs = gt.h_outputs, pi.gen_h_split = gt.h_split, pi.gen_h_rpt = gt.h_rpt;
+    pi.gen_v = gt.v, pi.gen_v_rows = gt.v_rows;
+    pi.idx_bytes = idx_bytes;
     return HQ_OK;
 }
 
@@ -351,6 +378,13 @@ int enqueue_wide(hq_ctx* c, int P, int K, ProfRec& pr) {
     hipStream_t s = c->stream;
     int lo = 0, Pl = P;
     if (int rc = begin_pass(c, P, K, true, &lo, &Pl)) return rc;
+    hq_path_info pi{};
+    pi.pass = HQ_PASS_FULL, pi.P = Pl, pi.K = K, pi.nch = 1;
+    // (this path has no fast cost to decline: HQ_WHY_WIDE is its own bit, and the others say what
+    // the state it was entered in would have kept from the fast kernels anyway -- run_pass sends a
+    // palette outside the range here, a long filter goes to the generic pair on every path)
+    pi.why_not_fast = cost_slow_why(c) | HQ_WHY_WIDE;
+    AssignTag at;
     WideArgs wa{c->d_pal_in.as<float4>(), c->d_pal.as<float4>(), c->d_opp.as<float4>(), c->d_pflags.as<int>(),
                 c->d_R.as<float>(), c->d_G.as<float>(), c->d_B.as<float>(), c->d_idx32.as<uint32_t>(),
                 c->d_used32.as<uint32_t>(), g.n_ext, g.idx_pitch, K};
@@ -363,8 +397,10 @@ int enqueue_wide(hq_ctx* c, int P, int K, ProfRec& pr) {
     ws.pal += (int64_t)lo * K;
     ws.opp += (int64_t)lo * K;
     ws.pflags += lo;
-    HIP_TRY(c, timed_launch(pr, kPAssign, [&] { return launch_assign_wide(ws, Pl, s); }));
-    if (int rc = enqueue_generic_cost(c, Pl, c->d_idx32.p, 4, K, pr, kPCost, lo)) return rc;
+    HIP_TRY(c, timed_launch(pr, kPAssign, [&] { return launch_assign_wide(ws, Pl, s, &at); }));
+    record_argmin(pi, at);
+    if (int rc = enqueue_generic_cost(c, Pl, c->d_idx32.p, 4, K, pr, kPCost, pi, lo)) return rc;
+    record_path(c, pi);
     const FinalizeArgs fa{acc_set(c, c->acc_par, Pl), nullptr, 0, c->d_out.as<double>() + (int64_t)lo * (1 + K), Pl,
                           K, c->d_used32.as<uint32_t>(), 8};
     return end_pass(c, Pass{}, fa, P, K, lo, Pl, Pl, pr);
@@ -374,20 +410,25 @@ int enqueue_wide(hq_ctx* c, int P, int K, ProfRec& pr) {
 // The grid (build_grid or the native 16-bit lists; both also zero the used bits and the sums),
 // or without one -- G2 = 0, a dithered pass -- the zeroing.
 int enqueue_grid(hq_ctx* c, const GridArgs& ga, bool build, bool n16, int K, int Pl, int Ps, Pair pgrid,
-                 ProfRec& pr) {
+                 ProfRec& pr, hq_path_info& pi) {
     hipStream_t s = c->stream;
     if (!build) {
+        pi.grid = HQ_GRID_NONE;
         HIP_TRY(c, hipMemsetAsync(ga.used_glob, 0, sizeof(uint32_t) * kUsedSlots * (size_t)used_stride(Ps), s));
         HIP_TRY(c, hipMemsetAsync(ga.acc_zero, 0, sizeof(uint64_t) * acc_words(Pl), s));
         return HQ_OK;
     }
     const int nch = c->nch_cur;
     HIP_TRY(c, timed_launch(pr, pgrid, [&] {
-        return n16 ? launch_lists16_grid(Lists16Args{ga.pal, ga.pflags, c->d_l1n.as<uint16_t>(),
-                                                     c->d_l2n.as<uint16_t>(), ga.used_glob, used_stride(Ps),
-                                                     ga.acc_zero, Pl, K, nch * kMaxK, nch},
-                                         Pl, s)
-                   : launch_build_grid(ga, Ps, s);
+        if (n16) {
+            pi.grid = HQ_GRID_LISTS16;
+            return launch_lists16_grid(Lists16Args{ga.pal, ga.pflags, c->d_l1n.as<uint16_t>(),
+                                                   c->d_l2n.as<uint16_t>(), ga.used_glob, used_stride(Ps),
+                                                   ga.acc_zero, Pl, K, nch * kMaxK, nch},
+                                       Pl, s);
+        }
+        pi.grid = HQ_GRID_BUILD_GRID;
+        return launch_build_grid(ga, Ps, s);
     }));
     return HQ_OK;
 }
@@ -472,24 +513,31 @@ int cost_args(hq_ctx* c, const GridArgs& ga, const FastGrid& f, int K, int so, i
 // The cost: the fast launch (under a mask over its live tiles, and none without one: the
 // zeroed counters are the partial), else the generic pair.
 int enqueue_cost(hq_ctx* c, const CostArgs& ca, bool fast, const FastGrid& f, int lo, int Pl, Pair pcost,
-                 ProfRec& pr) {
+                 ProfRec& pr, hq_path_info& pi) {
     hipStream_t s = c->stream;
     const int nch = c->nch_cur, de = c->de_type;
     const bool trim = c->trim && c->trim_ok;
     if (!fast)
-        return nch > 1 ? enqueue_generic_cost(c, Pl, c->d_idx16.p, 2, nch * kMaxK, pr, pcost, lo)
-                       : enqueue_generic_cost(c, Pl, c->d_idx.p, 1, kMaxK, pr, pcost, lo);
+        return nch > 1 ? enqueue_generic_cost(c, Pl, c->d_idx16.p, 2, nch * kMaxK, pr, pcost, pi, lo)
+                       : enqueue_generic_cost(c, Pl, c->d_idx.p, 1, kMaxK, pr, pcost, pi, lo);
+    pi.tiles_all = f.ntiles;
+    pi.tiles_run = c->mask_on ? ca.nlive : f.ntiles;
+    pi.cost_instance = !c->mask_on ? HQ_INSTANCE_PLAIN : c->weights_on ? HQ_INSTANCE_WEIGHTED : HQ_INSTANCE_MASKED;
     if (c->mask_on && ca.nlive == 0) return HQ_OK;
+    CostTag ct;
     HIP_TRY(c, timed_launch(pr, pcost, [&] {
         if (c->mask_on && c->weights_on)
-            return nch > 1 ? launch_cost_chunked_weighted(ca, Pl, nch, de, trim, s)
-                           : launch_cost_fast_weighted(ca, Pl, de, trim, f.rows, f.tw, c->fast_hb, s);
+            return nch > 1 ? launch_cost_chunked_weighted(ca, Pl, nch, de, trim, s, &ct)
+                           : launch_cost_fast_weighted(ca, Pl, de, trim, f.rows, f.tw, c->fast_hb, s, &ct);
         if (c->mask_on)
-            return nch > 1 ? launch_cost_chunked_masked(ca, Pl, nch, de, trim, s)
-                           : launch_cost_fast_masked(ca, Pl, de, trim, f.rows, f.tw, c->fast_hb, s);
-        return nch > 1 ? launch_cost_chunked(ca, Pl, nch, de, trim, s)
-                       : launch_cost_fast(ca, Pl, de, trim, f.rows, f.tw, c->fast_hb, s);
+            return nch > 1 ? launch_cost_chunked_masked(ca, Pl, nch, de, trim, s, &ct)
+                           : launch_cost_fast_masked(ca, Pl, de, trim, f.rows, f.tw, c->fast_hb, s, &ct);
+        return nch > 1 ? launch_cost_chunked(ca, Pl, nch, de, trim, s, &ct)
+                       : launch_cost_fast(ca, Pl, de, trim, f.rows, f.tw, c->fast_hb, s, &ct);
     }));
+    // (the instance is the launcher's own: each of the three translation units reports its MSK)
+    pi.cost = ct.kernel, pi.cost_hb = ct.hb, pi.cost_de = ct.de, pi.cost_trim = ct.trim;
+    pi.cost_waves = ct.waves, pi.cost_nch = ct.nch, pi.cost_instance = ct.msk;
     return HQ_OK;
 }
 
@@ -517,12 +565,18 @@ int hq::enqueue_core(hq_ctx* c, int P, int K, ProfRec& pr, Pass pass) {
     const int Ps = Pl * nch, so = lo * nch;  // sub-palettes, the first one's index
     const GridArgs ga = grid_args(c, Ps, Ks, so);
     const bool n16 = use_lists16(c);
-    if (int rc = enqueue_grid(c, ga, c->G2 > 0 && !dither, n16, K, Pl, Ps, Pair(p0), pr)) return rc;
+    hq_path_info pi{};
+    pi.pass = dither ? HQ_PASS_DITHER : costed ? HQ_PASS_FULL : HQ_PASS_ASSIGN_ONLY;
+    pi.ordered = pass.ordered, pi.P = Pl, pi.K = K, pi.nch = nch;
+    if (int rc = enqueue_grid(c, ga, c->G2 > 0 && !dither, n16, K, Pl, Ps, Pair(p0), pr, pi)) return rc;
     AssignArgs aa = assign_args(c, ga, Ps, Ks, pass.ordered);
     if (pass.ordered)
         if (int rc = add_ordered(c, pass, aa)) return rc;
     if (n16) add_lists16(c, K, Pl, aa);
-    const bool fast = cost_fast(c);
+    pi.idx_bytes = aa.idx16 ? 2 : 1;
+    const uint32_t why = cost_slow_why(c);  // (cost_fast)
+    const bool fast = why == 0;
+    AssignTag at;
     const FastGrid f = fast_grid(c);
     CostArgs ca{};
     if (fast)
@@ -531,13 +585,17 @@ int hq::enqueue_core(hq_ctx* c, int P, int K, ProfRec& pr, Pass pass) {
         return dither ? launch_dither(DitherArgs{aa.R, aa.G, aa.B, ga.pal, aa.idx, ga.used_glob,
                                                  c->d_dcarry.as<float>(), g.idx_pitch, g.W, g.H, K,
                                                  c->dither_rows, pass.strength},
-                                      Pl, s)
-               : n16  ? launch_assign16(aa, Pl, s)
-               : pass.ordered ? launch_assign_ordered(aa, Ps, s)
-                      : launch_assign(aa, Ps, s);
+                                      Pl, s, &at)
+               : n16  ? launch_assign16(aa, Pl, s, &at)
+               : pass.ordered ? launch_assign_ordered(aa, Ps, s, &at)
+                      : launch_assign(aa, Ps, s, &at);
     }));
-    if (costed)
-        if (int rc = enqueue_cost(c, ca, fast, f, lo, Pl, Pair(p0 + 2), pr)) return rc;
+    record_argmin(pi, at);
+    if (costed) {
+        pi.why_not_fast = why;
+        if (int rc = enqueue_cost(c, ca, fast, f, lo, Pl, Pair(p0 + 2), pr, pi)) return rc;
+    }
+    record_path(c, pi);
     const FinalizeArgs fa{ga.acc_zero, ga.used_glob, used_stride(Ps), c->d_out.as<double>() + (int64_t)lo * (1 + K),
                           Pl, K, nullptr, 8 * nch};
     return end_pass(c, pass, fa, P, K, lo, Pl, Ps, pr);

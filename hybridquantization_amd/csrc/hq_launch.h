@@ -95,6 +95,14 @@ bool allow_dyn_lds(const void* fn, size_t bytes);
         if (allow_dyn_lds(reinterpret_cast<const void*>(K), S)) HQ_LAUNCH(K, G, B, S, STREAM, __VA_ARGS__); \
     } while (0)
 
+// ---- what a launcher chose (hq_last_path) ---------------------------------------
+// Each launcher with a choice to make fills its tag next to the HQ_LAUNCH that makes
+// it, through an out-parameter (null: nobody asks).  The values are hq.h's
+// hq_path_argmin / hq_path_cost / hq_path_gen_h / hq_path_gen_v.
+struct AssignTag { int kernel = 0, u8 = 0, cmb = 0, passes = 0; };
+struct CostTag { int kernel = 0, hb = 0, de = 0, trim = 0, waves = 0, nch = 0, msk = 0; };
+struct GenTag { int cost = 0, h = 0, h_outputs = 0, h_split = 0, h_rpt = 0, v = 0, v_rows = 0; };
+
 // ---- the launchers -------------------------------------------------------------
 // hq_search.hip
 hipError_t launch_prep_palette(const PaletteArgs&, int P, hipStream_t);
@@ -104,40 +112,43 @@ hipError_t launch_reseed(const ReseedArgs&, int P, hipStream_t);
 hipError_t launch_build_grid(const GridArgs&, int P, hipStream_t);
 hipError_t launch_finalize(const FinalizeArgs&, int P, hipStream_t);
 // hq_assign.hip
-hipError_t launch_assign(const AssignArgs&, int P, hipStream_t);
+hipError_t launch_assign(const AssignArgs&, int P, hipStream_t, AssignTag* tag = nullptr);
 void launch_used_idx16(const AssignArgs&, int P, hipStream_t);
 int assign_residency(int NG);
 int assign_residency_chunked();
 // ... with ordered dithering (AssignArgs::map and what goes with it; K <= 256)
-hipError_t launch_assign_ordered(const AssignArgs&, int P, hipStream_t);
+hipError_t launch_assign_ordered(const AssignArgs&, int P, hipStream_t, AssignTag* tag = nullptr);
 int assign_residency_ordered(int NG);
 // hq_lists16.hip
 hipError_t launch_lists16_grid(const Lists16Args&, int P, hipStream_t);
-hipError_t launch_assign16(const AssignArgs&, int P, hipStream_t);
+hipError_t launch_assign16(const AssignArgs&, int P, hipStream_t, AssignTag* tag = nullptr);
 // hq_dither.hip: one workgroup per palette
-hipError_t launch_dither(const DitherArgs&, int P, hipStream_t);
+hipError_t launch_dither(const DitherArgs&, int P, hipStream_t, AssignTag* tag = nullptr);
 // hq_wide.hip
 hipError_t launch_prep_wide(const WideArgs&, int P, hipStream_t);
-hipError_t launch_assign_wide(const WideArgs&, int P, hipStream_t);
+hipError_t launch_assign_wide(const WideArgs&, int P, hipStream_t, AssignTag* tag = nullptr);
 // hq_cost.hip: half-widths up to 24
 size_t fast_taps_bytes(int HB);
 int fast_grid_row0(int de, int r0, int tile_rows);
 void fast_tile_dims(int W, int own_rows, int tile_rows, int tile_w, int* tiles_x, int* ntiles);
 int fast_tile_width(int tile_rows, int tile_w);  // columns of a tile of fast_tile_dims' grid
 hipError_t launch_cost_fast(const CostArgs&, int P, int de, bool trim, int tile_rows, int tile_w, int HB,
-                            hipStream_t);
-hipError_t launch_cost_chunked(const CostArgs&, int P, int nch, int de, bool trim, hipStream_t);
+                            hipStream_t, CostTag* tag = nullptr);
+hipError_t launch_cost_chunked(const CostArgs&, int P, int nch, int de, bool trim, hipStream_t,
+    CostTag* tag = nullptr);
 // hq_cost_masked.hip: the same under a pixel mask (CostArgs::mask, live, nlive: nlive >= 1 tiles)
 hipError_t launch_cost_fast_masked(const CostArgs&, int P, int de, bool trim, int tile_rows, int tile_w, int HB,
-                                   hipStream_t);
-hipError_t launch_cost_chunked_masked(const CostArgs&, int P, int nch, int de, bool trim, hipStream_t);
+                                   hipStream_t, CostTag* tag = nullptr);
+hipError_t launch_cost_chunked_masked(const CostArgs&, int P, int nch, int de, bool trim, hipStream_t,
+    CostTag* tag = nullptr);
 // hq_cost_weighted.hip: the same under pixel weights (CostArgs::mask holds the weights)
 hipError_t launch_cost_fast_weighted(const CostArgs&, int P, int de, bool trim, int tile_rows, int tile_w, int HB,
-                                     hipStream_t);
-hipError_t launch_cost_chunked_weighted(const CostArgs&, int P, int nch, int de, bool trim, hipStream_t);
+                                     hipStream_t, CostTag* tag = nullptr);
+hipError_t launch_cost_chunked_weighted(const CostArgs&, int P, int nch, int de, bool trim, hipStream_t,
+    CostTag* tag = nullptr);
 // hq_cost_generic.hip: any half-width, one palette per launch pair
-hipError_t launch_cost_generic(const GenArgs&, int de, int idx_bytes, hipStream_t);
-hipError_t launch_cost_tiled_generic(const GenArgs&, int de, int idx_bytes, hipStream_t);
+hipError_t launch_cost_generic(const GenArgs&, int de, int idx_bytes, hipStream_t, GenTag* tag = nullptr);
+hipError_t launch_cost_tiled_generic(const GenArgs&, int de, int idx_bytes, hipStream_t, GenTag* tag = nullptr);
 // hq_centroid.hip: per-colour pixel sums; idx_bytes 1, 2 or 4, num_cu sizes the grid
 hipError_t launch_cluster_sums(const ClusterArgs&, int idx_bytes, int num_cu, hipStream_t);
 // hq_errsum.hip: per-colour error sums and worst pixels, then the gather of their colours

@@ -628,7 +628,7 @@ __global__ __launch_bounds__(kN16Threads) void assign16_kernel(AssignArgs a, int
 
 // assign16 then the used bits from the final indices (launch_used_idx16,
 // hq_assign.hip); the profiling events bracket both.
-hipError_t launch_assign16(const AssignArgs& a0, int P, hipStream_t s) {
+hipError_t launch_assign16(const AssignArgs& a0, int P, hipStream_t s, AssignTag* tag) {
     LaunchEventPair ev;
     AssignArgs a = a0;
     const int npal = a.K <= 4096 ? 2 : 1;  // two 64 KiB tables fit one workgroup up to K = 4096
@@ -641,6 +641,7 @@ hipError_t launch_assign16(const AssignArgs& a0, int P, hipStream_t s) {
     };
     with_bool(a.rgbx, [&](auto RGBX) {
         with_bool(npal == 2, [&](auto TWO) { go(assign16_kernel<RGBX.value, TWO.value ? 2 : 1>); });
+        if (tag) *tag = AssignTag{3, RGBX.value, 0, 0};
     });
     if (!ok) return hipErrorInvalidConfiguration;  // the LDS raise was refused: nothing launched
     ev.second();

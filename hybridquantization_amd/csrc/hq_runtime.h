@@ -247,6 +247,9 @@ struct hq_ctx {
 
     // population work buffers
     hq::Resident res;  // what the last pass left in them (drop, commit)
+    // hq_last_path: the kernels the last enqueued pass took, written by enqueue_core and
+    // enqueue_wide where each launch is chosen (record_path); path.sequence counts the passes
+    hq_path_info path{};
     hq::DevBuf d_pal_in, d_pal, d_opp, d_opp16, d_dup, d_pflags, d_lvl1, d_lvl2, d_idx, d_used_mask,
         d_acc, d_out, d_gen_t;
     // d_acc: two sets of fixed-point dE sums [kAccSlots][P][4] u64 (acc_add), d_used_mask two
@@ -371,6 +374,7 @@ struct hq_search {
     hq::EventSet pev;                    // profiling: 2 kPairs events per iteration of a run
     hipGraphExec_t gexec = nullptr;      // option sa_graph: the last run's iteration chain
     int gexec_iters = 0;                 // (its iteration count: the topology an update must match)
+    bool graphed = false;                // hq_search_info: the last run was captured and replayed
 };
 
 namespace hq {

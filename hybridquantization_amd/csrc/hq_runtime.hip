@@ -501,6 +501,14 @@ int hq_mask_info(hq_ctx* c, int64_t* n_full, int64_t* n_owned, int64_t* tiles_ru
     return HQ_OK;
 }
 
+int hq_last_path(hq_ctx* c, hq_path_info* info) {
+    if (!c || !info || info->size < (int32_t)sizeof(int32_t)) return HQ_ERR_ARG;
+    hq_path_info pi = c->path;
+    pi.size = std::min<int32_t>(info->size, (int32_t)sizeof(hq_path_info));
+    std::memcpy(info, &pi, (size_t)pi.size);
+    return HQ_OK;
+}
+
 int hq_get_labref(hq_ctx* c, float* lab4) {
     if (!c || !lab4) return HQ_ERR_ARG;
     if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set");

@@ -313,6 +313,7 @@ int device_search_run(hq_search* s, int iterations, int* ran) {
     // when the iteration count (the topology) is the same, else instantiated
     // anew.  Not with profiling events (they ride on the launches).
     const bool graph = c->sa_graph && !prof;
+    s->graphed = graph;
     if (graph) HIP_TRY(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
     auto abort_capture = [&](int rc0) {
         if (graph) {
@@ -548,6 +549,14 @@ int hq_search_best(const hq_search* s, float* colors, double* best_error, int* i
     if (colors) std::copy(s->driver->best_colors().begin(), s->driver->best_colors().end(), colors);
     if (best_error) *best_error = s->driver->best_error();
     if (iteration) *iteration = s->driver->iteration();
+    return HQ_OK;
+}
+
+int hq_search_info(const hq_search* s, int* device_resident, int* nch, int* graph) {
+    if (!s) return HQ_ERR_ARG;
+    if (device_resident) *device_resident = s->driver ? 0 : 1;  // (hq_search_create_from built one or the other)
+    if (nch) *nch = s->nch;
+    if (graph) *graph = s->graphed ? 1 : 0;
     return HQ_OK;
 }
 

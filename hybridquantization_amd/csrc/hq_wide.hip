@@ -106,9 +106,10 @@ hipError_t launch_prep_wide(const WideArgs& a, int P, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_assign_wide(const WideArgs& a, int P, hipStream_t s) {
+hipError_t launch_assign_wide(const WideArgs& a, int P, hipStream_t s, AssignTag* tag) {
     const unsigned gx = (unsigned)((a.n_ext + 256 * kWidePPT - 1) / (256 * kWidePPT));
     HQ_LAUNCH(assign_wide_kernel, dim3(gx, (unsigned)P), dim3(256), 0, s, a);
+    if (tag) *tag = AssignTag{4, 0, 0, 0};  // (the planar floats, always)
     return hipGetLastError();
 }
 

@@ -409,6 +409,36 @@ class ImageManipulation:
         m = np.ascontiguousarray(m.reshape(-1), dtype=np.uint8)
         check(self._lib.hq_set_weights(ctx, _lib.u8ptr(m), w, h), ctx)
 
+    def lastPath(self) -> dict:
+        """hq_last_path as a dict with names, not numbers: the kernels the last pass enqueued on
+        this context took (an evaluation's, a rendering's, the last one of a refine, repair or
+        search call).  ``pass``, ``pixels``, ``grid``, ``argmin``, ``cost``, ``cost_instance``,
+        ``gen_h`` and ``gen_v`` are strings ("none" before the first pass), ``why_not_fast`` a
+        frozenset of reasons (empty on the fast path), everything else an int."""
+        ctx = self._require()
+        pi = _lib.hq_path_info()
+        pi.size = C.sizeof(pi)
+        check(self._lib.hq_last_path(ctx, C.byref(pi)), ctx)
+        out = {}
+        for name, _ in pi._fields_[1:]:
+            v = getattr(pi, name)
+            key = "pass" if name == "pass_" else name
+            if name in _lib.PATH_NAMES:
+                out[key] = _lib.PATH_NAMES[name][v]
+            elif name == "why_not_fast":
+                out[key] = frozenset(n for i, n in enumerate(_lib.PATH_WHY) if v >> i & 1)
+            else:
+                out[key] = int(v)
+        return out
+
+    def searchInfo(self, search) -> dict:
+        """hq_search_info of a search handle made on this context: ``device_resident`` (the
+        iterations run on the device, not through the host-driven driver), ``nch`` (its chunks
+        per palette) and ``graph`` (its last run was captured into a hipGraph)."""
+        v = [C.c_int() for _ in range(3)]
+        check(self._lib.hq_search_info(search, *[C.byref(x) for x in v]), self._require())
+        return {"device_resident": bool(v[0].value), "nch": v[1].value, "graph": bool(v[2].value)}
+
     def weightsInfo(self):
         """hq_weights_info -> (w_full, w_owned): the sum of the weights over the full image and
         over the owned rows (under a mask or with nothing set: maskInfo's n_full, n_owned)."""

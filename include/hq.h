@@ -706,6 +706,82 @@ int hq_profile_enable(hq_ctx *ctx, int on);
 int hq_profile_get(hq_ctx *ctx, const char *kernel, double *total_ms, int64_t *launches);
 int hq_profile_reset(hq_ctx *ctx);
 
+/* ---- the kernel path of the last pass (test surface): libhq's addition ----
+ * Nearly every fall-back of the dispatcher gives the same results, often bit for
+ * bit, so results cannot tell which kernels produced them.  hq_last_path reports
+ * it: the record of the last pass enqueued on the context -- an evaluation's, a
+ * rendering's, the last one of hq_refine_population, hq_repair_population or an
+ * hq_search_create / hq_search_run (host-driven or device-resident).  It is
+ * written on the host where each launch is chosen; no kernel knows of it.
+ * The caller sets info->size = sizeof(hq_path_info); at most that many bytes are
+ * filled (the struct may grow at its end) and size is set to the bytes filled.
+ * Before the first pass: sequence 0 and every kind 0 ("none").  A call refused
+ * before it enqueues anything (HQ_ERR_ARG, HQ_ERR_STATE, HQ_ERR_UNSUPPORTED)
+ * leaves the record as it was.  HQ_ERR_ARG: a null pointer, size < 4. */
+enum hq_path_pass { HQ_PASS_NONE = 0, HQ_PASS_FULL = 1, HQ_PASS_ASSIGN_ONLY = 2, HQ_PASS_DITHER = 3 };
+enum hq_path_pixels { HQ_PIXELS_NONE = 0, HQ_PIXELS_U8 = 1, HQ_PIXELS_PLANAR = 2 };
+enum hq_path_grid { HQ_GRID_NONE = 0, HQ_GRID_BUILD_GRID = 1, HQ_GRID_LISTS16 = 2 };
+enum hq_path_argmin {
+    HQ_ARGMIN_NONE = 0, HQ_ARGMIN_ASSIGN_PIPE = 1, HQ_ARGMIN_ASSIGN_PIPE_ORDERED = 2, HQ_ARGMIN_ASSIGN16 = 3,
+    HQ_ARGMIN_ASSIGN_WIDE = 4, HQ_ARGMIN_DITHER = 5
+};
+enum hq_path_cost {
+    HQ_COST_NONE = 0,        /* an assign-only pass, or a mask without a live tile */
+    HQ_COST_16W = 1,         /* cost16w_kernel: 16-row tiles */
+    HQ_COST_MFMA = 2,        /* cost_mfma_kernel: 8 x 108 tiles */
+    HQ_COST_TILED_GENERIC = 3,
+    HQ_COST_PIXEL_GENERIC = 4 /* option "cost_variant" 2 */
+};
+enum hq_path_instance { HQ_INSTANCE_PLAIN = 0, HQ_INSTANCE_MASKED = 1, HQ_INSTANCE_WEIGHTED = 2 };
+enum hq_path_gen_h { HQ_GENH_NONE = 0, HQ_GENH_HPASS = 1, HQ_GENH_HROW = 2, HQ_GENH_HROW4 = 3, HQ_GENH_HMFMA = 4 };
+enum hq_path_gen_v { HQ_GENV_NONE = 0, HQ_GENV_VPASS = 1, HQ_GENV_VTILE = 2, HQ_GENV_VTILE2 = 3, HQ_GENV_VMFMA = 4 };
+/* why the cost did not take the fast kernels: one bit per reason, 0 on the fast path */
+enum hq_path_why {
+    HQ_WHY_HALF = 1,         /* halfSize above 24: no tap bucket */
+    HQ_WHY_VARIANT = 2,      /* option "cost_variant" 1 or 2 */
+    HQ_WHY_PALETTE = 4,      /* a palette channel outside [-32, 1.9] or not finite */
+    HQ_WHY_TAPS = 8,         /* a tap outside the split-f16 range (hq_set_filters) */
+    HQ_WHY_CHUNK_FORM = 16,  /* chunked palette at a bucket or tile form without a chunked kernel */
+    HQ_WHY_NCH = 32,         /* more than 32 chunks (K > 8192) */
+    HQ_WHY_WIDE = 64         /* the exhaustive 32-bit path: K > 16384, "chunked" 0, "grid" 0, HQ_WHY_PALETTE */
+};
+typedef struct hq_path_info {
+    int32_t size;            /* in: sizeof(hq_path_info); out: the bytes filled */
+    int32_t pass;            /* hq_path_pass; a repair iteration's cost-only pass counts as full */
+    int64_t sequence;        /* passes enqueued on this context since hq_create */
+    int32_t ordered;         /* the argmin is the ordered-dithering one */
+    int32_t P, K, nch;       /* this device's palettes, colours, chunks per palette */
+    int32_t idx_bytes;       /* index width: 1, 2 or 4 */
+    int32_t pixels;          /* hq_path_pixels: what the argmin reads */
+    int32_t grid;            /* hq_path_grid */
+    int32_t argmin;          /* hq_path_argmin */
+    int32_t argmin_cmb;      /* assign_pipe: chunks combined per launch (1, 2 or 4) */
+    int32_t argmin_passes;   /* assign_pipe: launches over the chunk groups (nch / 4 above 4 chunks, else 1) */
+    int32_t cost;            /* hq_path_cost */
+    int32_t cost_hb, cost_de, cost_trim, cost_waves, cost_nch; /* the fast kernels' template tuple */
+    int32_t cost_instance;   /* hq_path_instance (fast and generic kernels alike) */
+    int32_t gen_h;           /* hq_path_gen_h */
+    int32_t gen_h_outputs;   /* gen_hrow4: outputs per thread, 4 or 8 */
+    int32_t gen_h_split;     /* gen_hrow4: writes the split-f16 planes (feeds gen_vmfma) */
+    int32_t gen_h_rpt;       /* gen_hmfma: 16-row tiles per workgroup */
+    int32_t gen_v;           /* hq_path_gen_v */
+    int32_t gen_v_rows;      /* gen_vmfma: rows per tile, 64 or 128 */
+    uint32_t why_not_fast;   /* hq_path_why bits */
+    int32_t previous_pass;   /* hq_path_pass of the pass before this one (sequence - 1) ... */
+    int32_t previous_cost;   /* ... and its hq_path_cost: a hybrid iteration is assign-only, then full */
+    int64_t tiles_run, tiles_all; /* hq_mask_info's, of this pass (0: not a fast cost launch) */
+} hq_path_info;
+int hq_last_path(hq_ctx *ctx, hq_path_info *info);
+/* *device_resident = 1 when the search's iterations run on the device, 0 when the
+ * host-driven driver makes one evaluation call each (option "sa_device" 0, a
+ * population above 64 palettes or 512 sub-palettes, K > 16384, "chunked" 0 or
+ * "grid" 0 at K > 256); *nch = its chunks per palette (1 when host-driven: each of
+ * its evaluations chooses its own); *graph = 1 when the last hq_search_run's
+ * kernels went into a hipGraph and were replayed (option "sa_graph" 1 on a
+ * device-resident search without profiling; 0 before the first run).  Any pointer
+ * may be NULL. */
+int hq_search_info(const hq_search *s, int *device_resident, int *nch, int *graph);
+
 /* Tuning knobs (testing / benchmarking; defaults are the measured best).  They
  * may change between calls, also between hq_search_run calls of one search:
  * every evaluation sizes the context's work buffers for the options and image

@@ -22,10 +22,11 @@ import pytest
 
 import hybridquantization_amd as hq
 import oracle as o
+import path_ref as pr
 import reuse_walk as rw
 from hybridquantization_amd import _lib
 from lloyd_ref import cluster_sums_ref, q32
-from mask_ref import inside, masked_cluster_sums, masked_histogram
+from mask_ref import inside, live_tiles_brute, masked_cluster_sums, masked_histogram
 from reseed_ref import cluster_errors_ref
 from seed_ref import coord_byte, coord_float, histogram_ref
 from test_fast_path_gpu import DEFAULTS as FAST_DEFAULTS
@@ -53,7 +54,7 @@ def bits(a):
 # Driving a context
 # ---------------------------------------------------------------------------
 def new_ctx(gpu, de=DE["de76"]):
-    m = hq.ImageManipulation(de, device=gpu)
+    m = pr.Context(de, device=gpu)
     assert m.getOpenCLAvailable()
     m.cur_filters = m.cur_image = None
     return m
@@ -92,6 +93,20 @@ def raw_errors(m, P, K):
     return rc, err, worst
 
 
+def check_class_path(m, cls):
+    """The record of the pass just made against tests/path_ref.py's statement for the class's own
+    options, image form, palettes and mask: a path decision left over from the class before
+    (the chunk count, the palette range, the live-tile list, the image form) shows here even
+    where the fall-back's results are the same."""
+    kind, w, h, _, _ = cls["image"]
+    kw = dict(pal_fits=pr.palette_fits(rw.palettes(cls)), image_u8=kind == "lattice", rows=rw.rows(cls),
+              kind="dither" if cls["op"] == "dither" else "full", ordered=cls["op"] == "ordered")
+    if cls["mask"] is not None:
+        tw, th, _ = pr.fast_tiles(cls["opts"], cls["filters"][2], w, h)
+        kw.update(mask="mask", live_tiles=len(live_tiles_brute(rw.mask_of(cls), w, h, tw, th)))
+    return pr.check(m, cls["K"], cls["P"], cls["name"], opts=cls["opts"], **kw)
+
+
 def operate(m, cls):
     """The class's operation and every read-back -> {name: array}, in a fixed order."""
     P, K, pals = cls["P"], cls["K"], rw.palettes(cls)
@@ -106,6 +121,7 @@ def operate(m, cls):
         out["costs"], out["used"] = m.orderedPopulation(pals, cls["amp"], 2.0, return_used=True)
     else:
         out["costs"], out["used"] = m.computeQuantizationErrorPopulation(pals, 2.0, return_used=True)
+    check_class_path(m, cls)
     for p in rw.local_palettes(cls):
         out[f"indices32[{p}]"] = m.getIndices32(p)
     if cls["opts"]["pixel_err"]:

@@ -19,6 +19,7 @@ import c_oracle
 import de2000_ref as d
 import hybridquantization_amd as hq
 import oracle as o
+import path_ref as pr
 from test_gpu import GOLD, _dark_case, _pal_with_dark, exact_pixel_err, load_case  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -40,7 +41,7 @@ def filt():
 
 
 def _ctx(gpu, rgba, lab, w, illum, de=DE00, dpi=72, vd=45.0, **opts):
-    m = hq.ImageManipulation(de, device=gpu)
+    m = pr.Context(de, device=gpu)
     hq.ScielabProcessor(dpi, vd, hq.Whitepoint.D65, None, m)
     for k, v in opts.items():
         m.setOption(k, v)
@@ -74,7 +75,7 @@ def _err_from_image(img):
 
 @pytest.fixture(scope="module")
 def de00_ctx(gpu):
-    m = hq.ImageManipulation(DE00, device=gpu)
+    m = pr.Context(DE00, device=gpu)
     assert m.getOpenCLAvailable()
     yield m
     m.close()
@@ -408,7 +409,7 @@ def test_de2000_row_block_shards_sum_to_full(gpu, filt, cost_variant):
     lib = hq.load()
 
     def partial(r0, r1):
-        m = hq.ImageManipulation(DE00, device=gpu)
+        m = pr.Context(DE00, device=gpu)
         hq.ScielabProcessor(72, 45.0, hq.Whitepoint.D65, None, m)
         m.setOption("cost_variant", cost_variant)
         m.setImage(rgba.reshape(-1), None, w, filt.illum, row_begin=r0, row_end=r1)
@@ -465,6 +466,7 @@ def _search(m, lib, P, K, imax, seed, chunks):
         hq._lib.check(lib.hq_search_run(handle, chunk, C.byref(ran)), m.ctx)
         hq._lib.check(lib.hq_search_best(handle, hq._lib.fptr(best), C.byref(err), C.byref(it)), m.ctx)
         traj.append((best.copy(), err.value, it.value, ran.value))
+    pr.check_search(m, handle, P, K, ran=True)  # device-resident exactly when sa_device is 1
     lib.hq_search_destroy(handle)
     return traj
 

@@ -13,6 +13,7 @@ import c_oracle
 import de2000_ref as d
 import hybridquantization_amd as hq
 import oracle as o
+import path_ref as pr
 from dither_ref import cube_corners, dither, ramp_image
 from hybridquantization_amd import _lib
 from test_de2000_gpu import EXCL_DEG, _cols
@@ -28,7 +29,7 @@ P = 3
 
 def new_ctx(gpu, de=DE76, **opts):
     """A context with the designed 72 dpi / 45 cm filters (half-width 10)."""
-    m = hq.ImageManipulation(de, device=gpu)
+    m = pr.Context(de, device=gpu)
     sp = hq.ScielabProcessor(72, 45.0, hq.Whitepoint.D65, None, m)
     m.illum = sp.illuminant
     for name, v in opts.items():

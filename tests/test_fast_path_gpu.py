@@ -18,6 +18,7 @@ import pytest
 import de2000_ref as d
 import hybridquantization_amd as hq
 import oracle as o
+import path_ref as pr
 from test_de2000_gpu import EXCL_CAP, EXCL_DEG, FP32_ABS, _cols, _dist
 from test_fast_path import (DPI_45, KINDS, VD, bucket, caller_filters, designed, designed_half, fits_split,
                             high_frequency_image, trim_window_ok)
@@ -38,7 +39,7 @@ F128, F256, F108 = ("16x128", {}), ("16x256", dict(cost_tw=256)), ("8x108", dict
 
 def _ctx(gpu, f, de=DE76, **opts):
     """A context with the filter set `f` uploaded through hq_set_filters."""
-    m = hq.ImageManipulation(de, device=gpu)
+    m = pr.Context(de, device=gpu)
     assert m.getOpenCLAvailable()
     k = [np.ascontiguousarray(a, np.float32) for a in (f.k1, f.k2, f.k3, f.absk3)]
     hq._lib.check(hq.load().hq_set_filters(m.ctx, f.taps, *(hq._lib.fptr(a) for a in k)), m.ctx)
@@ -120,6 +121,7 @@ def _eval76(m, r, n, label, fails, yard=None, idx32=False):
     against the oracle, the cost within 1e-5, the per-pixel bars.  -> (sum, err)."""
     K = r["K"]
     s, used = _partial(m, r["pal"], 1, K)
+    pr.check(m, K, 1, label)  # the kernels the options in force name (tests/path_ref.py)
     idx = m.getIndices32(0) if idx32 else m.getIndices(0)
     np.testing.assert_array_equal(idx, r["idx"].astype(idx.dtype), err_msg=label)
     np.testing.assert_array_equal(used[0] > 0, r["used"] > 0, err_msg=label)
@@ -148,6 +150,7 @@ def _eval94(m, ref, r, label, fails, idx32=False):
     r = _refs94(ref, r)
     K, pal = r["K"], r["pal"]
     cost = m.computeQuantizationErrorPopulation([pal.reshape(-1)], 2.0)[0]
+    pr.check(m, K, 1, label)
     idx = m.getIndices32(0) if idx32 else m.getIndices(0)
     np.testing.assert_array_equal(idx, r["idx"].astype(idx.dtype), err_msg=label)
     err = m.getPixelErrors(0)
@@ -200,6 +203,7 @@ def _eval00(m, ref, r, label, fails, idx32=False):
     assert share < EXCL_CAP, f"{label}: {share:.3g} of the pixels within {EXCL_DEG} degrees of the jump"
     keep = ~y["excl"]
     cost = m.computeQuantizationErrorPopulation([pal.reshape(-1)], 2.0)[0]
+    pr.check(m, K, 1, label)
     idx = m.getIndices32(0) if idx32 else m.getIndices(0)
     np.testing.assert_array_equal(idx, r["idx"].astype(idx.dtype), err_msg=label)
     err = m.getPixelErrors(0)
@@ -419,10 +423,15 @@ def test_chunked_cost_matrix(gpu, K, de, trim):
         m.setImage(rgba.reshape(-1), None if lab is None else lab.reshape(-1), w, m.illum)
         _set(m, chunked=0, **FP32_GENERIC)
         costs, used = m.computeQuantizationErrorPopulation(pals.reshape(P, -1), 2.0, return_used=True)
+        got = pr.check(m, K, P, f"K={K} {de} W={w} exhaustive")
+        assert (got["argmin"], got["idx_bytes"], got["gen_h"], got["gen_v"]) == ("assign_wide", 4, "gen_hrow4", "gen_vtile2")
         exh = (costs, used, [m.getIndices32(p) for p in range(P)], [m.getPixelErrors(p) for p in range(P)])
         for lists16 in (0, 1 if nch >= 4 else 2):
             _set(m, trim=trim, lists16=lists16)
             costs, used = m.computeQuantizationErrorPopulation(pals.reshape(P, -1), 2.0, return_used=True)
+            got = pr.check(m, K, P, f"K={K} {de} trim {trim} W={w} lists16 {lists16}")
+            assert pr.fast_instance(got) == ("cost16w", 10, det, trim, 4, nch)
+            assert got["argmin"] == ("assign16" if lists16 else "assign_pipe")
             for p in range(P):
                 label = f"K={K} {de} trim {trim} W={w} lists16 {lists16} palette {p}"
                 np.testing.assert_array_equal(m.getIndices32(p), exh[2][p], err_msg=label)
@@ -494,6 +503,8 @@ def _run_shard(gpu, f, de, rgba, w, r0, r1, pals, fopts):
     _set(m, **fopts)
     n_own = w * (r1 - r0)
     s, used = _partial(m, pals, P, K)
+    got = pr.check(m, K, P, f"rows [{r0},{r1}) {fopts}")
+    assert pr.fast_instance(got) is not None and got["why_not_fast"] == frozenset()
     out = dict(lab=m.getLabRef()[:4 * n_own].copy(), sum=s, used=used,
                err=[m.getPixelErrors(p)[:n_own].copy() for p in range(P)],
                idx=[m.getIndices32(p)[:n_own].copy() for p in range(P)])
@@ -617,6 +628,12 @@ def test_caller_filters(gpu, kind, half):
             _set(m, **opts)
             _partial(m, r["pal"], 1, r["K"])
             errs[name] = m.getPixelErrors(0)
+            got = pr.check(m, r["K"], 1, f"{kind} half {half} {w}x{h} {name}")
+            if not fits_split(f):  # the taps-range reason and an fp32 pair, whatever was asked for
+                assert "taps" in got["why_not_fast"] and got["gen_h_split"] == 0
+                assert got["gen_h"] in ("gen_hrow4", "gen_hpass") and got["gen_v"] in ("gen_vtile2", "gen_vpass")
+            elif kind == "wide-k1" and name == "16x128":  # trim 1 asked for, the window rule refuses it
+                assert m.options["trim"] == 1 and not trim_window_ok(f) and got["cost_trim"] == 0
         if not fits_split(f):  # the fp32 forms, whatever was asked for
             for name, kind_, _ in forms:
                 if kind_ in ("fast", "mfma"):

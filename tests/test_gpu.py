@@ -13,6 +13,7 @@ import pytest
 import c_oracle
 import hybridquantization_amd as hq
 import oracle as o
+import path_ref as pr
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -26,7 +27,7 @@ def filt():
 
 @pytest.fixture()
 def ip(gpu):
-    m = hq.ImageManipulation(hq.deltaETypes.CIE76, device=gpu)
+    m = pr.Context(hq.deltaETypes.CIE76, device=gpu)
     assert m.getOpenCLAvailable()
     sp = hq.ScielabProcessor(72, 45.0, hq.Whitepoint.D65, None, m)
     m.illum = sp.illuminant
@@ -161,7 +162,7 @@ def test_fast_path_matches_generic(gpu, de, trim, rows, tw):
     partial tiles (800 columns: two interior 256-column tiles)."""
     w, h = (300, 77) if rows == 8 else (290, 93) if tw == 128 else (800, 93)
     R, G, B = o.synthetic_image(w, h, seed=5)
-    m = hq.ImageManipulation(de, device=gpu)
+    m = pr.Context(de, device=gpu)
     sp = hq.ScielabProcessor(72, 45.0, hq.Whitepoint.D65, None, m)
     m.setImage(o.inline_rgba(R, G, B).reshape(-1), None, w, sp.illuminant)
     pals = [o.synthetic_palette(K, 7 + K) for K in (16, 64, 256)]
@@ -185,7 +186,7 @@ def test_generic_hrow4_bitwise(gpu, w, h, dpi, vd):
     segments; 300 dpi / 50 cm is 103 taps (half 51, not a multiple of 4)."""
     R, G, B = o.synthetic_image(w, h, seed=w * h)
     lib = hq.load()
-    m = hq.ImageManipulation(device=gpu)
+    m = pr.Context(device=gpu)
     sp = hq.ScielabProcessor(dpi, vd, hq.Whitepoint.D65, None, m)
     m.setImage(o.inline_rgba(R, G, B).reshape(-1), None, w, sp.illuminant)
     m.setOption("cost_variant", 1)
@@ -239,7 +240,7 @@ def test_fast_path_matches_generic_wide_buckets(gpu, de, dpi, vd):
     for both dE formulas, on interior, edge and partial tiles."""
     w, h = 290, 93
     R, G, B = o.synthetic_image(w, h, seed=dpi)
-    m = hq.ImageManipulation(de, device=gpu)
+    m = pr.Context(de, device=gpu)
     sp = hq.ScielabProcessor(dpi, vd, hq.Whitepoint.D65, None, m)
     m.setImage(o.inline_rgba(R, G, B).reshape(-1), None, w, sp.illuminant)
     pals = [o.synthetic_palette(K, 11 + K) for K in (16, 256)]
@@ -267,7 +268,7 @@ def test_viewing_geometry_vs_oracle(gpu, dpi, vd, half):
     for (w, h) in ((256, 256), (301, 173)):
         R, G, B = o.synthetic_image(w, h, seed=w + dpi)
         rgba = o.inline_rgba(R, G, B)
-        m = hq.ImageManipulation(device=gpu)
+        m = pr.Context(device=gpu)
         sp = hq.ScielabProcessor(dpi, vd, hq.Whitepoint.D65, None, m)
         m.setImage(rgba.reshape(-1), None, w, sp.illuminant)  # device LabRef
         lab_dev = m.getLabRef().reshape(-1, 4)
@@ -505,6 +506,8 @@ def test_out_of_range_palette_takes_generic_path(ip, filt):
     pal[5, 2] = -40.0
     pals = np.stack([pal, g["palettes"][1]])
     costs = ip.computeQuantizationErrorPopulation(pals.reshape(2, -1), 2.0)
+    got = pr.check(ip, pals.shape[1], 2, "out of range", pal_fits=pr.palette_fits(pals))
+    assert got["why_not_fast"] == {"palette"} and (got["gen_h"], got["gen_h_split"], got["gen_v"]) == ("gen_hrow4", 0, "gen_vtile2")
     for p in range(2):
         ref, parts = c_oracle.eval_palette(rgba, g["lab"], pals[p], filt, w, return_parts=True)
         assert np.isfinite(costs[p]) and abs(costs[p] - ref) <= 1e-6 * abs(ref), (p, costs[p], ref)
@@ -525,6 +528,8 @@ def test_out_of_range_palette_every_pixel(ip, filt):
     pal[:, 0] -= 0.5
     pals = np.stack([pal, g["palettes"][1]])
     costs = ip.computeQuantizationErrorPopulation(pals.reshape(2, -1), 2.0)
+    got = pr.check(ip, pals.shape[1], 2, "out of range", pal_fits=pr.palette_fits(pals))
+    assert got["why_not_fast"] == {"palette"} and (got["gen_h"], got["gen_h_split"], got["gen_v"]) == ("gen_hrow4", 0, "gen_vtile2")
     for p in range(2):
         ref, parts = c_oracle.eval_palette(rgba, g["lab"], pals[p], filt, w, return_parts=True)
         assert np.isfinite(costs[p]) and abs(costs[p] - ref) <= 1e-6 * abs(ref), (p, costs[p], ref)
@@ -547,7 +552,7 @@ def test_wide_palette_vs_oracle(gpu, filt, K, P):
     w = h = 256
     R, G, B = o.synthetic_image(w, h, seed=K)
     rgba = o.inline_rgba(R, G, B)
-    m = hq.ImageManipulation(device=gpu)
+    m = pr.Context(device=gpu)
     hq.ScielabProcessor(72, 45.0, hq.Whitepoint.D65, None, m)
     m.setImage(rgba.reshape(-1), None, w, filt.illum)
     lab = m.getLabRef().reshape(-1, 4)
@@ -557,6 +562,10 @@ def test_wide_palette_vs_oracle(gpu, filt, K, P):
     pals[-1, 100:110, :3] = rgba[1000:1010, :3]
     pals[-1, K - 5:, :3] = rgba[1000:1005, :3]  # same colours again at higher indices
     costs, used = m.computeQuantizationErrorPopulation(pals.reshape(P, -1), 2.0, return_used=True)
+    got = pr.check(m, K, P, f"K={K}")  # the kernels the docstring names
+    assert (got["grid"], got["argmin"], got["argmin_cmb"]) == (("build_grid", "assign_pipe", 2) if K <= 512 else
+                                                                ("lists16", "assign16", 0))
+    assert pr.fast_instance(got) == ("cost16w", 10, 0, 1, 4, pr.chunk_count(K))
     nt = _threads()
     for p in range(P):
         ref, parts = c_oracle.eval_palette(rgba, lab, pals[p], filt, w, nthreads=nt, return_parts=True)
@@ -596,13 +605,21 @@ def test_chunked_palettes_match_exhaustive(gpu, filt, K):
     pal[K - 3, :3] = 0.0
     pal[K - 2, :3] = 1.0
     pals = np.stack([pal, o.synthetic_palette(K, 77)])
-    m = hq.ImageManipulation(device=gpu)
+    m = pr.Context(device=gpu)
     hq.ScielabProcessor(72, 45.0, hq.Whitepoint.D65, None, m)
     m.setImage(rgba.reshape(-1), None, w, filt.illum)
     res = {}
     for chunked in (1, 0):
         m.setOption("chunked", chunked)
         costs, used = m.computeQuantizationErrorPopulation(pals.reshape(2, -1), 2.0, return_used=True)
+        got = pr.check(m, K, 2, f"K={K} chunked {chunked}")
+        nch = pr.chunk_count(K)
+        if chunked:  # 2 chunks and 64: per-chunk grids; between: the lists; the fast stencil up to 32 chunks
+            assert (got["nch"], got["idx_bytes"]) == (nch, 2)
+            assert got["argmin"] == ("assign16" if 4 <= nch <= 32 else "assign_pipe")
+            assert got["cost"] == ("cost16w" if nch <= 32 else "tiled_generic") and got["cost_nch"] == (nch if nch <= 32 else 0)
+        else:
+            assert (got["nch"], got["idx_bytes"], got["argmin"], got["cost"]) == (1, 4, "assign_wide", "tiled_generic")
         res[chunked] = (costs, used, [m.getIndices32(p) for p in range(2)])
     for p in range(2):
         np.testing.assert_array_equal(res[1][2][p], res[0][2][p])
@@ -642,7 +659,7 @@ def test_lists16_match_chunked_and_exhaustive(gpu, filt, K, img_u8, mode):
     far = uni.copy()
     far[:, :3] = (1.6 * far[:, :3] - 0.3).astype(np.float32)
     pals = np.stack([clus, uni, dup, far])
-    m = hq.ImageManipulation(device=gpu)
+    m = pr.Context(device=gpu)
     hq.ScielabProcessor(72, 45.0, hq.Whitepoint.D65, None, m)
     m.setImage(rgba.reshape(-1), None, w, filt.illum)
     m.setOption("img_u8", img_u8)
@@ -652,6 +669,12 @@ def test_lists16_match_chunked_and_exhaustive(gpu, filt, K, img_u8, mode):
         for k, v in opts.items():
             m.setOption(k, v)
         costs, used = m.computeQuantizationErrorPopulation(pals.reshape(len(pals), -1), 2.0, return_used=True)
+        got = pr.check(m, K, len(pals), f"K={K} {name}")
+        nch = pr.chunk_count(K)
+        want = {"n16": ("lists16", "assign16", 0, 0, "u8" if img_u8 else "planar"),
+                "chunk": ("build_grid", "assign_pipe", min(nch, 4), max(nch // 4, 1), "u8" if img_u8 else "planar"),
+                "exh": ("none", "assign_wide", 0, 0, "planar")}[name]
+        assert (got["grid"], got["argmin"], got["argmin_cmb"], got["argmin_passes"], got["pixels"]) == want, (name, got)
         res[name] = (costs, used, [m.getIndices32(p) for p in range(len(pals))])
     m.close()
     for other in ("chunk", "exh"):
@@ -700,13 +723,22 @@ def test_large_palettes_vs_oracle(gpu, filt, K, opts):
     far[:, :3] = (1.6 * far[:, :3] - 0.3).astype(np.float32)
     pals = np.stack([clus, uni, far])
     P = len(pals)
-    m = hq.ImageManipulation(device=gpu)
+    m = pr.Context(device=gpu)
     hq.ScielabProcessor(72, 45.0, hq.Whitepoint.D65, None, m)
     m.setImage(rgba.reshape(-1), None, w, filt.illum)
     for k, v in opts.items():
         m.setOption(k, v)
     lab = m.getLabRef().reshape(-1, 4)
     costs, used = m.computeQuantizationErrorPopulation(pals.reshape(P, -1), 2.0, return_used=True)
+    got = pr.check(m, K, P, f"K={K} {opts}")  # the path each case's comment names
+    if opts or K > 16384:
+        want = ("none", "assign_wide", 4, "tiled_generic", 0)
+    elif K > 8192:
+        want = ("build_grid", "assign_pipe", 2, "tiled_generic", 0)
+    else:
+        want = ("lists16", "assign16", 2, "cost16w", 32)
+    assert (got["grid"], got["argmin"], got["idx_bytes"], got["cost"], got["cost_nch"]) == want, got
+    assert K <= 8192 or K > 16384 or opts or (got["argmin_cmb"], got["argmin_passes"]) == (4, 16)
     idx = [m.getIndices32(p) for p in range(P)]
     m.close()
     nt = _threads()
@@ -785,6 +817,9 @@ def test_nonfinite_palette_falls_back_exactly(ip, K):
         pal[256, 2] = np.nan  # colour 0 of chunk 1
     ip.setImage(px.reshape(-1), np.zeros_like(px).reshape(-1), w, ip.illum)
     ip.computeQuantizationErrorPopulation([pal.reshape(-1)], 2.0)
+    got = pr.check(ip, K, 1, f"K={K}", pal_fits=pr.palette_fits(pal))
+    assert "palette" in got["why_not_fast"] and got["argmin"] == ("assign_wide" if K > 256 else "assign_pipe")
+    assert got["nch"] == 1 and got["gen_v"] == "gen_vtile2"
     ref_idx, _ = c_oracle.assign(px, pal)
     np.testing.assert_array_equal(ip.getIndices32(0), ref_idx.astype(np.uint32))
 
@@ -797,7 +832,7 @@ def test_row_block_shards_sum_to_full(gpu, filt):
     R, G, B = o.synthetic_image(w, h, seed=4)
     rgba = o.inline_rgba(R, G, B).reshape(-1)
     pals = np.stack([o.synthetic_palette(K, 60 + p) for p in range(P)]).reshape(P, -1)
-    full = hq.ImageManipulation(device=gpu)
+    full = pr.Context(device=gpu)
     hq.ScielabProcessor(72, 45.0, hq.Whitepoint.D65, None, full)
     full.setImage(rgba, None, w, filt.illum)
     lib = hq.load()
@@ -808,7 +843,7 @@ def test_row_block_shards_sum_to_full(gpu, filt):
         bounds = np.linspace(0, h, nshards + 1).astype(int)
         acc = np.zeros(P * (1 + K))
         for r0, r1 in zip(bounds[:-1], bounds[1:]):
-            sh = hq.ImageManipulation(device=gpu)
+            sh = pr.Context(device=gpu)
             hq.ScielabProcessor(72, 45.0, hq.Whitepoint.D65, None, sh)
             sh.setImage(rgba, None, w, filt.illum, row_begin=r0, row_end=r1)
             part = np.zeros(P * (1 + K))
@@ -831,7 +866,7 @@ def test_rccl_single_rank_allreduce(gpu, filt):
     R, G, B = o.synthetic_image(w, h, seed=6)
     rgba = o.inline_rgba(R, G, B).reshape(-1)
     pals = np.stack([o.synthetic_palette(K, 80 + p) for p in range(P)]).reshape(P, -1)
-    m = hq.ImageManipulation(device=gpu)
+    m = pr.Context(device=gpu)
     hq.ScielabProcessor(72, 45.0, hq.Whitepoint.D65, None, m)
     m.setImage(rgba, None, w, filt.illum, row_begin=0, row_end=h)
     c0, u0 = m.computeQuantizationErrorPopulation(pals, 2.0, return_used=True)
@@ -858,7 +893,7 @@ def test_quantize_matches_oracle(ip):
 @pytest.mark.parametrize("de", [hq.deltaETypes.CIE76, hq.deltaETypes.CIE94])
 def test_compute_error_matches_oracle(gpu, de):
     g, R, G, B = load_case("case_97x53_k64")
-    m = hq.ImageManipulation(de, device=gpu)
+    m = pr.Context(de, device=gpu)
     rng = np.random.default_rng(0)
     other = (g["lab"] + rng.normal(0, 2, g["lab"].shape)).astype(np.float32)
     other[:, 3] = 0
@@ -910,7 +945,7 @@ def test_device_search_matches_host_driven(gpu, filt, P, K):
     import ctypes as C
     w, h = 96, 64
     R, G, B = o.synthetic_image(w, h, seed=9)
-    m = hq.ImageManipulation(device=gpu)
+    m = pr.Context(device=gpu)
     hq.ScielabProcessor(72, 45.0, hq.Whitepoint.D65, None, m)
     m.setImage(o.inline_rgba(R, G, B).reshape(-1), None, w, filt.illum)
     lib = hq.load()
@@ -930,6 +965,8 @@ def test_device_search_matches_host_driven(gpu, filt, P, K):
         err = C.c_double()
         it = C.c_int()
         hq._lib.check(lib.hq_search_best(handle, hq._lib.fptr(best), C.byref(err), C.byref(it)), m.ctx)
+        # (the extremes the docstring names are device-resident, not the host driver against itself)
+        assert pr.check_search(m, handle, P, K, ran=True, label=f"P={P} K={K}")["device_resident"] == bool(dev)
         lib.hq_search_destroy(handle)
         res[dev] = (best, err.value, it.value, total)
     assert res[1][2] == res[0][2] == res[1][3] == res[0][3] == 50
@@ -953,7 +990,7 @@ def test_device_search_de94_nan_costs(gpu, filt, P):
     import ctypes as C
     w, h, K = 256, 128, 16
     R, G, B = o.synthetic_image(w, h, seed=19)
-    m = hq.ImageManipulation(hq.deltaETypes.CIE94, device=gpu)
+    m = pr.Context(hq.deltaETypes.CIE94, device=gpu)
     hq.ScielabProcessor(72, 45.0, hq.Whitepoint.D65, None, m)
     m.setImage(o.inline_rgba(R, G, B).reshape(-1), None, w, filt.illum)
     lib = hq.load()
@@ -971,6 +1008,7 @@ def test_device_search_de94_nan_costs(gpu, filt, P):
         for j, chunk in enumerate((1, 29)):
             hq._lib.check(lib.hq_search_run(handle, chunk, C.byref(ran)), m.ctx)
             hq._lib.check(lib.hq_search_best(handle, hq._lib.fptr(best[j]), C.byref(err), C.byref(it)), m.ctx)
+        assert pr.check_search(m, handle, P, K, ran=True)["device_resident"] == bool(dev)
         lib.hq_search_destroy(handle)
         res[dev] = (best, err.value, it.value)
     print(f"P={P}: best error host {res[0][1]!r} device {res[1][1]!r}")
@@ -997,7 +1035,7 @@ def test_device_search_with_single_rank_comm(gpu, filt, split):
     lib = hq.load()
     res = []
     for comm in (False, True):
-        m = hq.ImageManipulation(device=gpu)
+        m = pr.Context(device=gpu)
         hq.ScielabProcessor(72, 45.0, hq.Whitepoint.D65, None, m)
         m.setImage(o.inline_rgba(R, G, B).reshape(-1), None, w, filt.illum)
         m.setOption("palette_split", split)
@@ -1056,7 +1094,7 @@ def test_device_search_folds_rank_blocks(gpu, filt, K, P):
     pals = np.stack([o.synthetic_palette(K, 30 + p) for p in range(P)]).reshape(P, -1)
     res = []
     for nb, b in ((1, 0), (2, 1), (3, 0), (8, 5), (8, 7)):
-        m = hq.ImageManipulation(device=gpu)
+        m = pr.Context(device=gpu)
         hq.ScielabProcessor(72, 45.0, hq.Whitepoint.D65, None, m)
         m.setImage(o.inline_rgba(R, G, B).reshape(-1), None, w, filt.illum)
         m.setOption("fold_blocks", nb)
@@ -1072,6 +1110,7 @@ def test_device_search_folds_rank_blocks(gpu, filt, K, P):
         err = C.c_double()
         it = C.c_int()
         hq._lib.check(lib.hq_search_best(handle, hq._lib.fptr(best), C.byref(err), C.byref(it)), m.ctx)
+        assert pr.check_search(m, handle, P, K, ran=True)["device_resident"]
         lib.hq_search_destroy(handle)
         m.close()
         res.append((costs, best, err.value, it.value))
@@ -1100,7 +1139,7 @@ def test_palette_slices_sum_to_full(gpu, filt, K, P, ranks, opts):
     lib = hq.load()
 
     def run(slice_rank):
-        m = hq.ImageManipulation(device=gpu)
+        m = pr.Context(device=gpu)
         hq.ScielabProcessor(72, 45.0, hq.Whitepoint.D65, None, m)
         m.setImage(rgba, None, w, filt.illum)
         for k, v in opts.items():
@@ -1144,7 +1183,7 @@ def test_palette_slice_rank_out_of_range(gpu, filt):
     R, G, B = o.synthetic_image(w, h, seed=5)
     rgba = o.inline_rgba(R, G, B).reshape(-1)
     pals = np.stack([o.synthetic_palette(K, 2 + p) for p in range(P)]).reshape(P, -1)
-    m = hq.ImageManipulation(device=gpu)
+    m = pr.Context(device=gpu)
     hq.ScielabProcessor(72, 45.0, hq.Whitepoint.D65, None, m)
     m.setImage(rgba, None, w, filt.illum)
     with pytest.raises(hq.HQError):
@@ -1213,9 +1252,12 @@ def test_packed_image_path(gpu, filt, off_lattice):
     pals = np.stack([o.synthetic_palette(K, 60 + p) for p in range(P)])
     pals[4, 17, :3] = [R[9], G[9], B[9]]  # a colour on a pixel
     c1, used1 = m.computeQuantizationErrorPopulation(pals.reshape(P, -1), 2.0, return_used=True)
+    got = pr.check(m, K, P, "img_u8 1", image_u8=not off_lattice)  # which form ran, not only that they agree
+    assert got["pixels"] == ("planar" if off_lattice else "u8") and got["argmin"] == "assign_pipe"
     idx1 = [m.getIndices(p) for p in range(P)]
     m.setOption("img_u8", 0)
     c0, used0 = m.computeQuantizationErrorPopulation(pals.reshape(P, -1), 2.0, return_used=True)
+    assert pr.check(m, K, P, "img_u8 0", image_u8=not off_lattice)["pixels"] == "planar"
     np.testing.assert_array_equal(c0, c1)
     np.testing.assert_array_equal(used0, used1)
     px = np.stack([R, G, B, np.zeros_like(R)], 1)
@@ -1231,7 +1273,7 @@ def test_full_size_properties(gpu, filt):
     w = h = 4096
     K = 256
     R, G, B = o.synthetic_image(w, h, seed=1)
-    m = hq.ImageManipulation(device=gpu)
+    m = pr.Context(device=gpu)
     hq.ScielabProcessor(72, 45.0, hq.Whitepoint.D65, None, m)
     lib = hq.load()
     hq._lib.check(lib.hq_set_image_planar_shard(m.ctx, hq._lib.fptr(R), hq._lib.fptr(G),
@@ -1306,7 +1348,7 @@ def _threads():
 
 
 def _planar_ctx(gpu, R, G, B, w, h, illum, r0=0, r1=None):
-    m = hq.ImageManipulation(device=gpu)
+    m = pr.Context(device=gpu)
     hq.ScielabProcessor(72, 45.0, hq.Whitepoint.D65, None, m)
     r1 = h if r1 is None else r1
     lib = hq.load()
@@ -1552,7 +1594,7 @@ def test_pixel_errors_vs_oracle(gpu, case, variant):
         pals = [_pal_with_dark(64, 900 + w), _pal_with_dark(256, 901 + w)]
         lab = c_oracle.srgb_to_scielab(R, G, B, f, w, nthreads=_threads())
     rgba = o.inline_rgba(R, G, B)
-    m = hq.ImageManipulation(device=gpu)
+    m = pr.Context(device=gpu)
     sp = hq.ScielabProcessor(dpi, vd, hq.Whitepoint.D65, None, m)
     m.setOption("pixel_err", 1)
     m.setOption("cost_variant", variant[0])
@@ -1630,7 +1672,7 @@ def test_pixel_errors_de94_vs_oracle(gpu, case, variant):
         pals = [_pal_with_dark(64, 900 + w), _pal_with_dark(256, 901 + w)]
         lab = c_oracle.srgb_to_scielab(R, G, B, f, w, nthreads=_threads())
     rgba = o.inline_rgba(R, G, B)
-    m = hq.ImageManipulation(hq.deltaETypes.CIE94, device=gpu)
+    m = pr.Context(hq.deltaETypes.CIE94, device=gpu)
     sp = hq.ScielabProcessor(dpi, vd, hq.Whitepoint.D65, None, m)
     m.setOption("pixel_err", 1)
     m.setOption("cost_variant", variant[0])
@@ -1678,7 +1720,7 @@ def test_small_images_and_palettes_vs_oracle(gpu, filt, w, h, K, P):
     R, G, B = o.synthetic_image(w, h, seed=w * 131 + h + K)
     rgba = o.inline_rgba(R, G, B)
     pals = np.stack([o.synthetic_palette(K, 500 + p) for p in range(P)])
-    m = hq.ImageManipulation(device=gpu)
+    m = pr.Context(device=gpu)
     hq.ScielabProcessor(72, 45.0, hq.Whitepoint.D65, None, m)
     m.setImage(rgba.reshape(-1), None, w, filt.illum)
     lab = m.getLabRef().reshape(-1, 4)

@@ -13,6 +13,7 @@ import pytest
 
 import hybridquantization_amd as hq
 import oracle as o
+import path_ref as pr
 from hybridquantization_amd import _lib
 from lloyd_ref import bits, centroids_ref, cluster_sums_ref
 from test_lloyd_gpu import blob_image, float_image, lattice_image
@@ -36,7 +37,7 @@ def images():
 
 
 def new_ctx(gpu, de=hq.deltaETypes.CIE76):
-    m = hq.ImageManipulation(de, device=gpu)
+    m = pr.Context(de, device=gpu)
     sp = hq.ScielabProcessor(72, 45.0, hq.Whitepoint.D65, None, m)
     m.illum = sp.illuminant
     return m
@@ -50,6 +51,7 @@ class Search:
         params = sw.params()
         self.h = C.c_void_p()
         _lib.check(self.lib.hq_search_create(m.ctx, C.byref(params), K, sw.seed, C.byref(self.h)), m.ctx)
+        pr.check_search(m, self.h, params.population, K)  # device-resident exactly when sa_device is 1
 
     def set_lloyd(self, every):
         return self.lib.hq_search_set_lloyd(self.h, every)
@@ -81,6 +83,7 @@ def run_plan(m, K, P, seed, plan, device, imax=50):
             if every is not None:
                 assert s.set_lloyd(every) == _lib.HQ_OK, m._lib.hq_last_error(m.ctx)
             total += s.run(n)[1]
+            pr.check_search(m, s.h, P, K, ran=True)  # captured exactly when sa_graph is 1
         return s.best() + (total,)
     finally:
         s.close()

@@ -11,6 +11,7 @@ import pytest
 
 import hybridquantization_amd as hq
 import oracle as o
+import path_ref as pr
 from hybridquantization_amd import _lib
 from lloyd_ref import DEN32, bits, centroids_ref, cluster_sums_ref, q32
 
@@ -19,7 +20,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture()
 def ip(gpu):
-    m = hq.ImageManipulation(hq.deltaETypes.CIE76, device=gpu)
+    m = pr.Context(hq.deltaETypes.CIE76, device=gpu)
     assert m.getOpenCLAvailable()
     sp = hq.ScielabProcessor(72, 45.0, hq.Whitepoint.D65, None, m)
     assert m.halfSize == 10
@@ -29,7 +30,7 @@ def ip(gpu):
 
 
 def make_ctx(gpu):
-    m = hq.ImageManipulation(hq.deltaETypes.CIE76, device=gpu)
+    m = pr.Context(hq.deltaETypes.CIE76, device=gpu)
     sp = hq.ScielabProcessor(72, 45.0, hq.Whitepoint.D65, None, m)
     m.illum = sp.illuminant
     return m

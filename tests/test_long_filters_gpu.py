@@ -18,6 +18,7 @@ import c_oracle
 import de2000_ref as d
 import hybridquantization_amd as hq
 import oracle as o
+import path_ref as pr
 from test_de2000_gpu import EXCL_CAP, EXCL_DEG, FP32_ABS, _cols, _dist
 from test_gpu import _dark_case, _de94_exact, _pal_with_dark, _threads, exact_pixel_err
 
@@ -44,7 +45,7 @@ def _filters(dpi, vd, half):
 
 
 def _ctx(gpu, dpi, vd, de=DE76, **opts):
-    m = hq.ImageManipulation(de, device=gpu)
+    m = pr.Context(de, device=gpu)
     assert m.getOpenCLAvailable()
     sp = hq.ScielabProcessor(dpi, vd, hq.Whitepoint.D65, None, m)
     m.illum = sp.illuminant
@@ -202,6 +203,8 @@ def test_boundary_half_widths(gpu, half, size):
             _set(m, **opts)
             label = f"half {half} {size} {w}x{h} K={K} {name}"
             s, used = _partial(m, pal, 1, K)
+            got = pr.check(m, K, 1, label)  # the pair this form's options name (tests/path_ref.py)
+            assert kind == {"gen_vmfma": "mfma", "none": "mfma", "gen_vpass": "ref"}.get(got["gen_v"], "fp32"), (label, got)
             np.testing.assert_array_equal(m.getIndices(0), r["idx"].astype(np.uint8), err_msg=label)
             np.testing.assert_array_equal(used[0] > 0, r["used"] > 0, err_msg=label)
             cost = s[0] / n + 2.0 * unused  # (hq_eval_population's statement; checked on the default form below)
@@ -303,6 +306,7 @@ def test_de94_long_filters(gpu, half):
         for name, opts in _de_forms(half):
             _set(m, **opts)
             cost = m.computeQuantizationErrorPopulation([pal.reshape(-1)], 2.0)[0]
+            assert pr.check(m, K, 1, f"half {half} de94 {name}")["cost_de"] == DE94
             np.testing.assert_array_equal(m.getIndices(0), r["idx"].astype(np.uint8))
             err = m.getPixelErrors(0)
             nan_g = np.isnan(err)
@@ -355,6 +359,7 @@ def test_de2000_long_filters(gpu, half):
         for name, opts in _de_forms(half):
             _set(m, **opts)
             cost = m.computeQuantizationErrorPopulation([pal.reshape(-1)], 2.0)[0]
+            assert pr.check(m, K, 1, f"half {half} de2000 {name}")["cost_de"] == DE00
             np.testing.assert_array_equal(m.getIndices(0), r["idx"].astype(np.uint8))
             err = m.getPixelErrors(0)
             assert np.isfinite(err).all() and np.isfinite(cost)
@@ -400,6 +405,9 @@ def test_index_widths_long_filters(gpu, K, opts):
     for name, fo in forms:
         _set(m, **fo)
         costs, used = m.computeQuantizationErrorPopulation(pals.reshape(P, -1), 2.0, return_used=True)
+        got = pr.check(m, K, P, f"K={K} {opts} {name}")
+        assert got["idx_bytes"] == (4 if K > 16384 or opts.get("chunked") == 0 else 2), got
+        assert got["gen_h"] == {"hmfma": "gen_hmfma", "hrow": "gen_hrow", "hpass": "gen_hpass"}.get(name, "gen_hrow4")
         for p, r in enumerate(ref["pals"]):
             label = f"K={K} {opts} {name} palette {p}"
             np.testing.assert_array_equal(m.getIndices32(p), r["idx"].astype(np.uint32), err_msg=label)
@@ -449,7 +457,16 @@ def test_pal_generic_long_filters(gpu, K, kind):
     m = _ctx(gpu, dpi, vd)
     m.setImage(rgba.reshape(-1), lab.reshape(-1), w, m.illum)
     alone = m.computeQuantizationErrorPopulation([good.reshape(-1)], 2.0)[0]
+    got = pr.check(m, K, 1, f"K={K} alone")
+    assert (got["gen_h"], got["gen_v"], got["why_not_fast"]) == ("gen_hmfma", "gen_vmfma", frozenset({"half"}))
     costs, used = m.computeQuantizationErrorPopulation(pals.reshape(2, -1), 2.0, return_used=True)
+    fits = kind == "1.5"
+    assert pr.palette_fits(pals) == fits
+    got = pr.check(m, K, 2, f"K={K} {kind}", pal_fits=fits)
+    assert ("palette" in got["why_not_fast"]) == (not fits)
+    if not fits:  # the fp32 pair, and above 256 colours the exhaustive 32-bit argmin
+        assert (got["gen_h"], got["gen_h_split"], got["gen_v"]) == ("gen_hrow4", 0, "gen_vtile2")
+        assert got["argmin"] == ("assign_wide" if K > 256 else "assign_pipe")
     idx = [m.getIndices32(p) for p in range(2)]
     m.close()
     for p in range(2):
@@ -492,6 +509,7 @@ def _run_shard(gpu, dpi, vd, de, rgba, w, r0, r1, pals, P, K, forms):
     for name, _, opts in forms:
         _set(m, **opts)
         s, used = _partial(m, pals, P, K)
+        pr.check(m, K, P, f"rows [{r0},{r1}) {name}")
         out["forms"][name] = dict(sum=s, used=used, err=[m.getPixelErrors(p)[:n_own].copy() for p in range(P)],
                                   idx=[m.getIndices32(p)[:n_own].copy() for p in range(P)])
     m.close()
@@ -614,6 +632,9 @@ def test_device_search_long_filters(gpu):
         err = C.c_double()
         it = C.c_int()
         hq._lib.check(lib.hq_search_best(handle, hq._lib.fptr(best), C.byref(err), C.byref(it)), m.ctx)
+        assert pr.check_search(m, handle, P, K, ran=True)["device_resident"] == bool(dev)
+        got = m.lastPath()  # the search's last pass took the long-filter pair
+        assert (got["gen_h"], got["gen_v"], got["why_not_fast"]) == ("gen_hmfma", "gen_vmfma", {"half"})
         lib.hq_search_destroy(handle)
         res[dev] = (best, err.value, it.value, total)
     m.close()
@@ -646,13 +667,13 @@ def test_switching_filters_on_a_live_context(gpu):
         costs, used = m.computeQuantizationErrorPopulation(pals, 2.0, return_used=True)
         return costs, used, [m.getIndices(p) for p in range(P)], m.getLabRef()
 
-    m = hq.ImageManipulation(device=gpu)
+    m = pr.Context(device=gpu)
     first = switch(m, 72)
     middle = switch(m, DPI[65])
     assert m.halfSize == 65
     last = switch(m, 72)
     m.close()
-    fresh_ctx = hq.ImageManipulation(device=gpu)
+    fresh_ctx = pr.Context(device=gpu)
     fresh = switch(fresh_ctx, DPI[65])
     fresh_ctx.close()
     for a, b in ((first, last), (middle, fresh)):

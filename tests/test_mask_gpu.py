@@ -11,6 +11,7 @@ import pytest
 import c_oracle
 import hybridquantization_amd as hq
 import oracle as o
+import path_ref as pr
 from hybridquantization_amd import _lib
 from lloyd_ref import DEN32, q32
 from mask_ref import (inside, live_tiles, masked_cluster_sums, masked_histogram, masked_sum, masks_for, rectangle,
@@ -42,6 +43,18 @@ def set_image(m, rgba, w, **kw):
 
 def plain(m, pals):
     return m.computeQuantizationErrorPopulation(pals, DELTA, return_used=True)
+
+
+def path_under(m, pals, cover, label, weighted=False):
+    """The record of the last pass of `pals` against tests/path_ref.py under the mask or weight map
+    `cover` (None: neither): the instance (plain / masked / weighted) and the tiles that ran."""
+    Pn, K = pals.shape[0], pals.shape[1] // 4
+    kw = {}
+    if cover is not None:
+        tw, th, _ = pr.fast_tiles(m.options, m.halfSize, m.w, m.h)
+        on = (np.asarray(cover).reshape(m.h, m.w) != 0).astype(np.uint8)
+        kw = dict(mask="weights" if weighted else "mask", live_tiles=len(live_tiles(on, m.w, m.h, tw, th)))
+    return pr.check(m, K, Pn, label, **kw)
 
 
 def indices(m, p, K):
@@ -233,6 +246,11 @@ def test_all_ones_and_no_mask_are_the_unmasked_library(gpu, img_u8):
         m.setMask(np.ones((AH, AW), np.uint8))
         _assert_everything_equal(want, _everything(m, pals), "all ones")
         assert m.maskInfo() == (AW * AH, AW * AH, 4, 4)
+        plain(m, pals)  # the masked instance over every tile, not the plain one
+        got = path_under(m, pals, np.ones((AH, AW), np.uint8), "all ones")
+        assert (got["cost_instance"], got["tiles_run"], got["tiles_all"]) == ("masked", 4, 4)
+        plain(fresh, pals)
+        assert path_under(fresh, pals, None, "no mask")["cost_instance"] == "plain"
         m.setMask(masks_for(AW, AH)["bernoulli"])
         other = _everything(m, pals)
         assert not np.array_equal(other["costs"], want["costs"]) and not np.array_equal(other["sums"][0], want["sums"][0])
@@ -260,33 +278,48 @@ def test_the_skip_ran(gpu):
         m.setMask(rect)
         plain(m, pals)
         assert m.maskInfo() == (120 * 13, 120 * 13, 1, 9)
+        got = path_under(m, pals, rect, "skip")
+        assert (got["cost"], got["cost_instance"], got["tiles_run"], got["tiles_all"]) == ("cost16w", "masked", 1, 9)
         m.setOption("mask_skip", 0)
         plain(m, pals)
         assert m.maskInfo()[2:] == (9, 9)
+        got = path_under(m, pals, rect, "mask_skip 0")
+        assert (got["cost_instance"], got["tiles_run"], got["tiles_all"]) == ("masked", 9, 9)
         m.setOption("mask_skip", 1)
         m.setOption("cost_rows", 8)  # 8 x 108 tiles: 3 x 5
         plain(m, pals)
         want = live_tiles(rect, BW, BH, 108, 8)
         assert m.maskInfo()[2:] == (len(want), 15) and len(want) == 4
+        got = path_under(m, pals, rect, "8 x 108")
+        assert (got["cost"], got["cost_instance"], got["tiles_run"], got["tiles_all"]) == ("cost_mfma", "masked", 4, 15)
         m.setOption("cost_rows", 16)
         m.setOption("cost_tw", 256)  # 16 x 256 tiles: 2 x 3, the rectangle inside tile (0, 1)
         plain(m, pals)
         assert m.maskInfo()[2:] == (len(live_tiles(rect, BW, BH, 256, 16)), 6) == (1, 6)
+        got = path_under(m, pals, rect, "16 x 256")
+        assert (got["cost_waves"], got["cost_instance"], got["tiles_run"], got["tiles_all"]) == (8, "masked", 1, 6)
         m.setOption("cost_tw", 128)
         m.setOption("pixel_err", 1)  # every tile stores its pixels' dE
         plain(m, pals)
         assert m.maskInfo()[2:] == (9, 9)
+        got = path_under(m, pals, rect, "pixel_err 1")
+        assert (got["cost_instance"], got["tiles_run"], got["tiles_all"]) == ("masked", 9, 9)
         m.setOption("pixel_err", 0)
         m.setOption("cost_variant", 1)  # the generic path
         plain(m, pals)
         assert m.maskInfo()[2:] == (0, 0)
+        got = path_under(m, pals, rect, "generic")
+        assert (got["cost"], got["cost_instance"], got["tiles_run"], got["tiles_all"]) == ("tiled_generic", "masked", 0, 0)
         m.setOption("cost_variant", 0)
         m.setMask(edges)
         plain(m, pals)
         assert m.maskInfo()[2:] == (5, 9)
+        assert path_under(m, pals, edges, "edges")["tiles_run"] == 5
         m.setMask(None)
         plain(m, pals)
         assert m.maskInfo() == (BW * BH, BW * BH, 9, 9)
+        got = path_under(m, pals, None, "no mask")
+        assert (got["cost_instance"], got["tiles_run"], got["tiles_all"]) == ("plain", 9, 9)
     finally:
         m.close()
 
@@ -482,6 +515,7 @@ def _search(gpu, masks, runs=(30,), opts=None, lloyd=0, amp=None, given=None, pr
             _lib.check(lib.hq_search_create(m.ctx, C.byref(params), AK, sw.seed, C.byref(h)), m.ctx)
         else:
             _lib.check(lib.hq_search_create_from(m.ctx, C.byref(params), AK, sw.seed, _lib.fptr(given), C.byref(h)), m.ctx)
+        pr.check_search(m, h, AP, AK)  # device-resident exactly when sa_device is 1
         try:
             if amp is not None:
                 _lib.check(lib.hq_search_set_ordered(h, _lib.fptr(np.ascontiguousarray(amp, np.float32))), m.ctx)
@@ -497,6 +531,7 @@ def _search(gpu, masks, runs=(30,), opts=None, lloyd=0, amp=None, given=None, pr
                 best, err, it = np.zeros(4 * AK, np.float32), C.c_double(), C.c_int()
                 _lib.check(lib.hq_search_best(h, _lib.fptr(best), C.byref(err), C.byref(it)), m.ctx)
                 tr.append(err.value)
+            pr.check_search(m, h, AP, AK, ran=True)  # ... and captured exactly when sa_graph is 1
             if probe:
                 probe(m, best, err.value)
             return (best, err.value, it.value) + ((tr,) if trace else ())
@@ -622,7 +657,8 @@ def test_refusals_leave_outputs_and_state_untouched(gpu):
             return ([m.getIndices(p) for p in range(AP)] + [m.getPixelErrors(p) for p in range(AP)] +
                     [m.clusterSums(AP, AK)[0]])
 
-        held = state()
+        held, path = state(), m.lastPath()
+        assert path["sequence"] == 1 and path["cost_instance"] == "masked"
         costs, used = np.full(AP, -7.0), np.full((AP, AK), -7, np.int32)
         part = np.full((AP, 1 + AK), -7.0)
         scratch = pals.copy()
@@ -659,6 +695,7 @@ def test_refusals_leave_outputs_and_state_untouched(gpu):
         np.testing.assert_array_equal(u32(p2), u32(pals))
         for a, b in zip(held, state()):
             np.testing.assert_array_equal(a, b)
+        assert m.lastPath() == path  # no refused call enqueued a pass
         m.setMask(None)  # without a mask both answer
         assert lib.hq_cluster_errors(m.ctx, AP, AK, _lib.i64ptr(err), _lib.fptr(worst)) == _lib.HQ_OK
     finally:

@@ -14,6 +14,7 @@ import c_oracle
 import de2000_ref as d
 import hybridquantization_amd as hq
 import oracle as o
+import path_ref as pr
 from dither_ref import cube_corners, ramp_image
 from hybridquantization_amd import _lib
 from ordered_ref import amp3, bayer, ordered
@@ -478,6 +479,7 @@ def _search(gpu, Pn, amp, runs=(30,), before=True, opts=None, probe=None):
         sw = hq.SWASA(population=Pn, imax=100, seed=9, t0=0.05)
         params, h = sw.params(), C.c_void_p()
         _lib.check(lib.hq_search_create(m.ctx, C.byref(params), SK, sw.seed, C.byref(h)), m.ctx)
+        pr.check_search(m, h, Pn, SK)  # device-resident exactly when sa_device is 1
         try:
             if amp is not None and before:
                 a = None if isinstance(amp, str) else _lib.fptr(np.ascontiguousarray(amp, np.float32))
@@ -486,6 +488,7 @@ def _search(gpu, Pn, amp, runs=(30,), before=True, opts=None, probe=None):
                 ran = C.c_int()
                 _lib.check(lib.hq_search_run(h, n, C.byref(ran)), m.ctx)
                 assert ran.value == n
+            pr.check_search(m, h, Pn, SK, ran=True)  # ... and captured exactly when sa_graph is 1
             best, err, it = np.zeros(4 * SK, np.float32), C.c_double(), C.c_int()
             _lib.check(lib.hq_search_best(h, _lib.fptr(best), C.byref(err), C.byref(it)), m.ctx)
             if probe:

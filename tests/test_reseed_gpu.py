@@ -15,6 +15,7 @@ import pytest
 import c_oracle
 import hybridquantization_amd as hq
 import oracle as o
+import path_ref as pr
 from hybridquantization_amd import _lib
 from lloyd_ref import bits
 from reseed_ref import cluster_errors_ref, merge_ref, reseed_ref, tied_maxima
@@ -26,7 +27,7 @@ GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def new_ctx(gpu, de=hq.deltaETypes.CIE76):
-    m = hq.ImageManipulation(de, device=gpu)
+    m = pr.Context(de, device=gpu)
     sp = hq.ScielabProcessor(72, 45.0, hq.Whitepoint.D65, None, m)
     m.illum = sp.illuminant
     return m
@@ -466,6 +467,7 @@ class Search:
         params = sw.params()
         self.h = C.c_void_p()
         _lib.check(self.lib.hq_search_create(m.ctx, C.byref(params), K, sw.seed, C.byref(self.h)), m.ctx)
+        pr.check_search(m, self.h, params.population, K)  # device-resident exactly when sa_device is 1
 
     def set_repair(self, every, max_moves=-1):
         return self.lib.hq_search_set_repair(self.h, every, max_moves)
@@ -505,6 +507,7 @@ def run_search(m, K, P, seed, device, repair=None, lloyd=0, moves=-1, runs=(17, 
         for n in runs:
             assert s.run(n) == n
             out.append(s.best())
+            pr.check_search(m, s.h, P, K, ran=True)  # captured exactly when sa_graph is 1
         return out
     finally:
         s.close()

@@ -5,6 +5,7 @@ named after, from the table and the oracle alone."""
 import numpy as np
 import pytest
 
+import path_ref as pr
 import reuse_walk as rw
 from mask_ref import live_tiles_brute
 from ordered_ref import bayer
@@ -12,13 +13,6 @@ from test_fast_path import bucket
 
 ASSIGN_CHUNK = 256 * 6  # hq_eval.hip, assign_blocks: pixels per assign workgroup (HQ_ASSIGN_MINPX 6)
 FAST_TILE = {16: (128, 16), 8: (108, 8)}  # option cost_rows -> the fast cost launch's tile (columns, rows)
-
-
-def chunk_count(K):  # hq_internal.h
-    n = 1
-    while 256 * n < K:
-        n <<= 1
-    return n
 
 
 @pytest.mark.parametrize("n", [1, 2, 3, 5, 12, 13, 15])
@@ -67,15 +61,20 @@ def test_class_meets_its_path(name):
     # several assign workgroups, more than one cost tile (16 x 128), a halo where there is a shard
     e0, e1 = max(0, r0 - half), min(h, r1 + half)
     assert w * (e1 - e0) > ASSIGN_CHUNK and (r1 - r0 > 16 or w > 128)
-    nch = chunk_count(K) if 256 < K <= 16384 and opts["chunked"] and opts["grid"] > 0 and fits else 1
+    assert fits == pr.palette_fits(pals) and rw.FAST_RANGE == pr.FAST_RANGE
+    nch = pr.chunks_of(opts, K, fits)  # (the predicates below: tests/path_ref.py)
+    path = pr.expected(opts, 0, half, K, P, pal_fits=fits, image_u8=on_lattice,
+                       kind="dither" if c["op"] == "dither" else "full", ordered=c["op"] == "ordered")
     want = {
         "u8-fast": bucket(half) == 10 and nch == 1 and opts["cost_variant"] == 0 and opts["pixel_err"] == 1,
         "planar-generic": opts["cost_variant"] == 1 and K <= 256,
         "bucket-19": bucket(half) == 19 and half == 19 and K < 8,
         "long-filter": bucket(half) == 0 and 24 < half <= 64,
-        "chunk-grids": nch == 2 and opts["lists16"] == 0,
-        "lists16": 4 <= nch <= 32 and opts["lists16"] == 1 and opts["grid"] > 0,
-        "wide-u32": K > 16384 and nch == 1,
+        "chunk-grids": nch == 2 and opts["lists16"] == 0 and not pr.uses_lists16(opts, nch)
+        and (path["grid"], path["argmin"], path["argmin_cmb"]) == ("build_grid", "assign_pipe", 2),
+        "lists16": 4 <= nch <= 32 and opts["lists16"] == 1 and opts["grid"] > 0 and pr.uses_lists16(opts, nch)
+        and (path["grid"], path["argmin"]) == ("lists16", "assign16"),
+        "wide-u32": K > 16384 and nch == 1 and path["argmin"] == "assign_wide" and path["idx_bytes"] == 4,
         "grid-0": opts["grid"] == 0 and K <= 256,
         "shard": c["op"] == "partial" and r0 - half > 0 and r1 + half < h and r0 % 16 != 0,
         "dither": c["op"] == "dither" and K <= 256 and opts["dither_rows"] == 64 and c["strength"] == 1.0,

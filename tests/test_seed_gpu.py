@@ -11,6 +11,7 @@ import pytest
 
 import hybridquantization_amd as hq
 import oracle as o
+import path_ref as pr
 from hybridquantization_amd import _lib
 from lloyd_ref import bits as fbits
 from seed_ref import DEN32, coord_byte, coord_float, histogram_ref, median_cut_ref, q32
@@ -23,7 +24,7 @@ BLOB_SEED_COST = 4.4947951799986186  # the CPU oracle's cost of the blob image's
 
 
 def make_ctx(gpu):
-    m = hq.ImageManipulation(hq.deltaETypes.CIE76, device=gpu)
+    m = pr.Context(hq.deltaETypes.CIE76, device=gpu)
     assert m.getOpenCLAvailable()
     sp = hq.ScielabProcessor(72, 45.0, hq.Whitepoint.D65, None, m)
     m.illum = sp.illuminant
@@ -230,6 +231,7 @@ class Search:
         else:
             rc = self.lib.hq_search_create(m.ctx, C.byref(params), K, sw.seed, C.byref(self.h))
         _lib.check(rc, m.ctx)
+        pr.check_search(m, self.h, params.population, K)  # device-resident exactly when sa_device is 1
 
     def run(self, n):
         ran = C.c_int(-5)
@@ -268,6 +270,7 @@ def run_from(m, K, sw, pop, device, runs, every=0, create_from=True):
         for n in runs:
             assert s.run(n) == n
             out.append(s.best())
+            pr.check_search(m, s.h, sw.params().population, K, ran=True)  # captured exactly when sa_graph is 1
         return out
     finally:
         s.close()

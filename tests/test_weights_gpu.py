@@ -10,12 +10,13 @@ import numpy as np
 import pytest
 
 import hybridquantization_amd as hq
+import path_ref as pr
 from hybridquantization_amd import _lib
 from lloyd_ref import DEN32, q32
 from mask_ref import two_tone_image
 from seed_ref import coord_byte, coord_float, median_cut_ref
 from test_mask_gpu import (AH, AK, AP, AW, BH, BW, DE00, DE76, DE94, DELTA, LONG, SAMP, SHAPES, caller_filters,
-                           designed_half, filter_ctx, indices, new_ctx, noise, pals_of, partial_of, plain, set_image, u32,
+                           designed_half, filter_ctx, indices, new_ctx, noise, pals_of, partial_of, path_under, plain, set_image, u32,
                            u64)
 from weights_ref import (LIMIT, as_int64, live_tile_count, nonzero, weight_maps, weight_sum, weighted_cluster_sums,
                          weighted_histogram, weighted_sum)
@@ -174,6 +175,7 @@ def _search(gpu, maps, runs=(30,), opts=None, lloyd=0, amp=None, given=None, pro
             _lib.check(lib.hq_search_create(m.ctx, C.byref(params), AK, sw.seed, C.byref(h)), m.ctx)
         else:
             _lib.check(lib.hq_search_create_from(m.ctx, C.byref(params), AK, sw.seed, _lib.fptr(given), C.byref(h)), m.ctx)
+        pr.check_search(m, h, AP, AK)  # device-resident exactly when sa_device is 1
         try:
             if amp is not None:
                 _lib.check(lib.hq_search_set_ordered(h, _lib.fptr(np.ascontiguousarray(amp, np.float32))), m.ctx)
@@ -190,6 +192,7 @@ def _search(gpu, maps, runs=(30,), opts=None, lloyd=0, amp=None, given=None, pro
                 best, err, it = np.zeros(4 * AK, np.float32), C.c_double(), C.c_int()
                 _lib.check(lib.hq_search_best(h, _lib.fptr(best), C.byref(err), C.byref(it)), m.ctx)
                 tr.append(err.value)
+            pr.check_search(m, h, AP, AK, ran=True)  # ... and captured exactly when sa_graph is 1
             if probe:
                 probe(m, best, err.value)
             return (best, err.value, it.value) + ((tr,) if trace else ())
@@ -238,11 +241,18 @@ def test_zeros_and_ones_is_the_mask_bit_for_bit(gpu, img_u8):
         b.setWeights(np.ones((AH, AW), np.uint8))
         _assert_everything_equal(fresh, _everything(b, pals), "all ones")
         assert b.weightsInfo() == (AW * AH, AW * AH) and b.maskInfo() == (AW * AH, AW * AH, 4, 4)
-        for x in ("cost_rows", 8), ("cost_variant", 1):  # the other fast kernel; the generic pair
+        b.setWeights(zo)
+        for x in ("cost_rows", 16), ("cost_rows", 8), ("cost_variant", 1):  # both fast kernels; the generic pair
             for c in (a, b):
                 c.setOption(*x)
             b.setWeights(zo)
             np.testing.assert_array_equal(u64(plain(a, pals)[0]), u64(plain(b, pals)[0]), err_msg=str(x))
+            # equal outputs from different kernels: the masked instance there, the weighted one here
+            pa, pb = path_under(a, pals, zo, f"mask {x}"), path_under(b, pals, zo, f"weights {x}", weighted=True)
+            assert (pa["cost_instance"], pb["cost_instance"]) == ("masked", "weighted"), x
+            own = ("cost_instance", "sequence", "previous_pass", "previous_cost")  # (each context's own)
+            assert {k: v for k, v in pa.items() if k not in own} == {k: v for k, v in pb.items() if k not in own}
+            assert pa["cost"] == {("cost_rows", 16): "cost16w", ("cost_rows", 8): "cost_mfma"}.get(x, "tiled_generic")
     finally:
         a.close()
         b.close()
@@ -675,7 +685,8 @@ def test_refusals_leave_outputs_and_state_untouched(gpu):
             return ([m.getIndices(p) for p in range(AP)] + [m.getPixelErrors(p) for p in range(AP)] +
                     [m.clusterSums(AP, AK)[0]])
 
-        held = state()
+        held, path = state(), m.lastPath()
+        assert path["sequence"] == 1 and path["cost_instance"] == "weighted"
         costs, used = np.full(AP, -7.0), np.full((AP, AK), -7, np.int32)
         part = np.full((AP, 1 + AK), -7.0)
         scratch = pals.copy()
@@ -716,6 +727,7 @@ def test_refusals_leave_outputs_and_state_untouched(gpu):
         np.testing.assert_array_equal(u32(p2), u32(pals))
         for a, b in zip(held, state()):
             np.testing.assert_array_equal(a, b)
+        assert m.lastPath() == path  # no refused call enqueued a pass
         m.setWeights(None)  # with nothing set both answer
         assert lib.hq_cluster_errors(m.ctx, AP, AK, _lib.i64ptr(err), _lib.fptr(worst)) == _lib.HQ_OK
     finally:
