@@ -98,6 +98,11 @@ SIGNATURES = {
                                        _i32, _d]),
     "hq_cluster_errors": (C.c_int, [_ctx, C.c_int, C.c_int, _i64, _f]),
     "hq_reseed_unused": (C.c_int, [_i64, _f, C.c_int, C.c_int, C.c_int, _f, C.POINTER(C.c_int)]),
+    "hq_reseed_unused_fixed": (C.c_int, [_i64, _f, C.c_int, C.c_int, C.c_int, C.c_int, _f, C.POINTER(C.c_int)]),
+    "hq_set_fixed_colors": (C.c_int, [_ctx, _f, C.c_int]),
+    "hq_fixed_colors": (C.c_int, [_ctx, C.POINTER(C.c_int), _f]),
+    "hq_swasa_search_host_fixed": (C.c_int, [C.POINTER(hq_swasa_params), C.c_int, C.c_uint64, C.c_int, EVAL_FN,
+                                             REFINE_FN, C.c_int, _f, _f, C.c_int, C.c_void_p, _f, _d, _d]),
     "hq_repair_population": (C.c_int, [_ctx, _f, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int,
                                        _d, _i32, _d]),
     "hq_dither_population": (C.c_int, [_ctx, _f, C.c_int, C.c_int, C.c_float, C.c_float, _d, _i32]),

@@ -840,6 +840,8 @@ int check_improve_args(hq_ctx* c, const float* palettes, int P, int K, int steps
     if (!costs) return fail(c, HQ_ERR_ARG, "null output");
     if (int rc = check_eval_args(c, palettes, P, K)) return rc;
     if (steps < 0) return fail(c, HQ_ERR_ARG, "steps=%d < 0", steps);
+    if (c->fixed_n > K)
+        return fail(c, HQ_ERR_ARG, "%d fixed colours (hq_set_fixed_colors) in palettes of K=%d", c->fixed_n, K);
     // (option "palette_split" without a communicator slices nothing: these two go on)
     return whole_image_only(c, what, hint, false);
 }
@@ -968,20 +970,27 @@ int cluster_errors(hq_ctx* c, int P, int K, int64_t* err, float* worst, bool ign
 // The k-means move on the last evaluation's index images: its exact sums, then the centroids
 // into the palettes in place.  The repair move: its error statistics (ignore_bad: pixels
 // with no usable dE left out), then the rule; moved (may be null): colours moved per palette.
-int kmeans_move(hq_ctx* c, int P, int K, float* pal) {
+// Fixed colours: the first nfixed colours of every palette come out of either move with the
+// bits they went in with (the k-means move: their 16 bytes put back; the repair move: the rule).
+int kmeans_move(hq_ctx* c, int P, int K, int nfixed, float* pal) {
     std::vector<int64_t> sums((size_t)P * K * 4);
     int64_t den = 0;
     int r = cluster_sums(c, P, K, sums.data(), &den);
-    if (!r && (r = hq_centroids_from_sums(sums.data(), den, P, K, pal)))
-        return fail(c, r, "hq_centroids_from_sums failed");
+    if (r) return r;
+    std::vector<float> kept((size_t)P * 4 * nfixed);
+    for (int p = 0; p < P && nfixed > 0; ++p)
+        std::memcpy(&kept[(size_t)p * 4 * nfixed], pal + (size_t)p * 4 * K, sizeof(float) * 4 * nfixed);
+    if ((r = hq_centroids_from_sums(sums.data(), den, P, K, pal))) return fail(c, r, "hq_centroids_from_sums failed");
+    for (int p = 0; p < P && nfixed > 0; ++p)
+        std::memcpy(pal + (size_t)p * 4 * K, &kept[(size_t)p * 4 * nfixed], sizeof(float) * 4 * nfixed);
     return r;
 }
-int repair_move(hq_ctx* c, int P, int K, int max_moves, bool ignore_bad, float* pal, int* moved) {
+int repair_move(hq_ctx* c, int P, int K, int max_moves, int nfixed, bool ignore_bad, float* pal, int* moved) {
     std::vector<int64_t> err((size_t)P * K * 4);
     std::vector<float> worst(err.size());
     int r = cluster_errors(c, P, K, err.data(), worst.data(), ignore_bad);
-    if (!r && (r = hq_reseed_unused(err.data(), worst.data(), P, K, max_moves, pal, moved)))
-        return fail(c, r, "hq_reseed_unused failed");
+    if (!r && (r = hq_reseed_unused_fixed(err.data(), worst.data(), P, K, max_moves, nfixed, pal, moved)))
+        return fail(c, r, "hq_reseed_unused_fixed failed");
     return r;
 }
 
@@ -1237,7 +1246,7 @@ int hq_refine_population(hq_ctx* c, float* palettes, int P, int K, int steps, fl
     if (rc) return rc;
     if (steps > 0 && (rc = weighted_sums_scope(c, "hq_refine_population"))) return rc;
     return improve_population(c, palettes, P, K, steps, delta, keep_best, costs, used, trace,
-                              [&](float* cur, bool*) { return kmeans_move(c, P, K, cur); });
+                              [&](float* cur, bool*) { return kmeans_move(c, P, K, c->fixed_n, cur); });
 }
 
 int hq_repair_population(hq_ctx* c, float* palettes, int P, int K, int steps, float delta, int max_moves,
@@ -1251,7 +1260,7 @@ int hq_repair_population(hq_ctx* c, float* palettes, int P, int K, int steps, fl
     std::vector<int> moved(P);
     return improve_population(c, palettes, P, K, steps, delta, keep_best, costs, used, trace,
                               [&](float* cur, bool* changed) {
-        const int r = repair_move(c, P, K, max_moves, false, cur, moved.data());
+        const int r = repair_move(c, P, K, max_moves, c->fixed_n, false, cur, moved.data());
         // nothing left to repair: the remaining steps repeat this one
         *changed = !std::all_of(moved.begin(), moved.end(), [](int m) { return m == 0; });
         return r;

@@ -214,14 +214,14 @@ static inline float clampf_java(float v, float lo, float hi) {  // SW:103-106
     return v > lo ? (v > hi ? hi : v) : lo;
 }
 
-void Swasa::generate_neighboring_colors(const float* colors, float* next, int K, int iteration) {
+void Swasa::generate_neighboring_colors(const float* colors, float* next, int K, int iteration, int nfixed) {
     const float amax = max_step_width(iteration) / 256.0f;
     for (int i = 0; i < K; ++i) {
         const int o = 4 * i;
         for (int c = 0; c < 3; ++c) {
-            const float u = rng_.next_float();
+            const float u = rng_.next_float();  // (a fixed colour's draw is made and discarded)
             const float step = (u * 2 - 1) * amax;
-            next[o + c] = clampf_java(colors[o + c] + step, 0, 1);
+            next[o + c] = i < nfixed ? colors[o + c] : clampf_java(colors[o + c] + step, 0, 1);
         }
         next[o + 3] = 0.0f;
     }
@@ -246,6 +246,8 @@ int SearchDriver::start(const float* population) {
     for (int i = 0; i < P_; ++i) sw_.generate_random_colors(K_, &colors_[(size_t)i * n]);  // IM:413-417
     if (population)  // a given start: the draws above are made all the same
         for (size_t e = 0; e < colors_.size(); ++e) colors_[e] = e % 4 == 3 ? 0.0f : population[e];
+    for (int i = 0; i < P_ && !fixed_.empty(); ++i)  // fixed colours: the first nfixed of every member
+        std::copy(fixed_.begin(), fixed_.end(), &colors_[(size_t)i * n]);
     current_errors_.assign(P_, 0.0);
     errors_.assign(P_, 0.0);
     int rc = eval_(colors_.data(), P_, K_, current_errors_.data());  // IM:490
@@ -278,14 +280,21 @@ int SearchDriver::run(int iterations, int* ran, std::vector<double>* trace) {
         const int ite = ++ite_;                                       // IM:497
         sw_.reduce_temperature_if_necessary(ite);                     // IM:507
         for (int j = 0; j < P_; ++j)                                  // IM:508-511
-            sw_.generate_neighboring_colors(&colors_[(size_t)j * n], &current_[(size_t)j * n], K_, ite);
+            sw_.generate_neighboring_colors(&colors_[(size_t)j * n], &current_[(size_t)j * n], K_, ite, nfixed_);
+        // fixed colours: whatever a move did to them, the candidates carry the members' again
+        auto put_fixed_back = [&] {
+            for (int j = 0; j < P_ && nfixed_ > 0; ++j)
+                std::copy_n(&colors_[(size_t)j * n], 4 * nfixed_, &current_[(size_t)j * n]);
+        };
         if (every_ > 0 && refine_ && ite % every_ == 0) {             // hybrid iteration: one k-means move
             const int rr = refine_(current_.data(), P_, K_);
             if (rr) { if (ran) *ran = done; return rr; }
+            put_fixed_back();
         }
         if (repair_every_ > 0 && repair_ && ite % repair_every_ == 0) {  // repair iteration: unused colours reseeded
             const int rr = repair_(current_.data(), P_, K_);
             if (rr) { if (ran) *ran = done; return rr; }
+            put_fixed_back();
         }
         int rc = eval_(current_.data(), P_, K_, errors_.data());      // IM:515
         if (rc) { if (ran) *ran = done; return rc; }
@@ -327,14 +336,15 @@ bool hq::population_in_range(const float* population, int P, int K) {
     return true;
 }
 
-extern "C" int hq_swasa_search_host_from(const hq_swasa_params* params, int K, uint64_t seed,
-                                         int iterations, hq_eval_fn eval, hq_refine_fn refine, int every,
-                                         const float* population, void* user, float* best_colors,
-                                         double* best_error, double* trace) {
+extern "C" int hq_swasa_search_host_fixed(const hq_swasa_params* params, int K, uint64_t seed,
+                                          int iterations, hq_eval_fn eval, hq_refine_fn refine, int every,
+                                          const float* population, const float* fixed_colors, int nfixed,
+                                          void* user, float* best_colors, double* best_error, double* trace) {
     if (!params || !eval || K < 1 || params->population < 1 || params->imax < 1 ||
-        params->iTc < 1 || every < 0)
+        params->iTc < 1 || every < 0 || nfixed < 0 || nfixed > K)
         return HQ_ERR_ARG;
     if (population && !hq::population_in_range(population, params->population, K)) return HQ_ERR_ARG;
+    if (fixed_colors && nfixed > 0 && !hq::population_in_range(fixed_colors, 1, nfixed)) return HQ_ERR_ARG;
     hq::SearchDriver d(*params, K, seed, [&](const float* pal, int P, int KK, double* costs) {
         return eval(user, pal, P, KK, costs) ? HQ_ERR_ARG : HQ_OK;
     });
@@ -342,6 +352,7 @@ extern "C" int hq_swasa_search_host_from(const hq_swasa_params* params, int K, u
         d.set_refine([&](float* pal, int P, int KK) { return refine(user, pal, P, KK); });
         d.set_every(every);
     }
+    d.set_fixed(nfixed, nfixed > 0 ? fixed_colors : nullptr);
     int rc = d.start(population);
     if (rc) return rc;
     std::vector<double> tr;
@@ -352,6 +363,14 @@ extern "C" int hq_swasa_search_host_from(const hq_swasa_params* params, int K, u
     if (best_error) *best_error = d.best_error();
     if (trace) std::copy(tr.begin(), tr.end(), trace);
     return HQ_OK;
+}
+
+extern "C" int hq_swasa_search_host_from(const hq_swasa_params* params, int K, uint64_t seed,
+                                         int iterations, hq_eval_fn eval, hq_refine_fn refine, int every,
+                                         const float* population, void* user, float* best_colors,
+                                         double* best_error, double* trace) {
+    return hq_swasa_search_host_fixed(params, K, seed, iterations, eval, refine, every, population, nullptr, 0,
+                                      user, best_colors, best_error, trace);
 }
 
 extern "C" int hq_swasa_search_host_lloyd(const hq_swasa_params* params, int K, uint64_t seed,

@@ -125,6 +125,8 @@ struct SaArgs {
     int random;             // generate SW:40-52 random colours instead of neighbours
     int convergence;
     int nch;                // chunked palettes: chunks per palette (P nch workgroups), else 1
+    int nfixed;             // fixed colours (hq_set_fixed_colors): candidate colour k < nfixed is the
+                            // member's colour k, its draws discarded (0: none; 0 in a random step)
 };
 
 struct GridArgs {
@@ -378,6 +380,7 @@ struct LloydArgs {
     PaletteArgs prep;          // outputs of the palette prep of the updated candidates
     int K;
     int bytes;                 // sums in units of 1/255 (the packed image), else 2^-32
+    int nfixed;                // fixed colours: colour k < nfixed keeps its bits whatever its count
 };
 
 // reseed_kernel (hq_search.hip): the repair move of a device-resident repair
@@ -392,6 +395,7 @@ struct ReseedArgs {
     PaletteArgs prep;          // outputs of the palette prep of the repaired candidates
     int K;
     int max_moves;             // colours moved per palette at most (< 0: no limit)
+    int nfixed;                // fixed colours (hq_reseed_unused_fixed): colour k < nfixed is no receiver
 };
 
 // Generic two-pass path (any half-width), one palette per launch.

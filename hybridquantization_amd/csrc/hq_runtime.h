@@ -276,6 +276,11 @@ struct hq_ctx {
     int dmap_w = 0, dmap_h = 0;
     hq::DevBuf d_dmap;
     bool dmap_dirty = true;
+    // fixed palette colours (hq_set_fixed_colors; a property of the context like the map, kept by
+    // hq_set_image*): [fixed_n][4], .w = 0.  A search latches them at creation; the polishes read
+    // fixed_n when called
+    std::vector<float> fixed;
+    int fixed_n = 0;
     // pixel mask (hq_set_mask; a property of the context like the map, dropped by hq_set_image*):
     // the owned rows on the host (0 / 1, W bytes per row: what the live-tile list is built from),
     // on the device at the LabRef planes' pitch (the cost kernels) and over the extended rows'
@@ -366,6 +371,8 @@ struct hq_search {
     int nch = 1;                         // chunked palettes (256 < K <= 16384): chunks per palette
     bool ordered = false;                // hq_search_set_ordered: every evaluation is the ordered one
     float amp[3] = {0.f, 0.f, 0.f};      // ... at this amplitude per channel
+    int nfixed = 0;                      // the context's fixed colours at hq_search_create: colours
+    std::vector<float> fixed;            // 0 .. nfixed-1 of every member, [nfixed][4], for the search's life
     bool fold = false;                   // accept steps reduce the partials (no finalize launch)
     ncclComm_t comm = nullptr;           // the context's communicator at hq_search_create
     float t_acc = 0.f;                   // temperature / threshold of the iteration
@@ -471,8 +478,10 @@ int enqueue_core(hq_ctx* c, int P, int K, ProfRec& pr, Pass pass = {});
 void pack_chunks(const float* pal, int P, int K, int nch, float* out);
 ClusterArgs cluster_args(hq_ctx* c, int P, int K, int nch, int* idx_bytes);
 ClusterErrArgs cluster_err_args(hq_ctx* c, int P, int K, int nch, int* idx_bytes);
-int kmeans_move(hq_ctx* c, int P, int K, float* pal);  // the last evaluation's sums -> centroids, in place
-int repair_move(hq_ctx* c, int P, int K, int max_moves, bool ignore_bad, float* pal, int* moved);
+// the last evaluation's sums -> centroids, in place; the first nfixed colours of every palette keep their bits
+int kmeans_move(hq_ctx* c, int P, int K, int nfixed, float* pal);
+// (the rule: hq_reseed_unused_fixed)
+int repair_move(hq_ctx* c, int P, int K, int max_moves, int nfixed, bool ignore_bad, float* pal, int* moved);
 // planar_ok established (once per image), else HQ_ERR_UNSUPPORTED "<subject> with a pixel outside
 // [0, 1] or not finite: <what>"
 int require_unit_range_image(hq_ctx* c, const char* subject, const char* what);

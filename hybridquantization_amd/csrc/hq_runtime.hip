@@ -501,6 +501,27 @@ int hq_mask_info(hq_ctx* c, int64_t* n_full, int64_t* n_owned, int64_t* tiles_ru
     return HQ_OK;
 }
 
+// The context's fixed palette colours: host state alone (a search latches it at creation, the
+// polishes read its count when called), so nothing on the device and no record changes.
+int hq_set_fixed_colors(hq_ctx* c, const float* colors, int n) {
+    if (!c) return HQ_ERR_ARG;
+    if (n < 0 || n > kMaxKChunked) return fail(c, HQ_ERR_ARG, "n=%d fixed colours: 0 .. %d", n, kMaxKChunked);
+    if (!colors) n = 0;
+    if (n > 0 && !population_in_range(colors, 1, n))
+        return fail(c, HQ_ERR_ARG, "fixed colour with a channel that is not finite or outside [0, 1]");
+    c->fixed.assign(colors, colors + (size_t)4 * n);
+    for (size_t e = 3; e < c->fixed.size(); e += 4) c->fixed[e] = 0.0f;
+    c->fixed_n = n;
+    return HQ_OK;
+}
+
+int hq_fixed_colors(hq_ctx* c, int* n, float* colors) {
+    if (!c) return HQ_ERR_ARG;
+    if (n) *n = c->fixed_n;
+    if (colors) std::copy(c->fixed.begin(), c->fixed.end(), colors);
+    return HQ_OK;
+}
+
 int hq_last_path(hq_ctx* c, hq_path_info* info) {
     if (!c || !info || info->size < (int32_t)sizeof(int32_t)) return HQ_ERR_ARG;
     hq_path_info pi = c->path;

@@ -402,6 +402,9 @@ __device__ __forceinline__ void sa_keep(const SaArgs& a, int p, int e0, bool lea
 // Chunked palettes: chunk ch = colours 256 ch .. (draws t0 = 768 ch ..), and
 // the chunk's colours past K are copies of candidate colour 0 (pack_chunks'
 // padding), drawn again here from its source colour `src0`.
+// Fixed colours (a.nfixed > 0): the draws of colour k < nfixed -- its global
+// index, 256 ch + i -- are discarded and the candidate's colour is the member's,
+// its bits; candidate colour 0 is then `src0` itself, and so is the padding.
 __device__ __forceinline__ float sa_draw(const SaArgs& a, uint64_t st, float from) {
 #pragma clang fp contract(off)
     const float u = (float)(int32_t)(st >> 24) / (float)(1 << 24);
@@ -423,7 +426,9 @@ __device__ __forceinline__ void sa_generate(const SaArgs& a, int p, int ch, cons
     for (int j = 0; j < NPF; ++j) {
         const int tt = tid + nt * j, i = tt / 3, c = tt - 3 * i;
         if (tt < 3 * kn) {
-            const float v = sa_draw(a, lcg_jump(base, pf.jA[j], pf.jC[j]), s_from[4 * i + c]);
+            const float from = s_from[4 * i + c];
+            const float d = sa_draw(a, lcg_jump(base, pf.jA[j], pf.jC[j]), from);
+            const float v = k0 + i < a.nfixed ? from : d;
             reinterpret_cast<float*>(s_cand)[4 * i + c] = v;
             if (lead) a.cand_out[(int64_t)p * n4 + 4 * (k0 + i) + c] = v;
         }
@@ -434,7 +439,10 @@ __device__ __forceinline__ void sa_generate(const SaArgs& a, int p, int ch, cons
     }
     if (a.nch > 1 && kn < kMaxK) {  // padding: candidate colour 0 (draws 0, 1, 2)
         __shared__ float s_c0[3];
-        if (tid < 3) s_c0[tid] = sa_draw(a, lcg_jump(base, a.jump_A[tid + 1], a.jump_C[tid + 1]), src0[tid]);
+        if (tid < 3) {
+            const float d = sa_draw(a, lcg_jump(base, a.jump_A[tid + 1], a.jump_C[tid + 1]), src0[tid]);
+            s_c0[tid] = a.nfixed > 0 ? src0[tid] : d;
+        }
         __syncthreads();
         for (int k = kn + tid; k < kMaxK; k += nt) s_cand[k] = make_float4(s_c0[0], s_c0[1], s_c0[2], 0.f);
     }
@@ -502,7 +510,9 @@ __global__ __launch_bounds__(1024) void sa_step_kernel(SaArgs a) {
 // of sums (two 16-B loads): with a count > 0 the colour becomes the mean of its
 // pixels -- lloyd_mean, the host rule's own arithmetic in fp64, so the bits are
 // hq_centroids_from_sums' -- and goes back into the candidate buffer in place
-// (what the next sa_step reads as cand_in); with count 0 it keeps its bits.
+// (what the next sa_step reads as cand_in); with count 0 it keeps its bits, and
+// so does a fixed colour, k < nfixed, whatever its count (its sums are read and
+// zeroed like the others').
 // The sums are zeroed once read, for the next hybrid iteration, and the palette
 // is prepared again so pal, opp, opp16, dup and pflags are the updated one's.
 // ----------------------------------------------------------------------------
@@ -516,7 +526,7 @@ __global__ __launch_bounds__(1024) void lloyd_update_kernel(LloydArgs a) {
         ulonglong2* const sp = reinterpret_cast<ulonglong2*>(a.sums + ((int64_t)p * a.K + k) * 4);
         const ulonglong2 rg = sp[0], bn = sp[1];
         c = *cp;
-        if (bn.y > 0ull) {
+        if (bn.y > 0ull && k >= a.nfixed) {
             const bool bytes = a.bytes != 0;
             c = make_float4(lloyd_mean((int64_t)rg.x, (int64_t)bn.y, bytes), lloyd_mean((int64_t)rg.y, (int64_t)bn.y, bytes),
                             lloyd_mean((int64_t)bn.x, (int64_t)bn.y, bytes), 0.f);
@@ -954,7 +964,8 @@ __global__ __launch_bounds__(1024) void finalize_kernel(FinalizeArgs a) {
 // hq_reseed_unused's rule, in the same integers, so the bits are the host's.
 // Thread k < K holds candidate colour k of palette p and its 32 B of statistics
 // (sum, count, key of the worst movable pixel, 0).  A colour with count 0 is a
-// receiver, its rank the number of receivers below it; a colour with count > 0
+// receiver -- unless it is fixed, k < nfixed (hq_reseed_unused_fixed): such a
+// colour is neither, so it takes no rank and no donor -- its rank the number of receivers below it; a colour with count > 0
 // and a key is a donor, its rank the number of donors that precede it under (sum
 // descending, index ascending) -- K comparisons per thread out of LDS, a strict
 // order, so the ranks are a permutation.  The receiver of rank r takes the worst
@@ -979,7 +990,7 @@ __global__ __launch_bounds__(1024) void reseed_kernel(ReseedArgs a) {
         const ulonglong2 sn = sp[0], kz = sp[1];
         c = *cp;
         sum = sn.x;
-        role = sn.y == 0ull ? 1 : (kz.x != 0ull ? 2 : 0);
+        role = sn.y == 0ull ? (k >= a.nfixed ? 1 : 0) : (kz.x != 0ull ? 2 : 0);
         s_sum[k] = sum;
         s_role[k] = (uint8_t)role;
         sp[0] = sp[1] = make_ulonglong2(0ull, 0ull);

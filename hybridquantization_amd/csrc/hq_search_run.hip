@@ -42,6 +42,7 @@ SaArgs sa_args(hq_search* s, bool accept, bool init, bool generate, bool random,
     a.generate = generate;
     a.random = random;
     a.convergence = s->prm.convergence;
+    a.nfixed = random ? 0 : s->nfixed;  // (the random population's draws are all kept: create overwrites after them)
     a.acc = acc_base(c, c->acc_par, a.P);
     a.used_glob = used_base(c, c->acc_par, a.P * s->nch);
     a.used_stride = used_stride(a.P * s->nch);
@@ -119,7 +120,7 @@ int enqueue_lloyd(hq_search* s, ProfRec& pr) {
     int idx_bytes = 1;
     const ClusterArgs ca = cluster_args(c, s->P, s->K, s->nch, &idx_bytes);
     HIP_TRY(c, timed_launch(pr, kPSums, [&] { return launch_cluster_sums(ca, idx_bytes, c->num_cu, c->stream); }));
-    const LloydArgs la{ca.sums, s->cand[s->cd].as<float>(), prep_args(c, s->K), s->K, sums_u8(c) ? 1 : 0};
+    const LloydArgs la{ca.sums, s->cand[s->cd].as<float>(), prep_args(c, s->K), s->K, sums_u8(c) ? 1 : 0, s->nfixed};
     HIP_TRY(c, timed_launch(pr, kPLloydUpdate, [&] { return launch_lloyd_update(la, s->P, c->stream); }));
     return HQ_OK;
 }
@@ -143,7 +144,8 @@ int enqueue_repair(hq_search* s, ProfRec& pr) {
     int idx_bytes = 1;
     const ClusterErrArgs ea = cluster_err_args(c, s->P, s->K, s->nch, &idx_bytes);
     HIP_TRY(c, timed_launch(pr, kPErrsum, [&] { return launch_cluster_errors(ea, idx_bytes, c->num_cu, c->stream); }));
-    const ReseedArgs ra{ea.stats, ea.worst, s->cand[s->cd].as<float>(), prep_args(c, s->K), s->K, s->repair_moves};
+    const ReseedArgs ra{ea.stats, ea.worst, s->cand[s->cd].as<float>(), prep_args(c, s->K), s->K, s->repair_moves,
+                        s->nfixed};
     HIP_TRY(c, timed_launch(pr, kPReseed, [&] { return launch_reseed(ra, s->P, c->stream); }));
     return HQ_OK;
 }
@@ -257,10 +259,20 @@ int device_search_create(hq_ctx* c, const hq_swasa_params* params, int K, uint64
     // is past the 3 K P draws as always): into the candidate buffer the accept step reads,
     // and through the palette prep as an evaluation uploads it (upload_and_prep), so the prep's
     // outputs and the duplicate flags are the given colours'.
+    // Fixed colours: colours 0 .. nfixed-1 of every member of that population, given or drawn, are
+    // overwritten.  The draws are java.util.Random's on either side (SW:40-52), so without a given
+    // population the host makes them once more and goes the given population's way.
     std::vector<float> given;  // (.w = 0; read by the copy below until the synchronise)
-    if (population) {
-        given.assign(population, population + n4);
+    if (population || s->nfixed > 0) {
+        if (population) {
+            given.assign(population, population + n4);
+        } else {
+            given.resize(n4);
+            Swasa draws(*params, seed);
+            for (int i = 0; i < P; ++i) draws.generate_random_colors(K, &given[(size_t)i * 4 * K]);
+        }
         for (size_t e = 3; e < n4; e += 4) given[e] = 0.0f;
+        for (int i = 0; i < P; ++i) std::copy(s->fixed.begin(), s->fixed.end(), &given[(size_t)i * 4 * K]);
         HIP_TRY(c, hipMemcpyAsync(s->cand[s->cd].p, given.data(), sizeof(float) * n4, hipMemcpyHostToDevice,
                                   c->stream));
         if ((rc = upload_and_prep(c, given.data(), nullptr, P, K))) return rc;
@@ -405,6 +417,8 @@ int hq_search_create_from(hq_ctx* c, const hq_swasa_params* params, int K, uint6
         return fail(c, HQ_ERR_ARG, "bad SWASA parameters");
     if (population && !population_in_range(population, params->population, K))
         return fail(c, HQ_ERR_ARG, "initial population with a channel that is not finite or outside [0, 1]");
+    if (c->fixed_n > K)
+        return fail(c, HQ_ERR_ARG, "%d fixed colours (hq_set_fixed_colors) in palettes of K=%d", c->fixed_n, K);
     if (int rc = mask_scope(c)) return rc;
     // device-resident: K <= 256, or chunked palettes (256 < K <= 16384); at most
     // kSaMaxP palettes (sa_step's per-palette tables) and kSaMaxSub sub-palettes
@@ -413,6 +427,8 @@ int hq_search_create_from(hq_ctx* c, const hq_swasa_params* params, int K, uint6
     const bool device = c->sa_device && params->population <= kSaMaxP && params->population * nch <= kSaMaxSub &&
                         (K <= kMaxK || nch > 1);
     hq_search* s = new hq_search{c, nullptr, K};
+    s->nfixed = c->fixed_n;  // latched: a later hq_set_fixed_colors does not reach this search
+    s->fixed = c->fixed;
     int rc;
     if (device) {
         if (!c->have_image) rc = fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
@@ -433,10 +449,10 @@ int hq_search_create_from(hq_ctx* c, const hq_swasa_params* params, int K, uint6
         s->driver = new SearchDriver(*params, K, seed, eval);
         // the k-means move, host-driven, is the public triple: an evaluation of the
         // candidates for their argmin (its cost pass is wasted), the sums, the update
-        s->driver->set_refine([c, delta](float* pal, int P, int KK) {
+        s->driver->set_refine([c, delta, s](float* pal, int P, int KK) {
             std::vector<double> costs(P);
             const int rr = hq_eval_population(c, pal, P, KK, delta, costs.data(), nullptr);
-            return rr ? rr : kmeans_move(c, P, KK, pal);
+            return rr ? rr : kmeans_move(c, P, KK, s->nfixed, pal);
         });
         // the repair move, host-driven: an evaluation of the candidates that stores their
         // error image, the error statistics (pixels with no usable dE left out) and the rule
@@ -444,10 +460,11 @@ int hq_search_create_from(hq_ctx* c, const hq_swasa_params* params, int K, uint6
             const PixelErrScope scope(c);
             std::vector<double> costs(P);
             const int rr = hq_eval_population(c, pal, P, KK, delta, costs.data(), nullptr);
-            return rr ? rr : repair_move(c, P, KK, s->repair_moves, true, pal, nullptr);
+            return rr ? rr : repair_move(c, P, KK, s->repair_moves, s->nfixed, true, pal, nullptr);
         });
         s->prm = *params;
         s->P = params->population;
+        s->driver->set_fixed(s->nfixed, s->nfixed > 0 ? s->fixed.data() : nullptr);
         rc = s->driver->start(population);
     }
     search_commit(s, rc, 1);

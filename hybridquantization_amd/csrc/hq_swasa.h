@@ -47,7 +47,9 @@ class Swasa {
     float max_step_width(int i) const;                      // SW:69-72
     double compute_penalty(const int32_t* used, int K) const;  // SW:74-82
     void reduce_temperature_if_necessary(int iteration);    // SW:84-89
-    void generate_neighboring_colors(const float* colors, float* next, int K, int iteration);  // SW:91-101
+    // SW:91-101.  nfixed (libhq's addition): the draws of colour k < nfixed are made and
+    // discarded, and next's colour k is colors' colour k, its bits.
+    void generate_neighboring_colors(const float* colors, float* next, int K, int iteration, int nfixed = 0);
     const hq_swasa_params& params() const { return p_; }
     float temperature() const { return temperature_; }
 
@@ -87,6 +89,18 @@ class SearchDriver {
     // `repair` runs after `refine` when an iteration is both.
     void set_repair(PopulationRefine repair) { repair_ = std::move(repair); }
     void set_repair_every(int every) { repair_every_ = every; }
+    // Fixed colours (libhq's addition, hq_set_fixed_colors' semantics), set before start():
+    // the first n colours of every member are `colors` ([n][4], .w stored as 0; null: as the
+    // population or the draws have them) and no iteration changes them -- their draws are
+    // made and discarded, and they are put back after `refine` and `repair` return.
+    void set_fixed(int n, const float* colors) {
+        nfixed_ = n;
+        fixed_.clear();
+        if (colors) {
+            fixed_.assign(colors, colors + (size_t)4 * n);
+            for (size_t e = 3; e < fixed_.size(); e += 4) fixed_[e] = 0.0f;
+        }
+    }
     const std::vector<float>& best_colors() const { return best_colors_; }
     double best_error() const { return best_error_; }
     int iteration() const { return ite_; }
@@ -99,6 +113,8 @@ class SearchDriver {
     int every_ = 0;
     PopulationRefine repair_;
     int repair_every_ = 0;
+    int nfixed_ = 0;
+    std::vector<float> fixed_;              // [nfixed][4], or empty
     std::vector<float> colors_, current_;   // [P][4K]
     std::vector<double> current_errors_, errors_;
     std::vector<float> best_colors_;

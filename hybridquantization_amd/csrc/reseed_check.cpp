@@ -1,4 +1,4 @@
-// reseed_check.cpp -- hq_reseed_unused's edge cases as a stand-alone host
+// reseed_check.cpp -- hq_reseed_unused's and hq_reseed_unused_fixed's edge cases as a stand-alone host
 // program, built and run under the address and undefined-behaviour sanitizers
 // by `make reseed_check` (hq_reseed.cpp and this file: no GPU code, no Python).
 #include <cstdint>
@@ -38,6 +38,11 @@ struct Stats {
     int run(int max_moves, std::vector<int>* moved) {
         if (moved) moved->assign((size_t)P, -7);
         return hq_reseed_unused(err.data(), worst.data(), P, K, max_moves, pal.data(), moved ? moved->data() : nullptr);
+    }
+    int run_fixed(int max_moves, int nfixed, std::vector<int>* moved) {
+        if (moved) moved->assign((size_t)P, -7);
+        return hq_reseed_unused_fixed(err.data(), worst.data(), P, K, max_moves, nfixed, pal.data(),
+                                      moved ? moved->data() : nullptr);
     }
     bool is_donor(int p, int k, int donor) const {  // colour k now holds donor's worst pixel
         const float* c = &pal[4 * ((size_t)p * K + k)];
@@ -106,6 +111,43 @@ int main() {
         CHECK(hq_reseed_unused(s.err.data(), s.worst.data(), 1, 0, -1, s.pal.data(), nullptr) == HQ_ERR_ARG);
         CHECK(hq_reseed_unused(nullptr, s.worst.data(), 1, 3, -1, s.pal.data(), nullptr) == HQ_ERR_ARG);
         CHECK(s.untouched(0, 1));
+    }
+    // ---- hq_reseed_unused_fixed: the first nfixed colours are never receivers ----
+    {  // unused fixed colours stay, take no place in the receivers' order and consume no donor
+        Stats s(1, 6);
+        s.set(0, 2, 50, 1, 9), s.set(0, 4, 30, 2, 0);  // colours 0, 1 (fixed) and 3, 5 are unused
+        CHECK(s.run_fixed(-1, 2, &moved) == HQ_OK && moved[0] == 2);
+        CHECK(s.untouched(0, 0) && s.untouched(0, 1) && s.is_donor(0, 3, 2) && s.is_donor(0, 5, 4));
+    }
+    {  // a fixed colour gives like any other; max_moves counts free receivers only
+        Stats s(1, 5);
+        s.set(0, 0, 90, 4, 3), s.set(0, 3, 10, 1, 1);  // colour 0 (fixed) has the most error
+        CHECK(s.run_fixed(1, 2, &moved) == HQ_OK && moved[0] == 1);
+        CHECK(s.untouched(0, 0) && s.untouched(0, 1) && s.is_donor(0, 2, 0) && s.untouched(0, 4));
+    }
+    {  // more free receivers than donors, and the reverse; equal sums: the lower index first
+        Stats s(2, 6);
+        s.set(0, 1, 40, 1, 1);                                                  // palette 0: one donor
+        s.set(1, 0, 40, 1, 1), s.set(1, 1, 40, 1, 2), s.set(1, 2, 40, 1, 3), s.set(1, 4, 40, 1, 5);  // palette 1: four
+        CHECK(s.run_fixed(-1, 1, &moved) == HQ_OK && moved[0] == 1 && moved[1] == 2);
+        CHECK(s.untouched(0, 0) && s.is_donor(0, 2, 1) && s.untouched(0, 3) && s.untouched(0, 4) && s.untouched(0, 5));
+        CHECK(s.is_donor(1, 3, 0) && s.is_donor(1, 5, 1));
+    }
+    {  // nfixed = K: nothing moves; nfixed = 0: hq_reseed_unused itself
+        Stats s(1, 4), a(1, 4), b(1, 4);
+        s.set(0, 2, 8, 1, 1), a.set(0, 2, 8, 1, 1), b.set(0, 2, 8, 1, 1);
+        CHECK(s.run_fixed(-1, 4, &moved) == HQ_OK && moved[0] == 0);
+        for (int k = 0; k < 4; ++k) CHECK(s.untouched(0, k));
+        std::vector<int> ma, mb;
+        CHECK(a.run(-1, &ma) == HQ_OK && b.run_fixed(-1, 0, &mb) == HQ_OK && ma == mb);
+        CHECK(std::memcmp(a.pal.data(), b.pal.data(), sizeof(float) * a.pal.size()) == 0);
+    }
+    {  // nfixed < 0 and nfixed > K: refused, everything left alone
+        Stats s(1, 3);
+        s.set(0, 0, 5, 1, 0);
+        CHECK(s.run_fixed(-1, -1, &moved) == HQ_ERR_ARG && moved[0] == -7);
+        CHECK(s.run_fixed(-1, 4, &moved) == HQ_ERR_ARG && moved[0] == -7);
+        for (int k = 0; k < 3; ++k) CHECK(s.untouched(0, k));
     }
     if (failures) {
         std::fprintf(stderr, "reseed_check: %d failure(s)\n", failures);

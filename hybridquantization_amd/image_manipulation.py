@@ -24,7 +24,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import HQUnavailable, check, dptr, fptr, iptr, load
-from .swasa import initial_population
+from .swasa import fixed_colors, initial_population
 
 
 class deltaETypes:  # IM:20
@@ -216,17 +216,19 @@ class ImageManipulation:
         return err, worst
 
     @staticmethod
-    def reseedUnused(err, worst, palettes, max_moves=-1):
+    def reseedUnused(err, worst, palettes, max_moves=-1, nfixed=0):
         """The repair rule of hq_reseed_unused: palettes (P, 4K) float32 with every unused
         colour moved onto the worst pixel of the clusters with the most error (at most
-        max_moves per palette, < 0: no limit).  Returns (a new array, moved (P,))."""
+        max_moves per palette, < 0: no limit).  ``nfixed`` (hq_reseed_unused_fixed): the first
+        nfixed colours of every palette are fixed -- never receivers, donors like any other.
+        Returns (a new array, moved (P,))."""
         err = np.ascontiguousarray(err, dtype=np.int64)
         P, K = err.shape[0], err.shape[1]
         worst = np.ascontiguousarray(worst, dtype=np.float32).reshape(P, K, 4)
         pal = _f32(palettes).reshape(P, 4 * K).copy()
         moved = np.zeros(P, np.int32)
-        check(load().hq_reseed_unused(_lib.i64ptr(err), fptr(worst), P, K, int(max_moves), fptr(pal),
-                                      moved.ctypes.data_as(C.POINTER(C.c_int))))
+        check(load().hq_reseed_unused_fixed(_lib.i64ptr(err), fptr(worst), P, K, int(max_moves), int(nfixed),
+                                            fptr(pal), moved.ctypes.data_as(C.POINTER(C.c_int))))
         return pal, moved
 
     def repairPopulation(self, colors, steps, delta: float = 2.0, max_moves=-1, keep_best=True,
@@ -409,6 +411,27 @@ class ImageManipulation:
         m = np.ascontiguousarray(m.reshape(-1), dtype=np.uint8)
         check(self._lib.hq_set_weights(ctx, _lib.u8ptr(m), w, h), ctx)
 
+    # fixed palette colours: libhq's addition (hq_set_fixed_colors, no reference counterpart)
+    def setFixedColors(self, colors=None):
+        """hq_set_fixed_colors: the first n colours of every palette are ``colors`` -- (n, 3),
+        (n, 4) or flat 4n, values in [0, 1] -- and no move of a search created from now on, and
+        no polish called from now on, changes them.  None (or n = 0) clears them.  A property of
+        the context: setImage, setMask and setWeights keep it.  ValueError: a bad shape or a
+        value that is not finite or outside [0, 1]."""
+        ctx = self._require()
+        fx = np.ascontiguousarray(fixed_colors(colors))
+        check(self._lib.hq_set_fixed_colors(ctx, fptr(fx) if fx.shape[0] else None, fx.shape[0]), ctx)
+
+    def fixedColors(self):
+        """hq_fixed_colors: the context's fixed colours, float32 (n, 4) with .w = 0 ((0, 4): none)."""
+        ctx = self._require()
+        n = C.c_int()
+        check(self._lib.hq_fixed_colors(ctx, C.byref(n), None), ctx)
+        out = np.zeros((n.value, 4), np.float32)
+        if n.value:
+            check(self._lib.hq_fixed_colors(ctx, None, fptr(out)), ctx)
+        return out
+
     def lastPath(self) -> dict:
         """hq_last_path as a dict with names, not numbers: the kernels the last pass enqueued on
         this context took (an evaluation's, a rendering's, the last one of a refine, repair or
@@ -477,7 +500,7 @@ class ImageManipulation:
                              iterations=None, stop=None, lloydSteps=0, lloydEvery=0,
                              init=None, initBits=5, repairEvery=0, repairMoves=-1, repairSteps=0,
                              dither=0.0, ditherSearch=False, ordered=None, orderedSearch=False, mask=None,
-                             weights=None):
+                             weights=None, fixed=None):
         """Full SWASA search (IM:383-591) on the GPU; returns bestColors float[4K].
 
         ``simulatedAnnealing`` is a :class:`~hybridquantization_amd.swasa.SWASA`;
@@ -530,8 +553,39 @@ class ImageManipulation:
         reported error, exactly where a mask would apply.  ``mask`` and ``weights`` together,
         or ``weights`` with ``repairEvery`` / ``repairSteps`` (no weighted error statistic),
         raise ValueError before anything runs.
+        ``fixed`` (hq_set_fixed_colors; setFixedColors' argument): the first n colours of the
+        palette are given and only the others are optimised -- by the search, its k-means and
+        repair moves and the polishes after it, which all run under that state; the returned
+        palette's first n colours are ``fixed``'s bits.  It is set for this call and the
+        context's previous fixed colours are back afterwards, on every way out.  A bad shape, a
+        value outside [0, 1] or n > K raise ValueError before anything runs.
+        ``init="mediancut"`` under ``fixed`` cuts to K - n colours and puts the fixed ones in
+        front (n = K: no cut); the cut does not know about the fixed colours.  An array ``init``
+        keeps its meaning, and its first n colours are overwritten by the library.
+        ``ditherSearch`` goes through hq_swasa_search_host_fixed.
         """
         ctx = self._require()
+        fx = None if fixed is None else np.ascontiguousarray(fixed_colors(fixed, int(nbOfColors)))
+        before = None if fx is None else self.fixedColors()
+        try:
+            if fx is not None:
+                self.setFixedColors(fx)
+            return self._findBestQuantization(
+                inlinergbOriginal, inlineScielabOriginal, w, nbOfColors, simulatedAnnealing, filters, absfilters,
+                illuminant, iterations, stop, lloydSteps, lloydEvery, init, initBits, repairEvery, repairMoves,
+                repairSteps, dither, ditherSearch, ordered, orderedSearch, mask, weights, fx)
+        finally:
+            if before is not None:
+                self.setFixedColors(before)
+
+    def _findBestQuantization(self, inlinergbOriginal, inlineScielabOriginal, w, nbOfColors, simulatedAnnealing,
+                              filters, absfilters, illuminant, iterations, stop, lloydSteps, lloydEvery, init,
+                              initBits, repairEvery, repairMoves, repairSteps, dither, ditherSearch, ordered,
+                              orderedSearch, mask, weights, fx):
+        """findBestQuantization's body; fx: the call's fixed colours (n, 4), already set on the
+        context, or None (then whatever the context holds applies, as to any search)."""
+        ctx = self._require()
+        nfx = 0 if fx is None else fx.shape[0]
         if mask is not None and weights is not None:
             raise ValueError("mask and weights: one piece of state, give one of them")
         if mask is not None and (int(repairEvery) != 0 or int(repairSteps) != 0):
@@ -569,14 +623,18 @@ class ImageManipulation:
         if isinstance(init, str):
             if init != "mediancut":
                 raise ValueError(f"init={init!r}: None, 'mediancut' or an array")
-            cells, den = self.colorHistogram(int(initBits))
-            init, _ = self.medianCut(cells, int(initBits), den, K)
+            # under fixed colours: the cut makes the K - n free ones, the fixed ones go in front
+            init = np.zeros(4 * K, np.float32)
+            init[:4 * nfx] = 0.0 if fx is None else fx.reshape(-1)
+            if K - nfx > 0:
+                cells, den = self.colorHistogram(int(initBits))
+                init[4 * nfx:], _ = self.medianCut(cells, int(initBits), den, K - nfx)
         if ditherSearch:
             P = params.population
             total = params.imax if iterations is None else min(int(iterations), params.imax)
             best, err, _ = sw.search_host(
                 K, lambda ps: self.ditherPopulation(ps.reshape(P, -1), dither, sw.delta), iterations=total,
-                initial=None if init is None else initial_population(init, P, K))
+                initial=None if init is None else initial_population(init, P, K), fixed=fx)
             self.bestError = self.bestErrorDithered = err
             self.iterations = total
             if self.verbose:

@@ -14,6 +14,7 @@ import numpy as np
 from . import _lib
 from ._lib import check, fptr, load
 from .image_manipulation import ImageManipulation, deltaETypes
+from .swasa import fixed_colors
 
 
 class Whitepoint:  # SP:19
@@ -88,7 +89,7 @@ def makeChannels(inline):
 
 def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
                  whitepoint=Whitepoint.D65, verbose=False, device=0, iterations=None, dither=0.0,
-                 ordered=None, mask=None, weights=None):
+                 ordered=None, mask=None, weights=None, fixed=None):
     """HQ:93-137 without the GUI: planar float image (3, N) in [0,1] ->
     (quantized planar image (3, N), bestColors float[4K], best error).  ``dither`` > 0
     (libhq's addition): the returned image is the best palette's Floyd-Steinberg rendering
@@ -98,7 +99,11 @@ def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
     ``mask`` (ImageManipulation.setMask's argument): the search and the returned error measure
     the pixels where it is non-zero only; the whole image is rendered.  ``weights``
     (ImageManipulation.setWeights' argument, bytes 0 .. 255; not together with ``mask``): the
-    search and the returned error weigh every pixel's error by it."""
+    search and the returned error weigh every pixel's error by it.  ``fixed``
+    (ImageManipulation.setFixedColors' argument): the first n colours of the palette are these
+    and the search optimises the others; a bad shape, a value outside [0, 1] or n > K is a
+    ValueError before anything runs."""
+    fixed_colors(fixed, int(nbOfColors))
     if ordered is not None and float(dither) > 0.0:
         raise ValueError("dither and ordered: one rendering")
     ip = ImageManipulation(deltaETypes.CIE76, verbose, swasa.convergence, device=device)
@@ -107,7 +112,7 @@ def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
         sp = ScielabProcessor(dpi, viewingDistance, whitepoint, None, ip)
         sc_img = sp.sRGBToScielab(image, w)
         best = sp.bestColors(inline_rgb, sc_img, w, nbOfColors, swasa, iterations=iterations, dither=dither,
-                             ordered=ordered, mask=mask, weights=weights)
+                             ordered=ordered, mask=mask, weights=weights, fixed=fixed)
         q = (ip.quantizeOrdered(best, ordered) if ordered is not None else
              ip.quantizeDithered(best, dither) if float(dither) > 0.0 else ip.quantize(inline_rgb, best))
         return np.stack(makeChannels(q)), best, ip.bestError

@@ -27,6 +27,26 @@ def initial_population(init, P: int, K: int) -> np.ndarray:
     return np.ascontiguousarray(pop)
 
 
+def fixed_colors(fixed, K=None) -> np.ndarray:
+    """Fixed palette colours as the (n, 4) float32 array hq_set_fixed_colors takes, .w = 0:
+    ``fixed`` is (n, 3), (n, 4) or flat 4n; None or an empty one is n = 0.  ValueError: another
+    shape, a value that is not finite or lies outside [0, 1], n > K (K given)."""
+    if fixed is None:
+        return np.zeros((0, 4), np.float32)
+    a = np.asarray(fixed, np.float32)
+    if a.ndim == 1 and a.size % 4 == 0:
+        a = a.reshape(-1, 4)
+    if a.ndim != 2 or a.shape[1] not in (3, 4):
+        raise ValueError(f"fixed colours of shape {a.shape}: want (n, 3), (n, 4) or flat 4n")
+    out = np.zeros((a.shape[0], 4), np.float32)
+    out[:, :3] = a[:, :3]
+    if not np.all((out >= 0.0) & (out <= 1.0)):  # (a NaN fails both)
+        raise ValueError("fixed colours with a channel that is not finite or outside [0, 1]")
+    if K is not None and out.shape[0] > int(K):
+        raise ValueError(f"{out.shape[0]} fixed colours in a palette of K = {int(K)}")
+    return out
+
+
 class SWASA:
     """SW:14 ``SWASA(population, imax, iTc, delta, convDelay, convSpread, t0, alpha, s0, beta, HQ)``."""
 
@@ -61,7 +81,8 @@ class SWASA:
     def computePenalty(self, usedColors) -> float:  # SW:74-82
         return float(np.count_nonzero(np.asarray(usedColors) == 0)) * self.delta
 
-    def search_host(self, K: int, eval_population, iterations=None, refine=None, every=0, initial=None):
+    def search_host(self, K: int, eval_population, iterations=None, refine=None, every=0, initial=None,
+                    fixed=None):
         """Run the native SWASA driver with a Python population evaluator.
 
         eval_population(palettes (P, K, 4) float32) -> costs (P,).  Returns
@@ -77,11 +98,18 @@ class SWASA:
         ``initial`` (libhq's addition, hq_swasa_search_host_from): the population the
         search starts from, (P, 4K) or (4K,) for every member, in place of the
         random one, whose draws are still made.
+
+        ``fixed`` (libhq's addition, hq_swasa_search_host_fixed): the first n colours of every
+        palette, (n, 3), (n, 4) or flat 4n (ValueError before anything runs for a bad shape, a
+        value outside [0, 1] or n > K).  They are written over every member at the start and no
+        iteration changes them, not even ``refine``: the driver puts them back after it.
         """
         lib = load()
         params = self.params()
         iters = self.imax if iterations is None else int(iterations)
         errbox = []
+        fx = np.ascontiguousarray(fixed_colors(fixed, K))
+        nfx = fx.shape[0]
 
         def _cb(user, pal, P, KK, costs):
             try:
@@ -112,7 +140,13 @@ class SWASA:
                     return 1
 
             rf = _lib.REFINE_FN(_rf)
-        if initial is not None:
+        if nfx > 0:
+            pop = None if initial is None else initial_population(initial, self.population, int(K))
+            rc = lib.hq_swasa_search_host_fixed(C.byref(params), int(K), self.seed, iters, cb, rf, int(every),
+                                                None if pop is None else _lib.fptr(pop),
+                                                _lib.fptr(fx), nfx, None,
+                                                _lib.fptr(best), C.byref(err), _lib.dptr(trace))
+        elif initial is not None:
             pop = initial_population(initial, self.population, int(K))
             rc = lib.hq_swasa_search_host_from(C.byref(params), int(K), self.seed, iters, cb, rf,
                                                int(every), _lib.fptr(pop), None, _lib.fptr(best),

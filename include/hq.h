@@ -277,6 +277,14 @@ int hq_cluster_errors(hq_ctx *ctx, int P, int K, int64_t *err, float *worst_rgb)
  * sum, P < 1, K < 1, a null pointer; the palettes are then left untouched. */
 int hq_reseed_unused(const int64_t *err, const float *worst_rgb, int P, int K, int max_moves,
                      float *palettes, int *moved);
+/* The same rule when the first nfixed colours of every palette are fixed
+ * (hq_set_fixed_colors): a receiver is a colour k >= nfixed with count 0.  A
+ * fixed colour is never a receiver -- unused, it stays where it is, takes no
+ * place in the receivers' order and consumes no donor -- and is a donor like any
+ * other colour.  nfixed = 0 is hq_reseed_unused bit for bit.  HQ_ERR_ARG in
+ * addition: nfixed < 0 or nfixed > K; the palettes are then left untouched. */
+int hq_reseed_unused_fixed(const int64_t *err, const float *worst_rgb, int P, int K,
+                           int max_moves, int nfixed, float *palettes, int *moved);
 /* Evaluates the P palettes with "pixel_err" forced on for the call (the
  * caller's value is back afterwards), then `steps` times: hq_cluster_errors,
  * hq_reseed_unused(max_moves), an evaluation of the repaired palettes.  trace,
@@ -688,6 +696,64 @@ int hq_swasa_search_host_from(const hq_swasa_params *params, int K, uint64_t see
                               hq_eval_fn eval, hq_refine_fn refine, int every,
                               const float *population, void *user,
                               float *best_colors, double *best_error, double *trace);
+
+/* ---- fixed palette colours: libhq's addition, no reference counterpart ----
+ * "These colours are given, optimise the others": the first n colours of every
+ * palette are fixed, and no move of a search or a polish changes them.  (No other
+ * placement: a caller orders the palette.)
+ *
+ * hq_set_fixed_colors: colors [n][4], .w ignored and stored as 0.  n = 0 or
+ * colors NULL clears them, the state of a fresh context.  HQ_ERR_ARG: n < 0,
+ * n > 16384, a channel that is not finite or lies outside [0, 1]; the colours in
+ * force stay.  A property of the context like the threshold map: hq_set_image*,
+ * hq_set_filters, hq_set_mask and hq_set_weights keep it, and setting it does not
+ * end the read-back getters' answers.  hq_fixed_colors reads it back: *n (n may be
+ * NULL) and, colors not NULL, its [n][4] floats.
+ *
+ * A search: hq_search_create[_from] reads the context's fixed colours once and
+ * keeps that n and those values for its life; a later hq_set_fixed_colors does not
+ * reach it.  n > K: HQ_ERR_ARG.  The random population's 3 K P draws are made as
+ * always (or the given population replaces them); then colours 0 .. n-1 of every
+ * member are overwritten with the fixed colours, and that population is what is
+ * evaluated, ranked and recorded as best.  In every iteration the candidates'
+ * draws are made exactly as without fixed colours -- the same stream at the same
+ * positions -- and for k < n the draw is discarded: the candidate's colour k is
+ * the member's colour k, its bits.  Acceptance, best and the convergence copy move
+ * whole members, whose first n colours are all the same.  Chunked palettes
+ * (K > 256): with n > 0 the chunk padding, copies of candidate colour 0, is the
+ * member's colour 0 itself.  A hybrid iteration's k-means update leaves colours
+ * k < n alone whatever their count; a repair iteration's rule is
+ * hq_reseed_unused_fixed with the search's n, so an unused fixed colour stays
+ * where it is and keeps paying delta -- the cost's definition does not change.
+ * It composes with what a search composes with ("sa_device" 0 / 1, "sa_graph",
+ * hq_search_set_lloyd, _repair and _ordered under their own refusals, mask and
+ * weights, a communicator or row-block shards where every rank sets the same
+ * colours); the device-resident and the host-driven search agree bit for bit.
+ *
+ * The polishes: hq_refine_population and hq_repair_population read the context's n
+ * when called (the values are not used) and never change colours 0 .. n-1 of the
+ * palettes they are given, in any step or in the kept-best copy; n > K:
+ * HQ_ERR_ARG.  Everything else -- hq_eval_population*, the ditherings,
+ * hq_cluster_sums, hq_cluster_errors, hq_centroids_from_sums, hq_reseed_unused,
+ * the histogram, the median cut -- does not look at the fixed colours, and with
+ * none set every output of the library is what it was without this section.
+ * Left out: a seed that takes the fixed colours into account, a delta that exempts
+ * them, fixed colours at arbitrary indices, quantised channel depth. */
+int hq_set_fixed_colors(hq_ctx *ctx, const float *colors, int n);
+int hq_fixed_colors(hq_ctx *ctx, int *n, float *colors);
+/* hq_swasa_search_host_from under fixed colours (the semantics above, the same
+ * driver code as a host-driven hq_search_*): fixed_colors [nfixed][4] overwrite
+ * the first nfixed colours of every member at the start; fixed_colors NULL with
+ * nfixed > 0 means the first nfixed colours of the population, or of the draws,
+ * are the fixed ones as they stand.  All 3 K draws per member are still made in
+ * every iteration.  The driver itself puts the fixed colours back after `refine`
+ * returns, so a refine callback need not know about them.  nfixed = 0 is
+ * hq_swasa_search_host_from bit for bit.  HQ_ERR_ARG in addition: nfixed < 0,
+ * nfixed > K, a fixed channel that is not finite or lies outside [0, 1]. */
+int hq_swasa_search_host_fixed(const hq_swasa_params *params, int K, uint64_t seed, int iterations,
+                               hq_eval_fn eval, hq_refine_fn refine, int every,
+                               const float *population, const float *fixed_colors, int nfixed,
+                               void *user, float *best_colors, double *best_error, double *trace);
 
 /* Kernel timing of the dominant kernels, measured with HIP events on the
  * context stream while enabled (bench.py roofline). */
