@@ -14,7 +14,8 @@ from .image_manipulation import ImageManipulation, deltaETypes, pack_filters  # 
 from .scielab_processor import (ScielabProcessor, Whitepoint, design_filters,  # noqa: F401
                                 makeChannels, makeinline, quantization)
 from .swasa import SWASA  # noqa: F401
+from .pyramid import pyramidSearch  # noqa: F401
 
 __all__ = ["ImageManipulation", "ScielabProcessor", "SWASA", "deltaETypes", "Whitepoint",
            "design_filters", "makeinline", "makeChannels", "quantization", "HQError",
-           "HQUnavailable", "load", "LIB_PATH", "pack_filters"]
+           "HQUnavailable", "load", "LIB_PATH", "pack_filters", "pyramidSearch"]

@@ -87,6 +87,10 @@ SIGNATURES = {
     "hq_set_image_planar_shard": (C.c_int, [_ctx, _f, _f, _f, C.c_int, C.c_int, _f, C.c_int,
                                             C.c_int]),
     "hq_get_labref": (C.c_int, [_ctx, _f]),
+    "hq_get_image": (C.c_int, [_ctx, _f]),
+    "hq_reduced_size": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "hq_reduce_weights": (C.c_int, [_u8, C.c_int, C.c_int, C.c_int, C.c_int, _u8]),
+    "hq_set_image_reduced": (C.c_int, [_ctx, _ctx, C.c_int, _f]),
     "hq_eval_population": (C.c_int, [_ctx, _f, C.c_int, C.c_int, C.c_float, _d, _i32]),
     "hq_eval_population_partial": (C.c_int, [_ctx, _f, C.c_int, C.c_int, _d]),
     "hq_get_indices": (C.c_int, [_ctx, C.c_int, _u8]),
@@ -128,6 +132,7 @@ SIGNATURES = {
                                         C.POINTER(C.c_void_p)]),
     "hq_search_run": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "hq_search_best": (C.c_int, [C.c_void_p, _f, _d, C.POINTER(C.c_int)]),
+    "hq_search_population": (C.c_int, [C.c_void_p, _f, _d]),
     "hq_search_destroy": (None, [C.c_void_p]),
     "hq_search_set_lloyd": (C.c_int, [C.c_void_p, C.c_int]),
     "hq_search_set_repair": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),

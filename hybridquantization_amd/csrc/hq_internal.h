@@ -432,4 +432,22 @@ struct GenArgs {
     const uint8_t* mask = nullptr;
 };
 
+// reduce_u8_kernel / reduce_planar_kernel (hq_reduce.hip): the box reduction of a whole
+// image by an integer factor (hq_set_image_reduced), one context's image into another's
+// planes.  Output pixel (X, Y) is the mean of source columns [f X, min(f X + f, W)) and
+// the rows likewise.
+struct ReduceArgs {
+    const uint32_t* rgbx;  // the packed form: the source's 8-bit copy [H][W] (R | G << 8 | B << 16), or null
+    const float* R;        // the planar form: the source's planes [H][W]
+    const float* G;
+    const float* B;
+    float* oR;             // the reduced planes [rh][rw]
+    float* oG;
+    float* oB;
+    int W, H;              // the source image
+    int rw, rh;            // the reduced image: ceil(W / f), ceil(H / f)
+    int factor;            // f in 1 .. kMaxReduce
+};
+constexpr int kMaxReduce = 16;
+
 }  // namespace hq

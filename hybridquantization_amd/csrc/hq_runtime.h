@@ -112,10 +112,11 @@ struct ProfSlot {
 
 enum Stage {
     kStGrid, kStAssign, kStCost, kStFinalize, kStSaStep, kStComm, kStCentroid, kStLloyd, kStHist, kStErrsum,
-    kStReseed, kStDither, kStages
+    kStReseed, kStDither, kStReduce, kStages
 };
 inline constexpr const char* kStageNames[kStages] = {"grid", "assign", "cost", "finalize", "sa_step", "comm",
-                                                     "centroid", "lloyd", "hist", "errsum", "reseed", "dither"};
+                                                     "centroid", "lloyd", "hist", "errsum", "reseed", "dither",
+                                                     "reduce"};
 
 // The start/stop event pairs of one evaluation (the context's EventSet) or of one
 // search iteration (kPairs pairs per iteration of a run in hq_search::pev).  A pass
@@ -132,12 +133,13 @@ enum Pair {
     kPRepGrid, kPRepAssign, kPRepCost,     // repair iteration: the cost pass,
     kPErrsum, kPReseed,                    // the error kernels (also hq_cluster_errors'), the reseed kernel
     kPHist,                                // hq_color_histogram's kernel
+    kPReduce,                              // hq_set_image_reduced's kernel
     kPairs
 };
 // The stage each pair's time and launch count go to.
 inline constexpr Stage kPairStage[kPairs] = {kStGrid, kStAssign, kStCost, kStFinalize, kStSaStep, kStComm,
                                              kStDither, kStGrid, kStAssign, kStCentroid, kStLloyd, kStGrid,
-                                             kStAssign, kStCost, kStErrsum, kStReseed, kStHist};
+                                             kStAssign, kStCost, kStErrsum, kStReseed, kStHist, kStReduce};
 
 // One evaluation's or iteration's events and which pairs it recorded (events of an
 // earlier call may sit in the other slots, so only recorded pairs are accumulated).

@@ -173,11 +173,16 @@ int compute_labref_device(hq_ctx* c) {
     return HQ_OK;
 }
 
-int set_image_common(hq_ctx* c, const std::vector<float>& R, const std::vector<float>& G,
-                     const std::vector<float>& B, const float* lab4_full, const float* illum) {
+// A new image on the context, in three steps: begin_image (the geometry c->g is the new image's
+// already), the planes filled on the context's stream -- uploaded from the host
+// (set_image_common) or reduced from another context's image on the device
+// (hq_set_image_reduced) -- and finish_image, the same tail for both.
+//
+// begin_image: what belonged to the old image goes, and the planes have the new one's size.
+int begin_image(hq_ctx* c) {
     const Geom& g = c->g;
     // c->g is the new image's already: nothing evaluated on the old one may be read at it
-    c->have_image = false;  // (until every plane below is in place)
+    c->have_image = false;  // (until every plane is in place: finish_image)
     drop(c);
     c->mask_on = c->weights_on = false;  // a mask, or a weight map, belongs to an image
     c->live_dirty = true;
@@ -185,9 +190,14 @@ int set_image_common(hq_ctx* c, const std::vector<float>& R, const std::vector<f
     HIP_TRY(c, c->d_R.ensure(plane));
     HIP_TRY(c, c->d_G.ensure(plane));
     HIP_TRY(c, c->d_B.ensure(plane));
-    HIP_TRY(c, hipMemcpyAsync(c->d_R.p, R.data(), plane, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->d_G.p, G.data(), plane, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->d_B.p, B.data(), plane, hipMemcpyHostToDevice, c->stream));
+    return HQ_OK;
+}
+
+// finish_image: the planes are in place (enqueued on c->stream).  The packed-form check, the
+// illuminant, LabRef -- the caller's (lab4_full, the full image's) or computed on the device
+// under the context's filters -- and the flags.
+int finish_image(hq_ctx* c, const float* lab4_full, const float* illum) {
+    const Geom& g = c->g;
     // An image whose channels are all exactly k/255 (the reference's int-RGB
     // source, IM:100) is also kept as packed bytes: assign reads 4 B per pixel
     // instead of 12 and rebuilds k/255 exactly (u8_unit).  The check and the
@@ -231,6 +241,16 @@ int set_image_common(hq_ctx* c, const std::vector<float>& R, const std::vector<f
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->have_image = true;
     return HQ_OK;
+}
+
+int set_image_common(hq_ctx* c, const std::vector<float>& R, const std::vector<float>& G,
+                     const std::vector<float>& B, const float* lab4_full, const float* illum) {
+    if (int rc = begin_image(c)) return rc;
+    const size_t plane = sizeof(float) * (size_t)round_up(c->g.n_ext, 4);
+    HIP_TRY(c, hipMemcpyAsync(c->d_R.p, R.data(), plane, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_G.p, G.data(), plane, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_B.p, B.data(), plane, hipMemcpyHostToDevice, c->stream));
+    return finish_image(c, lab4_full, illum);
 }
 
 int check_geom_args(hq_ctx* c, int w, int h, int r0, int r1) {
@@ -423,6 +443,66 @@ int hq_set_image_planar_shard(hq_ctx* c, const float* R, const float* G, const f
     gather_rows(G, 1, 0, c->g, g);
     gather_rows(B, 1, 0, c->g, b);
     return set_image_common(c, r, g, b, nullptr, illum);
+}
+
+// The box reduction of src's image as dst's whole image: the second way into finish_image.
+// Every refusal comes before dst is touched.  The kernel runs on dst's stream and reads src's
+// buffers; both contexts are idle here, since every entry point synchronises its stream.
+int hq_set_image_reduced(hq_ctx* dst, hq_ctx* src, int factor, const float* illum) {
+    if (!dst) return HQ_ERR_ARG;
+    if (!src || src == dst) return fail(dst, HQ_ERR_ARG, "hq_set_image_reduced: a null source, or the source itself");
+    if (src->device != dst->device)
+        return fail(dst, HQ_ERR_UNSUPPORTED, "hq_set_image_reduced: source on device %d, destination on device %d",
+                    src->device, dst->device);
+    if (!src->have_image) return fail(dst, HQ_ERR_STATE, "hq_set_image_reduced: no image set on the source");
+    if (!whole_image(src))
+        return fail(dst, HQ_ERR_STATE, "hq_set_image_reduced: the source is a row-block shard (rows [%d, %d) of %d)",
+                    src->g.r0, src->g.r1, src->g.H);
+    int rw = 0, rh = 0;
+    if (hq_reduced_size(src->g.W, src->g.H, factor, &rw, &rh))
+        return fail(dst, HQ_ERR_ARG, "hq_set_image_reduced: factor %d outside 1 .. %d", factor, kMaxReduce);
+    int rc = check_geom_args(dst, rw, rh, 0, rh);
+    if (rc) return rc;
+    if ((rc = bind(dst))) return rc;
+    float il[3];  // (src's, read before anything of dst changes)
+    std::memcpy(il, illum ? illum : src->illum, sizeof il);
+    dst->g = make_geom(rw, rh, 0, rh, dst->half);
+    if ((rc = begin_image(dst))) return rc;
+    ReduceArgs a{};
+    a.rgbx = src->img_u8 ? src->d_rgbx.as<uint32_t>() : nullptr;
+    a.R = src->d_R.as<float>();
+    a.G = src->d_G.as<float>();
+    a.B = src->d_B.as<float>();
+    a.oR = dst->d_R.as<float>();
+    a.oG = dst->d_G.as<float>();
+    a.oB = dst->d_B.as<float>();
+    a.W = src->g.W;
+    a.H = src->g.H;
+    a.rw = rw;
+    a.rh = rh;
+    a.factor = factor;
+    ProfRec pr = prof_begin(dst);
+    HIP_TRY(dst, timed_launch(pr, kPReduce, [&] { return launch_reduce_image(a, dst->stream); }));
+    rc = finish_image(dst, nullptr, il);
+    if (!rc) prof_accumulate(dst, pr);  // (finish_image has synchronised the stream)
+    return rc;
+}
+
+int hq_get_image(hq_ctx* c, float* rgba4) {
+    if (!c || !rgba4) return HQ_ERR_ARG;
+    if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set");
+    int rc = bind(c);
+    if (rc) return rc;
+    const Geom& g = c->g;
+    const size_t n = (size_t)n_own(g), first = (size_t)own_first(g);
+    std::vector<float> R(n), G(n), B(n);
+    HIP_TRY(c, hipMemcpy(R.data(), c->d_R.as<float>() + first, sizeof(float) * n, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(G.data(), c->d_G.as<float>() + first, sizeof(float) * n, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(B.data(), c->d_B.as<float>() + first, sizeof(float) * n, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) {
+        rgba4[4 * i] = R[i]; rgba4[4 * i + 1] = G[i]; rgba4[4 * i + 2] = B[i]; rgba4[4 * i + 3] = 0.f;
+    }
+    return HQ_OK;
 }
 
 namespace {

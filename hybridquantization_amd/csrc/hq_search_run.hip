@@ -569,6 +569,25 @@ int hq_search_best(const hq_search* s, float* colors, double* best_error, int* i
     return HQ_OK;
 }
 
+// The state the next iteration starts from.  Device-resident: the state buffers the last accept
+// step wrote (colors[st], err[st]: plain [P][4K] and [P] whatever the chunk count -- the chunk
+// padding lives in the prepared palettes alone), after the stream has drained.
+int hq_search_population(const hq_search* s, float* colors, double* errors) {
+    if (!s || !colors) return HQ_ERR_ARG;
+    if (!s->driver) {
+        hq_ctx* c = s->ctx;
+        int rc = bind(c);
+        if (rc) return rc;
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipMemcpy(colors, s->colors[s->st].p, sizeof(float) * 4 * s->K * s->P, hipMemcpyDeviceToHost));
+        if (errors) HIP_TRY(c, hipMemcpy(errors, s->err[s->st].p, sizeof(double) * s->P, hipMemcpyDeviceToHost));
+        return HQ_OK;
+    }
+    std::copy(s->driver->colors().begin(), s->driver->colors().end(), colors);
+    if (errors) std::copy(s->driver->current_errors().begin(), s->driver->current_errors().end(), errors);
+    return HQ_OK;
+}
+
 int hq_search_info(const hq_search* s, int* device_resident, int* nch, int* graph) {
     if (!s) return HQ_ERR_ARG;
     if (device_resident) *device_resident = s->driver ? 0 : 1;  // (hq_search_create_from built one or the other)

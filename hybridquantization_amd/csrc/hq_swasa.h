@@ -104,6 +104,10 @@ class SearchDriver {
     const std::vector<float>& best_colors() const { return best_colors_; }
     double best_error() const { return best_error_; }
     int iteration() const { return ite_; }
+    // The current population [P][4K] and each member's error as the accept step holds it
+    // (hq_search_population).
+    const std::vector<float>& colors() const { return colors_; }
+    const std::vector<double>& current_errors() const { return current_errors_; }
 
    private:
     Swasa sw_;

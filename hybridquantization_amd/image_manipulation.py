@@ -57,6 +57,7 @@ class ImageManipulation:
         self.verbose = verbose
         self.convergence = convergence
         self.deltaEType = deltaEType
+        self.device = int(device)
         self._ctx = C.c_void_p()
         rc = self._lib.hq_create(device, deltaEType, C.byref(self._ctx))
         self.openCLAvailable = rc == _lib.HQ_OK  # IM:54, IM:78
@@ -131,6 +132,53 @@ class ImageManipulation:
         out = np.zeros(4 * self.w * self.h, np.float32)
         check(self._lib.hq_get_labref(ctx, fptr(out)), ctx)
         return out
+
+    def getImage(self):
+        """hq_get_image: the device image as the argmin sees it, inline RGBA float32[4 w h]
+        with .w = 0 (pairs with getLabRef)."""
+        ctx = self._require()
+        out = np.zeros(4 * self.w * self.h, np.float32)
+        check(self._lib.hq_get_image(ctx, fptr(out)), ctx)
+        return out
+
+    # an image pyramid on the device: libhq's additions (hq_set_image_reduced & co.)
+    @staticmethod
+    def reducedSize(w: int, h: int, factor: int):
+        """hq_reduced_size -> (ceil(w / factor), ceil(h / factor)); factor in 1 .. 16."""
+        rw, rh = C.c_int(), C.c_int()
+        check(load().hq_reduced_size(int(w), int(h), int(factor), C.byref(rw), C.byref(rh)))
+        return rw.value, rh.value
+
+    @staticmethod
+    def reduceWeights(src, w: int, factor: int, is_mask: bool = False):
+        """hq_reduce_weights: a mask (``is_mask``: non-zero counts as 255) or weight map of a
+        w-wide image, (h, w) or flat, integer or bool, values 0 .. 255 -> the uint8 (rh, rw)
+        weight map of the image reduced by ``factor``: the rounded mean of each block, raised
+        to 1 where any byte of the block is non-zero."""
+        m = np.asarray(src)
+        if m.dtype != np.bool_ and not np.issubdtype(m.dtype, np.integer):
+            raise ValueError(f"map of dtype {m.dtype}: an integer or bool array")
+        w = int(w)
+        if m.ndim not in (1, 2) or w < 1 or m.size == 0 or m.size % w or (m.ndim == 2 and m.shape[1] != w):
+            raise ValueError(f"map of shape {m.shape} for an image of width {w}")
+        if m.dtype != np.bool_ and (int(m.min()) < 0 or int(m.max()) > 255):
+            raise ValueError(f"map values in {int(m.min())} .. {int(m.max())}: bytes, 0 .. 255")
+        m = np.ascontiguousarray(m.reshape(-1), dtype=np.uint8)
+        h = m.size // w
+        rw, rh = ImageManipulation.reducedSize(w, h, factor)
+        out = np.zeros((rh, rw), np.uint8)
+        check(load().hq_reduce_weights(_lib.u8ptr(m), w, h, int(factor), int(bool(is_mask)), _lib.u8ptr(out)))
+        return out
+
+    def setImageReduced(self, src, factor: int, illuminant=None):
+        """hq_set_image_reduced: this context's image becomes the box reduction by ``factor`` of
+        the image the ImageManipulation ``src`` holds, made on the device; S-CIELAB is computed
+        here under this context's own filters.  ``illuminant`` None means ``src``'s.  Mask and
+        weights are dropped, as by setImage."""
+        ctx = self._require()
+        il = None if illuminant is None else _f32(illuminant)
+        check(self._lib.hq_set_image_reduced(ctx, src._require(), int(factor), None if il is None else fptr(il)), ctx)
+        self.w, self.h = self.reducedSize(src.w, src.h, factor)
 
     # IM:620 computeQuantizationErrorPopulation
     def computeQuantizationErrorPopulation(self, colors, delta: float = 2.0, return_used=False):
@@ -461,6 +509,15 @@ class ImageManipulation:
         v = [C.c_int() for _ in range(3)]
         check(self._lib.hq_search_info(search, *[C.byref(x) for x in v]), self._require())
         return {"device_resident": bool(v[0].value), "nch": v[1].value, "graph": bool(v[2].value)}
+
+    def searchPopulation(self, search, P: int, K: int):
+        """hq_search_population of a search handle made on this context with a population of P
+        palettes of K colours -> (colors float32 (P, 4K), errors float64 (P,)): the members the
+        next iteration moves, in the search's order, and each one's error as the search holds it."""
+        colors = np.zeros((int(P), 4 * int(K)), np.float32)
+        errors = np.zeros(int(P), np.float64)
+        check(self._lib.hq_search_population(search, fptr(colors), dptr(errors)), self._require())
+        return colors, errors
 
     def weightsInfo(self):
         """hq_weights_info -> (w_full, w_owned): the sum of the weights over the full image and

@@ -89,7 +89,7 @@ def makeChannels(inline):
 
 def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
                  whitepoint=Whitepoint.D65, verbose=False, device=0, iterations=None, dither=0.0,
-                 ordered=None, mask=None, weights=None, fixed=None):
+                 ordered=None, mask=None, weights=None, fixed=None, pyramid=None):
     """HQ:93-137 without the GUI: planar float image (3, N) in [0,1] ->
     (quantized planar image (3, N), bestColors float[4K], best error).  ``dither`` > 0
     (libhq's addition): the returned image is the best palette's Floyd-Steinberg rendering
@@ -102,13 +102,27 @@ def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
     search and the returned error weigh every pixel's error by it.  ``fixed``
     (ImageManipulation.setFixedColors' argument): the first n colours of the palette are these
     and the search optimises the others; a bad shape, a value outside [0, 1] or n > K is a
-    ValueError before anything runs."""
+    ValueError before anything runs.  ``pyramid`` (pyramid.pyramidSearch's ``levels``: (factor,
+    iterations) pairs with decreasing factors that end in 1): the search runs coarse to fine on
+    a device-built image pyramid; the levels carry the iteration counts, so ``iterations`` must
+    then be None.  None is the plain search, untouched."""
     fixed_colors(fixed, int(nbOfColors))
     if ordered is not None and float(dither) > 0.0:
         raise ValueError("dither and ordered: one rendering")
+    if pyramid is not None:
+        from .pyramid import check_levels, pyramidSearch
+        check_levels(pyramid)
+        if iterations is not None:
+            raise ValueError("pyramid and iterations: the levels carry the iteration counts")
     ip = ImageManipulation(deltaETypes.CIE76, verbose, swasa.convergence, device=device)
     try:
         inline_rgb = makeinline(image)
+        if pyramid is not None:
+            best = pyramidSearch(ip, inline_rgb, w, nbOfColors, swasa, dpi, viewingDistance, whitepoint,
+                                 levels=pyramid, mask=mask, weights=weights, fixed=fixed)
+            q = (ip.quantizeOrdered(best, ordered) if ordered is not None else
+                 ip.quantizeDithered(best, dither) if float(dither) > 0.0 else ip.quantize(inline_rgb, best))
+            return np.stack(makeChannels(q)), best, ip.bestError
         sp = ScielabProcessor(dpi, viewingDistance, whitepoint, None, ip)
         sc_img = sp.sRGBToScielab(image, w)
         best = sp.bestColors(inline_rgb, sc_img, w, nbOfColors, swasa, iterations=iterations, dither=dither,

@@ -115,6 +115,11 @@ int hq_set_image_planar_shard(hq_ctx *ctx, const float *R, const float *G, const
                               int w, int h, const float *illum, int row_begin, int row_end);
 /* Reads back the device S-CIELAB of the owned rows as inline float4. */
 int hq_get_labref(hq_ctx *ctx, float *lab4);
+/* Reads back the device image of the owned rows as the argmin sees it, inline RGBA
+ * float4 with .w = 0 (w*(row_end-row_begin) pixels): the planar floats; the packed
+ * 8-bit copy, where there is one, rebuilds the same bits.  HQ_ERR_STATE: no image
+ * set.  Pairs with hq_get_labref; the test surface of hq_set_image_reduced. */
+int hq_get_image(hq_ctx *ctx, float *rgba4);
 
 /* IM:620 computeQuantizationErrorPopulation for P palettes of K colours
  * (K in [1, 2^24] as the plugin allows, HQ:192).  K <= 256: the pruned grid
@@ -549,6 +554,57 @@ int hq_color_histogram(hq_ctx *ctx, int bits, int64_t *cells, int64_t *den);
  * count, a total count of 0 or above 2^48 (the priority would leave 64 bits). */
 int hq_median_cut(const int64_t *cells, int bits, int64_t den, int K, float *palette, int *made);
 
+/* ---- an image pyramid on the device: libhq's additions, no reference counterpart ----
+ * Every search runs at the image's full resolution, yet the cost is a blurred dE: it
+ * changes little when the image is box-reduced and the filters are designed for the
+ * correspondingly lower dpi.  The entry points below make the levels of a
+ * coarse-to-fine search: the reduced image without a trip through the host, and the
+ * reduced mask or weight map.  hq_search_population (further down) hands a level's
+ * population to hq_search_create_from on the next; the policy that chains them is the
+ * Python binding's pyramidSearch.  Left out: a sharded source or one on another
+ * device, non-integer or anisotropic factors, any filter other than the box, a
+ * pyramid inside one context or inside hq_search_run, the JNI / Java binding.
+ *
+ * hq_reduced_size: *rw = ceil(w / factor), *rh = ceil(h / factor), the size of the
+ * reduction of a w x h image.  Host-only.  HQ_ERR_ARG: factor outside 1 .. 16, w or
+ * h < 1, a null pointer. */
+int hq_reduced_size(int w, int h, int factor, int *rw, int *rh);
+/* The reduction of a mask (is_mask != 0: a non-zero byte counts as 255) or a weight map
+ * src[h][w] to out[rh][rw], a weight map for hq_set_weights on the reduced image.
+ * Host-only, needs no context, integer arithmetic.  Output block (X, Y) covers source
+ * columns [f X, min(f X + f, w)) and the rows likewise, n pixels of byte sum S:
+ *     out = floor((2 S + n) / (2 n))            (round half up)
+ * raised to 1 when any byte of the block is non-zero, so a reduced region never loses
+ * a block that held a counted pixel; an all-zero block stays 0.  factor 1 is the
+ * identity for weights and 0 / 255 for a mask.  HQ_ERR_ARG: hq_reduced_size's, a null
+ * pointer; nothing is written then. */
+int hq_reduce_weights(const uint8_t *src, int w, int h, int factor, int is_mask, uint8_t *out);
+/* dst receives the box reduction by `factor` of src's image as its whole image, made
+ * on the device from the image src holds (nothing is downloaded or uploaded).  dst
+ * otherwise behaves as after hq_set_image(dst, reduced, NULL, rw, rh, illum): the
+ * record of the last evaluation is dropped (the read-back rule), mask and weights are
+ * dropped, LabRef is computed on the device under dst's own filters, and the reduced
+ * image goes through the packed-form check.  illum NULL means src's.  Nothing of src
+ * changes, what its getters may still read included.  Output pixel (X, Y) is made
+ * from the block of hq_reduce_weights, n pixels, in one of two forms, each stated so
+ * that numpy restates it bit for bit:
+ *  - src holds the packed 8-bit copy of a k/255 image (whatever its option "img_u8"
+ *    says): per channel the integer sum s of the block's bytes, the byte
+ *    floor((2 s + n) / (2 n)), and dst's plane gets exactly the float k/255 of that
+ *    byte, as a host float division makes it.  dst therefore passes the packed check
+ *    and keeps the 4-byte argmin path; hq_last_path's `pixels` says which form dst
+ *    took.
+ *  - otherwise, per channel the fp32 sum of the block in raster order (rows outer,
+ *    columns inner), starting from the block's first pixel, every addition rounded to
+ *    nearest; then one correctly rounded fp32 division by (float)n.
+ * Refusals, dst left exactly as it was: a null dst or src, src == dst: HQ_ERR_ARG;
+ * contexts on different devices: HQ_ERR_UNSUPPORTED; src without an image, or src a
+ * row-block shard: HQ_ERR_STATE; dst without filters: HQ_ERR_STATE; factor outside
+ * 1 .. 16: HQ_ERR_ARG; a reduced width or height below dst's halfSize: HQ_ERR_ARG
+ * (hq_set_image's rule).  The message is dst's hq_last_error.  One host thread for
+ * the two contexts during the call. */
+int hq_set_image_reduced(hq_ctx *dst, hq_ctx *src, int factor, const float *illum);
+
 /* IM:770 quantize(inlineImageRGB, colors): chosen colour per pixel (CL:147-170).
  * used (K ints) may be NULL. */
 int hq_quantize(hq_ctx *ctx, const float *rgba4, int64_t n, const float *colors, int K,
@@ -608,6 +664,18 @@ int hq_search_create_from(hq_ctx *ctx, const hq_swasa_params *params, int K, uin
                           const float *population, hq_search **out);
 int hq_search_run(hq_search *s, int iterations, int *ran);
 int hq_search_best(const hq_search *s, float *colors, double *best_error, int *iteration);
+/* The search's current population (libhq's addition; hq_search_best reads its best
+ * member only): the P palettes the next iteration moves, in the order the search
+ * holds them, colors[P][4K] with .w = 0, and errors[p] (errors may be NULL), each
+ * member's error as the accept step holds it (IM:518-545: its own accepted
+ * candidate's, or the iteration's minimum after a convergence copy).  After
+ * hq_search_create_from it is the given population and its evaluation.  Plain [P][4K]
+ * for chunked palettes (K > 256) too, never the padded chunk layout.  A
+ * device-resident search copies from its state buffers after a stream synchronise, a
+ * host-driven one from its driver; the two agree bit for bit.  A search created from
+ * the returned population starts from the returned errors, bit for bit.  The best
+ * error is at most min(errors): the best member may have been replaced since. */
+int hq_search_population(const hq_search *s, float *colors, double *errors);
 void hq_search_destroy(hq_search *s);
 /* Hybrid iterations (libhq's addition: Schaefer & Nolle interleave a k-means
  * step with the annealing moves, the reference holds the annealing half only).
@@ -767,7 +835,8 @@ int hq_profile_enable(hq_ctx *ctx, int on);
  * kernel of a device-resident repair iteration, whose error pass counts under "grid", "assign"
  * and "cost"), "dither" (hq_dither_population's kernel, which stands in the place of "grid"
  * and "assign": a dithered evaluation counts nothing under those; an ordered evaluation's grid
- * and argmin count under "grid" and "assign" like the plain one's); returns total ms and launch
+ * and argmin count under "grid" and "assign" like the plain one's), "reduce" (hq_set_image_reduced's
+ * kernel, on the destination context); returns total ms and launch
  * count (HIP events on the context stream). */
 int hq_profile_get(hq_ctx *ctx, const char *kernel, double *total_ms, int64_t *launches);
 int hq_profile_reset(hq_ctx *ctx);
