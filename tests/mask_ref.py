@@ -93,6 +93,52 @@ def masks_for(w, h, worst=None):
     return out
 
 
+def tile_masks(w, h, tw, th, r0=0, r1=None, de2000=False):
+    """Masks cut along the tile grid of one fast cost launch (tiles of tw x th over the rows
+    [r0, r1), tile_grid's), name -> uint8 (h, w) of the full image; at least 2 x 2 tiles.  They
+    make the live-tile list differ wherever a tile width, a tile height or tiles_x is wrong:
+    edges: column w - 1 and row r1 - 1 only, the partial last tile column and row;
+    one_tile: every pixel of the interior tile (1, 1) and nothing else;
+    checker_corners: the four corner pixels of every tile with tx + ty odd;
+    seams: the two pixel columns and the two rows at every inner tile boundary."""
+    r1 = h if r1 is None else r1
+    g0, tx, ty = tile_grid(w, r0, r1, tw, th, de2000)
+    assert tx >= 2 and ty >= 2, (w, h, tw, th, r0, r1)
+    xs = [(i * tw, min((i + 1) * tw, w)) for i in range(tx)]
+    ys = [(max(g0 + j * th, r0), min(g0 + (j + 1) * th, r1)) for j in range(ty)]
+    own = np.zeros((h, w), bool)
+    own[r0:r1] = True
+    edges, one, checker, seams = (np.zeros((h, w), bool) for _ in range(4))
+    edges[:, w - 1] = edges[r1 - 1] = True
+    one[ys[1][0]:ys[1][1], xs[1][0]:xs[1][1]] = True
+    for j, (y0, y1) in enumerate(ys):
+        for i, (x0, x1) in enumerate(xs):
+            if (i + j) % 2:
+                checker[np.ix_((y0, y1 - 1), (x0, x1 - 1))] = True
+    for x0, _ in xs[1:]:
+        seams[:, x0 - 1:x0 + 1] = True
+    for y0, _ in ys[1:]:
+        seams[y0 - 1:y0 + 1] = True
+    rng = np.random.default_rng([w, h, tw, th])
+    out = {"ones": np.ones((h, w), bool), "edges": edges & own, "one_tile": one, "checker_corners": checker,
+           "seams": seams & own, "bernoulli": rng.random((h, w)) < 0.5}
+    return {k: np.ascontiguousarray(v, np.uint8) for k, v in out.items()}
+
+
+TILE_WEIGHTS = np.array([1, 7, 128, 255], np.uint8)
+
+
+def tile_weight_maps(w, h, tw, th, r0=0, r1=None, de2000=False):
+    """tile_masks' supports with weights drawn from {1, 7, 128, 255}, and ramp: (x + y) % 256,
+    which has zeros -> name -> uint8 (h, w)."""
+    rng = np.random.default_rng([w, h, tw, th, 1])
+    out = {k: np.where(m != 0, rng.choice(TILE_WEIGHTS, (h, w)), 0).astype(np.uint8)
+           for k, m in tile_masks(w, h, tw, th, r0, r1, de2000).items()}
+    yy, xx = np.mgrid[0:h, 0:w]
+    out["ramp"] = ((xx + yy) % 256).astype(np.uint8)
+    return out
+
+
 def two_tone_image(w=64, h=32):
     """A k/255 image whose left half is shades of blue and right half shades of red, and the
     mask of the left half -> (rgba (n, 4) float32, bytes (n, 3) int64, mask uint8 (h, w))."""

@@ -83,11 +83,15 @@ def check_cost(m, mask, costs, used, msg, n_full=None, delta=DELTA):
         assert miss <= bound, f"{msg} p={p}"
 
 
-def sweep_masks(m, pals, w, h, msg, evaluate=plain, masks=None, extra=None, skip_bits=True):
+def sweep_masks(m, pals, w, h, msg, evaluate=plain, masks=None, extra=None, skip_bits=True, tile=None, de2000=False,
+                each=None):
     """Every mask of the shape on the context m (image set, "pixel_err" 1): the unmasked
     evaluation first; under each mask the indices and the error image keep their bits and the
     cost satisfies check 1; with "pixel_err" 0 the cost's bits are the same with and without
-    the tile skip."""
+    the tile skip.  masks: name -> mask instead of masks_for's; tile = (tw, th) of the fast
+    launch: the skipping launch ran the restated number of live tiles, the other one all;
+    each(name, mask, skip): called after each of those two evaluations.
+    -> dict(fin, costs0, covers: name -> (the mask as set, its costs))."""
     Pn, K = pals.shape[0], pals.shape[1] // 4
     m.setMask(None)
     costs0, used0 = evaluate(m, pals)
@@ -97,6 +101,7 @@ def sweep_masks(m, pals, w, h, msg, evaluate=plain, masks=None, extra=None, skip
     worst = int(np.argmax(np.where(fin, errs0[0], -1.0)))
     ms = dict(masks_for(w, h, worst=worst) if masks is None else masks)
     ms.update(extra or {})
+    covers = {}
     for name, mask in ms.items():
         if not fin.all():
             mask = (inside(mask) & fin).astype(np.uint8).reshape(h, w)
@@ -109,6 +114,7 @@ def sweep_masks(m, pals, w, h, msg, evaluate=plain, masks=None, extra=None, skip
             np.testing.assert_array_equal(u32(m.getPixelErrors(p)), u32(errs0[p]), err_msg=f"{msg} {name} p={p}")
             np.testing.assert_array_equal(indices(m, p, K), idx0[p], err_msg=f"{msg} {name} p={p}")
         check_cost(m, mask, costs, used, f"{msg} {name}")
+        covers[name] = (mask, costs)
         info = m.maskInfo()
         assert info[0] == info[1] == int(inside(mask).sum()) and info[2] == info[3]
         if name == "ones" and fin.all():
@@ -120,11 +126,18 @@ def sweep_masks(m, pals, w, h, msg, evaluate=plain, masks=None, extra=None, skip
                 c2, u2 = evaluate(m, pals)
                 np.testing.assert_array_equal(u64(c2), u64(costs), err_msg=f"{msg} {name} mask_skip {skip}")
                 np.testing.assert_array_equal(u2, used0)
+                if tile is not None:
+                    live = len(live_tiles(mask, w, h, *tile, de2000=de2000))
+                    every = len(live_tiles(np.ones((h, w), np.uint8), w, h, *tile, de2000=de2000))
+                    assert m.maskInfo()[2:] == (live if skip else every, every), (msg, name, skip, m.maskInfo(), live, every)
+                if each is not None:
+                    each(name, mask, skip)
             m.setOption("mask_skip", 1)
             m.setOption("pixel_err", 1)
     m.setMask(None)
     c3, _ = evaluate(m, pals)
     np.testing.assert_array_equal(c3, costs0, err_msg=f"{msg}: the mask cleared")  # (dE94: NaN equals NaN)
+    return dict(fin=fin, costs0=costs0, covers=covers)
 
 
 # ---------------------------------------------------------------------------

@@ -40,18 +40,21 @@ def check_cost(m, wmap, costs, used, msg, w_full=None, delta=DELTA):
         assert miss <= bound, f"{msg} p={p}"
 
 
-def sweep_maps(m, pals, w, h, msg, evaluate=plain, tile=(128, 16), de2000=False):
+def sweep_maps(m, pals, w, h, msg, evaluate=plain, tile=(128, 16), de2000=False, maps=None, each=None):
     """Every weight map of the shape on the context m (image set, "pixel_err" 1): the unweighted
     evaluation first; under each map the indices, the used flags and the error image keep their
     bits and the cost satisfies check 1; with "pixel_err" 0 the cost's bits are the same with and
-    without the tile skip, and the skipping launch ran the restated number of live tiles."""
+    without the tile skip, and the skipping launch ran the restated number of live tiles.  maps:
+    name -> map instead of weight_maps'; each(name, map, skip): called after each of those two
+    evaluations.  -> dict(fin, costs0, covers: name -> (the map as set, its costs))."""
     Pn, K = pals.shape[0], pals.shape[1] // 4
     m.setWeights(None)
     costs0, used0 = evaluate(m, pals)
     errs0 = [m.getPixelErrors(p) for p in range(Pn)]
     idx0 = [indices(m, p, K) for p in range(Pn)]
     fin = np.all([np.isfinite(e) for e in errs0], axis=0)  # (dE94: the pixels whose dE is a number)
-    for name, wmap in weight_maps(w, h).items():
+    covers = {}
+    for name, wmap in (weight_maps(w, h) if maps is None else maps).items():
         if not fin.all():
             wmap = np.where(fin.reshape(h, w), wmap, 0).astype(np.uint8)
             if not wmap.any():
@@ -63,6 +66,7 @@ def sweep_maps(m, pals, w, h, msg, evaluate=plain, tile=(128, 16), de2000=False)
             np.testing.assert_array_equal(u32(m.getPixelErrors(p)), u32(errs0[p]), err_msg=f"{msg} {name} p={p}")
             np.testing.assert_array_equal(indices(m, p, K), idx0[p], err_msg=f"{msg} {name} p={p}")
         check_cost(m, wmap, costs, used, f"{msg} {name}")
+        covers[name] = (wmap, costs)
         assert m.weightsInfo() == (weight_sum(wmap),) * 2
         info = m.maskInfo()
         assert info[0] == info[1] == nonzero(wmap) and info[2] == info[3]
@@ -77,11 +81,14 @@ def sweep_maps(m, pals, w, h, msg, evaluate=plain, tile=(128, 16), de2000=False)
                 live = live_tile_count(wmap, w, h, *tile, de2000=de2000)
                 assert every == live_tile_count(np.ones((h, w)), w, h, *tile, de2000=de2000)
                 assert run == (live if skip else every), (msg, name, skip, run, live, every)
+            if each is not None:
+                each(name, wmap, skip)
         m.setOption("mask_skip", 1)
         m.setOption("pixel_err", 1)
     m.setWeights(None)
     c3, _ = evaluate(m, pals)
     np.testing.assert_array_equal(c3, costs0, err_msg=f"{msg}: the weights cleared")  # (dE94: NaN equals NaN)
+    return dict(fin=fin, costs0=costs0, covers=covers)
 
 
 # ---------------------------------------------------------------------------
