@@ -48,7 +48,18 @@ class hq_path_info(C.Structure):
                                   "cost_waves", "cost_nch", "cost_instance", "gen_h", "gen_h_outputs",
                                   "gen_h_split", "gen_h_rpt", "gen_v", "gen_v_rows")] + \
         [("why_not_fast", C.c_uint32), ("previous_pass", C.c_int32), ("previous_cost", C.c_int32),
-         ("tiles_run", C.c_int64), ("tiles_all", C.c_int64)]
+         ("tiles_run", C.c_int64), ("tiles_all", C.c_int64), ("diffuse_rows", C.c_int32),
+         ("diffuse_slope", C.c_int32)]
+
+
+class hq_diffusion_taps(C.Structure):
+    """include/hq.h's diffusion kernel: w[dy][dx + 2] / div goes from (x, y) to (x + dx, y + dy)."""
+    _fields_ = [("w", (C.c_int32 * 5) * 3), ("div", C.c_int32)]
+
+
+# hq.h's enum hq_diffusion, in its order
+DIFFUSION_PRESETS = ("floyd_steinberg", "jarvis", "stucki", "burkes", "sierra3", "sierra2", "sierra_lite",
+                     "atkinson")
 
 
 # the names of hq_path_info's kinds (hq.h's enums, in their order) and of hq_path_why's bits
@@ -58,7 +69,7 @@ PATH_NAMES = {
     "previous_cost": ("none", "cost16w", "cost_mfma", "tiled_generic", "pixel_generic"),
     "pixels": ("none", "u8", "planar"),
     "grid": ("none", "build_grid", "lists16"),
-    "argmin": ("none", "assign_pipe", "assign_pipe_ordered", "assign16", "assign_wide", "dither"),
+    "argmin": ("none", "assign_pipe", "assign_pipe_ordered", "assign16", "assign_wide", "dither", "diffuse"),
     "cost": ("none", "cost16w", "cost_mfma", "tiled_generic", "pixel_generic"),
     "cost_instance": ("plain", "masked", "weighted"),
     "gen_h": ("none", "gen_hpass", "gen_hrow", "gen_hrow4", "gen_hmfma"),
@@ -110,6 +121,11 @@ SIGNATURES = {
     "hq_repair_population": (C.c_int, [_ctx, _f, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int,
                                        _d, _i32, _d]),
     "hq_dither_population": (C.c_int, [_ctx, _f, C.c_int, C.c_int, C.c_float, C.c_float, _d, _i32]),
+    "hq_diffusion_preset": (C.c_int, [C.c_int, C.POINTER(hq_diffusion_taps)]),
+    "hq_diffusion_taps_legal": (C.c_int, [C.POINTER(hq_diffusion_taps)]),
+    "hq_diffusion_classify": (C.c_int, [C.POINTER(hq_diffusion_taps), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "hq_diffuse_population": (C.c_int, [_ctx, _f, C.c_int, C.c_int, C.POINTER(hq_diffusion_taps), C.c_float,
+                                        C.c_float, _d, _i32]),
     "hq_bayer_map": (C.c_int, [C.c_int, _f]),
     "hq_set_dither_map": (C.c_int, [_ctx, _f, C.c_int, C.c_int]),
     "hq_ordered_population": (C.c_int, [_ctx, _f, C.c_int, C.c_int, _f, C.c_float, _d, _i32]),

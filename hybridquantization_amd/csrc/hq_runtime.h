@@ -173,7 +173,9 @@ inline hipError_t timed_launch(ProfRec& pr, Pair p, F&& launch, bool start = tru
 //   reads.
 // Dither (hq_dither_population): a full pass whose index images are the
 //   Floyd-Steinberg rendering at `strength` -- the counter set and the used bits
-//   zeroed as without a grid, then dither_kernel in the place of grid + assign.
+//   zeroed as without a grid, then dither_kernel in the place of grid + assign;
+//   or (hq_diffuse_population) the rendering under the pass's diffusion taps, by
+//   diffuse_kernel in the same place and under the same profile stage.
 // Counter-set parity: each pass takes the other counter set than the last one
 // (build_grid zeroes it), so an accept step can read the last set while the next
 // is filled.  A side pass (AssignOnly, CostOnly: nothing reads its sums, so no
@@ -188,6 +190,11 @@ inline hipError_t timed_launch(ProfRec& pr, Pair p, F&& launch, bool start = tru
 struct Pass {
     enum Kind { Full, Fold, AssignOnly, CostOnly, Dither } kind = Full;
     float strength = 0.f;  // Dither
+    // Dither by hq_diffuse_population with a tap set that is not Floyd-Steinberg's: the
+    // instance <diffuse_rows, diffuse_slope> of diffuse_kernel (hq_diffuse.hip) in
+    // dither_kernel's place.  diffuse_rows 0: dither_kernel.
+    int diffuse_rows = 0, diffuse_slope = 0;
+    hq_diffusion_taps taps{};
     bool ordered = false;
     float amp[3] = {0.f, 0.f, 0.f};  // ordered: the amplitude per channel
     bool side() const { return kind == AssignOnly || kind == CostOnly; }
@@ -270,7 +277,8 @@ struct hq_ctx {
     int planar_ok = -1;
     hq::DevBuf d_hist;             // hq_color_histogram: [2^(3 bits)][4] int64 cells, then the range flag
     hq::DevBuf d_errstat, d_worst; // [P][K][4] u64 statistics, then the flag; [P][K] float4 worst pixels
-    hq::DevBuf d_dcarry;           // hq_dither_population: [P][3][W] errors of a strip's last row
+    hq::DevBuf d_dcarry;           // hq_dither_population: [P][3][W] errors of a strip's last row;
+                                   // hq_diffuse_population: [P][R][3][W], of its last R rows
     // ordered dithering: the threshold map (hq_set_dither_map; empty: the default, Bayer 16 x 16)
     // and its device copy, kMaxMapSide^2 floats made once by ensure_dither_map (its address is
     // in captured launches) and written by it whenever the host map has changed

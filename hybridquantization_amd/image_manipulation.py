@@ -295,27 +295,62 @@ class ImageManipulation:
         return (pal, costs, used, trace) if return_trace else (pal, costs, used)
 
     # dithered rendering: libhq's addition (hq_dither_population, no reference counterpart)
-    def ditherPopulation(self, colors, strength: float = 1.0, delta: float = 2.0, return_used=False):
+    @staticmethod
+    def diffusionPreset(name):
+        """hq_diffusion_preset: the diffusion kernel ``name`` ("floyd_steinberg", "jarvis", "stucki",
+        "burkes", "sierra3", "sierra2", "sierra_lite", "atkinson") -> (w int32 (3, 5), div): w[dy, dx + 2]
+        / div is the share of its error a pixel sends to (x + dx, y + dy)."""
+        if name not in _lib.DIFFUSION_PRESETS:
+            raise ValueError(f"diffusion kernel {name!r}: one of {', '.join(_lib.DIFFUSION_PRESETS)}")
+        t = _lib.hq_diffusion_taps()
+        check(load().hq_diffusion_preset(_lib.DIFFUSION_PRESETS.index(name), C.byref(t)))
+        return np.array([list(row) for row in t.w], np.int32), int(t.div)
+
+    @classmethod
+    def _taps(cls, kernel):
+        """``kernel=``: a preset's name or (3 x 5 array of integers, div) -> hq_diffusion_taps."""
+        w, div = cls.diffusionPreset(kernel) if isinstance(kernel, str) else kernel
+        w = np.asarray(w)
+        if w.shape != (3, 5) or not np.all(w == np.round(w)) or int(div) != div:
+            raise ValueError("kernel: a preset name or (3 x 5 array of integers, div)")
+        if np.any(np.abs(w.astype(np.float64)) >= 2.0 ** 31) or not abs(int(div)) < 2 ** 31:
+            raise ValueError("kernel: weights and div are 32-bit integers")
+        t = _lib.hq_diffusion_taps()
+        for dy in range(3):
+            for i in range(5):
+                t.w[dy][i] = int(w[dy, i])
+        t.div = int(div)
+        return t
+
+    def ditherPopulation(self, colors, strength: float = 1.0, delta: float = 2.0, return_used=False, kernel=None):
         """computeQuantizationErrorPopulation of the Floyd-Steinberg rendering at ``strength``
         in [0, 1] (0: the plain evaluation, bit for bit): colors (P, 4K), K <= 256 ->
         costs (P,) [, used (P, K)].  getIndices and getPixelErrors then answer for the
-        dithered rendering; clusterSums and clusterErrors need a plain evaluation again."""
+        dithered rendering; clusterSums and clusterErrors need a plain evaluation again.
+        ``kernel`` (hq_diffuse_population): another diffusion kernel, a preset's name
+        (diffusionPreset) or (3 x 5 array, div); None is hq_dither_population."""
         ctx = self._require()
+        taps = None if kernel is None else self._taps(kernel)
         pal = _f32(np.stack([np.asarray(c, np.float32).reshape(-1) for c in colors]))
         P, K = pal.shape[0], pal.shape[1] // 4
         costs = np.zeros(P, np.float64)
         used = np.zeros((P, K), np.int32)
-        check(self._lib.hq_dither_population(ctx, fptr(pal), P, K, float(strength), float(delta),
-                                             dptr(costs), iptr(used)), ctx)
+        if taps is None:
+            check(self._lib.hq_dither_population(ctx, fptr(pal), P, K, float(strength), float(delta),
+                                                 dptr(costs), iptr(used)), ctx)
+        else:
+            check(self._lib.hq_diffuse_population(ctx, fptr(pal), P, K, C.byref(taps), float(strength),
+                                                  float(delta), dptr(costs), iptr(used)), ctx)
         return (costs, used) if return_used else costs
 
-    def quantizeDithered(self, colors, strength: float = 1.0):
+    def quantizeDithered(self, colors, strength: float = 1.0, kernel=None):
         """The dithered rendering of the context's image (setImage, findBestQuantization)
         with the palette colors float[4K]: ``quantize``'s output format, an inline float4
         image palette[idx] with .w = 0, the indices read back from the device and gathered
-        on the host.  Sets ``lastUsedColors`` and ``ditherError``, the rendering's mean dE."""
+        on the host.  Sets ``lastUsedColors`` and ``ditherError``, the rendering's mean dE.
+        ``kernel``: ditherPopulation's."""
         pal = _f32(colors).reshape(1, -1)
-        costs, used = self.ditherPopulation(pal, strength, 0.0, return_used=True)
+        costs, used = self.ditherPopulation(pal, strength, 0.0, return_used=True, kernel=kernel)
         table = pal.reshape(-1, 4).copy()
         table[:, 3] = 0.0
         self.lastUsedColors = used[0]
@@ -557,7 +592,7 @@ class ImageManipulation:
                              iterations=None, stop=None, lloydSteps=0, lloydEvery=0,
                              init=None, initBits=5, repairEvery=0, repairMoves=-1, repairSteps=0,
                              dither=0.0, ditherSearch=False, ordered=None, orderedSearch=False, mask=None,
-                             weights=None, fixed=None):
+                             weights=None, fixed=None, ditherKernel=None):
         """Full SWASA search (IM:383-591) on the GPU; returns bestColors float[4K].
 
         ``simulatedAnnealing`` is a :class:`~hybridquantization_amd.swasa.SWASA`;
@@ -592,6 +627,8 @@ class ImageManipulation:
         ``stop`` is not polled); ``init`` composes with it, the k-means and repair moves
         do not (ValueError: both start from a nearest-colour assignment).  ``bestError``
         and ``bestErrorDithered`` are then both the dithered cost.
+        ``ditherKernel`` (hq_diffuse_population; ditherPopulation's ``kernel``): the diffusion
+        kernel of that final rendering and of ``ditherSearch``; None is Floyd-Steinberg.
         ``ordered`` (hq_ordered_population: an amplitude, a float or three, in [0, 1];
         ``orderedAmplitude(K)`` is a starting point): once the search and its polishes are
         done the best palette is also evaluated in its ordered-dither rendering,
@@ -630,7 +667,7 @@ class ImageManipulation:
             return self._findBestQuantization(
                 inlinergbOriginal, inlineScielabOriginal, w, nbOfColors, simulatedAnnealing, filters, absfilters,
                 illuminant, iterations, stop, lloydSteps, lloydEvery, init, initBits, repairEvery, repairMoves,
-                repairSteps, dither, ditherSearch, ordered, orderedSearch, mask, weights, fx)
+                repairSteps, dither, ditherSearch, ordered, orderedSearch, mask, weights, fx, ditherKernel)
         finally:
             if before is not None:
                 self.setFixedColors(before)
@@ -638,7 +675,7 @@ class ImageManipulation:
     def _findBestQuantization(self, inlinergbOriginal, inlineScielabOriginal, w, nbOfColors, simulatedAnnealing,
                               filters, absfilters, illuminant, iterations, stop, lloydSteps, lloydEvery, init,
                               initBits, repairEvery, repairMoves, repairSteps, dither, ditherSearch, ordered,
-                              orderedSearch, mask, weights, fx):
+                              orderedSearch, mask, weights, fx, ditherKernel=None):
         """findBestQuantization's body; fx: the call's fixed colours (n, 4), already set on the
         context, or None (then whatever the context holds applies, as to any search)."""
         ctx = self._require()
@@ -655,6 +692,8 @@ class ImageManipulation:
         if orderedSearch and (int(lloydSteps) != 0 or int(repairSteps) != 0):
             raise ValueError("orderedSearch with a k-means or repair polish")
         dither = float(dither)
+        if ditherKernel is not None:
+            self._taps(ditherKernel)  # (a bad one raises before anything runs)
         if not 0.0 <= dither <= 1.0:
             raise ValueError(f"dither={dither!r}: a strength in [0, 1]")
         if ditherSearch:
@@ -690,7 +729,8 @@ class ImageManipulation:
             P = params.population
             total = params.imax if iterations is None else min(int(iterations), params.imax)
             best, err, _ = sw.search_host(
-                K, lambda ps: self.ditherPopulation(ps.reshape(P, -1), dither, sw.delta), iterations=total,
+                K, lambda ps: self.ditherPopulation(ps.reshape(P, -1), dither, sw.delta, kernel=ditherKernel),
+                iterations=total,
                 initial=None if init is None else initial_population(init, P, K), fixed=fx)
             self.bestError = self.bestErrorDithered = err
             self.iterations = total
@@ -751,7 +791,8 @@ class ImageManipulation:
             if self.verbose:
                 print("Final error after %d k-means steps : %.5f" % (int(lloydSteps), self.bestError))
         if dither > 0.0:
-            self.bestErrorDithered = float(self.ditherPopulation(best.reshape(1, -1), dither, sw.delta)[0])
+            self.bestErrorDithered = float(self.ditherPopulation(best.reshape(1, -1), dither, sw.delta,
+                                                                 kernel=ditherKernel)[0])
             if self.verbose:
                 print("Final error, dithered at strength %g : %.5f" % (dither, self.bestErrorDithered))
         if amp is not None:

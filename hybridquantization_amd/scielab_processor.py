@@ -89,11 +89,13 @@ def makeChannels(inline):
 
 def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
                  whitepoint=Whitepoint.D65, verbose=False, device=0, iterations=None, dither=0.0,
-                 ordered=None, mask=None, weights=None, fixed=None, pyramid=None):
+                 ordered=None, mask=None, weights=None, fixed=None, pyramid=None, ditherKernel=None):
     """HQ:93-137 without the GUI: planar float image (3, N) in [0,1] ->
     (quantized planar image (3, N), bestColors float[4K], best error).  ``dither`` > 0
     (libhq's addition): the returned image is the best palette's Floyd-Steinberg rendering
-    at that strength (ImageManipulation.quantizeDithered) instead of the nearest-colour one.
+    at that strength (ImageManipulation.quantizeDithered) instead of the nearest-colour one;
+    ``ditherKernel`` (a preset's name or (3 x 5 array, div): ditherPopulation's ``kernel``) is the
+    diffusion kernel of that rendering, None Floyd-Steinberg's.
     ``ordered`` (an amplitude, a float or three; not together with ``dither``): the returned
     image is the best palette's ordered-dither rendering (ImageManipulation.quantizeOrdered).
     ``mask`` (ImageManipulation.setMask's argument): the search and the returned error measure
@@ -121,14 +123,16 @@ def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
             best = pyramidSearch(ip, inline_rgb, w, nbOfColors, swasa, dpi, viewingDistance, whitepoint,
                                  levels=pyramid, mask=mask, weights=weights, fixed=fixed)
             q = (ip.quantizeOrdered(best, ordered) if ordered is not None else
-                 ip.quantizeDithered(best, dither) if float(dither) > 0.0 else ip.quantize(inline_rgb, best))
+                 ip.quantizeDithered(best, dither, kernel=ditherKernel) if float(dither) > 0.0 else
+                 ip.quantize(inline_rgb, best))
             return np.stack(makeChannels(q)), best, ip.bestError
         sp = ScielabProcessor(dpi, viewingDistance, whitepoint, None, ip)
         sc_img = sp.sRGBToScielab(image, w)
         best = sp.bestColors(inline_rgb, sc_img, w, nbOfColors, swasa, iterations=iterations, dither=dither,
-                             ordered=ordered, mask=mask, weights=weights, fixed=fixed)
+                             ditherKernel=ditherKernel, ordered=ordered, mask=mask, weights=weights, fixed=fixed)
         q = (ip.quantizeOrdered(best, ordered) if ordered is not None else
-             ip.quantizeDithered(best, dither) if float(dither) > 0.0 else ip.quantize(inline_rgb, best))
+             ip.quantizeDithered(best, dither, kernel=ditherKernel) if float(dither) > 0.0 else
+             ip.quantize(inline_rgb, best))
         return np.stack(makeChannels(q)), best, ip.bestError
     finally:
         ip.close()

@@ -335,6 +335,68 @@ int hq_repair_population(hq_ctx *ctx, float *palettes, int P, int K, int steps, 
 int hq_dither_population(hq_ctx *ctx, const float *palettes, int P, int K, float strength,
                          float delta, double *costs, int32_t *used);
 
+/* ---- error diffusion with other kernels: libhq's addition ----
+ * A diffusion kernel in scatter notation, as the literature writes it:
+ * w[dy][dx + 2] / div is the share of its error that pixel (x, y) sends to
+ * (x + dx, y + dy), dy = 0 .. 2, dx = -2 .. 2.  A tap set is legal when every
+ * weight is >= 0, row 0 holds weights at dx = 1 and 2 only (the raster order has
+ * passed the others), div >= 1, at least one weight is non-zero and the weights'
+ * sum is at most div (and so fits an int32) -- under which every |e| and |t|
+ * below stays <= 1.
+ * The rendering is hq_dither_population's with another value for the argmin: in
+ * the argmin's space, per channel, every operation one fp32 operation rounded to
+ * nearest and none contracted into an fma, e = 0 outside the image, s = strength:
+ *     acc = the products float(w[dy][dx+2]) * e(x-dx, y-dy), added one at a time in
+ *           the order dy = 0 (dx = 1, 2), dy = 1 (dx = -2 .. 2), dy = 2 (dx = -2 .. 2);
+ *           acc starts as the first product
+ *     t   = acc / float(div)                 (IEEE division, correctly rounded)
+ *     v   = min(max(pix + s * t, 0), 1)
+ *     idx(x, y) = the first minimum over k of the argmin's distance(v, pal[k])
+ *     e(x, y) = v - pal[idx]                 (pal[k].w taken as 0)
+ * The device adds the product of every tap position its kernel instance holds,
+ * zero weights included: such a product is +-0 and changes no v.
+ * hq_diffusion_preset fills *taps with a kernel of the literature (HQ_ERR_ARG: a
+ * null taps, an unknown preset). */
+typedef struct hq_diffusion_taps {
+    int32_t w[3][5];
+    int32_t div;
+} hq_diffusion_taps;
+enum hq_diffusion {
+    HQ_DIFFUSION_FLOYD_STEINBERG = 0, /* 7 | 3 5 1                           / 16 */
+    HQ_DIFFUSION_JARVIS = 1,          /* 7 5 | 3 5 7 5 3 | 1 3 5 3 1         / 48 */
+    HQ_DIFFUSION_STUCKI = 2,          /* 8 4 | 2 4 8 4 2 | 1 2 4 2 1         / 42 */
+    HQ_DIFFUSION_BURKES = 3,          /* 8 4 | 2 4 8 4 2                     / 32 */
+    HQ_DIFFUSION_SIERRA3 = 4,         /* 5 3 | 2 4 5 4 2 | 0 2 3 2 0         / 32 */
+    HQ_DIFFUSION_SIERRA2 = 5,         /* 4 3 | 1 2 3 2 1                     / 16 */
+    HQ_DIFFUSION_SIERRA_LITE = 6,     /* 2 | 1 1 (dx = -1, 0)                /  4 */
+    HQ_DIFFUSION_ATKINSON = 7,        /* 1 1 | 1 1 1 (dx = -1 .. 1) | 1 (dx = 0) / 8 */
+    HQ_DIFFUSION_COUNT = 8
+};
+int hq_diffusion_preset(int which, hq_diffusion_taps *taps);
+/* 1 when the tap set is legal (above), else 0 (a null pointer included). */
+int hq_diffusion_taps_legal(const hq_diffusion_taps *taps);
+/* The kernel instance a legal tap set runs: *rows = R, the highest dy that holds a
+ * weight, at least 1; *slope = S = max(a, 1) + 1 with a the largest -dx among row
+ * 1's weights, the slope of the wavefronts t = x + S y whose order is the raster
+ * order's.  HQ_ERR_ARG: a null pointer, an illegal tap set. */
+int hq_diffusion_classify(const hq_diffusion_taps *taps, int *rows, int *slope);
+
+/* hq_dither_population with the diffusion kernel *taps: its refusals, the state
+ * afterwards (the getters answer for the rendering, hq_cluster_sums and
+ * hq_cluster_errors return HQ_ERR_STATE), its behaviour toward a live hq_search, a
+ * mask and weights, and in addition HQ_ERR_ARG for a null or illegal tap set.
+ * A tap set equal to the Floyd-Steinberg preset (weights and div) runs
+ * hq_dither_population's kernel with hq_dither_population's formula -- the result
+ * is that call's bit for bit (its formula multiplies by 1/16 and pairs the sums,
+ * which the division and the order above need not reproduce); hq_last_path then
+ * reports HQ_ARGMIN_DITHER.  Every other tap set runs the definition above
+ * (HQ_ARGMIN_DIFFUSE, with diffuse_rows and diffuse_slope).  The results do not
+ * depend on option "dither_rows"; instances of slope 3 run strips of at most 512
+ * rows. */
+int hq_diffuse_population(hq_ctx *ctx, const float *palettes, int P, int K,
+                          const hq_diffusion_taps *taps, float strength, float delta,
+                          double *costs, int32_t *used);
+
 /* ---- ordered dithering: libhq's addition, no reference counterpart ----
  * Error diffusion is a serial recurrence (one workgroup per palette); a threshold
  * map gives most of its S-CIELAB gain with every pixel independent, so it lives
@@ -833,7 +895,7 @@ int hq_profile_enable(hq_ctx *ctx, int on);
  * "assign" and "centroid"), "hist" (hq_color_histogram's kernel), "errsum" (hq_cluster_errors'
  * kernels: the statistics and the gather of the worst pixels' colours), "reseed" (the reseed
  * kernel of a device-resident repair iteration, whose error pass counts under "grid", "assign"
- * and "cost"), "dither" (hq_dither_population's kernel, which stands in the place of "grid"
+ * and "cost"), "dither" (hq_dither_population's and hq_diffuse_population's kernels, which stand in the place of "grid"
  * and "assign": a dithered evaluation counts nothing under those; an ordered evaluation's grid
  * and argmin count under "grid" and "assign" like the plain one's), "reduce" (hq_set_image_reduced's
  * kernel, on the destination context); returns total ms and launch
@@ -858,7 +920,8 @@ enum hq_path_pixels { HQ_PIXELS_NONE = 0, HQ_PIXELS_U8 = 1, HQ_PIXELS_PLANAR = 2
 enum hq_path_grid { HQ_GRID_NONE = 0, HQ_GRID_BUILD_GRID = 1, HQ_GRID_LISTS16 = 2 };
 enum hq_path_argmin {
     HQ_ARGMIN_NONE = 0, HQ_ARGMIN_ASSIGN_PIPE = 1, HQ_ARGMIN_ASSIGN_PIPE_ORDERED = 2, HQ_ARGMIN_ASSIGN16 = 3,
-    HQ_ARGMIN_ASSIGN_WIDE = 4, HQ_ARGMIN_DITHER = 5
+    HQ_ARGMIN_ASSIGN_WIDE = 4, HQ_ARGMIN_DITHER = 5,
+    HQ_ARGMIN_DIFFUSE = 6    /* hq_diffuse_population's kernels (hq_diffuse.hip) */
 };
 enum hq_path_cost {
     HQ_COST_NONE = 0,        /* an assign-only pass, or a mask without a live tile */
@@ -905,6 +968,8 @@ typedef struct hq_path_info {
     int32_t previous_pass;   /* hq_path_pass of the pass before this one (sequence - 1) ... */
     int32_t previous_cost;   /* ... and its hq_path_cost: a hybrid iteration is assign-only, then full */
     int64_t tiles_run, tiles_all; /* hq_mask_info's, of this pass (0: not a fast cost launch) */
+    int32_t diffuse_rows;    /* HQ_ARGMIN_DIFFUSE: R of the instance (hq_diffusion_classify), else 0 */
+    int32_t diffuse_slope;   /* HQ_ARGMIN_DIFFUSE: S of the instance, else 0 */
 } hq_path_info;
 int hq_last_path(hq_ctx *ctx, hq_path_info *info);
 /* *device_resident = 1 when the search's iterations run on the device, 0 when the
