@@ -77,6 +77,7 @@ int fast_bucket(int half);
 bool trim_window_ok(const float* k1, int H, int HB);
 bool taps_fit_split(const float* k1, const float* k2, const float* k3, const float* absk3, int taps);
 void opp2xyz_over_illum(const float inv_illum[3], float m[9]);
+int bad_illum_component(const float illum[3]);
 void build_fast_taps(int HB, int H, const float* k1, const float* k2, const float* k3, const float* absk3,
                      void* out);
 size_t vpass_f16_stack_fragment_halves(int HB);

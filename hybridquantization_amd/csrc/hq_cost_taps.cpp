@@ -18,6 +18,15 @@ void opp2xyz_over_illum(const float inv_illum[3], float m[9]) {
     for (int i = 0; i < 9; ++i) m[i] = (float)((double)opp2xyz[i] * inv_illum[i / 3]);
 }
 
+// The first component (0 .. 2) of an illuminant that is not finite and greater than 0; -1: none.
+// (-0.0f, 0.0f, negative values, NaN and the infinities all fail `finite and > 0`: 1 / Xn must
+// be a positive finite scale of the Opp->XYZ row.)
+int bad_illum_component(const float illum[3]) {
+    for (int i = 0; i < 3; ++i)
+        if (!(std::isfinite(illum[i]) && illum[i] > 0.0f)) return i;
+    return -1;
+}
+
 // The smallest tap bucket that holds a filter of half-width `half`; 0 = none (the generic path).
 int fast_bucket(int half) {
     for (const int HB : kFastBuckets)

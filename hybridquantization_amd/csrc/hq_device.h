@@ -60,7 +60,10 @@ __device__ __forceinline__ float lab_f(float t) {  // CL:137
 // t in (delta^3, ~1.1]: log2 t stays small, so its fp32 rounding moves the
 // root by ~2e-8 relative on average -- round 3 worked on t' = 116^3 t, whose
 // log2 near 20 carried 6x that), the linear segment fma(kappa / 116, t,
-// 16 / 116), selected branch-free.
+// 16 / 116), selected branch-free.  Off D65 t leaves that range: the tests
+// cover t up to 2.16 (Z/Zn at illuminant A; |log2 t| stays below 8 down to
+// delta^3) and Yn = 0.8 and 1.25, at the bars measured under D65
+// (tests/test_illuminant_gpu.py, DESIGN.md "The illuminant axis").
 __device__ __forceinline__ float lab_f_fast(float t) {
     // y is only selected for t > delta^3 > 0 (for t <= 0 it is 0 or NaN, discarded)
     const float y = __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(t) * (1.0f / 3.0f));

@@ -266,6 +266,16 @@ int check_geom_args(hq_ctx* c, int w, int h, int r0, int r1) {
     return HQ_OK;
 }
 
+// An illuminant a caller gave (NULL: none given, the context's stays): every component finite
+// and greater than 0, or 1.0f / illum is infinite or NaN and every cost with it.  Checked with
+// the other arguments, before anything of the context changes.
+int check_illum_arg(hq_ctx* c, const float* illum) {
+    const int i = illum ? bad_illum_component(illum) : -1;
+    if (i < 0) return HQ_OK;
+    return fail(c, HQ_ERR_ARG, "illum[%d] (%cn) is %g: every component of the illuminant must be finite and "
+                               "greater than 0", i, "XYZ"[i], (double)illum[i]);
+}
+
 }  // namespace
 
 // ============================================================================
@@ -416,6 +426,7 @@ int hq_set_image_shard(hq_ctx* c, const float* rgba4, const float* lab4, int w, 
     if (!rgba4) return fail(c, HQ_ERR_ARG, "null image");
     int rc = check_geom_args(c, w, h, row_begin, row_end);
     if (rc) return rc;
+    if ((rc = check_illum_arg(c, illum))) return rc;
     if ((rc = bind(c))) return rc;
     c->g = make_geom(w, h, row_begin, row_end, c->half);
     std::vector<float> R, G, B;
@@ -436,6 +447,7 @@ int hq_set_image_planar_shard(hq_ctx* c, const float* R, const float* G, const f
     if (!R || !G || !B) return fail(c, HQ_ERR_ARG, "null plane");
     int rc = check_geom_args(c, w, h, row_begin, row_end);
     if (rc) return rc;
+    if ((rc = check_illum_arg(c, illum))) return rc;
     if ((rc = bind(c))) return rc;
     c->g = make_geom(w, h, row_begin, row_end, c->half);
     std::vector<float> r, g, b;
@@ -463,6 +475,7 @@ int hq_set_image_reduced(hq_ctx* dst, hq_ctx* src, int factor, const float* illu
         return fail(dst, HQ_ERR_ARG, "hq_set_image_reduced: factor %d outside 1 .. %d", factor, kMaxReduce);
     int rc = check_geom_args(dst, rw, rh, 0, rh);
     if (rc) return rc;
+    if ((rc = check_illum_arg(dst, illum))) return rc;
     if ((rc = bind(dst))) return rc;
     float il[3];  // (src's, read before anything of dst changes)
     std::memcpy(il, illum ? illum : src->illum, sizeof il);
@@ -654,6 +667,7 @@ int hq_xyz_to_scielab(hq_ctx* c, const float* xyz4, int w, int h, const float* i
     if (!c || !xyz4 || !lab4) return HQ_ERR_ARG;
     int rc = check_geom_args(c, w, h, 0, h);
     if (rc) return rc;
+    if ((rc = check_illum_arg(c, illum))) return rc;
     if ((rc = bind(c))) return rc;
     const Geom g = make_geom(w, h, 0, h, c->half);
     const int64_t n = (int64_t)w * h;

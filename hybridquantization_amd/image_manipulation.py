@@ -115,15 +115,24 @@ class ImageManipulation:
 
     # device-resident image of IM:450-478 (uploaded once per search)
     def setImage(self, rgbInline, labInline, w, illuminant, row_begin=0, row_end=None):
+        """hq_set_image_shard: the inline RGBA image of width ``w`` (and its inline S-CIELAB
+        ``labInline``, or None: computed on the device) becomes the context's image.
+        ``illuminant``: the white point (Xn, Yn, Zn) Opp->Lab divides by, three floats, each
+        finite and greater than 0 (Yn need not be 1); it becomes the context's illuminant, read
+        by every later evaluation, rendering and search pass.  None keeps the context's current
+        illuminant: D65 on a new context, else the one the last successful setImage /
+        setImageReduced left.  A component that is NaN, infinite, zero or negative raises HQError
+        (HQ_ERR_ARG, the message names the component) and nothing of the context changes."""
         ctx = self._require()
         rgb = _f32(rgbInline)
         n = rgb.shape[0] // 4
         h = n // int(w)
         lab = _f32(labInline) if labInline is not None else None
-        il = _f32(illuminant)
+        il = None if illuminant is None else _f32(illuminant)
         row_end = h if row_end is None else row_end
         check(self._lib.hq_set_image_shard(ctx, fptr(rgb), fptr(lab) if lab is not None else None,
-                                           int(w), h, fptr(il), int(row_begin), int(row_end)),
+                                           int(w), h, None if il is None else fptr(il), int(row_begin),
+                                           int(row_end)),
               ctx)
         self.w, self.h = int(w), h
 

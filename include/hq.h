@@ -94,14 +94,29 @@ int hq_set_filters(hq_ctx *ctx, int taps, const float *k1, const float *k2, cons
 int hq_rgb_to_xyz(hq_ctx *ctx, const float *R, const float *G, const float *B, int64_t n,
                   float *xyz4);
 /* IM:285 XYZtoScielab(XYZ, filters, absfilters, w, illuminant): inline XYZ ->
- * inline S-CIELAB Lab (CL:111-116, CL:2-74 filter by filter, CL:124-145). */
+ * inline S-CIELAB Lab (CL:111-116, CL:2-74 filter by filter, CL:124-145).
+ * illum: the white point (Xn, Yn, Zn) of CL:124-131; NULL means the context's
+ * current illuminant (see hq_set_image).  The call never changes the context's
+ * illuminant.  A component that is not finite and greater than 0: HQ_ERR_ARG, as
+ * for hq_set_image. */
 int hq_xyz_to_scielab(hq_ctx *ctx, const float *xyz4, int w, int h, const float *illum,
                       float *lab4);
 
 /* Device-resident state of IM:383 findBestQuantization (IM:450-478):
  * uploads the inline RGBA image and its S-CIELAB (inline Lab float4) once.
  * lab4 may be NULL: the S-CIELAB of the image is then computed on the device
- * (IM:100 + IM:285 semantics).  Requires w, h >= halfSize. */
+ * (IM:100 + IM:285 semantics).  Requires w, h >= halfSize.
+ * illum: the white point (Xn, Yn, Zn) that Opp->Lab divides by (CL:124-131), any
+ * three floats, each finite and greater than 0 (Yn need not be 1); it becomes the
+ * context's illuminant, which every later evaluation, rendering and search pass
+ * reads.  illum == NULL keeps the context's current illuminant: D65 (0.95047, 1,
+ * 1.0883) on a new context, else the one the last successful hq_set_image* /
+ * hq_set_image_reduced call left.  A component that is NaN, infinite, zero (either
+ * sign) or negative: HQ_ERR_ARG, hq_last_error names the component (illum[i]), and
+ * nothing of the context changes -- its image, illuminant, evaluated population and
+ * what the getters read stay, and a live search runs on.  The same holds for
+ * hq_set_image_shard, hq_set_image_planar_shard, the explicit illum of
+ * hq_set_image_reduced and hq_xyz_to_scielab. */
 int hq_set_image(hq_ctx *ctx, const float *rgba4, const float *lab4, int w, int h,
                  const float *illum);
 /* Row-block shard of a (w x h) image for multi-GPU evaluation:
@@ -646,7 +661,9 @@ int hq_reduce_weights(const uint8_t *src, int w, int h, int factor, int is_mask,
  * otherwise behaves as after hq_set_image(dst, reduced, NULL, rw, rh, illum): the
  * record of the last evaluation is dropped (the read-back rule), mask and weights are
  * dropped, LabRef is computed on the device under dst's own filters, and the reduced
- * image goes through the packed-form check.  illum NULL means src's.  Nothing of src
+ * image goes through the packed-form check.  illum NULL means src's; an illum with a
+ * component that is not finite and greater than 0 is HQ_ERR_ARG (hq_set_image's rule),
+ * before dst is touched.  Nothing of src
  * changes, what its getters may still read included.  Output pixel (X, Y) is made
  * from the block of hq_reduce_weights, n pixels, in one of two forms, each stated so
  * that numpy restates it bit for bit:
