@@ -11,32 +11,6 @@
 
 namespace hq {
 
-// Four consecutive indices of an index image, widened to 32 bits: one aligned
-// load of 4, 8 or 16 bytes.
-__device__ __forceinline__ uint4 load_idx4(const uint8_t* p) {
-    const uint32_t v = *reinterpret_cast<const uint32_t*>(p);
-    return make_uint4(v & 0xffu, (v >> 8) & 0xffu, (v >> 16) & 0xffu, v >> 24);
-}
-__device__ __forceinline__ uint4 load_idx4(const uint16_t* p) {
-    const uint2 v = *reinterpret_cast<const uint2*>(p);
-    return make_uint4(v.x & 0xffffu, v.x >> 16, v.y & 0xffffu, v.y >> 16);
-}
-__device__ __forceinline__ uint4 load_idx4(const uint32_t* p) { return *reinterpret_cast<const uint4*>(p); }
-
-// q(v) = RN(v 2^32), ties to even, for v in [0, 1]: v 2^32 is exact in fp32 (a
-// power-of-two scaling), already an integer from v = 2^-9 on, and at most 2^32,
-// which is the one value past 32 bits.
-__device__ __forceinline__ uint64_t unit_q32(float v) {
-    const float x = rintf(v * 4294967296.0f);
-    return x >= 4294967296.0f ? (1ull << 32) : (uint64_t)(uint32_t)x;
-}
-
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
 // ----------------------------------------------------------------------------
 // centroid: grid (nblocks * ceil(P/4)), block 256, XCD-relabelled.
 // ----------------------------------------------------------------------------
@@ -195,10 +169,10 @@ __global__ __launch_bounds__(256) void centroid_kernel(ClusterArgs a, int ngroup
             const bool same = k[0] == k0 && k[1] == k0 && k[2] == k0 && k[3] == k0;
             if (full && __builtin_amdgcn_ballot_w64(!same) == 0) {
                 if (!have) {
-                    wr = wave_sum(r[0] + r[1] + r[2] + r[3]);
-                    wg = wave_sum(g[0] + g[1] + g[2] + g[3]);
-                    wb = wave_sum(b[0] + b[1] + b[2] + b[3]);
-                    if constexpr (WGT) wn = wave_sum((uint64_t)(wt(0) + wt(1) + wt(2) + wt(3)));  // the wave's weight sum
+                    wr = wave_sum_u64(r[0] + r[1] + r[2] + r[3]);
+                    wg = wave_sum_u64(g[0] + g[1] + g[2] + g[3]);
+                    wb = wave_sum_u64(b[0] + b[1] + b[2] + b[3]);
+                    if constexpr (WGT) wn = wave_sum_u64((uint64_t)(wt(0) + wt(1) + wt(2) + wt(3)));  // the wave's weight sum
                     have = true;
                 }
                 if (lane == 0) add(pp, k0, wr, wg, wb, wn);

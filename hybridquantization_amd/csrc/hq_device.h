@@ -395,6 +395,34 @@ __device__ __forceinline__ V wave_sum(V v) {
     return v;
 }
 
+// ---- shared by the per-colour sums (hq_centroid.hip, hq_errsum.hip, hq_hist.hip) ----
+// The sum of a 64-bit integer over the wave, in every lane.
+__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+// Four consecutive indices of an index image, widened to 32 bits: one aligned
+// load of 4, 8 or 16 bytes.
+__device__ __forceinline__ uint4 load_idx4(const uint8_t* p) {
+    const uint32_t v = *reinterpret_cast<const uint32_t*>(p);
+    return make_uint4(v & 0xffu, (v >> 8) & 0xffu, (v >> 16) & 0xffu, v >> 24);
+}
+__device__ __forceinline__ uint4 load_idx4(const uint16_t* p) {
+    const uint2 v = *reinterpret_cast<const uint2*>(p);
+    return make_uint4(v.x & 0xffffu, v.x >> 16, v.y & 0xffffu, v.y >> 16);
+}
+__device__ __forceinline__ uint4 load_idx4(const uint32_t* p) { return *reinterpret_cast<const uint4*>(p); }
+
+// q(v) = RN(v 2^32), ties to even, for v in [0, 1]: v 2^32 is exact in fp32 (a
+// power-of-two scaling), already an integer from v = 2^-9 on, and at most 2^32,
+// which is the one value past 32 bits.
+__device__ __forceinline__ uint64_t unit_q32(float v) {
+    const float x = rintf(v * 4294967296.0f);
+    return x >= 4294967296.0f ? (1ull << 32) : (uint64_t)(uint32_t)x;
+}
+
 // Sum of a double over the wave with DPP moves only (no LDS round trips: the
 // __shfl_down tree above is 12 dependent ds_bpermute for an f64).  Fixed order:
 // row_shr 1, 2, 4, 8 leave each 16-lane row's sum in its lane 15; row_bcast 15

@@ -17,22 +17,6 @@ namespace hq {
 
 namespace {
 
-// Four consecutive indices of an index image, widened to 32 bits (hq_centroid.hip's loads).
-__device__ __forceinline__ uint4 err_idx4(const uint8_t* p) {
-    const uint32_t v = *reinterpret_cast<const uint32_t*>(p);
-    return make_uint4(v & 0xffu, (v >> 8) & 0xffu, (v >> 16) & 0xffu, v >> 24);
-}
-__device__ __forceinline__ uint4 err_idx4(const uint16_t* p) {
-    const uint2 v = *reinterpret_cast<const uint2*>(p);
-    return make_uint4(v.x & 0xffffu, v.x >> 16, v.y & 0xffffu, v.y >> 16);
-}
-__device__ __forceinline__ uint4 err_idx4(const uint32_t* p) { return *reinterpret_cast<const uint4*>(p); }
-
-__device__ __forceinline__ unsigned long long err_wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
 __device__ __forceinline__ unsigned long long err_wave_max(unsigned long long v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) {
@@ -125,7 +109,7 @@ __global__ __launch_bounds__(256) void cluster_err_kernel(ClusterErrArgs a, int 
         const uint32_t q = qa + 4u * min(j, nq - 1u);
         uint4 kq[4];
 #pragma unroll
-        for (int pp = 0; pp < 4; ++pp) kq[pp] = err_idx4(idx + (int64_t)(p0 + min(pp, ng - 1)) * a.idx_pitch + q);
+        for (int pp = 0; pp < 4; ++pp) kq[pp] = load_idx4(idx + (int64_t)(p0 + min(pp, ng - 1)) * a.idx_pitch + q);
         float pr[4], pg[4], pb[4];  // the pixels as the argmin saw them
         bool own[4];
         if constexpr (U8) {
@@ -199,7 +183,7 @@ __global__ __launch_bounds__(256) void cluster_err_kernel(ClusterErrArgs a, int 
                     sn += v[i] + ((unsigned long long)(own[i] ? 1 : 0) << 52);
                     km = key[i] > km ? key[i] : km;
                 }
-                sn = err_wave_sum(sn);
+                sn = wave_sum_u64(sn);
                 km = err_wave_max(km);
                 if (lane == 0 && (sn >> 52)) add(pp, k0, sn & ((1ull << 52) - 1ull), sn >> 52, km);
             } else {

@@ -582,27 +582,23 @@ int hq::enqueue_core(hq_ctx* c, int P, int K, ProfRec& pr, Pass pass) {
     CostArgs ca{};
     if (fast)
         if (int rc = cost_args(c, ga, f, K, so, Pl, &ca)) return rc;
-    const bool diffuse = dither && pass.diffuse_rows > 0;
     HIP_TRY(c, timed_launch(pr, dither ? kPDither : Pair(p0 + 1), [&] {
-        if (diffuse) {
+        if (dither) {
             const hq_diffusion_taps& tp = pass.taps;
             DiffuseArgs da{aa.R, aa.G, aa.B, ga.pal, aa.idx, ga.used_glob, c->d_dcarry.as<float>(), g.idx_pitch,
-                           g.W, g.H, K, c->dither_rows, pass.diffuse_rows, pass.diffuse_slope, pass.strength};
+                           g.W, g.H, K, c->dither_rows, pass.diffuse_rows, pass.diffuse_slope, pass.fs, pass.strength};
             da.w0[0] = (float)tp.w[0][3], da.w0[1] = (float)tp.w[0][4];
             for (int i = 0; i < 5; ++i) da.w1[i] = (float)tp.w[1][i], da.w2[i] = (float)tp.w[2][i];
             da.div = (float)tp.div;
             return launch_diffuse(da, Pl, s, &at);
         }
-        return dither ? launch_dither(DitherArgs{aa.R, aa.G, aa.B, ga.pal, aa.idx, ga.used_glob,
-                                                 c->d_dcarry.as<float>(), g.idx_pitch, g.W, g.H, K,
-                                                 c->dither_rows, pass.strength},
-                                      Pl, s, &at)
-               : n16  ? launch_assign16(aa, Pl, s, &at)
+        return n16  ? launch_assign16(aa, Pl, s, &at)
                : pass.ordered ? launch_assign_ordered(aa, Ps, s, &at)
                       : launch_assign(aa, Ps, s, &at);
     }));
     record_argmin(pi, at);
-    if (diffuse) pi.diffuse_rows = pass.diffuse_rows, pi.diffuse_slope = pass.diffuse_slope;
+    // (HQ_ARGMIN_DITHER, the Floyd-Steinberg formula, reports no instance)
+    if (dither && !pass.fs) pi.diffuse_rows = pass.diffuse_rows, pi.diffuse_slope = pass.diffuse_slope;
     if (costed) {
         pi.why_not_fast = why;
         if (int rc = enqueue_cost(c, ca, fast, f, lo, Pl, Pair(p0 + 2), pr, pi)) return rc;
@@ -678,7 +674,7 @@ int run_pass(hq_ctx* c, const float* palettes, int P, int K, const Pass& pass) {
     c->pal_generic = !fits;  // (before ensure_population: it sizes the generic path's scratch)
     if (int rc = ensure_population(c, P, K)) return rc;
     if (pass.kind == Pass::Dither)
-        HIP_TRY(c, c->d_dcarry.ensure(sizeof(float) * diffuse_carry_floats(P, std::max(pass.diffuse_rows, 1), c->g.W)));
+        HIP_TRY(c, c->d_dcarry.ensure(sizeof(float) * diffuse_carry_floats(P, pass.diffuse_rows, c->g.W)));
     hipStream_t s = c->stream;
     ProfRec pr = prof_begin(c);
     int rc = upload_and_prep(c, palettes, nullptr, P, K);
@@ -1163,8 +1159,9 @@ int hq_eval_population(hq_ctx* c, const float* palettes, int P, int K, float del
 
 namespace {
 
-// hq_dither_population, or with `taps` hq_diffuse_population (legal, and not Floyd-Steinberg's).
-int dither_population(hq_ctx* c, const float* palettes, int P, int K, const hq_diffusion_taps* taps,
+// hq_dither_population (the Floyd-Steinberg preset) and hq_diffuse_population (a caller's legal
+// taps).  Floyd-Steinberg's taps, whoever gives them, take its own formula (hq.h).
+int dither_population(hq_ctx* c, const float* palettes, int P, int K, const hq_diffusion_taps& taps,
                       float strength, float delta, double* costs, int32_t* used) {
     if (!palettes || !costs || P < 1 || K < 1) return fail(c, HQ_ERR_ARG, "bad palettes / costs / P=%d / K=%d", P, K);
     if (!(strength >= 0.0f && strength <= 1.0f)) return fail(c, HQ_ERR_ARG, "strength %g not in [0, 1]", strength);
@@ -1181,12 +1178,12 @@ int dither_population(hq_ctx* c, const float* palettes, int P, int K, const hq_d
     // once per image as the hybrid search's is (the packed 8-bit copy exists only for k/255 images)
     if (!c->img_u8 && (rc = require_unit_range_image(c, "image", "no error diffusion"))) return rc;
     // (the getters then answer for the dithered rendering)
-    Pass pass{Pass::Dither, strength};
-    if (taps) {
-        pass.taps = *taps;
-        if ((rc = hq_diffusion_classify(taps, &pass.diffuse_rows, &pass.diffuse_slope)))
-            return fail(c, HQ_ERR_ARG, "illegal diffusion taps");
-    }
+    Pass pass{Pass::Dither, strength, taps};
+    if ((rc = hq_diffusion_classify(&taps, &pass.diffuse_rows, &pass.diffuse_slope)))
+        return fail(c, HQ_ERR_ARG, "illegal diffusion taps");
+    hq_diffusion_taps fs;
+    hq_diffusion_preset(HQ_DIFFUSION_FLOYD_STEINBERG, &fs);
+    pass.fs = !std::memcmp(&fs, &taps, sizeof fs);
     if ((rc = run_pass(c, palettes, P, K, pass))) return rc;
     costs_from_hout(c, P, K, delta, costs, used);
     return HQ_OK;
@@ -1197,18 +1194,16 @@ int dither_population(hq_ctx* c, const float* palettes, int P, int K, const hq_d
 int hq_dither_population(hq_ctx* c, const float* palettes, int P, int K, float strength, float delta,
                          double* costs, int32_t* used) {
     if (!c) return HQ_ERR_ARG;
-    return dither_population(c, palettes, P, K, nullptr, strength, delta, costs, used);
+    hq_diffusion_taps fs;
+    hq_diffusion_preset(HQ_DIFFUSION_FLOYD_STEINBERG, &fs);
+    return dither_population(c, palettes, P, K, fs, strength, delta, costs, used);
 }
 
 int hq_diffuse_population(hq_ctx* c, const float* palettes, int P, int K, const hq_diffusion_taps* taps,
                           float strength, float delta, double* costs, int32_t* used) {
     if (!c) return HQ_ERR_ARG;
     if (!hq_diffusion_taps_legal(taps)) return fail(c, HQ_ERR_ARG, "null or illegal diffusion taps (hq.h)");
-    // Floyd-Steinberg's own taps: hq_dither_population's kernel and formula
-    hq_diffusion_taps fs;
-    hq_diffusion_preset(HQ_DIFFUSION_FLOYD_STEINBERG, &fs);
-    const bool is_fs = !std::memcmp(&fs, taps, sizeof fs);
-    return dither_population(c, palettes, P, K, is_fs ? nullptr : taps, strength, delta, costs, used);
+    return dither_population(c, palettes, P, K, *taps, strength, delta, costs, used);
 }
 
 int hq_get_indices(hq_ctx* c, int p, uint8_t* idx) {

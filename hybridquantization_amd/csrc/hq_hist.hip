@@ -13,18 +13,6 @@
 
 namespace hq {
 
-// q(v) = RN(v 2^32), ties to even, for v in [0, 1] (hq_centroid.hip's unit_q32)
-__device__ __forceinline__ uint64_t hist_q32(float v) {
-    const float x = rintf(v * 4294967296.0f);
-    return x >= 4294967296.0f ? (1ull << 32) : (uint64_t)(uint32_t)x;
-}
-
-__device__ __forceinline__ uint64_t hist_wave_sum(uint64_t v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
 // Cell coordinate of a channel value in [0, 1]: min(floor(v 2^bits), 2^bits - 1);
 // v 2^bits is exact in fp32 (a power-of-two scaling), at most 64.
 __device__ __forceinline__ uint32_t hist_coord(float v, int bits) {
@@ -125,7 +113,7 @@ __global__ __launch_bounds__(256) void hist_kernel(HistArgs a) {
                 ok[i] = own && fits;
                 if constexpr (MSK != 0) ok[i] = ok[i] && ((mq >> (8 * i)) & 0xffu) != 0u;
                 const float cr = fits ? vr[i] : 0.f, cg = fits ? vg[i] : 0.f, cb = fits ? vb[i] : 0.f;
-                r[i] = hist_q32(cr), g[i] = hist_q32(cg), b[i] = hist_q32(cb);
+                r[i] = unit_q32(cr), g[i] = unit_q32(cg), b[i] = unit_q32(cb);
                 if constexpr (MSK == 2) {  // (at most 255 2^32: exact)
                     wt[i] = (mq >> (8 * i)) & 0xffu;
                     r[i] *= wt[i], g[i] *= wt[i], b[i] *= wt[i];
@@ -138,12 +126,12 @@ __global__ __launch_bounds__(256) void hist_kernel(HistArgs a) {
         const uint32_t c0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)cell[0]);
         const bool same = cell[0] == c0 && cell[1] == c0 && cell[2] == c0 && cell[3] == c0;
         if (full && __builtin_amdgcn_ballot_w64(!same) == 0) {
-            const uint64_t wr = hist_wave_sum(r[0] + r[1] + r[2] + r[3]);
-            const uint64_t wg = hist_wave_sum(g[0] + g[1] + g[2] + g[3]);
-            const uint64_t wb = hist_wave_sum(b[0] + b[1] + b[2] + b[3]);
+            const uint64_t wr = wave_sum_u64(r[0] + r[1] + r[2] + r[3]);
+            const uint64_t wg = wave_sum_u64(g[0] + g[1] + g[2] + g[3]);
+            const uint64_t wb = wave_sum_u64(b[0] + b[1] + b[2] + b[3]);
             if (run_n && run_cell != c0) flush();
             run_cell = c0;
-            if constexpr (MSK == 2) run_n += hist_wave_sum(wt[0] + wt[1] + wt[2] + wt[3]);  // the wave's weight sum
+            if constexpr (MSK == 2) run_n += wave_sum_u64(wt[0] + wt[1] + wt[2] + wt[3]);  // the wave's weight sum
             else run_n += 256ull;
             run_r += wr, run_g += wg, run_b += wb;
         } else {

@@ -215,22 +215,6 @@ struct AssignArgs {
 };
 constexpr int kMaxMapSide = 64;  // threshold maps: up to 64 x 64 (hq_set_dither_map)
 
-// dither_kernel (hq_dither.hip): the Floyd-Steinberg index images of P palettes
-// of K <= 256 colours over the whole image, in the place of grid + assign.
-struct DitherArgs {
-    const float* R;         // planar, the whole image (row y at y W)
-    const float* G;
-    const float* B;
-    const float4* pal;      // [P][256] the prepared palettes (.w = 0)
-    uint8_t* idx;           // [P][idx_pitch]
-    uint32_t* used_glob;    // [kUsedSlots][used_stride]: slot 0 is written, the others zeroed before the launch
-    float* carry;           // [P][3][W] the errors of a strip's last row, for the next strip's first
-    int64_t idx_pitch;
-    int W, H, K;
-    int rows;               // rows per strip: a multiple of 64 in 64 .. 1024
-    float strength;         // s in [0, 1]
-};
-
 struct CostArgs {
     const uint8_t* idx;     // [P][idx_pitch]
     const uint4* opp16;     // [P][256] split opponent table (PaletteArgs::opp16)

@@ -122,8 +122,6 @@ int assign_residency_ordered(int NG);
 // hq_lists16.hip
 hipError_t launch_lists16_grid(const Lists16Args&, int P, hipStream_t);
 hipError_t launch_assign16(const AssignArgs&, int P, hipStream_t, AssignTag* tag = nullptr);
-// hq_dither.hip: one workgroup per palette
-hipError_t launch_dither(const DitherArgs&, int P, hipStream_t, AssignTag* tag = nullptr);
 // hq_wide.hip
 hipError_t launch_prep_wide(const WideArgs&, int P, hipStream_t);
 hipError_t launch_assign_wide(const WideArgs&, int P, hipStream_t, AssignTag* tag = nullptr);

@@ -127,7 +127,7 @@ enum Pair {
     kPGrid, kPAssign, kPCost, kPFinalize,  // the evaluation
     kPSaStep,                              // the SA step that generated its population
     kPComm,                                // its collective
-    kPDither,                              // dither_kernel in the place of grid + assign
+    kPDither,                              // diffuse_kernel in the place of grid + assign
     kPLloydGrid, kPLloydAssign,            // hybrid iteration: the assign-only pass,
     kPSums, kPLloydUpdate,                 // the sums kernel (also hq_cluster_sums'), the update kernel
     kPRepGrid, kPRepAssign, kPRepCost,     // repair iteration: the cost pass,
@@ -171,11 +171,10 @@ inline hipError_t timed_launch(ProfRec& pr, Pair p, F&& launch, bool start = tru
 // CostOnly (a repair iteration's first pass): grid, assign and cost -- the index
 //   images and, with option "pixel_err" in force, the error image the error kernel
 //   reads.
-// Dither (hq_dither_population): a full pass whose index images are the
-//   Floyd-Steinberg rendering at `strength` -- the counter set and the used bits
-//   zeroed as without a grid, then dither_kernel in the place of grid + assign;
-//   or (hq_diffuse_population) the rendering under the pass's diffusion taps, by
-//   diffuse_kernel in the same place and under the same profile stage.
+// Dither (hq_dither_population, hq_diffuse_population): a full pass whose index
+//   images are the error-diffused rendering under the pass's taps at `strength` --
+//   the counter set and the used bits zeroed as without a grid, then diffuse_kernel
+//   (hq_diffuse.hip) in the place of grid + assign.
 // Counter-set parity: each pass takes the other counter set than the last one
 // (build_grid zeroes it), so an accept step can read the last set while the next
 // is filled.  A side pass (AssignOnly, CostOnly: nothing reads its sums, so no
@@ -190,11 +189,13 @@ inline hipError_t timed_launch(ProfRec& pr, Pair p, F&& launch, bool start = tru
 struct Pass {
     enum Kind { Full, Fold, AssignOnly, CostOnly, Dither } kind = Full;
     float strength = 0.f;  // Dither
-    // Dither by hq_diffuse_population with a tap set that is not Floyd-Steinberg's: the
-    // instance <diffuse_rows, diffuse_slope> of diffuse_kernel (hq_diffuse.hip) in
-    // dither_kernel's place.  diffuse_rows 0: dither_kernel.
-    int diffuse_rows = 0, diffuse_slope = 0;
+    // Dither: the tap set (hq_dither_population: the Floyd-Steinberg preset), its instance
+    // <diffuse_rows, diffuse_slope> of diffuse_kernel (hq_diffusion_classify), and whether the
+    // taps are Floyd-Steinberg's, which take that kernel's own formula (hq.h) and report
+    // HQ_ARGMIN_DITHER with no instance.
     hq_diffusion_taps taps{};
+    int diffuse_rows = 0, diffuse_slope = 0;
+    bool fs = false;
     bool ordered = false;
     float amp[3] = {0.f, 0.f, 0.f};  // ordered: the amplitude per channel
     bool side() const { return kind == AssignOnly || kind == CostOnly; }
@@ -277,8 +278,7 @@ struct hq_ctx {
     int planar_ok = -1;
     hq::DevBuf d_hist;             // hq_color_histogram: [2^(3 bits)][4] int64 cells, then the range flag
     hq::DevBuf d_errstat, d_worst; // [P][K][4] u64 statistics, then the flag; [P][K] float4 worst pixels
-    hq::DevBuf d_dcarry;           // hq_dither_population: [P][3][W] errors of a strip's last row;
-                                   // hq_diffuse_population: [P][R][3][W], of its last R rows
+    hq::DevBuf d_dcarry;           // a Dither pass: [P][R][3][W] errors of a strip's last R rows (DiffuseArgs::carry)
     // ordered dithering: the threshold map (hq_set_dither_map; empty: the default, Bayer 16 x 16)
     // and its device copy, kMaxMapSide^2 floats made once by ensure_dither_map (its address is
     // in captured launches) and written by it whenever the host map has changed

@@ -16,7 +16,8 @@ from diffusion_ref import (POSITIONS, PRESET_CLASS, PRESETS, classify, diffuse, 
 from dither_ref import cube_corners, ramp_image
 from hybridquantization_amd import _lib
 
-EDGE_SHAPES = [(1, 5), (2, 3), (5, 1), (23, 17)]
+# (the last three: the GPU tests' images narrower than the tap window that cross a strip of 64 rows)
+EDGE_SHAPES = [(1, 5), (2, 3), (5, 1), (23, 17), (1, 130), (2, 129), (3, 66)]
 # twelve distinct weights, div = their sum + 3
 TWELVE = (np.array([[0, 0, 0, 11, 2], [7, 3, 12, 5, 1], [4, 9, 6, 10, 8]], np.int64), 81)
 

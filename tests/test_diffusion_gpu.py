@@ -1,7 +1,7 @@
 """GPU tests of error diffusion under other kernels than Floyd-Steinberg's (libhq's addition):
 hq_diffuse_population through the C ABI and its Python surface.  The index images and used flags
 are checked bit for bit against the numpy restatement (diffusion_ref.py; the Floyd-Steinberg tap
-set runs hq_dither_population's kernel and formula, so dither_ref.py restates it), the costs
+set runs hq_dither_population's kernel instance and formula, so dither_ref.py restates it), the costs
 against the oracle's cost of those indices at tests/test_gpu.py's 1e-5.
 """
 
@@ -170,10 +170,12 @@ def test_a_planar_float_image(ip):
 
 
 # strips of 64 rows: three with the last partial; a second strip of one row (both of its upper rows
-# from the carry); of two rows (one from the carry, one from the ring); strips of 64, 64 and 1 rows
-@pytest.mark.parametrize("w,h", [(70, 150), (40, 65), (40, 66), (40, 129)])
+# from the carry); of two rows (one from the carry, one from the ring); strips of 64, 64 and 1 rows;
+# and images narrower than the tap window across a strip (filters of half-width 0): the carry rows
+# have no column 1, or no column 2, for the pre-load and the first steps to read
+@pytest.mark.parametrize("w,h", [(70, 150), (40, 65), (40, 66), (40, 129), (1, 130), (2, 129), (3, 66)])
 def test_strips(gpu, w, h):
-    check_shape(gpu, w, h, 8, NAMED, dither_rows=64)
+    check_shape(gpu, w, h, 8, NAMED, fkey="caller0" if w < 4 else None, dither_rows=64)
 
 
 def both(m, pals, s, kernel):

@@ -1,5 +1,5 @@
-"""GPU tests of the dithered rendering (libhq's addition): hq_dither_population through the
-C ABI and its Python surface.  The index images and used flags are checked bit for bit
+"""GPU tests of the dithered rendering (libhq's addition): hq_dither_population (the
+Floyd-Steinberg instance of the error-diffusion kernel) through the C ABI and its Python surface.  The index images and used flags are checked bit for bit
 against the numpy restatement (dither_ref.py), the costs against the oracle's cost of those
 indices; strength 0 is the plain evaluation bit for bit.
 """
@@ -79,6 +79,14 @@ CASES = {
     "1x5": (1, 5, 6, "caller0", {}),                            # no left or right neighbour
     "2x3": (2, 3, 6, "caller0", {}),
     "5x1": (5, 1, 6, "caller0", {}),                            # no upper neighbour
+    # strips of 64 rows: a second strip of one row and of two, and one row past two strips
+    "40x65_k8_rows64": (40, 65, 8, None, {"dither_rows": 64}),
+    "40x66_k8_rows64": (40, 66, 8, None, {"dither_rows": 64}),
+    "40x129_k8_rows64": (40, 129, 8, None, {"dither_rows": 64}),
+    # narrower than the tap window and across a strip: the carry row has no column 1, or no column 2
+    "1x130_k8_rows64": (1, 130, 8, "caller0", {"dither_rows": 64}),
+    "2x129_k8_rows64": (2, 129, 8, "caller0", {"dither_rows": 64}),
+    "3x66_k8_rows64": (3, 66, 8, "caller0", {"dither_rows": 64}),
 }
 _REF = {}
 
