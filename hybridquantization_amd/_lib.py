@@ -62,6 +62,15 @@ DIFFUSION_PRESETS = ("floyd_steinberg", "jarvis", "stucki", "burkes", "sierra3",
                      "atkinson")
 
 
+class hq_dot_classes(C.Structure):
+    """include/hq.h's class matrix of dot diffusion: side n, cls[y n + x] a permutation of 0 .. n n - 1."""
+    _fields_ = [("n", C.c_int32), ("cls", C.c_int32 * 256)]
+
+
+# hq.h's enum hq_dot_matrix, in its order
+DOT_PRESETS = ("knuth8",)
+
+
 # the names of hq_path_info's kinds (hq.h's enums, in their order) and of hq_path_why's bits
 PATH_NAMES = {
     "pass_": ("none", "full", "assign_only", "dither"),
@@ -69,7 +78,8 @@ PATH_NAMES = {
     "previous_cost": ("none", "cost16w", "cost_mfma", "tiled_generic", "pixel_generic"),
     "pixels": ("none", "u8", "planar"),
     "grid": ("none", "build_grid", "lists16"),
-    "argmin": ("none", "assign_pipe", "assign_pipe_ordered", "assign16", "assign_wide", "dither", "diffuse"),
+    "argmin": ("none", "assign_pipe", "assign_pipe_ordered", "assign16", "assign_wide", "dither", "diffuse",
+               "dot"),
     "cost": ("none", "cost16w", "cost_mfma", "tiled_generic", "pixel_generic"),
     "cost_instance": ("plain", "masked", "weighted"),
     "gen_h": ("none", "gen_hpass", "gen_hrow", "gen_hrow4", "gen_hmfma"),
@@ -126,6 +136,11 @@ SIGNATURES = {
     "hq_diffusion_classify": (C.c_int, [C.POINTER(hq_diffusion_taps), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "hq_diffuse_population": (C.c_int, [_ctx, _f, C.c_int, C.c_int, C.POINTER(hq_diffusion_taps), C.c_float,
                                         C.c_float, _d, _i32]),
+    "hq_dot_preset": (C.c_int, [C.c_int, C.POINTER(hq_dot_classes)]),
+    "hq_dot_classes_legal": (C.c_int, [C.POINTER(hq_dot_classes)]),
+    "hq_dot_barons": (C.c_int, [C.POINTER(hq_dot_classes)]),
+    "hq_dot_population": (C.c_int, [_ctx, _f, C.c_int, C.c_int, C.POINTER(hq_dot_classes), C.c_float, C.c_float,
+                                    _d, _i32]),
     "hq_bayer_map": (C.c_int, [C.c_int, _f]),
     "hq_set_dither_map": (C.c_int, [_ctx, _f, C.c_int, C.c_int]),
     "hq_ordered_population": (C.c_int, [_ctx, _f, C.c_int, C.c_int, _f, C.c_float, _d, _i32]),

@@ -1,6 +1,7 @@
 // hq_diffuse.h -- the launcher of hq_diffuse.hip (the error-diffusion kernels of
 // hq_dither_population and hq_diffuse_population) and its arguments, for that unit and the
-// runtime.  A header of its own: no other kernel unit reads it.
+// runtime; and the argmin those kernels share with dot diffusion's (hq_dot.hip).  A header of
+// its own: no other kernel unit reads it.
 #pragma once
 
 #include "hq_launch.h"
@@ -37,5 +38,35 @@ struct DiffuseArgs {
 inline size_t diffuse_carry_floats(int P, int rows_up, int W) { return (size_t)P * rows_up * 3 * W; }
 
 hipError_t launch_diffuse(const DiffuseArgs&, int P, hipStream_t, AssignTag* tag = nullptr);
+
+#ifdef HQ_DIFFUSE_DEVICE
+// (the kernel units that render by diffusion, hq_diffuse.hip and hq_dot.hip, after hq_device.h)
+// The reference's first minimum over all K colours (CL:179-192).  Ranked by the
+// fma-chain d^2 as the plain assign kernels rank (dist2_rank: ref_len's own d^2
+// for w = 0); a runner-up within near_d2 of the best -- v_sqrt_f32 can give two
+// d^2 one distance, and then the lower index wins -- is re-resolved by the
+// reference loop itself.  v and the colours are finite: no NaN arises.
+__device__ __forceinline__ int diffuse_argmin(float r, float g, float b, const float4* s_pal, int K) {
+    float best2 = dist2_rank(r, g, b, s_pal[0]), second2 = INFINITY;
+    int bi = 0;
+#pragma unroll 4
+    for (int k = 1; k < K; ++k) {
+        const float d2 = dist2_rank(r, g, b, s_pal[k]);
+        const bool lt = d2 < best2;
+        bi = lt ? k : bi;
+        second2 = __builtin_amdgcn_fmed3f(best2, second2, d2);
+        best2 = lt ? d2 : best2;
+    }
+    if (near_d2(best2, second2)) {
+        bi = 0;
+        float best = ref_dist(r, g, b, s_pal[0]);
+        for (int k = 1; k < K; ++k) {
+            const float d = ref_dist(r, g, b, s_pal[k]);
+            if (d < best) { best = d; bi = k; }
+        }
+    }
+    return bi;
+}
+#endif
 
 }  // namespace hq

@@ -26,6 +26,7 @@
 //   t = ((7 e(x-1, y) + 3 e(x+1, y-1)) + (5 e(x, y-1) + e(x-1, y-1))) * 0.0625
 // with v, idx and e as above: the instance FS, of the same kernel.
 #include "hq_device.h"
+#define HQ_DIFFUSE_DEVICE
 #include "hq_diffuse.h"
 
 namespace hq {
@@ -48,32 +49,7 @@ __device__ __forceinline__ float4 load_quad(const float* row, int x, int W, bool
     return v;
 }
 
-// The reference's first minimum over all K colours (CL:179-192).  Ranked by the
-// fma-chain d^2 as the plain assign kernels rank (dist2_rank: ref_len's own d^2
-// for w = 0); a runner-up within near_d2 of the best -- v_sqrt_f32 can give two
-// d^2 one distance, and then the lower index wins -- is re-resolved by the
-// reference loop itself.  v and the colours are finite: no NaN arises.
-__device__ __forceinline__ int diffuse_argmin(float r, float g, float b, const float4* s_pal, int K) {
-    float best2 = dist2_rank(r, g, b, s_pal[0]), second2 = INFINITY;
-    int bi = 0;
-#pragma unroll 4
-    for (int k = 1; k < K; ++k) {
-        const float d2 = dist2_rank(r, g, b, s_pal[k]);
-        const bool lt = d2 < best2;
-        bi = lt ? k : bi;
-        second2 = __builtin_amdgcn_fmed3f(best2, second2, d2);
-        best2 = lt ? d2 : best2;
-    }
-    if (near_d2(best2, second2)) {
-        bi = 0;
-        float best = ref_dist(r, g, b, s_pal[0]);
-        for (int k = 1; k < K; ++k) {
-            const float d = ref_dist(r, g, b, s_pal[k]);
-            if (d < best) { best = d; bi = k; }
-        }
-    }
-    return bi;
-}
+// (the argmin, diffuse_argmin: hq_diffuse.h, shared with hq_dot.hip)
 
 // The diffusion step of one channel: the value the argmin reads.  e1, e2: e(x-1, y) and
 // e(x-2, y); u1[i], u2[i]: e(x + 2 - i, y-1) and e(x + 2 - i, y-2), the tap dx = i - 2.

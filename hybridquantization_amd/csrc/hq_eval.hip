@@ -1,11 +1,12 @@
 // hq_eval.hip -- libhq host runtime, evaluation: the population buffers, the pass
 // over a prepared population (enqueue_core, enqueue_wide, the generic cost), the
-// evaluation, dither, ordered-dither, index, sums, error and histogram entry points, and the two
-// improvement loops built on them (refine, repair).  Shared declarations:
+// evaluation, dither, dot-diffusion, ordered-dither, index, sums, error and histogram entry
+// points, and the two improvement loops built on them (refine, repair).  Shared declarations:
 // hq_runtime.h.
 #include <cmath>
 
 #include "hq_diffuse.h"
+#include "hq_dot.h"
 #include "hq_runtime.h"
 
 using namespace hq;
@@ -582,7 +583,14 @@ int hq::enqueue_core(hq_ctx* c, int P, int K, ProfRec& pr, Pass pass) {
     CostArgs ca{};
     if (fast)
         if (int rc = cost_args(c, ga, f, K, so, Pl, &ca)) return rc;
-    HIP_TRY(c, timed_launch(pr, dither ? kPDither : Pair(p0 + 1), [&] {
+    HIP_TRY(c, timed_launch(pr, pass.dot ? kPDot : dither ? kPDither : Pair(p0 + 1), [&] {
+        if (pass.dot) {
+            // (the matrix read on the host here is the one whose tables d_dottab holds: ensure_dot_tables)
+            DotArgs da{aa.R, aa.G, aa.B, ga.pal, aa.idx, ga.used_glob, c->d_doterr.as<float>(),
+                       c->d_dottab.as<uint32_t>(), c->dot_cls.cls, g.idx_pitch, used_stride(Ps), g.W, g.H, K,
+                       c->dot_cls.n, pass.strength};
+            return launch_dot(da, Pl, s, &at);
+        }
         if (dither) {
             const hq_diffusion_taps& tp = pass.taps;
             DiffuseArgs da{aa.R, aa.G, aa.B, ga.pal, aa.idx, ga.used_glob, c->d_dcarry.as<float>(), g.idx_pitch,
@@ -598,7 +606,7 @@ int hq::enqueue_core(hq_ctx* c, int P, int K, ProfRec& pr, Pass pass) {
     }));
     record_argmin(pi, at);
     // (HQ_ARGMIN_DITHER, the Floyd-Steinberg formula, reports no instance)
-    if (dither && !pass.fs) pi.diffuse_rows = pass.diffuse_rows, pi.diffuse_slope = pass.diffuse_slope;
+    if (dither && !pass.fs && !pass.dot) pi.diffuse_rows = pass.diffuse_rows, pi.diffuse_slope = pass.diffuse_slope;
     if (costed) {
         pi.why_not_fast = why;
         if (int rc = enqueue_cost(c, ca, fast, f, lo, Pl, Pair(p0 + 2), pr, pi)) return rc;
@@ -673,7 +681,9 @@ int run_pass(hq_ctx* c, const float* palettes, int P, int K, const Pass& pass) {
     c->nch_cur = c->chunked && fits && c->G2 > 0 && K > kMaxK && K <= kMaxKChunked ? chunk_count(K) : 1;
     c->pal_generic = !fits;  // (before ensure_population: it sizes the generic path's scratch)
     if (int rc = ensure_population(c, P, K)) return rc;
-    if (pass.kind == Pass::Dither)
+    if (pass.kind == Pass::Dither && pass.dot)
+        HIP_TRY(c, c->d_doterr.ensure(sizeof(float) * dot_err_floats(P, c->g.W, c->g.H)));
+    else if (pass.kind == Pass::Dither)
         HIP_TRY(c, c->d_dcarry.ensure(sizeof(float) * diffuse_carry_floats(P, pass.diffuse_rows, c->g.W)));
     hipStream_t s = c->stream;
     ProfRec pr = prof_begin(c);
@@ -1159,10 +1169,31 @@ int hq_eval_population(hq_ctx* c, const float* palettes, int P, int K, float del
 
 namespace {
 
-// hq_dither_population (the Floyd-Steinberg preset) and hq_diffuse_population (a caller's legal
-// taps).  Floyd-Steinberg's taps, whoever gives them, take its own formula (hq.h).
+// The tables of class matrix m on the device: the buffer once, its contents when m differs from
+// the matrix of the last call (c->dot_cls; compared over n and its n^2 entries).
+// (Nothing of this context is in flight: every entry point synchronises its stream.)
+int ensure_dot_tables(hq_ctx* c, const hq_dot_classes& m) {
+    if (int rc = bind(c)) return rc;
+    const bool had = c->d_dottab.p != nullptr;
+    HIP_TRY(c, c->d_dottab.ensure(sizeof(uint32_t) * 2 * kDotCells));
+    if (had && c->dot_cls.n == m.n && !std::memcmp(c->dot_cls.cls, m.cls, sizeof(int32_t) * m.n * m.n)) return HQ_OK;
+    uint32_t tab[2 * kDotCells];
+    dot_tables(m, tab, tab + kDotCells);
+    c->dot_cls.n = 0;  // (no matrix while the copy may fail)
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(c->d_dottab.p, tab, sizeof tab, hipMemcpyHostToDevice));
+    std::memset(&c->dot_cls, 0, sizeof c->dot_cls);
+    c->dot_cls.n = m.n;
+    std::memcpy(c->dot_cls.cls, m.cls, sizeof(int32_t) * m.n * m.n);
+    return HQ_OK;
+}
+
+// hq_dither_population (the Floyd-Steinberg preset), hq_diffuse_population (a caller's legal
+// taps) and hq_dot_population (dot: a legal class matrix in the place of the taps).
+// Floyd-Steinberg's taps, whoever gives them, take its own formula (hq.h).
 int dither_population(hq_ctx* c, const float* palettes, int P, int K, const hq_diffusion_taps& taps,
-                      float strength, float delta, double* costs, int32_t* used) {
+                      float strength, float delta, double* costs, int32_t* used,
+                      const hq_dot_classes* dot = nullptr) {
     if (!palettes || !costs || P < 1 || K < 1) return fail(c, HQ_ERR_ARG, "bad palettes / costs / P=%d / K=%d", P, K);
     if (!(strength >= 0.0f && strength <= 1.0f)) return fail(c, HQ_ERR_ARG, "strength %g not in [0, 1]", strength);
     if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
@@ -1179,6 +1210,16 @@ int dither_population(hq_ctx* c, const float* palettes, int P, int K, const hq_d
     if (!c->img_u8 && (rc = require_unit_range_image(c, "image", "no error diffusion"))) return rc;
     // (the getters then answer for the dithered rendering)
     Pass pass{Pass::Dither, strength, taps};
+    if (dot) {
+        if (P > kDotMaxP)
+            return fail(c, HQ_ERR_UNSUPPORTED, "P=%d > %d: a dot-diffusion launch holds the palettes in its grid's y", P,
+                        kDotMaxP);
+        if ((rc = ensure_dot_tables(c, *dot))) return rc;
+        pass.dot = true;
+        if ((rc = run_pass(c, palettes, P, K, pass))) return rc;
+        costs_from_hout(c, P, K, delta, costs, used);
+        return HQ_OK;
+    }
     if ((rc = hq_diffusion_classify(&taps, &pass.diffuse_rows, &pass.diffuse_slope)))
         return fail(c, HQ_ERR_ARG, "illegal diffusion taps");
     hq_diffusion_taps fs;
@@ -1204,6 +1245,16 @@ int hq_diffuse_population(hq_ctx* c, const float* palettes, int P, int K, const 
     if (!c) return HQ_ERR_ARG;
     if (!hq_diffusion_taps_legal(taps)) return fail(c, HQ_ERR_ARG, "null or illegal diffusion taps (hq.h)");
     return dither_population(c, palettes, P, K, *taps, strength, delta, costs, used);
+}
+
+int hq_dot_population(hq_ctx* c, const float* palettes, int P, int K, const hq_dot_classes* cls, float strength,
+                      float delta, double* costs, int32_t* used) {
+    if (!c) return HQ_ERR_ARG;
+    hq_dot_classes knuth;
+    hq_dot_preset(HQ_DOT_KNUTH8, &knuth);
+    if (cls && !hq_dot_classes_legal(cls))
+        return fail(c, HQ_ERR_ARG, "illegal class matrix: side 4, 8 or 16 and a permutation of 0 .. n*n - 1 (hq.h)");
+    return dither_population(c, palettes, P, K, hq_diffusion_taps{}, strength, delta, costs, used, cls ? cls : &knuth);
 }
 
 int hq_get_indices(hq_ctx* c, int p, uint8_t* idx) {

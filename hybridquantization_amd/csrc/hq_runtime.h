@@ -112,11 +112,11 @@ struct ProfSlot {
 
 enum Stage {
     kStGrid, kStAssign, kStCost, kStFinalize, kStSaStep, kStComm, kStCentroid, kStLloyd, kStHist, kStErrsum,
-    kStReseed, kStDither, kStReduce, kStages
+    kStReseed, kStDither, kStReduce, kStDot, kStages
 };
 inline constexpr const char* kStageNames[kStages] = {"grid", "assign", "cost", "finalize", "sa_step", "comm",
                                                      "centroid", "lloyd", "hist", "errsum", "reseed", "dither",
-                                                     "reduce"};
+                                                     "reduce", "dot"};
 
 // The start/stop event pairs of one evaluation (the context's EventSet) or of one
 // search iteration (kPairs pairs per iteration of a run in hq_search::pev).  A pass
@@ -134,12 +134,14 @@ enum Pair {
     kPErrsum, kPReseed,                    // the error kernels (also hq_cluster_errors'), the reseed kernel
     kPHist,                                // hq_color_histogram's kernel
     kPReduce,                              // hq_set_image_reduced's kernel
+    kPDot,                                 // dot_kernel's launches (one per class) in the place of grid + assign
     kPairs
 };
 // The stage each pair's time and launch count go to.
 inline constexpr Stage kPairStage[kPairs] = {kStGrid, kStAssign, kStCost, kStFinalize, kStSaStep, kStComm,
                                              kStDither, kStGrid, kStAssign, kStCentroid, kStLloyd, kStGrid,
-                                             kStAssign, kStCost, kStErrsum, kStReseed, kStHist, kStReduce};
+                                             kStAssign, kStCost, kStErrsum, kStReseed, kStHist, kStReduce,
+                                             kStDot};
 
 // One evaluation's or iteration's events and which pairs it recorded (events of an
 // earlier call may sit in the other slots, so only recorded pairs are accumulated).
@@ -174,7 +176,9 @@ inline hipError_t timed_launch(ProfRec& pr, Pair p, F&& launch, bool start = tru
 // Dither (hq_dither_population, hq_diffuse_population): a full pass whose index
 //   images are the error-diffused rendering under the pass's taps at `strength` --
 //   the counter set and the used bits zeroed as without a grid, then diffuse_kernel
-//   (hq_diffuse.hip) in the place of grid + assign.
+//   (hq_diffuse.hip) in the place of grid + assign.  With `dot` set (hq_dot_population) the
+//   rendering is dot diffusion's under the context's class matrix (c->dot_cls, its tables on
+//   the device: ensure_dot_tables): dot_kernel's launches (hq_dot.hip) in that place instead.
 // Counter-set parity: each pass takes the other counter set than the last one
 // (build_grid zeroes it), so an accept step can read the last set while the next
 // is filled.  A side pass (AssignOnly, CostOnly: nothing reads its sums, so no
@@ -196,6 +200,7 @@ struct Pass {
     hq_diffusion_taps taps{};
     int diffuse_rows = 0, diffuse_slope = 0;
     bool fs = false;
+    bool dot = false;  // Dither: dot diffusion (taps, diffuse_rows, diffuse_slope and fs unused)
     bool ordered = false;
     float amp[3] = {0.f, 0.f, 0.f};  // ordered: the amplitude per channel
     bool side() const { return kind == AssignOnly || kind == CostOnly; }
@@ -279,6 +284,11 @@ struct hq_ctx {
     hq::DevBuf d_hist;             // hq_color_histogram: [2^(3 bits)][4] int64 cells, then the range flag
     hq::DevBuf d_errstat, d_worst; // [P][K][4] u64 statistics, then the flag; [P][K] float4 worst pixels
     hq::DevBuf d_dcarry;           // a Dither pass: [P][R][3][W] errors of a strip's last R rows (DiffuseArgs::carry)
+    // dot diffusion: the class matrix of the last hq_dot_population (n = 0: none yet), its two
+    // per-cell tables on the device ([2][kDotCells] words, uploaded when the matrix changes:
+    // ensure_dot_tables) and the errors e of a Dot pass ([P][3][H][W] floats, never zeroed)
+    hq_dot_classes dot_cls{};
+    hq::DevBuf d_dottab, d_doterr;
     // ordered dithering: the threshold map (hq_set_dither_map; empty: the default, Bayer 16 x 16)
     // and its device copy, kMaxMapSide^2 floats made once by ensure_dither_map (its address is
     // in captured launches) and written by it whenever the host map has changed

@@ -366,6 +366,62 @@ class ImageManipulation:
         self.ditherError = float(costs[0])
         return table[self.getIndices(0)].reshape(-1)
 
+    # dot diffusion: libhq's addition (hq_dot_population, no reference counterpart)
+    @staticmethod
+    def diffusionClasses(which="knuth8"):
+        """hq_dot_preset: the class matrix ``which`` ("knuth8", Knuth's 8 x 8) -> int32 (n, n);
+        cls[y, x] is the class of the pixels (x mod n, y mod n)."""
+        if which not in _lib.DOT_PRESETS:
+            raise ValueError(f"class matrix {which!r}: one of {', '.join(_lib.DOT_PRESETS)}")
+        m = _lib.hq_dot_classes()
+        check(load().hq_dot_preset(_lib.DOT_PRESETS.index(which), C.byref(m)))
+        return np.array(m.cls[:m.n * m.n], np.int32).reshape(m.n, m.n)
+
+    @classmethod
+    def _classes(cls, classes):
+        """``classes=``: a preset's name or a square integer array -> hq_dot_classes (the
+        library judges whether it is legal)."""
+        a = cls.diffusionClasses(classes) if isinstance(classes, str) else np.asarray(classes)
+        if a.ndim != 2 or a.shape[0] != a.shape[1] or not 1 <= a.shape[0] <= 16 or not np.all(a == np.round(a)):
+            raise ValueError("classes: a preset name or a square integer array of side 4, 8 or 16")
+        if np.any(np.abs(a.astype(np.float64)) >= 2.0 ** 31):
+            raise ValueError("classes: 32-bit integers")
+        m = _lib.hq_dot_classes()
+        m.n = a.shape[0]
+        for i, v in enumerate(a.reshape(-1)):
+            m.cls[i] = int(v)
+        return m
+
+    def dotPopulation(self, colors, strength: float = 1.0, delta: float = 2.0, classes=None, return_used=False):
+        """computeQuantizationErrorPopulation of the dot-diffused rendering (Knuth's dot
+        diffusion, one parallel step per class) at ``strength`` in [0, 1] (0: the plain
+        evaluation, bit for bit): colors (P, 4K), K <= 256 -> costs (P,) [, used (P, K)].
+        ``classes``: the class matrix, a preset's name (diffusionClasses) or a square array of
+        side 4, 8 or 16 holding a permutation of 0 .. n*n - 1; None is Knuth's 8 x 8.
+        getIndices and getPixelErrors then answer for this rendering; clusterSums and
+        clusterErrors need a plain evaluation again."""
+        ctx = self._require()
+        m = None if classes is None else self._classes(classes)
+        pal = _f32(np.stack([np.asarray(c, np.float32).reshape(-1) for c in colors]))
+        P, K = pal.shape[0], pal.shape[1] // 4
+        costs = np.zeros(P, np.float64)
+        used = np.zeros((P, K), np.int32)
+        check(self._lib.hq_dot_population(ctx, fptr(pal), P, K, None if m is None else C.byref(m), float(strength),
+                                          float(delta), dptr(costs), iptr(used)), ctx)
+        return (costs, used) if return_used else costs
+
+    def quantizeDotDiffused(self, colors, strength: float = 1.0, classes=None):
+        """The dot-diffused rendering of the context's image with the palette colors float[4K],
+        in ``quantize``'s output format (quantizeDithered's way).  Sets ``lastUsedColors`` and
+        ``dotError``, the rendering's mean dE.  ``classes``: dotPopulation's."""
+        pal = _f32(colors).reshape(1, -1)
+        costs, used = self.dotPopulation(pal, strength, 0.0, classes=classes, return_used=True)
+        table = pal.reshape(-1, 4).copy()
+        table[:, 3] = 0.0
+        self.lastUsedColors = used[0]
+        self.dotError = float(costs[0])
+        return table[self.getIndices(0)].reshape(-1)
+
     # ordered dithering: libhq's addition (hq_ordered_population, no reference counterpart)
     @staticmethod
     def bayerMap(log2n: int):
@@ -601,7 +657,8 @@ class ImageManipulation:
                              iterations=None, stop=None, lloydSteps=0, lloydEvery=0,
                              init=None, initBits=5, repairEvery=0, repairMoves=-1, repairSteps=0,
                              dither=0.0, ditherSearch=False, ordered=None, orderedSearch=False, mask=None,
-                             weights=None, fixed=None, ditherKernel=None):
+                             weights=None, fixed=None, ditherKernel=None, dot=0.0, dotSearch=False,
+                             dotClasses=None):
         """Full SWASA search (IM:383-591) on the GPU; returns bestColors float[4K].
 
         ``simulatedAnnealing`` is a :class:`~hybridquantization_amd.swasa.SWASA`;
@@ -666,6 +723,13 @@ class ImageManipulation:
         front (n = K: no cut); the cut does not know about the fixed colours.  An array ``init``
         keeps its meaning, and its first n colours are overwritten by the library.
         ``ditherSearch`` goes through hq_swasa_search_host_fixed.
+        ``dot`` > 0 (hq_dot_population, a strength up to 1; not together with ``dither`` or
+        ``ordered``): the best palette is also evaluated in its dot-diffused rendering under
+        the class matrix ``dotClasses`` (dotPopulation's ``classes``; None is Knuth's 8 x 8):
+        ``bestErrorDot``; ``bestError`` stays the plain one.  ``dotSearch`` (needs ``dot`` > 0):
+        the search optimises the dot-diffused cost instead, host-driven through
+        hq_swasa_search_host_fixed exactly as ``ditherSearch`` is, with the same exclusions of
+        the k-means and repair moves; ``bestError`` and ``bestErrorDot`` are then both that cost.
         """
         ctx = self._require()
         fx = None if fixed is None else np.ascontiguousarray(fixed_colors(fixed, int(nbOfColors)))
@@ -676,7 +740,8 @@ class ImageManipulation:
             return self._findBestQuantization(
                 inlinergbOriginal, inlineScielabOriginal, w, nbOfColors, simulatedAnnealing, filters, absfilters,
                 illuminant, iterations, stop, lloydSteps, lloydEvery, init, initBits, repairEvery, repairMoves,
-                repairSteps, dither, ditherSearch, ordered, orderedSearch, mask, weights, fx, ditherKernel)
+                repairSteps, dither, ditherSearch, ordered, orderedSearch, mask, weights, fx, ditherKernel,
+                dot, dotSearch, dotClasses)
         finally:
             if before is not None:
                 self.setFixedColors(before)
@@ -684,7 +749,8 @@ class ImageManipulation:
     def _findBestQuantization(self, inlinergbOriginal, inlineScielabOriginal, w, nbOfColors, simulatedAnnealing,
                               filters, absfilters, illuminant, iterations, stop, lloydSteps, lloydEvery, init,
                               initBits, repairEvery, repairMoves, repairSteps, dither, ditherSearch, ordered,
-                              orderedSearch, mask, weights, fx, ditherKernel=None):
+                              orderedSearch, mask, weights, fx, ditherKernel=None, dot=0.0, dotSearch=False,
+                              dotClasses=None):
         """findBestQuantization's body; fx: the call's fixed colours (n, 4), already set on the
         context, or None (then whatever the context holds applies, as to any search)."""
         ctx = self._require()
@@ -711,6 +777,19 @@ class ImageManipulation:
             moves = dict(lloydEvery=lloydEvery, repairEvery=repairEvery, lloydSteps=lloydSteps, repairSteps=repairSteps)
             if any(int(v) != 0 for v in moves.values()):
                 raise ValueError("ditherSearch with " + ", ".join(k for k, v in moves.items() if int(v) != 0))
+        dot = float(dot)
+        if dotClasses is not None:
+            self._classes(dotClasses)  # (a bad one raises before anything runs)
+        if not 0.0 <= dot <= 1.0:
+            raise ValueError(f"dot={dot!r}: a strength in [0, 1]")
+        if dot > 0.0 and (dither > 0.0 or amp is not None):
+            raise ValueError("dot with dither or ordered: one rendering")
+        if dotSearch:
+            if not dot > 0.0:
+                raise ValueError("dotSearch needs dot > 0")
+            moves = dict(lloydEvery=lloydEvery, repairEvery=repairEvery, lloydSteps=lloydSteps, repairSteps=repairSteps)
+            if any(int(v) != 0 for v in moves.values()):
+                raise ValueError("dotSearch with " + ", ".join(k for k, v in moves.items() if int(v) != 0))
         if not self.openCLFiltersReady:
             self.updateOpenCLFilters(filters, absfilters)
         # Always upload (IM:450-478 does too): an identity cache keyed on id() can
@@ -734,14 +813,23 @@ class ImageManipulation:
             if K - nfx > 0:
                 cells, den = self.colorHistogram(int(initBits))
                 init[4 * nfx:], _ = self.medianCut(cells, int(initBits), den, K - nfx)
-        if ditherSearch:
+        if ditherSearch or dotSearch:
             P = params.population
             total = params.imax if iterations is None else min(int(iterations), params.imax)
+            if dotSearch:
+                def render(ps):
+                    return self.dotPopulation(ps.reshape(P, -1), dot, sw.delta, classes=dotClasses)
+            else:
+                def render(ps):
+                    return self.ditherPopulation(ps.reshape(P, -1), dither, sw.delta, kernel=ditherKernel)
             best, err, _ = sw.search_host(
-                K, lambda ps: self.ditherPopulation(ps.reshape(P, -1), dither, sw.delta, kernel=ditherKernel),
-                iterations=total,
+                K, render, iterations=total,
                 initial=None if init is None else initial_population(init, P, K), fixed=fx)
-            self.bestError = self.bestErrorDithered = err
+            self.bestError = err
+            if dotSearch:
+                self.bestErrorDot = err
+            else:
+                self.bestErrorDithered = err
             self.iterations = total
             if self.verbose:
                 print("Final error : %.5f" % err)
@@ -804,6 +892,10 @@ class ImageManipulation:
                                                                  kernel=ditherKernel)[0])
             if self.verbose:
                 print("Final error, dithered at strength %g : %.5f" % (dither, self.bestErrorDithered))
+        if dot > 0.0:
+            self.bestErrorDot = float(self.dotPopulation(best.reshape(1, -1), dot, sw.delta, classes=dotClasses)[0])
+            if self.verbose:
+                print("Final error, dot-diffused at strength %g : %.5f" % (dot, self.bestErrorDot))
         if amp is not None:
             self.bestErrorOrdered = (self.bestError if orderedSearch else
                                      float(self.orderedPopulation(best.reshape(1, -1), amp, sw.delta)[0]))

@@ -89,7 +89,8 @@ def makeChannels(inline):
 
 def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
                  whitepoint=Whitepoint.D65, verbose=False, device=0, iterations=None, dither=0.0,
-                 ordered=None, mask=None, weights=None, fixed=None, pyramid=None, ditherKernel=None):
+                 ordered=None, mask=None, weights=None, fixed=None, pyramid=None, ditherKernel=None,
+                 dot=0.0, dotClasses=None):
     """HQ:93-137 without the GUI: planar float image (3, N) in [0,1] ->
     (quantized planar image (3, N), bestColors float[4K], best error).  ``dither`` > 0
     (libhq's addition): the returned image is the best palette's Floyd-Steinberg rendering
@@ -107,10 +108,15 @@ def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
     ValueError before anything runs.  ``pyramid`` (pyramid.pyramidSearch's ``levels``: (factor,
     iterations) pairs with decreasing factors that end in 1): the search runs coarse to fine on
     a device-built image pyramid; the levels carry the iteration counts, so ``iterations`` must
-    then be None.  None is the plain search, untouched."""
+    then be None.  None is the plain search, untouched.  ``dot`` > 0 (not together with
+    ``dither`` or ``ordered``): the returned image is the best palette's dot-diffused rendering
+    at that strength (ImageManipulation.quantizeDotDiffused) under the class matrix
+    ``dotClasses`` (None: Knuth's 8 x 8)."""
     fixed_colors(fixed, int(nbOfColors))
     if ordered is not None and float(dither) > 0.0:
         raise ValueError("dither and ordered: one rendering")
+    if float(dot) > 0.0 and (ordered is not None or float(dither) > 0.0):
+        raise ValueError("dot with dither or ordered: one rendering")
     if pyramid is not None:
         from .pyramid import check_levels, pyramidSearch
         check_levels(pyramid)
@@ -122,15 +128,18 @@ def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
         if pyramid is not None:
             best = pyramidSearch(ip, inline_rgb, w, nbOfColors, swasa, dpi, viewingDistance, whitepoint,
                                  levels=pyramid, mask=mask, weights=weights, fixed=fixed)
-            q = (ip.quantizeOrdered(best, ordered) if ordered is not None else
+            q = (ip.quantizeDotDiffused(best, dot, classes=dotClasses) if float(dot) > 0.0 else
+                 ip.quantizeOrdered(best, ordered) if ordered is not None else
                  ip.quantizeDithered(best, dither, kernel=ditherKernel) if float(dither) > 0.0 else
                  ip.quantize(inline_rgb, best))
             return np.stack(makeChannels(q)), best, ip.bestError
         sp = ScielabProcessor(dpi, viewingDistance, whitepoint, None, ip)
         sc_img = sp.sRGBToScielab(image, w)
         best = sp.bestColors(inline_rgb, sc_img, w, nbOfColors, swasa, iterations=iterations, dither=dither,
-                             ditherKernel=ditherKernel, ordered=ordered, mask=mask, weights=weights, fixed=fixed)
-        q = (ip.quantizeOrdered(best, ordered) if ordered is not None else
+                             ditherKernel=ditherKernel, ordered=ordered, mask=mask, weights=weights, fixed=fixed,
+                             dot=dot, dotClasses=dotClasses)
+        q = (ip.quantizeDotDiffused(best, dot, classes=dotClasses) if float(dot) > 0.0 else
+             ip.quantizeOrdered(best, ordered) if ordered is not None else
              ip.quantizeDithered(best, dither, kernel=ditherKernel) if float(dither) > 0.0 else
              ip.quantize(inline_rgb, best))
         return np.stack(makeChannels(q)), best, ip.bestError

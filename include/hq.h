@@ -412,6 +412,71 @@ int hq_diffuse_population(hq_ctx *ctx, const float *palettes, int P, int K,
                           const hq_diffusion_taps *taps, float strength, float delta,
                           double *costs, int32_t *used);
 
+/* ---- dot diffusion: libhq's addition, no reference counterpart ----
+ * Knuth's dot diffusion (1987) is error diffusion without the raster recurrence.
+ * A class matrix of side n in {4, 8, 16}, tiled over the image, gives every pixel
+ * a class: cls[y*n + x] is a permutation of 0 .. n*n - 1 (anything else is
+ * illegal; entries past n*n are not read), and the class of pixel (x, y) is
+ * cls[(y mod n)*n + (x mod n)].  Pixels are taken in ascending class, and each
+ * hands its error only to those of its 8 neighbours that have a higher class.
+ * Two pixels of one class are at least n apart and share no neighbour, so a class
+ * is one parallel step over all its pixels: the device runs one launch per class,
+ * in ascending class on the context's stream (a class without a pixel -- the image
+ * is smaller than the tile -- gets none).
+ * The 8 neighbour offsets: the four orthogonal ones have weight wt = 2, the four
+ * diagonal ones wt = 1.  In the argmin's space (the pixel as hq_dither_population
+ * reads it), per channel, every operation one fp32 operation rounded to nearest and
+ * none contracted into an fma, s = strength:
+ *     W(p)   = the sum of the weights of p's neighbours that lie inside the image
+ *              and have a class above p's
+ *     a(q)   = +0, then, for q's in-image neighbours p of lower class, in ascending
+ *              class of p (they are pairwise distinct):
+ *                  a = a + (float(wt(p, q)) * e(p)) / float(W(p))   (IEEE division)
+ *     v      = min(max(pix(q) + s * a(q), 0), 1)
+ *     idx(q) = the first minimum over k of the argmin's distance(v, pal[k])
+ *     e(q)   = v - pal[idx]                 (pal[k].w taken as 0)
+ * A pixel with no in-image neighbour of higher class (a "baron", or a pixel an edge
+ * makes one) drops its error.  At strength 0 the indices, used flags and costs are
+ * hq_eval_population's, bit for bit.  A colour is used when it appears in the index
+ * image; the costs are this rendering's under the context's dE type, cost path,
+ * mask or weights, exactly as for hq_dither_population.
+ * HQ_DOT_KNUTH8 is Knuth's 8 x 8 class matrix, row by row:
+ *     34 48 40 32 29 15 23 31        28 14 22 30 35 49 41 33
+ *     42 58 56 53 21  5  7 10        20  4  6 11 43 59 57 52
+ *     50 62 61 45 13  1  2 18        12  0  3 19 51 63 60 44
+ *     38 46 54 37 25 17  9 26        24 16  8 27 39 47 55 36
+ * (rows 0 .. 3 on the left, 4 .. 7 on the right); tiled, it has 2 barons.
+ * Measured on one MI355X (profiles/dot_c3.json): the 64 launches take
+ * 2.89 ms at 4096 x 4096, K = 256 for one palette and 7.37 ms for four, against 338 ms
+ * for hq_dither_population's kernel in the same process; 0.36 against 2.41 ms at
+ * 512 x 512, K = 16.  On a 64 x 64 ramp under the eight cube corners the cost is 0.514
+ * of the nearest-colour one (Floyd-Steinberg 0.479).  Not measured: a search under
+ * this objective, more than one GPU (refused), K > 256 (refused). */
+typedef struct hq_dot_classes {
+    int32_t n;
+    int32_t cls[256];
+} hq_dot_classes;
+enum hq_dot_matrix { HQ_DOT_KNUTH8 = 0, HQ_DOT_COUNT = 1 };
+/* Fills *out with a built-in matrix (entries past n*n are 0).  HQ_ERR_ARG: a null
+ * out, an unknown preset. */
+int hq_dot_preset(int which, hq_dot_classes *out);
+/* 1 when the matrix is legal (above), else 0 (a null pointer included). */
+int hq_dot_classes_legal(const hq_dot_classes *cls);
+/* The number of cells whose 8 neighbours on the torus all have a lower class
+ * (informational); -1 for an illegal matrix. */
+int hq_dot_barons(const hq_dot_classes *cls);
+/* hq_dither_population with the dot-diffused rendering under *cls (NULL: the
+ * HQ_DOT_KNUTH8 matrix): its refusals, the state afterwards (the getters answer for
+ * the rendering, hq_cluster_sums and hq_cluster_errors return HQ_ERR_STATE until the
+ * next hq_eval_population[_partial]), its behaviour toward a live hq_search, a mask
+ * and weights, and in addition HQ_ERR_ARG for an illegal matrix and
+ * HQ_ERR_UNSUPPORTED for P > 65535 (a launch holds the palettes in its grid).  On any
+ * refusal the outputs and the evaluated state are untouched.  hq_last_path reports
+ * HQ_ARGMIN_DOT (diffuse_rows and diffuse_slope 0).  The matrix's tables are
+ * uploaded when it differs from the last call's. */
+int hq_dot_population(hq_ctx *ctx, const float *palettes, int P, int K, const hq_dot_classes *cls,
+                      float strength, float delta, double *costs, int32_t *used);
+
 /* ---- ordered dithering: libhq's addition, no reference counterpart ----
  * Error diffusion is a serial recurrence (one workgroup per palette); a threshold
  * map gives most of its S-CIELAB gain with every pixel independent, so it lives
@@ -915,7 +980,9 @@ int hq_profile_enable(hq_ctx *ctx, int on);
  * and "cost"), "dither" (hq_dither_population's and hq_diffuse_population's kernels, which stand in the place of "grid"
  * and "assign": a dithered evaluation counts nothing under those; an ordered evaluation's grid
  * and argmin count under "grid" and "assign" like the plain one's), "reduce" (hq_set_image_reduced's
- * kernel, on the destination context); returns total ms and launch
+ * kernel, on the destination context), "dot" (hq_dot_population's launches, one per class, in the
+ * place of "grid" and "assign": the time from the first one's start to the last one's end, counted
+ * as one launch per call); returns total ms and launch
  * count (HIP events on the context stream). */
 int hq_profile_get(hq_ctx *ctx, const char *kernel, double *total_ms, int64_t *launches);
 int hq_profile_reset(hq_ctx *ctx);
@@ -938,7 +1005,8 @@ enum hq_path_grid { HQ_GRID_NONE = 0, HQ_GRID_BUILD_GRID = 1, HQ_GRID_LISTS16 = 
 enum hq_path_argmin {
     HQ_ARGMIN_NONE = 0, HQ_ARGMIN_ASSIGN_PIPE = 1, HQ_ARGMIN_ASSIGN_PIPE_ORDERED = 2, HQ_ARGMIN_ASSIGN16 = 3,
     HQ_ARGMIN_ASSIGN_WIDE = 4, HQ_ARGMIN_DITHER = 5,
-    HQ_ARGMIN_DIFFUSE = 6    /* hq_diffuse_population's kernels (hq_diffuse.hip) */
+    HQ_ARGMIN_DIFFUSE = 6,   /* hq_diffuse_population's kernels (hq_diffuse.hip) */
+    HQ_ARGMIN_DOT = 7        /* hq_dot_population's kernel (hq_dot.hip), one launch per class */
 };
 enum hq_path_cost {
     HQ_COST_NONE = 0,        /* an assign-only pass, or a mask without a live tile */
