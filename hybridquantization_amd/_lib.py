@@ -141,6 +141,9 @@ SIGNATURES = {
     "hq_dot_barons": (C.c_int, [C.POINTER(hq_dot_classes)]),
     "hq_dot_population": (C.c_int, [_ctx, _f, C.c_int, C.c_int, C.POINTER(hq_dot_classes), C.c_float, C.c_float,
                                     _d, _i32]),
+    "hq_dot_reach": (C.c_int, [C.POINTER(hq_dot_classes), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "hq_dot_apron": (C.c_int, [_ctx, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "hq_dot_population_partial": (C.c_int, [_ctx, _f, C.c_int, C.c_int, C.POINTER(hq_dot_classes), C.c_float, _d]),
     "hq_bayer_map": (C.c_int, [C.c_int, _f]),
     "hq_set_dither_map": (C.c_int, [_ctx, _f, C.c_int, C.c_int]),
     "hq_ordered_population": (C.c_int, [_ctx, _f, C.c_int, C.c_int, _f, C.c_float, _d, _i32]),

@@ -56,10 +56,29 @@ struct DotArgs {
     int cx, cy, nx, ny;     // (set per launch) the class's cell and its pixels: columns, rows
 };
 
-// floats of DotArgs::err for P palettes
+// floats of DotArgs::err for P palettes (H: the rows rendered -- the image's, or a window's)
 inline size_t dot_err_floats(int P, int W, int H) { return (size_t)P * 3 * W * H; }
 
 hipError_t launch_dot(const DotArgs&, int P, hipStream_t, AssignTag* tag = nullptr);
+
+// dot_kernel's windowed instance (hq_dot_population_partial on a row-block shard): the launches
+// run over the full-image rows [a0, a1) only.  A pixel's class comes from its full-image row and
+// W(p)'s border rule from the full image's H (DotArgs::H), so the window's outer edge is not an
+// image border; a source outside the window contributes nothing and is never read.  Indices and
+// used bits are written for rows [e0, e1) alone -- the shard's extended rows, whose pixels
+// R, G, B and whose index images hold (row e0 first); the rows [a0, e0) and [e1, a1) are
+// rendered for their errors, their pixels among the apron planes' rows.  err is [P][3][a1 - a0][W].
+struct DotWinArgs : DotArgs {
+    const float* aR;        // the apron held: rows [h0, e0), then rows [e1, h1), W floats each
+    const float* aG;        // (null when it holds none)
+    const float* aB;
+    int h0, h1;             // h0 <= a0, a1 <= h1: the window may take less than is held
+    int a0, a1;             // 0 <= a0 <= e0 < e1 <= a1 <= H
+    int e0, e1;
+    int y0;                 // (set per launch) the class's first row in the window
+};
+
+hipError_t launch_dot_window(const DotWinArgs&, int P, hipStream_t, AssignTag* tag = nullptr);
 
 }  // namespace hq
 #endif

@@ -15,6 +15,8 @@
 // of a pixel has a lower class.  So one launch per class, in ascending class on the stream,
 // computes the definition: the stream's order is the only order between classes, and no
 // workgroup waits on another.
+#include <type_traits>
+
 #include "hq_device.h"
 #define HQ_DIFFUSE_DEVICE
 #include "hq_diffuse.h"
@@ -54,8 +56,14 @@ __device__ __forceinline__ int dot_weight_sum(uint32_t hi, int px, int py, int W
 //   the first launch).
 //   A source q + off(d) sends to q along 7 - d, whose weight is d's.  q is itself an in-image
 //   neighbour of higher class of every source it reads, so W >= wt >= 1.
+// WIN (DotWinArgs; hq_dot_population_partial on a shard): the class's pixels in the full-image
+//   rows [a0, a1) -- rows y0 + j n.  The error planes hold those rows (row a0 first).  A source
+//   must also lie in the window; its W is still the full image's (H is the image's).  The
+//   pixel comes from the shard's planes (rows [e0, e1)) or the apron's (the rows around them);
+//   only a row in [e0, e1) writes its index and its used bit.
 // ----------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void dot_kernel(DotArgs a) {
+template <bool WIN>
+__global__ __launch_bounds__(256) void dot_kernel(std::conditional_t<WIN, DotWinArgs, DotArgs> a) {
 #pragma clang fp contract(off)
     __shared__ __attribute__((aligned(16))) float4 s_pal[kMaxK];
     __shared__ uint32_t s_used[8];
@@ -67,8 +75,12 @@ __global__ __launch_bounds__(256) void dot_kernel(DotArgs a) {
     const int t = blockIdx.x * 256 + tid;
     if (t < a.nx * a.ny) {
         const int j = t / a.nx, i = t - j * a.nx;
-        const int x = a.cx + i * n, y = a.cy + j * n;  // inside the image by nx, ny
-        const int64_t plane = (int64_t)W * H, q = (int64_t)y * W + x;
+        // (x, y): the position in the full image; yb, rows: the first row and the rows of the error planes
+        const int x = a.cx + i * n;  // inside the image (the window) by nx, ny
+        int y, yb, rows;
+        if constexpr (WIN) y = a.y0 + j * n, yb = a.a0, rows = a.a1 - a.a0;
+        else y = a.cy + j * n, yb = 0, rows = H;
+        const int64_t plane = (int64_t)W * rows, q = (int64_t)(y - yb) * W + x;
         const float* err = a.err + (int64_t)p * 3 * plane;
         const uint32_t low = a.tab[a.cy * n + a.cx];
         float acc[3] = {0.f, 0.f, 0.f};
@@ -78,17 +90,31 @@ __global__ __launch_bounds__(256) void dot_kernel(DotArgs a) {
             const int dx = dot_dx((int)d), dy = dot_dy((int)d);
             const int px = x + dx, py = y + dy;
             if (!inside(px, py, W, H)) continue;
+            if constexpr (WIN)
+                if (py < a.a0 || py >= a.a1) continue;
             const uint32_t hi = a.tab[kDotCells + ((a.cy + dy) & (n - 1)) * n + ((a.cx + dx) & (n - 1))];
             const float wsum = (float)dot_weight_sum(hi, px, py, W, H);
             const float wt = (float)dot_weight((int)d);
-            const int64_t src = (int64_t)py * W + px;
+            const int64_t src = (int64_t)(py - yb) * W + px;
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) {
                 const float prod = wt * err[ch * plane + src];
                 acc[ch] = acc[ch] + prod / wsum;
             }
         }
-        const float pix[3] = {a.R[q], a.G[q], a.B[q]};
+        float pix[3];
+        bool keep = true;  // this row's index and used bit are written
+        if constexpr (WIN) {
+            keep = y >= a.e0 && y < a.e1;
+            // the apron's rows: those held above the shard's (from row h0), then those below
+            const int64_t ap = ((int64_t)(y < a.e0 ? y - a.h0 : a.e0 - a.h0 + y - a.e1)) * W + x;
+            const int64_t in = (int64_t)(y - a.e0) * W + x;
+            pix[0] = *(keep ? a.R + in : a.aR + ap);  // (one address, one load)
+            pix[1] = *(keep ? a.G + in : a.aG + ap);
+            pix[2] = *(keep ? a.B + in : a.aB + ap);
+        } else {
+            pix[0] = a.R[q], pix[1] = a.G[q], pix[2] = a.B[q];
+        }
         float v[3];
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
@@ -101,50 +127,97 @@ __global__ __launch_bounds__(256) void dot_kernel(DotArgs a) {
         out[0] = v[0] - c.x;
         out[plane] = v[1] - c.y;
         out[2 * plane] = v[2] - c.z;
-        a.idx[(int64_t)p * a.idx_pitch + q] = (uint8_t)k;
-        atomicOr(&s_used[k >> 5], 1u << (k & 31));
+        if constexpr (WIN) {
+            if (keep) {
+                a.idx[(int64_t)p * a.idx_pitch + (int64_t)(y - a.e0) * W + x] = (uint8_t)k;
+                atomicOr(&s_used[k >> 5], 1u << (k & 31));
+            }
+        } else {
+            a.idx[(int64_t)p * a.idx_pitch + q] = (uint8_t)k;
+            atomicOr(&s_used[k >> 5], 1u << (k & 31));
+        }
     }
     __syncthreads();
     if (tid < 8 && s_used[tid])
         atomicOr(&a.used_glob[(blockIdx.x & (kUsedSlots - 1)) * a.used_stride + p * 8 + tid], s_used[tid]);
 }
 
-// The launches of one call: the classes 0 .. n^2 - 1 in ascending order, each over the pixels its
-// cell has in the image; a class without one (the image is smaller than the tile) gets no launch
-// -- a zero-sized grid is an error.  The pending profiling events bracket the whole chain: start
-// on the first launch, stop on the last.
-hipError_t launch_dot(const DotArgs& a0, int P, hipStream_t s, AssignTag* tag) {
-    const int n = a0.n, cells = n * n;
-    if ((n != 4 && n != 8 && n != 16) || a0.K < 1 || a0.K > kMaxK || a0.W < 1 || a0.H < 1 || P < 1 || P > kDotMaxP ||
-        !a0.cls || !a0.tab || !a0.err || (int64_t)a0.W * a0.H > INT32_MAX)  // (a class's pixel count fits an int)
-        return hipErrorInvalidValue;
-    int cell_of[kDotCells];
+namespace {
+
+// What both launchers refuse, and the matrix's cells by class (cell_of[k] = cy n + cx).
+bool dot_cells(const DotArgs& a, int P, int rows, int* cell_of) {
+    const int n = a.n, cells = n * n;
+    if ((n != 4 && n != 8 && n != 16) || a.K < 1 || a.K > kMaxK || a.W < 1 || rows < 1 || P < 1 || P > kDotMaxP ||
+        !a.cls || !a.tab || !a.err || (int64_t)a.W * rows > INT32_MAX)  // (a class's pixel count fits an int)
+        return false;
     for (int c = 0; c < cells; ++c) cell_of[c] = -1;
     for (int c = 0; c < cells; ++c) {
-        if (a0.cls[c] < 0 || a0.cls[c] >= cells || cell_of[a0.cls[c]] >= 0) return hipErrorInvalidValue;
-        cell_of[a0.cls[c]] = c;
+        if (a.cls[c] < 0 || a.cls[c] >= cells || cell_of[a.cls[c]] >= 0) return false;
+        cell_of[a.cls[c]] = c;
     }
-    // the classes with a pixel: cell (cx, cy) has one when cx < W and cy < H
+    return true;
+}
+
+// The launches of one call: the classes 0 .. n^2 - 1 in ascending order, each over the pixels
+// place(args, cell) says it has (false: none, and no launch -- a zero-sized grid is an error).
+// The pending profiling events bracket the whole chain: start on the first launch, stop on the
+// last.
+template <bool WIN, typename Args, typename Place>
+hipError_t launch_classes(const Args& a0, const int* cell_of, int P, hipStream_t s, AssignTag* tag, Place&& place) {
+    const int cells = a0.n * a0.n;
+    Args a = a0;
     int first = -1, last = -1;
     for (int k = 0; k < cells; ++k)
-        if (cell_of[k] % n < a0.W && cell_of[k] / n < a0.H) {
+        if (place(a, cell_of[k])) {
             if (first < 0) first = k;
             last = k;
         }
     const hipEvent_t start = t_ev_start, stop = t_ev_stop;
-    DotArgs a = a0;
     for (int k = 0; k < cells; ++k) {
-        a.cx = cell_of[k] % n, a.cy = cell_of[k] / n;
-        if (a.cx >= a.W || a.cy >= a.H) continue;
-        a.nx = (a.W - a.cx + n - 1) / n, a.ny = (a.H - a.cy + n - 1) / n;
+        if (!place(a, cell_of[k])) continue;
         t_ev_start = k == first ? start : nullptr;
         t_ev_stop = k == last ? stop : nullptr;
-        HQ_LAUNCH(dot_kernel, dim3(blocks_for((int64_t)a.nx * a.ny), P), dim3(256), 0, s, a);
+        HQ_LAUNCH(dot_kernel<WIN>, dim3(blocks_for((int64_t)a.nx * a.ny), P), dim3(256), 0, s, a);
     }
     t_ev_start = start, t_ev_stop = stop;
     // hq.h's hq_path_argmin: HQ_ARGMIN_DOT (the planar floats, always)
     if (tag) *tag = AssignTag{7, 0, 0, 0};
     return hipGetLastError();
+}
+
+}  // namespace
+
+// The whole image: cell (cx, cy) has a pixel when cx < W and cy < H (else the image is smaller
+// than the tile).
+hipError_t launch_dot(const DotArgs& a0, int P, hipStream_t s, AssignTag* tag) {
+    int cell_of[kDotCells];
+    if (!dot_cells(a0, P, a0.H, cell_of)) return hipErrorInvalidValue;
+    return launch_classes<false>(a0, cell_of, P, s, tag, [](DotArgs& a, int cell) {
+        const int n = a.n;
+        a.cx = cell % n, a.cy = cell / n;
+        if (a.cx >= a.W || a.cy >= a.H) return false;
+        a.nx = (a.W - a.cx + n - 1) / n, a.ny = (a.H - a.cy + n - 1) / n;
+        return true;
+    });
+}
+
+// A window: cell (cx, cy)'s rows are the full-image rows y = cy (mod n) of [a0, a1) -- a0 is
+// generally no multiple of n, so y0 is counted from it.
+hipError_t launch_dot_window(const DotWinArgs& a0, int P, hipStream_t s, AssignTag* tag) {
+    int cell_of[kDotCells];
+    if (!(0 <= a0.a0 && a0.a0 <= a0.e0 && a0.e0 < a0.e1 && a0.e1 <= a0.a1 && a0.a1 <= a0.H) ||
+        !(a0.h0 <= a0.a0 && a0.a1 <= a0.h1) ||  // (the window's rows are held)
+        ((a0.a0 < a0.e0 || a0.e1 < a0.a1) && (!a0.aR || !a0.aG || !a0.aB)) ||
+        !dot_cells(a0, P, a0.a1 - a0.a0, cell_of))
+        return hipErrorInvalidValue;
+    return launch_classes<true>(a0, cell_of, P, s, tag, [](DotWinArgs& a, int cell) {
+        const int n = a.n;
+        a.cx = cell % n, a.cy = cell / n;
+        a.y0 = a.a0 + ((a.cy - a.a0) % n + n) % n;
+        if (a.cx >= a.W || a.y0 >= a.a1) return false;
+        a.nx = (a.W - a.cx + n - 1) / n, a.ny = (a.a1 - a.y0 + n - 1) / n;
+        return true;
+    });
 }
 
 }  // namespace hq

@@ -1,5 +1,7 @@
 // hq_dot_classes.cpp -- the class matrices of hq_dot_population (hq.h): the preset, the legality
-// rule, the baron count and the two per-cell tables the kernel reads (hq_dot.h, hq_dot.hip).
+// rule, the baron count, the reach (how many rows above and below a pixel its sources lie: what a
+// row-block shard renders beyond its own rows, hq_dot_population_partial) and the two per-cell
+// tables the kernel reads (hq_dot.h, hq_dot.hip).
 // Host code only; links alone into a CPU program (dot_check.cpp).
 #include <algorithm>
 #include <cstdint>
@@ -82,6 +84,32 @@ int hq_dot_barons(const hq_dot_classes* m) {
     int barons = 0;
     for (int i = 0; i < m->n * m->n; ++i) barons += higher[i] == 0;
     return barons;
+}
+
+// A pixel's index depends on the pixels a path of neighbour steps with strictly descending class
+// reaches from it.  The matrix is periodic, so the longest such path's extent up and down is a
+// property of the cells: in ascending class each cell takes the larger of what it has and what
+// each lower neighbour p, dy rows away, brings -- p's own extent shifted by dy.
+int hq_dot_reach(const hq_dot_classes* m, int* above, int* below) {
+    if (!above || !below || !hq_dot_classes_legal(m)) return HQ_ERR_ARG;
+    const int n = m->n, cells = n * n;
+    int cell_of[hq::kDotCells], up[hq::kDotCells] = {}, down[hq::kDotCells] = {};
+    for (int c = 0; c < cells; ++c) cell_of[m->cls[c]] = c;
+    int a = 0, b = 0;
+    for (int k = 0; k < cells; ++k) {
+        const int c = cell_of[k], cx = c % n, cy = c / n;
+        for (int d = 0; d < 8; ++d) {
+            const int dy = hq::dot_dy(d), p = (cy + dy + n) % n * n + (cx + hq::dot_dx(d) + n) % n;
+            if (m->cls[p] >= k) continue;
+            up[c] = std::max(up[c], up[p] - dy);
+            down[c] = std::max(down[c], down[p] + dy);
+        }
+        a = std::max(a, up[c]);
+        b = std::max(b, down[c]);
+    }
+    *above = a;
+    *below = b;
+    return HQ_OK;
 }
 
 }  // extern "C"

@@ -589,7 +589,16 @@ int hq::enqueue_core(hq_ctx* c, int P, int K, ProfRec& pr, Pass pass) {
             DotArgs da{aa.R, aa.G, aa.B, ga.pal, aa.idx, ga.used_glob, c->d_doterr.as<float>(),
                        c->d_dottab.as<uint32_t>(), c->dot_cls.cls, g.idx_pitch, used_stride(Ps), g.W, g.H, K,
                        c->dot_cls.n, pass.strength};
-            return launch_dot(da, Pl, s, &at);
+            if (whole_image(c)) return launch_dot(da, Pl, s, &at);
+            // a row-block shard: the window's rows, the apron's planes from the row it holds first
+            DotWinArgs wa{};
+            static_cast<DotArgs&>(wa) = da;
+            const int64_t aplane = (int64_t)(c->apron_above + c->apron_below) * g.W;
+            const float* ap = c->d_apron.as<float>();
+            wa.a0 = pass.dot_a0, wa.a1 = pass.dot_a1, wa.e0 = g.e0, wa.e1 = g.e1;
+            wa.h0 = g.e0 - c->apron_above, wa.h1 = g.e1 + c->apron_below;
+            wa.aR = ap, wa.aG = ap ? ap + aplane : nullptr, wa.aB = ap ? ap + 2 * aplane : nullptr;
+            return launch_dot_window(wa, Pl, s, &at);
         }
         if (dither) {
             const hq_diffusion_taps& tp = pass.taps;
@@ -681,8 +690,9 @@ int run_pass(hq_ctx* c, const float* palettes, int P, int K, const Pass& pass) {
     c->nch_cur = c->chunked && fits && c->G2 > 0 && K > kMaxK && K <= kMaxKChunked ? chunk_count(K) : 1;
     c->pal_generic = !fits;  // (before ensure_population: it sizes the generic path's scratch)
     if (int rc = ensure_population(c, P, K)) return rc;
-    if (pass.kind == Pass::Dither && pass.dot)
-        HIP_TRY(c, c->d_doterr.ensure(sizeof(float) * dot_err_floats(P, c->g.W, c->g.H)));
+    if (pass.kind == Pass::Dither && pass.dot)  // (the rows rendered: the image's, or a shard's window's)
+        HIP_TRY(c, c->d_doterr.ensure(sizeof(float) * dot_err_floats(P, c->g.W, whole_image(c) ? c->g.H
+                                                                                   : pass.dot_a1 - pass.dot_a0)));
     else if (pass.kind == Pass::Dither)
         HIP_TRY(c, c->d_dcarry.ensure(sizeof(float) * diffuse_carry_floats(P, pass.diffuse_rows, c->g.W)));
     hipStream_t s = c->stream;
@@ -1188,16 +1198,47 @@ int ensure_dot_tables(hq_ctx* c, const hq_dot_classes& m) {
     return HQ_OK;
 }
 
+// hq_dot_population_partial's scope and window.  A palette slice and a communicator of more than
+// one rank are refused as hq_dot_population refuses them; a row-block shard is served when the
+// apron it holds covers, on each side, the reach of matrix m or all the rows up to the image's
+// border.  [*a0, *a1): the rows to render -- the extended rows and the apron rows needed (a whole
+// image: all its rows, the whole-image launches).
+int dot_window(hq_ctx* c, const hq_dot_classes& m, int* a0, int* a1) {
+    const char* const what = "hq_dot_population_partial";
+    if (c->comm && c->nranks > 1)
+        return fail(c, HQ_ERR_UNSUPPORTED, "%s with a communicator of %d ranks: add the ranks' partials yourself", what,
+                    c->nranks);
+    if (c->psplit || c->slice_ranks > 1) return fail(c, HQ_ERR_UNSUPPORTED, "%s on a palette slice", what);
+    const Geom& g = c->g;
+    *a0 = g.e0, *a1 = g.e1;
+    if (whole_image(c)) return HQ_OK;
+    int above = 0, below = 0;
+    if (hq_dot_reach(&m, &above, &below)) return fail(c, HQ_ERR_ARG, "illegal class matrix");
+    const int need_a = std::min(above, g.e0), need_b = std::min(below, g.H - g.e1);
+    if (c->apron_above < need_a || c->apron_below < need_b)
+        return fail(c, HQ_ERR_STATE, "%s on rows [%d, %d) of %d: the class matrix reaches %d rows above and %d below, "
+                                     "so %d and %d rows are needed beyond the extended rows [%d, %d) and %d and %d are "
+                                     "held (option dot_apron before hq_set_image_shard)",
+                    what, g.r0, g.r1, g.H, above, below, need_a, need_b, g.e0, g.e1, c->apron_above, c->apron_below);
+    *a0 = g.e0 - need_a, *a1 = g.e1 + need_b;
+    return HQ_OK;
+}
+
 // hq_dither_population (the Floyd-Steinberg preset), hq_diffuse_population (a caller's legal
 // taps) and hq_dot_population (dot: a legal class matrix in the place of the taps).
 // Floyd-Steinberg's taps, whoever gives them, take its own formula (hq.h).
+// hq_dot_population_partial (dot and partial: the [P][1 + K] rows in the place of costs and used)
+// also serves a row-block shard, over the window dot_window finds.
 int dither_population(hq_ctx* c, const float* palettes, int P, int K, const hq_diffusion_taps& taps,
                       float strength, float delta, double* costs, int32_t* used,
-                      const hq_dot_classes* dot = nullptr) {
-    if (!palettes || !costs || P < 1 || K < 1) return fail(c, HQ_ERR_ARG, "bad palettes / costs / P=%d / K=%d", P, K);
+                      const hq_dot_classes* dot = nullptr, double* partial = nullptr) {
+    if (!palettes || !(costs || partial) || P < 1 || K < 1)
+        return fail(c, HQ_ERR_ARG, "bad palettes / %s / P=%d / K=%d", partial ? "partial" : "costs", P, K);
     if (!(strength >= 0.0f && strength <= 1.0f)) return fail(c, HQ_ERR_ARG, "strength %g not in [0, 1]", strength);
     if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
-    int rc = whole_image_only(c, "hq_dither_population (error diffusion)");
+    int rc, a0 = 0, a1 = 0;
+    if (partial) rc = dot_window(c, *dot, &a0, &a1);
+    else rc = whole_image_only(c, "hq_dither_population (error diffusion)");
     if (rc) return rc;
     if ((rc = mask_scope(c))) return rc;
     if (K > kMaxK)
@@ -1208,6 +1249,10 @@ int dither_population(hq_ctx* c, const float* palettes, int P, int K, const hq_d
     // the errors stay bounded (|e| <= 1) for pixels in [0, 1]: a property of the image, established
     // once per image as the hybrid search's is (the packed 8-bit copy exists only for k/255 images)
     if (!c->img_u8 && (rc = require_unit_range_image(c, "image", "no error diffusion"))) return rc;
+    // ... and of the rows a shard renders beyond its owned ones (found on the host with the apron)
+    if (partial && !c->apron_ok)
+        return fail(c, HQ_ERR_UNSUPPORTED, "image with a pixel outside [0, 1] or not finite in the rows held around "
+                                           "the owned ones: no error diffusion");
     // (the getters then answer for the dithered rendering)
     Pass pass{Pass::Dither, strength, taps};
     if (dot) {
@@ -1216,8 +1261,10 @@ int dither_population(hq_ctx* c, const float* palettes, int P, int K, const hq_d
                         kDotMaxP);
         if ((rc = ensure_dot_tables(c, *dot))) return rc;
         pass.dot = true;
+        pass.dot_a0 = a0, pass.dot_a1 = a1;
         if ((rc = run_pass(c, palettes, P, K, pass))) return rc;
-        costs_from_hout(c, P, K, delta, costs, used);
+        if (partial) std::memcpy(partial, c->h_out.p, sizeof(double) * (size_t)P * (1 + K));
+        else costs_from_hout(c, P, K, delta, costs, used);
         return HQ_OK;
     }
     if ((rc = hq_diffusion_classify(&taps, &pass.diffuse_rows, &pass.diffuse_slope)))
@@ -1255,6 +1302,18 @@ int hq_dot_population(hq_ctx* c, const float* palettes, int P, int K, const hq_d
     if (cls && !hq_dot_classes_legal(cls))
         return fail(c, HQ_ERR_ARG, "illegal class matrix: side 4, 8 or 16 and a permutation of 0 .. n*n - 1 (hq.h)");
     return dither_population(c, palettes, P, K, hq_diffusion_taps{}, strength, delta, costs, used, cls ? cls : &knuth);
+}
+
+int hq_dot_population_partial(hq_ctx* c, const float* palettes, int P, int K, const hq_dot_classes* cls,
+                              float strength, double* partial) {
+    if (!c) return HQ_ERR_ARG;
+    if (!partial) return fail(c, HQ_ERR_ARG, "null output");
+    hq_dot_classes knuth;
+    hq_dot_preset(HQ_DOT_KNUTH8, &knuth);
+    if (cls && !hq_dot_classes_legal(cls))
+        return fail(c, HQ_ERR_ARG, "illegal class matrix: side 4, 8 or 16 and a permutation of 0 .. n*n - 1 (hq.h)");
+    return dither_population(c, palettes, P, K, hq_diffusion_taps{}, strength, 0.0f, nullptr, nullptr,
+                             cls ? cls : &knuth, partial);
 }
 
 int hq_get_indices(hq_ctx* c, int p, uint8_t* idx) {

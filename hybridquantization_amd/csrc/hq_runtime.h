@@ -178,7 +178,8 @@ inline hipError_t timed_launch(ProfRec& pr, Pair p, F&& launch, bool start = tru
 //   the counter set and the used bits zeroed as without a grid, then diffuse_kernel
 //   (hq_diffuse.hip) in the place of grid + assign.  With `dot` set (hq_dot_population) the
 //   rendering is dot diffusion's under the context's class matrix (c->dot_cls, its tables on
-//   the device: ensure_dot_tables): dot_kernel's launches (hq_dot.hip) in that place instead.
+//   the device: ensure_dot_tables): dot_kernel's launches (hq_dot.hip) in that place instead --
+//   on a row-block shard (hq_dot_population_partial) its windowed instance over the pass's rows.
 // Counter-set parity: each pass takes the other counter set than the last one
 // (build_grid zeroes it), so an accept step can read the last set while the next
 // is filled.  A side pass (AssignOnly, CostOnly: nothing reads its sums, so no
@@ -201,6 +202,9 @@ struct Pass {
     int diffuse_rows = 0, diffuse_slope = 0;
     bool fs = false;
     bool dot = false;  // Dither: dot diffusion (taps, diffuse_rows, diffuse_slope and fs unused)
+    // ... on a row-block shard: dot_kernel's windowed instance over rows [dot_a0, dot_a1), the
+    // extended rows and what of the apron the matrix's reach needs (dot_window)
+    int dot_a0 = 0, dot_a1 = 0;
     bool ordered = false;
     float amp[3] = {0.f, 0.f, 0.f};  // ordered: the amplitude per channel
     bool side() const { return kind == AssignOnly || kind == CostOnly; }
@@ -289,6 +293,16 @@ struct hq_ctx {
     // ensure_dot_tables) and the errors e of a Dot pass ([P][3][H][W] floats, never zeroed)
     hq_dot_classes dot_cls{};
     hq::DevBuf d_dottab, d_doterr;
+    // dot diffusion on a row-block shard (hq_dot_population_partial): the apron, the image rows
+    // [e0 - apron_above, e0) and [e1, e1 + apron_below) kept beyond the extended rows by
+    // hq_set_image[_planar]_shard under option "dot_apron" -- [3][apron_above + apron_below][W]
+    // planar floats, the rows above first.  The image's: begin_image drops it.  apron_ok: every
+    // float of it, and of the extended rows outside the owned ones, is finite and in [0, 1]
+    // (found on the host when it is gathered: the rows the device's range flag does not look at)
+    int dot_apron = 0;             // the option: rows asked for by the next shard
+    int apron_above = 0, apron_below = 0;
+    bool apron_ok = true;
+    hq::DevBuf d_apron;
     // ordered dithering: the threshold map (hq_set_dither_map; empty: the default, Bayer 16 x 16)
     // and its device copy, kMaxMapSide^2 floats made once by ensure_dither_map (its address is
     // in captured launches) and written by it whenever the host map has changed

@@ -186,6 +186,9 @@ int begin_image(hq_ctx* c) {
     drop(c);
     c->mask_on = c->weights_on = false;  // a mask, or a weight map, belongs to an image
     c->live_dirty = true;
+    c->d_apron.release();  // ... and so does a shard's apron (set_apron brings the new image's)
+    c->apron_above = c->apron_below = 0;
+    c->apron_ok = true;
     const size_t plane = sizeof(float) * (size_t)round_up(g.n_ext, 4);
     HIP_TRY(c, c->d_R.ensure(plane));
     HIP_TRY(c, c->d_G.ensure(plane));
@@ -251,6 +254,46 @@ int set_image_common(hq_ctx* c, const std::vector<float>& R, const std::vector<f
     HIP_TRY(c, hipMemcpyAsync(c->d_G.p, G.data(), plane, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->d_B.p, B.data(), plane, hipMemcpyHostToDevice, c->stream));
     return finish_image(c, lab4_full, illum);
+}
+
+// The apron of the shard just set (option "dot_apron", hq.h): the rows [max(0, e0 - A), e0) and
+// [e1, min(H, e1 + A)) of the full-image host source -- plane ch at src[ch] with `sstride` floats
+// between pixels -- into storage of their own, and whether they are all in [0, 1].  A whole image
+// or A = 0 holds none and allocates nothing.  Failing leaves the context without an image.
+int set_apron(hq_ctx* c, const float* const src[3], int sstride) {
+    const Geom& g = c->g;
+    const int A = whole_image(c) ? 0 : c->dot_apron;
+    const int a0 = std::max(0, g.e0 - A), a1 = std::min(g.H, g.e1 + A);
+    const int above = g.e0 - a0, below = a1 - g.e1;
+    if (above + below == 0) return HQ_OK;
+    const size_t plane = (size_t)(above + below) * g.W;
+    std::vector<float> rows(3 * plane);
+    bool ok = true;
+    for (int ch = 0; ch < 3; ++ch) {
+        for (int r = 0; r < above + below; ++r) {
+            const int64_t y = r < above ? a0 + r : g.e1 + (r - above);
+            for (int x = 0; x < g.W; ++x) {
+                const float v = src[ch][(y * g.W + x) * sstride];
+                ok = ok && v >= 0.0f && v <= 1.0f;  // (a NaN fails both)
+                rows[ch * plane + (size_t)r * g.W + x] = v;
+            }
+        }
+        // (the extended rows outside the owned ones are rendered with them, and the device's flag
+        // looks at the owned rows alone)
+        for (int64_t y = g.e0; y < g.e1; ++y) {
+            if (y >= g.r0 && y < g.r1) continue;
+            for (int x = 0; x < g.W; ++x) {
+                const float v = src[ch][(y * g.W + x) * sstride];
+                ok = ok && v >= 0.0f && v <= 1.0f;
+            }
+        }
+    }
+    c->have_image = false;
+    HIP_TRY(c, c->d_apron.upload(rows.data(), sizeof(float) * rows.size()));
+    c->apron_above = above, c->apron_below = below;
+    c->apron_ok = ok;
+    c->have_image = true;
+    return HQ_OK;
 }
 
 int check_geom_args(hq_ctx* c, int w, int h, int r0, int r1) {
@@ -433,7 +476,9 @@ int hq_set_image_shard(hq_ctx* c, const float* rgba4, const float* lab4, int w, 
     gather_rows(rgba4, 4, 0, c->g, R);
     gather_rows(rgba4, 4, 1, c->g, G);
     gather_rows(rgba4, 4, 2, c->g, B);
-    return set_image_common(c, R, G, B, lab4, illum);
+    if ((rc = set_image_common(c, R, G, B, lab4, illum))) return rc;
+    const float* const planes[3] = {rgba4, rgba4 + 1, rgba4 + 2};
+    return set_apron(c, planes, 4);
 }
 
 int hq_set_image(hq_ctx* c, const float* rgba4, const float* lab4, int w, int h,
@@ -454,7 +499,9 @@ int hq_set_image_planar_shard(hq_ctx* c, const float* R, const float* G, const f
     gather_rows(R, 1, 0, c->g, r);
     gather_rows(G, 1, 0, c->g, g);
     gather_rows(B, 1, 0, c->g, b);
-    return set_image_common(c, r, g, b, nullptr, illum);
+    if ((rc = set_image_common(c, r, g, b, nullptr, illum))) return rc;
+    const float* const planes[3] = {R, G, B};
+    return set_apron(c, planes, 1);
 }
 
 // The box reduction of src's image as dst's whole image: the second way into finish_image.
@@ -499,6 +546,14 @@ int hq_set_image_reduced(hq_ctx* dst, hq_ctx* src, int factor, const float* illu
     rc = finish_image(dst, nullptr, il);
     if (!rc) prof_accumulate(dst, pr);  // (finish_image has synchronised the stream)
     return rc;
+}
+
+int hq_dot_apron(hq_ctx* c, int* above, int* below) {
+    if (!c) return HQ_ERR_ARG;
+    if (!above || !below) return fail(c, HQ_ERR_ARG, "null output");
+    *above = c->have_image ? c->apron_above : 0;
+    *below = c->have_image ? c->apron_below : 0;
+    return HQ_OK;
 }
 
 int hq_get_image(hq_ctx* c, float* rgba4) {
@@ -849,6 +904,9 @@ int hq_set_option(hq_ctx* c, const char* name, int value) {
         if (value < 64 || value > 1024 || value % 64)
             return fail(c, HQ_ERR_ARG, "dither_rows must be a multiple of 64 in 64 .. 1024");
         c->dither_rows = value;
+    } else if (!std::strcmp(name, "dot_apron")) {
+        if (value < 0 || value > 255) return fail(c, HQ_ERR_ARG, "dot_apron must be in 0 .. 255");
+        c->dot_apron = value;  // (read by the next hq_set_image[_planar]_shard: set_apron)
     } else if (!std::strcmp(name, "cent_span")) {
         if (value < 0) return fail(c, HQ_ERR_ARG, "cent_span must be >= 0 (0 = auto)");
         c->cent_span = value;

@@ -422,6 +422,43 @@ class ImageManipulation:
         self.dotError = float(costs[0])
         return table[self.getIndices(0)].reshape(-1)
 
+    @classmethod
+    def dotReach(cls, classes=None):
+        """hq_dot_reach: (above, below), the largest number of rows by which a pixel that a
+        pixel's dot-diffused index depends on can lie above and below it under the class matrix
+        ``classes`` (dotPopulation's; None is Knuth's 8 x 8: (5, 5)).  What a row-block shard
+        keeps beyond its extended rows for dotPopulationPartial: setOption("dot_apron", n) with
+        n >= both, before setImage(..., row_begin, row_end)."""
+        m = cls._classes("knuth8" if classes is None else classes)
+        above, below = C.c_int(0), C.c_int(0)
+        check(load().hq_dot_reach(C.byref(m), C.byref(above), C.byref(below)))
+        return above.value, below.value
+
+    def dotApron(self):
+        """hq_dot_apron: (above, below), the image rows this context holds beyond its extended
+        rows on each side (option "dot_apron" when the shard was set, clipped at the image's
+        border; (0, 0) on a whole image)."""
+        ctx = self._require()
+        above, below = C.c_int(0), C.c_int(0)
+        check(self._lib.hq_dot_apron(ctx, C.byref(above), C.byref(below)), ctx)
+        return above.value, below.value
+
+    def dotPopulationPartial(self, colors, strength: float = 1.0, classes=None):
+        """hq_dot_population_partial: the shard-local (P, 1 + K) partial rows of the dot-diffused
+        rendering -- column 0 the dE sum over the owned rows, then the used flags of the extended
+        rows.  The partials of disjoint shards of one image add up to the whole image's, the flags
+        OR, and each shard's getIndices are the whole image's rows, bit for bit.  A row-block
+        shard must hold an apron of at least dotReach(classes) rows on each side (or up to the
+        image's border); the sum across shards or ranks is the caller's."""
+        ctx = self._require()
+        m = None if classes is None else self._classes(classes)
+        pal = _f32(np.stack([np.asarray(c, np.float32).reshape(-1) for c in colors]))
+        P, K = pal.shape[0], pal.shape[1] // 4
+        part = np.zeros((P, 1 + K), np.float64)
+        check(self._lib.hq_dot_population_partial(ctx, fptr(pal), P, K, None if m is None else C.byref(m),
+                                                  float(strength), dptr(part)), ctx)
+        return part
+
     # ordered dithering: libhq's addition (hq_ordered_population, no reference counterpart)
     @staticmethod
     def bayerMap(log2n: int):

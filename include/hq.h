@@ -477,6 +477,55 @@ int hq_dot_barons(const hq_dot_classes *cls);
 int hq_dot_population(hq_ctx *ctx, const float *palettes, int P, int K, const hq_dot_classes *cls,
                       float strength, float delta, double *costs, int32_t *used);
 
+/* ---- dot diffusion on row-block shards ----
+ * idx(q) depends on the pixels a path of neighbour steps with strictly descending class
+ * reaches from q, and on nothing else.  The matrix is periodic, so how far above and below q
+ * such a path can get is a property of the matrix alone, its reach.  A shard that also
+ * renders that many rows above and below its extended rows (its owned rows +- the filters'
+ * half-width) therefore produces the whole image's indices on its extended rows bit for bit,
+ * with no exchange between devices; the rows beyond the extended ones (the apron) are
+ * rendered for their errors alone.
+ *
+ * hq_dot_reach: *above is the largest number of rows by which a pixel that idx(q) depends on
+ * can lie above q, *below the same below q, over all q of the tiled plane (host-only).  In
+ * ascending class, for a cell c and each neighbour p of lower class at offset (dx, dy), taken
+ * on the torus:  above[c] = max(above[c], above[p] - dy),  below[c] = max(below[c], below[p] + dy),
+ * both from 0; the result is the maximum over the cells.  Both lie in 1 .. n*n - 1 and may
+ * exceed n (paths cross tile borders).  HQ_DOT_KNUTH8: (5, 5); the row-major 16 x 16 matrix:
+ * (15, 1).  HQ_ERR_ARG (outputs untouched): an illegal matrix, a null pointer. */
+int hq_dot_reach(const hq_dot_classes *cls, int *above, int *below);
+/* Option "dot_apron" (rows, 0 .. 255, default 0) is read by hq_set_image_shard and
+ * hq_set_image_planar_shard: a shard with extended rows [e0, e1) of an image of h rows also
+ * keeps the planar floats of rows [max(0, e0 - A), e0) and [e1, min(h, e1 + A)), in storage of
+ * its own that no other call reads.  A whole image keeps none whatever the option says, and
+ * changing the option afterwards does not change what is held; the apron goes where the image
+ * goes and is replaced by the next hq_set_image*.  hq_dot_apron reports the rows held on each
+ * side (0, 0 without an image).  HQ_ERR_ARG: a null pointer. */
+int hq_dot_apron(hq_ctx *ctx, int *above, int *below);
+/* hq_dot_population without the final division and penalty, in hq_eval_population_partial's
+ * layout partial[P][1 + K]: the partials of disjoint shards of one image add up to the whole
+ * image's, and the used flags OR.  On a whole image it is hq_dot_population's rendering
+ * (the same launches).  On a row-block shard the held apron must be at least
+ * min(reach, rows between the extended rows and the image's border) on each side, under the
+ * reach of *cls (NULL: HQ_DOT_KNUTH8); else HQ_ERR_STATE, and hq_last_error names the needed
+ * and the held rows.  The shard's launches run over the window [e0 - above, e1 + below)
+ * (clipped to the image): the class of a pixel comes from its full-image row and the border
+ * rule of W(p) from the full image's height, a pixel outside the window is never read, and
+ * indices and used flags are written for the extended rows only -- they are the whole
+ * image's.  A class without a pixel in the window gets no launch.
+ * Everything else is hq_dot_population's: its refusals (K > 256, a palette slice, a
+ * communicator of more than one rank -- the reduction across ranks is the caller's --, an
+ * illegal matrix, palette or strength, P > 65535, an image pixel outside [0, 1] or not
+ * finite, the apron's rows included), the outputs and the evaluated state untouched on a
+ * refusal, a mask and weights as hq_eval_population_partial composes them on a shard, the
+ * getters afterwards (hq_get_indices and hq_get_pixel_errors answer for the owned rows of
+ * this rendering; hq_cluster_sums and hq_cluster_errors return HQ_ERR_STATE), and
+ * HQ_ARGMIN_DOT in hq_last_path.
+ * Measured on one MI355X (profiles/dot_shards_c3.json); more than one GPU has
+ * not been run. */
+int hq_dot_population_partial(hq_ctx *ctx, const float *palettes, int P, int K,
+                              const hq_dot_classes *cls, float strength, double *partial);
+
 /* ---- ordered dithering: libhq's addition, no reference counterpart ----
  * Error diffusion is a serial recurrence (one workgroup per palette); a threshold
  * map gives most of its S-CIELAB gain with every pixel independent, so it lives
@@ -1113,6 +1162,9 @@ int hq_search_info(const hq_search *s, int *device_resident, int *nch, int *grap
  *   "dither_rows"  hq_dither_population: rows per strip of the dither kernel, a multiple of 64
  *                  in 64 .. 1024 (default 1024; anything else is HQ_ERR_ARG).  The results do
  *                  not depend on it, bit for bit: it lets small test images cross strips
+ *   "dot_apron"    rows (0 .. 255, default 0; anything else is HQ_ERR_ARG) a row-block shard keeps
+ *                  beyond its extended rows on each side for hq_dot_population_partial; read by
+ *                  hq_set_image_shard and hq_set_image_planar_shard (hq_dot_apron)
  *   "cent_span"    test only: pixels per workgroup of the k-means sums kernel (0, default: by
  *                  the grid), rounded up to whole steps of 1024 and clamped to the bound of the
  *                  kernel's accumulator fields.  The results do not depend on it, bit for bit:
