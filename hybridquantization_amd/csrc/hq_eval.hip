@@ -453,31 +453,84 @@ AssignArgs assign_args(hq_ctx* c, const GridArgs& ga, int Ps, int Ks, bool order
     return aa;
 }
 
-// ... an ordered pass: the map (on the device: ensure_dither_map) and the amplitudes; K <= 256
-int add_ordered(hq_ctx* c, const Pass& pass, AssignArgs& aa) {
-    if (c->nch_cur > 1 || pass.kind == Pass::Dither || !c->d_dmap.p)
-        return fail(c, HQ_ERR_STATE, "ordered pass: K > 256 or no map");
-    const int mw = c->dmap.empty() ? 16 : c->dmap_w, mh = c->dmap.empty() ? 16 : c->dmap_h;
-    aa.map = c->d_dmap.as<float>();
-    aa.mw_mask = (uint32_t)mw - 1u;
-    aa.mh_mask = (uint32_t)mh - 1u;
-    while ((1u << aa.lg_mw) < (uint32_t)mw) ++aa.lg_mw;
-    for (int ch = 0; ch < 3; ++ch) aa.amp[ch] = pass.amp[ch];
-    aa.W = (uint32_t)c->g.W;
-    aa.y0 = (uint32_t)c->g.e0;
-    return HQ_OK;
+// ---- the argmin stage: one function per rendering, each launching under its own pair ---------
+// (the native 16-bit lists: one palette of K colours per workgroup, its table in LDS)
+hipError_t argmin_plain(hq_ctx* c, AssignArgs& aa, bool n16, int K, int Pl, int Ps, Pair pair, ProfRec& pr,
+                        AssignTag* at) {
+    if (n16) {
+        aa.l1n = c->d_l1n.as<uint16_t>(), aa.l2n = c->d_l2n.as<uint16_t>();
+        aa.kpal = c->nch_cur * kMaxK, aa.K = K;
+        // one resident round of 1024-thread workgroups over the P palettes, >= 4 pixels per thread
+        const int ngr = K <= 4096 ? (Pl + 1) / 2 : Pl;  // workgroup groups: palette pairs up to K = 4096
+        aa.nblocks = (int)std::max<int64_t>(
+            1, std::min<int64_t>(std::max(1, c->num_cu / ngr), (c->g.n_ext + 4095) / 4096));
+    }
+    return timed_launch(pr, pair, [&] {
+        return n16 ? launch_assign16(aa, Pl, c->stream, at) : launch_assign(aa, Ps, c->stream, at);
+    });
 }
 
-// ... the native 16-bit lists: one palette of K colours per workgroup (its table in LDS).
-void add_lists16(const hq_ctx* c, int K, int Pl, AssignArgs& aa) {
-    aa.l1n = c->d_l1n.as<uint16_t>();
-    aa.l2n = c->d_l2n.as<uint16_t>();
-    aa.kpal = c->nch_cur * kMaxK;
-    aa.K = K;
-    // one resident round of 1024-thread workgroups over the P palettes, >= 4 pixels per thread
-    const int ngr = K <= 4096 ? (Pl + 1) / 2 : Pl;  // workgroup groups: palette pairs up to K = 4096
-    aa.nblocks = (int)std::max<int64_t>(
-        1, std::min<int64_t>(std::max(1, c->num_cu / ngr), (c->g.n_ext + 4095) / 4096));
+// (the map is on the device and K <= 256: enqueue_argmin has looked)
+hipError_t argmin_ordered(hq_ctx* c, const Ordered& o, AssignArgs& aa, int Ps, Pair pair, ProfRec& pr, AssignTag* at) {
+    const int mw = c->dmap.empty() ? 16 : c->dmap_w, mh = c->dmap.empty() ? 16 : c->dmap_h;
+    aa.map = c->d_dmap.as<float>();
+    aa.mw_mask = (uint32_t)mw - 1u, aa.mh_mask = (uint32_t)mh - 1u;
+    while ((1u << aa.lg_mw) < (uint32_t)mw) ++aa.lg_mw;
+    for (int ch = 0; ch < 3; ++ch) aa.amp[ch] = o.amp[ch];
+    aa.W = (uint32_t)c->g.W, aa.y0 = (uint32_t)c->g.e0;
+    return timed_launch(pr, pair, [&] { return launch_assign_ordered(aa, Ps, c->stream, at); });
+}
+
+// (HQ_ARGMIN_DITHER, the Floyd-Steinberg formula, reports no instance)
+hipError_t argmin_diffused(hq_ctx* c, const Diffused& d, const AssignArgs& aa, const GridArgs& ga, int K, int Pl,
+                           ProfRec& pr, AssignTag* at, hq_path_info& pi) {
+    const Geom& g = c->g;
+    DiffuseArgs da{aa.R, aa.G, aa.B, ga.pal, aa.idx, ga.used_glob, c->d_dcarry.as<float>(), g.idx_pitch,
+                   g.W, g.H, K, c->dither_rows, d.rows, d.slope, d.floyd_steinberg, d.strength};
+    da.w0[0] = (float)d.taps.w[0][3], da.w0[1] = (float)d.taps.w[0][4];
+    for (int i = 0; i < 5; ++i) da.w1[i] = (float)d.taps.w[1][i], da.w2[i] = (float)d.taps.w[2][i];
+    da.div = (float)d.taps.div;
+    if (!d.floyd_steinberg) pi.diffuse_rows = d.rows, pi.diffuse_slope = d.slope;
+    return timed_launch(pr, kPDither, [&] { return launch_diffuse(da, Pl, c->stream, at); });
+}
+
+// (the matrix read on the host here is the one whose tables d_dottab holds: ensure_dot_tables)
+hipError_t argmin_dot(hq_ctx* c, const Dot& d, const AssignArgs& aa, const GridArgs& ga, int K, int Pl, int Ps,
+                      ProfRec& pr, AssignTag* at) {
+    const Geom& g = c->g;
+    DotWinArgs wa{};  // (on a whole image the DotArgs in it alone)
+    static_cast<DotArgs&>(wa) = DotArgs{aa.R, aa.G, aa.B, ga.pal, aa.idx, ga.used_glob, c->d_doterr.as<float>(),
+                                        c->d_dottab.as<uint32_t>(), c->dot_cls.cls, g.idx_pitch, used_stride(Ps), g.W,
+                                        g.H, K, c->dot_cls.n, d.strength};
+    if (!whole_image(c)) {  // a row-block shard: the window's rows, the apron's planes from the row it holds first
+        const int64_t aplane = (int64_t)(c->apron_above + c->apron_below) * g.W;
+        const float* ap = c->d_apron.as<float>();
+        wa.a0 = d.a0, wa.a1 = d.a1, wa.e0 = g.e0, wa.e1 = g.e1;
+        wa.h0 = g.e0 - c->apron_above, wa.h1 = g.e1 + c->apron_below;
+        wa.aR = ap, wa.aG = ap ? ap + aplane : nullptr, wa.aB = ap ? ap + 2 * aplane : nullptr;
+    }
+    return timed_launch(pr, kPDot, [&] {
+        return whole_image(c) ? launch_dot(wa, Pl, c->stream, at) : launch_dot_window(wa, Pl, c->stream, at);
+    });
+}
+
+// The index images of `pass`: its rendering's function, then what the launch reported.
+int enqueue_argmin(hq_ctx* c, const Pass& pass, const GridArgs& ga, bool n16, int K, int Pl, int Ps, ProfRec& pr,
+                   hq_path_info& pi) {
+    const Ordered* const o = pass.as<Ordered>();
+    if (o && (c->nch_cur > 1 || !c->d_dmap.p)) return fail(c, HQ_ERR_STATE, "ordered pass: K > 256 or no map");
+    AssignArgs aa = assign_args(c, ga, Ps, c->nch_cur > 1 ? kMaxK : K, o != nullptr);
+    const Pair pair = Pair(pass.pairs() + 1);
+    AssignTag at;
+    hipError_t launched;
+    if (o) launched = argmin_ordered(c, *o, aa, Ps, pair, pr, &at);
+    else if (const Diffused* d = pass.as<Diffused>()) launched = argmin_diffused(c, *d, aa, ga, K, Pl, pr, &at, pi);
+    else if (const Dot* d = pass.as<Dot>()) launched = argmin_dot(c, *d, aa, ga, K, Pl, Ps, pr, &at);
+    else launched = argmin_plain(c, aa, n16, K, Pl, Ps, pair, pr, &at);
+    HIP_TRY(c, launched);
+    pi.idx_bytes = aa.idx16 ? 2 : 1;
+    record_argmin(pi, at);
+    return HQ_OK;
 }
 
 // The fast cost launch; under a mask its live-tile list, which has to be this launch's.
@@ -554,11 +607,9 @@ int enqueue_cost(hq_ctx* c, const CostArgs& ca, bool fast, const FastGrid& f, in
 // prep_palette made them), assign combines them into 16-bit indices, the cost
 // kernel reads those with a 256 nch-entry table.
 // What it leaves on the device is the caller's to commit (resident_of).
-int hq::enqueue_core(hq_ctx* c, int P, int K, ProfRec& pr, Pass pass) {
-    const Geom& g = c->g;
-    hipStream_t s = c->stream;
+int hq::enqueue_core(hq_ctx* c, int P, int K, ProfRec& pr, const Pass& pass) {
     const int nch = c->nch_cur, Ks = nch > 1 ? kMaxK : K;
-    const bool dither = pass.kind == Pass::Dither, costed = pass.kind != Pass::AssignOnly;
+    const bool costed = pass.kind != Pass::AssignOnly;
     const int p0 = pass.pairs();
     // the palettes this device evaluates: all, or a palette split's slice [lo, lo + Pl)
     int lo = 0, Pl = P;
@@ -568,54 +619,16 @@ int hq::enqueue_core(hq_ctx* c, int P, int K, ProfRec& pr, Pass pass) {
     const GridArgs ga = grid_args(c, Ps, Ks, so);
     const bool n16 = use_lists16(c);
     hq_path_info pi{};
-    pi.pass = dither ? HQ_PASS_DITHER : costed ? HQ_PASS_FULL : HQ_PASS_ASSIGN_ONLY;
-    pi.ordered = pass.ordered, pi.P = Pl, pi.K = K, pi.nch = nch;
-    if (int rc = enqueue_grid(c, ga, c->G2 > 0 && !dither, n16, K, Pl, Ps, Pair(p0), pr, pi)) return rc;
-    AssignArgs aa = assign_args(c, ga, Ps, Ks, pass.ordered);
-    if (pass.ordered)
-        if (int rc = add_ordered(c, pass, aa)) return rc;
-    if (n16) add_lists16(c, K, Pl, aa);
-    pi.idx_bytes = aa.idx16 ? 2 : 1;
+    pi.pass = pass.gridless() ? HQ_PASS_DITHER : costed ? HQ_PASS_FULL : HQ_PASS_ASSIGN_ONLY;
+    pi.ordered = pass.as<Ordered>() != nullptr, pi.P = Pl, pi.K = K, pi.nch = nch;
+    if (int rc = enqueue_grid(c, ga, c->G2 > 0 && !pass.gridless(), n16, K, Pl, Ps, Pair(p0), pr, pi)) return rc;
     const uint32_t why = cost_slow_why(c);  // (cost_fast)
     const bool fast = why == 0;
-    AssignTag at;
     const FastGrid f = fast_grid(c);
     CostArgs ca{};
     if (fast)
         if (int rc = cost_args(c, ga, f, K, so, Pl, &ca)) return rc;
-    HIP_TRY(c, timed_launch(pr, pass.dot ? kPDot : dither ? kPDither : Pair(p0 + 1), [&] {
-        if (pass.dot) {
-            // (the matrix read on the host here is the one whose tables d_dottab holds: ensure_dot_tables)
-            DotArgs da{aa.R, aa.G, aa.B, ga.pal, aa.idx, ga.used_glob, c->d_doterr.as<float>(),
-                       c->d_dottab.as<uint32_t>(), c->dot_cls.cls, g.idx_pitch, used_stride(Ps), g.W, g.H, K,
-                       c->dot_cls.n, pass.strength};
-            if (whole_image(c)) return launch_dot(da, Pl, s, &at);
-            // a row-block shard: the window's rows, the apron's planes from the row it holds first
-            DotWinArgs wa{};
-            static_cast<DotArgs&>(wa) = da;
-            const int64_t aplane = (int64_t)(c->apron_above + c->apron_below) * g.W;
-            const float* ap = c->d_apron.as<float>();
-            wa.a0 = pass.dot_a0, wa.a1 = pass.dot_a1, wa.e0 = g.e0, wa.e1 = g.e1;
-            wa.h0 = g.e0 - c->apron_above, wa.h1 = g.e1 + c->apron_below;
-            wa.aR = ap, wa.aG = ap ? ap + aplane : nullptr, wa.aB = ap ? ap + 2 * aplane : nullptr;
-            return launch_dot_window(wa, Pl, s, &at);
-        }
-        if (dither) {
-            const hq_diffusion_taps& tp = pass.taps;
-            DiffuseArgs da{aa.R, aa.G, aa.B, ga.pal, aa.idx, ga.used_glob, c->d_dcarry.as<float>(), g.idx_pitch,
-                           g.W, g.H, K, c->dither_rows, pass.diffuse_rows, pass.diffuse_slope, pass.fs, pass.strength};
-            da.w0[0] = (float)tp.w[0][3], da.w0[1] = (float)tp.w[0][4];
-            for (int i = 0; i < 5; ++i) da.w1[i] = (float)tp.w[1][i], da.w2[i] = (float)tp.w[2][i];
-            da.div = (float)tp.div;
-            return launch_diffuse(da, Pl, s, &at);
-        }
-        return n16  ? launch_assign16(aa, Pl, s, &at)
-               : pass.ordered ? launch_assign_ordered(aa, Ps, s, &at)
-                      : launch_assign(aa, Ps, s, &at);
-    }));
-    record_argmin(pi, at);
-    // (HQ_ARGMIN_DITHER, the Floyd-Steinberg formula, reports no instance)
-    if (dither && !pass.fs && !pass.dot) pi.diffuse_rows = pass.diffuse_rows, pi.diffuse_slope = pass.diffuse_slope;
+    if (int rc = enqueue_argmin(c, pass, ga, n16, K, Pl, Ps, pr, pi)) return rc;
     if (costed) {
         pi.why_not_fast = why;
         if (int rc = enqueue_cost(c, ca, fast, f, lo, Pl, Pair(p0 + 2), pr, pi)) return rc;
@@ -673,6 +686,17 @@ bool palette_fits_fast(const float* pal, int P, int K) {
     return true;
 }
 
+// The scratch a rendering needs -- dot diffusion's errors over the rows rendered, a raster diffusion's carry
+// rows -- ensured by run_pass before anything is enqueued: nothing allocates between prof_begin and the
+// synchronise, and nothing inside a captured search run (its passes are plain or ordered and need none).
+int ensure_render_scratch(hq_ctx* c, const Pass& pass, int P) {
+    if (const Dot* d = pass.as<Dot>())
+        HIP_TRY(c, c->d_doterr.ensure(sizeof(float) * dot_err_floats(P, c->g.W, whole_image(c) ? c->g.H : d->a1 - d->a0)));
+    if (const Diffused* d = pass.as<Diffused>())
+        HIP_TRY(c, c->d_dcarry.ensure(sizeof(float) * diffuse_carry_floats(P, d->rows, c->g.W)));
+    return HQ_OK;
+}
+
 // One host-driven pass, after the caller's last refusal: upload, prep, `pass` (K > 256
 // unchunked: enqueue_wide), d_out back into h_out ([P][1 + K]).  The record is dropped before
 // the first buffer is grown or written and committed when the pass has come back.
@@ -690,11 +714,7 @@ int run_pass(hq_ctx* c, const float* palettes, int P, int K, const Pass& pass) {
     c->nch_cur = c->chunked && fits && c->G2 > 0 && K > kMaxK && K <= kMaxKChunked ? chunk_count(K) : 1;
     c->pal_generic = !fits;  // (before ensure_population: it sizes the generic path's scratch)
     if (int rc = ensure_population(c, P, K)) return rc;
-    if (pass.kind == Pass::Dither && pass.dot)  // (the rows rendered: the image's, or a shard's window's)
-        HIP_TRY(c, c->d_doterr.ensure(sizeof(float) * dot_err_floats(P, c->g.W, whole_image(c) ? c->g.H
-                                                                                   : pass.dot_a1 - pass.dot_a0)));
-    else if (pass.kind == Pass::Dither)
-        HIP_TRY(c, c->d_dcarry.ensure(sizeof(float) * diffuse_carry_floats(P, pass.diffuse_rows, c->g.W)));
+    if (int rc = ensure_render_scratch(c, pass, P)) return rc;
     hipStream_t s = c->stream;
     ProfRec pr = prof_begin(c);
     int rc = upload_and_prep(c, palettes, nullptr, P, K);
@@ -703,8 +723,7 @@ int run_pass(hq_ctx* c, const float* palettes, int P, int K, const Pass& pass) {
     HIP_TRY(c, hipMemcpyAsync(c->h_out.p, c->d_out.p, sizeof(double) * (size_t)P * (1 + K), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     prof_accumulate(c, pr);
-    const bool render = pass.kind == Pass::Dither || pass.ordered;
-    commit(c, resident_of(c, render ? Resident::Render : Resident::Eval, P, K));
+    commit(c, resident_of(c, pass.rendered() ? Resident::Render : Resident::Eval, P, K));
     return HQ_OK;
 }
 
@@ -804,7 +823,9 @@ int color_histogram(hq_ctx* c, int bits, int64_t* out, int64_t* den) {
 
 // IM:712 from the [P][1+K] rows in h_out: averageArray(error) + computePenalty(used).
 // After an all-reduce the used entries count the ranks using colour k; unused <=> 0.
-void costs_from_hout(const hq_ctx* c, int P, int K, float delta, double* costs, int32_t* used) {
+// partial_from_hout: the rows themselves, as a _partial call returns them.  (Both return HQ_OK:
+// the last line of an entry point whose pass has come back.)
+int costs_from_hout(const hq_ctx* c, int P, int K, float delta, double* costs, int32_t* used) {
     const double n_total = cost_divisor(c);  // (a pixel mask: its pixels in the full image)
     for (int p = 0; p < P; ++p) {
         const double* o = c->h_out.as<double>() + (size_t)p * (1 + K);
@@ -816,6 +837,11 @@ void costs_from_hout(const hq_ctx* c, int P, int K, float delta, double* costs, 
         }
         costs[p] = o[0] / n_total + penalty;
     }
+    return HQ_OK;
+}
+int partial_from_hout(const hq_ctx* c, int P, int K, double* partial) {
+    std::memcpy(partial, c->h_out.p, sizeof(double) * (size_t)P * (1 + K));
+    return HQ_OK;
 }
 
 // The improvement loop of hq_refine_population and hq_repair_population: evaluate,
@@ -1095,89 +1121,69 @@ int ensure_dither_map(hq_ctx* c) {
 
 namespace {
 
-// hq_ordered_population[_partial]: every check, then the evaluation into h_out.  On a refusal
-// nothing has been touched.
-int ordered_into_hout(hq_ctx* c, const float* palettes, int P, int K, const float* amp, const void* out,
-                      bool partial) {
-    if (!c) return HQ_ERR_ARG;
-    if (!palettes || !out || P < 1 || K < 1) return fail(c, HQ_ERR_ARG, "bad palettes / output / P=%d / K=%d", P, K);
-    int rc = check_ordered_amp(c, amp);
-    if (rc) return rc;
+// ---- the rendered entry points ----------------------------------------------------------------
+// A rendered call as its checks see it: the population, the output (costs, or a _partial call's
+// [P][1 + K] rows), and its family with that family's parameter: the amplitudes per channel
+// (ordered), else the strength.
+struct RenderCall {
+    const float* palettes;
+    const void* out;
+    int P, K;
+    bool partial, ordered;
+    const float* amp;
+    float strength;
+};
+
+// Every check of a rendered evaluation on the call and the context; a refused call has touched
+// nothing.  scope(): where the call may run (the diffused family's whole_image_only or dot_window,
+// the ordered family's shard without _partial).  Both families open with the arguments, the
+// parameter and the image.  After that each keeps its own order, because the order decides which
+// refusal wins when two conditions hold (tests/golden/render_contract.json): under a mask on a palette
+// slice the diffused family names the slice and the ordered family the mask.
+template <typename Scope>
+int check_rendered(hq_ctx* c, const RenderCall& r, Scope&& scope) {
+    if (!r.palettes || !r.out || r.P < 1 || r.K < 1)
+        return fail(c, HQ_ERR_ARG, "bad palettes / %s / P=%d / K=%d", r.ordered ? "output" : r.partial ? "partial" : "costs",
+                    r.P, r.K);
+    int rc = HQ_OK;
+    if (r.ordered && (rc = check_ordered_amp(c, r.amp))) return rc;
+    if (!r.ordered && !(r.strength >= 0.0f && r.strength <= 1.0f))
+        return fail(c, HQ_ERR_ARG, "strength %g not in [0, 1]", r.strength);
     if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
-    if ((rc = mask_scope(c))) return rc;
-    if (K <= kMaxK && !population_in_range(palettes, P, K))
+    auto palette_range = [&] {
+        if (population_in_range(r.palettes, r.P, r.K)) return (int)HQ_OK;
         return fail(c, HQ_ERR_ARG, "palette with a channel that is not finite or outside [0, 1]");
-    if (!partial && !whole_image(c) && !(c->comm && c->nranks > 1))
-        return fail(c, HQ_ERR_STATE, "sharded context without a communicator: use hq_ordered_population_partial");
-    if ((rc = ordered_scope(c, K))) return rc;
-    if ((rc = ensure_dither_map(c))) return rc;
-    Pass pass{};
-    pass.ordered = true;
-    for (int ch = 0; ch < 3; ++ch) pass.amp[ch] = amp[ch];
-    return run_pass(c, palettes, P, K, pass);  // (the getters then answer for the ordered rendering)
-}
-
-}  // namespace
-
-extern "C" {
-
-int hq_set_dither_map(hq_ctx* c, const float* map, int mw, int mh) {
-    if (!c) return HQ_ERR_ARG;
-    if (map) {
-        auto side = [](int v) { return v >= 1 && v <= kMaxMapSide && (v & (v - 1)) == 0; };
-        if (!side(mw) || !side(mh))
-            return fail(c, HQ_ERR_ARG, "map of %d x %d: each side a power of two in 1 .. %d", mw, mh, kMaxMapSide);
-        for (int i = 0; i < mw * mh; ++i)
-            if (!(map[i] >= -0.5f && map[i] <= 0.5f))
-                return fail(c, HQ_ERR_ARG, "map[%d] = %g not in [-0.5, 0.5]", i, map[i]);
-        c->dmap.assign(map, map + (size_t)mw * mh);
-        c->dmap_w = mw;
-        c->dmap_h = mh;
-    } else {
-        c->dmap.clear();
-        c->dmap_w = c->dmap_h = 0;
+    };
+    if (r.ordered) {  // mask, palette range, scope, then ordered_scope's K, palette slice and image range
+        if ((rc = mask_scope(c)) || (r.K <= kMaxK && (rc = palette_range())) || (rc = scope())) return rc;
+        return ordered_scope(c, r.K);
     }
-    c->dmap_dirty = true;  // (uploaded by the next ordered evaluation or search run: ensure_dither_map)
+    // the diffused family: scope, mask, K, palette range, image range
+    if ((rc = scope()) || (rc = mask_scope(c))) return rc;
+    if (r.K > kMaxK)
+        return fail(c, HQ_ERR_UNSUPPORTED, "K=%d > %d: the dither kernel keeps the palette in LDS and writes "
+                                           "8-bit indices", r.K, kMaxK);
+    if ((rc = palette_range())) return rc;
+    // the errors stay bounded (|e| <= 1) for pixels in [0, 1]: a property of the image, established
+    // once per image as the hybrid search's is (the packed 8-bit copy exists only for k/255 images)
+    if (!c->img_u8 && (rc = require_unit_range_image(c, "image", "no error diffusion"))) return rc;
+    // ... and of the rows a shard renders beyond its owned ones (found on the host with the apron)
+    if (r.partial && !c->apron_ok)
+        return fail(c, HQ_ERR_UNSUPPORTED, "image with a pixel outside [0, 1] or not finite in the rows held around "
+                                           "the owned ones: no error diffusion");
     return HQ_OK;
 }
 
-int hq_ordered_population(hq_ctx* c, const float* palettes, int P, int K, const float amp[3], float delta,
-                          double* costs, int32_t* used) {
-    int rc = ordered_into_hout(c, palettes, P, K, amp, costs, false);
-    if (rc) return rc;
-    costs_from_hout(c, P, K, delta, costs, used);
-    return HQ_OK;
+// hq_ordered_population[_partial] into h_out (the getters then answer for the ordered rendering).
+int ordered_into_hout(hq_ctx* c, const RenderCall& r) {
+    if (!c) return HQ_ERR_ARG;
+    int rc = check_rendered(c, r, [&] {
+        if (r.partial || whole_image(c) || (c->comm && c->nranks > 1)) return (int)HQ_OK;
+        return fail(c, HQ_ERR_STATE, "sharded context without a communicator: use hq_ordered_population_partial");
+    });
+    if (rc || (rc = ensure_dither_map(c))) return rc;
+    return run_pass(c, r.palettes, r.P, r.K, Pass{Pass::Full, Ordered{{r.amp[0], r.amp[1], r.amp[2]}}});
 }
-
-int hq_ordered_population_partial(hq_ctx* c, const float* palettes, int P, int K, const float amp[3],
-                                  double* partial) {
-    int rc = ordered_into_hout(c, palettes, P, K, amp, partial, true);
-    if (rc) return rc;
-    std::memcpy(partial, c->h_out.p, sizeof(double) * (size_t)P * (1 + K));
-    return HQ_OK;
-}
-
-int hq_eval_population_partial(hq_ctx* c, const float* palettes, int P, int K, double* partial) {
-    if (!partial) return fail(c, HQ_ERR_ARG, "null output");
-    int rc = eval_partial_into_hout(c, palettes, P, K);
-    if (rc) return rc;
-    std::memcpy(partial, c->h_out.p, sizeof(double) * (size_t)P * (1 + K));
-    return HQ_OK;
-}
-
-int hq_eval_population(hq_ctx* c, const float* palettes, int P, int K, float delta,
-                       double* costs, int32_t* used) {
-    if (!costs) return fail(c, HQ_ERR_ARG, "null output");
-    int rc = eval_partial_into_hout(c, palettes, P, K);
-    if (rc) return rc;
-    if ((!whole_image(c) || c->slice_ranks > 1) && !(c->comm && c->nranks > 1))
-        return fail(c, HQ_ERR_STATE, "sharded context or palette slice without a communicator: use "
-                                     "hq_eval_population_partial");
-    costs_from_hout(c, P, K, delta, costs, used);
-    return HQ_OK;
-}
-
-namespace {
 
 // The tables of class matrix m on the device: the buffer once, its contents when m differs from
 // the matrix of the last call (c->dot_cls; compared over n and its n^2 entries).
@@ -1224,96 +1230,117 @@ int dot_window(hq_ctx* c, const hq_dot_classes& m, int* a0, int* a1) {
     return HQ_OK;
 }
 
-// hq_dither_population (the Floyd-Steinberg preset), hq_diffuse_population (a caller's legal
-// taps) and hq_dot_population (dot: a legal class matrix in the place of the taps).
-// Floyd-Steinberg's taps, whoever gives them, take its own formula (hq.h).
-// hq_dot_population_partial (dot and partial: the [P][1 + K] rows in the place of costs and used)
-// also serves a row-block shard, over the window dot_window finds.
-int dither_population(hq_ctx* c, const float* palettes, int P, int K, const hq_diffusion_taps& taps,
-                      float strength, float delta, double* costs, int32_t* used,
-                      const hq_dot_classes* dot = nullptr, double* partial = nullptr) {
-    if (!palettes || !(costs || partial) || P < 1 || K < 1)
-        return fail(c, HQ_ERR_ARG, "bad palettes / %s / P=%d / K=%d", partial ? "partial" : "costs", P, K);
-    if (!(strength >= 0.0f && strength <= 1.0f)) return fail(c, HQ_ERR_ARG, "strength %g not in [0, 1]", strength);
-    if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
-    int rc, a0 = 0, a1 = 0;
-    if (partial) rc = dot_window(c, *dot, &a0, &a1);
-    else rc = whole_image_only(c, "hq_dither_population (error diffusion)");
+// hq_dot_population[_partial] into h_out: the class matrix (the caller's when legal, Knuth's for none), the
+// checks -- a _partial call may be a row-block shard's, over the window dot_window finds -- and the pass.
+int dot_into_hout(hq_ctx* c, const RenderCall& r, const hq_dot_classes* cls) {
+    if (cls && !hq_dot_classes_legal(cls))
+        return fail(c, HQ_ERR_ARG, "illegal class matrix: side 4, 8 or 16 and a permutation of 0 .. n*n - 1 (hq.h)");
+    hq_dot_classes m;
+    if (cls) m = *cls;
+    else hq_dot_preset(HQ_DOT_KNUTH8, &m);
+    int a0 = 0, a1 = 0;
+    int rc = check_rendered(c, r, [&] {
+        return r.partial ? dot_window(c, m, &a0, &a1) : whole_image_only(c, "hq_dither_population (error diffusion)");
+    });
     if (rc) return rc;
-    if ((rc = mask_scope(c))) return rc;
-    if (K > kMaxK)
-        return fail(c, HQ_ERR_UNSUPPORTED, "K=%d > %d: the dither kernel keeps the palette in LDS and writes "
-                                           "8-bit indices", K, kMaxK);
-    if (!population_in_range(palettes, P, K))
-        return fail(c, HQ_ERR_ARG, "palette with a channel that is not finite or outside [0, 1]");
-    // the errors stay bounded (|e| <= 1) for pixels in [0, 1]: a property of the image, established
-    // once per image as the hybrid search's is (the packed 8-bit copy exists only for k/255 images)
-    if (!c->img_u8 && (rc = require_unit_range_image(c, "image", "no error diffusion"))) return rc;
-    // ... and of the rows a shard renders beyond its owned ones (found on the host with the apron)
-    if (partial && !c->apron_ok)
-        return fail(c, HQ_ERR_UNSUPPORTED, "image with a pixel outside [0, 1] or not finite in the rows held around "
-                                           "the owned ones: no error diffusion");
-    // (the getters then answer for the dithered rendering)
-    Pass pass{Pass::Dither, strength, taps};
-    if (dot) {
-        if (P > kDotMaxP)
-            return fail(c, HQ_ERR_UNSUPPORTED, "P=%d > %d: a dot-diffusion launch holds the palettes in its grid's y", P,
-                        kDotMaxP);
-        if ((rc = ensure_dot_tables(c, *dot))) return rc;
-        pass.dot = true;
-        pass.dot_a0 = a0, pass.dot_a1 = a1;
-        if ((rc = run_pass(c, palettes, P, K, pass))) return rc;
-        if (partial) std::memcpy(partial, c->h_out.p, sizeof(double) * (size_t)P * (1 + K));
-        else costs_from_hout(c, P, K, delta, costs, used);
-        return HQ_OK;
-    }
-    if ((rc = hq_diffusion_classify(&taps, &pass.diffuse_rows, &pass.diffuse_slope)))
-        return fail(c, HQ_ERR_ARG, "illegal diffusion taps");
-    hq_diffusion_taps fs;
-    hq_diffusion_preset(HQ_DIFFUSION_FLOYD_STEINBERG, &fs);
-    pass.fs = !std::memcmp(&fs, &taps, sizeof fs);
-    if ((rc = run_pass(c, palettes, P, K, pass))) return rc;
-    costs_from_hout(c, P, K, delta, costs, used);
-    return HQ_OK;
+    if (r.P > kDotMaxP)
+        return fail(c, HQ_ERR_UNSUPPORTED, "P=%d > %d: a dot-diffusion launch holds the palettes in its grid's y", r.P,
+                    kDotMaxP);
+    if ((rc = ensure_dot_tables(c, m))) return rc;
+    return run_pass(c, r.palettes, r.P, r.K, Pass{Dot{r.strength, a0, a1}});  // (the getters then answer for it)
 }
 
 }  // namespace
 
+extern "C" {
+
+int hq_set_dither_map(hq_ctx* c, const float* map, int mw, int mh) {
+    if (!c) return HQ_ERR_ARG;
+    if (map) {
+        auto side = [](int v) { return v >= 1 && v <= kMaxMapSide && (v & (v - 1)) == 0; };
+        if (!side(mw) || !side(mh))
+            return fail(c, HQ_ERR_ARG, "map of %d x %d: each side a power of two in 1 .. %d", mw, mh, kMaxMapSide);
+        for (int i = 0; i < mw * mh; ++i)
+            if (!(map[i] >= -0.5f && map[i] <= 0.5f))
+                return fail(c, HQ_ERR_ARG, "map[%d] = %g not in [-0.5, 0.5]", i, map[i]);
+        c->dmap.assign(map, map + (size_t)mw * mh);
+        c->dmap_w = mw;
+        c->dmap_h = mh;
+    } else {
+        c->dmap.clear();
+        c->dmap_w = c->dmap_h = 0;
+    }
+    c->dmap_dirty = true;  // (uploaded by the next ordered evaluation or search run: ensure_dither_map)
+    return HQ_OK;
+}
+
+int hq_ordered_population(hq_ctx* c, const float* palettes, int P, int K, const float amp[3], float delta,
+                          double* costs, int32_t* used) {
+    const int rc = ordered_into_hout(c, RenderCall{palettes, costs, P, K, false, true, amp, 0.f});
+    return rc ? rc : costs_from_hout(c, P, K, delta, costs, used);
+}
+
+int hq_ordered_population_partial(hq_ctx* c, const float* palettes, int P, int K, const float amp[3],
+                                  double* partial) {
+    const int rc = ordered_into_hout(c, RenderCall{palettes, partial, P, K, true, true, amp, 0.f});
+    return rc ? rc : partial_from_hout(c, P, K, partial);
+}
+
+int hq_eval_population_partial(hq_ctx* c, const float* palettes, int P, int K, double* partial) {
+    if (!partial) return fail(c, HQ_ERR_ARG, "null output");
+    const int rc = eval_partial_into_hout(c, palettes, P, K);
+    return rc ? rc : partial_from_hout(c, P, K, partial);
+}
+
+int hq_eval_population(hq_ctx* c, const float* palettes, int P, int K, float delta,
+                       double* costs, int32_t* used) {
+    if (!costs) return fail(c, HQ_ERR_ARG, "null output");
+    int rc = eval_partial_into_hout(c, palettes, P, K);
+    if (rc) return rc;
+    if ((!whole_image(c) || c->slice_ranks > 1) && !(c->comm && c->nranks > 1))
+        return fail(c, HQ_ERR_STATE, "sharded context or palette slice without a communicator: use "
+                                     "hq_eval_population_partial");
+    costs_from_hout(c, P, K, delta, costs, used);
+    return HQ_OK;
+}
+
+// (the Floyd-Steinberg preset; its taps, whoever gives them, take the kernel's own formula: hq.h)
 int hq_dither_population(hq_ctx* c, const float* palettes, int P, int K, float strength, float delta,
                          double* costs, int32_t* used) {
-    if (!c) return HQ_ERR_ARG;
     hq_diffusion_taps fs;
     hq_diffusion_preset(HQ_DIFFUSION_FLOYD_STEINBERG, &fs);
-    return dither_population(c, palettes, P, K, fs, strength, delta, costs, used);
+    return hq_diffuse_population(c, palettes, P, K, &fs, strength, delta, costs, used);
 }
 
 int hq_diffuse_population(hq_ctx* c, const float* palettes, int P, int K, const hq_diffusion_taps* taps,
                           float strength, float delta, double* costs, int32_t* used) {
     if (!c) return HQ_ERR_ARG;
     if (!hq_diffusion_taps_legal(taps)) return fail(c, HQ_ERR_ARG, "null or illegal diffusion taps (hq.h)");
-    return dither_population(c, palettes, P, K, *taps, strength, delta, costs, used);
+    int rc = check_rendered(c, RenderCall{palettes, costs, P, K, false, false, nullptr, strength},
+                            [&] { return whole_image_only(c, "hq_dither_population (error diffusion)"); });
+    if (rc) return rc;
+    Diffused d{strength, *taps, 0, 0, false};
+    if (hq_diffusion_classify(taps, &d.rows, &d.slope)) return fail(c, HQ_ERR_ARG, "illegal diffusion taps");
+    hq_diffusion_taps fs;
+    hq_diffusion_preset(HQ_DIFFUSION_FLOYD_STEINBERG, &fs);
+    d.floyd_steinberg = !std::memcmp(&fs, taps, sizeof fs);
+    rc = run_pass(c, palettes, P, K, Pass{d});  // (the getters then answer for the rendering)
+    return rc ? rc : costs_from_hout(c, P, K, delta, costs, used);
 }
 
 int hq_dot_population(hq_ctx* c, const float* palettes, int P, int K, const hq_dot_classes* cls, float strength,
                       float delta, double* costs, int32_t* used) {
     if (!c) return HQ_ERR_ARG;
-    hq_dot_classes knuth;
-    hq_dot_preset(HQ_DOT_KNUTH8, &knuth);
-    if (cls && !hq_dot_classes_legal(cls))
-        return fail(c, HQ_ERR_ARG, "illegal class matrix: side 4, 8 or 16 and a permutation of 0 .. n*n - 1 (hq.h)");
-    return dither_population(c, palettes, P, K, hq_diffusion_taps{}, strength, delta, costs, used, cls ? cls : &knuth);
+    const int rc = dot_into_hout(c, RenderCall{palettes, costs, P, K, false, false, nullptr, strength}, cls);
+    return rc ? rc : costs_from_hout(c, P, K, delta, costs, used);
 }
 
 int hq_dot_population_partial(hq_ctx* c, const float* palettes, int P, int K, const hq_dot_classes* cls,
                               float strength, double* partial) {
     if (!c) return HQ_ERR_ARG;
     if (!partial) return fail(c, HQ_ERR_ARG, "null output");
-    hq_dot_classes knuth;
-    hq_dot_preset(HQ_DOT_KNUTH8, &knuth);
-    if (cls && !hq_dot_classes_legal(cls))
-        return fail(c, HQ_ERR_ARG, "illegal class matrix: side 4, 8 or 16 and a permutation of 0 .. n*n - 1 (hq.h)");
-    return dither_population(c, palettes, P, K, hq_diffusion_taps{}, strength, 0.0f, nullptr, nullptr,
-                             cls ? cls : &knuth, partial);
+    const int rc = dot_into_hout(c, RenderCall{palettes, partial, P, K, true, false, nullptr, strength}, cls);
+    return rc ? rc : partial_from_hout(c, P, K, partial);
 }
 
 int hq_get_indices(hq_ctx* c, int p, uint8_t* idx) {

@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <cstring>
 #include <string>
+#include <variant>
 #include <vector>
 
 #include "hq_launch.h"
@@ -165,7 +166,24 @@ inline hipError_t timed_launch(ProfRec& pr, Pair p, F&& launch, bool start = tru
 }
 
 // ---- a pass: how far an evaluation goes and how its index images are made -------
-// Full: grid, assign, cost, finalize into d_out, the collective on d_out.
+// The rendering, how the argmin stage makes the index images: one alternative, with its own
+// parameters and nobody else's (hq.h says what each computes).
+//   Plain: grid, then assign.
+//   Ordered: the same grid, then assign's ordered-dithering instances with the context's
+//     threshold map at `amp` per channel.  K <= 256.
+//   Diffused: the counter set and the used bits zeroed as without a grid, then diffuse_kernel's
+//     instance <rows, slope> (hq_diffusion_classify) of `taps` in the place of grid + assign.
+//     floyd_steinberg: that preset's taps, whoever gave them: the kernel's own formula, no instance.
+//   Dot: zeroed the same way, then dot_kernel's launches under the context's class matrix (c->dot_cls,
+//     its tables on the device: ensure_dot_tables); on a row-block shard its windowed instance over rows
+//     [a0, a1), the extended rows and what of the apron the matrix's reach needs (dot_window).
+struct Plain {};
+struct Ordered { float amp[3]; };
+struct Diffused { float strength; hq_diffusion_taps taps; int rows, slope; bool floyd_steinberg; };
+struct Dot { float strength; int a0, a1; };
+using Rendering = std::variant<Plain, Ordered, Diffused, Dot>;
+
+// The kind, how far the pass goes.  Full: grid, assign, cost, finalize into d_out, the collective on d_out.
 // Fold: a folding search's evaluation -- no finalize (the accept step reads the
 //   fixed-point sums itself); the collective gathers the ranks' counter blocks.
 // AssignOnly (a hybrid iteration's first pass): the argmin alone -- grid build or
@@ -173,13 +191,8 @@ inline hipError_t timed_launch(ProfRec& pr, Pair p, F&& launch, bool start = tru
 // CostOnly (a repair iteration's first pass): grid, assign and cost -- the index
 //   images and, with option "pixel_err" in force, the error image the error kernel
 //   reads.
-// Dither (hq_dither_population, hq_diffuse_population): a full pass whose index
-//   images are the error-diffused rendering under the pass's taps at `strength` --
-//   the counter set and the used bits zeroed as without a grid, then diffuse_kernel
-//   (hq_diffuse.hip) in the place of grid + assign.  With `dot` set (hq_dot_population) the
-//   rendering is dot diffusion's under the context's class matrix (c->dot_cls, its tables on
-//   the device: ensure_dot_tables): dot_kernel's launches (hq_dot.hip) in that place instead --
-//   on a row-block shard (hq_dot_population_partial) its windowed instance over the pass's rows.
+// Any kind may be plain or ordered.  A diffused or dot rendering exists on a full pass only: its
+// constructors take no kind, and the members are const.
 // Counter-set parity: each pass takes the other counter set than the last one
 // (build_grid zeroes it), so an accept step can read the last set while the next
 // is filled.  A side pass (AssignOnly, CostOnly: nothing reads its sums, so no
@@ -187,26 +200,18 @@ inline hipError_t timed_launch(ProfRec& pr, Pair p, F&& launch, bool start = tru
 // one: c->acc_par stays the set of the last full pass (what sa_args, the fold and
 // the finalize read), and the full pass that follows takes, and zeroes, the same
 // set again.
-// Ordered (hq_ordered_population, hq_search_set_ordered): any of the argmin kinds
-//   above with `ordered` set -- the same grid, then assign's ordered-dithering
-//   instances with the context's threshold map and `amp` (launch_assign_ordered);
-//   everything after the index images is the kind's own.  K <= 256.
 struct Pass {
-    enum Kind { Full, Fold, AssignOnly, CostOnly, Dither } kind = Full;
-    float strength = 0.f;  // Dither
-    // Dither: the tap set (hq_dither_population: the Floyd-Steinberg preset), its instance
-    // <diffuse_rows, diffuse_slope> of diffuse_kernel (hq_diffusion_classify), and whether the
-    // taps are Floyd-Steinberg's, which take that kernel's own formula (hq.h) and report
-    // HQ_ARGMIN_DITHER with no instance.
-    hq_diffusion_taps taps{};
-    int diffuse_rows = 0, diffuse_slope = 0;
-    bool fs = false;
-    bool dot = false;  // Dither: dot diffusion (taps, diffuse_rows, diffuse_slope and fs unused)
-    // ... on a row-block shard: dot_kernel's windowed instance over rows [dot_a0, dot_a1), the
-    // extended rows and what of the apron the matrix's reach needs (dot_window)
-    int dot_a0 = 0, dot_a1 = 0;
-    bool ordered = false;
-    float amp[3] = {0.f, 0.f, 0.f};  // ordered: the amplitude per channel
+    enum Kind { Full, Fold, AssignOnly, CostOnly };
+    const Kind kind;
+    const Rendering rendering;
+    Pass(Kind k = Full) : kind(k) {}
+    Pass(Kind k, const Ordered& o) : kind(k), rendering(o) {}
+    Pass(const Diffused& d) : kind(Full), rendering(d) {}
+    Pass(const Dot& d) : kind(Full), rendering(d) {}
+    template <typename R>
+    const R* as() const { return std::get_if<R>(&rendering); }     // the alternative's parameters, or null
+    bool rendered() const { return !as<Plain>(); }                 // the getters answer for a rendering
+    bool gridless() const { return as<Diffused>() || as<Dot>(); }  // no grid is built: HQ_PASS_DITHER
     bool side() const { return kind == AssignOnly || kind == CostOnly; }
     Pair pairs() const { return kind == AssignOnly ? kPLloydGrid : kind == CostOnly ? kPRepGrid : kPGrid; }
 };
@@ -287,7 +292,7 @@ struct hq_ctx {
     int planar_ok = -1;
     hq::DevBuf d_hist;             // hq_color_histogram: [2^(3 bits)][4] int64 cells, then the range flag
     hq::DevBuf d_errstat, d_worst; // [P][K][4] u64 statistics, then the flag; [P][K] float4 worst pixels
-    hq::DevBuf d_dcarry;           // a Dither pass: [P][R][3][W] errors of a strip's last R rows (DiffuseArgs::carry)
+    hq::DevBuf d_dcarry;           // a Diffused pass: [P][R][3][W] errors of a strip's last R rows (DiffuseArgs::carry)
     // dot diffusion: the class matrix of the last hq_dot_population (n = 0: none yet), its two
     // per-cell tables on the device ([2][kDotCells] words, uploaded when the matrix changes:
     // ensure_dot_tables) and the errors e of a Dot pass ([P][3][H][W] floats, never zeroed)
@@ -404,7 +409,7 @@ struct hq_search {
     int repair_moves = -1;               // ... at most so many colours per palette (< 0: no limit)
     int nch = 1;                         // chunked palettes (256 < K <= 16384): chunks per palette
     bool ordered = false;                // hq_search_set_ordered: every evaluation is the ordered one
-    float amp[3] = {0.f, 0.f, 0.f};      // ... at this amplitude per channel
+    hq::Ordered ord{};                   // ... at this amplitude per channel
     int nfixed = 0;                      // the context's fixed colours at hq_search_create: colours
     std::vector<float> fixed;            // 0 .. nfixed-1 of every member, [nfixed][4], for the search's life
     bool fold = false;                   // accept steps reduce the partials (no finalize launch)
@@ -508,7 +513,7 @@ int upload_and_prep(hq_ctx* c, const float* host, const void* dev, int P, int K)
 PaletteArgs prep_args(hq_ctx* c, int K);
 uint64_t* acc_base(hq_ctx* c, int par, int P);
 uint32_t* used_base(hq_ctx* c, int par, int Ps);
-int enqueue_core(hq_ctx* c, int P, int K, ProfRec& pr, Pass pass = {});
+int enqueue_core(hq_ctx* c, int P, int K, ProfRec& pr, const Pass& pass = {});
 void pack_chunks(const float* pal, int P, int K, int nch, float* out);
 ClusterArgs cluster_args(hq_ctx* c, int P, int K, int nch, int* idx_bytes);
 ClusterErrArgs cluster_err_args(hq_ctx* c, int P, int K, int nch, int* idx_bytes);

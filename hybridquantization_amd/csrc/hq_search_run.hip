@@ -167,10 +167,8 @@ void search_commit(hq_search* s, int rc, int evaluations) {
 // A search's evaluation pass: folding (search_folds) or full.
 // (hq_search_set_ordered: the ordered one at the search's amplitude)
 Pass search_pass(const hq_search* s) {
-    Pass p{s->fold ? Pass::Fold : Pass::Full};
-    p.ordered = s->ordered;
-    for (int ch = 0; ch < 3; ++ch) p.amp[ch] = s->amp[ch];
-    return p;
+    const Pass::Kind kind = s->fold ? Pass::Fold : Pass::Full;
+    return s->ordered ? Pass{kind, s->ord} : Pass{kind};
 }
 
 // A search under the ordered cost moves by annealing alone: a k-means or repair move from a
@@ -443,7 +441,7 @@ int hq_search_create_from(hq_ctx* c, const hq_swasa_params* params, int K, uint6
     } else {
         const float delta = params->delta;
         auto eval = [c, delta, s](const float* pal, int P, int KK, double* costs) {
-            return s->ordered ? hq_ordered_population(c, pal, P, KK, s->amp, delta, costs, nullptr)
+            return s->ordered ? hq_ordered_population(c, pal, P, KK, s->ord.amp, delta, costs, nullptr)
                               : hq_eval_population(c, pal, P, KK, delta, costs, nullptr);
         };
         s->driver = new SearchDriver(*params, K, seed, eval);
@@ -532,21 +530,18 @@ int hq_search_set_ordered(hq_search* s, const float amp[3]) {
             return fail(c, HQ_ERR_UNSUPPORTED, "a search with hybrid or repair iterations: no ordered cost");
         if (int rc = ordered_scope(c, s->K)) return rc;
     }
-    if (on == s->ordered && (!on || (amp[0] == s->amp[0] && amp[1] == s->amp[1] && amp[2] == s->amp[2])))
+    const Ordered old = s->ord;
+    if (on == s->ordered && (!on || (amp[0] == old.amp[0] && amp[1] == old.amp[1] && amp[2] == old.amp[2])))
         return HQ_OK;  // (nothing changes: nothing is enqueued)
     const bool was = s->ordered;
-    const float old[3] = {s->amp[0], s->amp[1], s->amp[2]};
     s->ordered = on;
-    for (int ch = 0; ch < 3; ++ch) s->amp[ch] = on ? amp[ch] : 0.f;  // (zeros: the plain pass itself)
+    for (int ch = 0; ch < 3; ++ch) s->ord.amp[ch] = on ? amp[ch] : 0.f;  // (zeros: the plain pass itself)
     const int ite = s->driver ? s->driver->iteration() : s->ite;
     if (ite != 0) return HQ_OK;
     // before the first iteration: the initial population's errors and its best are the new evaluation's
     const int rc = s->driver ? s->driver->rerank() : device_search_rerank(s);
     search_commit(s, rc, 1);
-    if (rc) {
-        s->ordered = was;
-        for (int ch = 0; ch < 3; ++ch) s->amp[ch] = old[ch];
-    }
+    if (rc) s->ordered = was, s->ord = old;
     return rc;
 }
 

@@ -19,6 +19,7 @@ method instead of returning zeros.
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 
 import numpy as np
 
@@ -35,6 +36,15 @@ class deltaETypes:  # IM:20
 
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+class _Rendering(namedtuple("_Rendering", "name method parameter kw error_attr verbose")):
+    """A rendering findBestQuantization was asked for: its *Population method with its parameter (a
+    strength, the amplitudes) and keywords, the bestError* attribute its cost goes to, and the verbose
+    line's format over (parameter, cost)."""
+
+    def population(self, palettes, delta):
+        return self.method(palettes, self.parameter, delta, **self.kw)
 
 
 def pack_filters(filters, absfilters):
@@ -189,16 +199,36 @@ class ImageManipulation:
         check(self._lib.hq_set_image_reduced(ctx, src._require(), int(factor), None if il is None else fptr(il)), ctx)
         self.w, self.h = self.reducedSize(src.w, src.h, factor)
 
+    @staticmethod
+    def _population(colors):
+        """colors: (P, 4K) or list of float[4K] palettes -> (a float32 (P, 4K) array of its own, P, K)."""
+        pal = _f32(np.stack([np.asarray(c, np.float32).reshape(-1) for c in colors]))
+        return pal, pal.shape[0], pal.shape[1] // 4
+
+    @staticmethod
+    def _outputs(P, K, partial=False):
+        """A population call's outputs: (costs (P,), used (P, K)), or ``partial`` the (P, 1 + K) rows."""
+        return np.zeros((P, 1 + K), np.float64) if partial else (np.zeros(P, np.float64), np.zeros((P, K), np.int32))
+
     # IM:620 computeQuantizationErrorPopulation
     def computeQuantizationErrorPopulation(self, colors, delta: float = 2.0, return_used=False):
         """colors: (P, 4K) or list of float[4K] palettes -> costs (P,) [, used (P, K)]."""
+        return self._populationCall(self._lib.hq_eval_population, colors, (), delta, return_used)
+
+    def _populationCall(self, fn, colors, mid, delta=None, return_used=False):
+        """fn(ctx, palettes, P, K, *mid, delta, costs, used) -> costs (P,) [, used (P, K)]; delta None, a
+        _partial entry point: fn(ctx, palettes, P, K, *mid, partial) -> the (P, 1 + K) rows.  ``mid`` may be
+        a callable, made once the palettes are stacked; a float32 array in it goes as its pointer."""
         ctx = self._require()
-        pal = _f32(np.stack([np.asarray(c, np.float32).reshape(-1) for c in colors]))
-        P, K = pal.shape[0], pal.shape[1] // 4
-        costs = np.zeros(P, np.float64)
-        used = np.zeros((P, K), np.int32)
-        check(self._lib.hq_eval_population(ctx, fptr(pal), P, K, float(delta), dptr(costs),
-                                           iptr(used)), ctx)
+        pal, P, K = self._population(colors)
+        held = mid() if callable(mid) else mid  # (alive until the call has returned)
+        mid = [fptr(x) if isinstance(x, np.ndarray) else x for x in held]
+        if delta is None:
+            part = self._outputs(P, K, partial=True)
+            check(fn(ctx, fptr(pal), P, K, *mid, dptr(part)), ctx)
+            return part
+        costs, used = self._outputs(P, K)
+        check(fn(ctx, fptr(pal), P, K, *mid, float(delta), dptr(costs), iptr(used)), ctx)
         return (costs, used) if return_used else costs
 
     def getIndices(self, p: int = 0):
@@ -249,15 +279,17 @@ class ImageManipulation:
     def refinePopulation(self, colors, steps, delta: float = 2.0, keep_best=True, return_trace=False):
         """hq_refine_population: `steps` k-means steps on each palette of colors (P, 4K).
         Returns (palettes (P, 4K), costs (P,), used (P, K)) [, trace (steps + 1, P)]."""
+        return self._improve(self._lib.hq_refine_population, colors, steps, (float(delta), int(bool(keep_best))),
+                             return_trace)
+
+    def _improve(self, fn, colors, steps, mid, return_trace):
+        """hq_refine_population's and hq_repair_population's call: fn(ctx, palettes, P, K, steps, *mid, costs,
+        used, trace)."""
         ctx = self._require()
-        pal = _f32(np.stack([np.asarray(c, np.float32).reshape(-1) for c in colors])).copy()
-        P, K = pal.shape[0], pal.shape[1] // 4
-        costs = np.zeros(P, np.float64)
-        used = np.zeros((P, K), np.int32)
+        pal, P, K = self._population(colors)
+        costs, used = self._outputs(P, K)
         trace = np.zeros((int(steps) + 1, P), np.float64)
-        check(self._lib.hq_refine_population(ctx, fptr(pal), P, K, int(steps), float(delta),
-                                             int(bool(keep_best)), dptr(costs), iptr(used),
-                                             dptr(trace)), ctx)
+        check(fn(ctx, fptr(pal), P, K, int(steps), *mid, dptr(costs), iptr(used), dptr(trace)), ctx)
         return (pal, costs, used, trace) if return_trace else (pal, costs, used)
 
     # repairing unused colours: libhq's additions (hq_cluster_errors & co., no reference counterpart)
@@ -292,16 +324,8 @@ class ImageManipulation:
                          return_trace=False):
         """hq_repair_population: `steps` repair steps on each palette of colors (P, 4K).
         Returns (palettes (P, 4K), costs (P,), used (P, K)) [, trace (steps + 1, P)]."""
-        ctx = self._require()
-        pal = _f32(np.stack([np.asarray(c, np.float32).reshape(-1) for c in colors])).copy()
-        P, K = pal.shape[0], pal.shape[1] // 4
-        costs = np.zeros(P, np.float64)
-        used = np.zeros((P, K), np.int32)
-        trace = np.zeros((int(steps) + 1, P), np.float64)
-        check(self._lib.hq_repair_population(ctx, fptr(pal), P, K, int(steps), float(delta),
-                                             int(max_moves), int(bool(keep_best)), dptr(costs),
-                                             iptr(used), dptr(trace)), ctx)
-        return (pal, costs, used, trace) if return_trace else (pal, costs, used)
+        return self._improve(self._lib.hq_repair_population, colors, steps,
+                             (float(delta), int(max_moves), int(bool(keep_best))), return_trace)
 
     # dithered rendering: libhq's addition (hq_dither_population, no reference counterpart)
     @staticmethod
@@ -338,19 +362,10 @@ class ImageManipulation:
         dithered rendering; clusterSums and clusterErrors need a plain evaluation again.
         ``kernel`` (hq_diffuse_population): another diffusion kernel, a preset's name
         (diffusionPreset) or (3 x 5 array, div); None is hq_dither_population."""
-        ctx = self._require()
-        taps = None if kernel is None else self._taps(kernel)
-        pal = _f32(np.stack([np.asarray(c, np.float32).reshape(-1) for c in colors]))
-        P, K = pal.shape[0], pal.shape[1] // 4
-        costs = np.zeros(P, np.float64)
-        used = np.zeros((P, K), np.int32)
-        if taps is None:
-            check(self._lib.hq_dither_population(ctx, fptr(pal), P, K, float(strength), float(delta),
-                                                 dptr(costs), iptr(used)), ctx)
-        else:
-            check(self._lib.hq_diffuse_population(ctx, fptr(pal), P, K, C.byref(taps), float(strength),
-                                                  float(delta), dptr(costs), iptr(used)), ctx)
-        return (costs, used) if return_used else costs
+        self._require()
+        fn, mid = ((self._lib.hq_dither_population, ()) if kernel is None else
+                   (self._lib.hq_diffuse_population, (C.byref(self._taps(kernel)),)))
+        return self._populationCall(fn, colors, mid + (float(strength),), delta, return_used)
 
     def quantizeDithered(self, colors, strength: float = 1.0, kernel=None):
         """The dithered rendering of the context's image (setImage, findBestQuantization)
@@ -358,12 +373,18 @@ class ImageManipulation:
         image palette[idx] with .w = 0, the indices read back from the device and gathered
         on the host.  Sets ``lastUsedColors`` and ``ditherError``, the rendering's mean dE.
         ``kernel``: ditherPopulation's."""
+        return self._quantizeRendered(
+            colors, lambda p: self.ditherPopulation(p, strength, 0.0, return_used=True, kernel=kernel), "ditherError")
+
+    def _quantizeRendered(self, colors, population_call, error_attr):
+        """The three quantize* renderings' body: population_call(pal (1, 4K)) -> (costs, used)
+        renders on the device; its cost goes to the attribute ``error_attr``."""
         pal = _f32(colors).reshape(1, -1)
-        costs, used = self.ditherPopulation(pal, strength, 0.0, return_used=True, kernel=kernel)
+        costs, used = population_call(pal)
         table = pal.reshape(-1, 4).copy()
         table[:, 3] = 0.0
         self.lastUsedColors = used[0]
-        self.ditherError = float(costs[0])
+        setattr(self, error_attr, float(costs[0]))
         return table[self.getIndices(0)].reshape(-1)
 
     # dot diffusion: libhq's addition (hq_dot_population, no reference counterpart)
@@ -400,27 +421,16 @@ class ImageManipulation:
         side 4, 8 or 16 holding a permutation of 0 .. n*n - 1; None is Knuth's 8 x 8.
         getIndices and getPixelErrors then answer for this rendering; clusterSums and
         clusterErrors need a plain evaluation again."""
-        ctx = self._require()
-        m = None if classes is None else self._classes(classes)
-        pal = _f32(np.stack([np.asarray(c, np.float32).reshape(-1) for c in colors]))
-        P, K = pal.shape[0], pal.shape[1] // 4
-        costs = np.zeros(P, np.float64)
-        used = np.zeros((P, K), np.int32)
-        check(self._lib.hq_dot_population(ctx, fptr(pal), P, K, None if m is None else C.byref(m), float(strength),
-                                          float(delta), dptr(costs), iptr(used)), ctx)
-        return (costs, used) if return_used else costs
+        self._require()
+        mid = (None if classes is None else C.byref(self._classes(classes)), float(strength))
+        return self._populationCall(self._lib.hq_dot_population, colors, mid, delta, return_used)
 
     def quantizeDotDiffused(self, colors, strength: float = 1.0, classes=None):
         """The dot-diffused rendering of the context's image with the palette colors float[4K],
         in ``quantize``'s output format (quantizeDithered's way).  Sets ``lastUsedColors`` and
         ``dotError``, the rendering's mean dE.  ``classes``: dotPopulation's."""
-        pal = _f32(colors).reshape(1, -1)
-        costs, used = self.dotPopulation(pal, strength, 0.0, classes=classes, return_used=True)
-        table = pal.reshape(-1, 4).copy()
-        table[:, 3] = 0.0
-        self.lastUsedColors = used[0]
-        self.dotError = float(costs[0])
-        return table[self.getIndices(0)].reshape(-1)
+        return self._quantizeRendered(
+            colors, lambda pal: self.dotPopulation(pal, strength, 0.0, classes=classes, return_used=True), "dotError")
 
     @classmethod
     def dotReach(cls, classes=None):
@@ -438,10 +448,14 @@ class ImageManipulation:
         """hq_dot_apron: (above, below), the image rows this context holds beyond its extended
         rows on each side (option "dot_apron" when the shard was set, clipped at the image's
         border; (0, 0) on a whole image)."""
+        return self._values(self._lib.hq_dot_apron, 2)
+
+    def _values(self, fn, n, ctype=C.c_int):
+        """fn(ctx, n pointers to ctype) -> the n values it wrote."""
         ctx = self._require()
-        above, below = C.c_int(0), C.c_int(0)
-        check(self._lib.hq_dot_apron(ctx, C.byref(above), C.byref(below)), ctx)
-        return above.value, below.value
+        v = [ctype() for _ in range(n)]
+        check(fn(ctx, *[C.byref(x) for x in v]), ctx)
+        return tuple(x.value for x in v)
 
     def dotPopulationPartial(self, colors, strength: float = 1.0, classes=None):
         """hq_dot_population_partial: the shard-local (P, 1 + K) partial rows of the dot-diffused
@@ -450,14 +464,9 @@ class ImageManipulation:
         OR, and each shard's getIndices are the whole image's rows, bit for bit.  A row-block
         shard must hold an apron of at least dotReach(classes) rows on each side (or up to the
         image's border); the sum across shards or ranks is the caller's."""
-        ctx = self._require()
-        m = None if classes is None else self._classes(classes)
-        pal = _f32(np.stack([np.asarray(c, np.float32).reshape(-1) for c in colors]))
-        P, K = pal.shape[0], pal.shape[1] // 4
-        part = np.zeros((P, 1 + K), np.float64)
-        check(self._lib.hq_dot_population_partial(ctx, fptr(pal), P, K, None if m is None else C.byref(m),
-                                                  float(strength), dptr(part)), ctx)
-        return part
+        self._require()
+        mid = (None if classes is None else C.byref(self._classes(classes)), float(strength))
+        return self._populationCall(self._lib.hq_dot_population_partial, colors, mid)
 
     # ordered dithering: libhq's addition (hq_ordered_population, no reference counterpart)
     @staticmethod
@@ -505,37 +514,19 @@ class ImageManipulation:
         map at its position.  colors (P, 4K), K <= 256 -> costs (P,) [, used (P, K)]; amp 0 is
         the plain evaluation, bit for bit.  getIndices and getPixelErrors then answer for this
         rendering; clusterSums and clusterErrors need a plain evaluation again."""
-        ctx = self._require()
-        pal = _f32(np.stack([np.asarray(c, np.float32).reshape(-1) for c in colors]))
-        P, K = pal.shape[0], pal.shape[1] // 4
-        a = self._amp3(amp)
-        costs = np.zeros(P, np.float64)
-        used = np.zeros((P, K), np.int32)
-        check(self._lib.hq_ordered_population(ctx, fptr(pal), P, K, fptr(a), float(delta),
-                                              dptr(costs), iptr(used)), ctx)
-        return (costs, used) if return_used else costs
+        return self._populationCall(self._lib.hq_ordered_population, colors, lambda: (self._amp3(amp),), delta,
+                                    return_used)
 
     def orderedPopulationPartial(self, colors, amp):
         """hq_ordered_population_partial: the shard-local (P, 1 + K) partial rows."""
-        ctx = self._require()
-        pal = _f32(np.stack([np.asarray(c, np.float32).reshape(-1) for c in colors]))
-        P, K = pal.shape[0], pal.shape[1] // 4
-        a = self._amp3(amp)
-        part = np.zeros((P, 1 + K), np.float64)
-        check(self._lib.hq_ordered_population_partial(ctx, fptr(pal), P, K, fptr(a), dptr(part)), ctx)
-        return part
+        return self._populationCall(self._lib.hq_ordered_population_partial, colors, lambda: (self._amp3(amp),))
 
     def quantizeOrdered(self, colors, amp):
         """The ordered-dither rendering of the context's image with the palette colors
         float[4K], in ``quantize``'s output format (quantizeDithered's way).  Sets
         ``lastUsedColors`` and ``orderedError``, the rendering's mean dE."""
-        pal = _f32(colors).reshape(1, -1)
-        costs, used = self.orderedPopulation(pal, amp, 0.0, return_used=True)
-        table = pal.reshape(-1, 4).copy()
-        table[:, 3] = 0.0
-        self.lastUsedColors = used[0]
-        self.orderedError = float(costs[0])
-        return table[self.getIndices(0)].reshape(-1)
+        return self._quantizeRendered(
+            colors, lambda pal: self.orderedPopulation(pal, amp, 0.0, return_used=True), "orderedError")
 
     # a pixel mask on the cost: libhq's addition (hq_set_mask, no reference counterpart)
     def setMask(self, mask=None):
@@ -547,26 +538,28 @@ class ImageManipulation:
         if mask is None:
             check(self._lib.hq_set_mask(ctx, None, 0, 0), ctx)
             return
-        m = np.asarray(mask)
-        if m.dtype != np.bool_ and not np.issubdtype(m.dtype, np.integer):
-            raise ValueError(f"mask of dtype {m.dtype}: an integer or bool array")
-        if m.ndim not in (1, 2):
-            raise ValueError(f"mask of shape {m.shape}: (h, w) or flat")
-        w, h = getattr(self, "w", 0), getattr(self, "h", 0)
-        if (m.ndim == 2 and m.shape != (h, w)) or m.size != w * h:
-            raise ValueError(f"mask of shape {m.shape} on an image of {h} x {w}")
+        m, w, h = self._pixelMap(mask, "mask")
         m = np.ascontiguousarray((m != 0).reshape(-1), dtype=np.uint8)
         check(self._lib.hq_set_mask(ctx, _lib.u8ptr(m), w, h), ctx)
+
+    def _pixelMap(self, src, noun):
+        """setMask's and setWeights' argument as an array of the image's shape -> (it, w, h)."""
+        m = np.asarray(src)
+        if m.dtype != np.bool_ and not np.issubdtype(m.dtype, np.integer):
+            raise ValueError(f"{noun} of dtype {m.dtype}: an integer or bool array")
+        if m.ndim not in (1, 2):
+            raise ValueError(f"{noun} of shape {m.shape}: (h, w) or flat")
+        w, h = getattr(self, "w", 0), getattr(self, "h", 0)
+        if (m.ndim == 2 and m.shape != (h, w)) or m.size != w * h:
+            raise ValueError(f"{noun} of shape {m.shape} on an image of {h} x {w}")
+        return m, w, h
 
     def maskInfo(self):
         """hq_mask_info -> (n_full, n_owned, tiles_run, tiles_all): the in-mask pixels of the
         full image (w h without a mask) and of the owned rows, and the output tiles per palette
         the last evaluation's fast cost pass launched / would launch without a mask (0, 0 when
         it took the generic path)."""
-        ctx = self._require()
-        v = [C.c_int64() for _ in range(4)]
-        check(self._lib.hq_mask_info(ctx, *[C.byref(x) for x in v]), ctx)
-        return tuple(x.value for x in v)
+        return self._values(self._lib.hq_mask_info, 4, C.c_int64)
 
     # pixel weights on the cost: libhq's addition (hq_set_weights, no reference counterpart)
     def setWeights(self, weights=None):
@@ -583,14 +576,7 @@ class ImageManipulation:
         if weights is None:
             check(self._lib.hq_set_weights(ctx, None, 0, 0), ctx)
             return
-        m = np.asarray(weights)
-        if m.dtype != np.bool_ and not np.issubdtype(m.dtype, np.integer):
-            raise ValueError(f"weights of dtype {m.dtype}: an integer or bool array")
-        if m.ndim not in (1, 2):
-            raise ValueError(f"weights of shape {m.shape}: (h, w) or flat")
-        w, h = getattr(self, "w", 0), getattr(self, "h", 0)
-        if (m.ndim == 2 and m.shape != (h, w)) or m.size != w * h:
-            raise ValueError(f"weights of shape {m.shape} on an image of {h} x {w}")
+        m, w, h = self._pixelMap(weights, "weights")
         if m.size and (int(m.min()) < 0 or int(m.max()) > 255):
             raise ValueError(f"weights in {int(m.min())} .. {int(m.max())}: bytes, 0 .. 255")
         m = np.ascontiguousarray(m.reshape(-1), dtype=np.uint8)
@@ -659,10 +645,7 @@ class ImageManipulation:
     def weightsInfo(self):
         """hq_weights_info -> (w_full, w_owned): the sum of the weights over the full image and
         over the owned rows (under a mask or with nothing set: maskInfo's n_full, n_owned)."""
-        ctx = self._require()
-        v = [C.c_int64() for _ in range(2)]
-        check(self._lib.hq_weights_info(ctx, *[C.byref(x) for x in v]), ctx)
-        return tuple(x.value for x in v)
+        return self._values(self._lib.hq_weights_info, 2, C.c_int64)
 
     # seeding the search from the image: libhq's additions (hq_color_histogram, hq_median_cut)
     def colorHistogram(self, bits: int = 5):
@@ -794,10 +777,9 @@ class ImageManipulation:
         nfx = 0 if fx is None else fx.shape[0]
         if mask is not None and weights is not None:
             raise ValueError("mask and weights: one piece of state, give one of them")
-        if mask is not None and (int(repairEvery) != 0 or int(repairSteps) != 0):
-            raise ValueError("mask with repairEvery or repairSteps: no masked error statistic")
-        if weights is not None and (int(repairEvery) != 0 or int(repairSteps) != 0):
-            raise ValueError("weights with repairEvery or repairSteps: no weighted error statistic")
+        for given, noun, adj in ((mask, "mask", "masked"), (weights, "weights", "weighted")):
+            if given is not None and (int(repairEvery) != 0 or int(repairSteps) != 0):
+                raise ValueError(f"{noun} with repairEvery or repairSteps: no {adj} error statistic")
         amp = None if ordered is None else self._amp3(ordered)
         if orderedSearch and (amp is None or not np.any(amp != 0)):
             raise ValueError("orderedSearch needs a non-zero ordered amplitude")
@@ -808,12 +790,17 @@ class ImageManipulation:
             self._taps(ditherKernel)  # (a bad one raises before anything runs)
         if not 0.0 <= dither <= 1.0:
             raise ValueError(f"dither={dither!r}: a strength in [0, 1]")
-        if ditherSearch:
-            if not dither > 0.0:
-                raise ValueError("ditherSearch needs dither > 0")
-            moves = dict(lloydEvery=lloydEvery, repairEvery=repairEvery, lloydSteps=lloydSteps, repairSteps=repairSteps)
+        moves = dict(lloydEvery=lloydEvery, repairEvery=repairEvery, lloydSteps=lloydSteps, repairSteps=repairSteps)
+
+        def host_search_ok(flag, strength_name, strength):
+            """ditherSearch / dotSearch: its rendering is on, and no k-means or repair move with it."""
+            if not strength > 0.0:
+                raise ValueError(f"{flag} needs {strength_name} > 0")
             if any(int(v) != 0 for v in moves.values()):
-                raise ValueError("ditherSearch with " + ", ".join(k for k, v in moves.items() if int(v) != 0))
+                raise ValueError(f"{flag} with " + ", ".join(k for k, v in moves.items() if int(v) != 0))
+
+        if ditherSearch:
+            host_search_ok("ditherSearch", "dither", dither)
         dot = float(dot)
         if dotClasses is not None:
             self._classes(dotClasses)  # (a bad one raises before anything runs)
@@ -822,11 +809,19 @@ class ImageManipulation:
         if dot > 0.0 and (dither > 0.0 or amp is not None):
             raise ValueError("dot with dither or ordered: one rendering")
         if dotSearch:
-            if not dot > 0.0:
-                raise ValueError("dotSearch needs dot > 0")
-            moves = dict(lloydEvery=lloydEvery, repairEvery=repairEvery, lloydSteps=lloydSteps, repairSteps=repairSteps)
-            if any(int(v) != 0 for v in moves.values()):
-                raise ValueError("dotSearch with " + ", ".join(k for k, v in moves.items() if int(v) != 0))
+            host_search_ok("dotSearch", "dot", dot)
+        # the renderings asked for, in the order their final errors are reported, and the one the
+        # search itself optimises (None: the plain cost)
+        sw = simulatedAnnealing
+        rendered = [_Rendering(*r) for on, *r in (
+            (dither > 0.0, "dither", self.ditherPopulation, dither, dict(kernel=ditherKernel), "bestErrorDithered",
+             "Final error, dithered at strength %g : %.5f"),
+            (dot > 0.0, "dot", self.dotPopulation, dot, dict(classes=dotClasses), "bestErrorDot",
+             "Final error, dot-diffused at strength %g : %.5f"),
+            (amp is not None, "ordered", self.orderedPopulation, amp, {}, "bestErrorOrdered",
+             "Final error, ordered dither at amplitude %s : %.5f")) if on]
+        goal = "dot" if dotSearch else "dither" if ditherSearch else "ordered" if orderedSearch else None
+        searched = next((r for r in rendered if r.name == goal), None)
         if not self.openCLFiltersReady:
             self.updateOpenCLFilters(filters, absfilters)
         # Always upload (IM:450-478 does too): an identity cache keyed on id() can
@@ -837,7 +832,6 @@ class ImageManipulation:
             self.setMask(mask)
         if weights is not None:
             self.setWeights(weights)
-        sw = simulatedAnnealing
         params = sw.params()
         handle = C.c_void_p()
         K = int(nbOfColors)
@@ -850,23 +844,14 @@ class ImageManipulation:
             if K - nfx > 0:
                 cells, den = self.colorHistogram(int(initBits))
                 init[4 * nfx:], _ = self.medianCut(cells, int(initBits), den, K - nfx)
+        total = params.imax if iterations is None else min(int(iterations), params.imax)
         if ditherSearch or dotSearch:
             P = params.population
-            total = params.imax if iterations is None else min(int(iterations), params.imax)
-            if dotSearch:
-                def render(ps):
-                    return self.dotPopulation(ps.reshape(P, -1), dot, sw.delta, classes=dotClasses)
-            else:
-                def render(ps):
-                    return self.ditherPopulation(ps.reshape(P, -1), dither, sw.delta, kernel=ditherKernel)
             best, err, _ = sw.search_host(
-                K, render, iterations=total,
+                K, lambda ps: searched.population(ps.reshape(P, -1), sw.delta), iterations=total,
                 initial=None if init is None else initial_population(init, P, K), fixed=fx)
             self.bestError = err
-            if dotSearch:
-                self.bestErrorDot = err
-            else:
-                self.bestErrorDithered = err
+            setattr(self, searched.error_attr, err)
             self.iterations = total
             if self.verbose:
                 print("Final error : %.5f" % err)
@@ -889,7 +874,6 @@ class ImageManipulation:
                 check(self._lib.hq_search_set_lloyd(handle, int(lloydEvery)), ctx)
             if int(repairEvery) != 0:
                 check(self._lib.hq_search_set_repair(handle, int(repairEvery), int(repairMoves)), ctx)
-            total = params.imax if iterations is None else min(int(iterations), params.imax)
             done = 0
             while done < total:
                 if stop is not None and stop():
@@ -924,20 +908,11 @@ class ImageManipulation:
             best, self.bestError = pal[0], float(costs[0])
             if self.verbose:
                 print("Final error after %d k-means steps : %.5f" % (int(lloydSteps), self.bestError))
-        if dither > 0.0:
-            self.bestErrorDithered = float(self.ditherPopulation(best.reshape(1, -1), dither, sw.delta,
-                                                                 kernel=ditherKernel)[0])
+        for r in rendered:  # (the searched one, here the ordered: bestError is already its cost)
+            err = self.bestError if r is searched else float(r.population(best.reshape(1, -1), sw.delta)[0])
+            setattr(self, r.error_attr, err)
             if self.verbose:
-                print("Final error, dithered at strength %g : %.5f" % (dither, self.bestErrorDithered))
-        if dot > 0.0:
-            self.bestErrorDot = float(self.dotPopulation(best.reshape(1, -1), dot, sw.delta, classes=dotClasses)[0])
-            if self.verbose:
-                print("Final error, dot-diffused at strength %g : %.5f" % (dot, self.bestErrorDot))
-        if amp is not None:
-            self.bestErrorOrdered = (self.bestError if orderedSearch else
-                                     float(self.orderedPopulation(best.reshape(1, -1), amp, sw.delta)[0]))
-            if self.verbose:
-                print("Final error, ordered dither at amplitude %s : %.5f" % (amp.tolist(), self.bestErrorOrdered))
+                print(r.verbose % (np.asarray(r.parameter).tolist(), err))
         return best
 
     # IM:770
@@ -973,10 +948,7 @@ class ImageManipulation:
     def commInfo(self) -> tuple[int, int]:
         """(ranks, this rank) of the context's RCCL communicator as RCCL reports
         them; (0, -1) without one."""
-        ctx = self._require()
-        n, r = C.c_int(), C.c_int()
-        check(self._lib.hq_comm_info(ctx, C.byref(n), C.byref(r)), ctx)
-        return n.value, r.value
+        return self._values(self._lib.hq_comm_info, 2)
 
     @staticmethod
     def commUniqueId() -> bytes:
