@@ -143,6 +143,9 @@ SIGNATURES = {
                                     _d, _i32]),
     "hq_dot_reach": (C.c_int, [C.POINTER(hq_dot_classes), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "hq_dot_apron": (C.c_int, [_ctx, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "hq_dot_reach2": (C.c_int, [C.POINTER(hq_dot_classes)] + [C.POINTER(C.c_int)] * 4),
+    "hq_dot_levels": (C.c_int, [C.POINTER(hq_dot_classes), _i32, C.POINTER(C.c_int)]),
+    "hq_dot_form": (C.c_int, [_ctx] + [C.POINTER(C.c_int)] * 4),
     "hq_dot_population_partial": (C.c_int, [_ctx, _f, C.c_int, C.c_int, C.POINTER(hq_dot_classes), C.c_float, _d]),
     "hq_bayer_map": (C.c_int, [C.c_int, _f]),
     "hq_set_dither_map": (C.c_int, [_ctx, _f, C.c_int, C.c_int]),
@@ -171,6 +174,7 @@ SIGNATURES = {
     "hq_search_set_lloyd": (C.c_int, [C.c_void_p, C.c_int]),
     "hq_search_set_repair": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "hq_search_set_ordered": (C.c_int, [C.c_void_p, _f]),
+    "hq_search_set_dot": (C.c_int, [C.c_void_p, C.POINTER(hq_dot_classes), C.c_float]),
     "hq_swasa_search_host": (C.c_int, [C.POINTER(hq_swasa_params), C.c_int, C.c_uint64,
                                        C.c_int, EVAL_FN, C.c_void_p, _f, _d, _d]),
     "hq_swasa_search_host_lloyd": (C.c_int, [C.POINTER(hq_swasa_params), C.c_int, C.c_uint64,

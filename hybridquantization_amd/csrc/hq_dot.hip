@@ -32,6 +32,7 @@ __device__ __forceinline__ bool inside(int x, int y, int W, int H) {
 
 // W(p) of the pixel p = (px, py) whose cell has the higher-class directions `hi`: all of them
 // away from the image's border, else those that stay inside.
+// (hq_dot_tile.hip holds a copy of inside() and of this function: the two must stay the same.)
 __device__ __forceinline__ int dot_weight_sum(uint32_t hi, int px, int py, int W, int H) {
     if (px >= 1 && px < W - 1 && py >= 1 && py < H - 1) return 2 * __popc(hi & kDotOrth) + __popc(hi & kDotDiag);
     int w = 0;

@@ -1,7 +1,8 @@
 // hq_dot_classes.cpp -- the class matrices of hq_dot_population (hq.h): the preset, the legality
 // rule, the baron count, the reach (how many rows above and below a pixel its sources lie: what a
-// row-block shard renders beyond its own rows, hq_dot_population_partial) and the two per-cell
-// tables the kernel reads (hq_dot.h, hq_dot.hip).
+// row-block shard renders beyond its own rows, hq_dot_population_partial; in four directions: what
+// a tile of the tiled form renders around itself), the levels (the sequential depth of the matrix)
+// and the per-cell tables and the schedule the kernels read (hq_dot.h, hq_dot.hip, hq_dot_tile.hip).
 // Host code only; links alone into a CPU program (dot_check.cpp).
 #include <algorithm>
 #include <cstdint>
@@ -51,6 +52,70 @@ void dot_tables(const hq_dot_classes& m, uint32_t* lower, uint32_t* higher) {
             lower[cy * n + cx] = lo;
             higher[cy * n + cx] = hi;
         }
+}
+
+// The cells by level, ties by cell: a counting sort over hq_dot_levels' answer.
+void dot_schedule(const hq_dot_classes& m, DotSchedule* out) {
+    std::memset(out, 0, sizeof *out);
+    int32_t level[kDotCells];
+    if (hq_dot_levels(&m, level, &out->depth)) {
+        out->depth = 0;
+        return;
+    }
+    const int cells = m.n * m.n;
+    for (int c = 0; c < cells; ++c) ++out->start[level[c] + 1];
+    for (int l = 0; l < out->depth; ++l) out->start[l + 1] += out->start[l];
+    uint32_t next[kDotCells + 1];
+    std::memcpy(next, out->start, sizeof next);
+    for (int c = 0; c < cells; ++c) out->cell[next[level[c]]++] = (uint32_t)c;
+    for (int l = out->depth + 1; l <= kDotCells; ++l) out->start[l] = (uint32_t)cells;
+}
+
+bool dot_matrix_info(const hq_dot_classes& m, DotMatrixInfo* out) {
+    DotMatrixInfo i{};
+    int32_t level[kDotCells];
+    if (hq_dot_reach2(&m, &i.above, &i.below, &i.left, &i.right) || hq_dot_levels(&m, level, &i.depth)) return false;
+    *out = i;
+    return true;
+}
+
+// The lanes per pixel: the threads of a workgroup (256) over the pixels a level has on average,
+// rounded down to a power of two, at most kDotTileMaxLanes, and no more lanes than leave each at
+// least 4 colours.
+bool dot_tile_eligible(const DotMatrixInfo& info, int K, int shape, DotTilePlan* plan) {
+    DotTilePlan p{};
+    if (K < 1 || K > 256 || shape < 0 || shape > kDotTileShapes || info.depth < 1) return false;
+    p.above = info.above, p.below = info.below, p.left = info.left, p.right = info.right, p.depth = info.depth;
+    const int first = shape ? shape - 1 : kDotTileShapes - 1, last = shape ? shape - 1 : 0;
+    for (int s = first; s >= last; --s) {
+        const int64_t window = (int64_t)(kDotTileW[s] + p.left + p.right) * (kDotTileH[s] + p.above + p.below);
+        if (window * 12 > kDotTileErrBytes) continue;
+        p.shape = s, p.tw = kDotTileW[s], p.th = kDotTileH[s], p.window = (int)window;
+        const int per_level = std::max(1, p.window / p.depth);
+        while ((2 << p.lg_lanes) <= kDotTileMaxLanes && (256 >> (p.lg_lanes + 1)) >= per_level &&
+               (4 << (p.lg_lanes + 1)) <= K)
+            ++p.lg_lanes;
+        *plan = p;
+        return true;
+    }
+    return false;
+}
+
+bool dot_tile_eligible(const hq_dot_classes& m, int K, int shape, DotTilePlan* plan) {
+    DotMatrixInfo info;
+    return dot_matrix_info(m, &info) && dot_tile_eligible(info, K, shape, plan);
+}
+
+// Measured (profiles/dot_tile_c3.json), Knuth's matrix and a 16 x 16 permutation, P = 1 and 4: with a
+// 32 x 32 or 64 x 32 tile the tiled form beat the chain by more than the chain's spread in every case
+// at 512^2, K = 16 and at 1024^2, K = 64; the 16 x 16 tile lost one of them (1024^2, P = 4),
+// and at 4096^2 the tiled form lost at K = 256 (three cases of four).  Auto stays inside what won:
+// not the 16 x 16 tile, no more pixels than 1024^2 (nothing between that and 4096^2 was measured) and
+// no larger pixels x P x K than 1024^2 x 4 x 64 = 2^28.  The rule does not look at the matrix: the
+// two measured ones span 64 and 256 classes.
+bool dot_tile_auto(int W, int H, int P, int K, int shape) {
+    const int64_t pixels = (int64_t)W * H;
+    return shape >= 1 && pixels <= (int64_t)1 << 20 && pixels * P * K <= (int64_t)1 << 28;
 }
 
 }  // namespace hq
@@ -109,6 +174,55 @@ int hq_dot_reach(const hq_dot_classes* m, int* above, int* below) {
     }
     *above = a;
     *below = b;
+    return HQ_OK;
+}
+
+// The same recurrence with the columns beside the rows: p's extent to the left and right shifted
+// by dx.  (The rows are hq_dot_reach's own: the two recurrences do not meet.)
+int hq_dot_reach2(const hq_dot_classes* m, int* above, int* below, int* left, int* right) {
+    if (!above || !below || !left || !right || !hq_dot_classes_legal(m)) return HQ_ERR_ARG;
+    const int n = m->n, cells = n * n;
+    int cell_of[hq::kDotCells], lf[hq::kDotCells] = {}, rt[hq::kDotCells] = {};
+    for (int c = 0; c < cells; ++c) cell_of[m->cls[c]] = c;
+    int l = 0, r = 0;
+    for (int k = 0; k < cells; ++k) {
+        const int c = cell_of[k], cx = c % n, cy = c / n;
+        for (int d = 0; d < 8; ++d) {
+            const int dx = hq::dot_dx(d), p = (cy + hq::dot_dy(d) + n) % n * n + (cx + dx + n) % n;
+            if (m->cls[p] >= k) continue;
+            lf[c] = std::max(lf[c], lf[p] - dx);
+            rt[c] = std::max(rt[c], rt[p] + dx);
+        }
+        l = std::max(l, lf[c]);
+        r = std::max(r, rt[c]);
+    }
+    hq_dot_reach(m, above, below);
+    *left = l;
+    *right = r;
+    return HQ_OK;
+}
+
+// In ascending class every lower neighbour's level is final when the cell takes its own.
+int hq_dot_levels(const hq_dot_classes* m, int32_t* level, int* depth) {
+    if (!level || !depth || !hq_dot_classes_legal(m)) return HQ_ERR_ARG;
+    const int n = m->n, cells = n * n;
+    int cell_of[hq::kDotCells];
+    for (int c = 0; c < cells; ++c) cell_of[m->cls[c]] = c;
+    int32_t lv[hq::kDotCells] = {};
+    int deepest = 0;
+    for (int k = 0; k < cells; ++k) {
+        const int c = cell_of[k], cx = c % n, cy = c / n;
+        int32_t own = 0;
+        for (int d = 0; d < 8; ++d) {
+            const int p = (cy + hq::dot_dy(d) + n) % n * n + (cx + hq::dot_dx(d) + n) % n;
+            if (m->cls[p] < k) own = std::max(own, lv[p] + 1);
+        }
+        lv[c] = own;
+        deepest = std::max(deepest, (int)own);
+    }
+    std::memset(level, 0, sizeof(int32_t) * hq::kDotCells);
+    std::memcpy(level, lv, sizeof(int32_t) * cells);
+    *depth = deepest + 1;
     return HQ_OK;
 }
 

@@ -494,10 +494,35 @@ hipError_t argmin_diffused(hq_ctx* c, const Diffused& d, const AssignArgs& aa, c
     return timed_launch(pr, kPDither, [&] { return launch_diffuse(da, Pl, c->stream, at); });
 }
 
+// The form a dot pass over P palettes of K colours takes under the context's matrix (c->dot_cls), one
+// function for the scratch (ensure_render_scratch) and the launch (argmin_dot): the tiled kernel on a whole
+// image whose matrix dot_tile_eligible admits, under option "dot_tile" 1 always and under -1 (auto) where it
+// was measured faster than the chain (hq.h states the rule); else the chain.
+bool dot_tiled(const hq_ctx* c, int P, int K, DotTilePlan* plan) {
+    if (!whole_image(c) || c->dot_tile == 0 || !c->d_dotsched.p) return false;
+    DotTilePlan pl;
+    if (c->dot_cls.n == 0 || !dot_tile_eligible(c->dot_info, K, c->dot_tile_shape, &pl)) return false;
+    if (c->dot_tile < 0 && !dot_tile_auto(c->g.W, c->g.H, P, K, pl.shape)) return false;
+    if (plan) *plan = pl;
+    return true;
+}
+
 // (the matrix read on the host here is the one whose tables d_dottab holds: ensure_dot_tables)
 hipError_t argmin_dot(hq_ctx* c, const Dot& d, const AssignArgs& aa, const GridArgs& ga, int K, int Pl, int Ps,
                       ProfRec& pr, AssignTag* at) {
     const Geom& g = c->g;
+    DotTilePlan plan;
+    if (dot_tiled(c, Pl, K, &plan)) {
+        const DotTileArgs ta{aa.R, aa.G, aa.B, ga.pal, aa.idx, ga.used_glob, c->d_dottab.as<uint32_t>(),
+                             c->d_dotsched.as<uint32_t>(), g.idx_pitch, used_stride(Ps), g.W, g.H, K, c->dot_cls.n,
+                             d.strength, plan};
+        const hipError_t e = timed_launch(pr, kPDot, [&] { return launch_dot_tile(ta, Pl, c->stream, at); });
+        if (e == hipSuccess) c->dot_form = 2, c->dot_form_tw = plan.tw, c->dot_form_th = plan.th, c->dot_form_levels = plan.depth;
+        return e;
+    }
+    // (the chain's errors were sized by the same rule: ensure_render_scratch)
+    if (c->d_doterr.bytes < sizeof(float) * dot_err_floats(Pl, g.W, whole_image(c) ? g.H : d.a1 - d.a0))
+        return hipErrorInvalidValue;
     DotWinArgs wa{};  // (on a whole image the DotArgs in it alone)
     static_cast<DotArgs&>(wa) = DotArgs{aa.R, aa.G, aa.B, ga.pal, aa.idx, ga.used_glob, c->d_doterr.as<float>(),
                                         c->d_dottab.as<uint32_t>(), c->dot_cls.cls, g.idx_pitch, used_stride(Ps), g.W,
@@ -509,9 +534,11 @@ hipError_t argmin_dot(hq_ctx* c, const Dot& d, const AssignArgs& aa, const GridA
         wa.h0 = g.e0 - c->apron_above, wa.h1 = g.e1 + c->apron_below;
         wa.aR = ap, wa.aG = ap ? ap + aplane : nullptr, wa.aB = ap ? ap + 2 * aplane : nullptr;
     }
-    return timed_launch(pr, kPDot, [&] {
+    const hipError_t e = timed_launch(pr, kPDot, [&] {
         return whole_image(c) ? launch_dot(wa, Pl, c->stream, at) : launch_dot_window(wa, Pl, c->stream, at);
     });
+    if (e == hipSuccess) c->dot_form = 1, c->dot_form_tw = c->dot_form_th = 0, c->dot_form_levels = c->dot_info.depth;
+    return e;
 }
 
 // The index images of `pass`: its rendering's function, then what the launch reported.
@@ -686,11 +713,12 @@ bool palette_fits_fast(const float* pal, int P, int K) {
     return true;
 }
 
-// The scratch a rendering needs -- dot diffusion's errors over the rows rendered, a raster diffusion's carry
+// The scratch a rendering needs -- dot diffusion's errors over the rows rendered (the chain's), a raster diffusion's carry
 // rows -- ensured by run_pass before anything is enqueued: nothing allocates between prof_begin and the
-// synchronise, and nothing inside a captured search run (its passes are plain or ordered and need none).
-int ensure_render_scratch(hq_ctx* c, const Pass& pass, int P) {
-    if (const Dot* d = pass.as<Dot>())
+// synchronise; a search under the dot-diffused cost asks for it before its run's capture begins (ensure_dot_pass),
+// so nothing allocates inside a captured run (its other passes are plain or ordered and need none).
+int ensure_render_scratch(hq_ctx* c, const Pass& pass, int P, int K) {
+    if (const Dot* d = pass.as<Dot>(); d && !dot_tiled(c, P, K, nullptr))  // (the tiled form keeps its errors in LDS)
         HIP_TRY(c, c->d_doterr.ensure(sizeof(float) * dot_err_floats(P, c->g.W, whole_image(c) ? c->g.H : d->a1 - d->a0)));
     if (const Diffused* d = pass.as<Diffused>())
         HIP_TRY(c, c->d_dcarry.ensure(sizeof(float) * diffuse_carry_floats(P, d->rows, c->g.W)));
@@ -714,7 +742,7 @@ int run_pass(hq_ctx* c, const float* palettes, int P, int K, const Pass& pass) {
     c->nch_cur = c->chunked && fits && c->G2 > 0 && K > kMaxK && K <= kMaxKChunked ? chunk_count(K) : 1;
     c->pal_generic = !fits;  // (before ensure_population: it sizes the generic path's scratch)
     if (int rc = ensure_population(c, P, K)) return rc;
-    if (int rc = ensure_render_scratch(c, pass, P)) return rc;
+    if (int rc = ensure_render_scratch(c, pass, P, K)) return rc;
     hipStream_t s = c->stream;
     ProfRec pr = prof_begin(c);
     int rc = upload_and_prep(c, palettes, nullptr, P, K);
@@ -1192,15 +1220,22 @@ int ensure_dot_tables(hq_ctx* c, const hq_dot_classes& m) {
     if (int rc = bind(c)) return rc;
     const bool had = c->d_dottab.p != nullptr;
     HIP_TRY(c, c->d_dottab.ensure(sizeof(uint32_t) * 2 * kDotCells));
+    HIP_TRY(c, c->d_dotsched.ensure(sizeof(uint32_t) * kDotSchedWords));
     if (had && c->dot_cls.n == m.n && !std::memcmp(c->dot_cls.cls, m.cls, sizeof(int32_t) * m.n * m.n)) return HQ_OK;
     uint32_t tab[2 * kDotCells];
     dot_tables(m, tab, tab + kDotCells);
     c->dot_cls.n = 0;  // (no matrix while the copy may fail)
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipMemcpy(c->d_dottab.p, tab, sizeof tab, hipMemcpyHostToDevice));
+    DotMatrixInfo info;
+    if (!dot_matrix_info(m, &info)) return fail(c, HQ_ERR_ARG, "illegal class matrix");
+    DotSchedule sched;  // (the tiled form's: cell, then start)
+    dot_schedule(m, &sched);
+    HIP_TRY(c, hipMemcpy(c->d_dotsched.p, sched.cell, sizeof(uint32_t) * kDotSchedWords, hipMemcpyHostToDevice));
     std::memset(&c->dot_cls, 0, sizeof c->dot_cls);
     c->dot_cls.n = m.n;
     std::memcpy(c->dot_cls.cls, m.cls, sizeof(int32_t) * m.n * m.n);
+    c->dot_info = info;
     return HQ_OK;
 }
 
@@ -1251,6 +1286,23 @@ int dot_into_hout(hq_ctx* c, const RenderCall& r, const hq_dot_classes* cls) {
 }
 
 }  // namespace
+
+namespace hq {
+
+int dot_search_scope(hq_ctx* c, int K) {
+    if (int rc = whole_image_only(c, "hq_dither_population (error diffusion)")) return rc;
+    if (K > kMaxK)
+        return fail(c, HQ_ERR_UNSUPPORTED, "K=%d > %d: the dither kernel keeps the palette in LDS and writes "
+                                           "8-bit indices", K, kMaxK);
+    return c->have_image && !c->img_u8 ? require_unit_range_image(c, "image", "no error diffusion") : HQ_OK;
+}
+
+int ensure_dot_pass(hq_ctx* c, const hq_dot_classes& m, int P, int K) {
+    if (int rc = ensure_dot_tables(c, m)) return rc;
+    return ensure_render_scratch(c, Pass{Dot{0.f, 0, 0}}, P, K);
+}
+
+}  // namespace hq
 
 extern "C" {
 
@@ -1333,6 +1385,15 @@ int hq_dot_population(hq_ctx* c, const float* palettes, int P, int K, const hq_d
     if (!c) return HQ_ERR_ARG;
     const int rc = dot_into_hout(c, RenderCall{palettes, costs, P, K, false, false, nullptr, strength}, cls);
     return rc ? rc : costs_from_hout(c, P, K, delta, costs, used);
+}
+
+int hq_dot_form(hq_ctx* c, int* form, int* tile_w, int* tile_h, int* levels) {
+    if (!c) return HQ_ERR_ARG;
+    if (form) *form = c->dot_form;
+    if (tile_w) *tile_w = c->dot_form_tw;
+    if (tile_h) *tile_h = c->dot_form_th;
+    if (levels) *levels = c->dot_form_levels;
+    return HQ_OK;
 }
 
 int hq_dot_population_partial(hq_ctx* c, const float* palettes, int P, int K, const hq_dot_classes* cls,

@@ -19,6 +19,7 @@
 #include <variant>
 #include <vector>
 
+#include "hq_dot.h"
 #include "hq_launch.h"
 #include "hq_mask.h"
 #include "hq_swasa.h"
@@ -135,7 +136,7 @@ enum Pair {
     kPErrsum, kPReseed,                    // the error kernels (also hq_cluster_errors'), the reseed kernel
     kPHist,                                // hq_color_histogram's kernel
     kPReduce,                              // hq_set_image_reduced's kernel
-    kPDot,                                 // dot_kernel's launches (one per class) in the place of grid + assign
+    kPDot,                                 // dot_kernel's launches (one per class), or dot_tile_kernel's one, in the place of grid + assign
     kPairs
 };
 // The stage each pair's time and launch count go to.
@@ -176,7 +177,8 @@ inline hipError_t timed_launch(ProfRec& pr, Pair p, F&& launch, bool start = tru
 //     floyd_steinberg: that preset's taps, whoever gave them: the kernel's own formula, no instance.
 //   Dot: zeroed the same way, then dot_kernel's launches under the context's class matrix (c->dot_cls,
 //     its tables on the device: ensure_dot_tables); on a row-block shard its windowed instance over rows
-//     [a0, a1), the extended rows and what of the apron the matrix's reach needs (dot_window).
+//     [a0, a1), the extended rows and what of the apron the matrix's reach needs (dot_window).  On a whole
+//     image dot_tile_kernel's one launch in their place where dot_tiled (hq_eval.hip) says so (option "dot_tile").
 struct Plain {};
 struct Ordered { float amp[3]; };
 struct Diffused { float strength; hq_diffusion_taps taps; int rows, slope; bool floyd_steinberg; };
@@ -191,8 +193,9 @@ using Rendering = std::variant<Plain, Ordered, Diffused, Dot>;
 // CostOnly (a repair iteration's first pass): grid, assign and cost -- the index
 //   images and, with option "pixel_err" in force, the error image the error kernel
 //   reads.
-// Any kind may be plain or ordered.  A diffused or dot rendering exists on a full pass only: its
-// constructors take no kind, and the members are const.
+// Any kind may be plain or ordered.  A diffused rendering exists on a full pass only: its
+// constructor takes no kind, and the members are const.  A dot rendering may also be a folding
+// search's evaluation (hq_search_set_dot): Full or Fold, nothing else.
 // Counter-set parity: each pass takes the other counter set than the last one
 // (build_grid zeroes it), so an accept step can read the last set while the next
 // is filled.  A side pass (AssignOnly, CostOnly: nothing reads its sums, so no
@@ -208,6 +211,7 @@ struct Pass {
     Pass(Kind k, const Ordered& o) : kind(k), rendering(o) {}
     Pass(const Diffused& d) : kind(Full), rendering(d) {}
     Pass(const Dot& d) : kind(Full), rendering(d) {}
+    Pass(bool fold, const Dot& d) : kind(fold ? Fold : Full), rendering(d) {}
     template <typename R>
     const R* as() const { return std::get_if<R>(&rendering); }     // the alternative's parameters, or null
     bool rendered() const { return !as<Plain>(); }                 // the getters answer for a rendering
@@ -298,6 +302,15 @@ struct hq_ctx {
     // ensure_dot_tables) and the errors e of a Dot pass ([P][3][H][W] floats, never zeroed)
     hq_dot_classes dot_cls{};
     hq::DevBuf d_dottab, d_doterr;
+    // the tiled form (hq_dot_tile.hip): the schedule of the same matrix on the device
+    // ([kDotSchedWords] words, uploaded with the tables); options "dot_tile" (-1 auto, 0 the
+    // chain, 1 tiled wherever eligible) and "dot_tile_shape" (0: the largest shape whose window
+    // fits, else 1 .. kDotTileShapes); what hq_dot_form reports: the form of the last dot pass
+    // enqueued (0 none yet, 1 chain, 2 tiled), its tile and the matrix's levels
+    hq::DevBuf d_dotsched;
+    hq::DotMatrixInfo dot_info{};  // dot_cls' reach and levels, made where its tables are (ensure_dot_tables)
+    int dot_tile = -1, dot_tile_shape = 0;
+    int dot_form = 0, dot_form_tw = 0, dot_form_th = 0, dot_form_levels = 0;
     // dot diffusion on a row-block shard (hq_dot_population_partial): the apron, the image rows
     // [e0 - apron_above, e0) and [e1, e1 + apron_below) kept beyond the extended rows by
     // hq_set_image[_planar]_shard under option "dot_apron" -- [3][apron_above + apron_below][W]
@@ -410,6 +423,9 @@ struct hq_search {
     int nch = 1;                         // chunked palettes (256 < K <= 16384): chunks per palette
     bool ordered = false;                // hq_search_set_ordered: every evaluation is the ordered one
     hq::Ordered ord{};                   // ... at this amplitude per channel
+    bool dot = false;                    // hq_search_set_dot: every evaluation is the dot-diffused one
+    float dot_strength = 0.f;            // ... at this strength
+    hq_dot_classes dot_cls{};            // ... under this matrix, the search's own (latched at the call)
     int nfixed = 0;                      // the context's fixed colours at hq_search_create: colours
     std::vector<float> fixed;            // 0 .. nfixed-1 of every member, [nfixed][4], for the search's life
     bool fold = false;                   // accept steps reduce the partials (no finalize launch)
@@ -529,6 +545,11 @@ int require_unit_range_image(hq_ctx* c, const char* subject, const char* what);
 int check_ordered_amp(hq_ctx* c, const float* amp);
 int ordered_scope(hq_ctx* c, int K);
 int ensure_dither_map(hq_ctx* c);
+// A search under the dot-diffused cost (hq_search_set_dot): where it may run -- hq_dot_population's
+// scope, K and image range, in that order -- and, before anything is enqueued or captured, matrix m's
+// tables on the device and the scratch the form that will run needs for P palettes of K colours.
+int dot_search_scope(hq_ctx* c, int K);
+int ensure_dot_pass(hq_ctx* c, const hq_dot_classes& m, int P, int K);
 // pixel mask: the divisor that finishes a cost (the in-mask pixels of the full image; without a
 // mask W H, the expression it always was); the refusal of a palette slice under a mask; the
 // live-tile list on the device for the launch the options in force select (ensure_population

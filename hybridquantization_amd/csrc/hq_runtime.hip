@@ -907,6 +907,13 @@ int hq_set_option(hq_ctx* c, const char* name, int value) {
     } else if (!std::strcmp(name, "dot_apron")) {
         if (value < 0 || value > 255) return fail(c, HQ_ERR_ARG, "dot_apron must be in 0 .. 255");
         c->dot_apron = value;  // (read by the next hq_set_image[_planar]_shard: set_apron)
+    } else if (!std::strcmp(name, "dot_tile")) {
+        if (value < -1 || value > 1) return fail(c, HQ_ERR_ARG, "dot_tile must be -1, 0 or 1");
+        c->dot_tile = value;
+    } else if (!std::strcmp(name, "dot_tile_shape")) {
+        if (value < 0 || value > kDotTileShapes)
+            return fail(c, HQ_ERR_ARG, "dot_tile_shape must be in 0 .. %d", kDotTileShapes);
+        c->dot_tile_shape = value;
     } else if (!std::strcmp(name, "cent_span")) {
         if (value < 0) return fail(c, HQ_ERR_ARG, "cent_span must be >= 0 (0 = auto)");
         c->cent_span = value;

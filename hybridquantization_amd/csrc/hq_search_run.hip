@@ -165,9 +165,11 @@ void search_commit(hq_search* s, int rc, int evaluations) {
 }
 
 // A search's evaluation pass: folding (search_folds) or full.
-// (hq_search_set_ordered: the ordered one at the search's amplitude)
+// (hq_search_set_ordered: the ordered one at the search's amplitude; hq_search_set_dot: the
+// dot-diffused one at the search's strength, under the tables ensure_dot_pass has put in place)
 Pass search_pass(const hq_search* s) {
     const Pass::Kind kind = s->fold ? Pass::Fold : Pass::Full;
+    if (s->dot) return Pass{s->fold, Dot{s->dot_strength, 0, 0}};  // (a whole image: no window)
     return s->ordered ? Pass{kind, s->ord} : Pass{kind};
 }
 
@@ -176,6 +178,8 @@ Pass search_pass(const hq_search* s) {
 int ordered_excludes(hq_search* s, const char* what) {
     if (s->ordered)
         return fail(s->ctx, HQ_ERR_UNSUPPORTED, "%s in a search under the ordered cost (hq_search_set_ordered)", what);
+    if (s->dot)
+        return fail(s->ctx, HQ_ERR_UNSUPPORTED, "%s in a search under the dot-diffused cost (hq_search_set_dot)", what);
     return HQ_OK;
 }
 
@@ -191,6 +195,7 @@ int device_search_rerank(hq_search* s) {
     const NchScope scope(c, s->nch);
     if ((rc = ensure_population(c, s->P, s->K))) return rc;
     if (s->ordered && (rc = ensure_dither_map(c))) return rc;
+    if (s->dot && (rc = ensure_dot_pass(c, s->dot_cls, s->P, s->K))) return rc;
     if (s->nch > 1) return fail(c, HQ_ERR_UNSUPPORTED, "K=%d > %d", s->K, kMaxK);
     if ((rc = upload_and_prep(c, nullptr, s->cand[s->cd].p, s->P, s->K))) return rc;
     ProfRec untimed;
@@ -293,6 +298,8 @@ int device_search_run(hq_search* s, int iterations, int* ran) {
     const NchScope scope(c, s->nch);
     if ((rc = ensure_population(c, s->P, s->K))) return rc;
     if (s->ordered && (rc = ensure_dither_map(c))) return rc;  // (before a capture begins)
+    // the search's own matrix, whatever hq_dot_population has put there since, and the chain's errors
+    if (s->dot && (rc = ensure_dot_pass(c, s->dot_cls, s->P, s->K))) return rc;
     if (s->comm != c->comm || s->fold != search_folds(c))
         return fail(c, HQ_ERR_STATE, "communicator or palette split changed after hq_search_create: "
                                      "recreate the search");
@@ -395,6 +402,7 @@ int run_scope(hq_search* s, int iterations) {
     if (period_in_run(s, s->every, ite, iterations) && ((rc = lloyd_scope(s)) || (rc = lloyd_validate(s)))) return rc;
     if (period_in_run(s, s->repair_every, ite, iterations) && (rc = repair_scope(s))) return rc;
     if ((rc = mask_scope(s->ctx))) return rc;
+    if (s->dot) return dot_search_scope(s->ctx, s->K);
     return s->ordered ? ordered_scope(s->ctx, s->K) : HQ_OK;
 }
 
@@ -441,6 +449,7 @@ int hq_search_create_from(hq_ctx* c, const hq_swasa_params* params, int K, uint6
     } else {
         const float delta = params->delta;
         auto eval = [c, delta, s](const float* pal, int P, int KK, double* costs) {
+            if (s->dot) return hq_dot_population(c, pal, P, KK, &s->dot_cls, s->dot_strength, delta, costs, nullptr);
             return s->ordered ? hq_ordered_population(c, pal, P, KK, s->ord.amp, delta, costs, nullptr)
                               : hq_eval_population(c, pal, P, KK, delta, costs, nullptr);
         };
@@ -528,6 +537,7 @@ int hq_search_set_ordered(hq_search* s, const float amp[3]) {
     if (on) {
         if (s->every > 0 || s->repair_every > 0)
             return fail(c, HQ_ERR_UNSUPPORTED, "a search with hybrid or repair iterations: no ordered cost");
+        if (s->dot) return fail(c, HQ_ERR_UNSUPPORTED, "a search under the dot-diffused cost: one rendering per search");
         if (int rc = ordered_scope(c, s->K)) return rc;
     }
     const Ordered old = s->ord;
@@ -542,6 +552,43 @@ int hq_search_set_ordered(hq_search* s, const float amp[3]) {
     const int rc = s->driver ? s->driver->rerank() : device_search_rerank(s);
     search_commit(s, rc, 1);
     if (rc) s->ordered = was, s->ord = old;
+    return rc;
+}
+
+int hq_search_set_dot(hq_search* s, const hq_dot_classes* cls, float strength) {
+    if (!s || !s->ctx) return HQ_ERR_ARG;
+    hq_ctx* c = s->ctx;
+    if (cls && !hq_dot_classes_legal(cls))
+        return fail(c, HQ_ERR_ARG, "illegal class matrix: side 4, 8 or 16 and a permutation of 0 .. n*n - 1 (hq.h)");
+    if (!(strength >= 0.0f && strength <= 1.0f)) return fail(c, HQ_ERR_ARG, "strength %g not in [0, 1]", strength);
+    const bool on = strength != 0.f;
+    hq_dot_classes m;
+    if (cls) m = *cls;
+    else hq_dot_preset(HQ_DOT_KNUTH8, &m);
+    if (on) {
+        if (s->every > 0 || s->repair_every > 0)
+            return fail(c, HQ_ERR_UNSUPPORTED, "a search with hybrid or repair iterations: no dot-diffused cost");
+        if (s->ordered) return fail(c, HQ_ERR_UNSUPPORTED, "a search under the ordered cost: one rendering per search");
+        if (int rc = dot_search_scope(c, s->K)) return rc;
+    }
+    const bool same_matrix = s->dot_cls.n == m.n && !std::memcmp(s->dot_cls.cls, m.cls, sizeof(int32_t) * m.n * m.n);
+    if (on == s->dot && (!on || (strength == s->dot_strength && same_matrix))) return HQ_OK;  // (nothing changes)
+    const bool was = s->dot;
+    const float old_strength = s->dot_strength;
+    const hq_dot_classes old_cls = s->dot_cls;
+    s->dot = on;
+    s->dot_strength = on ? strength : 0.f;  // (off: the plain pass itself)
+    if (on) {
+        std::memset(&s->dot_cls, 0, sizeof s->dot_cls);
+        s->dot_cls.n = m.n;
+        std::memcpy(s->dot_cls.cls, m.cls, sizeof(int32_t) * m.n * m.n);
+    }
+    const int ite = s->driver ? s->driver->iteration() : s->ite;
+    if (ite != 0) return HQ_OK;
+    // before the first iteration: the initial population's errors and its best are the new evaluation's
+    const int rc = s->driver ? s->driver->rerank() : device_search_rerank(s);
+    search_commit(s, rc, 1);
+    if (rc) s->dot = was, s->dot_strength = old_strength, s->dot_cls = old_cls;
     return rc;
 }
 

@@ -444,6 +444,32 @@ class ImageManipulation:
         check(load().hq_dot_reach(C.byref(m), C.byref(above), C.byref(below)))
         return above.value, below.value
 
+    @classmethod
+    def dotReach2(cls, classes=None):
+        """hq_dot_reach2: (above, below, left, right), dotReach's rows and the same for columns:
+        how far around a tile the tiled form of dot diffusion renders (None: Knuth's 8 x 8,
+        (5, 5, 5, 5))."""
+        m = cls._classes("knuth8" if classes is None else classes)
+        v = [C.c_int(0) for _ in range(4)]
+        check(load().hq_dot_reach2(C.byref(m), *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    @classmethod
+    def dotLevels(cls, classes=None):
+        """hq_dot_levels: (level int32 (n, n), depth): each cell's level -- 0 without a neighbour
+        of lower class on the torus, else 1 + the largest level among those -- and the number of
+        levels (None: Knuth's 8 x 8, 15 levels)."""
+        m = cls._classes("knuth8" if classes is None else classes)
+        level, depth = np.zeros(256, np.int32), C.c_int(0)
+        check(load().hq_dot_levels(C.byref(m), level.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(depth)))
+        return level[:m.n * m.n].reshape(m.n, m.n).copy(), depth.value
+
+    def dotForm(self):
+        """hq_dot_form: (form, tile_w, tile_h, levels) of the last dot-diffused pass on this
+        context: form 0 none yet, 1 the chain of one launch per class, 2 the tiled kernel
+        (option "dot_tile"); the tile is (0, 0) for the chain."""
+        return self._values(self._lib.hq_dot_form, 4)
+
     def dotApron(self):
         """hq_dot_apron: (above, below), the image rows this context holds beyond its extended
         rows on each side (option "dot_apron" when the shard was set, clipped at the image's
@@ -746,7 +772,10 @@ class ImageManipulation:
         ``dot`` > 0 (hq_dot_population, a strength up to 1; not together with ``dither`` or
         ``ordered``): the best palette is also evaluated in its dot-diffused rendering under
         the class matrix ``dotClasses`` (dotPopulation's ``classes``; None is Knuth's 8 x 8):
-        ``bestErrorDot``; ``bestError`` stays the plain one.  ``dotSearch`` (needs ``dot`` > 0):
+        ``bestErrorDot``; ``bestError`` stays the plain one.  ``dotSearch`` "device" (needs ``dot`` > 0, no k-means or repair move): the search runs under
+        the dot-diffused cost in the library (hq_search_create[_from] + hq_search_set_dot, device-resident
+        where the plain search is); ``bestError`` and ``bestErrorDot`` are one dotPopulation evaluation of
+        the returned palette.  ``dotSearch`` True (needs ``dot`` > 0):
         the search optimises the dot-diffused cost instead, host-driven through
         hq_swasa_search_host_fixed exactly as ``ditherSearch`` is, with the same exclusions of
         the k-means and repair moves; ``bestError`` and ``bestErrorDot`` are then both that cost.
@@ -808,8 +837,11 @@ class ImageManipulation:
             raise ValueError(f"dot={dot!r}: a strength in [0, 1]")
         if dot > 0.0 and (dither > 0.0 or amp is not None):
             raise ValueError("dot with dither or ordered: one rendering")
+        if isinstance(dotSearch, str) and dotSearch != "device":
+            raise ValueError(f"dotSearch={dotSearch!r}: False, True or 'device'")
         if dotSearch:
             host_search_ok("dotSearch", "dot", dot)
+        dot_device = isinstance(dotSearch, str)  # hq_search_set_dot; True: the Python host loop
         # the renderings asked for, in the order their final errors are reported, and the one the
         # search itself optimises (None: the plain cost)
         sw = simulatedAnnealing
@@ -845,7 +877,7 @@ class ImageManipulation:
                 cells, den = self.colorHistogram(int(initBits))
                 init[4 * nfx:], _ = self.medianCut(cells, int(initBits), den, K - nfx)
         total = params.imax if iterations is None else min(int(iterations), params.imax)
-        if ditherSearch or dotSearch:
+        if ditherSearch or (dotSearch and not dot_device):
             P = params.population
             best, err, _ = sw.search_host(
                 K, lambda ps: searched.population(ps.reshape(P, -1), sw.delta), iterations=total,
@@ -870,6 +902,9 @@ class ImageManipulation:
                 self.seedColors, self.seedError = seed, seed_err.value
             if orderedSearch:
                 check(self._lib.hq_search_set_ordered(handle, fptr(amp)), ctx)
+            if dot_device:
+                classes = None if dotClasses is None else C.byref(self._classes(dotClasses))
+                check(self._lib.hq_search_set_dot(handle, classes, dot), ctx)
             if int(lloydEvery) != 0:
                 check(self._lib.hq_search_set_lloyd(handle, int(lloydEvery)), ctx)
             if int(repairEvery) != 0:
@@ -894,6 +929,8 @@ class ImageManipulation:
                 print("Final error : %.5f" % err.value)  # IM:589
         finally:
             self._lib.hq_search_destroy(handle)
+        if dot_device:  # one evaluation of the returned palette: bestError and bestErrorDot are that cost
+            self.bestError = float(searched.population(best.reshape(1, -1), sw.delta)[0])
         if int(repairSteps) > 0 or int(lloydSteps) > 0:
             self.bestErrorSA = self.bestError
         if int(repairSteps) > 0:

@@ -90,7 +90,7 @@ def makeChannels(inline):
 def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
                  whitepoint=Whitepoint.D65, verbose=False, device=0, iterations=None, dither=0.0,
                  ordered=None, mask=None, weights=None, fixed=None, pyramid=None, ditherKernel=None,
-                 dot=0.0, dotClasses=None):
+                 dot=0.0, dotClasses=None, dotSearch=False):
     """HQ:93-137 without the GUI: planar float image (3, N) in [0,1] ->
     (quantized planar image (3, N), bestColors float[4K], best error).  ``dither`` > 0
     (libhq's addition): the returned image is the best palette's Floyd-Steinberg rendering
@@ -111,7 +111,8 @@ def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
     then be None.  None is the plain search, untouched.  ``dot`` > 0 (not together with
     ``dither`` or ``ordered``): the returned image is the best palette's dot-diffused rendering
     at that strength (ImageManipulation.quantizeDotDiffused) under the class matrix
-    ``dotClasses`` (None: Knuth's 8 x 8)."""
+    ``dotClasses`` (None: Knuth's 8 x 8); ``dotSearch`` is findBestQuantization's (False, True
+    or "device": the search itself runs under that cost)."""
     fixed_colors(fixed, int(nbOfColors))
     if ordered is not None and float(dither) > 0.0:
         raise ValueError("dither and ordered: one rendering")
@@ -137,7 +138,7 @@ def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
         sc_img = sp.sRGBToScielab(image, w)
         best = sp.bestColors(inline_rgb, sc_img, w, nbOfColors, swasa, iterations=iterations, dither=dither,
                              ditherKernel=ditherKernel, ordered=ordered, mask=mask, weights=weights, fixed=fixed,
-                             dot=dot, dotClasses=dotClasses)
+                             dot=dot, dotClasses=dotClasses, dotSearch=dotSearch)
         q = (ip.quantizeDotDiffused(best, dot, classes=dotClasses) if float(dot) > 0.0 else
              ip.quantizeOrdered(best, ordered) if ordered is not None else
              ip.quantizeDithered(best, dither, kernel=ditherKernel) if float(dither) > 0.0 else

@@ -450,8 +450,9 @@ int hq_diffuse_population(hq_ctx *ctx, const float *palettes, int P, int K,
  * 2.89 ms at 4096 x 4096, K = 256 for one palette and 7.37 ms for four, against 338 ms
  * for hq_dither_population's kernel in the same process; 0.36 against 2.41 ms at
  * 512 x 512, K = 16.  On a 64 x 64 ramp under the eight cube corners the cost is 0.514
- * of the nearest-colour one (Floyd-Steinberg 0.479).  Not measured: a search under
- * this objective, more than one GPU (refused), K > 256 (refused). */
+ * of the nearest-colour one (Floyd-Steinberg 0.479).  A search under this objective:
+ * hq_search_set_dot.  Not measured: more than one GPU (refused), K > 256 (refused).  On a whole image the
+ * launches may be one (the tiled form below, option "dot_tile"): the same indices, bit for bit. */
 typedef struct hq_dot_classes {
     int32_t n;
     int32_t cls[256];
@@ -525,6 +526,72 @@ int hq_dot_apron(hq_ctx *ctx, int *above, int *below);
  * not been run. */
 int hq_dot_population_partial(hq_ctx *ctx, const float *palettes, int P, int K,
                               const hq_dot_classes *cls, float strength, double *partial);
+
+/* ---- dot diffusion in one launch: the tiled form ----
+ * The reach holds sideways as it holds for rows, and the same argument makes a tile exact: a
+ * workgroup that renders a tile together with the window around it -- the tile extended by
+ * the reach on each of its four sides, clipped to the image -- produces the whole image's
+ * indices on the tile, bit for bit, with the window's errors in LDS and none in global
+ * memory.  Classes come from full-image coordinates, W(p)'s border rule from the full image,
+ * a source outside the window contributes nothing.  One launch renders every tile of every
+ * palette (dot_tile_kernel, hq_dot_tile.hip) in the place of the chain of n*n launches.
+ *
+ * hq_dot_reach2: hq_dot_reach's recurrence applied to the columns as well:
+ *     left[c] = max(left[c], left[p] - dx),  right[c] = max(right[c], right[p] + dx),
+ * so *left is the largest number of columns by which a pixel that idx(q) depends on can lie
+ * left of q, *right the same to the right; *above and *below are hq_dot_reach's exactly.
+ * HQ_DOT_KNUTH8: (5, 5, 5, 5); the row-major 16 x 16 matrix: (15, 1, 255, 17).
+ * HQ_ERR_ARG (outputs untouched): an illegal matrix, a null pointer.
+ *
+ * hq_dot_levels: inside a window the order need not be by class.  A cell's level is 0 when none
+ * of its 8 neighbours on the torus has a lower class, else 1 + the largest level among those
+ * that have; level[cy*n + cx] receives it (entries past n*n: 0) and *depth the number of
+ * levels, 1 + the largest.  Cells of one level do not depend on each other, so a level is one
+ * parallel step and a barrier separates two; every pixel still adds its sources in ascending
+ * class, so the bits are the chain's.  HQ_DOT_KNUTH8 has 15 levels, the row-major 16 x 16
+ * matrix 256.  HQ_ERR_ARG (outputs untouched): an illegal matrix, a null pointer.
+ *
+ * Eligibility (one host-side rule, dot_tile_eligible): a whole image (not a row-block shard:
+ * hq_dot_population_partial on a shard keeps the chain), K <= 256, and a matrix whose window
+ * holds its errors, 12 bytes per pixel, in 56 KiB of LDS under the tile shape in force:
+ *     (tw + left + right) * (th + above + below) * 12 <= 57344.
+ * The shapes tw x th are 16 x 16, 32 x 32 and 64 x 32; option "dot_tile_shape" 1, 2 or 3 names
+ * one, 0 (default) takes the largest that fits.  Knuth's matrix and every 16 x 16 permutation
+ * tried (360 of them; above + below up to 21, left + right up to 20) fit all three; the row-major and column-major 16 x 16
+ * matrices fit none.  Whatever is not eligible takes the chain.
+ *
+ * Option "dot_tile": -1 (default) auto, 0 always the chain, 1 the tiled kernel wherever it is
+ * eligible.  The results do not depend on it, bit for bit; hq_last_path reports HQ_ARGMIN_DOT
+ * and the profile counts one "dot" launch per pass under either form.  The tiled form sizes no
+ * error planes ([P][3][H][W] floats for the chain).
+ * Auto takes the tiled kernel for an eligible pass whose tile is 32 x 32 or 64 x 32 (never under
+ * "dot_tile_shape" 1), with W * H <= 2^20 and W * H * P * K <= 2^28; anything else takes the
+ * chain.  That is the region in which every measured case beat the chain by more than the spread
+ * of the chain's own repeated runs in the same process, bounded in pixels and in the product by
+ * the largest case measured there.  Measured on one MI355X (DESIGN.md 28,
+ * profiles/dot_tile_c3.json; "dot" stage, median of 5, chain against tiled 64 x 32, ms):
+ *                              Knuth's 8 x 8            a 16 x 16 permutation
+ *                              P = 1         P = 4         P = 1          P = 4
+ *     512 x 512,   K = 16    0.359 / 0.071  0.377 / 0.082  1.409 / 0.107  1.451 / 0.121
+ *     1024 x 1024, K = 64    0.492 / 0.121  0.628 / 0.347  1.885 / 0.175  2.188 / 0.658
+ *     4096 x 4096, K = 256   2.878 / 2.980  7.302 / 11.60  6.271 / 5.590  15.82 / 22.10
+ * The first two rows are the region: all 8 cases won, under the 32 x 32 tile too; the 16 x 16
+ * tile lost one of them (1024 x 1024, P = 4, Knuth's), so auto does not take it.  At 4096 x 4096,
+ * the only larger image measured, the tiled form lost three cases of four, so auto stays on the
+ * chain above 2^20 pixels whatever K is.  The rule is a region around 8 measured points, not a
+ * measurement of every shape in it: images below 512 x 512, other K at these sizes and other
+ * matrices than these two were not timed.
+ * The device-resident search under this cost (hq_search_set_dot) at 4096 x 4096, K = 256, P = 4:
+ * 8.49 ms per iteration with the chain, 13.40 with the tiled kernel, the plain step
+ * 0.551 in the same process.  Not measured: more than one GPU.
+ *
+ * hq_dot_form: the form the last dot pass enqueued on the context took: *form 0 = none yet,
+ * 1 = the chain, 2 = the tiled kernel; *tile_w and *tile_h its tile (0 for the chain), *levels
+ * the levels of its matrix.  A refused call leaves the answer as it was.  Any pointer but ctx
+ * may be NULL; HQ_ERR_ARG for a null ctx. */
+int hq_dot_reach2(const hq_dot_classes *cls, int *above, int *below, int *left, int *right);
+int hq_dot_levels(const hq_dot_classes *cls, int32_t level[256], int *depth);
+int hq_dot_form(hq_ctx *ctx, int *form, int *tile_w, int *tile_h, int *levels);
 
 /* ---- ordered dithering: libhq's addition, no reference counterpart ----
  * Error diffusion is a serial recurrence (one workgroup per palette); a threshold
@@ -930,6 +997,23 @@ int hq_search_set_repair(hq_search *s, int every, int max_moves);
  * period likewise while it is on; "palette_split" or "slice_ranks" > 1; an image
  * pixel outside [0, 1] (also checked by each hq_search_run, *ran = 0). */
 int hq_search_set_ordered(hq_search *s, const float amp[3]);
+/* The same for dot diffusion: from now on every evaluation of the search is hq_dot_population's
+ * at `strength` under *cls (NULL: HQ_DOT_KNUTH8), in whichever form option "dot_tile" and the
+ * eligibility rule give (the results do not depend on the form).  The matrix is latched at the
+ * call and is the search's own: every hq_search_run puts its tables in place before anything is
+ * enqueued, so an hq_dot_population call with another matrix between two runs changes nothing.
+ * Strength 0 turns it off: the search is then the plain search bit for bit.  Before the first
+ * iteration the initial population is re-ranked under the new evaluation; afterwards the change
+ * takes effect from the next iteration.  Device-resident (also with "sa_graph" 1) and
+ * host-driven searches give the same results bit for bit.  Fixed colours, hq_search_create_from,
+ * a mask and weights compose as for the plain search (the rendering does not read the mask, the
+ * cost does).  HQ_ERR_ARG: a null search, an illegal matrix, a strength outside [0, 1] or NaN.
+ * HQ_ERR_UNSUPPORTED: hybrid or repair iterations set (and hq_search_set_lloyd /
+ * hq_search_set_repair under this cost), an ordered cost in force (and hq_search_set_ordered
+ * under this one: one rendering per search), K > 256, an image pixel outside [0, 1] or not
+ * finite; a sharded context, a communicator of more than one rank and a palette slice get
+ * hq_dot_population's answers.  A refused call leaves the search as it was. */
+int hq_search_set_dot(hq_search *s, const hq_dot_classes *cls, float strength);
 
 /* Host-only SWASA driver with a caller-supplied population evaluator; same
  * policy code as hq_search_*.  Used to test the SA semantics without a GPU.
@@ -1029,9 +1113,9 @@ int hq_profile_enable(hq_ctx *ctx, int on);
  * and "cost"), "dither" (hq_dither_population's and hq_diffuse_population's kernels, which stand in the place of "grid"
  * and "assign": a dithered evaluation counts nothing under those; an ordered evaluation's grid
  * and argmin count under "grid" and "assign" like the plain one's), "reduce" (hq_set_image_reduced's
- * kernel, on the destination context), "dot" (hq_dot_population's launches, one per class, in the
- * place of "grid" and "assign": the time from the first one's start to the last one's end, counted
- * as one launch per call); returns total ms and launch
+ * kernel, on the destination context), "dot" (hq_dot_population's launches, one per class or the
+ * tiled form's one, in the place of "grid" and "assign": the time from the first one's start to
+ * the last one's end, counted as one launch per call); returns total ms and launch
  * count (HIP events on the context stream). */
 int hq_profile_get(hq_ctx *ctx, const char *kernel, double *total_ms, int64_t *launches);
 int hq_profile_reset(hq_ctx *ctx);
@@ -1055,7 +1139,8 @@ enum hq_path_argmin {
     HQ_ARGMIN_NONE = 0, HQ_ARGMIN_ASSIGN_PIPE = 1, HQ_ARGMIN_ASSIGN_PIPE_ORDERED = 2, HQ_ARGMIN_ASSIGN16 = 3,
     HQ_ARGMIN_ASSIGN_WIDE = 4, HQ_ARGMIN_DITHER = 5,
     HQ_ARGMIN_DIFFUSE = 6,   /* hq_diffuse_population's kernels (hq_diffuse.hip) */
-    HQ_ARGMIN_DOT = 7        /* hq_dot_population's kernel (hq_dot.hip), one launch per class */
+    HQ_ARGMIN_DOT = 7        /* hq_dot_population's kernels: hq_dot.hip, one launch per class, or
+                              * hq_dot_tile.hip, one launch (hq_dot_form says which) */
 };
 enum hq_path_cost {
     HQ_COST_NONE = 0,        /* an assign-only pass, or a mask without a live tile */
@@ -1165,6 +1250,13 @@ int hq_search_info(const hq_search *s, int *device_resident, int *nch, int *grap
  *   "dot_apron"    rows (0 .. 255, default 0; anything else is HQ_ERR_ARG) a row-block shard keeps
  *                  beyond its extended rows on each side for hq_dot_population_partial; read by
  *                  hq_set_image_shard and hq_set_image_planar_shard (hq_dot_apron)
+ *   "dot_tile"     hq_dot_population[_partial] on a whole image: -1 (default) = the tiled kernel where
+ *                  it was measured faster (a 32 x 32 or 64 x 32 tile, W * H <= 2^20, W * H * P * K <= 2^28), 0 = the chain of one launch
+ *                  per class, 1 = the tiled kernel wherever it is eligible (hq_dot_form; anything
+ *                  else is HQ_ERR_ARG).  The results do not depend on it, bit for bit
+ *   "dot_tile_shape" the tiled kernel's tile: 0 (default) = the largest of 16 x 16, 32 x 32 and
+ *                  64 x 32 whose window fits, 1, 2, 3 = that one (anything else is HQ_ERR_ARG).  The
+ *                  results do not depend on it, bit for bit: 1 lets small test images cross tiles
  *   "cent_span"    test only: pixels per workgroup of the k-means sums kernel (0, default: by
  *                  the grid), rounded up to whole steps of 1024 and clamped to the bound of the
  *                  kernel's accumulator fields.  The results do not depend on it, bit for bit:
