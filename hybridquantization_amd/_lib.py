@@ -158,6 +158,7 @@ SIGNATURES = {
     "hq_color_histogram": (C.c_int, [_ctx, C.c_int, _i64, _i64]),
     "hq_median_cut": (C.c_int, [_i64, C.c_int, C.c_int64, C.c_int, _f, C.POINTER(C.c_int)]),
     "hq_quantize": (C.c_int, [_ctx, _f, C.c_int64, _f, C.c_int, _f, _i32]),
+    "hq_assign_coords": (C.c_int, [_ctx, C.c_int, _f, C.c_int64, _f]),
     "hq_compute_error": (C.c_int, [_ctx, _f, _f, C.c_int64, _f, _d]),
     "hq_comm_unique_id": (C.c_int, [C.POINTER(C.c_ubyte)]),
     "hq_comm_init": (C.c_int, [_ctx, C.c_int, C.c_int, C.POINTER(C.c_ubyte)]),

@@ -85,6 +85,26 @@ __device__ __forceinline__ float3 opp2f_fast(float o0, float o1, float o2, const
                        lab_f_fast(dot3(o0, o1, o2, m + 6)));
 }
 
+// The argmin coordinates of a colour in CIELAB (option "assign_space" 1; libhq's own addition):
+// (L, a + 128, b + 128) / 256 of the unfiltered colour, from its linear RGB (srgb_lin of each
+// channel) and the illuminant's reciprocals.  One isotropic scale, so the Euclidean distance
+// between two coordinates is dE76 / 256, and under D65 and D50 the sRGB cube lands inside
+// [0, 1]^3.  The one statement of the transform: the coordinate kernel, the palette prep and
+// hq_assign_coords all call it, so a colour has one coordinate whichever way it arrives.
+// The matrix rows are explicit FMA chains, not dot3: the compiler contracts dot3's sum as it
+// sees fit in each kernel, and the same colour must get the same bits in all three.
+__device__ __forceinline__ float assign_coord_t(float lr, float lg, float lb, const float* m, float inv) {
+    return fmaf(lb, m[2], fmaf(lg, m[1], lr * m[0])) * inv;
+}
+__device__ __forceinline__ float3 assign_coord_lab(float lr, float lg, float lb, const float* inv_illum) {
+    const float fx = lab_f_fast(assign_coord_t(lr, lg, lb, c_RGB2XYZ + 0, inv_illum[0]));
+    const float fy = lab_f_fast(assign_coord_t(lr, lg, lb, c_RGB2XYZ + 3, inv_illum[1]));
+    const float fz = lab_f_fast(assign_coord_t(lr, lg, lb, c_RGB2XYZ + 6, inv_illum[2]));
+    return make_float3(fmaf(116.0f, fy, -16.0f) * (1.0f / 256.0f),
+                       fmaf(500.0f, fx - fy, 128.0f) * (1.0f / 256.0f),
+                       fmaf(200.0f, fy - fz, 128.0f) * (1.0f / 256.0f));
+}
+
 // CL:124-145 with true division (setup paths: LabRef, quantize/error image).
 __device__ __forceinline__ float3 opp2lab_ref(float o0, float o1, float o2, const float* illum) {
     const float X = dot3(o0, o1, o2, c_Opp2XYZ + 0);

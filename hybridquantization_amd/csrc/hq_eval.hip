@@ -221,12 +221,53 @@ int ensure_population(hq_ctx* c, int P, int K) {
     if (!cost_fast(c) || K > kMaxK) HIP_TRY(c, c->d_gen_t.ensure(sizeof(float) * 7 * (size_t)g.n_ext + 256));
     HIP_TRY(c, c->h_pal.ensure(sizeof(float) * 4 * (size_t)P * K));
     HIP_TRY(c, c->h_out.ensure(sizeof(double) * (size_t)P * (1 + K)));
+    if (c->assign_space) {  // the argmin's own views: the palettes' coordinates, the pixels'
+        HIP_TRY(c, c->d_arg.ensure(sizeof(float4) * (size_t)P * std::max(K, kMaxK)));
+        if (int rc = ensure_assign_coords(c)) return rc;
+    }
     return ensure_live_tiles(c);  // (a pixel mask on the fast path: the list its launch reads)
 }
 
+// The pixels' coordinate planes under option "assign_space" 1: allocated at the image planes'
+// size and filled by one launch from the packed copy when the context has one, else from the
+// planar floats -- both hold the same k/255 (u8_unit), so the option "img_u8" does not matter
+// here.  Stale after a new image or illuminant (begin_image).  The launch is enqueued on the
+// context's stream, in front of the pass that reads the planes.
+int ensure_assign_coords(hq_ctx* c) {
+    if (c->coords_ok || !c->have_image) return HQ_OK;
+    if (int rc = bind(c)) return rc;
+    const int64_t quads = round_up(c->g.n_ext, 4) / 4;
+    const size_t plane = sizeof(float) * 4 * (size_t)quads;
+    HIP_TRY(c, c->d_cR.ensure(plane));
+    HIP_TRY(c, c->d_cG.ensure(plane));
+    HIP_TRY(c, c->d_cB.ensure(plane));
+    CoordArgs a{c->img_u8 ? c->d_rgbx.as<uint32_t>() : nullptr, c->d_R.as<float>(), c->d_G.as<float>(),
+                c->d_B.as<float>(), c->d_cR.as<float>(), c->d_cG.as<float>(), c->d_cB.as<float>(), c->g.n_ext, quads, {}};
+    inv_illuminant(c, a.inv_illum);
+    // (profiling: timed here and now -- once per image, so the synchronise costs nothing that
+    // matters, and the context's events are free again for the pass that follows)
+    ProfRec pr = prof_begin(c);
+    HIP_TRY(c, timed_launch(pr, kPCoords, [&] { return launch_coords(a, c->stream); }));
+    if (pr.ev) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        prof_accumulate(c, pr);
+    }
+    c->coords_ok = true;
+    return HQ_OK;
+}
+
+int assign_space_excludes(hq_ctx* c, const char* what) {
+    if (!c->assign_space) return HQ_OK;
+    return fail(c, HQ_ERR_UNSUPPORTED, "%s under option assign_space 1 (CIELAB nearest colour): it keeps the sRGB "
+                                       "rule, set assign_space 0", what);
+}
+
 PaletteArgs prep_args(hq_ctx* c, int K) {
-    return PaletteArgs{c->d_pal_in.as<float4>(), c->d_pal.as<float4>(), c->d_opp.as<float4>(),
-                       c->d_opp16.as<uint4>(), c->d_dup.as<uint8_t>(), c->d_pflags.as<int>(), K};
+    PaletteArgs a{c->d_pal_in.as<float4>(), c->d_pal.as<float4>(), c->d_opp.as<float4>(),
+                  c->d_opp16.as<uint4>(), c->d_dup.as<uint8_t>(), c->d_pflags.as<int>(), K,
+                  c->assign_space ? c->d_arg.as<float4>() : c->d_pal.as<float4>(), c->assign_space, {}};
+    inv_illuminant(c, a.inv_illum);
+    return a;
 }
 
 // Counter set `par` of an evaluation of P palettes (P nch sub-palettes Ps).
@@ -250,8 +291,11 @@ GridArgs grid_args(hq_ctx* c, int P, int K, int so = 0) {
     const GridLayout gl = grid_layout(c);
     // (P = sub-palettes; the counters of set c->acc_par)
     const int nch = c->nch_cur;
+    // option "assign_space": the argmin's table is the palettes' coordinates (PaletteArgs::arg);
+    // the grid, the native lists and assign all take it from here (ga.pal)
+    const float4* const table = c->assign_space ? c->d_arg.as<float4>() : c->d_pal.as<float4>();
     // (so: the first of the P sub-palettes in the prepared tables, a palette split's slice)
-    return GridArgs{c->d_pal.as<float4>() + (int64_t)so * kMaxK, c->d_dup.as<uint8_t>() + (int64_t)so * kMaxK,
+    return GridArgs{table + (int64_t)so * kMaxK, c->d_dup.as<uint8_t>() + (int64_t)so * kMaxK,
                     c->d_pflags.as<int>() + so, c->d_lvl1.as<uint8_t>(), c->d_lvl2.as<uint8_t>(),
                     used_set(c, c->acc_par, P),
                     used_stride(P), K, gl.G1, gl.l1p, gl.l2g,
@@ -439,8 +483,12 @@ int enqueue_grid(hq_ctx* c, const GridArgs& ga, bool build, bool n16, int K, int
 AssignArgs assign_args(hq_ctx* c, const GridArgs& ga, int Ps, int Ks, bool ordered) {
     const Geom& g = c->g;
     const int nch = c->nch_cur;
-    AssignArgs aa{c->d_R.as<float>(), c->d_G.as<float>(), c->d_B.as<float>(),
-                  sums_u8(c) ? c->d_rgbx.as<uint32_t>() : nullptr, ga.pal, ga.pflags,
+    // option "assign_space" 1: the pixels' coordinate planes and no packed form, so every argmin
+    // kernel runs its planar instance on them (ga.pal is the coordinate table already)
+    const bool sp = c->assign_space != 0;
+    AssignArgs aa{(sp ? c->d_cR : c->d_R).as<float>(), (sp ? c->d_cG : c->d_G).as<float>(),
+                  (sp ? c->d_cB : c->d_B).as<float>(),
+                  !sp && sums_u8(c) ? c->d_rgbx.as<uint32_t>() : nullptr, ga.pal, ga.pflags,
                   c->d_lvl1.as<uint8_t>(), c->d_lvl2.as<uint8_t>(),
                   c->d_idx.as<uint8_t>(), ga.used_glob, used_stride(Ps), g.n_ext, g.idx_pitch,
                   ga.lvl1_pitch, ga.lvl2_gstride, Ks, c->G2, assign_blocks(c, Ps, ordered)};
@@ -733,13 +781,18 @@ int ensure_render_scratch(hq_ctx* c, const Pass& pass, int P, int K) {
 // exhaustive K > 256 path instead, which keeps the reference's NaN semantics.
 int run_pass(hq_ctx* c, const float* palettes, int P, int K, const Pass& pass) {
     if (int rc = bind(c)) return rc;
-    drop(c);
     const bool fits = palette_fits_fast(palettes, P, K);
+    const int nch = c->chunked && fits && c->G2 > 0 && K > kMaxK && K <= kMaxKChunked ? chunk_count(K) : 1;
+    if (K > kMaxK && nch == 1)  // (enqueue_wide: its argmin reads the colours themselves)
+        if (int rc = assign_space_excludes(c, "K > 256 outside the chunked path (K > 16384, option chunked 0, grid 0 or "
+                                              "a palette outside the fast range)"))
+            return rc;
+    drop(c);
     struct Reset {  // device-resident searches generate clamped palettes of their own chunk count
         hq_ctx* c;
         ~Reset() { c->pal_generic = false, c->nch_cur = 1; }
     } reset{c};
-    c->nch_cur = c->chunked && fits && c->G2 > 0 && K > kMaxK && K <= kMaxKChunked ? chunk_count(K) : 1;
+    c->nch_cur = nch;
     c->pal_generic = !fits;  // (before ensure_population: it sizes the generic path's scratch)
     if (int rc = ensure_population(c, P, K)) return rc;
     if (int rc = ensure_render_scratch(c, pass, P, K)) return rc;
@@ -1178,6 +1231,7 @@ int check_rendered(hq_ctx* c, const RenderCall& r, Scope&& scope) {
     if (!r.ordered && !(r.strength >= 0.0f && r.strength <= 1.0f))
         return fail(c, HQ_ERR_ARG, "strength %g not in [0, 1]", r.strength);
     if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
+    if (int rc0 = assign_space_excludes(c, r.ordered ? "ordered dithering" : "error diffusion")) return rc0;
     auto palette_range = [&] {
         if (population_in_range(r.palettes, r.P, r.K)) return (int)HQ_OK;
         return fail(c, HQ_ERR_ARG, "palette with a channel that is not finite or outside [0, 1]");

@@ -64,6 +64,27 @@ struct PaletteArgs {
     uint8_t* dup;           // [P][256] 1 if an identical colour exists at a lower index
     int* pflags;            // [P] bit0: non-finite colour present -> exhaustive argmin
     int K;
+    // option "assign_space": the table the argmin kernels read, [P][256] (.w = 0).  space 0:
+    // arg == pal, nothing more is stored.  space 1: each colour's CIELAB coordinates
+    // (assign_coord_lab under inv_illum); a coordinate that is not finite sets pflags too
+    float4* arg;
+    int space;
+    float inv_illum[3];
+};
+
+// coords_kernel (hq_argspace.hip): the argmin coordinates of the extended rows' pixels,
+// from the packed bytes (rgbx) or, rgbx null, the planar floats, into three planes of the
+// same length and padding (quads: their floats / 4; the padding reads as zero).
+struct CoordArgs {
+    const uint32_t* rgbx;
+    const float* R;
+    const float* G;
+    const float* B;
+    float* oR;
+    float* oG;
+    float* oB;
+    int64_t n_ext, quads;
+    float inv_illum[3];
 };
 
 constexpr int kSaMaxP = 64;        // device-resident SWASA: largest population

@@ -155,6 +155,10 @@ hipError_t launch_cluster_errors(const ClusterErrArgs&, int idx_bytes, int num_c
 hipError_t launch_color_histogram(const HistArgs&, int num_cu, hipStream_t);
 // hq_reduce.hip: the box reduction of a whole image (the packed form when a.rgbx, else the planar one)
 hipError_t launch_reduce_image(const ReduceArgs&, hipStream_t);
+// hq_argspace.hip: the argmin coordinates (option "assign_space") of the extended rows, and of a list of colours
+hipError_t launch_coords(const CoordArgs&, hipStream_t);
+hipError_t launch_coords_list(const float4* in, float4* out, int64_t n, int space, const float inv_illum[3],
+                              hipStream_t);
 // hq_setup.hip
 hipError_t launch_pack_u8(const float*, const float*, const float*, uint32_t*, int*, int64_t, hipStream_t);
 hipError_t launch_labref_opp(const float*, const float*, const float*, float4*, int64_t, hipStream_t);

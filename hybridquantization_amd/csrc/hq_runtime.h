@@ -114,11 +114,11 @@ struct ProfSlot {
 
 enum Stage {
     kStGrid, kStAssign, kStCost, kStFinalize, kStSaStep, kStComm, kStCentroid, kStLloyd, kStHist, kStErrsum,
-    kStReseed, kStDither, kStReduce, kStDot, kStages
+    kStReseed, kStDither, kStReduce, kStDot, kStCoords, kStages
 };
 inline constexpr const char* kStageNames[kStages] = {"grid", "assign", "cost", "finalize", "sa_step", "comm",
                                                      "centroid", "lloyd", "hist", "errsum", "reseed", "dither",
-                                                     "reduce", "dot"};
+                                                     "reduce", "dot", "coords"};
 
 // The start/stop event pairs of one evaluation (the context's EventSet) or of one
 // search iteration (kPairs pairs per iteration of a run in hq_search::pev).  A pass
@@ -137,13 +137,14 @@ enum Pair {
     kPHist,                                // hq_color_histogram's kernel
     kPReduce,                              // hq_set_image_reduced's kernel
     kPDot,                                 // dot_kernel's launches (one per class), or dot_tile_kernel's one, in the place of grid + assign
+    kPCoords,                              // coords_kernel (option "assign_space" 1), in front of a pass: ensure_assign_coords
     kPairs
 };
 // The stage each pair's time and launch count go to.
 inline constexpr Stage kPairStage[kPairs] = {kStGrid, kStAssign, kStCost, kStFinalize, kStSaStep, kStComm,
                                              kStDither, kStGrid, kStAssign, kStCentroid, kStLloyd, kStGrid,
                                              kStAssign, kStCost, kStErrsum, kStReseed, kStHist, kStReduce,
-                                             kStDot};
+                                             kStDot, kStCoords};
 
 // One evaluation's or iteration's events and which pairs it recorded (events of an
 // earlier call may sit in the other slots, so only recorded pairs are accumulated).
@@ -272,6 +273,14 @@ struct hq_ctx {
     hq::DevBuf d_rgbx;                 // packed 8-bit copy of R,G,B when every channel is k/255
     bool img_u8 = false;
     hq::DevBuf d_labL, d_labA, d_labB;  // planar LabRef, owned rows, lab_pitch
+    // option "assign_space" (0 sRGB, 1 CIELAB): the pixels' argmin coordinates, three planes of
+    // d_R's length and padding, made on the device from the image the context holds by the
+    // first evaluation that needs them (ensure_assign_coords) and the image's and the
+    // illuminant's: begin_image says they are stale.  d_arg: the palettes' coordinates
+    // ([P][256], PaletteArgs::arg).  With space 0 none of the four is allocated or read.
+    int assign_space = 0;
+    hq::DevBuf d_cR, d_cG, d_cB, d_arg;
+    bool coords_ok = false;
 
     // population work buffers
     hq::Resident res;  // what the last pass left in them (drop, commit)
@@ -430,7 +439,8 @@ struct hq_search {
     std::vector<float> fixed;            // 0 .. nfixed-1 of every member, [nfixed][4], for the search's life
     bool fold = false;                   // accept steps reduce the partials (no finalize launch)
     ncclComm_t comm = nullptr;           // the context's communicator at hq_search_create
-    float t_acc = 0.f;                   // temperature / threshold of the iteration
+    int assign_space = 0;                // ... and its option "assign_space": a run under another value is refused
+    float t_acc = 0.f;                  // temperature / threshold of the iteration
     double keep_acc = 0.0;               // whose population awaits acceptance
     hq::DevBuf colors[2], cand[2], err[2], seed[2], best_err[2], best_colors, jA, jC;
     hq::EventSet pev;                    // profiling: 2 kPairs events per iteration of a run
@@ -522,6 +532,15 @@ void commit(hq_ctx* c, const Resident& r);
 Resident resident_of(hq_ctx* c, Resident::Owner owner, int P, int K);
 // (drops the record when, and only when, it reallocates a buffer the record vouches for)
 int ensure_population(hq_ctx* c, int P, int K);
+// option "assign_space" 1: the pixels' coordinate planes in place and current (one launch of
+// coords_kernel when they are stale; ensure_population calls it, so never inside a capture).
+// assign_space_excludes: HQ_ERR_UNSUPPORTED "<what> under option assign_space 1 ..." when the
+// option is on, for the calls that keep the sRGB rule.  inv_illuminant: 1 / the illuminant.
+int ensure_assign_coords(hq_ctx* c);
+int assign_space_excludes(hq_ctx* c, const char* what);
+inline void inv_illuminant(const hq_ctx* c, float inv[3]) {
+    for (int i = 0; i < 3; ++i) inv[i] = 1.0f / c->illum[i];
+}
 // P palettes of K colours ([P][4K]) into d_pal_in -- from the host (through h_pal; chunked:
 // pack_chunks' sub-palettes) or, host null, from the device -- and the palette prep (K > 256
 // unchunked: the upload alone, enqueue_wide preps).

@@ -189,6 +189,7 @@ int begin_image(hq_ctx* c) {
     c->d_apron.release();  // ... and so does a shard's apron (set_apron brings the new image's)
     c->apron_above = c->apron_below = 0;
     c->apron_ok = true;
+    c->coords_ok = false;  // option "assign_space": the coordinates were the old image's and illuminant's
     const size_t plane = sizeof(float) * (size_t)round_up(g.n_ext, 4);
     HIP_TRY(c, c->d_R.ensure(plane));
     HIP_TRY(c, c->d_G.ensure(plane));
@@ -765,6 +766,24 @@ int hq_quantize(hq_ctx* c, const float* rgba4, int64_t n, const float* colors, i
     return HQ_OK;
 }
 
+int hq_assign_coords(hq_ctx* c, int space, const float* rgba4, int64_t n, float* out4) {
+    if (!c) return HQ_ERR_ARG;
+    if (!rgba4 || !out4 || n < 1) return fail(c, HQ_ERR_ARG, "bad colours / output / n=%lld", (long long)n);
+    if (space != 0 && space != 1) return fail(c, HQ_ERR_ARG, "space must be 0 (sRGB) or 1 (CIELAB)");
+    int rc = bind(c);
+    if (rc) return rc;
+    DevBuf din, dout;
+    HIP_TRY(c, din.ensure(sizeof(float4) * n));
+    HIP_TRY(c, dout.ensure(sizeof(float4) * n));
+    float inv[3];
+    inv_illuminant(c, inv);
+    HIP_TRY(c, hipMemcpyAsync(din.p, rgba4, sizeof(float4) * n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, launch_coords_list(din.as<float4>(), dout.as<float4>(), n, space, inv, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out4, dout.p, sizeof(float4) * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return HQ_OK;
+}
+
 int hq_compute_error(hq_ctx* c, const float* orig4, const float* quant4, int64_t n,
                      float* err_img4, double* mean) {
     if (!c || !orig4 || !quant4 || n < 1 || !mean) return HQ_ERR_ARG;
@@ -860,7 +879,12 @@ int hq_set_option(hq_ctx* c, const char* name, int value) {
             c->*o.flag = value != 0;
             return HQ_OK;
         }
-    if (!std::strcmp(name, "grid")) {
+    if (!std::strcmp(name, "assign_space")) {
+        // (the coordinates stay current across a change of the option: they depend on the image
+        // and the illuminant alone, and space 0 reads none of them)
+        if (value != 0 && value != 1) return fail(c, HQ_ERR_ARG, "assign_space must be 0 (sRGB) or 1 (CIELAB)");
+        c->assign_space = value;
+    } else if (!std::strcmp(name, "grid")) {
         if (value != 0 && value != 16 && value != 32 && value != 64)
             return fail(c, HQ_ERR_ARG, "grid must be 0, 16, 32 or 64");
         c->G2 = value;

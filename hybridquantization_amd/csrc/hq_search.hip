@@ -91,6 +91,17 @@ __device__ __forceinline__ bool prep_palette_body(const PaletteArgs& a, int p, f
     if (tid == 0 && blockIdx.x == 0) g_sa_t[3] = wall_clock64();
 #endif
     const bool dup = own && s_min[slot] < (uint32_t)k;
+    // option "assign_space" 1 (a uniform branch): the argmin's table is the colours' CIELAB
+    // coordinates, from the linear RGB above.  A finite colour far outside the cube can have a
+    // coordinate that is not finite (inf - inf): that palette takes the exhaustive argmin too.
+    if (a.space != 0) {
+        if (own) {
+            const float3 q = assign_coord_lab(s_lin[3 * k], s_lin[3 * k + 1], s_lin[3 * k + 2], a.inv_illum);
+            if (!(isfinite(q.x) && isfinite(q.y) && isfinite(q.z))) atomicOr(&L.nonfinite, 1);
+            if (write) a.arg[(int64_t)p * kMaxK + k] = make_float4(q.x, q.y, q.z, 0.f);
+        }
+        __syncthreads();
+    }
     nonfinite = L.nonfinite != 0;
     if (own && write) {
         const float lr = s_lin[3 * k], lg = s_lin[3 * k + 1], lb = s_lin[3 * k + 2];

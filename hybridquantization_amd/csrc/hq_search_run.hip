@@ -399,6 +399,10 @@ int device_search_run(hq_search* s, int iterations, int* ran) {
 int run_scope(hq_search* s, int iterations) {
     const int ite = s->driver ? s->driver->iteration() : s->ite;
     int rc;
+    // the errors a search holds were measured under the argmin rule it was created with
+    if (s->assign_space != s->ctx->assign_space)
+        return fail(s->ctx, HQ_ERR_STATE, "option assign_space changed after hq_search_create (%d, now %d): "
+                                          "recreate the search", s->assign_space, s->ctx->assign_space);
     if (period_in_run(s, s->every, ite, iterations) && ((rc = lloyd_scope(s)) || (rc = lloyd_validate(s)))) return rc;
     if (period_in_run(s, s->repair_every, ite, iterations) && (rc = repair_scope(s))) return rc;
     if ((rc = mask_scope(s->ctx))) return rc;
@@ -435,6 +439,7 @@ int hq_search_create_from(hq_ctx* c, const hq_swasa_params* params, int K, uint6
     hq_search* s = new hq_search{c, nullptr, K};
     s->nfixed = c->fixed_n;  // latched: a later hq_set_fixed_colors does not reach this search
     s->fixed = c->fixed;
+    s->assign_space = c->assign_space;  // latched too: hq_search_run refuses another value
     int rc;
     if (device) {
         if (!c->have_image) rc = fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
@@ -538,6 +543,7 @@ int hq_search_set_ordered(hq_search* s, const float amp[3]) {
         if (s->every > 0 || s->repair_every > 0)
             return fail(c, HQ_ERR_UNSUPPORTED, "a search with hybrid or repair iterations: no ordered cost");
         if (s->dot) return fail(c, HQ_ERR_UNSUPPORTED, "a search under the dot-diffused cost: one rendering per search");
+        if (int rc = assign_space_excludes(c, "hq_search_set_ordered")) return rc;
         if (int rc = ordered_scope(c, s->K)) return rc;
     }
     const Ordered old = s->ord;
@@ -569,6 +575,7 @@ int hq_search_set_dot(hq_search* s, const hq_dot_classes* cls, float strength) {
         if (s->every > 0 || s->repair_every > 0)
             return fail(c, HQ_ERR_UNSUPPORTED, "a search with hybrid or repair iterations: no dot-diffused cost");
         if (s->ordered) return fail(c, HQ_ERR_UNSUPPORTED, "a search under the ordered cost: one rendering per search");
+        if (int rc = assign_space_excludes(c, "hq_search_set_dot")) return rc;
         if (int rc = dot_search_scope(c, s->K)) return rc;
     }
     const bool same_matrix = s->dot_cls.n == m.n && !std::memcmp(s->dot_cls.cls, m.cls, sizeof(int32_t) * m.n * m.n);

@@ -75,6 +75,7 @@ class ImageManipulation:
             check(rc)
         self.openCLFiltersReady = False
         self._filters = None
+        self._assign_space = 0  # option "assign_space" as last set through setOption
 
     # IM:95
     def getOpenCLAvailable(self) -> bool:
@@ -697,6 +698,65 @@ class ImageManipulation:
         check(load().hq_median_cut(_lib.i64ptr(cells), int(bits), int(den), int(K), fptr(pal), C.byref(made)))
         return pal, made.value
 
+    # the space of the nearest-colour rule: libhq's addition (option "assign_space", hq_assign_coords)
+    ASSIGN_SPACES = ("rgb", "lab")
+
+    @classmethod
+    def assignSpaceValue(cls, name) -> int:
+        """``assignSpace=``: "rgb" or "lab" -> option "assign_space"'s value; anything else is a ValueError."""
+        if not isinstance(name, str) or name not in cls.ASSIGN_SPACES:
+            raise ValueError(f"assignSpace={name!r}: one of {', '.join(map(repr, cls.ASSIGN_SPACES))}")
+        return cls.ASSIGN_SPACES.index(name)
+
+    @classmethod
+    def checkAssignSpace(cls, name, **renderings) -> int:
+        """assignSpaceValue, and under "lab" a ValueError naming the renderings asked for with it
+        (``renderings``: name -> value; off when None, False or a zero strength): they keep the sRGB rule."""
+        space = cls.assignSpaceValue(name)
+        on = [k for k, v in renderings.items()
+              if not (v is None or v is False or (isinstance(v, (int, float)) and float(v) == 0.0))]
+        if space and on:
+            raise ValueError(f"assignSpace={name!r} with {', '.join(on)}: error diffusion and ordered dithering keep "
+                             "the sRGB rule")
+        return space
+
+    def assignCoords(self, colors, space="lab"):
+        """hq_assign_coords: the coordinates the argmin ranks ``colors`` -- (n, 3), (n, 4) or flat
+        4n -- by in ``space`` under the context's illuminant, float32 (n, 4) with .w = 0: "rgb"
+        copies R, G, B; "lab" is (L, a + 128, b + 128) / 256 of the colour's CIELAB, made by the
+        device function the evaluation itself uses."""
+        value = self.assignSpaceValue(space)
+        ctx = self._require()
+        a = np.asarray(colors, np.float32)
+        if a.ndim == 2 and a.shape[1] == 3:
+            a = np.concatenate([a, np.zeros((a.shape[0], 1), np.float32)], axis=1)
+        if a.size == 0 or a.size % 4 or (a.ndim == 2 and a.shape[1] != 4) or a.ndim > 2:
+            raise ValueError(f"colors of shape {np.shape(colors)}: (n, 3), (n, 4) or flat 4n")
+        a = np.ascontiguousarray(a.reshape(-1, 4))
+        out = np.zeros_like(a)
+        check(self._lib.hq_assign_coords(ctx, value, fptr(a), a.shape[0], fptr(out)), ctx)
+        return out
+
+    def quantizeAssigned(self, colors, assignSpace="lab"):
+        """The nearest-colour rendering of the context's image with the palette colors float[4K]
+        under ``assignSpace``, in ``quantize``'s output format: palette[idx] of the index image of
+        one evaluation, so the picture is the one that evaluation scored.  Sets ``lastUsedColors``
+        and ``assignedError``, its mean dE.  The context's option is back afterwards."""
+        value = self.assignSpaceValue(assignSpace)
+        pal = _f32(colors).reshape(1, -1)
+        before = self._assign_space
+        try:
+            self.setOption("assign_space", value)
+            costs, used = self.computeQuantizationErrorPopulation(pal, 0.0, return_used=True)
+            idx = self.getIndices(0) if pal.shape[1] // 4 <= 256 else self.getIndices32(0)
+        finally:
+            self.setOption("assign_space", before)
+        table = pal.reshape(-1, 4).copy()
+        table[:, 3] = 0.0
+        self.lastUsedColors = used[0]
+        self.assignedError = float(costs[0])
+        return table[idx].reshape(-1)
+
     # IM:383
     def findBestQuantization(self, inlinergbOriginal, inlineScielabOriginal, w, nbOfColors,
                              simulatedAnnealing, filters, absfilters, illuminant,
@@ -704,7 +764,7 @@ class ImageManipulation:
                              init=None, initBits=5, repairEvery=0, repairMoves=-1, repairSteps=0,
                              dither=0.0, ditherSearch=False, ordered=None, orderedSearch=False, mask=None,
                              weights=None, fixed=None, ditherKernel=None, dot=0.0, dotSearch=False,
-                             dotClasses=None):
+                             dotClasses=None, assignSpace=None):
         """Full SWASA search (IM:383-591) on the GPU; returns bestColors float[4K].
 
         ``simulatedAnnealing`` is a :class:`~hybridquantization_amd.swasa.SWASA`;
@@ -779,19 +839,34 @@ class ImageManipulation:
         the search optimises the dot-diffused cost instead, host-driven through
         hq_swasa_search_host_fixed exactly as ``ditherSearch`` is, with the same exclusions of
         the k-means and repair moves; ``bestError`` and ``bestErrorDot`` are then both that cost.
+        ``assignSpace`` (option "assign_space"): None leaves the context's option as the caller
+        set it (0, sRGB, on a new context), and no option call is made; "rgb" is the reference's
+        nearest colour in sRGB; "lab" assigns every pixel the palette colour nearest in CIELAB under ``illuminant``, in the
+        search, its k-means and repair moves (which stay in RGB) and the polishes, and every
+        reported error is that assignment's.  "rgb" or "lab" is set for this call and the value
+        last set through setOption is back afterwards.  Anything else, or "lab" together with ``dither``, ``dot``,
+        ``ordered`` or their searches, raises ValueError before anything runs.
         """
+        space = None if assignSpace is None else self.checkAssignSpace(
+            assignSpace, dither=dither, ditherSearch=ditherSearch, ordered=ordered, orderedSearch=orderedSearch,
+            dot=dot, dotSearch=dotSearch)
         ctx = self._require()
         fx = None if fixed is None else np.ascontiguousarray(fixed_colors(fixed, int(nbOfColors)))
         before = None if fx is None else self.fixedColors()
+        space_before = self._assign_space
         try:
             if fx is not None:
                 self.setFixedColors(fx)
+            if space is not None:
+                self.setOption("assign_space", space)
             return self._findBestQuantization(
                 inlinergbOriginal, inlineScielabOriginal, w, nbOfColors, simulatedAnnealing, filters, absfilters,
                 illuminant, iterations, stop, lloydSteps, lloydEvery, init, initBits, repairEvery, repairMoves,
                 repairSteps, dither, ditherSearch, ordered, orderedSearch, mask, weights, fx, ditherKernel,
                 dot, dotSearch, dotClasses)
         finally:
+            if space is not None:
+                self.setOption("assign_space", space_before)
             if before is not None:
                 self.setFixedColors(before)
 
@@ -996,6 +1071,8 @@ class ImageManipulation:
     def setOption(self, name: str, value: int):
         ctx = self._require()
         check(self._lib.hq_set_option(ctx, name.encode(), int(value)), ctx)
+        if name == "assign_space":  # (the library has no getter: what findBestQuantization puts back)
+            self._assign_space = int(value)
 
     # IM:265
     def close(self):

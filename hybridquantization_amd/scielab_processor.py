@@ -90,7 +90,7 @@ def makeChannels(inline):
 def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
                  whitepoint=Whitepoint.D65, verbose=False, device=0, iterations=None, dither=0.0,
                  ordered=None, mask=None, weights=None, fixed=None, pyramid=None, ditherKernel=None,
-                 dot=0.0, dotClasses=None, dotSearch=False):
+                 dot=0.0, dotClasses=None, dotSearch=False, assignSpace=None):
     """HQ:93-137 without the GUI: planar float image (3, N) in [0,1] ->
     (quantized planar image (3, N), bestColors float[4K], best error).  ``dither`` > 0
     (libhq's addition): the returned image is the best palette's Floyd-Steinberg rendering
@@ -112,8 +112,15 @@ def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
     ``dither`` or ``ordered``): the returned image is the best palette's dot-diffused rendering
     at that strength (ImageManipulation.quantizeDotDiffused) under the class matrix
     ``dotClasses`` (None: Knuth's 8 x 8); ``dotSearch`` is findBestQuantization's (False, True
-    or "device": the search itself runs under that cost)."""
+    or "device": the search itself runs under that cost).  ``assignSpace`` (None, "rgb" or "lab":
+    findBestQuantization's): under "lab" every pixel takes the palette colour nearest in CIELAB,
+    in the search and in the returned image, which is rendered from the index image of the best
+    palette's evaluation (ImageManipulation.quantizeAssigned) and so is the picture the search
+    scored (hq_quantize keeps the sRGB rule).  Anything else, or "lab" with ``dither``,
+    ``ordered``, ``dot``, ``dotSearch`` or ``pyramid``, is a ValueError before anything runs."""
     fixed_colors(fixed, int(nbOfColors))
+    lab = assignSpace is not None and ImageManipulation.checkAssignSpace(
+        assignSpace, dither=dither, ordered=ordered, dot=dot, dotSearch=dotSearch, pyramid=pyramid) != 0
     if ordered is not None and float(dither) > 0.0:
         raise ValueError("dither and ordered: one rendering")
     if float(dot) > 0.0 and (ordered is not None or float(dither) > 0.0):
@@ -138,7 +145,10 @@ def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
         sc_img = sp.sRGBToScielab(image, w)
         best = sp.bestColors(inline_rgb, sc_img, w, nbOfColors, swasa, iterations=iterations, dither=dither,
                              ditherKernel=ditherKernel, ordered=ordered, mask=mask, weights=weights, fixed=fixed,
-                             dot=dot, dotClasses=dotClasses, dotSearch=dotSearch)
+                             dot=dot, dotClasses=dotClasses, dotSearch=dotSearch, assignSpace=assignSpace)
+        if lab:
+            q = ip.quantizeAssigned(best, assignSpace)
+            return np.stack(makeChannels(q)), best, ip.bestError
         q = (ip.quantizeDotDiffused(best, dot, classes=dotClasses) if float(dot) > 0.0 else
              ip.quantizeOrdered(best, ordered) if ordered is not None else
              ip.quantizeDithered(best, dither, kernel=ditherKernel) if float(dither) > 0.0 else

@@ -1115,7 +1115,9 @@ int hq_profile_enable(hq_ctx *ctx, int on);
  * and argmin count under "grid" and "assign" like the plain one's), "reduce" (hq_set_image_reduced's
  * kernel, on the destination context), "dot" (hq_dot_population's launches, one per class or the
  * tiled form's one, in the place of "grid" and "assign": the time from the first one's start to
- * the last one's end, counted as one launch per call); returns total ms and launch
+ * the last one's end, counted as one launch per call), "coords" (option "assign_space" 1: the
+ * kernel that makes the pixels' argmin coordinates, once per image and illuminant, in front of
+ * the evaluation that first needs them); returns total ms and launch
  * count (HIP events on the context stream). */
 int hq_profile_get(hq_ctx *ctx, const char *kernel, double *total_ms, int64_t *launches);
 int hq_profile_reset(hq_ctx *ctx);
@@ -1269,8 +1271,47 @@ int hq_search_info(const hq_search *s, int *device_resident, int *nch, int *grap
  *                  all-gather gives every rank all P results (SURVEY 8e's split of large
  *                  populations; P must divide by N); 0 (default) = row-block shards
  *   "slice_ranks", "slice_rank"  test only: the same palette slice without a
- *                  communicator (hq_eval_population_partial: other rows read 0) */
+ *                  communicator (hq_eval_population_partial: other rows read 0)
+ *
+ * Not a tuning knob, since it changes what is computed:
+ *   "assign_space" the space in which a pixel's nearest palette colour is found: 0 (default) =
+ *                  sRGB, the reference's rule (CL:172-199), every output and launch what it was;
+ *                  1 = CIELAB under the context's illuminant (libhq's own addition); anything else
+ *                  is HQ_ERR_ARG.  Under 1 a colour (R, G, B) has the coordinates (L, a + 128,
+ *                  b + 128) / 256 of its unfiltered CIELAB (hq_assign_coords), whose Euclidean
+ *                  distance is dE76 / 256, and the same exact argmin kernels run on the pixels'
+ *                  and the palettes' coordinates in their planar form (hq_last_path reports
+ *                  HQ_PIXELS_PLANAR); the index images, used flags and costs are that
+ *                  assignment's.  The stencil cost, the k-means sums, the error statistics, the
+ *                  repair rule and the histogram read colours as before, so a k-means or repair
+ *                  move works from the CIELAB assignment and stays in RGB.  The pixels'
+ *                  coordinates are made on the device before the next evaluation that needs them
+ *                  and again after a new image or illuminant (hq_set_image*, hq_set_image_reduced).
+ *                  Under D65 and D50 the whole sRGB cube lands inside [0, 1]^3; under illuminant A
+ *                  saturated blues do not (b < -128), and such pixels take the argmin's exact
+ *                  reference loop for pixels outside the cube: correct and slow.  The coordinates
+ *                  are not rescaled per illuminant.  The sRGB gamut fills about 7 % of the coordinate cube,
+ *                  so a palette's candidate lists are as long as those of one 14 times as large under 0:
+ *                  at K = 256 set "grid" 64 with it (at C3 the argmin takes 0.20 ms there against 2.26 ms
+ *                  under the default 32, where most pixels fall back to the exhaustive loop).
+ *                  Served under 1: hq_eval_population[_partial] (row-block shards, a communicator),
+ *                  every cost path, dE type, mask and weights, "grid" 0 .. 64, K <= 16384 on the
+ *                  chunked path, hq_cluster_sums, hq_cluster_errors, hq_refine_population,
+ *                  hq_repair_population, fixed colours, hq_search_* (a search latches the value at
+ *                  hq_search_create*; hq_search_run under another value is HQ_ERR_STATE, ran = 0).
+ *                  HQ_ERR_UNSUPPORTED under 1: K > 256 off the chunked path (K > 16384, "chunked" 0,
+ *                  "grid" 0, a palette outside the fast range), hq_dither_population,
+ *                  hq_diffuse_population, hq_dot_population[_partial],
+ *                  hq_ordered_population[_partial], hq_search_set_ordered and hq_search_set_dot with
+ *                  a non-zero parameter.  hq_quantize keeps the reference's sRGB rule (CL:147-170)
+ *                  whatever the option says. */
 int hq_set_option(hq_ctx *ctx, const char *name, int value);
+
+/* The argmin coordinates of n colours (rgba4, n x 4 floats) in space `space` (option
+ * "assign_space"'s values) under the context's illuminant, by the device function the
+ * evaluation itself uses; out4 is n x 4 floats, .w = 0.  space 0 copies R, G, B.  A null
+ * pointer, n < 1 or another space: HQ_ERR_ARG. */
+int hq_assign_coords(hq_ctx *ctx, int space, const float *rgba4, int64_t n, float *out4);
 
 #ifdef __cplusplus
 }
