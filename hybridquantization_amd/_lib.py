@@ -122,6 +122,8 @@ SIGNATURES = {
     "hq_refine_population": (C.c_int, [_ctx, _f, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _d,
                                        _i32, _d]),
     "hq_cluster_errors": (C.c_int, [_ctx, C.c_int, C.c_int, _i64, _f]),
+    "hq_cost_gradient": (C.c_int, [_ctx, C.c_int, C.c_int, _d]),
+    "hq_descend_population": (C.c_int, [_ctx, _f, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _d, _i32, _d]),
     "hq_reseed_unused": (C.c_int, [_i64, _f, C.c_int, C.c_int, C.c_int, _f, C.POINTER(C.c_int)]),
     "hq_reseed_unused_fixed": (C.c_int, [_i64, _f, C.c_int, C.c_int, C.c_int, C.c_int, _f, C.POINTER(C.c_int)]),
     "hq_set_fixed_colors": (C.c_int, [_ctx, _f, C.c_int]),

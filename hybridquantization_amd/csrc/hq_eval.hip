@@ -7,6 +7,7 @@
 
 #include "hq_diffuse.h"
 #include "hq_dot.h"
+#include "hq_grad.h"
 #include "hq_runtime.h"
 
 using namespace hq;
@@ -1358,6 +1359,149 @@ int ensure_dot_pass(hq_ctx* c, const hq_dot_classes& m, int P, int K) {
 
 }  // namespace hq
 
+namespace {
+
+// ---- the cost's palette gradient (hq_grad.hip; hq.h) -----------------------
+// What hq_cost_gradient refuses: first what the context is (HQ_ERR_UNSUPPORTED), then what it
+// holds (hq_cluster_sums' state rule, but a rendering's index images serve as an evaluation's do).
+int gradient_config(hq_ctx* c, int K) {
+    const char* const what = "hq_cost_gradient";
+    if (K > kMaxK) return fail(c, HQ_ERR_UNSUPPORTED, "%s at K=%d > %d: the bins are the u8 index images'", what, K, kMaxK);
+    if (c->de_type != HQ_DE_CIE76)
+        return fail(c, HQ_ERR_UNSUPPORTED, "%s under dE type %d: the gradient is dE76's", what, c->de_type);
+    if (c->have_image && !whole_image(c))
+        return fail(c, HQ_ERR_UNSUPPORTED, "%s on a row-block shard: the adjoint blur needs the whole image", what);
+    if (c->comm && c->nranks > 1)
+        return fail(c, HQ_ERR_UNSUPPORTED, "%s with a communicator of %d ranks", what, c->nranks);
+    if (c->psplit || c->slice_ranks > 1) return fail(c, HQ_ERR_UNSUPPORTED, "%s on a palette slice", what);
+    if (c->mask_on) return fail(c, HQ_ERR_UNSUPPORTED, "%s under %s (%s)", what, mask_noun(c), mask_call(c));
+    if (c->have_image && (int64_t)c->g.W * c->g.H > ((int64_t)1 << 30))
+        return fail(c, HQ_ERR_UNSUPPORTED, "%s on more than 2^30 pixels: the fixed-point sums are sized for that", what);
+    return HQ_OK;
+}
+int gradient_scope(hq_ctx* c, int P, int K) {
+    if (int rc = gradient_config(c, K)) return rc;
+    const Resident& r = c->res;
+    if (!c->have_image || !(r.owner == Resident::Eval || r.owner == Resident::Render))
+        return fail(c, HQ_ERR_STATE, "no population evaluated or rendered on this image and these filters since the "
+                                     "last search run");
+    if (P != r.P || K != r.K)
+        return fail(c, HQ_ERR_STATE, "P=%d, K=%d: the last evaluation had P=%d, K=%d", P, K, r.P, r.K);
+    if (r.n != r.P || r.nch != 1)
+        return fail(c, HQ_ERR_UNSUPPORTED, "palette slice: this device holds %d of the %d index images", r.n, r.P);
+    return HQ_OK;
+}
+
+// hq_cost_gradient into grad ([P][K][4]); nothing is written unless HQ_OK.  The index images, the
+// prepared palettes, the counter sets and every other table stay what they are.
+int cost_gradient(hq_ctx* c, int P, int K, double* grad) {
+    if (int rc = gradient_scope(c, P, K)) return rc;
+    if (int rc = bind(c)) return rc;
+    const Geom& g = c->g;
+    const int64_t N = (int64_t)g.W * g.H;
+    const bool tiled = c->half <= kGradMaxHalfTiled && c->grad_tiled != 0;
+    if (c->grad_tiled == 1 && !tiled)
+        return fail(c, HQ_ERR_UNSUPPORTED, "option grad_tiled 1 at half-width %d > %d", c->half, kGradMaxHalfTiled);
+    GradArgs a{};
+    lab_matrix(c, a.m_lab);
+    const int shift = grad_shift(grad_bound(a.m_lab, c->k1.data(), c->k2.data(), c->k3.data(), c->absk3.data(), c->taps));
+    if (shift == kGradNoShift) return fail(c, HQ_ERR_UNSUPPORTED, "hq_cost_gradient: taps too large for the fixed-point sums");
+    hipStream_t s = c->stream;
+    const size_t n4 = (size_t)P * K * 4;
+    HIP_TRY(c, c->d_grad_g.ensure(sizeof(float4) * (size_t)P * (size_t)N));
+    HIP_TRY(c, c->d_grad_sums.ensure(sizeof(int64_t) * n4));
+    if (!tiled) HIP_TRY(c, c->d_grad_t.ensure(sizeof(float) * 7 * (size_t)N));
+    HIP_TRY(c, hipMemsetAsync(c->d_grad_sums.p, 0, sizeof(int64_t) * n4, s));
+    a.idx = c->d_idx.as<uint8_t>();
+    a.opp = c->d_opp.as<float4>();
+    a.k1 = c->d_k1.as<float>();
+    a.k2 = c->d_k2.as<float>();
+    a.k3 = c->d_k3.as<float>();
+    a.absk3 = c->d_absk3.as<float>();
+    a.labL = c->d_labL.as<float>();
+    a.labA = c->d_labA.as<float>();
+    a.labB = c->d_labB.as<float>();
+    a.t = c->d_grad_t.as<float>();
+    a.g = c->d_grad_g.as<float4>();
+    a.sums = c->d_grad_sums.as<unsigned long long>();
+    a.idx_pitch = g.idx_pitch;
+    a.W = g.W, a.H = g.H, a.lab_pitch = g.lab_pitch;
+    a.P = P, a.K = K, a.half = c->half;
+    a.scale = std::ldexp(1.0f, shift);
+    ProfRec pr = prof_begin(c);
+    hipEvent_t ev_pix[2] = {nullptr, nullptr}, ev_adj[2] = {nullptr, nullptr};
+    if (pr.ev) {
+        ev_pix[0] = pr.ev[2 * kPGradPixel], ev_pix[1] = pr.ev[2 * kPGradPixel + 1];
+        ev_adj[0] = pr.ev[2 * kPGradAdjoint], ev_adj[1] = pr.ev[2 * kPGradAdjoint + 1];
+        pr.recorded |= (1u << kPGradPixel) | (1u << kPGradAdjoint);
+    }
+    HIP_TRY(c, tiled ? launch_grad_tiled(a, s, pr.ev ? ev_pix : nullptr, pr.ev ? ev_adj : nullptr)
+                     : launch_grad_plain(a, s, pr.ev ? ev_pix : nullptr, pr.ev ? ev_adj : nullptr));
+    std::vector<int64_t> sums(n4);
+    std::vector<float> pal((size_t)P * kMaxK * 4);
+    HIP_TRY(c, hipMemcpyAsync(sums.data(), c->d_grad_sums.p, sizeof(int64_t) * n4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(pal.data(), c->d_pal.p, sizeof(float) * pal.size(), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    prof_accumulate(c, pr);
+    static const double rgb2opp[9] = {0.266413f, 0.603167f, 0.00113333f, -0.124957f, 0.0375879f,
+                                      -0.133381f, -0.0803345f, -0.331467f, 0.449132f};  // (hq_device.h c_RGB2Opp)
+    for (int p = 0; p < P; ++p)
+        grad_chain(&sums[(size_t)p * K * 4], &pal[(size_t)p * kMaxK * 4], K, (double)N, shift, rgb2opp,
+                   grad + (size_t)p * K * 4);
+    return HQ_OK;
+}
+
+// hq_descend_population's loop: evaluate; then per step the gradient of what the device holds,
+// the candidates (descend_step, hq_host.cpp), their evaluation and the acceptance per palette.
+// The device ends on the candidates of the last step taken; the palettes returned are the
+// accepted ones, whose costs and used flags were kept from their own evaluations.
+int descend_population(hq_ctx* c, float* palettes, int P, int K, int steps, float rate, float delta, double* costs,
+                       int32_t* used, double* trace) {
+    const size_t n4 = (size_t)P * K * 4, nu = (size_t)P * K;
+    const double N = (double)c->g.W * (double)c->g.H;
+    std::vector<float> cur(palettes, palettes + n4), cand(n4);
+    std::vector<double> cst(P), ccst(P), eta(P, (double)rate), grad(n4);
+    std::vector<int32_t> usd(nu), cusd(nu);
+    int rc;
+    if ((rc = hq_eval_population(c, cur.data(), P, K, delta, cst.data(), usd.data()))) return rc;
+    if (trace) std::copy(cst.begin(), cst.end(), trace);
+    bool at_cur = true;  // the device holds cur's index images (else: the last candidates')
+    for (int s = 1; s <= steps; ++s) {
+        if (!at_cur && (rc = hq_eval_population(c, cur.data(), P, K, delta, ccst.data(), cusd.data()))) return rc;
+        if ((rc = cost_gradient(c, P, K, grad.data()))) return rc;
+        bool changed = false;
+        for (int p = 0; p < P; ++p)
+            changed |= descend_step(&cur[(size_t)p * K * 4], &grad[(size_t)p * K * 4], K, c->fixed_n, N, eta[p],
+                                    &cand[(size_t)p * K * 4]);
+        if (!changed) {  // every colour at rest (or clamped where it is): the remaining steps repeat this one
+            for (int t = s; trace && t <= steps; ++t) std::copy(cst.begin(), cst.end(), trace + (size_t)t * P);
+            at_cur = true;
+            break;
+        }
+        if ((rc = hq_eval_population(c, cand.data(), P, K, delta, ccst.data(), cusd.data()))) return rc;
+        at_cur = true;
+        for (int p = 0; p < P; ++p) {
+            if (ccst[p] < cst[p]) {
+                cst[p] = ccst[p];
+                std::copy(cand.begin() + (size_t)p * K * 4, cand.begin() + (size_t)(p + 1) * K * 4,
+                          cur.begin() + (size_t)p * K * 4);
+                std::copy(cusd.begin() + (size_t)p * K, cusd.begin() + (size_t)(p + 1) * K, usd.begin() + (size_t)p * K);
+                eta[p] *= 1.5;
+            } else {
+                eta[p] *= 0.5;
+                at_cur = false;  // (the device holds a rejected candidate's index image for p)
+            }
+        }
+        if (trace) std::copy(cst.begin(), cst.end(), trace + (size_t)s * P);
+    }
+    std::copy(cur.begin(), cur.end(), palettes);
+    std::copy(cst.begin(), cst.end(), costs);
+    if (used) std::copy(usd.begin(), usd.end(), used);
+    return HQ_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int hq_set_dither_map(hq_ctx* c, const float* map, int mw, int mh) {
@@ -1552,6 +1696,26 @@ int hq_repair_population(hq_ctx* c, float* palettes, int P, int K, int steps, fl
         *changed = !std::all_of(moved.begin(), moved.end(), [](int m) { return m == 0; });
         return r;
     });
+}
+
+int hq_cost_gradient(hq_ctx* c, int P, int K, double* grad) {
+    if (!c) return HQ_ERR_ARG;
+    if (!grad || P < 1 || K < 1) return fail(c, HQ_ERR_ARG, "bad grad / P=%d / K=%d", P, K);
+    std::vector<double> out((size_t)P * K * 4);
+    const int rc = cost_gradient(c, P, K, out.data());
+    if (!rc) std::copy(out.begin(), out.end(), grad);
+    return rc;
+}
+
+int hq_descend_population(hq_ctx* c, float* palettes, int P, int K, int steps, float rate, float delta,
+                          double* costs, int32_t* used, double* trace) {
+    int rc = check_improve_args(c, palettes, P, K, steps, costs, "hq_descend_population", "");
+    if (rc) return rc;
+    if (!(rate > 0.0f) || !std::isfinite(rate)) return fail(c, HQ_ERR_ARG, "rate=%g: a finite step above 0", (double)rate);
+    // hq_cost_gradient's refusals that need no evaluation, before anything is enqueued (steps = 0 is
+    // hq_eval_population and takes none of them)
+    if (steps > 0 && (rc = gradient_config(c, K))) return rc;
+    return descend_population(c, palettes, P, K, steps, rate, delta, costs, used, trace);
 }
 
 }  // extern "C"

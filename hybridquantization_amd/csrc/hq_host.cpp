@@ -12,6 +12,7 @@
 #include <limits>
 #include <vector>
 
+#include "hq_grad.h"
 #include "hq_lloyd.h"
 #include "hq_swasa.h"
 
@@ -424,4 +425,26 @@ extern "C" int hq_bayer_map(int log2n, float* map) {
             map[y * n + x] = ((float)B + 0.5f) * inv - 0.5f;
         }
     return HQ_OK;
+}
+
+// The descent step of hq_descend_population (libhq's addition; hq.h): a colour with pixels that
+// is not fixed moves against the mean gradient over its own pixels, grad N / n, by `rate`, is
+// clamped to [0, 1] in double and stored as float; every other colour keeps its bits.  A
+// gradient that is not finite moves nothing (the colour keeps its bits).
+bool hq::descend_step(const float* pal, const double* grad, int K, int nfixed, double n_pixels, double rate,
+                      float* cand) {
+    bool changed = false;
+    std::memcpy(cand, pal, sizeof(float) * 4 * (size_t)K);
+    for (int k = nfixed > 0 ? nfixed : 0; k < K; ++k) {
+        const double n = grad[4 * k + 3];
+        if (!(n > 0.0)) continue;
+        for (int ch = 0; ch < 3; ++ch) {
+            const double v = (double)pal[4 * k + ch] - rate * grad[4 * k + ch] * n_pixels / n;
+            if (!std::isfinite(v)) continue;
+            const float f = (float)std::min(std::max(v, 0.0), 1.0);
+            changed |= std::memcmp(&f, &pal[4 * k + ch], sizeof(float)) != 0;
+            cand[4 * k + ch] = f;
+        }
+    }
+    return changed;
 }

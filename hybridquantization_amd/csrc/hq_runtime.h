@@ -114,11 +114,11 @@ struct ProfSlot {
 
 enum Stage {
     kStGrid, kStAssign, kStCost, kStFinalize, kStSaStep, kStComm, kStCentroid, kStLloyd, kStHist, kStErrsum,
-    kStReseed, kStDither, kStReduce, kStDot, kStCoords, kStages
+    kStReseed, kStDither, kStReduce, kStDot, kStCoords, kStGradPixel, kStGradAdjoint, kStages
 };
 inline constexpr const char* kStageNames[kStages] = {"grid", "assign", "cost", "finalize", "sa_step", "comm",
                                                      "centroid", "lloyd", "hist", "errsum", "reseed", "dither",
-                                                     "reduce", "dot", "coords"};
+                                                     "reduce", "dot", "coords", "grad_pixel", "grad_adjoint"};
 
 // The start/stop event pairs of one evaluation (the context's EventSet) or of one
 // search iteration (kPairs pairs per iteration of a run in hq_search::pev).  A pass
@@ -138,13 +138,14 @@ enum Pair {
     kPReduce,                              // hq_set_image_reduced's kernel
     kPDot,                                 // dot_kernel's launches (one per class), or dot_tile_kernel's one, in the place of grid + assign
     kPCoords,                              // coords_kernel (option "assign_space" 1), in front of a pass: ensure_assign_coords
+    kPGradPixel, kPGradAdjoint,            // hq_cost_gradient: the kernels that make g, those that make a and the sums
     kPairs
 };
 // The stage each pair's time and launch count go to.
 inline constexpr Stage kPairStage[kPairs] = {kStGrid, kStAssign, kStCost, kStFinalize, kStSaStep, kStComm,
                                              kStDither, kStGrid, kStAssign, kStCentroid, kStLloyd, kStGrid,
                                              kStAssign, kStCost, kStErrsum, kStReseed, kStHist, kStReduce,
-                                             kStDot, kStCoords};
+                                             kStDot, kStCoords, kStGradPixel, kStGradAdjoint};
 
 // One evaluation's or iteration's events and which pairs it recorded (events of an
 // earlier call may sit in the other slots, so only recorded pairs are accumulated).
@@ -305,6 +306,11 @@ struct hq_ctx {
     int planar_ok = -1;
     hq::DevBuf d_hist;             // hq_color_histogram: [2^(3 bits)][4] int64 cells, then the range flag
     hq::DevBuf d_errstat, d_worst; // [P][K][4] u64 statistics, then the flag; [P][K] float4 worst pixels
+    // hq_cost_gradient (hq_grad.hip): g [P][N] float4, the sums [P][K][4] int64, the plain pair's
+    // [7][N] scratch; option "grad_tiled" (-1 by the half-width, 0 the plain pair, 1 the tiled form
+    // wherever it exists)
+    hq::DevBuf d_grad_g, d_grad_sums, d_grad_t;
+    int grad_tiled = -1;
     hq::DevBuf d_dcarry;           // a Diffused pass: [P][R][3][W] errors of a strip's last R rows (DiffuseArgs::carry)
     // dot diffusion: the class matrix of the last hq_dot_population (n = 0: none yet), its two
     // per-cell tables on the device ([2][kDotCells] words, uploaded when the matrix changes:

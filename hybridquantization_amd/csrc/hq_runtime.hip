@@ -941,6 +941,9 @@ int hq_set_option(hq_ctx* c, const char* name, int value) {
     } else if (!std::strcmp(name, "cent_span")) {
         if (value < 0) return fail(c, HQ_ERR_ARG, "cent_span must be >= 0 (0 = auto)");
         c->cent_span = value;
+    } else if (!std::strcmp(name, "grad_tiled")) {
+        if (value < -1 || value > 1) return fail(c, HQ_ERR_ARG, "grad_tiled must be -1, 0 or 1");
+        c->grad_tiled = value;
     } else if (!std::strcmp(name, "assign_blocks_per_cu")) {
         if (value < 0 || value > 64) return fail(c, HQ_ERR_ARG, "assign_blocks_per_cu in [0,64] (0 = auto)");
         c->assign_blocks_per_cu = value;

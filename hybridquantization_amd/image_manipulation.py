@@ -34,6 +34,11 @@ class deltaETypes:  # IM:20
     CIEDE2000 = _lib.HQ_DE_CIEDE2000
 
 
+# descendPopulation's starting step: a colour moves by this times the mean dE/dRGB over its own
+# pixels (DESIGN.md 30 has the measurement it comes from)
+DESCEND_RATE = 1e-3
+
+
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
@@ -292,6 +297,22 @@ class ImageManipulation:
         trace = np.zeros((int(steps) + 1, P), np.float64)
         check(fn(ctx, fptr(pal), P, K, int(steps), *mid, dptr(costs), iptr(used), dptr(trace)), ctx)
         return (pal, costs, used, trace) if return_trace else (pal, costs, used)
+
+    # the cost's palette gradient and the descent polish: libhq's additions (hq_cost_gradient & co.)
+    def costGradient(self, P: int, K: int):
+        """hq_cost_gradient of the population whose index images the context holds (P, K: the last
+        evaluation's or rendering's): (grad float64 (P, K, 3) = dC/d(R, G, B) with the index images
+        held fixed, counts int64 (P, K))."""
+        ctx = self._require()
+        out = np.zeros((int(P), int(K), 4), np.float64)
+        check(self._lib.hq_cost_gradient(ctx, int(P), int(K), dptr(out)), ctx)
+        return out[..., :3].copy(), out[..., 3].astype(np.int64)
+
+    def descendPopulation(self, colors, steps, rate: float = DESCEND_RATE, delta: float = 2.0, return_trace=False):
+        """hq_descend_population: `steps` accepted-or-halved gradient steps on each palette of colors
+        (P, 4K).  Returns (palettes (P, 4K), costs (P,), used (P, K)) [, trace (steps + 1, P)]."""
+        return self._improve(self._lib.hq_descend_population, colors, steps, (float(rate), float(delta)),
+                             return_trace)
 
     # repairing unused colours: libhq's additions (hq_cluster_errors & co., no reference counterpart)
     def clusterErrors(self, P: int, K: int):
@@ -764,7 +785,7 @@ class ImageManipulation:
                              init=None, initBits=5, repairEvery=0, repairMoves=-1, repairSteps=0,
                              dither=0.0, ditherSearch=False, ordered=None, orderedSearch=False, mask=None,
                              weights=None, fixed=None, ditherKernel=None, dot=0.0, dotSearch=False,
-                             dotClasses=None, assignSpace=None):
+                             dotClasses=None, assignSpace=None, descendSteps=0, descendRate=None):
         """Full SWASA search (IM:383-591) on the GPU; returns bestColors float[4K].
 
         ``simulatedAnnealing`` is a :class:`~hybridquantization_amd.swasa.SWASA`;
@@ -791,6 +812,11 @@ class ImageManipulation:
         when the iteration is hybrid too.  ``repairSteps`` > 0: the best palette is
         polished by that many repair steps (hq_repair_population, keep_best) before
         the k-means polish; ``bestErrorSA`` is the search's own error.
+        ``descendSteps`` > 0 (hq_descend_population): the last polish, after the repair and k-means
+        ones -- that many gradient steps on the cost itself at the starting step ``descendRate``
+        (None: DESCEND_RATE); the returned cost is never above the one it starts from.  The plain
+        dE76 cost only: with a searched rendering (``ditherSearch``, ``orderedSearch``,
+        ``dotSearch``), ``mask`` or ``weights`` it raises ValueError before anything runs.
         ``dither`` > 0 (hq_dither_population, a strength up to 1): once the search and its
         polishes are done, the best palette is also evaluated in its Floyd-Steinberg
         rendering; ``bestErrorDithered`` is that cost, ``bestError`` stays the plain one.
@@ -863,7 +889,8 @@ class ImageManipulation:
                 inlinergbOriginal, inlineScielabOriginal, w, nbOfColors, simulatedAnnealing, filters, absfilters,
                 illuminant, iterations, stop, lloydSteps, lloydEvery, init, initBits, repairEvery, repairMoves,
                 repairSteps, dither, ditherSearch, ordered, orderedSearch, mask, weights, fx, ditherKernel,
-                dot, dotSearch, dotClasses)
+                dot, dotSearch, dotClasses, descendSteps=descendSteps,
+                descendRate=DESCEND_RATE if descendRate is None else descendRate)
         finally:
             if space is not None:
                 self.setOption("assign_space", space_before)
@@ -874,7 +901,7 @@ class ImageManipulation:
                               filters, absfilters, illuminant, iterations, stop, lloydSteps, lloydEvery, init,
                               initBits, repairEvery, repairMoves, repairSteps, dither, ditherSearch, ordered,
                               orderedSearch, mask, weights, fx, ditherKernel=None, dot=0.0, dotSearch=False,
-                              dotClasses=None):
+                              dotClasses=None, descendSteps=0, descendRate=None):
         """findBestQuantization's body; fx: the call's fixed colours (n, 4), already set on the
         context, or None (then whatever the context holds applies, as to any search)."""
         ctx = self._require()
@@ -884,6 +911,10 @@ class ImageManipulation:
         for given, noun, adj in ((mask, "mask", "masked"), (weights, "weights", "weighted")):
             if given is not None and (int(repairEvery) != 0 or int(repairSteps) != 0):
                 raise ValueError(f"{noun} with repairEvery or repairSteps: no {adj} error statistic")
+        if int(descendSteps) != 0 and (mask is not None or weights is not None or ditherSearch or orderedSearch
+                                       or dotSearch):
+            raise ValueError("descendSteps with a mask, weights or a searched rendering: the gradient is the "
+                             "plain cost's")
         amp = None if ordered is None else self._amp3(ordered)
         if orderedSearch and (amp is None or not np.any(amp != 0)):
             raise ValueError("orderedSearch needs a non-zero ordered amplitude")
@@ -1006,7 +1037,7 @@ class ImageManipulation:
             self._lib.hq_search_destroy(handle)
         if dot_device:  # one evaluation of the returned palette: bestError and bestErrorDot are that cost
             self.bestError = float(searched.population(best.reshape(1, -1), sw.delta)[0])
-        if int(repairSteps) > 0 or int(lloydSteps) > 0:
+        if int(repairSteps) > 0 or int(lloydSteps) > 0 or int(descendSteps) > 0:
             self.bestErrorSA = self.bestError
         if int(repairSteps) > 0:
             pal, costs, _ = self.repairPopulation(best.reshape(1, -1), int(repairSteps), sw.delta,
@@ -1020,6 +1051,12 @@ class ImageManipulation:
             best, self.bestError = pal[0], float(costs[0])
             if self.verbose:
                 print("Final error after %d k-means steps : %.5f" % (int(lloydSteps), self.bestError))
+        if int(descendSteps) > 0:
+            pal, costs, _ = self.descendPopulation(best.reshape(1, -1), int(descendSteps), float(descendRate),
+                                                   sw.delta)
+            best, self.bestError = pal[0], float(costs[0])
+            if self.verbose:
+                print("Final error after %d descent steps : %.5f" % (int(descendSteps), self.bestError))
         for r in rendered:  # (the searched one, here the ordered: bestError is already its cost)
             err = self.bestError if r is searched else float(r.population(best.reshape(1, -1), sw.delta)[0])
             setattr(self, r.error_attr, err)

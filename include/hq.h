@@ -317,6 +317,81 @@ int hq_repair_population(hq_ctx *ctx, float *palettes, int P, int K, int steps, 
                          int max_moves, int keep_best, double *costs, int32_t *used,
                          double *trace);
 
+/* ---- the cost's palette gradient and a descent polish: libhq's additions ----
+ * The moves above lower something else than the cost: k-means the RGB distortion,
+ * the repair move the penalty.  With the index images held fixed the cost is a
+ * smooth function of the K colours, and its own derivative is as cheap as the cost.
+ *
+ * Definition.  For palette p of the population whose index images
+ * the context holds (the read-back rule of hq_get_indices), N = w h, idx fixed:
+ *   forward   O(x) = opp(pal[idx(x)]) (CL:194-198); B = F O, the candidate blur
+ *             (CL:234-306): F_0 = V(k1)H(k1) + V(k2)H(k2) + V(|k3|)H(k3) on channel
+ *             0, F_c = V(k1)H(k1) + V(k2)H(k2) on channels 1 and 2, reflection
+ *             CL:256-263; Lab(x) = Opp2LAB(B(x)) under the context's illuminant;
+ *             E(x) = dE76(Lab(x), LabRef(x)); C = (1/N) sum E(x).
+ *   pointwise g(x) = dE/dB(x) = J^T(B(x)) (Lab(x) - LabRef(x)) / E(x), J the
+ *             Jacobian of Opp2LAB: the 3x3 Opp->XYZ, the division by the
+ *             illuminant, f' of the branch CL:124-145 takes (1 / (3 t^(2/3)) above
+ *             delta^3, kappa / 116 below), the (116, 500, 200) combination.
+ *             g(x) = 0 exactly where E(x) == 0.
+ *   adjoint   in gather form.  g~ = g inside the image, 0 outside.  The transpose
+ *             of a reflecting 1-D pass with taps k[t], t = -h .. h, over n pixels:
+ *             (H^T g)(y) = sum_t k[t] (g~(y-t) + g~(-y-1-t) + g~(2n-y-1-t)).
+ *             a_c = sum_j H_j^T V_j^T g_c: the vertical pass's transpose first,
+ *             |k3| on the vertical pass and k3 on the horizontal one -- the exact
+ *             transpose of the forward order.
+ *   sums      S[k][c] = sum over {x: idx(x) = k} of a_c(x), n[k] their count;
+ *             dC/dpal[k][ch] = (1/N) sum_c S[k][c] RGB2Opp[c][ch] srgb_lin'(pal[k][ch]),
+ *             srgb_lin' the derivative of the branch srgb_lin takes (1 / 12.92 up
+ *             to 0.04045, 2.4 / 1.055 ((x + 0.055) / 1.055)^1.4 above).  The delta
+ *             penalty has zero gradient; a colour with n[k] = 0 has gradient 0 exactly.
+ *
+ * hq_cost_gradient: grad[(p*K+k)*4 + {0,1,2}] = dC/d(R, G, B) of colour k of
+ * palette p, grad[(p*K+k)*4 + 3] = n[k].  The kernels work in fp32; the sums S are
+ * 64-bit integers: a pixel adds llrint(a_c 2^s), so the result does not depend on
+ * the order of the atomics -- two calls give the same bits, a palette alone and
+ * inside a population too.  s = min(30, 32 - e) with 2^e the power of two above
+ * the bound A >= |a_c|:
+ *   A = max_c (kappa / 116) (500 |m_0c| + 816 |m_1c| + 200 |m_2c|)
+ *             9 ((sum |k1_c|)^2 + (sum |k2_c|)^2 + [c = 0] (sum |k3|)^2),
+ * m = Opp->XYZ with row r over the illuminant's component r -- (Lab - LabRef) / E is
+ * a unit vector, f' <= kappa / 116 on both branches, and a transposed reflecting
+ * pass has at most three sources per tap -- so N <= 2^30 pixels sum below 2^62.
+ * (The designed filters under D65: A < 2^18, s = 14.)  The chain rule runs on the
+ * host in double.
+ * State: hq_cluster_sums' rule -- HQ_ERR_STATE when P or K differ from the last
+ * evaluation's, when nothing has been evaluated, when a search run has evaluated
+ * since, or when an image or filter change has ended the read-back -- except that
+ * the index images of every kind of evaluation serve: plain, ordered, diffused,
+ * dot-diffused, under either "assign_space".
+ * HQ_ERR_UNSUPPORTED: K > 256; a dE type other than dE76; a row-block shard, a
+ * palette slice ("slice_ranks" > 1, "palette_split") or a communicator of more
+ * than one rank; a pixel mask or pixel weights; more than 2^30 pixels.  A refused
+ * call writes nothing.  The evaluated population is not disturbed.
+ * Option "grad_tiled": -1 (default) the tiled kernels up to half-width 24 and the
+ * plain per-pixel pair above, 0 the plain pair, 1 the tiled kernels (refused above
+ * 24).  Profiling stages "grad_pixel" (the kernels that make g) and "grad_adjoint". */
+int hq_cost_gradient(hq_ctx *ctx, int P, int K, double *grad);
+/* A descent polish on that gradient.  Evaluates the P palettes; then `steps`
+ * times, per palette p with a step eta_p of its own (start: rate):
+ * hq_cost_gradient; for each colour k with n[k] > 0 that is not fixed
+ * (hq_set_fixed_colors), candidate = clamp(pal - eta_p grad N / n[k], 0, 1) --
+ * the mean gradient over the colour's own pixels, so small clusters move as far as
+ * large ones; double arithmetic, stored as float -- every other colour keeps its
+ * bits; an evaluation of the candidates.  A palette whose cost fell keeps the
+ * candidate and eta_p <- 1.5 eta_p; otherwise it keeps its bits and
+ * eta_p <- 0.5 eta_p.  The evaluation assigns anew, so assignment changes are
+ * handled by acceptance, not by the gradient.  A palette's returned cost is never
+ * above its input cost; palettes, costs and used (may be NULL) are those of the
+ * accepted state, trace[s*P + p] (may be NULL) its cost after step s, s = 0 the
+ * input, as in hq_refine_population.  A step whose candidates equal the palettes
+ * bit for bit ends the loop.  steps = 0 is hq_eval_population.  The index images
+ * left on the device are those of the last evaluation made, which may be a
+ * rejected candidate's.  Refusals: hq_refine_population's and, for steps > 0,
+ * hq_cost_gradient's; rate not a finite number above 0: HQ_ERR_ARG. */
+int hq_descend_population(hq_ctx *ctx, float *palettes, int P, int K, int steps, float rate,
+                          float delta, double *costs, int32_t *used, double *trace);
+
 /* ---- dithered rendering: libhq's addition, no reference counterpart ----
  * S-CIELAB blurs the opponent channels as the eye does before it takes dE; the
  * nearest-colour rendering's error is low-frequency and survives that blur, an
