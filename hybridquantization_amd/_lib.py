@@ -124,6 +124,7 @@ SIGNATURES = {
     "hq_cluster_errors": (C.c_int, [_ctx, C.c_int, C.c_int, _i64, _f]),
     "hq_cost_gradient": (C.c_int, [_ctx, C.c_int, C.c_int, _d]),
     "hq_descend_population": (C.c_int, [_ctx, _f, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _d, _i32, _d]),
+    "hq_descend_move": (C.c_int, [_ctx, _f, C.c_int, C.c_int, C.c_float, _f]),
     "hq_reseed_unused": (C.c_int, [_i64, _f, C.c_int, C.c_int, C.c_int, _f, C.POINTER(C.c_int)]),
     "hq_reseed_unused_fixed": (C.c_int, [_i64, _f, C.c_int, C.c_int, C.c_int, C.c_int, _f, C.POINTER(C.c_int)]),
     "hq_set_fixed_colors": (C.c_int, [_ctx, _f, C.c_int]),
@@ -175,6 +176,8 @@ SIGNATURES = {
     "hq_search_population": (C.c_int, [C.c_void_p, _f, _d]),
     "hq_search_destroy": (None, [C.c_void_p]),
     "hq_search_set_lloyd": (C.c_int, [C.c_void_p, C.c_int]),
+    "hq_search_set_descend": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
+    "hq_search_descend_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     "hq_search_set_repair": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "hq_search_set_ordered": (C.c_int, [C.c_void_p, _f]),
     "hq_search_set_dot": (C.c_int, [C.c_void_p, C.POINTER(hq_dot_classes), C.c_float]),

@@ -1357,15 +1357,10 @@ int ensure_dot_pass(hq_ctx* c, const hq_dot_classes& m, int P, int K) {
     return ensure_render_scratch(c, Pass{Dot{0.f, 0, 0}}, P, K);
 }
 
-}  // namespace hq
-
-namespace {
-
-// ---- the cost's palette gradient (hq_grad.hip; hq.h) -----------------------
-// What hq_cost_gradient refuses: first what the context is (HQ_ERR_UNSUPPORTED), then what it
-// holds (hq_cluster_sums' state rule, but a rendering's index images serve as an evaluation's do).
-int gradient_config(hq_ctx* c, int K) {
-    const char* const what = "hq_cost_gradient";
+// ---- the cost's palette gradient (hq_grad.hip; hq.h) -----------------
+// What hq_cost_gradient refuses of the context (HQ_ERR_UNSUPPORTED), `what` named: the descent
+// move of a search refuses the same under its own name.
+int gradient_config(hq_ctx* c, int K, const char* what) {
     if (K > kMaxK) return fail(c, HQ_ERR_UNSUPPORTED, "%s at K=%d > %d: the bins are the u8 index images'", what, K, kMaxK);
     if (c->de_type != HQ_DE_CIE76)
         return fail(c, HQ_ERR_UNSUPPORTED, "%s under dE type %d: the gradient is dE76's", what, c->de_type);
@@ -1379,39 +1374,28 @@ int gradient_config(hq_ctx* c, int K) {
         return fail(c, HQ_ERR_UNSUPPORTED, "%s on more than 2^30 pixels: the fixed-point sums are sized for that", what);
     return HQ_OK;
 }
-int gradient_scope(hq_ctx* c, int P, int K) {
-    if (int rc = gradient_config(c, K)) return rc;
-    const Resident& r = c->res;
-    if (!c->have_image || !(r.owner == Resident::Eval || r.owner == Resident::Render))
-        return fail(c, HQ_ERR_STATE, "no population evaluated or rendered on this image and these filters since the "
-                                     "last search run");
-    if (P != r.P || K != r.K)
-        return fail(c, HQ_ERR_STATE, "P=%d, K=%d: the last evaluation had P=%d, K=%d", P, K, r.P, r.K);
-    if (r.n != r.P || r.nch != 1)
-        return fail(c, HQ_ERR_UNSUPPORTED, "palette slice: this device holds %d of the %d index images", r.n, r.P);
+
+int ensure_gradient(hq_ctx* c, int P, int K, const char* what, bool* tiled, int* shift) {
+    *tiled = c->half <= kGradMaxHalfTiled && c->grad_tiled != 0;
+    if (c->grad_tiled == 1 && !*tiled)
+        return fail(c, HQ_ERR_UNSUPPORTED, "option grad_tiled 1 at half-width %d > %d", c->half, kGradMaxHalfTiled);
+    float m[9];
+    lab_matrix(c, m);
+    *shift = grad_shift(grad_bound(m, c->k1.data(), c->k2.data(), c->k3.data(), c->absk3.data(), c->taps));
+    if (*shift == kGradNoShift) return fail(c, HQ_ERR_UNSUPPORTED, "%s: taps too large for the fixed-point sums", what);
+    if (P < 1) return HQ_OK;  // (a set call's check: nothing to size yet)
+    if (*tiled) (void)grad_tiled_grant(c->half);
+    const size_t N = (size_t)c->g.W * c->g.H;
+    HIP_TRY(c, c->d_grad_g.ensure(sizeof(float4) * (size_t)P * N));
+    HIP_TRY(c, c->d_grad_sums.ensure(sizeof(int64_t) * (size_t)P * K * 4));
+    if (!*tiled) HIP_TRY(c, c->d_grad_t.ensure(sizeof(float) * 7 * N));
     return HQ_OK;
 }
 
-// hq_cost_gradient into grad ([P][K][4]); nothing is written unless HQ_OK.  The index images, the
-// prepared palettes, the counter sets and every other table stay what they are.
-int cost_gradient(hq_ctx* c, int P, int K, double* grad) {
-    if (int rc = gradient_scope(c, P, K)) return rc;
-    if (int rc = bind(c)) return rc;
+int enqueue_gradient(hq_ctx* c, int P, int K, bool tiled, int shift, ProfRec& pr) {
     const Geom& g = c->g;
-    const int64_t N = (int64_t)g.W * g.H;
-    const bool tiled = c->half <= kGradMaxHalfTiled && c->grad_tiled != 0;
-    if (c->grad_tiled == 1 && !tiled)
-        return fail(c, HQ_ERR_UNSUPPORTED, "option grad_tiled 1 at half-width %d > %d", c->half, kGradMaxHalfTiled);
     GradArgs a{};
     lab_matrix(c, a.m_lab);
-    const int shift = grad_shift(grad_bound(a.m_lab, c->k1.data(), c->k2.data(), c->k3.data(), c->absk3.data(), c->taps));
-    if (shift == kGradNoShift) return fail(c, HQ_ERR_UNSUPPORTED, "hq_cost_gradient: taps too large for the fixed-point sums");
-    hipStream_t s = c->stream;
-    const size_t n4 = (size_t)P * K * 4;
-    HIP_TRY(c, c->d_grad_g.ensure(sizeof(float4) * (size_t)P * (size_t)N));
-    HIP_TRY(c, c->d_grad_sums.ensure(sizeof(int64_t) * n4));
-    if (!tiled) HIP_TRY(c, c->d_grad_t.ensure(sizeof(float) * 7 * (size_t)N));
-    HIP_TRY(c, hipMemsetAsync(c->d_grad_sums.p, 0, sizeof(int64_t) * n4, s));
     a.idx = c->d_idx.as<uint8_t>();
     a.opp = c->d_opp.as<float4>();
     a.k1 = c->d_k1.as<float>();
@@ -1428,15 +1412,53 @@ int cost_gradient(hq_ctx* c, int P, int K, double* grad) {
     a.W = g.W, a.H = g.H, a.lab_pitch = g.lab_pitch;
     a.P = P, a.K = K, a.half = c->half;
     a.scale = std::ldexp(1.0f, shift);
-    ProfRec pr = prof_begin(c);
     hipEvent_t ev_pix[2] = {nullptr, nullptr}, ev_adj[2] = {nullptr, nullptr};
     if (pr.ev) {
         ev_pix[0] = pr.ev[2 * kPGradPixel], ev_pix[1] = pr.ev[2 * kPGradPixel + 1];
         ev_adj[0] = pr.ev[2 * kPGradAdjoint], ev_adj[1] = pr.ev[2 * kPGradAdjoint + 1];
         pr.recorded |= (1u << kPGradPixel) | (1u << kPGradAdjoint);
     }
+    hipStream_t s = c->stream;
     HIP_TRY(c, tiled ? launch_grad_tiled(a, s, pr.ev ? ev_pix : nullptr, pr.ev ? ev_adj : nullptr)
                      : launch_grad_plain(a, s, pr.ev ? ev_pix : nullptr, pr.ev ? ev_adj : nullptr));
+    return HQ_OK;
+}
+
+}  // namespace hq
+
+namespace {
+
+// What hq_cost_gradient refuses: first what the context is (gradient_config), then what it
+// holds (hq_cluster_sums' state rule, but a rendering's index images serve as an evaluation's do).
+int gradient_scope(hq_ctx* c, int P, int K) {
+    if (int rc = gradient_config(c, K)) return rc;
+    const Resident& r = c->res;
+    if (!c->have_image || !(r.owner == Resident::Eval || r.owner == Resident::Render))
+        return fail(c, HQ_ERR_STATE, "no population evaluated or rendered on this image and these filters since the "
+                                     "last search run");
+    if (P != r.P || K != r.K)
+        return fail(c, HQ_ERR_STATE, "P=%d, K=%d: the last evaluation had P=%d, K=%d", P, K, r.P, r.K);
+    if (r.n != r.P || r.nch != 1)
+        return fail(c, HQ_ERR_UNSUPPORTED, "palette slice: this device holds %d of the %d index images", r.n, r.P);
+    return HQ_OK;
+}
+
+// hq_cost_gradient into grad ([P][K][4]); nothing is written unless HQ_OK.  The index images, the
+// prepared palettes, the counter sets and every other table stay what they are.  The enqueue
+// (ensure_gradient, the bins zeroed, enqueue_gradient), then the read-back and the chain rule on
+// the host in double.
+int cost_gradient(hq_ctx* c, int P, int K, double* grad) {
+    if (int rc = gradient_scope(c, P, K)) return rc;
+    if (int rc = bind(c)) return rc;
+    const int64_t N = (int64_t)c->g.W * c->g.H;
+    bool tiled = false;
+    int shift = 0;
+    if (int rc = ensure_gradient(c, P, K, "hq_cost_gradient", &tiled, &shift)) return rc;
+    hipStream_t s = c->stream;
+    const size_t n4 = (size_t)P * K * 4;
+    HIP_TRY(c, hipMemsetAsync(c->d_grad_sums.p, 0, sizeof(int64_t) * n4, s));
+    ProfRec pr = prof_begin(c);
+    if (int rc = enqueue_gradient(c, P, K, tiled, shift, pr)) return rc;
     std::vector<int64_t> sums(n4);
     std::vector<float> pal((size_t)P * kMaxK * 4);
     HIP_TRY(c, hipMemcpyAsync(sums.data(), c->d_grad_sums.p, sizeof(int64_t) * n4, hipMemcpyDeviceToHost, s));
@@ -1448,6 +1470,34 @@ int cost_gradient(hq_ctx* c, int P, int K, double* grad) {
     for (int p = 0; p < P; ++p)
         grad_chain(&sums[(size_t)p * K * 4], &pal[(size_t)p * kMaxK * 4], K, (double)N, shift, rgb2opp,
                    grad + (size_t)p * K * 4);
+    return HQ_OK;
+}
+
+// hq_descend_move: one descent move on the P palettes, the kernels a device-resident search's
+// descent iteration enqueues (enqueue_descend, hq_search_run.hip) through d_pal_in as the
+// candidate buffer.  Nothing is left to read back (drop).
+int descend_move(hq_ctx* c, float* palettes, int P, int K, float rate, const Ordered* ord) {
+    if (int rc = bind(c)) return rc;
+    drop(c);
+    if (int rc = ensure_population(c, P, K)) return rc;
+    bool tiled = false;
+    int shift = 0;
+    if (int rc = ensure_gradient(c, P, K, "hq_descend_move", &tiled, &shift)) return rc;
+    hipStream_t s = c->stream;
+    const size_t n4 = (size_t)P * K * 4;
+    HIP_TRY(c, hipMemsetAsync(c->d_grad_sums.p, 0, sizeof(int64_t) * n4, s));
+    ProfRec pr = prof_begin(c);
+    int rc = upload_and_prep(c, palettes, nullptr, P, K);
+    if (!rc) rc = enqueue_core(c, P, K, pr, ord ? Pass{Pass::AssignOnly, *ord, kPDescGrid} : Pass{Pass::AssignOnly, kPDescGrid});
+    if (!rc) rc = enqueue_gradient(c, P, K, tiled, shift, pr);
+    if (rc) return rc;
+    const DescendArgs da{c->d_grad_sums.as<unsigned long long>(), c->d_pal_in.as<float>(), prep_args(c, K), (double)rate, K,
+                         shift, c->fixed_n};
+    HIP_TRY(c, timed_launch(pr, kPDescend, [&] { return launch_descend_update(da, P, s); }));
+    HIP_TRY(c, hipMemcpyAsync(c->h_pal.p, c->d_pal_in.p, sizeof(float) * n4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    prof_accumulate(c, pr);
+    std::memcpy(palettes, c->h_pal.p, sizeof(float) * n4);
     return HQ_OK;
 }
 
@@ -1704,6 +1754,26 @@ int hq_cost_gradient(hq_ctx* c, int P, int K, double* grad) {
     std::vector<double> out((size_t)P * K * 4);
     const int rc = cost_gradient(c, P, K, out.data());
     if (!rc) std::copy(out.begin(), out.end(), grad);
+    return rc;
+}
+
+int hq_descend_move(hq_ctx* c, float* palettes, int P, int K, float rate, const float amp[3]) {
+    if (!c) return HQ_ERR_ARG;
+    if (!palettes || P < 1 || K < 1) return fail(c, HQ_ERR_ARG, "bad palettes / P=%d / K=%d", P, K);
+    if (!(rate > 0.0f) || !std::isfinite(rate)) return fail(c, HQ_ERR_ARG, "rate=%g: a finite step above 0", (double)rate);
+    const bool on = amp && (amp[0] != 0.f || amp[1] != 0.f || amp[2] != 0.f);
+    int rc = amp ? check_ordered_amp(c, amp) : (int)HQ_OK;
+    if (rc) return rc;
+    if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
+    if ((rc = gradient_config(c, K, "hq_descend_move"))) return rc;
+    if (!population_in_range(palettes, P, K))
+        return fail(c, HQ_ERR_ARG, "palette with a channel that is not finite or outside [0, 1]");
+    if (on && ((rc = assign_space_excludes(c, "ordered dithering")) || (rc = ordered_scope(c, K)) ||
+               (rc = ensure_dither_map(c))))
+        return rc;
+    const Ordered ord{{on ? amp[0] : 0.f, on ? amp[1] : 0.f, on ? amp[2] : 0.f}};
+    rc = descend_move(c, palettes, P, K, rate, on ? &ord : nullptr);
+    if (rc) drop(c);
     return rc;
 }
 

@@ -45,10 +45,40 @@ inline int grad_shift(double bound) {
     return s > 30 ? 30 : s;
 }
 
+#if defined(__HIPCC__)
+#define HQ_GRAD_HD __host__ __device__
+#else
+#define HQ_GRAD_HD
+#endif
+
 // d srgb_lin / dx of the branch srgb_lin takes (CL:85-87)
-inline double srgb_lin_slope(double x) {
+HQ_GRAD_HD inline double srgb_lin_slope(double x) {
     return x <= (double)0.04045f ? 1.0 / (double)12.92f
                                  : (double)2.4f / (double)1.055f * pow((x + (double)0.055f) / (double)1.055f, (double)2.4f - 1.0);
+}
+
+// The move of one channel of one colour, the one statement of it for the host's chain rule and
+// step (grad_chain, descend_step) and the search's kernel (descend_update_kernel, hq_search.hip):
+//   g = (sum_c ldexp(S_c, -shift) rgb2opp[c][ch]) srgb_lin'(x) / den
+//   x' = clamp(x - rate g scale / n, 0, 1) in double, stored as float; x's bits when that is not finite.
+// *grad (may be null) receives g.  The host's pair: den = N gives dC/dx, and the step takes that
+// gradient back (s null: g is given) with scale = N.  The kernel: den = scale = 1, exact, so
+// x' = clamp(x - rate srgb_lin'(x) (sum) / n, 0, 1) -- N cancels.  Nothing is contracted.
+HQ_GRAD_HD inline float descend_channel(const int64_t* s, int shift, const double* rgb2opp, int ch, float x, double den,
+                                        double g, double rate, double scale, double n, double* grad) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    if (s) {
+        double v = 0.0;
+        for (int c = 0; c < 3; ++c) v += ldexp((double)s[c], -shift) * rgb2opp[3 * c + ch];
+        g = v * srgb_lin_slope((double)x) / den;
+    }
+    if (grad) *grad = g;
+    if (!(n > 0.0)) return x;
+    const double v = (double)x - rate * g * scale / n;
+    if (!isfinite(v)) return x;
+    return (float)fmin(fmax(v, 0.0), 1.0);
 }
 
 // The chain rule of one palette: sums [K][4] (S_0, S_1, S_2 in units of 2^-shift, n), pal [K][4]
@@ -61,12 +91,8 @@ inline void grad_chain(const int64_t* sums, const float* pal, int K, double n_pi
         double* g = grad + 4 * k;
         g[3] = (double)s[3];
         for (int ch = 0; ch < 3; ++ch) {
-            double v = 0.0;
-            if (s[3] > 0) {
-                for (int c = 0; c < 3; ++c) v += ldexp((double)s[c], -shift) * rgb2opp[3 * c + ch];
-                v = v * srgb_lin_slope((double)pal[4 * k + ch]) / n_pixels;
-            }
-            g[ch] = v;
+            g[ch] = 0.0;
+            if (s[3] > 0) (void)descend_channel(s, shift, rgb2opp, ch, pal[4 * k + ch], n_pixels, 0.0, 0.0, 0.0, 0.0, &g[ch]);
         }
     }
 }
@@ -113,6 +139,9 @@ struct GradArgs {
 // ev_* (profiling, may be null): the pixel stage's pair and the adjoint stage's.
 hipError_t launch_grad_plain(const GradArgs&, hipStream_t, hipEvent_t ev_pix[2], hipEvent_t ev_adj[2]);
 hipError_t launch_grad_tiled(const GradArgs&, hipStream_t, hipEvent_t ev_pix[2], hipEvent_t ev_adj[2]);
+// The tiled kernels' dynamic LDS granted at this half-width now (a search does it before its run is
+// captured); false: the runtime refused, and the launcher will return its error.
+bool grad_tiled_grant(int half);
 size_t grad_pixel_lds(int half);
 size_t grad_adjoint_lds(int half);
 

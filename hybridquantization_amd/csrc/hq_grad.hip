@@ -415,6 +415,11 @@ hipError_t launch_grad_plain(const GradArgs& a, hipStream_t s, hipEvent_t ev_pix
     return hipGetLastError();
 }
 
+bool grad_tiled_grant(int half) {
+    return allow_dyn_lds(reinterpret_cast<const void*>(grad_pixel_kernel), grad_pixel_lds(half)) &&
+           allow_dyn_lds(reinterpret_cast<const void*>(grad_adjoint_kernel), grad_adjoint_lds(half));
+}
+
 hipError_t launch_grad_tiled(const GradArgs& a, hipStream_t s, hipEvent_t ev_pix[2], hipEvent_t ev_adj[2]) {
     if (!grad_args_ok(a) || a.half > kGradMaxHalfTiled) return hipErrorInvalidValue;
     const int tiles_x = (a.W + kGradTW - 1) / kGradTW;

@@ -297,6 +297,11 @@ int SearchDriver::run(int iterations, int* ran, std::vector<double>* trace) {
             if (rr) { if (ran) *ran = done; return rr; }
             put_fixed_back();
         }
+        if (descend_every_ > 0 && descend_ && ite % descend_every_ == 0) {  // descent iteration: the finest move, last
+            const int rr = descend_(current_.data(), P_, K_);
+            if (rr) { if (ran) *ran = done; return rr; }
+            put_fixed_back();
+        }
         int rc = eval_(current_.data(), P_, K_, errors_.data());      // IM:515
         if (rc) { if (ran) *ran = done; return rc; }
         double minerror = std::numeric_limits<double>::max();
@@ -439,9 +444,8 @@ bool hq::descend_step(const float* pal, const double* grad, int K, int nfixed, d
         const double n = grad[4 * k + 3];
         if (!(n > 0.0)) continue;
         for (int ch = 0; ch < 3; ++ch) {
-            const double v = (double)pal[4 * k + ch] - rate * grad[4 * k + ch] * n_pixels / n;
-            if (!std::isfinite(v)) continue;
-            const float f = (float)std::min(std::max(v, 0.0), 1.0);
+            const float f = descend_channel(nullptr, 0, nullptr, ch, pal[4 * k + ch], 0.0, grad[4 * k + ch], rate,
+                                            n_pixels, n, nullptr);
             changed |= std::memcmp(&f, &pal[4 * k + ch], sizeof(float)) != 0;
             cand[4 * k + ch] = f;
         }

@@ -403,6 +403,21 @@ struct ReseedArgs {
     int nfixed;                // fixed colours (hq_reseed_unused_fixed): colour k < nfixed is no receiver
 };
 
+// descend_update_kernel (hq_search.hip): the descent move of a device-resident
+// descent iteration.  Candidate colour k >= nfixed of palette p with n > 0 takes
+// one step down the cost's own gradient (descend_channel, hq_grad.h), in place;
+// the palette is prepared again (prep's outputs) and the bins it read are zeroed
+// for the next descent iteration.
+struct DescendArgs {
+    unsigned long long* sums;  // [P][K][4] GradArgs::sums of the gradient kernels: S_0, S_1, S_2, n
+    float* cand;               // [P][4K] the search's candidates (the next sa_step's cand_in)
+    PaletteArgs prep;          // outputs of the palette prep of the moved candidates
+    double rate;               // the step: a colour moves by rate times the mean gradient over its pixels
+    int K;
+    int shift;                 // the sums' unit is 2^-shift (grad_shift)
+    int nfixed;                // fixed colours: colour k < nfixed keeps its bits whatever its count
+};
+
 // Generic two-pass path (any half-width), one palette per launch.
 struct GenArgs {
     const void* idx;         // palette's index image (extended rows): u8, or u32 for K > 256

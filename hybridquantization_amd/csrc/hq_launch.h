@@ -109,6 +109,7 @@ hipError_t launch_prep_palette(const PaletteArgs&, int P, hipStream_t);
 hipError_t launch_sa_step(const SaArgs&, hipStream_t);
 hipError_t launch_lloyd_update(const LloydArgs&, int P, hipStream_t);
 hipError_t launch_reseed(const ReseedArgs&, int P, hipStream_t);
+hipError_t launch_descend_update(const DescendArgs&, int P, hipStream_t);
 hipError_t launch_build_grid(const GridArgs&, int P, hipStream_t);
 hipError_t launch_finalize(const FinalizeArgs&, int P, hipStream_t);
 // hq_assign.hip

@@ -114,11 +114,12 @@ struct ProfSlot {
 
 enum Stage {
     kStGrid, kStAssign, kStCost, kStFinalize, kStSaStep, kStComm, kStCentroid, kStLloyd, kStHist, kStErrsum,
-    kStReseed, kStDither, kStReduce, kStDot, kStCoords, kStGradPixel, kStGradAdjoint, kStages
+    kStReseed, kStDither, kStReduce, kStDot, kStCoords, kStGradPixel, kStGradAdjoint, kStDescend, kStages
 };
 inline constexpr const char* kStageNames[kStages] = {"grid", "assign", "cost", "finalize", "sa_step", "comm",
                                                      "centroid", "lloyd", "hist", "errsum", "reseed", "dither",
-                                                     "reduce", "dot", "coords", "grad_pixel", "grad_adjoint"};
+                                                     "reduce", "dot", "coords", "grad_pixel", "grad_adjoint",
+                                                     "descend"};
 
 // The start/stop event pairs of one evaluation (the context's EventSet) or of one
 // search iteration (kPairs pairs per iteration of a run in hq_search::pev).  A pass
@@ -139,13 +140,16 @@ enum Pair {
     kPDot,                                 // dot_kernel's launches (one per class), or dot_tile_kernel's one, in the place of grid + assign
     kPCoords,                              // coords_kernel (option "assign_space" 1), in front of a pass: ensure_assign_coords
     kPGradPixel, kPGradAdjoint,            // hq_cost_gradient: the kernels that make g, those that make a and the sums
+    kPDescGrid, kPDescAssign,              // descent iteration: the assign-only pass, a pair of its own (an iteration
+    kPDescend,                             // may be hybrid too), the update kernel (hq_search_set_descend, hq_descend_move)
     kPairs
 };
 // The stage each pair's time and launch count go to.
 inline constexpr Stage kPairStage[kPairs] = {kStGrid, kStAssign, kStCost, kStFinalize, kStSaStep, kStComm,
                                              kStDither, kStGrid, kStAssign, kStCentroid, kStLloyd, kStGrid,
                                              kStAssign, kStCost, kStErrsum, kStReseed, kStHist, kStReduce,
-                                             kStDot, kStCoords, kStGradPixel, kStGradAdjoint};
+                                             kStDot, kStCoords, kStGradPixel, kStGradAdjoint, kStGrid, kStAssign,
+                                             kStDescend};
 
 // One evaluation's or iteration's events and which pairs it recorded (events of an
 // earlier call may sit in the other slots, so only recorded pairs are accumulated).
@@ -209,8 +213,9 @@ struct Pass {
     enum Kind { Full, Fold, AssignOnly, CostOnly };
     const Kind kind;
     const Rendering rendering;
-    Pass(Kind k = Full) : kind(k) {}
-    Pass(Kind k, const Ordered& o) : kind(k), rendering(o) {}
+    const Pair first = kPairs;  // an assign-only pass's pairs when they are not the hybrid iteration's (else kPairs)
+    Pass(Kind k = Full, Pair own = kPairs) : kind(k), first(own) {}
+    Pass(Kind k, const Ordered& o, Pair own = kPairs) : kind(k), rendering(o), first(own) {}
     Pass(const Diffused& d) : kind(Full), rendering(d) {}
     Pass(const Dot& d) : kind(Full), rendering(d) {}
     Pass(bool fold, const Dot& d) : kind(fold ? Fold : Full), rendering(d) {}
@@ -219,7 +224,9 @@ struct Pass {
     bool rendered() const { return !as<Plain>(); }                 // the getters answer for a rendering
     bool gridless() const { return as<Diffused>() || as<Dot>(); }  // no grid is built: HQ_PASS_DITHER
     bool side() const { return kind == AssignOnly || kind == CostOnly; }
-    Pair pairs() const { return kind == AssignOnly ? kPLloydGrid : kind == CostOnly ? kPRepGrid : kPGrid; }
+    Pair pairs() const {
+        return first != kPairs ? first : kind == AssignOnly ? kPLloydGrid : kind == CostOnly ? kPRepGrid : kPGrid;
+    }
 };
 
 // ---- what the last pass left on the device ---------------------------------------
@@ -435,6 +442,8 @@ struct hq_search {
     int every = 0;                       // hq_search_set_lloyd: iteration ite % every == 0 is hybrid (0: none)
     int repair_every = 0;                // hq_search_set_repair: iteration ite % repair_every == 0 repairs (0: none)
     int repair_moves = -1;               // ... at most so many colours per palette (< 0: no limit)
+    int descend_every = 0;               // hq_search_set_descend: iteration ite % descend_every == 0 descends (0: none)
+    float descend_rate = 0.f;            // ... by this step
     int nch = 1;                         // chunked palettes (256 < K <= 16384): chunks per palette
     bool ordered = false;                // hq_search_set_ordered: every evaluation is the ordered one
     hq::Ordered ord{};                   // ... at this amplitude per channel
@@ -562,6 +571,16 @@ ClusterErrArgs cluster_err_args(hq_ctx* c, int P, int K, int nch, int* idx_bytes
 int kmeans_move(hq_ctx* c, int P, int K, int nfixed, float* pal);
 // (the rule: hq_reseed_unused_fixed)
 int repair_move(hq_ctx* c, int P, int K, int max_moves, int nfixed, bool ignore_bad, float* pal, int* moved);
+// The cost's palette gradient as an enqueue (hq_grad.hip), for hq_cost_gradient and the descent move.
+// gradient_config: what the context must be for it, `what` named in the refusal (HQ_ERR_UNSUPPORTED).
+// ensure_gradient: the form option "grad_tiled" and the half-width give and the fixed-point shift
+// (both refusable), then g, the bins and the plain pair's scratch sized for P palettes of K colours
+// -- before anything is enqueued or captured.  enqueue_gradient: the bins (zero on entry) filled
+// from the index images and opponent tables the device holds; pr: the pairs kPGradPixel, kPGradAdjoint.
+// descend_move: hq_descend_move's body (the host-driven search's descent move).
+int gradient_config(hq_ctx* c, int K, const char* what = "hq_cost_gradient");
+int ensure_gradient(hq_ctx* c, int P, int K, const char* what, bool* tiled, int* shift);
+int enqueue_gradient(hq_ctx* c, int P, int K, bool tiled, int shift, ProfRec& pr);
 // planar_ok established (once per image), else HQ_ERR_UNSUPPORTED "<subject> with a pixel outside
 // [0, 1] or not finite: <what>"
 int require_unit_range_image(hq_ctx* c, const char* subject, const char* what);

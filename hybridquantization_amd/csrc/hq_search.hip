@@ -1,10 +1,12 @@
 // hq_search.hip -- per-iteration kernels of the SWASA search around the
 // assign and cost kernels: palette prep (opponent table, duplicates, non-finite
 // guard), the device-resident SA step (IM:497-568 with SW:54-101), the k-means
-// update of a hybrid iteration (libhq's addition), the exact
+// update of a hybrid iteration, the reseed of a repair iteration and the gradient
+// step of a descent iteration (libhq's additions), the exact
 // two-level candidate grid of the pruned argmin, and the fixed-order fp64
 // finalize (IM:736-768, SW:74-82).
 #include "hq_device.h"
+#include "hq_grad.h"
 #include "hq_launch.h"
 #include "hq_lloyd.h"
 
@@ -1028,6 +1030,47 @@ __global__ __launch_bounds__(1024) void reseed_kernel(ReseedArgs a) {
 }
 
 // ----------------------------------------------------------------------------
+// descend_update: grid (P), block 1024 (after the kernels that were here before it, as
+// reseed is).  The descent move of a descent iteration (libhq's addition), between the
+// assign-only pass + the gradient kernels (hq_grad.hip) and the evaluation.  Thread
+// k < K holds candidate colour k of palette p and its 32 B of bins (S_0, S_1 | S_2, n:
+// two 16-B loads), zeroed once read for the next descent iteration.  With n > 0 and
+// k >= nfixed each channel takes descend_channel's step (hq_grad.h) in fp64 -- the chain
+// rule through RGB2Opp and srgb_lin' and the step by rate over the colour's own pixels,
+// the host rule's statement with N cancelled -- and the colour goes back into the
+// candidate buffer in place (what the next sa_step reads as cand_in); every other
+// colour keeps its bits.  The three channels are one thread's: K threads of fp64, a
+// few hundred instructions each, next to a prep that takes 1024.  The palette is
+// prepared again so pal, opp, opp16, dup and pflags are the moved one's.
+// ----------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void descend_update_kernel(DescendArgs a) {
+    const int p = blockIdx.x, k = threadIdx.x;
+    __shared__ float4 s[kMaxK];
+    __shared__ PrepLds L;
+    float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (k < a.K) {
+        float4* const cp = reinterpret_cast<float4*>(a.cand) + (int64_t)p * a.K + k;
+        ulonglong2* const sp = reinterpret_cast<ulonglong2*>(a.sums + ((int64_t)p * a.K + k) * 4);
+        const ulonglong2 s01 = sp[0], s2n = sp[1];
+        c = *cp;
+        sp[0] = sp[1] = make_ulonglong2(0ull, 0ull);
+        if (s2n.y > 0ull && k >= a.nfixed) {
+            const int64_t sum[3] = {(int64_t)s01.x, (int64_t)s01.y, (int64_t)s2n.x};
+            double m[9];
+#pragma unroll
+            for (int i = 0; i < 9; ++i) m[i] = (double)c_RGB2Opp[i];
+            const double n = (double)s2n.y;
+            c.x = descend_channel(sum, a.shift, m, 0, c.x, 1.0, 0.0, a.rate, 1.0, n, nullptr);
+            c.y = descend_channel(sum, a.shift, m, 1, c.y, 1.0, 0.0, a.rate, 1.0, n, nullptr);
+            c.z = descend_channel(sum, a.shift, m, 2, c.z, 1.0, 0.0, a.rate, 1.0, n, nullptr);
+            *cp = c;
+        }
+    }
+    bool nf;
+    (void)prep_palette_body(a.prep, p, c, s, L, true, nf);
+}
+
+// ----------------------------------------------------------------------------
 // Launchers
 // ----------------------------------------------------------------------------
 hipError_t launch_prep_palette(const PaletteArgs& a, int P, hipStream_t s) {
@@ -1047,6 +1090,12 @@ hipError_t launch_lloyd_update(const LloydArgs& a, int P, hipStream_t s) {
 
 hipError_t launch_reseed(const ReseedArgs& a, int P, hipStream_t s) {
     HQ_LAUNCH(reseed_kernel, dim3(P), dim3(1024), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_descend_update(const DescendArgs& a, int P, hipStream_t s) {
+    if (P < 1 || a.K < 1 || a.K > kMaxK || !a.sums || !a.cand) return hipErrorInvalidValue;
+    HQ_LAUNCH(descend_update_kernel, dim3(P), dim3(1024), 0, s, a);
     return hipGetLastError();
 }
 

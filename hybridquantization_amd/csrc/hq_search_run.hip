@@ -150,6 +150,39 @@ int enqueue_repair(hq_search* s, ProfRec& pr) {
     return HQ_OK;
 }
 
+// ---- descent iterations (hq_search_set_descend) ---------------------------------
+// hq_cost_gradient's scope under the move's own name, the form and the shift the filters give,
+// and no dot-diffused cost: it has no assign-only pass.
+int descend_scope(hq_search* s) {
+    hq_ctx* c = s->ctx;
+    const char* const what = "descent iterations";
+    if (s->dot)
+        return fail(c, HQ_ERR_UNSUPPORTED, "%s in a search under the dot-diffused cost (hq_search_set_dot): it has no "
+                                           "assign-only pass", what);
+    if (int rc = gradient_config(c, s->K, what)) return rc;
+    bool tiled;
+    int shift;
+    return ensure_gradient(c, 0, s->K, what, &tiled, &shift);
+}
+
+// The descent move of a device-resident descent iteration, after the sa_step that generated
+// and prepared the candidates (now cand[cd]) and after the k-means and repair moves when the
+// iteration is those too -- the finest move last.  One linear chain: the assign-only pass under
+// the search's own rendering (plain under the context's "assign_space", or ordered at the
+// search's amplitude), recorded in pairs of its own; the gradient kernels on those index images
+// into d_grad_sums (zero on entry: the run's memset, then the update kernel's own zeroing); the
+// update kernel, which prepares the moved candidates for the evaluation that follows.
+int enqueue_descend(hq_search* s, bool tiled, int shift, ProfRec& pr) {
+    hq_ctx* c = s->ctx;
+    int rc = enqueue_core(c, s->P, s->K, pr, s->ordered ? Pass{Pass::AssignOnly, s->ord, kPDescGrid}
+                                                        : Pass{Pass::AssignOnly, kPDescGrid});
+    if (rc || (rc = enqueue_gradient(c, s->P, s->K, tiled, shift, pr))) return rc;
+    const DescendArgs da{c->d_grad_sums.as<unsigned long long>(), s->cand[s->cd].as<float>(), prep_args(c, s->K),
+                         (double)s->descend_rate, s->K, shift, s->nfixed};
+    HIP_TRY(c, timed_launch(pr, kPDescend, [&] { return launch_descend_update(da, s->P, c->stream); }));
+    return HQ_OK;
+}
+
 // The end of hq_search_create*, hq_search_run and hq_search_set_ordered (status rc, so many
 // evaluations enqueued).  What the getters may read then (hq.h) is the index images of the
 // last candidates evaluated and nothing else: a device-resident search enqueued its passes
@@ -323,6 +356,15 @@ int device_search_run(hq_search* s, int iterations, int* ran) {
         HIP_TRY(c, c->d_errstat.ensure(sums_bytes));
         HIP_TRY(c, c->d_worst.ensure(sizeof(float) * (size_t)s->P * s->K * 4));
     }
+    // descent iterations in this run: g, the bins and the plain pair's scratch, the bins zeroed
+    // here on the stream, in front of the capture -- the update kernel leaves them zero
+    const bool descend = period_in_run(s, s->descend_every, s->ite, iterations);
+    bool grad_tiled = false;
+    int grad_sh = 0;
+    if (descend) {
+        if ((rc = ensure_gradient(c, s->P, s->K, "descent iterations", &grad_tiled, &grad_sh))) return rc;
+        HIP_TRY(c, hipMemsetAsync(c->d_grad_sums.p, 0, sizeof(int64_t) * (size_t)s->P * s->K * 4, c->stream));
+    }
     // option sa_graph: the run's kernels go into one hipGraph (stream capture),
     // replayed as a whole -- a chain of dependent kernels costs ~2.7 us per
     // kernel from the stream and ~1.8 from a graph (profiles/r04_graph_gap_
@@ -356,6 +398,8 @@ int device_search_run(hq_search* s, int iterations, int* ran) {
         if ((rc = enqueue_sa_step(s, done > 0, false, true, false, amax, pr))) return abort_capture(rc);
         if (s->every > 0 && ite % s->every == 0 && (rc = enqueue_lloyd(s, pr))) return abort_capture(rc);
         if (s->repair_every > 0 && ite % s->repair_every == 0 && (rc = enqueue_repair(s, pr)))
+            return abort_capture(rc);
+        if (s->descend_every > 0 && ite % s->descend_every == 0 && (rc = enqueue_descend(s, grad_tiled, grad_sh, pr)))
             return abort_capture(rc);
         if ((rc = enqueue_core(c, s->P, s->K, pr, search_pass(s)))) return abort_capture(rc);
         s->t_acc = s->pol->temperature();     // SW:54-57 at this iteration
@@ -405,6 +449,7 @@ int run_scope(hq_search* s, int iterations) {
                                           "recreate the search", s->assign_space, s->ctx->assign_space);
     if (period_in_run(s, s->every, ite, iterations) && ((rc = lloyd_scope(s)) || (rc = lloyd_validate(s)))) return rc;
     if (period_in_run(s, s->repair_every, ite, iterations) && (rc = repair_scope(s))) return rc;
+    if (period_in_run(s, s->descend_every, ite, iterations) && (rc = descend_scope(s))) return rc;
     if ((rc = mask_scope(s->ctx))) return rc;
     if (s->dot) return dot_search_scope(s->ctx, s->K);
     return s->ordered ? ordered_scope(s->ctx, s->K) : HQ_OK;
@@ -474,6 +519,10 @@ int hq_search_create_from(hq_ctx* c, const hq_swasa_params* params, int K, uint6
             const int rr = hq_eval_population(c, pal, P, KK, delta, costs.data(), nullptr);
             return rr ? rr : repair_move(c, P, KK, s->repair_moves, s->nfixed, true, pal, nullptr);
         });
+        // the descent move, host-driven: the public call, the device-resident form's own kernels
+        s->driver->set_descend([c, s](float* pal, int P, int KK) {
+            return hq_descend_move(c, pal, P, KK, s->descend_rate, s->ordered ? s->ord.amp : nullptr);
+        });
         s->prm = *params;
         s->P = params->population;
         s->driver->set_fixed(s->nfixed, s->nfixed > 0 ? s->fixed.data() : nullptr);
@@ -532,6 +581,27 @@ int hq_search_set_repair(hq_search* s, int every, int max_moves) {
     return HQ_OK;
 }
 
+int hq_search_set_descend(hq_search* s, int every, float rate) {
+    if (!s || !s->ctx) return HQ_ERR_ARG;
+    if (every < 0) return fail(s->ctx, HQ_ERR_ARG, "every=%d < 0", every);
+    if (every > 0) {
+        if (!(rate > 0.0f) || !std::isfinite(rate))
+            return fail(s->ctx, HQ_ERR_ARG, "rate=%g: a finite step above 0", (double)rate);
+        if (int rc = descend_scope(s)) return rc;
+    }
+    s->descend_every = every;
+    s->descend_rate = every > 0 ? rate : 0.f;
+    if (s->driver) s->driver->set_descend_every(every);
+    return HQ_OK;
+}
+
+int hq_search_descend_info(const hq_search* s, int* every, float* rate) {
+    if (!s) return HQ_ERR_ARG;
+    if (every) *every = s->descend_every;
+    if (rate) *rate = s->descend_rate;
+    return HQ_OK;
+}
+
 int hq_search_set_ordered(hq_search* s, const float amp[3]) {
     if (!s || !s->ctx) return HQ_ERR_ARG;
     hq_ctx* c = s->ctx;
@@ -574,6 +644,9 @@ int hq_search_set_dot(hq_search* s, const hq_dot_classes* cls, float strength) {
     if (on) {
         if (s->every > 0 || s->repair_every > 0)
             return fail(c, HQ_ERR_UNSUPPORTED, "a search with hybrid or repair iterations: no dot-diffused cost");
+        if (s->descend_every > 0)
+            return fail(c, HQ_ERR_UNSUPPORTED, "a search with descent iterations: the dot-diffused cost has no "
+                                               "assign-only pass");
         if (s->ordered) return fail(c, HQ_ERR_UNSUPPORTED, "a search under the ordered cost: one rendering per search");
         if (int rc = assign_space_excludes(c, "hq_search_set_dot")) return rc;
         if (int rc = dot_search_scope(c, s->K)) return rc;

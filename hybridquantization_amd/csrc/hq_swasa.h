@@ -89,6 +89,10 @@ class SearchDriver {
     // `repair` runs after `refine` when an iteration is both.
     void set_repair(PopulationRefine repair) { repair_ = std::move(repair); }
     void set_repair_every(int every) { repair_every_ = every; }
+    // Descent iterations (libhq's addition), the same way with a period of their own:
+    // `descend` runs last, after `refine` and `repair` when an iteration is those too.
+    void set_descend(PopulationRefine descend) { descend_ = std::move(descend); }
+    void set_descend_every(int every) { descend_every_ = every; }
     // Fixed colours (libhq's addition, hq_set_fixed_colors' semantics), set before start():
     // the first n colours of every member are `colors` ([n][4], .w stored as 0; null: as the
     // population or the draws have them) and no iteration changes them -- their draws are
@@ -117,6 +121,8 @@ class SearchDriver {
     int every_ = 0;
     PopulationRefine repair_;
     int repair_every_ = 0;
+    PopulationRefine descend_;
+    int descend_every_ = 0;
     int nfixed_ = 0;
     std::vector<float> fixed_;              // [nfixed][4], or empty
     std::vector<float> colors_, current_;   // [P][4K]

@@ -314,6 +314,17 @@ class ImageManipulation:
         return self._improve(self._lib.hq_descend_population, colors, steps, (float(rate), float(delta)),
                              return_trace)
 
+    def descendMove(self, palettes, rate: float = DESCEND_RATE, ordered=None):
+        """hq_descend_move: one descent move of each palette of palettes (P, 4K) on the device, the move of
+        a search's descent iteration -- the argmin (``ordered``, an amplitude, a float or three: the ordered
+        rendering at it; None: plain), the gradient kernels, the update kernel.  Returns the moved palettes
+        (P, 4K); nothing is evaluated and the read-back of an earlier evaluation ends."""
+        ctx = self._require()
+        pal, P, K = self._population(palettes)
+        amp = None if ordered is None else self._amp3(ordered)
+        check(self._lib.hq_descend_move(ctx, fptr(pal), P, K, float(rate), None if amp is None else fptr(amp)), ctx)
+        return pal
+
     # repairing unused colours: libhq's additions (hq_cluster_errors & co., no reference counterpart)
     def clusterErrors(self, P: int, K: int):
         """Per palette and colour of the last population evaluated with option
@@ -681,6 +692,13 @@ class ImageManipulation:
         check(self._lib.hq_search_info(search, *[C.byref(x) for x in v]), self._require())
         return {"device_resident": bool(v[0].value), "nch": v[1].value, "graph": bool(v[2].value)}
 
+    def searchDescendInfo(self, search) -> tuple[int, float]:
+        """hq_search_descend_info of a search handle made on this context: (the period of its descent
+        iterations, 0 for none; their rate)."""
+        every, rate = C.c_int(), C.c_float()
+        check(self._lib.hq_search_descend_info(search, C.byref(every), C.byref(rate)), self._require())
+        return every.value, rate.value
+
     def searchPopulation(self, search, P: int, K: int):
         """hq_search_population of a search handle made on this context with a population of P
         palettes of K colours -> (colors float32 (P, 4K), errors float64 (P,)): the members the
@@ -785,7 +803,7 @@ class ImageManipulation:
                              init=None, initBits=5, repairEvery=0, repairMoves=-1, repairSteps=0,
                              dither=0.0, ditherSearch=False, ordered=None, orderedSearch=False, mask=None,
                              weights=None, fixed=None, ditherKernel=None, dot=0.0, dotSearch=False,
-                             dotClasses=None, assignSpace=None, descendSteps=0, descendRate=None):
+                             dotClasses=None, assignSpace=None, descendSteps=0, descendRate=None, descendEvery=0):
         """Full SWASA search (IM:383-591) on the GPU; returns bestColors float[4K].
 
         ``simulatedAnnealing`` is a :class:`~hybridquantization_amd.swasa.SWASA`;
@@ -817,6 +835,13 @@ class ImageManipulation:
         (None: DESCEND_RATE); the returned cost is never above the one it starts from.  The plain
         dE76 cost only: with a searched rendering (``ditherSearch``, ``orderedSearch``,
         ``dotSearch``), ``mask`` or ``weights`` it raises ValueError before anything runs.
+        ``descendEvery`` > 0 (hq_search_set_descend): every iteration whose 1-based count is a
+        multiple of it is a descent iteration -- each candidate takes one gradient step of
+        ``descendRate`` on the cost itself before it is evaluated, after the k-means and repair
+        moves when the iteration is those too, on the device when the search is device-resident.
+        It composes with ``orderedSearch`` (the gradient is then the ordered rendering's, the only
+        local move such a search has); with ``ditherSearch``, ``dotSearch``, ``mask`` or ``weights``
+        it raises ValueError before anything runs.
         ``dither`` > 0 (hq_dither_population, a strength up to 1): once the search and its
         polishes are done, the best palette is also evaluated in its Floyd-Steinberg
         rendering; ``bestErrorDithered`` is that cost, ``bestError`` stays the plain one.
@@ -890,7 +915,7 @@ class ImageManipulation:
                 illuminant, iterations, stop, lloydSteps, lloydEvery, init, initBits, repairEvery, repairMoves,
                 repairSteps, dither, ditherSearch, ordered, orderedSearch, mask, weights, fx, ditherKernel,
                 dot, dotSearch, dotClasses, descendSteps=descendSteps,
-                descendRate=DESCEND_RATE if descendRate is None else descendRate)
+                descendRate=DESCEND_RATE if descendRate is None else descendRate, descendEvery=descendEvery)
         finally:
             if space is not None:
                 self.setOption("assign_space", space_before)
@@ -901,7 +926,7 @@ class ImageManipulation:
                               filters, absfilters, illuminant, iterations, stop, lloydSteps, lloydEvery, init,
                               initBits, repairEvery, repairMoves, repairSteps, dither, ditherSearch, ordered,
                               orderedSearch, mask, weights, fx, ditherKernel=None, dot=0.0, dotSearch=False,
-                              dotClasses=None, descendSteps=0, descendRate=None):
+                              dotClasses=None, descendSteps=0, descendRate=None, descendEvery=0):
         """findBestQuantization's body; fx: the call's fixed colours (n, 4), already set on the
         context, or None (then whatever the context holds applies, as to any search)."""
         ctx = self._require()
@@ -915,6 +940,9 @@ class ImageManipulation:
                                        or dotSearch):
             raise ValueError("descendSteps with a mask, weights or a searched rendering: the gradient is the "
                              "plain cost's")
+        if int(descendEvery) != 0 and (mask is not None or weights is not None or ditherSearch or dotSearch):
+            raise ValueError("descendEvery with a mask, weights, ditherSearch or dotSearch: the gradient needs an "
+                             "unmasked cost and an assign-only pass")
         amp = None if ordered is None else self._amp3(ordered)
         if orderedSearch and (amp is None or not np.any(amp != 0)):
             raise ValueError("orderedSearch needs a non-zero ordered amplitude")
@@ -1015,6 +1043,8 @@ class ImageManipulation:
                 check(self._lib.hq_search_set_lloyd(handle, int(lloydEvery)), ctx)
             if int(repairEvery) != 0:
                 check(self._lib.hq_search_set_repair(handle, int(repairEvery), int(repairMoves)), ctx)
+            if int(descendEvery) != 0:
+                check(self._lib.hq_search_set_descend(handle, int(descendEvery), float(descendRate)), ctx)
             done = 0
             while done < total:
                 if stop is not None and stop():

@@ -24,7 +24,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, fptr
-from .image_manipulation import ImageManipulation
+from .image_manipulation import DESCEND_RATE, ImageManipulation
 from .scielab_processor import ScielabProcessor, Whitepoint, design_filters
 from .swasa import fixed_colors, initial_population
 
@@ -56,7 +56,8 @@ def level_dpi(dpi, factor):
     return max(1, round(int(dpi) / int(factor)))
 
 
-def _run_level(m, sw, K, iterations, population, t0, lloydEvery, repairEvery, repairMoves, stop):
+def _run_level(m, sw, K, iterations, population, t0, lloydEvery, repairEvery, repairMoves, stop, descendEvery=0,
+               descendRate=DESCEND_RATE):
     """One level's search on the context ``m`` (image, filters, weights and fixed colours in
     place): ``sw``'s parameters with imax = ``iterations`` (and ``t0``, when given), started
     from ``population`` ((P, 4K), or None: the reference's random start) and run to its end.
@@ -77,6 +78,8 @@ def _run_level(m, sw, K, iterations, population, t0, lloydEvery, repairEvery, re
             check(lib.hq_search_set_lloyd(handle, int(lloydEvery)), ctx)
         if int(repairEvery) != 0:
             check(lib.hq_search_set_repair(handle, int(repairEvery), int(repairMoves)), ctx)
+        if int(descendEvery) != 0:
+            check(lib.hq_search_set_descend(handle, int(descendEvery), float(descendRate)), ctx)
         done = 0
         while done < int(iterations):
             if stop is not None and stop():
@@ -97,7 +100,7 @@ def _run_level(m, sw, K, iterations, population, t0, lloydEvery, repairEvery, re
 
 def pyramidSearch(ip, inlineRGB, w, K, swasa, dpi=72, viewingDistance=45.0, whitepoint=Whitepoint.D65,
                   levels=None, init=None, mask=None, weights=None, fixed=None, lloydEvery=0, initBits=5,
-                  repairEvery=0, repairMoves=-1, fineT0=None, stop=None):
+                  repairEvery=0, repairMoves=-1, fineT0=None, stop=None, descendEvery=0, descendRate=None):
     """A coarse-to-fine SWASA search for K colours on the inline RGBA image ``inlineRGB`` of
     width ``w``; returns bestColors float[4K] at full resolution.
 
@@ -118,7 +121,8 @@ def pyramidSearch(ip, inlineRGB, w, K, swasa, dpi=72, viewingDistance=45.0, whit
     in findBestQuantization) or an array (4K,) / (P, 4K) -- and every level's final population
     seeds the next through hq_search_create_from.  A level of 0 iterations evaluates its seed
     and hands it on.  ``lloydEvery``, ``repairEvery`` / ``repairMoves``: the hybrid and repair
-    iterations of findBestQuantization, on every level.
+    iterations of findBestQuantization, on every level; ``descendEvery`` / ``descendRate`` (None:
+    DESCEND_RATE) its descent iterations likewise.
     With ``levels=((1, n),)`` this is findBestQuantization(iterations=n) of a ``swasa`` with
     imax = n, bit for bit.
 
@@ -129,7 +133,8 @@ def pyramidSearch(ip, inlineRGB, w, K, swasa, dpi=72, viewingDistance=45.0, whit
 
     ValueError before anything runs or any context is created: malformed ``levels``; a level
     whose (reduced) image is narrower or lower than its filters' halfSize, or for whose dpi no filters can be designed; ``mask`` together
-    with ``weights``; either of them with ``repairEvery`` (no masked error statistic); bad
+    with ``weights``; either of them with ``repairEvery`` (no masked error statistic) or ``descendEvery`` (the
+    gradient is the unmasked cost's); bad
     ``fixed`` colours; an ``init`` string other than "mediancut".
     """
     lv = check_levels(((4, swasa.imax // 2), (2, swasa.imax // 4), (1, swasa.imax // 4)) if levels is None else levels)
@@ -140,6 +145,8 @@ def pyramidSearch(ip, inlineRGB, w, K, swasa, dpi=72, viewingDistance=45.0, whit
         raise ValueError("mask and weights: one piece of state, give one of them")
     if (mask is not None or weights is not None) and int(repairEvery) != 0:
         raise ValueError("mask or weights with repairEvery: no masked or weighted error statistic")
+    if (mask is not None or weights is not None) and int(descendEvery) != 0:
+        raise ValueError("mask or weights with descendEvery: the gradient is the unmasked cost's")
     if isinstance(init, str) and init != "mediancut":
         raise ValueError(f"init={init!r}: None, 'mediancut' or an array")
     fx = None if fixed is None else np.ascontiguousarray(fixed_colors(fixed, K))
@@ -190,7 +197,8 @@ def pyramidSearch(ip, inlineRGB, w, K, swasa, dpi=72, viewingDistance=45.0, whit
                             start[4 * nfx:], _ = m.medianCut(cells, int(initBits), den, K - nfx)
                     population = initial_population(start, swasa.population, K)
                 best, err, (seed, seed_err), population, done = _run_level(
-                    m, swasa, K, n, population, fineT0 if i > 0 else None, lloydEvery, repairEvery, repairMoves, stop)
+                    m, swasa, K, n, population, fineT0 if i > 0 else None, lloydEvery, repairEvery, repairMoves, stop,
+                    descendEvery, DESCEND_RATE if descendRate is None else descendRate)
                 errors.append(err)
                 if ip.verbose:
                     print("Level 1/%d (%d x %d): %d iterations, error %.5f -> %.5f" % (f, m.w, m.h, done, seed_err, err))

@@ -90,7 +90,7 @@ def makeChannels(inline):
 def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
                  whitepoint=Whitepoint.D65, verbose=False, device=0, iterations=None, dither=0.0,
                  ordered=None, mask=None, weights=None, fixed=None, pyramid=None, ditherKernel=None,
-                 dot=0.0, dotClasses=None, dotSearch=False, assignSpace=None):
+                 dot=0.0, dotClasses=None, dotSearch=False, assignSpace=None, descendEvery=0):
     """HQ:93-137 without the GUI: planar float image (3, N) in [0,1] ->
     (quantized planar image (3, N), bestColors float[4K], best error).  ``dither`` > 0
     (libhq's addition): the returned image is the best palette's Floyd-Steinberg rendering
@@ -117,7 +117,9 @@ def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
     in the search and in the returned image, which is rendered from the index image of the best
     palette's evaluation (ImageManipulation.quantizeAssigned) and so is the picture the search
     scored (hq_quantize keeps the sRGB rule).  Anything else, or "lab" with ``dither``,
-    ``ordered``, ``dot``, ``dotSearch`` or ``pyramid``, is a ValueError before anything runs."""
+    ``ordered``, ``dot``, ``dotSearch`` or ``pyramid``, is a ValueError before anything runs.
+    ``descendEvery`` (findBestQuantization's, pyramidSearch's: a descent iteration every so many, at
+    ImageManipulation's DESCEND_RATE)."""
     fixed_colors(fixed, int(nbOfColors))
     lab = assignSpace is not None and ImageManipulation.checkAssignSpace(
         assignSpace, dither=dither, ordered=ordered, dot=dot, dotSearch=dotSearch, pyramid=pyramid) != 0
@@ -135,7 +137,8 @@ def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
         inline_rgb = makeinline(image)
         if pyramid is not None:
             best = pyramidSearch(ip, inline_rgb, w, nbOfColors, swasa, dpi, viewingDistance, whitepoint,
-                                 levels=pyramid, mask=mask, weights=weights, fixed=fixed)
+                                 levels=pyramid, mask=mask, weights=weights, fixed=fixed,
+                                 descendEvery=descendEvery)
             q = (ip.quantizeDotDiffused(best, dot, classes=dotClasses) if float(dot) > 0.0 else
                  ip.quantizeOrdered(best, ordered) if ordered is not None else
                  ip.quantizeDithered(best, dither, kernel=ditherKernel) if float(dither) > 0.0 else
@@ -145,7 +148,8 @@ def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
         sc_img = sp.sRGBToScielab(image, w)
         best = sp.bestColors(inline_rgb, sc_img, w, nbOfColors, swasa, iterations=iterations, dither=dither,
                              ditherKernel=ditherKernel, ordered=ordered, mask=mask, weights=weights, fixed=fixed,
-                             dot=dot, dotClasses=dotClasses, dotSearch=dotSearch, assignSpace=assignSpace)
+                             dot=dot, dotClasses=dotClasses, dotSearch=dotSearch, assignSpace=assignSpace,
+                             descendEvery=descendEvery)
         if lab:
             q = ip.quantizeAssigned(best, assignSpace)
             return np.stack(makeChannels(q)), best, ip.bestError

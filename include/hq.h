@@ -391,6 +391,25 @@ int hq_cost_gradient(hq_ctx *ctx, int P, int K, double *grad);
  * hq_cost_gradient's; rate not a finite number above 0: HQ_ERR_ARG. */
 int hq_descend_population(hq_ctx *ctx, float *palettes, int P, int K, int steps, float rate,
                           float delta, double *costs, int32_t *used, double *trace);
+/* One descent move on the device, the move of a search's descent iteration
+ * (hq_search_set_descend): uploads the P palettes, assigns (an assign-only pass:
+ * the plain argmin under "assign_space", or with a non-zero amp the ordered
+ * rendering at amp; amp NULL or zeros is plain), runs hq_cost_gradient's kernels
+ * on those index images and, with S, n and s that call's sums, counts and shift,
+ * for every colour k >= the fixed colours' count with n[k] > 0 and every channel ch
+ *   X'[k][ch] = clamp(X[k][ch] - rate srgb_lin'(X[k][ch])
+ *                     (sum_c ldexp(S[k][c], -s) RGB2Opp[c][ch]) / n[k], 0, 1)
+ * in double on the device, stored as float; every other colour keeps its bits.
+ * This is hq_descend_population's step with eta = rate and N cancelled; the sums
+ * are the same integers, the device's pow is not the host's, so a channel may
+ * differ from the host rule by one float spacing.  The moved palettes are read
+ * back into `palettes`.  Nothing is evaluated: the call ends any read-back
+ * (hq_get_indices and the like answer HQ_ERR_STATE until the next evaluation).
+ * Profiling stage "descend" (the update kernel).  HQ_ERR_ARG: rate not a finite
+ * number above 0, an amp outside [0, 1], a palette channel outside [0, 1] or not
+ * finite.  HQ_ERR_UNSUPPORTED: hq_cost_gradient's refusals and, with a non-zero
+ * amp, hq_ordered_population's. */
+int hq_descend_move(hq_ctx *ctx, float *palettes, int P, int K, float rate, const float amp[3]);
 
 /* ---- dithered rendering: libhq's addition, no reference counterpart ----
  * S-CIELAB blurs the opponent channels as the eye does before it takes dE; the
@@ -1058,6 +1077,35 @@ int hq_search_set_lloyd(hq_search *s, int every);
  * pass -- the error kernels ("errsum" in hq_profile_get), the reseed kernel
  * ("reseed"), then the evaluation.  Both forms give the same search bit for bit. */
 int hq_search_set_repair(hq_search *s, int every, int max_moves);
+/* Descent iterations (libhq's addition): hq_search_set_lloyd's iteration rule and
+ * call times with a period of its own; every = 0 (the default) is the search
+ * without them, bit for bit: nothing is enqueued, allocated or written for them.
+ * In a descent iteration the candidates are drawn as always (no extra draws); the
+ * k-means move runs first when the iteration is hybrid, the repair move next when
+ * it repairs, and then each candidate X takes hq_descend_move(X, rate) -- one step
+ * down the gradient of the cost itself, at the index images of the search's own
+ * evaluation of X: the plain argmin under the context's "assign_space", or the
+ * ordered rendering at the search's amplitude (hq_search_set_ordered), for which
+ * this is the only local move.  The moved candidate is what is evaluated, accepted
+ * or rejected, copied by the convergence step and recorded as best.  The
+ * device-resident search runs it without a host round trip, as one linear chain
+ * ("sa_graph" 1 captures it): an assign-only pass, the gradient kernels
+ * ("grad_pixel", "grad_adjoint" in hq_profile_get; option "grad_tiled" as for
+ * hq_cost_gradient), the update kernel ("descend"), then the evaluation.  The
+ * host-driven search (option "sa_device" 0) calls hq_descend_move, the same
+ * kernels: both forms give the same search bit for bit.
+ * HQ_ERR_ARG: every < 0, or with every > 0 a rate that is not a finite number
+ * above 0.  HQ_ERR_UNSUPPORTED (every > 0, here and again in each hq_search_run
+ * that holds a descent iteration, *ran = 0): hq_cost_gradient's -- K > 256, a dE
+ * type other than dE76, a row-block shard, a communicator of more than one rank,
+ * a palette slice, a pixel mask or weights, more than 2^30 pixels, taps too large
+ * for the fixed-point sums -- and a search under the dot-diffused cost, which has
+ * no assign-only pass (hq_search_set_dot refuses likewise while a period is set).
+ * A refused call leaves the search as it was. */
+int hq_search_set_descend(hq_search *s, int every, float rate);
+/* What hq_search_set_descend last set (either may be NULL): the period, 0 for none,
+ * and the rate (0 without a period); hq_search_info's companion. */
+int hq_search_descend_info(const hq_search *s, int *every, float *rate);
 /* A search whose objective is the ordered rendering (libhq's addition): from this
  * call on every evaluation of the search is hq_ordered_population's at `amp` -- the
  * candidates of the runs that follow and, when no iteration has run yet, the
