@@ -14,6 +14,7 @@
 #include <mutex>
 #include <unordered_map>
 
+#include "hq_kmpp.h"
 #include "hq_runtime.h"
 
 namespace hq {  // launch state shared by every launcher (hq_launch.h)
@@ -671,6 +672,100 @@ int hq_fixed_colors(hq_ctx* c, int* n, float* colors) {
     return HQ_OK;
 }
 
+// k-means++ seeding of P palettes (hq.h states the rule; the kernels: hq_kmpp.hip).  Every refusal
+// comes before anything is allocated or enqueued, and the outputs are written from host copies
+// once the draws are back: a call that does not return HQ_OK writes nothing.  It reads the image,
+// the mask and the fixed colours and writes buffers of its own: the evaluated population stays.
+int hq_kmeanspp_seed(hq_ctx* c, int P, int K, uint64_t seed, float* palettes, int64_t* pixels) {
+    if (!c) return HQ_ERR_ARG;
+    if (!palettes || P < 1 || K < 1 || K > kMaxKChunked)
+        return fail(c, HQ_ERR_ARG, "bad palettes / P=%d / K=%d (1 .. %d)", P, K, kMaxKChunked);
+    if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
+    int rc = whole_image_only(c, "hq_kmeanspp_seed");
+    if (rc) return rc;
+    if ((rc = assign_space_excludes(c, "hq_kmeanspp_seed"))) return rc;
+    const int nfx = c->fixed_n;
+    if (nfx > K) return fail(c, HQ_ERR_ARG, "%d fixed colours (hq_set_fixed_colors) in palettes of K=%d", nfx, K);
+    const int64_t n = (int64_t)c->g.W * c->g.H;
+    if (n > kKmppMaxPixels)
+        return fail(c, HQ_ERR_UNSUPPORTED, "hq_kmeanspp_seed: %lld pixels, more than 2^30", (long long)n);
+    if (c->mask_on && c->mask_w_full == 0)
+        return fail(c, HQ_ERR_ARG, "hq_kmeanspp_seed under %s without a non-zero byte", mask_noun(c));
+    if ((rc = bind(c))) return rc;
+    const bool u8 = sums_u8(c);
+    const size_t pk = (size_t)P * K;
+    std::vector<float> h_out(4 * pk);
+    std::vector<int64_t> h_pix(pk, -1);
+    if (nfx < K) {
+        KmppArgs a{};
+        kmpp_spans((uint32_t)n, P, (uint32_t)c->kmpp_span, c->num_cu, &a.qspan, &a.nspans);
+        const size_t nq = (size_t)((n + 3) / 4);
+        HIP_TRY(c, c->d_kmpp_mind.ensure(sizeof(uint32_t) * 4 * nq * P));
+        HIP_TRY(c, c->d_kmpp_part.ensure(sizeof(uint64_t) * (size_t)a.nspans * (P + 1)));
+        HIP_TRY(c, c->d_kmpp_cent.ensure((sizeof(int4) + sizeof(float4) + sizeof(int64_t)) * pk));
+        a.R = c->d_R.as<float>();
+        a.G = c->d_G.as<float>();
+        a.B = c->d_B.as<float>();
+        a.rgbx = u8 ? c->d_rgbx.as<uint32_t>() : nullptr;
+        a.mask = c->mask_on ? c->d_maskq.as<uint8_t>() : nullptr;
+        a.mind = c->d_kmpp_mind.as<uint32_t>();
+        a.part = c->d_kmpp_part.as<unsigned long long>();
+        a.wpart = a.part + (size_t)a.nspans * P;
+        a.cent = c->d_kmpp_cent.as<int4>();
+        a.out = reinterpret_cast<float4*>(a.cent + pk);
+        a.pix = reinterpret_cast<long long*>(a.out + pk);
+        a.n = (uint32_t)n;
+        a.P = P;
+        a.K = K;
+        a.seed = seed;
+        hipStream_t s = c->stream;
+        if (nfx > 0) {  // the fixed colours are every palette's centres 0 .. nfx - 1
+            std::vector<int4> cent(pk, make_int4(0, 0, 0, 0));
+            const float scale = u8 ? 255.0f : kKmppScale;
+            for (int p = 0; p < P; ++p)
+                for (int k = 0; k < nfx; ++k) {
+                    const float* f = c->fixed.data() + 4 * (size_t)k;
+                    cent[(size_t)p * K + k] = make_int4(kmpp_q(f[0], scale), kmpp_q(f[1], scale), kmpp_q(f[2], scale), 0);
+                }
+            HIP_TRY(c, hipMemcpyAsync(a.cent, cent.data(), sizeof(int4) * pk, hipMemcpyHostToDevice, s));
+            HIP_TRY(c, hipStreamSynchronize(s));  // (cent is pageable memory of this scope)
+        }
+        // Profiling: a round's two pairs are read back before the next round records them again,
+        // one synchronise per round; without it nothing waits until the draws are copied back.
+        ProfRec pr = prof_begin(c);
+        auto update = [&](int k_new, bool init, bool first, bool last) {
+            return timed_launch(pr, kPKmppUpdate, [&] { return launch_kmpp_update(a, k_new, init, s); }, first, last);
+        };
+        if (nfx == 0) HIP_TRY(c, update(-1, true, true, true));
+        for (int k = 0; k < nfx; ++k) HIP_TRY(c, update(k, k == 0, k == 0, k == nfx - 1));
+        for (int r = nfx; r < K; ++r) {
+            if (r > nfx) HIP_TRY(c, update(r - 1, false, true, true));
+            HIP_TRY(c, timed_launch(pr, kPKmppPick, [&] { return launch_kmpp_pick(a, r, r == 0, s); }));
+            if (pr.ev) {
+                HIP_TRY(c, hipStreamSynchronize(s));
+                prof_accumulate(c, pr);
+                pr = prof_begin(c);
+            }
+        }
+        HIP_TRY(c, hipMemcpyAsync(h_out.data(), a.out, sizeof(float4) * pk, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(h_pix.data(), a.pix, sizeof(int64_t) * pk, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+    }
+    for (int p = 0; p < P; ++p)
+        for (int k = 0; k < K; ++k) {
+            const size_t e = (size_t)p * K + k;
+            if (k < nfx) {
+                std::copy(c->fixed.begin() + 4 * (size_t)k, c->fixed.begin() + 4 * (size_t)(k + 1), h_out.begin() + 4 * e);
+                h_pix[e] = -1;
+            } else if (h_pix[e] < 0 || h_pix[e] >= n) {
+                return fail(c, HQ_ERR_DEVICE, "hq_kmeanspp_seed: palette %d, round %d drew no pixel", p, k);
+            }
+        }
+    std::copy(h_out.begin(), h_out.end(), palettes);
+    if (pixels) std::copy(h_pix.begin(), h_pix.end(), pixels);
+    return HQ_OK;
+}
+
 int hq_last_path(hq_ctx* c, hq_path_info* info) {
     if (!c || !info || info->size < (int32_t)sizeof(int32_t)) return HQ_ERR_ARG;
     hq_path_info pi = c->path;
@@ -941,6 +1036,9 @@ int hq_set_option(hq_ctx* c, const char* name, int value) {
     } else if (!std::strcmp(name, "cent_span")) {
         if (value < 0) return fail(c, HQ_ERR_ARG, "cent_span must be >= 0 (0 = auto)");
         c->cent_span = value;
+    } else if (!std::strcmp(name, "kmpp_span")) {
+        if (value < 0) return fail(c, HQ_ERR_ARG, "kmpp_span must be >= 0 (0 = auto)");
+        c->kmpp_span = value;
     } else if (!std::strcmp(name, "grad_tiled")) {
         if (value < -1 || value > 1) return fail(c, HQ_ERR_ARG, "grad_tiled must be -1, 0 or 1");
         c->grad_tiled = value;

@@ -737,6 +737,19 @@ class ImageManipulation:
         check(load().hq_median_cut(_lib.i64ptr(cells), int(bits), int(den), int(K), fptr(pal), C.byref(made)))
         return pal, made.value
 
+    def kmeansppSeed(self, P: int, K: int, seed: int = 0):
+        """hq_kmeanspp_seed: P palettes of K colours drawn from the image set by k-means++ (each
+        colour a pixel, drawn by weight times squared distance to the palette's nearest colour so
+        far; the context's mask or weights and fixed colours apply) -> (palettes float32 (P, 4K),
+        pixels int64 (P, K): the drawn pixels' raster indices, -1 for a fixed colour).  Integer
+        arithmetic on the device: the same seed gives the same bits."""
+        ctx = self._require()
+        pal = np.zeros((max(int(P), 1), 4 * max(int(K), 1)), np.float32)
+        pix = np.zeros((pal.shape[0], pal.shape[1] // 4), np.int64)
+        check(self._lib.hq_kmeanspp_seed(ctx, int(P), int(K), int(seed) & (2**64 - 1), fptr(pal), _lib.i64ptr(pix)),
+              ctx)
+        return pal, pix
+
     # the space of the nearest-colour rule: libhq's addition (option "assign_space", hq_assign_coords)
     ASSIGN_SPACES = ("rgb", "lab")
 
@@ -819,7 +832,10 @@ class ImageManipulation:
         ``init`` (hq_search_create_from): None is the reference's random start;
         ``"mediancut"`` starts every member of the population from the median cut of
         the image's colour histogram at ``initBits`` bits per channel (the members
-        part at iteration 1, each with its own draws); an array of shape (4K,) or
+        part at iteration 1, each with its own draws); ``"kmeans++"`` starts member p from
+        palette p of ``kmeansppSeed(population, K, seed)`` -- the search's seed -- so the members
+        are distinct good starts (the mask, weights and fixed colours of this call apply to the
+        draws); an array of shape (4K,) or
         (P, 4K) is the start as given.  ``seedColors`` is then the creation's best
         palette and ``seedError`` its cost, before any iteration.  It composes
         with ``lloydEvery`` and ``lloydSteps``.
@@ -1001,9 +1017,12 @@ class ImageManipulation:
         params = sw.params()
         handle = C.c_void_p()
         K = int(nbOfColors)
+        if isinstance(init, str) and init == "kmeans++":
+            # P distinct starts (the fixed colours, which the context holds, in front of each)
+            init, _ = self.kmeansppSeed(params.population, K, sw.seed)
         if isinstance(init, str):
             if init != "mediancut":
-                raise ValueError(f"init={init!r}: None, 'mediancut' or an array")
+                raise ValueError(f"init={init!r}: None, 'mediancut', 'kmeans++' or an array")
             # under fixed colours: the cut makes the K - n free ones, the fixed ones go in front
             init = np.zeros(4 * K, np.float32)
             init[:4 * nfx] = 0.0 if fx is None else fx.reshape(-1)

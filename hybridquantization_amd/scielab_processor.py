@@ -90,7 +90,7 @@ def makeChannels(inline):
 def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
                  whitepoint=Whitepoint.D65, verbose=False, device=0, iterations=None, dither=0.0,
                  ordered=None, mask=None, weights=None, fixed=None, pyramid=None, ditherKernel=None,
-                 dot=0.0, dotClasses=None, dotSearch=False, assignSpace=None, descendEvery=0):
+                 dot=0.0, dotClasses=None, dotSearch=False, assignSpace=None, descendEvery=0, init=None):
     """HQ:93-137 without the GUI: planar float image (3, N) in [0,1] ->
     (quantized planar image (3, N), bestColors float[4K], best error).  ``dither`` > 0
     (libhq's addition): the returned image is the best palette's Floyd-Steinberg rendering
@@ -119,7 +119,8 @@ def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
     scored (hq_quantize keeps the sRGB rule).  Anything else, or "lab" with ``dither``,
     ``ordered``, ``dot``, ``dotSearch`` or ``pyramid``, is a ValueError before anything runs.
     ``descendEvery`` (findBestQuantization's, pyramidSearch's: a descent iteration every so many, at
-    ImageManipulation's DESCEND_RATE)."""
+    ImageManipulation's DESCEND_RATE).  ``init`` (findBestQuantization's: None, "mediancut", "kmeans++" or an
+    array; under ``pyramid`` pyramidSearch's, which knows no "kmeans++"): how the search starts."""
     fixed_colors(fixed, int(nbOfColors))
     lab = assignSpace is not None and ImageManipulation.checkAssignSpace(
         assignSpace, dither=dither, ordered=ordered, dot=dot, dotSearch=dotSearch, pyramid=pyramid) != 0
@@ -138,7 +139,7 @@ def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
         if pyramid is not None:
             best = pyramidSearch(ip, inline_rgb, w, nbOfColors, swasa, dpi, viewingDistance, whitepoint,
                                  levels=pyramid, mask=mask, weights=weights, fixed=fixed,
-                                 descendEvery=descendEvery)
+                                 descendEvery=descendEvery, init=init)
             q = (ip.quantizeDotDiffused(best, dot, classes=dotClasses) if float(dot) > 0.0 else
                  ip.quantizeOrdered(best, ordered) if ordered is not None else
                  ip.quantizeDithered(best, dither, kernel=ditherKernel) if float(dither) > 0.0 else
@@ -149,7 +150,7 @@ def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
         best = sp.bestColors(inline_rgb, sc_img, w, nbOfColors, swasa, iterations=iterations, dither=dither,
                              ditherKernel=ditherKernel, ordered=ordered, mask=mask, weights=weights, fixed=fixed,
                              dot=dot, dotClasses=dotClasses, dotSearch=dotSearch, assignSpace=assignSpace,
-                             descendEvery=descendEvery)
+                             descendEvery=descendEvery, init=init)
         if lab:
             q = ip.quantizeAssigned(best, assignSpace)
             return np.stack(makeChannels(q)), best, ip.bestError

@@ -906,6 +906,50 @@ int hq_color_histogram(hq_ctx *ctx, int bits, int64_t *cells, int64_t *den);
  * count, a total count of 0 or above 2^48 (the priority would leave 64 bits). */
 int hq_median_cut(const int64_t *cells, int bits, int64_t den, int K, float *palette, int *made);
 
+/* ---- k-means++ seeding of a population: libhq's addition, no reference counterpart ----
+ * The median cut is one palette; a search works on P.  hq_kmeanspp_seed draws P palettes of K
+ * colours from the context's image by k-means++ (Arthur & Vassilvitskii 2007): every colour is a
+ * pixel of the image, drawn with probability proportional to its weight times its squared
+ * distance to the palette's nearest colour so far.  The rule is integer throughout, so a
+ * restatement in Python integers gives the same pixels, and two calls give the same bits.
+ *  - q(x), the integer channels of pixel x: the bytes 0 .. 255 when the argmin reads the packed
+ *    8-bit copy of a k/255 image (option "img_u8" 1, the default; S = 255), else per channel
+ *    RN(clamp(v, 0, 1) S), S = 4095: the fp32 product rounded to nearest, ties to even, a NaN
+ *    counting as 0.
+ *  - w(x), the integer weight: 1 with neither mask nor weights; (mask byte != 0) under hq_set_mask;
+ *    the weight byte under hq_set_weights.
+ *  - u(p, r), the 64-bit word of palette p and round r: with x = seed + (p << 32) + r (mod 2^64),
+ *      z = x + 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *      z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  u = z ^ (z >> 31)          (SplitMix64).
+ *  - Round r of palette p: T = sum over x of w(x) D(x), t = floor(u(p, r) T / 2^64), and the
+ *    chosen pixel is the first x in raster order whose inclusive prefix sum of w D is above t.
+ *    T < 2^64: an image has at most 2^30 pixels (more: HQ_ERR_UNSUPPORTED) of w D <= 255 * 3 *
+ *    4095^2.
+ *  - D: 1 for every x while the palette has no colour yet (round 0: the draw is by weight alone);
+ *    afterwards the minimum, over the colours the palette has so far, of the squared integer
+ *    distance |q(x) - q(colour)|^2.  When that makes T = 0 (every in-mask colour is in the palette
+ *    already) the round falls back to D = 1.
+ *  - Fixed colours (hq_set_fixed_colors, n of them): colours 0 .. n - 1 of every palette are those,
+ *    with q = RN(clamp(v, 0, 1) S) per channel; they count in D before the first draw, and the
+ *    draws are rounds n .. K - 1 (n = K: none).
+ * palettes[P][K][4]: colour k of palette p, the chosen pixel's colour as the image holds it --
+ * (float)byte / 255.0f per channel of the packed form, the planar floats' bits otherwise -- with
+ * .w = 0; a fixed colour's bits for k < n.  pixels[P][K] (may be NULL): the chosen pixel's raster
+ * index y w + x, -1 for a fixed colour.  Palette p of a population is the palette a call with
+ * P = 1 draws under the seed that gives the same words (they depend on seed + (p << 32) alone).
+ * HQ_ERR_ARG: palettes NULL, P < 1, K < 1, K > 16384, more fixed colours than K.  HQ_ERR_STATE: no
+ * image set, or a row-block shard.  HQ_ERR_UNSUPPORTED: a communicator of more than one rank, a
+ * palette slice (options "palette_split", "slice_ranks" > 1), option "assign_space" 1 (the
+ * distances are sRGB's).  hq_set_mask and hq_set_weights refuse a map without a non-zero byte, so
+ * the weights never sum to 0.  A call that does not return HQ_OK writes neither output.  It needs
+ * no evaluated population and disturbs none.  Profiling stages "kmpp_update" and "kmpp_pick"
+ * (with profiling on the call synchronises once per round to read them).  Test option
+ * "kmpp_span": the pixels per workgroup of the streaming kernel (0: by the grid), rounded up to
+ * 1024; the result does not depend on it.  Left out: shards and communicators (the spans'
+ * partial sums would add exactly), CIELAB distances, several candidates per round, the JNI /
+ * Java binding. */
+int hq_kmeanspp_seed(hq_ctx *ctx, int P, int K, uint64_t seed, float *palettes, int64_t *pixels);
+
 /* ---- an image pyramid on the device: libhq's additions, no reference counterpart ----
  * Every search runs at the image's full resolution, yet the cost is a blurred dE: it
  * changes little when the image is box-reduced and the filters are designed for the
