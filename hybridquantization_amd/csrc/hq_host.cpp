@@ -287,18 +287,9 @@ int SearchDriver::run(int iterations, int* ran, std::vector<double>* trace) {
             for (int j = 0; j < P_ && nfixed_ > 0; ++j)
                 std::copy_n(&colors_[(size_t)j * n], 4 * nfixed_, &current_[(size_t)j * n]);
         };
-        if (every_ > 0 && refine_ && ite % every_ == 0) {             // hybrid iteration: one k-means move
-            const int rr = refine_(current_.data(), P_, K_);
-            if (rr) { if (ran) *ran = done; return rr; }
-            put_fixed_back();
-        }
-        if (repair_every_ > 0 && repair_ && ite % repair_every_ == 0) {  // repair iteration: unused colours reseeded
-            const int rr = repair_(current_.data(), P_, K_);
-            if (rr) { if (ran) *ran = done; return rr; }
-            put_fixed_back();
-        }
-        if (descend_every_ > 0 && descend_ && ite % descend_every_ == 0) {  // descent iteration: the finest move, last
-            const int rr = descend_(current_.data(), P_, K_);
+        for (const auto& mv : moves_) {  // in Move's order: one k-means move, unused colours reseeded, the finest last
+            if (mv.every <= 0 || !mv.apply || ite % mv.every != 0) continue;
+            const int rr = mv.apply(current_.data(), P_, K_);
             if (rr) { if (ran) *ran = done; return rr; }
             put_fixed_back();
         }
@@ -355,8 +346,8 @@ extern "C" int hq_swasa_search_host_fixed(const hq_swasa_params* params, int K, 
         return eval(user, pal, P, KK, costs) ? HQ_ERR_ARG : HQ_OK;
     });
     if (refine && every > 0) {
-        d.set_refine([&](float* pal, int P, int KK) { return refine(user, pal, P, KK); });
-        d.set_every(every);
+        d.set_move(hq::kLloyd, [&](float* pal, int P, int KK) { return refine(user, pal, P, KK); });
+        d.set_every(hq::kLloyd, every);
     }
     d.set_fixed(nfixed, nfixed > 0 ? fixed_colors : nullptr);
     int rc = d.start(population);

@@ -446,17 +446,20 @@ struct hq_search {
     hq::Swasa* pol = nullptr;
     hq_swasa_params prm{};
     int P = 0, ite = 0, st = 0, cd = 0;  // state and candidate buffer parities
-    int every = 0;                       // hq_search_set_lloyd: iteration ite % every == 0 is hybrid (0: none)
-    int repair_every = 0;                // hq_search_set_repair: iteration ite % repair_every == 0 repairs (0: none)
-    int repair_moves = -1;               // ... at most so many colours per palette (< 0: no limit)
-    int descend_every = 0;               // hq_search_set_descend: iteration ite % descend_every == 0 descends (0: none)
-    float descend_rate = 0.f;            // ... by this step
+    // hq_search_set_lloyd, _repair, _descend: iteration ite % every == 0 applies move [hq::Move] (0: none), in that
+    // order, with the one parameter that is its own; hq_search_run.hip's table says what each needs and enqueues
+    struct MoveState {
+        int every = 0;
+        float rate = 0.f;    // descent: by this step
+        int max_moves = -1;  // repair: at most so many colours per palette (< 0: no limit)
+    } moves[hq::kMoves];
+    bool grad_tiled = false;             // the descent moves of the run being enqueued: the gradient's form and
+    int grad_shift = 0;                  // its fixed-point shift (ensure_gradient, before the run's capture)
     int nch = 1;                         // chunked palettes (256 < K <= 16384): chunks per palette
-    bool ordered = false;                // hq_search_set_ordered: every evaluation is the ordered one
-    hq::Ordered ord{};                   // ... at this amplitude per channel
-    bool dot = false;                    // hq_search_set_dot: every evaluation is the dot-diffused one
-    float dot_strength = 0.f;            // ... at this strength
-    hq_dot_classes dot_cls{};            // ... under this matrix, the search's own (latched at the call)
+    // hq_search_set_ordered, hq_search_set_dot: every evaluation is the ordered one at this amplitude per channel or
+    // the dot-diffused one at this strength (no window: a whole image); never Diffused
+    hq::Rendering rendering;
+    hq_dot_classes dot_cls{};            // ... the dot-diffused one under this matrix, the search's own (latched at the call)
     int nfixed = 0;                      // the context's fixed colours at hq_search_create: colours
     std::vector<float> fixed;            // 0 .. nfixed-1 of every member, [nfixed][4], for the search's life
     bool fold = false;                   // accept steps reduce the partials (no finalize launch)

@@ -62,6 +62,9 @@ int enqueue_sa_step(hq_search* s, bool accept, bool init, bool generate, bool ra
     return HQ_OK;
 }
 
+// The last iteration done, whichever side counts it.
+int iteration(const hq_search* s) { return s->driver ? s->driver->iteration() : s->ite; }
+
 // What a hybrid or a repair iteration of a device-resident search needs beyond the whole image.
 int device_move_scope(hq_search* s, const char* what) {
     if (!s->driver && s->nch > 1)
@@ -108,6 +111,27 @@ int lloyd_validate(hq_search* s) {
     return sums_u8(c) ? HQ_OK : require_unit_range_image(c, "planar image", "no exact sums, no hybrid iteration");
 }
 
+// d_sums' and d_errstat's size: [P][K][4] 64-bit words, then the flag.
+size_t table_bytes(const hq_search* s) { return sizeof(int64_t) * ((size_t)s->P * s->K * 4 + 1); }
+
+// Hybrid iterations in a run: the sums buffer before anything is enqueued (no allocation
+// while a run is captured), zeroed once inside the capture (the table's `zeroed`) -- the
+// update kernel leaves it zero for the next hybrid iteration.
+int prepare_lloyd(hq_search* s) {
+    HIP_TRY(s->ctx, s->ctx->d_sums.ensure(table_bytes(s)));
+    return HQ_OK;
+}
+
+// Repair iterations in a run: the same for the error image, the statistics and the worst
+// pixels -- nothing of it without one.
+int prepare_repair(hq_search* s) {
+    hq_ctx* c = s->ctx;
+    HIP_TRY(c, c->d_pixerr.ensure(sizeof(float) * (size_t)s->P * std::max<int64_t>(n_own(c->g), 1)));
+    HIP_TRY(c, c->d_errstat.ensure(table_bytes(s)));
+    HIP_TRY(c, c->d_worst.ensure(sizeof(float) * (size_t)s->P * s->K * 4));
+    return HQ_OK;
+}
+
 // The k-means move of a device-resident hybrid iteration, after the sa_step that
 // generated and prepared the candidates (now cand[cd]): the assign-only pass,
 // the sums kernel into d_sums (zero on entry: the run's memset, then the update
@@ -144,8 +168,8 @@ int enqueue_repair(hq_search* s, ProfRec& pr) {
     int idx_bytes = 1;
     const ClusterErrArgs ea = cluster_err_args(c, s->P, s->K, s->nch, &idx_bytes);
     HIP_TRY(c, timed_launch(pr, kPErrsum, [&] { return launch_cluster_errors(ea, idx_bytes, c->num_cu, c->stream); }));
-    const ReseedArgs ra{ea.stats, ea.worst, s->cand[s->cd].as<float>(), prep_args(c, s->K), s->K, s->repair_moves,
-                        s->nfixed};
+    const ReseedArgs ra{ea.stats, ea.worst, s->cand[s->cd].as<float>(), prep_args(c, s->K), s->K,
+                        s->moves[kRepair].max_moves, s->nfixed};
     HIP_TRY(c, timed_launch(pr, kPReseed, [&] { return launch_reseed(ra, s->P, c->stream); }));
     return HQ_OK;
 }
@@ -156,13 +180,23 @@ int enqueue_repair(hq_search* s, ProfRec& pr) {
 int descend_scope(hq_search* s) {
     hq_ctx* c = s->ctx;
     const char* const what = "descent iterations";
-    if (s->dot)
+    if (std::holds_alternative<Dot>(s->rendering))
         return fail(c, HQ_ERR_UNSUPPORTED, "%s in a search under the dot-diffused cost (hq_search_set_dot): it has no "
                                            "assign-only pass", what);
     if (int rc = gradient_config(c, s->K, what)) return rc;
     bool tiled;
     int shift;
     return ensure_gradient(c, 0, s->K, what, &tiled, &shift);
+}
+
+// Descent iterations in a run: g, the bins and the plain pair's scratch, and the form and the
+// shift the run's descent moves take; the bins zeroed here on the stream, in front of the
+// capture -- the update kernel leaves them zero.
+int prepare_descend(hq_search* s) {
+    hq_ctx* c = s->ctx;
+    if (int rc = ensure_gradient(c, s->P, s->K, "descent iterations", &s->grad_tiled, &s->grad_shift)) return rc;
+    HIP_TRY(c, hipMemsetAsync(c->d_grad_sums.p, 0, sizeof(int64_t) * (size_t)s->P * s->K * 4, c->stream));
+    return HQ_OK;
 }
 
 // The descent move of a device-resident descent iteration, after the sa_step that generated
@@ -172,16 +206,37 @@ int descend_scope(hq_search* s) {
 // search's amplitude), recorded in pairs of its own; the gradient kernels on those index images
 // into d_grad_sums (zero on entry: the run's memset, then the update kernel's own zeroing); the
 // update kernel, which prepares the moved candidates for the evaluation that follows.
-int enqueue_descend(hq_search* s, bool tiled, int shift, ProfRec& pr) {
+int enqueue_descend(hq_search* s, ProfRec& pr) {
     hq_ctx* c = s->ctx;
-    int rc = enqueue_core(c, s->P, s->K, pr, s->ordered ? Pass{Pass::AssignOnly, s->ord, kPDescGrid}
-                                                        : Pass{Pass::AssignOnly, kPDescGrid});
-    if (rc || (rc = enqueue_gradient(c, s->P, s->K, tiled, shift, pr))) return rc;
+    const Ordered* ord = std::get_if<Ordered>(&s->rendering);
+    int rc = enqueue_core(c, s->P, s->K, pr, ord ? Pass{Pass::AssignOnly, *ord, kPDescGrid}
+                                                 : Pass{Pass::AssignOnly, kPDescGrid});
+    if (rc || (rc = enqueue_gradient(c, s->P, s->K, s->grad_tiled, s->grad_shift, pr))) return rc;
     const DescendArgs da{c->d_grad_sums.as<unsigned long long>(), s->cand[s->cd].as<float>(), prep_args(c, s->K),
-                         (double)s->descend_rate, s->K, shift, s->nfixed};
+                         (double)s->moves[kDescend].rate, s->K, s->grad_shift, s->nfixed};
     HIP_TRY(c, timed_launch(pr, kPDescend, [&] { return launch_descend_update(da, s->P, c->stream); }));
     return HQ_OK;
 }
+
+// ---- the moves, in the order an iteration applies them (hq::Move) ----------------
+// what: the move's name in the refusals.  scope: what the search and the context must be for
+// it, the setter's check; validate: what a run with such an iteration asks of the image beyond
+// that (null: nothing).  prepare: what such a run puts in place before anything is enqueued or
+// captured; zeroed: the table it then zeroes inside the capture (null: prepare zeroed the
+// move's on the stream, in front of it).  enqueue: the move itself, after the sa_step.
+struct MoveRow {
+    const char* what;
+    int (*scope)(hq_search*);
+    int (*validate)(hq_search*);
+    int (*prepare)(hq_search*);
+    DevBuf hq_ctx::*zeroed;
+    int (*enqueue)(hq_search*, ProfRec&);
+};
+const MoveRow kMoveTable[kMoves] = {
+    {"hybrid iterations", lloyd_scope, lloyd_validate, prepare_lloyd, &hq_ctx::d_sums, enqueue_lloyd},
+    {"repair iterations", repair_scope, nullptr, prepare_repair, &hq_ctx::d_errstat, enqueue_repair},
+    {"descent iterations", descend_scope, nullptr, prepare_descend, nullptr, enqueue_descend},
+};
 
 // The end of hq_search_create*, hq_search_run and hq_search_set_ordered (status rc, so many
 // evaluations enqueued).  What the getters may read then (hq.h) is the index images of the
@@ -202,16 +257,26 @@ void search_commit(hq_search* s, int rc, int evaluations) {
 // dot-diffused one at the search's strength, under the tables ensure_dot_pass has put in place)
 Pass search_pass(const hq_search* s) {
     const Pass::Kind kind = s->fold ? Pass::Fold : Pass::Full;
-    if (s->dot) return Pass{s->fold, Dot{s->dot_strength, 0, 0}};  // (a whole image: no window)
-    return s->ordered ? Pass{kind, s->ord} : Pass{kind};
+    if (const Dot* dot = std::get_if<Dot>(&s->rendering)) return Pass{s->fold, *dot};
+    const Ordered* ord = std::get_if<Ordered>(&s->rendering);
+    return ord ? Pass{kind, *ord} : Pass{kind};
+}
+
+// What the search's rendering needs on the device before anything is enqueued or captured: the
+// threshold map; the search's own matrix, whatever hq_dot_population has put there since, and
+// the chain's errors.
+int ensure_rendering(hq_search* s) {
+    if (std::holds_alternative<Ordered>(s->rendering)) return ensure_dither_map(s->ctx);
+    if (std::holds_alternative<Dot>(s->rendering)) return ensure_dot_pass(s->ctx, s->dot_cls, s->P, s->K);
+    return HQ_OK;
 }
 
 // A search under the ordered cost moves by annealing alone: a k-means or repair move from a
 // dithered assignment is neither (hq_ordered_population's rule for hq_cluster_sums).
 int ordered_excludes(hq_search* s, const char* what) {
-    if (s->ordered)
+    if (std::holds_alternative<Ordered>(s->rendering))
         return fail(s->ctx, HQ_ERR_UNSUPPORTED, "%s in a search under the ordered cost (hq_search_set_ordered)", what);
-    if (s->dot)
+    if (std::holds_alternative<Dot>(s->rendering))
         return fail(s->ctx, HQ_ERR_UNSUPPORTED, "%s in a search under the dot-diffused cost (hq_search_set_dot)", what);
     return HQ_OK;
 }
@@ -227,8 +292,7 @@ int device_search_rerank(hq_search* s) {
     if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
     const NchScope scope(c, s->nch);
     if ((rc = ensure_population(c, s->P, s->K))) return rc;
-    if (s->ordered && (rc = ensure_dither_map(c))) return rc;
-    if (s->dot && (rc = ensure_dot_pass(c, s->dot_cls, s->P, s->K))) return rc;
+    if ((rc = ensure_rendering(s))) return rc;
     if (s->nch > 1) return fail(c, HQ_ERR_UNSUPPORTED, "K=%d > %d", s->K, kMaxK);
     if ((rc = upload_and_prep(c, nullptr, s->cand[s->cd].p, s->P, s->K))) return rc;
     ProfRec untimed;
@@ -330,9 +394,7 @@ int device_search_run(hq_search* s, int iterations, int* ran) {
     if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
     const NchScope scope(c, s->nch);
     if ((rc = ensure_population(c, s->P, s->K))) return rc;
-    if (s->ordered && (rc = ensure_dither_map(c))) return rc;  // (before a capture begins)
-    // the search's own matrix, whatever hq_dot_population has put there since, and the chain's errors
-    if (s->dot && (rc = ensure_dot_pass(c, s->dot_cls, s->P, s->K))) return rc;
+    if ((rc = ensure_rendering(s))) return rc;  // (before a capture begins)
     if (s->comm != c->comm || s->fold != search_folds(c))
         return fail(c, HQ_ERR_STATE, "communicator or palette split changed after hq_search_create: "
                                      "recreate the search");
@@ -342,28 +404,11 @@ int device_search_run(hq_search* s, int iterations, int* ran) {
     if (prof) HIP_TRY(c, s->pev.ensure((size_t)2 * kPairs * iterations));
     std::vector<ProfRec> recs(prof ? iterations : 0);
     ProfRec untimed;
-    // hybrid iterations in this run: the sums buffer before anything is enqueued
-    // (no allocation while a run is captured), zeroed once below -- the update
-    // kernel leaves it zero for the next hybrid iteration
-    const bool lloyd = period_in_run(s, s->every, s->ite, iterations);
-    const size_t sums_bytes = sizeof(int64_t) * ((size_t)s->P * s->K * 4 + 1);  // (d_sums' and d_errstat's)
-    if (lloyd) HIP_TRY(c, c->d_sums.ensure(sums_bytes));
-    // repair iterations in this run: the same for the error image, the statistics and the
-    // worst pixels -- nothing of it without one
-    const bool repair = period_in_run(s, s->repair_every, s->ite, iterations);
-    if (repair) {
-        HIP_TRY(c, c->d_pixerr.ensure(sizeof(float) * (size_t)s->P * std::max<int64_t>(n_own(c->g), 1)));
-        HIP_TRY(c, c->d_errstat.ensure(sums_bytes));
-        HIP_TRY(c, c->d_worst.ensure(sizeof(float) * (size_t)s->P * s->K * 4));
-    }
-    // descent iterations in this run: g, the bins and the plain pair's scratch, the bins zeroed
-    // here on the stream, in front of the capture -- the update kernel leaves them zero
-    const bool descend = period_in_run(s, s->descend_every, s->ite, iterations);
-    bool grad_tiled = false;
-    int grad_sh = 0;
-    if (descend) {
-        if ((rc = ensure_gradient(c, s->P, s->K, "descent iterations", &grad_tiled, &grad_sh))) return rc;
-        HIP_TRY(c, hipMemsetAsync(c->d_grad_sums.p, 0, sizeof(int64_t) * (size_t)s->P * s->K * 4, c->stream));
+    // the moves with an iteration in this run: what each needs in place (kMoveTable's prepare)
+    bool in_run[kMoves];
+    for (int m = 0; m < kMoves; ++m) {
+        in_run[m] = period_in_run(s, s->moves[m].every, s->ite, iterations);
+        if (in_run[m] && (rc = kMoveTable[m].prepare(s))) return rc;
     }
     // option sa_graph: the run's kernels go into one hipGraph (stream capture),
     // replayed as a whole -- a chain of dependent kernels costs ~2.7 us per
@@ -386,8 +431,8 @@ int device_search_run(hq_search* s, int iterations, int* ran) {
         if (e != hipSuccess) (void)abort_capture(0);
         return e;
     };
-    if (lloyd) HIP_TRY(c, zero_table(c->d_sums, sums_bytes));
-    if (repair) HIP_TRY(c, zero_table(c->d_errstat, sums_bytes));
+    for (int m = 0; m < kMoves; ++m)
+        if (in_run[m] && kMoveTable[m].zeroed) HIP_TRY(c, zero_table(c->*kMoveTable[m].zeroed, table_bytes(s)));
     for (; done < iterations && s->ite < s->prm.imax; ++done) {
         const int ite = ++s->ite;
         s->pol->reduce_temperature_if_necessary(ite);                  // IM:507
@@ -396,11 +441,9 @@ int device_search_run(hq_search* s, int iterations, int* ran) {
         if (prof) pr.ev = &s->pev.ev[(size_t)2 * kPairs * done];
         // accept the previous iteration's population (none at the first of a run)
         if ((rc = enqueue_sa_step(s, done > 0, false, true, false, amax, pr))) return abort_capture(rc);
-        if (s->every > 0 && ite % s->every == 0 && (rc = enqueue_lloyd(s, pr))) return abort_capture(rc);
-        if (s->repair_every > 0 && ite % s->repair_every == 0 && (rc = enqueue_repair(s, pr)))
-            return abort_capture(rc);
-        if (s->descend_every > 0 && ite % s->descend_every == 0 && (rc = enqueue_descend(s, grad_tiled, grad_sh, pr)))
-            return abort_capture(rc);
+        for (int m = 0; m < kMoves; ++m)
+            if (s->moves[m].every > 0 && ite % s->moves[m].every == 0 && (rc = kMoveTable[m].enqueue(s, pr)))
+                return abort_capture(rc);
         if ((rc = enqueue_core(c, s->P, s->K, pr, search_pass(s)))) return abort_capture(rc);
         s->t_acc = s->pol->temperature();     // SW:54-57 at this iteration
         s->keep_acc = s->pol->keep_threshold(ite);
@@ -438,21 +481,60 @@ int device_search_run(hq_search* s, int iterations, int* ran) {
 }
 
 // What a run of `iterations` needs of the context as it is now (the image or an option may
-// have changed): a hybrid iteration in it, its scope and the image's validity; a repair
-// iteration, its scope; no palette slice under a pixel mask; the ordered cost's scope.
+// have changed): each move with an iteration in it, its scope (a hybrid iteration: the image's
+// validity too); no palette slice under a pixel mask; the searched rendering's scope.
 int run_scope(hq_search* s, int iterations) {
-    const int ite = s->driver ? s->driver->iteration() : s->ite;
+    const int ite = iteration(s);
     int rc;
     // the errors a search holds were measured under the argmin rule it was created with
     if (s->assign_space != s->ctx->assign_space)
         return fail(s->ctx, HQ_ERR_STATE, "option assign_space changed after hq_search_create (%d, now %d): "
                                           "recreate the search", s->assign_space, s->ctx->assign_space);
-    if (period_in_run(s, s->every, ite, iterations) && ((rc = lloyd_scope(s)) || (rc = lloyd_validate(s)))) return rc;
-    if (period_in_run(s, s->repair_every, ite, iterations) && (rc = repair_scope(s))) return rc;
-    if (period_in_run(s, s->descend_every, ite, iterations) && (rc = descend_scope(s))) return rc;
+    for (int m = 0; m < kMoves; ++m) {
+        const MoveRow& row = kMoveTable[m];
+        if (!period_in_run(s, s->moves[m].every, ite, iterations)) continue;
+        if ((rc = row.scope(s)) || (row.validate && (rc = row.validate(s)))) return rc;
+    }
     if ((rc = mask_scope(s->ctx))) return rc;
-    if (s->dot) return dot_search_scope(s->ctx, s->K);
-    return s->ordered ? ordered_scope(s->ctx, s->K) : HQ_OK;
+    if (std::holds_alternative<Dot>(s->rendering)) return dot_search_scope(s->ctx, s->K);
+    return std::holds_alternative<Ordered>(s->rendering) ? ordered_scope(s->ctx, s->K) : HQ_OK;
+}
+
+// hq_search_set_lloyd, _repair and _descend: move m's period and parameter become `state`.  A
+// period above 0 first passes `own` -- the entry point's check of its argument and of what
+// excludes its move -- and the move's scope; a refusal leaves the search as it was.
+template <typename Own>
+int set_move(hq_search* s, Move m, const hq_search::MoveState& state, Own own) {
+    if (!s || !s->ctx) return HQ_ERR_ARG;
+    if (state.every < 0) return fail(s->ctx, HQ_ERR_ARG, "every=%d < 0", state.every);
+    if (state.every > 0) {
+        if (int rc = own()) return rc;
+        if (int rc = kMoveTable[m].scope(s)) return rc;
+    }
+    s->moves[m] = state;
+    if (s->driver) s->driver->set_every(m, state.every);
+    return HQ_OK;
+}
+
+// The end of hq_search_set_ordered and hq_search_set_dot, past their refusals: `next` (and, of
+// a dot rendering switched on, its matrix) becomes the search's rendering unless it is the
+// `same`.  Before the first iteration the initial population's errors and its best are the
+// new evaluation's; a rerank that fails leaves the previous rendering in force.
+int set_rendering(hq_search* s, bool same, const Rendering& next, const hq_dot_classes* cls = nullptr) {
+    if (same) return HQ_OK;  // (nothing changes: nothing is enqueued)
+    const Rendering old = s->rendering;
+    const hq_dot_classes old_cls = s->dot_cls;
+    s->rendering = next;
+    if (cls) {
+        std::memset(&s->dot_cls, 0, sizeof s->dot_cls);
+        s->dot_cls.n = cls->n;
+        std::memcpy(s->dot_cls.cls, cls->cls, sizeof(int32_t) * cls->n * cls->n);
+    }
+    if (iteration(s) != 0) return HQ_OK;
+    const int rc = s->driver ? s->driver->rerank() : device_search_rerank(s);
+    search_commit(s, rc, 1);
+    if (rc) s->rendering = old, s->dot_cls = old_cls;
+    return rc;
 }
 
 }  // namespace
@@ -499,29 +581,32 @@ int hq_search_create_from(hq_ctx* c, const hq_swasa_params* params, int K, uint6
     } else {
         const float delta = params->delta;
         auto eval = [c, delta, s](const float* pal, int P, int KK, double* costs) {
-            if (s->dot) return hq_dot_population(c, pal, P, KK, &s->dot_cls, s->dot_strength, delta, costs, nullptr);
-            return s->ordered ? hq_ordered_population(c, pal, P, KK, s->ord.amp, delta, costs, nullptr)
-                              : hq_eval_population(c, pal, P, KK, delta, costs, nullptr);
+            if (const Dot* dot = std::get_if<Dot>(&s->rendering))
+                return hq_dot_population(c, pal, P, KK, &s->dot_cls, dot->strength, delta, costs, nullptr);
+            const Ordered* ord = std::get_if<Ordered>(&s->rendering);
+            return ord ? hq_ordered_population(c, pal, P, KK, ord->amp, delta, costs, nullptr)
+                       : hq_eval_population(c, pal, P, KK, delta, costs, nullptr);
         };
         s->driver = new SearchDriver(*params, K, seed, eval);
         // the k-means move, host-driven, is the public triple: an evaluation of the
         // candidates for their argmin (its cost pass is wasted), the sums, the update
-        s->driver->set_refine([c, delta, s](float* pal, int P, int KK) {
+        s->driver->set_move(kLloyd, [c, delta, s](float* pal, int P, int KK) {
             std::vector<double> costs(P);
             const int rr = hq_eval_population(c, pal, P, KK, delta, costs.data(), nullptr);
             return rr ? rr : kmeans_move(c, P, KK, s->nfixed, pal);
         });
         // the repair move, host-driven: an evaluation of the candidates that stores their
         // error image, the error statistics (pixels with no usable dE left out) and the rule
-        s->driver->set_repair([c, delta, s](float* pal, int P, int KK) {
+        s->driver->set_move(kRepair, [c, delta, s](float* pal, int P, int KK) {
             const PixelErrScope scope(c);
             std::vector<double> costs(P);
             const int rr = hq_eval_population(c, pal, P, KK, delta, costs.data(), nullptr);
-            return rr ? rr : repair_move(c, P, KK, s->repair_moves, s->nfixed, true, pal, nullptr);
+            return rr ? rr : repair_move(c, P, KK, s->moves[kRepair].max_moves, s->nfixed, true, pal, nullptr);
         });
         // the descent move, host-driven: the public call, the device-resident form's own kernels
-        s->driver->set_descend([c, s](float* pal, int P, int KK) {
-            return hq_descend_move(c, pal, P, KK, s->descend_rate, s->ordered ? s->ord.amp : nullptr);
+        s->driver->set_move(kDescend, [c, s](float* pal, int P, int KK) {
+            const Ordered* ord = std::get_if<Ordered>(&s->rendering);
+            return hq_descend_move(c, pal, P, KK, s->moves[kDescend].rate, ord ? ord->amp : nullptr);
         });
         s->prm = *params;
         s->P = params->population;
@@ -557,48 +642,26 @@ int hq_search_run(hq_search* s, int iterations, int* ran) {
 }
 
 int hq_search_set_lloyd(hq_search* s, int every) {
-    if (!s || !s->ctx) return HQ_ERR_ARG;
-    if (every < 0) return fail(s->ctx, HQ_ERR_ARG, "every=%d < 0", every);
-    if (every > 0) {
-        if (int rc = ordered_excludes(s, "hybrid iterations")) return rc;
-        if (int rc = lloyd_scope(s)) return rc;
-    }
-    s->every = every;
-    if (s->driver) s->driver->set_every(every);
-    return HQ_OK;
+    return set_move(s, kLloyd, {every}, [&] { return ordered_excludes(s, kMoveTable[kLloyd].what); });
 }
 
+// (max_moves is stored as given, whatever the period)
 int hq_search_set_repair(hq_search* s, int every, int max_moves) {
-    if (!s || !s->ctx) return HQ_ERR_ARG;
-    if (every < 0) return fail(s->ctx, HQ_ERR_ARG, "every=%d < 0", every);
-    if (every > 0) {
-        if (int rc = ordered_excludes(s, "repair iterations")) return rc;
-        if (int rc = repair_scope(s)) return rc;
-    }
-    s->repair_every = every;
-    s->repair_moves = max_moves;
-    if (s->driver) s->driver->set_repair_every(every);
-    return HQ_OK;
+    return set_move(s, kRepair, {every, 0.f, max_moves}, [&] { return ordered_excludes(s, kMoveTable[kRepair].what); });
 }
 
+// (composes with the ordered cost; the dot-diffused one is its scope's refusal.  No period: a rate of 0)
 int hq_search_set_descend(hq_search* s, int every, float rate) {
-    if (!s || !s->ctx) return HQ_ERR_ARG;
-    if (every < 0) return fail(s->ctx, HQ_ERR_ARG, "every=%d < 0", every);
-    if (every > 0) {
-        if (!(rate > 0.0f) || !std::isfinite(rate))
-            return fail(s->ctx, HQ_ERR_ARG, "rate=%g: a finite step above 0", (double)rate);
-        if (int rc = descend_scope(s)) return rc;
-    }
-    s->descend_every = every;
-    s->descend_rate = every > 0 ? rate : 0.f;
-    if (s->driver) s->driver->set_descend_every(every);
-    return HQ_OK;
+    return set_move(s, kDescend, {every, every > 0 ? rate : 0.f}, [&] {
+        return !(rate > 0.0f) || !std::isfinite(rate)
+                   ? fail(s->ctx, HQ_ERR_ARG, "rate=%g: a finite step above 0", (double)rate) : HQ_OK;
+    });
 }
 
 int hq_search_descend_info(const hq_search* s, int* every, float* rate) {
     if (!s) return HQ_ERR_ARG;
-    if (every) *every = s->descend_every;
-    if (rate) *rate = s->descend_rate;
+    if (every) *every = s->moves[kDescend].every;
+    if (rate) *rate = s->moves[kDescend].rate;
     return HQ_OK;
 }
 
@@ -610,25 +673,17 @@ int hq_search_set_ordered(hq_search* s, const float amp[3]) {
     if (int rc = check_ordered_amp(c, amp)) return rc;
     const bool on = amp[0] != 0.f || amp[1] != 0.f || amp[2] != 0.f;
     if (on) {
-        if (s->every > 0 || s->repair_every > 0)
+        if (s->moves[kLloyd].every > 0 || s->moves[kRepair].every > 0)
             return fail(c, HQ_ERR_UNSUPPORTED, "a search with hybrid or repair iterations: no ordered cost");
-        if (s->dot) return fail(c, HQ_ERR_UNSUPPORTED, "a search under the dot-diffused cost: one rendering per search");
+        if (std::holds_alternative<Dot>(s->rendering))
+            return fail(c, HQ_ERR_UNSUPPORTED, "a search under the dot-diffused cost: one rendering per search");
         if (int rc = assign_space_excludes(c, "hq_search_set_ordered")) return rc;
         if (int rc = ordered_scope(c, s->K)) return rc;
     }
-    const Ordered old = s->ord;
-    if (on == s->ordered && (!on || (amp[0] == old.amp[0] && amp[1] == old.amp[1] && amp[2] == old.amp[2])))
-        return HQ_OK;  // (nothing changes: nothing is enqueued)
-    const bool was = s->ordered;
-    s->ordered = on;
-    for (int ch = 0; ch < 3; ++ch) s->ord.amp[ch] = on ? amp[ch] : 0.f;  // (zeros: the plain pass itself)
-    const int ite = s->driver ? s->driver->iteration() : s->ite;
-    if (ite != 0) return HQ_OK;
-    // before the first iteration: the initial population's errors and its best are the new evaluation's
-    const int rc = s->driver ? s->driver->rerank() : device_search_rerank(s);
-    search_commit(s, rc, 1);
-    if (rc) s->ordered = was, s->ord = old;
-    return rc;
+    // (off: the plain pass itself, and nothing changes unless the ordered cost is the one in force)
+    const Ordered* old = std::get_if<Ordered>(&s->rendering);
+    const bool same = on ? old && amp[0] == old->amp[0] && amp[1] == old->amp[1] && amp[2] == old->amp[2] : !old;
+    return set_rendering(s, same, on ? Rendering{Ordered{{amp[0], amp[1], amp[2]}}} : Rendering{Plain{}});
 }
 
 int hq_search_set_dot(hq_search* s, const hq_dot_classes* cls, float strength) {
@@ -642,34 +697,21 @@ int hq_search_set_dot(hq_search* s, const hq_dot_classes* cls, float strength) {
     if (cls) m = *cls;
     else hq_dot_preset(HQ_DOT_KNUTH8, &m);
     if (on) {
-        if (s->every > 0 || s->repair_every > 0)
+        if (s->moves[kLloyd].every > 0 || s->moves[kRepair].every > 0)
             return fail(c, HQ_ERR_UNSUPPORTED, "a search with hybrid or repair iterations: no dot-diffused cost");
-        if (s->descend_every > 0)
+        if (s->moves[kDescend].every > 0)
             return fail(c, HQ_ERR_UNSUPPORTED, "a search with descent iterations: the dot-diffused cost has no "
                                                "assign-only pass");
-        if (s->ordered) return fail(c, HQ_ERR_UNSUPPORTED, "a search under the ordered cost: one rendering per search");
+        if (std::holds_alternative<Ordered>(s->rendering))
+            return fail(c, HQ_ERR_UNSUPPORTED, "a search under the ordered cost: one rendering per search");
         if (int rc = assign_space_excludes(c, "hq_search_set_dot")) return rc;
         if (int rc = dot_search_scope(c, s->K)) return rc;
     }
+    // (off: the plain pass itself, the matrix stays, and nothing changes unless the dot-diffused cost is in force)
+    const Dot* old = std::get_if<Dot>(&s->rendering);
     const bool same_matrix = s->dot_cls.n == m.n && !std::memcmp(s->dot_cls.cls, m.cls, sizeof(int32_t) * m.n * m.n);
-    if (on == s->dot && (!on || (strength == s->dot_strength && same_matrix))) return HQ_OK;  // (nothing changes)
-    const bool was = s->dot;
-    const float old_strength = s->dot_strength;
-    const hq_dot_classes old_cls = s->dot_cls;
-    s->dot = on;
-    s->dot_strength = on ? strength : 0.f;  // (off: the plain pass itself)
-    if (on) {
-        std::memset(&s->dot_cls, 0, sizeof s->dot_cls);
-        s->dot_cls.n = m.n;
-        std::memcpy(s->dot_cls.cls, m.cls, sizeof(int32_t) * m.n * m.n);
-    }
-    const int ite = s->driver ? s->driver->iteration() : s->ite;
-    if (ite != 0) return HQ_OK;
-    // before the first iteration: the initial population's errors and its best are the new evaluation's
-    const int rc = s->driver ? s->driver->rerank() : device_search_rerank(s);
-    search_commit(s, rc, 1);
-    if (rc) s->dot = was, s->dot_strength = old_strength, s->dot_cls = old_cls;
-    return rc;
+    const bool same = on ? old && strength == old->strength && same_matrix : !old;
+    return set_rendering(s, same, on ? Rendering{Dot{strength, 0, 0}} : Rendering{Plain{}}, on ? &m : nullptr);
 }
 
 int hq_search_best(const hq_search* s, float* colors, double* best_error, int* iteration) {

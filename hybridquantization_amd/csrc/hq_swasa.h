@@ -63,8 +63,11 @@ class Swasa {
 bool population_in_range(const float* population, int P, int K);
 
 using PopulationEval = std::function<int(const float* palettes, int P, int K, double* costs)>;
-// The k-means move of a hybrid iteration: updates the candidates in place.
+// A move of an iteration: updates the candidates in place.
 using PopulationRefine = std::function<int(float* palettes, int P, int K)>;
+// The moves a search knows, in the order an iteration applies them before its evaluation:
+// k-means (a hybrid iteration), repair of unused colours, gradient descent.
+enum Move { kLloyd, kRepair, kDescend, kMoves };
 
 // IM:383-591 as a resumable state machine.
 class SearchDriver {
@@ -79,24 +82,17 @@ class SearchDriver {
     // initial population evaluated and ranked again (IM:490-493); no draws.  HQ_ERR_STATE
     // once an iteration has run.
     int rerank();
-    // Hybrid iterations (libhq's addition): with every > 0 and a refine step,
-    // the candidates of iteration ite (1-based, counted across run calls) with
-    // ite % every == 0 go through `refine` between their generation and their
-    // evaluation.  Applies to the iterations that follow.
-    void set_refine(PopulationRefine refine) { refine_ = std::move(refine); }
-    void set_every(int every) { every_ = every; }
-    // Repair iterations (libhq's addition), the same way with a period of their own:
-    // `repair` runs after `refine` when an iteration is both.
-    void set_repair(PopulationRefine repair) { repair_ = std::move(repair); }
-    void set_repair_every(int every) { repair_every_ = every; }
-    // Descent iterations (libhq's addition), the same way with a period of their own:
-    // `descend` runs last, after `refine` and `repair` when an iteration is those too.
-    void set_descend(PopulationRefine descend) { descend_ = std::move(descend); }
-    void set_descend_every(int every) { descend_every_ = every; }
+    // The moves (libhq's addition): with every > 0 and a callback, the candidates of
+    // iteration ite (1-based, counted across run calls) with ite % every == 0 go through
+    // move `m` between their generation and their evaluation; an iteration that several
+    // moves claim applies them in Move's order, the finest last.  Applies to the
+    // iterations that follow.
+    void set_move(Move m, PopulationRefine apply) { moves_[m].apply = std::move(apply); }
+    void set_every(Move m, int every) { moves_[m].every = every; }
     // Fixed colours (libhq's addition, hq_set_fixed_colors' semantics), set before start():
     // the first n colours of every member are `colors` ([n][4], .w stored as 0; null: as the
     // population or the draws have them) and no iteration changes them -- their draws are
-    // made and discarded, and they are put back after `refine` and `repair` return.
+    // made and discarded, and they are put back after every move returns.
     void set_fixed(int n, const float* colors) {
         nfixed_ = n;
         fixed_.clear();
@@ -117,12 +113,7 @@ class SearchDriver {
     Swasa sw_;
     int K_, P_;
     PopulationEval eval_;
-    PopulationRefine refine_;
-    int every_ = 0;
-    PopulationRefine repair_;
-    int repair_every_ = 0;
-    PopulationRefine descend_;
-    int descend_every_ = 0;
+    struct { PopulationRefine apply; int every = 0; } moves_[kMoves];
     int nfixed_ = 0;
     std::vector<float> fixed_;              // [nfixed][4], or empty
     std::vector<float> colors_, current_;   // [P][4K]
