@@ -20,11 +20,13 @@ from __future__ import annotations
 
 import ctypes as C
 from collections import namedtuple
+from contextlib import contextmanager
 
 import numpy as np
 
 from . import _lib
 from ._lib import HQUnavailable, check, dptr, fptr, iptr, load
+from .search import POLISHES, asked, run_search
 from .swasa import fixed_colors, initial_population
 
 
@@ -917,8 +919,128 @@ class ImageManipulation:
         space = None if assignSpace is None else self.checkAssignSpace(
             assignSpace, dither=dither, ditherSearch=ditherSearch, ordered=ordered, orderedSearch=orderedSearch,
             dot=dot, dotSearch=dotSearch)
-        ctx = self._require()
+        self._require()
         fx = None if fixed is None else np.ascontiguousarray(fixed_colors(fixed, int(nbOfColors)))
+        sw, K = simulatedAnnealing, int(nbOfColors)
+        moves = dict(lloydEvery=lloydEvery, repairEvery=repairEvery, descendEvery=descendEvery, lloydSteps=lloydSteps,
+                     repairSteps=repairSteps, descendSteps=descendSteps, repairMoves=repairMoves, delta=sw.delta,
+                     descendRate=DESCEND_RATE if descendRate is None else descendRate)
+        with self._heldForCall(fx, space):
+            if mask is not None and weights is not None:
+                raise ValueError("mask and weights: one piece of state, give one of them")
+            for given, noun, adj in ((mask, "mask", "masked"), (weights, "weights", "weighted")):
+                if given is not None and (int(repairEvery) != 0 or int(repairSteps) != 0):
+                    raise ValueError(f"{noun} with repairEvery or repairSteps: no {adj} error statistic")
+            if int(descendSteps) != 0 and (mask is not None or weights is not None or ditherSearch or orderedSearch
+                                           or dotSearch):
+                raise ValueError("descendSteps with a mask, weights or a searched rendering: the gradient is the "
+                                 "plain cost's")
+            if int(descendEvery) != 0 and (mask is not None or weights is not None or ditherSearch or dotSearch):
+                raise ValueError("descendEvery with a mask, weights, ditherSearch or dotSearch: the gradient needs an "
+                                 "unmasked cost and an assign-only pass")
+            amp = None if ordered is None else self._amp3(ordered)
+            if orderedSearch and (amp is None or not np.any(amp != 0)):
+                raise ValueError("orderedSearch needs a non-zero ordered amplitude")
+            if orderedSearch and asked(moves, ("steps",)):
+                raise ValueError("orderedSearch with a k-means or repair polish")
+            dither = float(dither)
+            if ditherKernel is not None:
+                self._taps(ditherKernel)  # (a bad one raises before anything runs)
+            if not 0.0 <= dither <= 1.0:
+                raise ValueError(f"dither={dither!r}: a strength in [0, 1]")
+
+            def host_search_ok(flag, strength_name, strength):
+                """ditherSearch / dotSearch: its rendering is on, and no move or polish with it."""
+                if not strength > 0.0:
+                    raise ValueError(f"{flag} needs {strength_name} > 0")
+                if asked(moves):
+                    raise ValueError(f"{flag} with " + ", ".join(asked(moves)))
+
+            if ditherSearch:
+                host_search_ok("ditherSearch", "dither", dither)
+            dot = float(dot)
+            classes = None if dotClasses is None else self._classes(dotClasses)  # (a bad one raises here)
+            if not 0.0 <= dot <= 1.0:
+                raise ValueError(f"dot={dot!r}: a strength in [0, 1]")
+            if dot > 0.0 and (dither > 0.0 or amp is not None):
+                raise ValueError("dot with dither or ordered: one rendering")
+            if isinstance(dotSearch, str) and dotSearch != "device":
+                raise ValueError(f"dotSearch={dotSearch!r}: False, True or 'device'")
+            if dotSearch:
+                host_search_ok("dotSearch", "dot", dot)
+            dot_device = isinstance(dotSearch, str)  # hq_search_set_dot; True: the Python host loop
+            # the renderings asked for, in the order their final errors are reported, and the one the
+            # search itself optimises (None: the plain cost)
+            rendered = [_Rendering(*r) for on, *r in (
+                (dither > 0.0, "dither", self.ditherPopulation, dither, dict(kernel=ditherKernel), "bestErrorDithered",
+                 "Final error, dithered at strength %g : %.5f"),
+                (dot > 0.0, "dot", self.dotPopulation, dot, dict(classes=dotClasses), "bestErrorDot",
+                 "Final error, dot-diffused at strength %g : %.5f"),
+                (amp is not None, "ordered", self.orderedPopulation, amp, {}, "bestErrorOrdered",
+                 "Final error, ordered dither at amplitude %s : %.5f")) if on]
+            goal = "dot" if dotSearch else "dither" if ditherSearch else "ordered" if orderedSearch else None
+            searched = next((r for r in rendered if r.name == goal), None)
+            if not self.openCLFiltersReady:
+                self.updateOpenCLFilters(filters, absfilters)
+            # Always upload (IM:450-478 does too): an identity cache keyed on id() can
+            # match a new array that reuses a freed one's id, or miss an in-place edit,
+            # and the upload is small next to a 5000-iteration search.
+            self.setImage(inlinergbOriginal, inlineScielabOriginal, w, illuminant)
+            if mask is not None:
+                self.setMask(mask)
+            if weights is not None:
+                self.setWeights(weights)
+            params = sw.params()
+            if isinstance(init, str) and init == "kmeans++":
+                # P distinct starts (the fixed colours, which the context holds, in front of each)
+                init, _ = self.kmeansppSeed(params.population, K, sw.seed)
+            if isinstance(init, str):
+                if init != "mediancut":
+                    raise ValueError(f"init={init!r}: None, 'mediancut', 'kmeans++' or an array")
+                init = self.medianCutStart(K, initBits, fx)
+            start = None if init is None else initial_population(init, params.population, K)
+            total = params.imax if iterations is None else min(int(iterations), params.imax)
+            if ditherSearch or (dotSearch and not dot_device):
+                P = params.population
+                best, err, _ = sw.search_host(
+                    K, lambda ps: searched.population(ps.reshape(P, -1), sw.delta), iterations=total,
+                    initial=start, fixed=fx)
+                self.bestError = err
+                setattr(self, searched.error_attr, err)
+                self.iterations = total
+                if self.verbose:
+                    print("Final error : %.5f" % err)
+                return best
+            found = run_search(self, params, sw.seed, K, start, moves, total, stop, seeded=start is not None,
+                               ordered=amp if orderedSearch else None, dot=(classes, dot) if dot_device else None)
+            if found.seed is not None:
+                self.seedColors, self.seedError = found.seed
+            best, self.bestError, self.iterations = found.best, found.error, found.iterations
+            if self.verbose:
+                print("Final error : %.5f" % self.bestError)  # IM:589
+            if dot_device:  # one evaluation of the returned palette: bestError and bestErrorDot are that cost
+                self.bestError = float(searched.population(best.reshape(1, -1), sw.delta)[0])
+            polishes = [mv for mv in POLISHES if int(moves[mv.steps]) > 0]
+            if polishes:
+                self.bestErrorSA = self.bestError
+            for mv in polishes:
+                pal, costs, _ = getattr(self, mv.polish)(best.reshape(1, -1), int(moves[mv.steps]),
+                                                         *[moves[name] for name in mv.polish_args])
+                best, self.bestError = pal[0], float(costs[0])
+                if self.verbose:
+                    print("Final error after %d %s steps : %.5f" % (int(moves[mv.steps]), mv.noun, self.bestError))
+            for r in rendered:  # (the searched one, here the ordered: bestError is already its cost)
+                err = self.bestError if r is searched else float(r.population(best.reshape(1, -1), sw.delta)[0])
+                setattr(self, r.error_attr, err)
+                if self.verbose:
+                    print(r.verbose % (np.asarray(r.parameter).tolist(), err))
+            return best
+
+    @contextmanager
+    def _heldForCall(self, fx, space=None):
+        """One call's fixed colours ``fx`` ((n, 4), or None: whatever the context holds applies, as to
+        any search) and option "assign_space" ``space`` (or None) set on the context for the block, and
+        what it held before put back on every way out."""
         before = None if fx is None else self.fixedColors()
         space_before = self._assign_space
         try:
@@ -926,192 +1048,26 @@ class ImageManipulation:
                 self.setFixedColors(fx)
             if space is not None:
                 self.setOption("assign_space", space)
-            return self._findBestQuantization(
-                inlinergbOriginal, inlineScielabOriginal, w, nbOfColors, simulatedAnnealing, filters, absfilters,
-                illuminant, iterations, stop, lloydSteps, lloydEvery, init, initBits, repairEvery, repairMoves,
-                repairSteps, dither, ditherSearch, ordered, orderedSearch, mask, weights, fx, ditherKernel,
-                dot, dotSearch, dotClasses, descendSteps=descendSteps,
-                descendRate=DESCEND_RATE if descendRate is None else descendRate, descendEvery=descendEvery)
+            yield
         finally:
             if space is not None:
                 self.setOption("assign_space", space_before)
             if before is not None:
                 self.setFixedColors(before)
 
-    def _findBestQuantization(self, inlinergbOriginal, inlineScielabOriginal, w, nbOfColors, simulatedAnnealing,
-                              filters, absfilters, illuminant, iterations, stop, lloydSteps, lloydEvery, init,
-                              initBits, repairEvery, repairMoves, repairSteps, dither, ditherSearch, ordered,
-                              orderedSearch, mask, weights, fx, ditherKernel=None, dot=0.0, dotSearch=False,
-                              dotClasses=None, descendSteps=0, descendRate=None, descendEvery=0):
-        """findBestQuantization's body; fx: the call's fixed colours (n, 4), already set on the
-        context, or None (then whatever the context holds applies, as to any search)."""
-        ctx = self._require()
-        nfx = 0 if fx is None else fx.shape[0]
-        if mask is not None and weights is not None:
-            raise ValueError("mask and weights: one piece of state, give one of them")
-        for given, noun, adj in ((mask, "mask", "masked"), (weights, "weights", "weighted")):
-            if given is not None and (int(repairEvery) != 0 or int(repairSteps) != 0):
-                raise ValueError(f"{noun} with repairEvery or repairSteps: no {adj} error statistic")
-        if int(descendSteps) != 0 and (mask is not None or weights is not None or ditherSearch or orderedSearch
-                                       or dotSearch):
-            raise ValueError("descendSteps with a mask, weights or a searched rendering: the gradient is the "
-                             "plain cost's")
-        if int(descendEvery) != 0 and (mask is not None or weights is not None or ditherSearch or dotSearch):
-            raise ValueError("descendEvery with a mask, weights, ditherSearch or dotSearch: the gradient needs an "
-                             "unmasked cost and an assign-only pass")
-        amp = None if ordered is None else self._amp3(ordered)
-        if orderedSearch and (amp is None or not np.any(amp != 0)):
-            raise ValueError("orderedSearch needs a non-zero ordered amplitude")
-        if orderedSearch and (int(lloydSteps) != 0 or int(repairSteps) != 0):
-            raise ValueError("orderedSearch with a k-means or repair polish")
-        dither = float(dither)
-        if ditherKernel is not None:
-            self._taps(ditherKernel)  # (a bad one raises before anything runs)
-        if not 0.0 <= dither <= 1.0:
-            raise ValueError(f"dither={dither!r}: a strength in [0, 1]")
-        moves = dict(lloydEvery=lloydEvery, repairEvery=repairEvery, lloydSteps=lloydSteps, repairSteps=repairSteps)
-
-        def host_search_ok(flag, strength_name, strength):
-            """ditherSearch / dotSearch: its rendering is on, and no k-means or repair move with it."""
-            if not strength > 0.0:
-                raise ValueError(f"{flag} needs {strength_name} > 0")
-            if any(int(v) != 0 for v in moves.values()):
-                raise ValueError(f"{flag} with " + ", ".join(k for k, v in moves.items() if int(v) != 0))
-
-        if ditherSearch:
-            host_search_ok("ditherSearch", "dither", dither)
-        dot = float(dot)
-        if dotClasses is not None:
-            self._classes(dotClasses)  # (a bad one raises before anything runs)
-        if not 0.0 <= dot <= 1.0:
-            raise ValueError(f"dot={dot!r}: a strength in [0, 1]")
-        if dot > 0.0 and (dither > 0.0 or amp is not None):
-            raise ValueError("dot with dither or ordered: one rendering")
-        if isinstance(dotSearch, str) and dotSearch != "device":
-            raise ValueError(f"dotSearch={dotSearch!r}: False, True or 'device'")
-        if dotSearch:
-            host_search_ok("dotSearch", "dot", dot)
-        dot_device = isinstance(dotSearch, str)  # hq_search_set_dot; True: the Python host loop
-        # the renderings asked for, in the order their final errors are reported, and the one the
-        # search itself optimises (None: the plain cost)
-        sw = simulatedAnnealing
-        rendered = [_Rendering(*r) for on, *r in (
-            (dither > 0.0, "dither", self.ditherPopulation, dither, dict(kernel=ditherKernel), "bestErrorDithered",
-             "Final error, dithered at strength %g : %.5f"),
-            (dot > 0.0, "dot", self.dotPopulation, dot, dict(classes=dotClasses), "bestErrorDot",
-             "Final error, dot-diffused at strength %g : %.5f"),
-            (amp is not None, "ordered", self.orderedPopulation, amp, {}, "bestErrorOrdered",
-             "Final error, ordered dither at amplitude %s : %.5f")) if on]
-        goal = "dot" if dotSearch else "dither" if ditherSearch else "ordered" if orderedSearch else None
-        searched = next((r for r in rendered if r.name == goal), None)
-        if not self.openCLFiltersReady:
-            self.updateOpenCLFilters(filters, absfilters)
-        # Always upload (IM:450-478 does too): an identity cache keyed on id() can
-        # match a new array that reuses a freed one's id, or miss an in-place edit,
-        # and the upload is small next to a 5000-iteration search.
-        self.setImage(inlinergbOriginal, inlineScielabOriginal, w, illuminant)
-        if mask is not None:
-            self.setMask(mask)
-        if weights is not None:
-            self.setWeights(weights)
-        params = sw.params()
-        handle = C.c_void_p()
-        K = int(nbOfColors)
-        if isinstance(init, str) and init == "kmeans++":
-            # P distinct starts (the fixed colours, which the context holds, in front of each)
-            init, _ = self.kmeansppSeed(params.population, K, sw.seed)
-        if isinstance(init, str):
-            if init != "mediancut":
-                raise ValueError(f"init={init!r}: None, 'mediancut', 'kmeans++' or an array")
-            # under fixed colours: the cut makes the K - n free ones, the fixed ones go in front
-            init = np.zeros(4 * K, np.float32)
-            init[:4 * nfx] = 0.0 if fx is None else fx.reshape(-1)
-            if K - nfx > 0:
-                cells, den = self.colorHistogram(int(initBits))
-                init[4 * nfx:], _ = self.medianCut(cells, int(initBits), den, K - nfx)
-        total = params.imax if iterations is None else min(int(iterations), params.imax)
-        if ditherSearch or (dotSearch and not dot_device):
-            P = params.population
-            best, err, _ = sw.search_host(
-                K, lambda ps: searched.population(ps.reshape(P, -1), sw.delta), iterations=total,
-                initial=None if init is None else initial_population(init, P, K), fixed=fx)
-            self.bestError = err
-            setattr(self, searched.error_attr, err)
-            self.iterations = total
-            if self.verbose:
-                print("Final error : %.5f" % err)
-            return best
-        if init is None:
-            check(self._lib.hq_search_create(ctx, C.byref(params), K, sw.seed, C.byref(handle)), ctx)
-        else:
-            pop = initial_population(init, params.population, K)
-            check(self._lib.hq_search_create_from(ctx, C.byref(params), K, sw.seed, fptr(pop),
-                                                  C.byref(handle)), ctx)
-        try:
-            if init is not None:
-                seed = np.zeros(4 * K, np.float32)
-                seed_err = C.c_double()
-                check(self._lib.hq_search_best(handle, fptr(seed), C.byref(seed_err), None), ctx)
-                self.seedColors, self.seedError = seed, seed_err.value
-            if orderedSearch:
-                check(self._lib.hq_search_set_ordered(handle, fptr(amp)), ctx)
-            if dot_device:
-                classes = None if dotClasses is None else C.byref(self._classes(dotClasses))
-                check(self._lib.hq_search_set_dot(handle, classes, dot), ctx)
-            if int(lloydEvery) != 0:
-                check(self._lib.hq_search_set_lloyd(handle, int(lloydEvery)), ctx)
-            if int(repairEvery) != 0:
-                check(self._lib.hq_search_set_repair(handle, int(repairEvery), int(repairMoves)), ctx)
-            if int(descendEvery) != 0:
-                check(self._lib.hq_search_set_descend(handle, int(descendEvery), float(descendRate)), ctx)
-            done = 0
-            while done < total:
-                if stop is not None and stop():
-                    break
-                ran = C.c_int()
-                chunk = min(64, total - done)
-                check(self._lib.hq_search_run(handle, chunk, C.byref(ran)), ctx)
-                done += ran.value
-                if ran.value == 0:
-                    break
-            best = np.zeros(4 * int(nbOfColors), np.float32)
-            err = C.c_double()
-            it = C.c_int()
-            check(self._lib.hq_search_best(handle, fptr(best), C.byref(err), C.byref(it)), ctx)
-            self.bestError = err.value
-            self.iterations = it.value
-            if self.verbose:
-                print("Final error : %.5f" % err.value)  # IM:589
-        finally:
-            self._lib.hq_search_destroy(handle)
-        if dot_device:  # one evaluation of the returned palette: bestError and bestErrorDot are that cost
-            self.bestError = float(searched.population(best.reshape(1, -1), sw.delta)[0])
-        if int(repairSteps) > 0 or int(lloydSteps) > 0 or int(descendSteps) > 0:
-            self.bestErrorSA = self.bestError
-        if int(repairSteps) > 0:
-            pal, costs, _ = self.repairPopulation(best.reshape(1, -1), int(repairSteps), sw.delta,
-                                                  int(repairMoves), keep_best=True)
-            best, self.bestError = pal[0], float(costs[0])
-            if self.verbose:
-                print("Final error after %d repair steps : %.5f" % (int(repairSteps), self.bestError))
-        if int(lloydSteps) > 0:
-            pal, costs, _ = self.refinePopulation(best.reshape(1, -1), int(lloydSteps), sw.delta,
-                                                  keep_best=True)
-            best, self.bestError = pal[0], float(costs[0])
-            if self.verbose:
-                print("Final error after %d k-means steps : %.5f" % (int(lloydSteps), self.bestError))
-        if int(descendSteps) > 0:
-            pal, costs, _ = self.descendPopulation(best.reshape(1, -1), int(descendSteps), float(descendRate),
-                                                   sw.delta)
-            best, self.bestError = pal[0], float(costs[0])
-            if self.verbose:
-                print("Final error after %d descent steps : %.5f" % (int(descendSteps), self.bestError))
-        for r in rendered:  # (the searched one, here the ordered: bestError is already its cost)
-            err = self.bestError if r is searched else float(r.population(best.reshape(1, -1), sw.delta)[0])
-            setattr(self, r.error_attr, err)
-            if self.verbose:
-                print(r.verbose % (np.asarray(r.parameter).tolist(), err))
-        return best
+    def medianCutStart(self, K: int, bits: int = 5, fixed=None):
+        """``init="mediancut"``: the palette float32[4K] every member of a population starts from -- the
+        fixed colours ``fixed`` ((n, 4), or None) in front, then the median cut of the image's colour
+        histogram at ``bits`` bits per channel to the K - n free ones (n = K: nothing is cut).  The cut
+        does not know about the fixed colours."""
+        n = 0 if fixed is None else fixed.shape[0]
+        start = np.zeros(4 * K, np.float32)
+        if n:
+            start[:4 * n] = fixed.reshape(-1)
+        if K - n > 0:
+            cells, den = self.colorHistogram(int(bits))
+            start[4 * n:], _ = self.medianCut(cells, int(bits), den, K - n)
+        return start
 
     # IM:770
     def quantize(self, inlineImageRGB, colors):

@@ -18,14 +18,12 @@ hq_search_run.
 
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
-from ._lib import check, fptr
 from .image_manipulation import DESCEND_RATE, ImageManipulation
 from .scielab_processor import ScielabProcessor, Whitepoint, design_filters
+from .search import run_search
 from .swasa import fixed_colors, initial_population
 
 
@@ -54,48 +52,6 @@ def level_dpi(dpi, factor):
     """The dpi a level's filters are designed at: the image reduced by ``factor`` shows
     ``factor`` times fewer pixels per inch at the same viewing distance."""
     return max(1, round(int(dpi) / int(factor)))
-
-
-def _run_level(m, sw, K, iterations, population, t0, lloydEvery, repairEvery, repairMoves, stop, descendEvery=0,
-               descendRate=DESCEND_RATE):
-    """One level's search on the context ``m`` (image, filters, weights and fixed colours in
-    place): ``sw``'s parameters with imax = ``iterations`` (and ``t0``, when given), started
-    from ``population`` ((P, 4K), or None: the reference's random start) and run to its end.
-    -> (best colours, best error, (best colours, error) at creation, final population (P, 4K),
-    iterations run)."""
-    lib, ctx = m._lib, m.ctx
-    params = sw.params()
-    params.imax = max(int(iterations), 1)  # (a level of 0 iterations evaluates its seed and hands it on)
-    if t0 is not None:
-        params.t0 = float(np.float32(t0))
-    handle = C.c_void_p()
-    check(lib.hq_search_create_from(ctx, C.byref(params), K, sw.seed, None if population is None else fptr(population),
-                                    C.byref(handle)), ctx)
-    try:
-        seed, seed_err = np.zeros(4 * K, np.float32), C.c_double()
-        check(lib.hq_search_best(handle, fptr(seed), C.byref(seed_err), None), ctx)
-        if int(lloydEvery) != 0:
-            check(lib.hq_search_set_lloyd(handle, int(lloydEvery)), ctx)
-        if int(repairEvery) != 0:
-            check(lib.hq_search_set_repair(handle, int(repairEvery), int(repairMoves)), ctx)
-        if int(descendEvery) != 0:
-            check(lib.hq_search_set_descend(handle, int(descendEvery), float(descendRate)), ctx)
-        done = 0
-        while done < int(iterations):
-            if stop is not None and stop():
-                break
-            ran = C.c_int()
-            check(lib.hq_search_run(handle, min(64, int(iterations) - done), C.byref(ran)), ctx)
-            done += ran.value
-            if ran.value == 0:
-                break
-        best = np.zeros(4 * K, np.float32)
-        err = C.c_double()
-        check(lib.hq_search_best(handle, fptr(best), C.byref(err), None), ctx)
-        pop, _ = m.searchPopulation(handle, params.population, K)
-    finally:
-        lib.hq_search_destroy(handle)
-    return best, err.value, (seed, seed_err.value), pop, done
 
 
 def pyramidSearch(ip, inlineRGB, w, K, swasa, dpi=72, viewingDistance=45.0, whitepoint=Whitepoint.D65,
@@ -150,7 +106,6 @@ def pyramidSearch(ip, inlineRGB, w, K, swasa, dpi=72, viewingDistance=45.0, whit
     if isinstance(init, str) and init != "mediancut":
         raise ValueError(f"init={init!r}: None, 'mediancut' or an array")
     fx = None if fixed is None else np.ascontiguousarray(fixed_colors(fixed, K))
-    nfx = 0 if fx is None else fx.shape[0]
     for f, _ in lv:  # every level's geometry against its own filters, on the host
         try:
             half = design_filters(level_dpi(dpi, f), viewingDistance, whitepoint)[0].shape[0] * 4 // 8
@@ -162,12 +117,11 @@ def pyramidSearch(ip, inlineRGB, w, K, swasa, dpi=72, viewingDistance=45.0, whit
             raise ValueError(f"level of factor {f}: its {rw} x {rh} image is smaller than its filters' halfSize {half} "
                              f"(designed at {level_dpi(dpi, f)} dpi)")
     region = mask if mask is not None else weights
+    moves = dict(lloydEvery=lloydEvery, repairEvery=repairEvery, repairMoves=repairMoves, descendEvery=descendEvery,
+                 descendRate=DESCEND_RATE if descendRate is None else descendRate)
 
     sp = ScielabProcessor(dpi, viewingDistance, whitepoint, None, ip)
-    before = None if fx is None else ip.fixedColors()
-    try:
-        if fx is not None:
-            ip.setFixedColors(fx)
+    with ip._heldForCall(fx):
         held = ip.fixedColors()  # (fixed's, or what the context held already: every level gets the same)
         ip.setImage(rgb, None, w, sp.illuminant)
         if mask is not None:
@@ -187,29 +141,27 @@ def pyramidSearch(ip, inlineRGB, w, K, swasa, dpi=72, viewingDistance=45.0, whit
                         m.setWeights(ImageManipulation.reduceWeights(region, w, f, is_mask=mask is not None))
                     if held.shape[0]:
                         m.setFixedColors(held)
-                if i == 0 and init is not None:
-                    start = init
-                    if isinstance(init, str):  # the median cut of this level's image, the fixed colours in front
-                        start = np.zeros(4 * K, np.float32)
-                        start[:4 * nfx] = 0.0 if fx is None else fx.reshape(-1)
-                        if K - nfx > 0:
-                            cells, den = m.colorHistogram(int(initBits))
-                            start[4 * nfx:], _ = m.medianCut(cells, int(initBits), den, K - nfx)
+                if i == 0 and init is not None:  # (a string: the median cut of this level's image)
+                    start = m.medianCutStart(K, initBits, fx) if isinstance(init, str) else init
                     population = initial_population(start, swasa.population, K)
-                best, err, (seed, seed_err), population, done = _run_level(
-                    m, swasa, K, n, population, fineT0 if i > 0 else None, lloydEvery, repairEvery, repairMoves, stop,
-                    descendEvery, DESCEND_RATE if descendRate is None else descendRate)
-                errors.append(err)
+                # the level's search: swasa's parameters with imax = n (a level of 0 iterations evaluates
+                # its seed and hands it on) and, on the levels after the coarsest, fineT0
+                params = swasa.params()
+                params.imax = max(n, 1)
+                if i > 0 and fineT0 is not None:
+                    params.t0 = float(np.float32(fineT0))
+                found = run_search(m, params, swasa.seed, K, population, moves, n, stop, seeded=True,
+                                   want_population=True)
+                population = found.population
+                errors.append(found.error)
                 if ip.verbose:
-                    print("Level 1/%d (%d x %d): %d iterations, error %.5f -> %.5f" % (f, m.w, m.h, done, seed_err, err))
+                    print("Level 1/%d (%d x %d): %d iterations, error %.5f -> %.5f"
+                          % (f, m.w, m.h, found.ran, found.seed[1], found.error))
             finally:
                 if m is not ip:
                     m.close()
-    finally:
-        if before is not None:
-            ip.setFixedColors(before)
-    ip.bestError, ip.levelErrors, ip.iterations = err, errors, done
-    ip.seedColors, ip.seedError = seed, seed_err
+    ip.bestError, ip.levelErrors, ip.iterations = found.error, errors, found.ran
+    ip.seedColors, ip.seedError = found.seed
     if ip.verbose:
-        print("Final error : %.5f" % err)
-    return best
+        print("Final error : %.5f" % found.error)
+    return found.best

@@ -140,21 +140,16 @@ def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
             best = pyramidSearch(ip, inline_rgb, w, nbOfColors, swasa, dpi, viewingDistance, whitepoint,
                                  levels=pyramid, mask=mask, weights=weights, fixed=fixed,
                                  descendEvery=descendEvery, init=init)
-            q = (ip.quantizeDotDiffused(best, dot, classes=dotClasses) if float(dot) > 0.0 else
-                 ip.quantizeOrdered(best, ordered) if ordered is not None else
-                 ip.quantizeDithered(best, dither, kernel=ditherKernel) if float(dither) > 0.0 else
-                 ip.quantize(inline_rgb, best))
-            return np.stack(makeChannels(q)), best, ip.bestError
-        sp = ScielabProcessor(dpi, viewingDistance, whitepoint, None, ip)
-        sc_img = sp.sRGBToScielab(image, w)
-        best = sp.bestColors(inline_rgb, sc_img, w, nbOfColors, swasa, iterations=iterations, dither=dither,
-                             ditherKernel=ditherKernel, ordered=ordered, mask=mask, weights=weights, fixed=fixed,
-                             dot=dot, dotClasses=dotClasses, dotSearch=dotSearch, assignSpace=assignSpace,
-                             descendEvery=descendEvery, init=init)
-        if lab:
-            q = ip.quantizeAssigned(best, assignSpace)
-            return np.stack(makeChannels(q)), best, ip.bestError
-        q = (ip.quantizeDotDiffused(best, dot, classes=dotClasses) if float(dot) > 0.0 else
+        else:
+            sp = ScielabProcessor(dpi, viewingDistance, whitepoint, None, ip)
+            sc_img = sp.sRGBToScielab(image, w)
+            best = sp.bestColors(inline_rgb, sc_img, w, nbOfColors, swasa, iterations=iterations, dither=dither,
+                                 ditherKernel=ditherKernel, ordered=ordered, mask=mask, weights=weights, fixed=fixed,
+                                 dot=dot, dotClasses=dotClasses, dotSearch=dotSearch, assignSpace=assignSpace,
+                                 descendEvery=descendEvery, init=init)
+        # the returned rendering ("lab" with another rendering or a pyramid was refused above)
+        q = (ip.quantizeAssigned(best, assignSpace) if lab else
+             ip.quantizeDotDiffused(best, dot, classes=dotClasses) if float(dot) > 0.0 else
              ip.quantizeOrdered(best, ordered) if ordered is not None else
              ip.quantizeDithered(best, dither, kernel=ditherKernel) if float(dither) > 0.0 else
              ip.quantize(inline_rgb, best))
