@@ -122,6 +122,7 @@ SIGNATURES = {
     "hq_refine_population": (C.c_int, [_ctx, _f, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _d,
                                        _i32, _d]),
     "hq_cluster_errors": (C.c_int, [_ctx, C.c_int, C.c_int, _i64, _f]),
+    "hq_error_stats": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_float, _i64, _i64, _f, _i64]),
     "hq_cost_gradient": (C.c_int, [_ctx, C.c_int, C.c_int, _d]),
     "hq_descend_population": (C.c_int, [_ctx, _f, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _d, _i32, _d]),
     "hq_descend_move": (C.c_int, [_ctx, _f, C.c_int, C.c_int, C.c_float, _f]),

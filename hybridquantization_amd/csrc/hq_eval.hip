@@ -7,6 +7,7 @@
 
 #include "hq_diffuse.h"
 #include "hq_dot.h"
+#include "hq_errstats.h"
 #include "hq_grad.h"
 #include "hq_runtime.h"
 
@@ -903,6 +904,65 @@ int color_histogram(hq_ctx* c, int bits, int64_t* out, int64_t* den) {
     return HQ_OK;
 }
 
+// hq_get_pixel_errors' and hq_error_stats' state rule: option "pixel_err" still on, palette p of
+// the last evaluation on this device (*local: its place), its error image stored and still vouched for.
+int check_error_image(hq_ctx* c, int p, int* local) {
+    if (!c->pixel_err) return fail(c, HQ_ERR_STATE, "option pixel_err is off");
+    if (int rc = check_local_palette(c, p, local)) return rc;
+    if (!c->res.pixerr_ok())
+        return fail(c, HQ_ERR_STATE, "no error image of the last evaluation: pixel_err was set after it, or a search "
+                                     "has run since");
+    return HQ_OK;
+}
+
+// hq_error_stats into hist ([P][nbins]) and, where asked for, nonfinite, max_de and max_pixel ([P]
+// each); nothing is written unless HQ_OK.  The error image and the map are read, a table of its own
+// is written: the index images, the error image, the counter sets, d_sums and d_errstat stay what
+// they are.
+int error_stats(hq_ctx* c, int P, int nbins, float top, int64_t* hist, int64_t* nonfinite, float* max_de,
+                int64_t* max_pixel) {
+    if (c->slice_ranks > 1 || c->psplit)
+        return fail(c, HQ_ERR_UNSUPPORTED, "hq_error_stats on a palette slice (options slice_ranks, palette_split)");
+    int local = 0;
+    if (int rc = check_error_image(c, c->res.lo, &local)) return rc;
+    const Resident& r = c->res;
+    const Geom& g = c->g;
+    if (P != r.P) return fail(c, HQ_ERR_STATE, "P=%d: the last evaluation had P=%d", P, r.P);
+    if (r.n != r.P || c->d_pixerr.bytes < sizeof(float) * (size_t)P * (size_t)n_own(g))
+        return fail(c, HQ_ERR_UNSUPPORTED, "palette slice: this device holds %d of the %d error images", r.n, r.P);
+    if ((int64_t)g.W * g.H >= ((int64_t)1 << 32))
+        return fail(c, HQ_ERR_UNSUPPORTED, "image of 2^32 pixels or more: a position does not fit 32 bits");
+    const size_t nh = (size_t)P * nbins, n = nh + 2 * (size_t)P;
+    std::vector<int64_t> h;
+    int rc = run_table_kernel(c, c->d_errhist, n, kPErrstats, nullptr, h, [&] {
+        ErrStatsArgs a{};
+        a.err = c->d_pixerr.as<float>();
+        a.mask = c->mask_on ? c->d_maskq.as<uint8_t>() + own_first(g) : nullptr;
+        a.hist = c->d_errhist.as<unsigned long long>();
+        a.nonfinite = a.hist + nh;
+        a.key = a.nonfinite + P;
+        a.pitch = n_own(g);
+        a.n = (uint32_t)n_own(g);
+        a.pos0 = (uint32_t)((int64_t)g.r0 * g.W);
+        errstats_spans(a.n, P, (uint32_t)c->errstats_span, c->num_cu, &a.span, &a.nspans);
+        a.P = P;
+        a.nbins = nbins;
+        a.scale = (float)nbins / top;
+        a.weighted = c->mask_on && c->weights_on;
+        return launch_error_stats(a, c->stream);
+    });
+    if (rc) return rc;
+    std::memcpy(hist, h.data(), sizeof(int64_t) * nh);
+    for (int p = 0; p < P; ++p) {
+        const uint64_t key = (uint64_t)h[nh + P + p];
+        const uint32_t bits = (uint32_t)(key >> 32);
+        if (nonfinite) nonfinite[p] = h[nh + p];
+        if (max_de) std::memcpy(max_de + p, &bits, sizeof(float));
+        if (max_pixel) max_pixel[p] = key ? (int64_t)(0xffffffffu - (uint32_t)key) : -1;
+    }
+    return HQ_OK;
+}
+
 // IM:712 from the [P][1+K] rows in h_out: averageArray(error) + computePenalty(used).
 // After an all-reduce the used entries count the ranks using colour k; unused <=> 0.
 // partial_from_hout: the rows themselves, as a _partial call returns them.  (Both return HQ_OK:
@@ -1688,12 +1748,8 @@ int hq_get_indices32(hq_ctx* c, int p, uint32_t* idx) {
 
 int hq_get_pixel_errors(hq_ctx* c, int p, float* err) {
     if (!c || !err) return HQ_ERR_ARG;
-    if (!c->pixel_err) return fail(c, HQ_ERR_STATE, "option pixel_err is off");
-    int rc = check_local_palette(c, p, &p);
+    int rc = check_error_image(c, p, &p);
     if (rc) return rc;
-    if (!c->res.pixerr_ok())
-        return fail(c, HQ_ERR_STATE, "no error image of the last evaluation: pixel_err was set after it, or a search "
-                                     "has run since");
     if ((rc = bind(c))) return rc;
     const int64_t n = n_own(c->g);
     HIP_TRY(c, hipMemcpy(err, c->d_pixerr.as<float>() + (int64_t)p * n, sizeof(float) * n, hipMemcpyDeviceToHost));
@@ -1718,6 +1774,15 @@ int hq_cluster_errors(hq_ctx* c, int P, int K, int64_t* err, float* worst_rgb) {
     if (!err || !worst_rgb || P < 1 || K < 1) return fail(c, HQ_ERR_ARG, "bad err / worst_rgb / P=%d / K=%d", P, K);
     if (c->mask_on) return fail(c, HQ_ERR_UNSUPPORTED, "hq_cluster_errors under %s (%s)", mask_noun(c), mask_call(c));
     return cluster_errors(c, P, K, err, worst_rgb, false);
+}
+
+int hq_error_stats(hq_ctx* c, int P, int nbins, float top, int64_t* hist, int64_t* nonfinite, float* max_de,
+                   int64_t* max_pixel) {
+    if (!c) return HQ_ERR_ARG;
+    if (!hist || P < 1 || nbins < 1 || nbins > kErrStatsMaxBins || !std::isfinite(top) || !(top > 0.0f))
+        return fail(c, HQ_ERR_ARG, "bad hist / P=%d / nbins=%d (1 .. %d) / top=%g (finite, > 0)", P, nbins,
+                    kErrStatsMaxBins, (double)top);
+    return error_stats(c, P, nbins, top, hist, nonfinite, max_de, max_pixel);
 }
 
 int hq_refine_population(hq_ctx* c, float* palettes, int P, int K, int steps, float delta, int keep_best,

@@ -115,12 +115,12 @@ struct ProfSlot {
 enum Stage {
     kStGrid, kStAssign, kStCost, kStFinalize, kStSaStep, kStComm, kStCentroid, kStLloyd, kStHist, kStErrsum,
     kStReseed, kStDither, kStReduce, kStDot, kStCoords, kStGradPixel, kStGradAdjoint, kStDescend, kStKmppUpdate,
-    kStKmppPick, kStages
+    kStKmppPick, kStErrstats, kStages
 };
 inline constexpr const char* kStageNames[kStages] = {"grid", "assign", "cost", "finalize", "sa_step", "comm",
                                                      "centroid", "lloyd", "hist", "errsum", "reseed", "dither",
                                                      "reduce", "dot", "coords", "grad_pixel", "grad_adjoint",
-                                                     "descend", "kmpp_update", "kmpp_pick"};
+                                                     "descend", "kmpp_update", "kmpp_pick", "errstats"};
 
 // The start/stop event pairs of one evaluation (the context's EventSet) or of one
 // search iteration (kPairs pairs per iteration of a run in hq_search::pev).  A pass
@@ -144,6 +144,7 @@ enum Pair {
     kPDescGrid, kPDescAssign,              // descent iteration: the assign-only pass, a pair of its own (an iteration
     kPDescend,                             // may be hybrid too), the update kernel (hq_search_set_descend, hq_descend_move)
     kPKmppUpdate, kPKmppPick,              // hq_kmeanspp_seed: one round's update launches and its pick
+    kPErrstats,                            // hq_error_stats' kernel
     kPairs
 };
 // The stage each pair's time and launch count go to.
@@ -151,7 +152,7 @@ inline constexpr Stage kPairStage[kPairs] = {kStGrid, kStAssign, kStCost, kStFin
                                              kStDither, kStGrid, kStAssign, kStCentroid, kStLloyd, kStGrid,
                                              kStAssign, kStCost, kStErrsum, kStReseed, kStHist, kStReduce,
                                              kStDot, kStCoords, kStGradPixel, kStGradAdjoint, kStGrid, kStAssign,
-                                             kStDescend, kStKmppUpdate, kStKmppPick};
+                                             kStDescend, kStKmppUpdate, kStKmppPick, kStErrstats};
 
 // One evaluation's or iteration's events and which pairs it recorded (events of an
 // earlier call may sit in the other slots, so only recorded pairs are accumulated).
@@ -315,6 +316,8 @@ struct hq_ctx {
     int planar_ok = -1;
     hq::DevBuf d_hist;             // hq_color_histogram: [2^(3 bits)][4] int64 cells, then the range flag
     hq::DevBuf d_errstat, d_worst; // [P][K][4] u64 statistics, then the flag; [P][K] float4 worst pixels
+    // hq_error_stats (hq_errstats.hip): [P][nbins] u64 bins, [P] non-finite weights, [P] keys, back to back
+    hq::DevBuf d_errhist;
     // hq_kmeanspp_seed (hq_kmpp.hip): minD [P][N] u32; the spans' partials [P + 1][nspans] u64 (the last
     // row: the weights'); the centres' q [P][K] int4, the drawn colours [P][K] float4 and their pixels
     // [P][K] int64 back to back
@@ -417,6 +420,7 @@ struct hq_ctx {
     int dither_rows = 1024;  // hq_dither_population: rows per strip (option "dither_rows")
     int cent_span = 0;       // test option "cent_span": the sums kernel's pixels per workgroup (0: by the grid)
     int kmpp_span = 0;       // test option "kmpp_span": kmpp_update_kernel's pixels per workgroup (0: by the grid)
+    int errstats_span = 0;   // test option "errstats_span": errstats_kernel's pixels per workgroup (0: by the grid)
     int trim = 1;          // skip taps < 1e-9 of the peak of the narrow k1 filters
     bool trim_ok = false;  // set by hq_set_filters (the bucket's narrow-filter windows hold)
     bool pal_generic = false;  // this population needs the generic cost path (palette_fits_fast)

@@ -1039,6 +1039,9 @@ int hq_set_option(hq_ctx* c, const char* name, int value) {
     } else if (!std::strcmp(name, "kmpp_span")) {
         if (value < 0) return fail(c, HQ_ERR_ARG, "kmpp_span must be >= 0 (0 = auto)");
         c->kmpp_span = value;
+    } else if (!std::strcmp(name, "errstats_span")) {
+        if (value < 0) return fail(c, HQ_ERR_ARG, "errstats_span must be >= 0 (0 = auto)");
+        c->errstats_span = value;
     } else if (!std::strcmp(name, "grad_tiled")) {
         if (value < -1 || value > 1) return fail(c, HQ_ERR_ARG, "grad_tiled must be -1, 0 or 1");
         c->grad_tiled = value;

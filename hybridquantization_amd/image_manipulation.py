@@ -339,6 +339,35 @@ class ImageManipulation:
         check(self._lib.hq_cluster_errors(ctx, int(P), int(K), _lib.i64ptr(err), fptr(worst)), ctx)
         return err, worst
 
+    # the dE distribution of an evaluation: libhq's addition (hq_error_stats, no reference counterpart)
+    def errorStats(self, P: int, nbins: int = 256, top: float = 50.0):
+        """hq_error_stats of the P palettes of the last evaluation or rendering made with option
+        "pixel_err" 1: (hist int64 (P, nbins) over [0, top) with the last bin the overflow bin,
+        nonfinite int64 (P,), max_de float32 (P,), max_pixel int64 (P,) = y w + x in the full
+        image or -1); under weights every count is a sum of weights."""
+        ctx = self._require()
+        hist = np.zeros((int(P), max(int(nbins), 0)), np.int64)
+        nonfinite, max_pixel = np.zeros(int(P), np.int64), np.zeros(int(P), np.int64)
+        max_de = np.zeros(int(P), np.float32)
+        check(self._lib.hq_error_stats(ctx, int(P), int(nbins), float(top), _lib.i64ptr(hist), _lib.i64ptr(nonfinite),
+                                       fptr(max_de), _lib.i64ptr(max_pixel)), ctx)
+        return hist, nonfinite, max_de, max_pixel
+
+    @staticmethod
+    def errorQuantile(hist_row, top: float, q: float):
+        """The dE below which the share q of a histogram row's weight lies, to a bin: the upper edge
+        (b + 1) top / nbins of the first bin b at which the cumulative count reaches q times the
+        row's total.  In the overflow bin the edge is ``top``: a lower bound.  An empty row or q outside (0, 1] is a ValueError."""
+        row = [int(v) for v in np.asarray(hist_row).reshape(-1)]
+        total = sum(row)
+        if total <= 0 or not 0.0 < q <= 1.0:
+            raise ValueError("errorQuantile: an empty histogram row or q outside (0, 1]")
+        cum = 0
+        for b, v in enumerate(row):
+            cum += v
+            if cum >= q * total:
+                return (b + 1) * float(top) / len(row)
+
     @staticmethod
     def reseedUnused(err, worst, palettes, max_moves=-1, nfixed=0):
         """The repair rule of hq_reseed_unused: palettes (P, 4K) float32 with every unused

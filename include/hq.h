@@ -317,6 +317,52 @@ int hq_repair_population(hq_ctx *ctx, float *palettes, int P, int K, int steps, 
                          int max_moves, int keep_best, double *costs, int32_t *used,
                          double *trace);
 
+/* ---- the dE distribution of an evaluation: libhq's addition, no reference counterpart ----
+ * The cost is a mean, and two renderings with one mean can look very different: a
+ * dE of 3 everywhere is invisible, a few patches at 25 are not.  hq_error_stats
+ * reduces the error image on the device -- the one hq_get_pixel_errors would return
+ * for each of the P palettes of the last evaluation or rendering (plain, ordered,
+ * diffused, dot) -- to a histogram, the weight of the pixels without a usable dE and
+ * the worst pixel, over the owned rows (halo rows are not counted).
+ *
+ * The rule, operation by operation.  scale = (float)nbins / top, one fp32 division
+ * on the host.  A counted pixel with fp32 error e:
+ *   e a NaN, an infinity or below zero: adds to nonfinite[p] and to nothing else;
+ *   else t = e * scale, one fp32 multiply (nothing contracted into it), and the pixel
+ *   adds to hist[p*nbins + b], b = t >= (float)nbins ? nbins - 1 : (int)t.
+ * The last bin is the overflow bin.  (A scale that overflowed to infinity makes t a
+ * NaN at e = 0: the last bin.)
+ * What is counted, and by how much: without a map every owned pixel, by 1; under
+ * hq_set_mask the in-mask owned pixels, by 1; under hq_set_weights the pixels of
+ * non-zero weight, by their weight, in hist and in nonfinite alike.  A weight map
+ * of zeros and ones gives the mask's output bit for bit, and a masked-out pixel's
+ * NaN is not counted.
+ * max_de[p] = the largest finite e >= 0 among the counted pixels, max_pixel[p] = the
+ * lowest raster index y*w + x in the FULL image where it occurs; no such pixel:
+ * 0 and -1.  (One 64-bit integer maximum of (bits of e) << 32 | (2^32 - 1 - index),
+ * which is why a full image of 2^32 pixels or more is refused.)
+ * Everything returned is an exact integer or one pixel's own bits: two calls, and a
+ * palette alone or inside a population, give identical bytes.  Shards: the
+ * histograms and nonfinite of disjoint shards of one image add up to the whole
+ * image's (where the shards' stored dE are: hq_cluster_errors' note); merging the
+ * maxima -- the larger max_de, then the lower max_pixel -- is the caller's job.  A
+ * communicator of more than one rank changes nothing: every rank answers for its
+ * own rows, no collective is used.
+ * nonfinite, max_de and max_pixel may be NULL.  Nothing is written unless HQ_OK, and
+ * the evaluated population is not disturbed (hq_get_indices, hq_get_pixel_errors,
+ * hq_cluster_sums and hq_cluster_errors answer after it as before it).
+ * HQ_ERR_ARG: hist NULL, P < 1, nbins outside 1 .. 4096, top not finite or not
+ * > 0.  HQ_ERR_STATE: hq_get_pixel_errors' rule -- option "pixel_err" is off, no
+ * population evaluated on the current image and filters, that evaluation stored no
+ * error image, a search has run since -- or P is not that evaluation's.
+ * HQ_ERR_UNSUPPORTED: a palette slice ("slice_ranks" > 1, "palette_split"); a full
+ * image of 2^32 pixels or more.  Profiling stage "errstats".  Test option
+ * "errstats_span": the pixels per workgroup of the kernel (0, default: by the grid),
+ * rounded up to 1024 and clamped to 2^24, so that a small image spans several
+ * workgroups; the results do not depend on it, bit for bit. */
+int hq_error_stats(hq_ctx *ctx, int P, int nbins, float top, int64_t *hist, int64_t *nonfinite,
+                   float *max_de, int64_t *max_pixel);
+
 /* ---- the cost's palette gradient and a descent polish: libhq's additions ----
  * The moves above lower something else than the cost: k-means the RGB distortion,
  * the repair move the penalty.  With the index images held fixed the cost is a
@@ -1284,7 +1330,7 @@ int hq_profile_enable(hq_ctx *ctx, int on);
  * tiled form's one, in the place of "grid" and "assign": the time from the first one's start to
  * the last one's end, counted as one launch per call), "coords" (option "assign_space" 1: the
  * kernel that makes the pixels' argmin coordinates, once per image and illuminant, in front of
- * the evaluation that first needs them); returns total ms and launch
+ * the evaluation that first needs them), "errstats" (hq_error_stats' kernel); returns total ms and launch
  * count (HIP events on the context stream). */
 int hq_profile_get(hq_ctx *ctx, const char *kernel, double *total_ms, int64_t *launches);
 int hq_profile_reset(hq_ctx *ctx);
