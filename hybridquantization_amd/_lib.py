@@ -79,7 +79,7 @@ PATH_NAMES = {
     "pixels": ("none", "u8", "planar"),
     "grid": ("none", "build_grid", "lists16"),
     "argmin": ("none", "assign_pipe", "assign_pipe_ordered", "assign16", "assign_wide", "dither", "diffuse",
-               "dot"),
+               "dot", "pattern"),
     "cost": ("none", "cost16w", "cost_mfma", "tiled_generic", "pixel_generic"),
     "cost_instance": ("plain", "masked", "weighted"),
     "gen_h": ("none", "gen_hpass", "gen_hrow", "gen_hrow4", "gen_hmfma"),
@@ -155,6 +155,8 @@ SIGNATURES = {
     "hq_set_dither_map": (C.c_int, [_ctx, _f, C.c_int, C.c_int]),
     "hq_ordered_population": (C.c_int, [_ctx, _f, C.c_int, C.c_int, _f, C.c_float, _d, _i32]),
     "hq_ordered_population_partial": (C.c_int, [_ctx, _f, C.c_int, C.c_int, _f, _d]),
+    "hq_pattern_population": (C.c_int, [_ctx, _f, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _d, _i32]),
+    "hq_pattern_population_partial": (C.c_int, [_ctx, _f, C.c_int, C.c_int, C.c_int, C.c_float, _d]),
     "hq_set_mask": (C.c_int, [_ctx, _u8, C.c_int, C.c_int]),
     "hq_mask_info": (C.c_int, [_ctx, _i64, _i64, _i64, _i64]),
     "hq_set_weights": (C.c_int, [_ctx, _u8, C.c_int, C.c_int]),

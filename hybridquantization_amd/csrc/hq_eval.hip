@@ -9,6 +9,7 @@
 #include "hq_dot.h"
 #include "hq_errstats.h"
 #include "hq_grad.h"
+#include "hq_pattern.h"
 #include "hq_runtime.h"
 
 using namespace hq;
@@ -591,6 +592,22 @@ hipError_t argmin_dot(hq_ctx* c, const Dot& d, const AssignArgs& aa, const GridA
     return e;
 }
 
+// (the map and the palettes' luminance orders are on the device and K <= 256: enqueue_argmin has looked)
+hipError_t argmin_pattern(hq_ctx* c, const Pattern& pt, const AssignArgs& aa, const GridArgs& ga, int K, int Pl, int Ps,
+                          ProfRec& pr, AssignTag* at) {
+    const int mw = c->dmap.empty() ? 16 : c->dmap_w, mh = c->dmap.empty() ? 16 : c->dmap_h;
+    PatternArgs pa{};
+    pa.R = aa.R, pa.G = aa.G, pa.B = aa.B, pa.rgbx = aa.rgbx;
+    pa.pal = ga.pal, pa.tab = c->d_pattab.as<uint8_t>(), pa.map = c->d_dmap.as<float>();
+    pa.mw_mask = (uint32_t)mw - 1u, pa.mh_mask = (uint32_t)mh - 1u;
+    while ((1u << pa.lg_mw) < (uint32_t)mw) ++pa.lg_mw;
+    pa.idx = aa.idx, pa.used_glob = ga.used_glob, pa.used_stride = used_stride(Ps);
+    pa.n_ext = c->g.n_ext, pa.idx_pitch = c->g.idx_pitch;
+    pa.W = (uint32_t)c->g.W, pa.y0 = (uint32_t)c->g.e0;
+    pa.K = K, pa.n = pt.n, pa.strength = pt.strength;
+    return timed_launch(pr, kPPattern, [&] { return launch_pattern(pa, Pl, c->stream, at); });
+}
+
 // The index images of `pass`: its rendering's function, then what the launch reported.
 int enqueue_argmin(hq_ctx* c, const Pass& pass, const GridArgs& ga, bool n16, int K, int Pl, int Ps, ProfRec& pr,
                    hq_path_info& pi) {
@@ -603,6 +620,12 @@ int enqueue_argmin(hq_ctx* c, const Pass& pass, const GridArgs& ga, bool n16, in
     if (o) launched = argmin_ordered(c, *o, aa, Ps, pair, pr, &at);
     else if (const Diffused* d = pass.as<Diffused>()) launched = argmin_diffused(c, *d, aa, ga, K, Pl, pr, &at, pi);
     else if (const Dot* d = pass.as<Dot>()) launched = argmin_dot(c, *d, aa, ga, K, Pl, Ps, pr, &at);
+    else if (const Pattern* pt = pass.as<Pattern>()) {
+        if (c->nch_cur > 1 || c->assign_space != 0 || !c->d_dmap.p ||
+            c->d_pattab.bytes < (size_t)Pl * 2 * kPatternMaxK)
+            return fail(c, HQ_ERR_STATE, "pattern pass: K > 256, option assign_space 1, no map or no luminance orders");
+        launched = argmin_pattern(c, *pt, aa, ga, K, Pl, Ps, pr, &at);
+    }
     else launched = argmin_plain(c, aa, n16, K, Pl, Ps, pair, pr, &at);
     HIP_TRY(c, launched);
     pi.idx_bytes = aa.idx16 ? 2 : 1;
@@ -698,7 +721,7 @@ int hq::enqueue_core(hq_ctx* c, int P, int K, ProfRec& pr, const Pass& pass) {
     hq_path_info pi{};
     pi.pass = pass.gridless() ? HQ_PASS_DITHER : costed ? HQ_PASS_FULL : HQ_PASS_ASSIGN_ONLY;
     pi.ordered = pass.as<Ordered>() != nullptr, pi.P = Pl, pi.K = K, pi.nch = nch;
-    if (int rc = enqueue_grid(c, ga, c->G2 > 0 && !pass.gridless(), n16, K, Pl, Ps, Pair(p0), pr, pi)) return rc;
+    if (int rc = enqueue_grid(c, ga, c->G2 > 0 && pass.builds_grid(), n16, K, Pl, Ps, Pair(p0), pr, pi)) return rc;
     const uint32_t why = cost_slow_why(c);  // (cost_fast)
     const bool fast = why == 0;
     const FastGrid f = fast_grid(c);
@@ -1274,6 +1297,7 @@ struct RenderCall {
     bool partial, ordered;
     const float* amp;
     float strength;
+    int pattern_n = 0;  // hq_pattern_population[_partial]: the ordered family's checks with (n, strength) for amp
 };
 
 // Every check of a rendered evaluation on the call and the context; a refused call has touched
@@ -1288,8 +1312,10 @@ int check_rendered(hq_ctx* c, const RenderCall& r, Scope&& scope) {
         return fail(c, HQ_ERR_ARG, "bad palettes / %s / P=%d / K=%d", r.ordered ? "output" : r.partial ? "partial" : "costs",
                     r.P, r.K);
     int rc = HQ_OK;
-    if (r.ordered && (rc = check_ordered_amp(c, r.amp))) return rc;
-    if (!r.ordered && !(r.strength >= 0.0f && r.strength <= 1.0f))
+    if (r.ordered && !r.pattern_n && (rc = check_ordered_amp(c, r.amp))) return rc;
+    if (r.pattern_n && !pattern_n_valid(r.pattern_n))
+        return fail(c, HQ_ERR_ARG, "n=%d: the list length is 1, 2, 4, 8, 16, 32 or 64", r.pattern_n);
+    if ((!r.ordered || r.pattern_n) && !(r.strength >= 0.0f && r.strength <= 1.0f))
         return fail(c, HQ_ERR_ARG, "strength %g not in [0, 1]", r.strength);
     if (!c->have_image) return fail(c, HQ_ERR_STATE, "no image set (hq_set_image)");
     if (int rc0 = assign_space_excludes(c, r.ordered ? "ordered dithering" : "error diffusion")) return rc0;
@@ -1326,6 +1352,30 @@ int ordered_into_hout(hq_ctx* c, const RenderCall& r) {
     });
     if (rc || (rc = ensure_dither_map(c))) return rc;
     return run_pass(c, r.palettes, r.P, r.K, Pass{Pass::Full, Ordered{{r.amp[0], r.amp[1], r.amp[2]}}});
+}
+
+// hq_pattern_population[_partial] into h_out: the ordered call's checks and scope, the palettes' luminance
+// orders made on the host and copied in front of the pass (on its stream), then the pass.
+int pattern_into_hout(hq_ctx* c, const float* palettes, const void* out, int P, int K, int n, float strength,
+                      bool partial) {
+    if (!c) return HQ_ERR_ARG;
+    // (RenderCall keeps pattern_n 0 for the ordered call itself: n = 0 goes in as another bad length)
+    const RenderCall r{palettes, out, P, K, partial, true, nullptr, strength, n ? n : -1};
+    int rc = check_rendered(c, r, [&] {
+        if (r.partial || whole_image(c) || (c->comm && c->nranks > 1)) return (int)HQ_OK;
+        return fail(c, HQ_ERR_STATE, "sharded context without a communicator: use hq_pattern_population_partial");
+    });
+    if (rc || (rc = ensure_dither_map(c))) return rc;
+    const size_t bytes = (size_t)P * 2 * kPatternMaxK;
+    HIP_TRY(c, c->h_pattab.ensure(bytes));
+    HIP_TRY(c, c->d_pattab.ensure(bytes));
+    uint8_t* tab = c->h_pattab.as<uint8_t>();
+    for (int p = 0; p < P; ++p)
+        if (!pattern_tables(palettes + (size_t)4 * K * p, K, tab + (size_t)p * 2 * kPatternMaxK,
+                            tab + (size_t)p * 2 * kPatternMaxK + kPatternMaxK))
+            return fail(c, HQ_ERR_ARG, "palette %d: no luminance order", p);
+    HIP_TRY(c, hipMemcpyAsync(c->d_pattab.p, tab, bytes, hipMemcpyHostToDevice, c->stream));
+    return run_pass(c, r.palettes, r.P, r.K, Pass{Pattern{n, strength}});
 }
 
 // The tables of class matrix m on the device: the buffer once, its contents when m differs from
@@ -1643,6 +1693,18 @@ int hq_ordered_population(hq_ctx* c, const float* palettes, int P, int K, const 
 int hq_ordered_population_partial(hq_ctx* c, const float* palettes, int P, int K, const float amp[3],
                                   double* partial) {
     const int rc = ordered_into_hout(c, RenderCall{palettes, partial, P, K, true, true, amp, 0.f});
+    return rc ? rc : partial_from_hout(c, P, K, partial);
+}
+
+int hq_pattern_population(hq_ctx* c, const float* palettes, int P, int K, int n, float strength, float delta,
+                          double* costs, int32_t* used) {
+    const int rc = pattern_into_hout(c, palettes, costs, P, K, n, strength, false);
+    return rc ? rc : costs_from_hout(c, P, K, delta, costs, used);
+}
+
+int hq_pattern_population_partial(hq_ctx* c, const float* palettes, int P, int K, int n, float strength,
+                                  double* partial) {
+    const int rc = pattern_into_hout(c, palettes, partial, P, K, n, strength, true);
     return rc ? rc : partial_from_hout(c, P, K, partial);
 }
 

@@ -115,12 +115,12 @@ struct ProfSlot {
 enum Stage {
     kStGrid, kStAssign, kStCost, kStFinalize, kStSaStep, kStComm, kStCentroid, kStLloyd, kStHist, kStErrsum,
     kStReseed, kStDither, kStReduce, kStDot, kStCoords, kStGradPixel, kStGradAdjoint, kStDescend, kStKmppUpdate,
-    kStKmppPick, kStErrstats, kStages
+    kStKmppPick, kStErrstats, kStPattern, kStages
 };
 inline constexpr const char* kStageNames[kStages] = {"grid", "assign", "cost", "finalize", "sa_step", "comm",
                                                      "centroid", "lloyd", "hist", "errsum", "reseed", "dither",
                                                      "reduce", "dot", "coords", "grad_pixel", "grad_adjoint",
-                                                     "descend", "kmpp_update", "kmpp_pick", "errstats"};
+                                                     "descend", "kmpp_update", "kmpp_pick", "errstats", "pattern"};
 
 // The start/stop event pairs of one evaluation (the context's EventSet) or of one
 // search iteration (kPairs pairs per iteration of a run in hq_search::pev).  A pass
@@ -145,6 +145,7 @@ enum Pair {
     kPDescend,                             // may be hybrid too), the update kernel (hq_search_set_descend, hq_descend_move)
     kPKmppUpdate, kPKmppPick,              // hq_kmeanspp_seed: one round's update launches and its pick
     kPErrstats,                            // hq_error_stats' kernel
+    kPPattern,                             // pattern_kernel in the place of grid + assign
     kPairs
 };
 // The stage each pair's time and launch count go to.
@@ -152,7 +153,7 @@ inline constexpr Stage kPairStage[kPairs] = {kStGrid, kStAssign, kStCost, kStFin
                                              kStDither, kStGrid, kStAssign, kStCentroid, kStLloyd, kStGrid,
                                              kStAssign, kStCost, kStErrsum, kStReseed, kStHist, kStReduce,
                                              kStDot, kStCoords, kStGradPixel, kStGradAdjoint, kStGrid, kStAssign,
-                                             kStDescend, kStKmppUpdate, kStKmppPick, kStErrstats};
+                                             kStDescend, kStKmppUpdate, kStKmppPick, kStErrstats, kStPattern};
 
 // One evaluation's or iteration's events and which pairs it recorded (events of an
 // earlier call may sit in the other slots, so only recorded pairs are accumulated).
@@ -188,11 +189,16 @@ inline hipError_t timed_launch(ProfRec& pr, Pair p, F&& launch, bool start = tru
 //     its tables on the device: ensure_dot_tables); on a row-block shard its windowed instance over rows
 //     [a0, a1), the extended rows and what of the apron the matrix's reach needs (dot_window).  On a whole
 //     image dot_tile_kernel's one launch in their place where dot_tiled (hq_eval.hip) says so (option "dot_tile").
+//   Pattern: zeroed the same way, then pattern_kernel's one launch (hq_pattern.hip) in the place of grid +
+//     assign, with the context's threshold map and the palettes' luminance orders (c->d_pattab, made by the
+//     entry point).  Every pixel is independent, so a row-block shard is served as a whole image is: the pass
+//     reports what an ordered one reports (HQ_PASS_FULL), without a grid.  K <= 256.
 struct Plain {};
 struct Ordered { float amp[3]; };
 struct Diffused { float strength; hq_diffusion_taps taps; int rows, slope; bool floyd_steinberg; };
 struct Dot { float strength; int a0, a1; };
-using Rendering = std::variant<Plain, Ordered, Diffused, Dot>;
+struct Pattern { int n; float strength; };
+using Rendering = std::variant<Plain, Ordered, Diffused, Dot, Pattern>;
 
 // The kind, how far the pass goes.  Full: grid, assign, cost, finalize into d_out, the collective on d_out.
 // Fold: a folding search's evaluation -- no finalize (the accept step reads the
@@ -222,10 +228,12 @@ struct Pass {
     Pass(const Diffused& d) : kind(Full), rendering(d) {}
     Pass(const Dot& d) : kind(Full), rendering(d) {}
     Pass(bool fold, const Dot& d) : kind(fold ? Fold : Full), rendering(d) {}
+    Pass(const Pattern& p) : kind(Full), rendering(p) {}
     template <typename R>
     const R* as() const { return std::get_if<R>(&rendering); }     // the alternative's parameters, or null
     bool rendered() const { return !as<Plain>(); }                 // the getters answer for a rendering
     bool gridless() const { return as<Diffused>() || as<Dot>(); }  // no grid is built: HQ_PASS_DITHER
+    bool builds_grid() const { return !gridless() && !as<Pattern>(); }  // (a pattern pass: none either, HQ_PASS_FULL)
     bool side() const { return kind == AssignOnly || kind == CostOnly; }
     Pair pairs() const {
         return first != kPairs ? first : kind == AssignOnly ? kPLloydGrid : kind == CostOnly ? kPRepGrid : kPGrid;
@@ -359,6 +367,10 @@ struct hq_ctx {
     int dmap_w = 0, dmap_h = 0;
     hq::DevBuf d_dmap;
     bool dmap_dirty = true;
+    // pattern dithering (hq_pattern_population): the palettes' luminance orders, [P][2][256] bytes
+    // (pattern_tables), made on the host by the entry point and copied in front of its pass
+    hq::PinBuf h_pattab;
+    hq::DevBuf d_pattab;
     // fixed palette colours (hq_set_fixed_colors; a property of the context like the map, kept by
     // hq_set_image*): [fixed_n][4], .w = 0.  A search latches them at creation; the polishes read
     // fixed_n when called

@@ -618,6 +618,39 @@ class ImageManipulation:
         return self._quantizeRendered(
             colors, lambda pal: self.orderedPopulation(pal, amp, 0.0, return_used=True), "orderedError")
 
+    # pattern dithering: libhq's addition (hq_pattern_population, no reference counterpart)
+    PATTERN_LENGTHS = (1, 2, 4, 8, 16, 32, 64)
+
+    @classmethod
+    def _patternArgs(cls, n, strength):
+        if isinstance(n, bool) or int(n) != n or int(n) not in cls.PATTERN_LENGTHS:
+            raise ValueError(f"pattern n={n!r}: one of {', '.join(map(str, cls.PATTERN_LENGTHS))}")
+        if not 0.0 <= float(strength) <= 1.0:
+            raise ValueError(f"patternStrength={strength!r}: a strength in [0, 1]")
+        return int(n), float(strength)
+
+    def patternPopulation(self, colors, n: int = 16, strength: float = 1.0, delta: float = 2.0, return_used=False):
+        """computeQuantizationErrorPopulation of the pattern-dither rendering (Knoll's): every pixel
+        builds a list of ``n`` palette colours (1, 2, 4 .. 64) whose mean approximates it, by error
+        feedback at ``strength`` in [0, 1] on that pixel alone, and the context's threshold map
+        (setDitherMap) picks the entry of the list sorted by luminance.  colors (P, 4K), K <= 256 ->
+        costs (P,) [, used (P, K)]; n = 1 or strength 0 is the plain evaluation, bit for bit.
+        getIndices and getPixelErrors then answer for this rendering; clusterSums and clusterErrors
+        need a plain evaluation again."""
+        return self._populationCall(self._lib.hq_pattern_population, colors, (int(n), float(strength)), delta,
+                                    return_used)
+
+    def patternPopulationPartial(self, colors, n: int = 16, strength: float = 1.0):
+        """hq_pattern_population_partial: the shard-local (P, 1 + K) partial rows."""
+        return self._populationCall(self._lib.hq_pattern_population_partial, colors, (int(n), float(strength)))
+
+    def quantizePattern(self, colors, n: int = 16, strength: float = 1.0):
+        """The pattern-dither rendering of the context's image with the palette colors float[4K],
+        in ``quantize``'s output format (quantizeDithered's way).  Sets ``lastUsedColors`` and
+        ``patternError``, the rendering's mean dE."""
+        return self._quantizeRendered(
+            colors, lambda pal: self.patternPopulation(pal, n, strength, 0.0, return_used=True), "patternError")
+
     # a pixel mask on the cost: libhq's addition (hq_set_mask, no reference counterpart)
     def setMask(self, mask=None):
         """hq_set_mask: restrict what every cost, clusterSums and colorHistogram measure to
@@ -847,7 +880,8 @@ class ImageManipulation:
                              init=None, initBits=5, repairEvery=0, repairMoves=-1, repairSteps=0,
                              dither=0.0, ditherSearch=False, ordered=None, orderedSearch=False, mask=None,
                              weights=None, fixed=None, ditherKernel=None, dot=0.0, dotSearch=False,
-                             dotClasses=None, assignSpace=None, descendSteps=0, descendRate=None, descendEvery=0):
+                             dotClasses=None, assignSpace=None, descendSteps=0, descendRate=None, descendEvery=0,
+                             pattern=None, patternStrength=1.0):
         """Full SWASA search (IM:383-591) on the GPU; returns bestColors float[4K].
 
         ``simulatedAnnealing`` is a :class:`~hybridquantization_amd.swasa.SWASA`;
@@ -937,6 +971,10 @@ class ImageManipulation:
         the search optimises the dot-diffused cost instead, host-driven through
         hq_swasa_search_host_fixed exactly as ``ditherSearch`` is, with the same exclusions of
         the k-means and repair moves; ``bestError`` and ``bestErrorDot`` are then both that cost.
+        ``pattern`` (hq_pattern_population: the list length n, one of 1, 2, 4 .. 64; not together with
+        ``dither``, ``ordered`` or ``dot``) with ``patternStrength`` in [0, 1]: once the search and its
+        polishes are done the best palette is also evaluated in its pattern-dither rendering,
+        ``bestErrorPattern``; ``bestError`` stays the plain one.  There is no search under that cost.
         ``assignSpace`` (option "assign_space"): None leaves the context's option as the caller
         set it (0, sRGB, on a new context), and no option call is made; "rgb" is the reference's
         nearest colour in sRGB; "lab" assigns every pixel the palette colour nearest in CIELAB under ``illuminant``, in the
@@ -947,7 +985,7 @@ class ImageManipulation:
         """
         space = None if assignSpace is None else self.checkAssignSpace(
             assignSpace, dither=dither, ditherSearch=ditherSearch, ordered=ordered, orderedSearch=orderedSearch,
-            dot=dot, dotSearch=dotSearch)
+            dot=dot, dotSearch=dotSearch, pattern=pattern)
         self._require()
         fx = None if fixed is None else np.ascontiguousarray(fixed_colors(fixed, int(nbOfColors)))
         sw, K = simulatedAnnealing, int(nbOfColors)
@@ -998,6 +1036,10 @@ class ImageManipulation:
             if dotSearch:
                 host_search_ok("dotSearch", "dot", dot)
             dot_device = isinstance(dotSearch, str)  # hq_search_set_dot; True: the Python host loop
+            if pattern is not None:
+                pattern, patternStrength = self._patternArgs(pattern, patternStrength)
+                if dither > 0.0 or dot > 0.0 or amp is not None:
+                    raise ValueError("pattern with dither, ordered or dot: one rendering")
             # the renderings asked for, in the order their final errors are reported, and the one the
             # search itself optimises (None: the plain cost)
             rendered = [_Rendering(*r) for on, *r in (
@@ -1006,7 +1048,10 @@ class ImageManipulation:
                 (dot > 0.0, "dot", self.dotPopulation, dot, dict(classes=dotClasses), "bestErrorDot",
                  "Final error, dot-diffused at strength %g : %.5f"),
                 (amp is not None, "ordered", self.orderedPopulation, amp, {}, "bestErrorOrdered",
-                 "Final error, ordered dither at amplitude %s : %.5f")) if on]
+                 "Final error, ordered dither at amplitude %s : %.5f"),
+                (pattern is not None, "pattern",
+                 lambda pals, n, delta: self.patternPopulation(pals, n, patternStrength, delta), pattern, {},
+                 "bestErrorPattern", "Final error, pattern dither with lists of %s : %.5f")) if on]
             goal = "dot" if dotSearch else "dither" if ditherSearch else "ordered" if orderedSearch else None
             searched = next((r for r in rendered if r.name == goal), None)
             if not self.openCLFiltersReady:

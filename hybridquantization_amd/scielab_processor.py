@@ -90,7 +90,8 @@ def makeChannels(inline):
 def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
                  whitepoint=Whitepoint.D65, verbose=False, device=0, iterations=None, dither=0.0,
                  ordered=None, mask=None, weights=None, fixed=None, pyramid=None, ditherKernel=None,
-                 dot=0.0, dotClasses=None, dotSearch=False, assignSpace=None, descendEvery=0, init=None):
+                 dot=0.0, dotClasses=None, dotSearch=False, assignSpace=None, descendEvery=0, init=None,
+                 pattern=None, patternStrength=1.0):
     """HQ:93-137 without the GUI: planar float image (3, N) in [0,1] ->
     (quantized planar image (3, N), bestColors float[4K], best error).  ``dither`` > 0
     (libhq's addition): the returned image is the best palette's Floyd-Steinberg rendering
@@ -120,10 +121,18 @@ def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
     ``ordered``, ``dot``, ``dotSearch`` or ``pyramid``, is a ValueError before anything runs.
     ``descendEvery`` (findBestQuantization's, pyramidSearch's: a descent iteration every so many, at
     ImageManipulation's DESCEND_RATE).  ``init`` (findBestQuantization's: None, "mediancut", "kmeans++" or an
-    array; under ``pyramid`` pyramidSearch's, which knows no "kmeans++"): how the search starts."""
+    array; under ``pyramid`` pyramidSearch's, which knows no "kmeans++"): how the search starts.
+    ``pattern`` (a list length, 1, 2, 4 .. 64; not together with ``dither``, ``ordered``, ``dot``, ``pyramid``
+    or "lab") with ``patternStrength`` in [0, 1]: the returned image is the best palette's pattern-dither
+    rendering (ImageManipulation.quantizePattern)."""
     fixed_colors(fixed, int(nbOfColors))
     lab = assignSpace is not None and ImageManipulation.checkAssignSpace(
-        assignSpace, dither=dither, ordered=ordered, dot=dot, dotSearch=dotSearch, pyramid=pyramid) != 0
+        assignSpace, dither=dither, ordered=ordered, dot=dot, dotSearch=dotSearch, pyramid=pyramid,
+        pattern=pattern) != 0
+    if pattern is not None:
+        pattern, patternStrength = ImageManipulation._patternArgs(pattern, patternStrength)
+        if ordered is not None or float(dither) > 0.0 or float(dot) > 0.0 or pyramid is not None:
+            raise ValueError("pattern with dither, ordered, dot or pyramid: one rendering, on the plain search")
     if ordered is not None and float(dither) > 0.0:
         raise ValueError("dither and ordered: one rendering")
     if float(dot) > 0.0 and (ordered is not None or float(dither) > 0.0):
@@ -146,11 +155,13 @@ def quantization(image, w, nbOfColors, swasa, dpi=72, viewingDistance=45.0,
             best = sp.bestColors(inline_rgb, sc_img, w, nbOfColors, swasa, iterations=iterations, dither=dither,
                                  ditherKernel=ditherKernel, ordered=ordered, mask=mask, weights=weights, fixed=fixed,
                                  dot=dot, dotClasses=dotClasses, dotSearch=dotSearch, assignSpace=assignSpace,
-                                 descendEvery=descendEvery, init=init)
+                                 descendEvery=descendEvery, init=init,
+                                 **({} if pattern is None else dict(pattern=pattern, patternStrength=patternStrength)))
         # the returned rendering ("lab" with another rendering or a pyramid was refused above)
         q = (ip.quantizeAssigned(best, assignSpace) if lab else
              ip.quantizeDotDiffused(best, dot, classes=dotClasses) if float(dot) > 0.0 else
              ip.quantizeOrdered(best, ordered) if ordered is not None else
+             ip.quantizePattern(best, pattern, patternStrength) if pattern is not None else
              ip.quantizeDithered(best, dither, kernel=ditherKernel) if float(dither) > 0.0 else
              ip.quantize(inline_rgb, best))
         return np.stack(makeChannels(q)), best, ip.bestError

@@ -787,6 +787,49 @@ int hq_ordered_population(hq_ctx *ctx, const float *palettes, int P, int K, cons
 int hq_ordered_population_partial(hq_ctx *ctx, const float *palettes, int P, int K,
                                   const float amp[3], double *partial);
 
+/* ---- pattern dithering: libhq's addition, no reference counterpart ----
+ * Ordered dithering adds one threshold offset per pixel and knows nothing of the palette.
+ * Pattern dithering (Thomas Knoll's; Yliluoma's write-ups) is the positional dither that does:
+ * for each pixel it builds a list of n palette colours whose mean approximates the pixel, by
+ * error feedback on that pixel alone, sorts the list by luminance, and lets the threshold map
+ * pick the entry.  Every pixel is independent: one launch over the whole GPU, exact on row-block
+ * shards, stable under animation.
+ *
+ * In the argmin's sRGB space, every operation one fp32 operation rounded to nearest and none
+ * contracted into an fma; pix, the position (x, y) in the FULL image and the distance with its
+ * first-minimum rule are hq_ordered_population's.  Per palette, once:
+ *     Y_k = ((0.299f R_k) + (0.587f G_k)) + (0.114f B_k)
+ * the colours ordered by (Y_k, k) ascending, rank[k] the position of colour k in that order.
+ * Per pixel, with list length n and strength:
+ *     e = (0, 0, 0)
+ *     for i = 0 .. n-1:
+ *         v_c = min(max(pix_c + e_c * strength, 0), 1)
+ *         k_i = the first minimum over k of distance(v, pal[k])
+ *         e_c = e_c + (pix_c - pal[k_i]_c)
+ *     s_0 .. s_{n-1} = the k_i sorted by rank, ascending (equal entries stay equal)
+ *     m = map[(y mod mh) * mw + (x mod mw)]      the context's threshold map (hq_set_dither_map)
+ *     r = min((int)((m + 0.5f) * (float)n), n - 1)
+ *     idx(x, y) = s_r
+ * At n = 1, and at strength = 0 for any n, the indices, used flags and costs are
+ * hq_eval_population's, bit for bit.
+ *
+ * hq_pattern_population[_partial] behave as hq_ordered_population[_partial] do in everything not
+ * named here: the outputs, the read-back getters answering for this rendering, hq_cluster_sums
+ * and hq_cluster_errors returning HQ_ERR_STATE afterwards, row-block shards (y is the full-image
+ * row, so a shard's rows are the whole image's bit for bit), the communicator, mask and weights
+ * (through the unchanged cost path), the refusals with their statuses and order, and a refused
+ * call touching nothing.  Added: n must be one of 1, 2, 4, 8, 16, 32, 64 and strength finite and
+ * in [0, 1], else HQ_ERR_ARG (checked where the ordered call checks amp); K > 256 is
+ * HQ_ERR_UNSUPPORTED.  hq_last_path reports HQ_PASS_FULL with grid HQ_GRID_NONE (no candidate grid
+ * is built: the argmins are exhaustive), ordered 0 and argmin HQ_ARGMIN_PATTERN; the profile counts
+ * one "pattern" launch per pass and nothing under "grid" and "assign".
+ * The work is n K distances per pixel.  Not built: K > 256, a search under this cost, pruning the
+ * argmins by the candidate grid, the JNI binding.  Not measured: more than one GPU. */
+int hq_pattern_population(hq_ctx *ctx, const float *palettes, int P, int K, int n, float strength,
+                          float delta, double *costs, int32_t *used);
+int hq_pattern_population_partial(hq_ctx *ctx, const float *palettes, int P, int K, int n,
+                                  float strength, double *partial);
+
 /* ---- a pixel mask on the cost: libhq's addition, no reference counterpart ----
  * Every cost above is a mean over all w * h pixels.  A mask restricts what is
  * measured to a region: one byte per pixel of the FULL image, mask[y*w + x],
@@ -1330,8 +1373,9 @@ int hq_profile_enable(hq_ctx *ctx, int on);
  * tiled form's one, in the place of "grid" and "assign": the time from the first one's start to
  * the last one's end, counted as one launch per call), "coords" (option "assign_space" 1: the
  * kernel that makes the pixels' argmin coordinates, once per image and illuminant, in front of
- * the evaluation that first needs them), "errstats" (hq_error_stats' kernel); returns total ms and launch
- * count (HIP events on the context stream). */
+ * the evaluation that first needs them), "errstats" (hq_error_stats' kernel), "pattern"
+ * (hq_pattern_population's kernel, one launch per pass in the place of "grid" and "assign"); returns
+ * total ms and launch count (HIP events on the context stream). */
 int hq_profile_get(hq_ctx *ctx, const char *kernel, double *total_ms, int64_t *launches);
 int hq_profile_reset(hq_ctx *ctx);
 
@@ -1354,8 +1398,9 @@ enum hq_path_argmin {
     HQ_ARGMIN_NONE = 0, HQ_ARGMIN_ASSIGN_PIPE = 1, HQ_ARGMIN_ASSIGN_PIPE_ORDERED = 2, HQ_ARGMIN_ASSIGN16 = 3,
     HQ_ARGMIN_ASSIGN_WIDE = 4, HQ_ARGMIN_DITHER = 5,
     HQ_ARGMIN_DIFFUSE = 6,   /* hq_diffuse_population's kernels (hq_diffuse.hip) */
-    HQ_ARGMIN_DOT = 7        /* hq_dot_population's kernels: hq_dot.hip, one launch per class, or
+    HQ_ARGMIN_DOT = 7,       /* hq_dot_population's kernels: hq_dot.hip, one launch per class, or
                               * hq_dot_tile.hip, one launch (hq_dot_form says which) */
+    HQ_ARGMIN_PATTERN = 8    /* hq_pattern_population's kernel (hq_pattern.hip) */
 };
 enum hq_path_cost {
     HQ_COST_NONE = 0,        /* an assign-only pass, or a mask without a live tile */
